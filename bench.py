@@ -12,6 +12,12 @@ convert_extra_time 0.5 s at 5 ms frames (/root/reference/config.yaml:14; BASELIN
 N times the windows (weak scaling) with one RCCL broadcast of each weight blob at start-up and no collective in the timed region.
 Prints ONE JSON line on rank 0.
 
+A plain run sets up, primes the ring slots, warms up, times ONE bracket of exactly K steps (`ms_per_step` = its wall time / K) and prints
+the headline.  `--full` adds everything else this script measures: the median of seven brackets, the mixed-stream brackets, graph replays,
+host-path / batch / discard-hint / small-window / split-bf16 figures, the roofline objects and the CPU baseline with its parity check.
+`--dump-outputs DIR` writes the mc and sp blocks of the last timed step as float32 .npy files (seeded inputs and weights: two builds run
+with the same arguments can be compared output for output).
+
 `--force-dist` runs the N > 1 code path (process group, broadcast, barrier, all-reduce of the elapsed time) with ONE rank on one GPU;
 `--comm native` takes RCCL through the C ABI (ry_comm_*) instead of torch.distributed; `--emulator` (tests only) runs the same script on
 the host-side emulator build with gloo -- its numbers mean nothing.
@@ -32,6 +38,7 @@ sys.path.insert(0, str(ROOT))
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md); 6290 measured copy
 F32_MFMA_PEAK_TF = 157.3       # v_mfma_f32_32x32x2_f32 dense peak (= fp32 vector peak)
 SP_FLOOR = 1e-16               # voice_changer.py:39
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs writes at most this much
 
 
 def parse(argv=None):
@@ -39,11 +46,19 @@ def parse(argv=None):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=7,
+    ap.add_argument('--repeats', type=int, default=None,
                     help='the K-step bracket is timed this many times back to back (same K, same fences); `value` comes from the MEDIAN bracket, every '
-                         'bracket is listed in `brackets`')
+                         'bracket is listed in `brackets`.  Default 1 (exactly K timed steps), 7 with --full')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline as well: seven brackets, the mixed-stream brackets, graph replays, host-path / batch / '
+                         'discard / small-window / split-bf16 measurements, the roofline objects and the CPU baseline.  A plain run sets up, '
+                         'warms up, times the K steps and prints the headline')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step returned as DIR/mc.npy (windows, frames, mc dims) and DIR/sp.npy '
+                         '(windows, frames, bins), float32; inputs and weights are seeded, so the same arguments give the same inputs')
     ap.add_argument('--details-out', default=None,
-                    help='file for the long form of the result (per-kernel table, batch / host-path / discard measurements, notes); default '
+                    help='file for the long form of the result (per-kernel table, batch / host-path / discard measurements, notes); a plain run '
+                         'writes it only when this is given; default with --full: '
                          'gpurun_out/bench_details_<N>gpu.json.  The printed line carries the headline, the brackets and the roofline objects only')
     ap.add_argument('--frames', type=int, default=300, help='real frames per window (N)')
     ap.add_argument('--extra-frames', type=int, default=None,
@@ -231,6 +246,8 @@ def self_launch(n, argv):
 
 def main(argv=None):
     args = parse(argv)
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
     if args.dispatcher:
         return dispatcher_bench(args)
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')     # dmabuf IPC for RCCL / device-buffer sharing: before the HIP runtime comes up
@@ -449,19 +466,34 @@ def main(argv=None):
     mc_gpu = numpy.empty((N, d1.out_ch), numpy.float32); ctx.dev_download(d_mc[turn['w0']], mc_gpu)
     x_checked = xs_host[turn['w0_win']]                                                                        # ... which converted this input
     assert numpy.isfinite(sp_gpu).all() and numpy.isfinite(mc_gpu).all() and (sp_gpu > 0).all()
-    # the same K steps over the 'mixed' set (one window in three cut by the silence gate); every rank runs it (the fences hold barriers)
-    turn['set'] = 'mixed'; primed['done'] = False
-    elapsed_mixed = median_of(timed(min(3, args.repeats)))
-    # a gated window of that region for the parity check: run the shortest one once more, synchronously, into a block of its own
-    qm = wsets['mixed'][8 % len(wsets['mixed'])]
-    sync_all(); core.enqueue_device(qm['d_x'], qm['d_rows'], qm['n_eff'], N, d_mc[0], d_sp[0], SP_FLOOR); sync_all()
-    sp_gated = numpy.empty((N, synth.FFT_BINS), numpy.float32); ctx.dev_download(d_sp[0], sp_gated)
-    mc_gated = numpy.empty((N, d1.out_ch), numpy.float32); ctx.dev_download(d_mc[0], mc_gated)
-    assert not mc_gated[~qm['eff']].any() and numpy.isfinite(sp_gated).all()
-    turn['set'] = 'all'; primed['done'] = False
-    for _ in range(n_prime):
-        step()
-    sync_all(); primed['done'] = True
+    if args.dump_outputs and rank == 0:
+        # every window of the last timed step: result block k of window w is where step() put it
+        blocks = [(turn['n'] - Wn + w) % NB for w in range(Wn)]
+        per_window = N * (d1.out_ch + synth.FFT_BINS) * 4
+        if len(blocks) * per_window > DUMP_BYTES:                         # a fixed, seeded sample of the windows
+            keep = numpy.sort(numpy.random.default_rng(0).choice(len(blocks), DUMP_BYTES // per_window, replace=False))
+            blocks = [blocks[i] for i in keep]
+        mc_out = numpy.empty((len(blocks), N, d1.out_ch), numpy.float32)
+        sp_out = numpy.empty((len(blocks), N, synth.FFT_BINS), numpy.float32)
+        for i, k in enumerate(blocks):
+            ctx.dev_download(d_mc[k], mc_out[i]); ctx.dev_download(d_sp[k], sp_out[i])
+        Path(args.dump_outputs).mkdir(parents=True, exist_ok=True)
+        numpy.save(str(Path(args.dump_outputs) / 'mc.npy'), mc_out)
+        numpy.save(str(Path(args.dump_outputs) / 'sp.npy'), sp_out)
+    if args.full:
+        # the same K steps over the 'mixed' set (one window in three cut by the silence gate); every rank runs it (the fences hold barriers)
+        turn['set'] = 'mixed'; primed['done'] = False
+        elapsed_mixed = median_of(timed(min(3, args.repeats)))
+        # a gated window of that region for the parity check: run the shortest one once more, synchronously, into a block of its own
+        qm = wsets['mixed'][8 % len(wsets['mixed'])]
+        sync_all(); core.enqueue_device(qm['d_x'], qm['d_rows'], qm['n_eff'], N, d_mc[0], d_sp[0], SP_FLOOR); sync_all()
+        sp_gated = numpy.empty((N, synth.FFT_BINS), numpy.float32); ctx.dev_download(d_sp[0], sp_gated)
+        mc_gated = numpy.empty((N, d1.out_ch), numpy.float32); ctx.dev_download(d_mc[0], mc_gated)
+        assert not mc_gated[~qm['eff']].any() and numpy.isfinite(sp_gated).all()
+        turn['set'] = 'all'; primed['done'] = False
+        for _ in range(n_prime):
+            step()
+        sync_all(); primed['done'] = True
 
     frames_total = world * Wn * N * args.steps
     value = frames_total / elapsed
@@ -475,7 +507,7 @@ def main(argv=None):
         # `value` / `ms_per_step` come from the MEDIAN of `repeats` brackets of exactly K steps each (same fences); every bracket is listed:
         # wall ms (max over the ranks), ms the host needed to enqueue the K steps, ms between HIP events on rank 0
         'device_ms_per_step_rank0': round(dev_ms / args.steps, 4),
-        'repeats': len(brs), 'value_from': 'median bracket',
+        'repeats': len(brs), 'value_from': 'median bracket' if len(brs) > 1 else 'single bracket',
         'brackets': [{'wall_ms': round(b[0] * 1e3, 3), 'enq_ms': round(b[1] * 1e3, 3), 'dev_ms': round(b[2], 3)} for b in brs],
         'spread': round((max(b[0] for b in brs) - min(b[0] for b in brs)) / elapsed, 4),
         'slow_brackets': [i for i, b in enumerate(brs) if b[0] > 1.2 * elapsed],
@@ -488,12 +520,6 @@ def main(argv=None):
                                      % (2 * extra, N, (N - 2 * extra) * 0.005, ms_window),
         'step': 'chained device-resident core (ry_vc_enqueue_device): stage-1 -> combine_silent -> mc2sp + 1e-16 -> stage-2, two windows in flight; '
                 '%d distinct windows take turns, every frame effective' % NW,
-        'mixed_stream': {'value': round(frames_total / elapsed_mixed, 1), 'unit': 'frames/s', 'ms_per_step': round(elapsed_mixed / args.steps * 1e3, 4),
-                         'steps': args.steps, 'effective_frames_of_the_gated_windows': [int(q['n_eff']) for q in wsets['mixed'] if q['n_eff'] < N],
-                         'note': 'the same K steps, the same bracket, over the same %d windows with one in three cut by the silence gate (a silent '
-                                 'stretch in the middle): stage 1 converts only the effective frames -- another padded length and launch plan, frame '
-                                 'counts that change from window to window on every ring slot -- and combine_silent scatters them back; `value` still '
-                                 'counts every frame handed to convert' % NW},
         'comm': None if comm is None else comm.kind, 'comm_ranks': None if comm is None else comm.ranks_seen,
         'config': {'workload': 'BASELINE config #3: stage-1 + stage-2 SR forward, buffer_time 0.5 s + 2x0.5 s convert_extra_time '
                                '@16 kHz / 5 ms -> %d real frames (%d padded) per window, %d window(s) per GPU per step, %s random-init weights'
@@ -502,6 +528,13 @@ def main(argv=None):
                    'lanes_per_gpu': core.lanes,
                    'parallelism': 'chunk-dp%d (independent windows, RCCL weight broadcast at init, no steady-state collective); %d window lane(s) per GPU' % (world, core.lanes)},
     }
+    if args.full:
+        out['mixed_stream'] = {'value': round(frames_total / elapsed_mixed, 1), 'unit': 'frames/s', 'ms_per_step': round(elapsed_mixed / args.steps * 1e3, 4),
+                               'steps': args.steps, 'effective_frames_of_the_gated_windows': [int(q['n_eff']) for q in wsets['mixed'] if q['n_eff'] < N],
+                               'note': 'the same K steps, the same bracket, over the same %d windows with one in three cut by the silence gate (a silent '
+                                       'stretch in the middle): stage 1 converts only the effective frames -- another padded length and launch plan, frame '
+                                       'counts that change from window to window on every ring slot -- and combine_silent scatters them back; `value` still '
+                                       'counts every frame handed to convert' % NW}
 
     def convert_now(widx):
         """Window `widx` of the all-effective set through the current settings, synchronously, into result block 0: (mc, sp) on the host."""
@@ -519,7 +552,7 @@ def main(argv=None):
             fn()
         return ctx.timer_stop() / reps
 
-    if rank == 0 and not emu:
+    if rank == 0 and not emu and args.full:
         d_y1 = ctx.dev_alloc(N * d1.out_ch); d_s2in = ctx.dev_alloc(N * synth.FFT_BINS); d_s2out = ctx.dev_alloc(N * synth.FFT_BINS)
         ctx.dev_upload(d_s2in, synth.stage2_input(N)[0])
         s1_ms = time_only(lambda: net1.convert_device(d_x[0], d_y1, 1, N))
@@ -831,9 +864,12 @@ def main(argv=None):
             out['mixed_stream']['gpu_result_of_a_gated_window_vs_cpu_restatement'] = out['cpu_baseline'].pop('gated_window')
     if rank == 0:
         details = args.details_out or str(ROOT / 'gpurun_out' / ('bench_details_%dgpu.json' % world))
+        if not (args.full or args.details_out):
+            details = None                      # a plain run writes no long form unless asked for one
         try:
-            Path(details).parent.mkdir(parents=True, exist_ok=True)
-            Path(details).write_text(json.dumps(out, indent=1))
+            if details is not None:
+                Path(details).parent.mkdir(parents=True, exist_ok=True)
+                Path(details).write_text(json.dumps(out, indent=1))
         except OSError as e:
             details = 'not written (%s)' % e
         print(json.dumps(compact_line(out, details)), flush=True)

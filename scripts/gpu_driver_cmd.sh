@@ -6,7 +6,7 @@
 cd "$GRAFT_REPO_ROOT"; N=${1:-12}; RND=${2:-r06}; export O=gpurun_out/${RND}_driver_cmd; mkdir -p $O
 for i in $(seq 1 $N); do
   X=""; [ $i -gt 3 ] && X="--no-extras --no-cpu-baseline"
-  BENCH_DEBUG_FENCE=1 timeout 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 $X --details-out $O/details_$i.json > $O/run_$i.json 2> $O/run_$i.err
+  BENCH_DEBUG_FENCE=1 timeout 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 $X --details-out $O/details_$i.json > $O/run_$i.json 2> $O/run_$i.err
   echo "run $i exit $?"
 done
 python3 - <<'PY' > $O/summary.txt
@@ -21,7 +21,7 @@ for f in sorted(glob.glob(O + '/run_*.json'), key=lambda s: int(re.findall(r'run
     b = d['brackets']
     rows.append((f.split('/')[-1], d['value'], d['ms_per_step'], d['spread'], [round(x['wall_ms'] / d['steps'], 4) for x in b],
                  [round(x['enq_ms'] / d['steps'], 4) for x in b], [round(x['dev_ms'] / d['steps'], 4) for x in b]))
-print('# python3 bench.py --gpus 1 --steps 20 --warmup 5 in fresh processes (runs 1-3 exact, the others with --no-extras --no-cpu-baseline)')
+print('# python3 bench.py --full --gpus 1 --steps 20 --warmup 5 in fresh processes (runs 1-3 exact, the others with --no-extras --no-cpu-baseline)')
 print('# per run: value (median bracket), ms/step, spread, then per bracket: wall ms/step | enqueue ms/step | device-event ms/step')
 for r in rows:
     print('%-12s value %9.1f  ms/step %.4f  spread %.4f' % r[:4]); print('    wall', r[4]); print('    enq ', r[5]); print('    dev ', r[6])

@@ -14,12 +14,15 @@ from pathlib import Path
 import numpy
 import pytest
 
+import reference_checkout
+
 import test_shims_e2e as e2e
 from realtime_yukarin_amd import compat, dispatch, engine
 
 compat.install()
 ROOT = Path(__file__).resolve().parent.parent
 REF = Path('/root/reference')
+REF = reference_checkout.locate(REF)
 KEYS = ('f0', 'ap', 'sp', 'voiced', 'mc')
 
 
@@ -226,7 +229,7 @@ def test_weightless_copies_for_the_broadcast_receivers(tmp_path):
         ls._get_net(513)
 
 
-@pytest.mark.skipif(not REF.exists(), reason='/root/reference is not mounted here')
+@pytest.mark.skipif(REF is None, reason=reference_checkout.SKIP_REASON)
 def test_drop_in_worker_over_two_gpus_matches_the_single_gpu_mirror(tmp_path, emu_ctx, monkeypatch):
     """`convert_worker_multi_gpu` (the reference's ConvertStream for add / fetch, two emulator workers) against the single-GPU mirror
     worker on the same items: same windows out, in order."""

@@ -125,3 +125,22 @@ def test_bench_starts_its_own_ranks_when_run_plainly(tmp_path, world):
     assert d['value'] > 0 and d['config']['parallelism'].startswith('chunk-dp%d' % world) and 'metric' in d and len(d['brackets']) >= 1
     # whole-job aggregate: `world` ranks x windows per rank x frames over the max-over-ranks time (value is rounded to 0.1)
     assert abs(d['value'] - world * d['config']['windows_per_gpu'] * 24 / (d['ms_per_step'] * 1e-3)) / d['value'] < 5e-3
+
+
+def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the mc / sp blocks of the last timed step as float32 .npy files; inputs and weights are seeded,
+    so two fresh runs of one build with the same arguments write the same arrays (what lets two builds be compared output for output)."""
+    import subprocess
+    from realtime_yukarin_amd import build
+    build.build_emu()
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+    got = []
+    for i in range(2):
+        d = tmp_path / ('run%d' % i)
+        r = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--emulator', '--frames', '24', '--steps', '2', '--warmup', '1', '--dump-outputs', str(d)],
+                           capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-2000:]
+        got.append({k: numpy.load(str(d / (k + '.npy'))) for k in ('mc', 'sp')})
+    assert got[0]['mc'].shape == (1, 24, 9) and got[0]['sp'].shape == (1, 24, 513) and (got[0]['sp'] > 0).all()
+    for k in ('mc', 'sp'):
+        assert got[0][k].dtype == numpy.float32 and numpy.array_equal(got[0][k], got[1][k]), k

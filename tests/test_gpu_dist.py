@@ -61,7 +61,7 @@ def test_bench_force_dist(comm):
     """bench.py through its `comm is not None` branches on one GPU, at the DRIVER'S step count (--steps 20 --warmup 5): same JSON contract,
     the headline where the plain run has it (round 3's driver line was 130 k frames/s from one unrepeated bracket with a garbage collection
     inside, and this test asked for 50 k at --steps 10: it would not have noticed)."""
-    out = _run(['bench.py', '--force-dist', '--comm', comm, '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-extras'],
+    out = _run(['bench.py', '--full', '--force-dist', '--comm', comm, '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-extras'],
                {'MASTER_PORT': '29613' if comm == 'torch' else '29614', 'RANK': '0', 'LOCAL_RANK': '0', 'WORLD_SIZE': '1'})
     d = json.loads([ln for ln in out.splitlines() if ln.startswith('{')][-1])
     assert d['n_gpus'] == 1 and d['comm'] is not None and d['value'] > 200000 and d['dtype'] == 'f32'
@@ -73,7 +73,7 @@ def test_bench_force_dist(comm):
 def test_bench_at_the_drivers_own_command():
     """`python3 bench.py --gpus 1 --steps 20 --warmup 5` (what the driver runs at round end) in a fresh process: the printed line is short
     enough for an 8 KB tail, carries every bracket, and the brackets agree with each other."""
-    out = _run(['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5', '--no-extras', '--cpu-seconds', '2'])
+    out = _run(['bench.py', '--full', '--gpus', '1', '--steps', '20', '--warmup', '5', '--no-extras', '--cpu-seconds', '2'])
     line = [ln for ln in out.splitlines() if ln.startswith('{')][-1]
     d = json.loads(line)
     assert len(line) < 6144, len(line)
@@ -84,3 +84,16 @@ def test_bench_at_the_drivers_own_command():
         assert d['value'] > 200000 and d['roofline']['frac'] > 0.5
         assert d['slow_brackets'] == [] and walls[-1] < 1.10 * walls[0], d['brackets']
         assert abs(d['device_ms_per_step_rank0'] - d['ms_per_step']) < 0.05 * d['ms_per_step']
+
+
+def test_plain_bench_times_exactly_k_steps_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` is the headline alone: one bracket of exactly K steps and none of the measurements
+    of --full; `--dump-outputs` writes the mc / sp blocks of the last timed step as float32 arrays."""
+    out = _run(['bench.py', '--gpus', '1', '--steps', '30', '--warmup', '5', '--dump-outputs', str(tmp_path / 'dump')])
+    d = json.loads([ln for ln in out.splitlines() if ln.startswith('{')][-1])
+    assert d['steps'] == 30 and d['repeats'] == 1 and len(d['brackets']) == 1 and d['value'] > 0 and d['dtype'] == 'f32'
+    assert abs(d['brackets'][0]['wall_ms'] / 30 - d['ms_per_step']) < 1e-3
+    assert not set(d) & {'mixed_stream', 'roofline', 'cpu_baseline', 'graph_replay_ms', 'host_path', 'split_bf16'}, sorted(d)
+    sp, mc = (numpy.load(str(tmp_path / 'dump' / (k + '.npy'))) for k in ('sp', 'mc'))
+    assert sp.dtype == mc.dtype == numpy.float32 and sp.shape == (1, 300, 513) and mc.shape[:2] == (1, 300)
+    assert numpy.isfinite(sp).all() and (sp > 0).all() and numpy.isfinite(mc).all()

@@ -1,6 +1,6 @@
 """Drop-in check: the reference's own model-free unittest files run UNCHANGED on top of the `yukarin` /
 `become_yukarin` / `chainer` shims (five of the six test files need no trained model).
-Only possible where /root/reference is mounted (this container); skipped on the GPU box."""
+Needs a readable checkout of the reference (tests/reference_checkout.py); skipped where there is none."""
 import os
 import subprocess
 import sys
@@ -8,13 +8,16 @@ from pathlib import Path
 
 import pytest
 
+import reference_checkout
+
 ROOT = Path(__file__).resolve().parent.parent
 REF = Path('/root/reference')
+REF = reference_checkout.locate(REF)
 
 FILES = ['test_segment', 'test_base_stream', 'test_encode_stream', 'test_convert_stream', 'test_feature_wrapper_segment_method']
 
 
-@pytest.mark.skipif(not REF.exists(), reason='/root/reference is not mounted here')
+@pytest.mark.skipif(REF is None, reason=reference_checkout.SKIP_REASON)
 @pytest.mark.parametrize('name', FILES)
 def test_reference_unittest_file_passes_on_shims(name):
     env = dict(os.environ)
@@ -25,7 +28,7 @@ def test_reference_unittest_file_passes_on_shims(name):
     assert 'OK' in r.stdout
 
 
-@pytest.mark.skipif(not REF.exists(), reason='/root/reference is not mounted here')
+@pytest.mark.skipif(REF is None, reason=reference_checkout.SKIP_REASON)
 def test_reference_hot_path_modules_import_on_shims():
     """convert_worker / yukarin_converter / check.py import cleanly (chainer stub, config loaders, F0Converter)."""
     env = dict(os.environ)

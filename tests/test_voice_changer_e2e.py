@@ -12,6 +12,8 @@ from pathlib import Path
 import numpy
 import pytest
 
+import reference_checkout
+
 from oracle import effective_frame as oef
 from oracle import mc2sp as omc
 from oracle import unet
@@ -22,6 +24,7 @@ from realtime_yukarin_amd.weights import save_npz, synthetic_params
 compat.install()
 ROOT = Path(__file__).resolve().parent.parent
 REF = Path('/root/reference')
+REF = reference_checkout.locate(REF)
 FS, FRAME_PERIOD, N = 16000, 5, 60
 
 
@@ -172,7 +175,6 @@ def test_all_silent_window_skips_the_stage1_cnn_through_the_wave_gate(models, on
     assert calls == []                                                        # AcousticConverter.convert never ran
 
 
-@pytest.mark.skipif(not REF.exists(), reason='/root/reference is not mounted here')
 def test_super_resolution_dtype_is_selectable_from_the_environment(models, on_emulator, monkeypatch):
     """RY_SR_DTYPE lets an unchanged run.py / check.py opt into the split-bf16 (or bf16) stage-2 arithmetic; anything else
     is refused before the first convert.  (The base-8 test model has no MFMA-bound layer, so the result is the fp32 one.)"""
@@ -189,6 +191,7 @@ def test_super_resolution_dtype_is_selectable_from_the_environment(models, on_em
         bad.convert(sp)
 
 
+@pytest.mark.skipif(REF is None, reason=reference_checkout.SKIP_REASON)
 def test_reference_voice_changer_and_convert_stream_run_unchanged_on_the_shims(models, on_emulator, monkeypatch):
     for p in (str(ROOT / 'tests' / 'stubs'), str(REF)):
         monkeypatch.syspath_prepend(p)
@@ -209,7 +212,7 @@ def test_reference_voice_changer_and_convert_stream_run_unchanged_on_the_shims(m
         sys.modules.pop(m)
 
 
-@pytest.mark.skipif(not REF.exists(), reason='/root/reference is not mounted here')
+@pytest.mark.skipif(REF is None, reason=reference_checkout.SKIP_REASON)
 def test_unchanged_reference_class_keeps_the_data_on_the_device_between_the_cnns(models, on_emulator, monkeypatch):
     """The reference's OWN VoiceChanger, not edited, calling the shims step by step (voice_changer.py:33-41): `convert` leaves its
     rows on the device, `decode_spectrogram` hands back a lazy spectrogram, `+= 1e-16` / `astype` are remembered and
@@ -280,7 +283,7 @@ def test_unchanged_reference_class_keeps_the_data_on_the_device_between_the_cnns
         sys.modules.pop(m)
 
 
-@pytest.mark.skipif(not REF.exists(), reason='/root/reference is not mounted here')
+@pytest.mark.skipif(REF is None, reason=reference_checkout.SKIP_REASON)
 def test_convert_worker_mirror_matches_the_reference_loop_and_stays_bounded(models, on_emulator, monkeypatch):
     """`realtime_yukarin_amd.worker.convert_worker` over FeatureQueues against the reference's loop body
     (convert_worker.py:33-57) run inline: same windows out, while the mirror's stream no longer grows."""
