@@ -248,6 +248,35 @@ int ry_debug_plan_os2(int M, int Cout, int nphases, int units, int* mt4, int* nt
  * then stays on the direct implicit GEMM).  No device work. */
 int ry_debug_plan_wino(int Mh, int Mw, int Cout, int nphases, int npatches, int batch, int* cfg, int* mbw, int* splits);
 
+/* ---- CREPE pitch tracker (`crepe.predict(audio, 16000, viterbi=True, model_capacity=..., step_size=...)`, called by the reference's
+ * CrepeAcousticFeatureWrapper.extract_f0, yukarin_wrapper/acoustic_feature_wrapper.py:65-80).  Semantics: INTEGRATION.md section 9.
+ * `capacity` is the filter multiplier m: tiny 4, small 8, medium 16, large 24, full 32 (any 1 .. 32 is accepted).  Layer filters
+ * [32, 4, 4, 4, 8, 16] x m, widths [512, 64 x 5], conv1 stride 4; conv -> ReLU -> BatchNorm -> max-pool 2; dense 360 + sigmoid.
+ * Weight blob, per conv layer i = 1 .. 6: weight (Cout, Cin, width), bias, BN gamma, beta, running mean, running var (Cout each);
+ * then classifier weight (360, 4 C6) (input index = position * C6 + channel) and bias (360). */
+typedef struct ry_crepe ry_crepe;
+size_t ry_crepe_param_count(int capacity);         /* 0 (and ry_last_error) for a bad capacity */
+int ry_crepe_create(ry_ctx* ctx, int capacity, const float* weights, size_t n_floats, float bn_eps, ry_crepe** out);
+void ry_crepe_destroy(ry_crepe* crepe);
+/* audio16k: float32 samples at 16 kHz.  Frames: 1 + (n_samples + (center ? 1024 : 0) - 1024) / hop, each 1024 samples from
+ * frame * hop - (center ? 512 : 0), mean / std normalised (std clamped at 1e-10).  f0 [frames] (Hz, 0 where the average is undefined),
+ * confidence [frames] (max of the activation), activation [frames][360] (may be null).  viterbi = 1: the 360-state Viterbi path;
+ * 0: the argmax of each frame.  on_device = 1: every pointer is a device pointer, the call only enqueues on the context stream. */
+int ry_crepe_predict(ry_crepe* crepe, const float* audio16k, int n_samples, int hop, int center, int viterbi,
+                     float* f0, float* confidence, float* activation, int on_device);
+/* The decode alone on a host activation [n_frames][360]: f0, confidence and (may be null) the centre bin of every frame -- the Viterbi
+ * path, or with viterbi = 0 the argmax. */
+int ry_crepe_decode(ry_crepe* crepe, const float* activation, int n_frames, int viterbi, float* f0, float* confidence, int* path);
+/* The float64 log tables of the Viterbi pass: logT [360][360] (from, to), logE [360][360] (state, observation), logS [360].
+ * ry_crepe_create builds them with the C library's log; a caller whose decode must match its own restatement bit for bit uploads
+ * that restatement's values (realtime_yukarin_amd/crepe.py uploads numpy's). */
+int ry_crepe_set_viterbi_tables(ry_crepe* crepe, const double* logT, const double* logE, const double* logS);
+/* tests: the buffers of the last pass of ry_crepe_predict (its last <= 256 frames): layer 0 the normalised frames [n][1024],
+ * 1 .. 6 the pooled conv outputs [n][positions][channels], 7 the logits [n][360]. */
+int ry_crepe_debug_layer(ry_crepe* crepe, int layer, float* out);
+/* diagnostics: the split-K count of conv1 .. conv6 and the dense layer (7 ints). */
+int ry_crepe_debug_splits(ry_crepe* crepe, int* splits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,8 @@ ABI_SYMBOLS = (
     'ry_vc_submit_wave', 'ry_vc_wait_wave', 'ry_vc_gate',
     'ry_comm_unique_id', 'ry_comm_init', 'ry_comm_destroy', 'ry_comm_bcast_weights', 'ry_comm_allreduce_max', 'ry_comm_barrier',
     'ry_dev_alloc', 'ry_dev_free', 'ry_dev_upload', 'ry_dev_download',
+    'ry_crepe_param_count', 'ry_crepe_create', 'ry_crepe_destroy', 'ry_crepe_predict', 'ry_crepe_decode', 'ry_crepe_set_viterbi_tables',
+    'ry_crepe_debug_layer', 'ry_crepe_debug_splits',
 )
 
 
@@ -160,6 +162,17 @@ class Ry355Lib(object):
         d.ry_timer_stop.argtypes = [_VP, ctypes.POINTER(ctypes.c_float)]
         d.ry_net_profile.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RyKernelStat),
                                      ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        _DP = ctypes.POINTER(ctypes.c_double)
+        d.ry_crepe_param_count.argtypes = [ctypes.c_int]
+        d.ry_crepe_param_count.restype = ctypes.c_size_t
+        d.ry_crepe_create.argtypes = [_VP, ctypes.c_int, _FP, ctypes.c_size_t, ctypes.c_float, ctypes.POINTER(_VP)]
+        d.ry_crepe_destroy.argtypes = [_VP]
+        d.ry_crepe_destroy.restype = None
+        d.ry_crepe_predict.argtypes = [_VP, _FP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _FP, _FP, _FP, ctypes.c_int]
+        d.ry_crepe_decode.argtypes = [_VP, _FP, ctypes.c_int, ctypes.c_int, _FP, _FP, ctypes.POINTER(ctypes.c_int)]
+        d.ry_crepe_set_viterbi_tables.argtypes = [_VP, _DP, _DP, _DP]
+        d.ry_crepe_debug_layer.argtypes = [_VP, ctypes.c_int, _FP]
+        d.ry_crepe_debug_splits.argtypes = [_VP, ctypes.POINTER(ctypes.c_int)]
         d.ry_net_profile_window.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RyKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
 
     def check(self, rc):

@@ -1,0 +1,333 @@
+"""CREPE pitch tracker on the MI355X: network spec, weights (seeded synthetic, or a `.npz` / torch state-dict file), the host-side
+pieces (resampling to 16 kHz, the HMM tables, `predict_voicing`) and `CrepeModel`, the handle over `ry_crepe_*` (include/ry355.h).
+
+The reference turns CREPE on with `extract_f0_mode: crepe` (realtime-yukarin: realtime_voice_conversion/config.py:8-10); its
+CrepeAcousticFeatureWrapper.extract_f0 calls `crepe.predict(x, fs, viterbi=True, model_capacity='full', step_size=frame_period)` and
+`crepe.predict_voicing(confidence)` (yukarin_wrapper/acoustic_feature_wrapper.py:65-80).  The drop-in module with those names is
+`realtime_yukarin_amd/compat/crepe`.  Everything here is restated from the public crepe package and its PyTorch fork ([MEM]): no
+trained weights, crepe, resampy or hmmlearn exist to pin it against.
+"""
+import ctypes
+import os
+from pathlib import Path
+from typing import Dict, List, Optional, Tuple
+
+import numpy
+
+from . import _lib
+
+# ---- the network ([MEM], one place) --------------------------------------------------------------------------------------------
+CAPACITIES = {'tiny': 4, 'small': 8, 'medium': 16, 'large': 24, 'full': 32}
+FILTERS = (32, 4, 4, 4, 8, 16)           # x multiplier
+WIDTHS = (512, 64, 64, 64, 64, 64)
+STRIDES = (4, 1, 1, 1, 1, 1)
+PADS = ((254, 254), (31, 32), (31, 32), (31, 32), (31, 32), (31, 32))     # Keras 'same'
+MODEL_SRATE = 16000
+FRAME = 1024
+BINS = 360
+BN_EPS = 1e-3                            # Keras BatchNormalization default
+STD_FLOOR = 1e-10                        # divisor clamp of a silent frame (torchcrepe's choice; the original gives NaN)
+CENTS_OFFSET = 1997.3794084376191        # cents of bin b = 7180 / 359 * b + CENTS_OFFSET (linspace(0, 7180, 360))
+# resampy's 'kaiser_best' filter ([MEM]): 64 zero crossings, 2^9 table entries per crossing, Kaiser beta, roll-off
+KAISER_BEST = dict(num_zeros=64, precision=9, beta=14.769656459379492, rolloff=0.9475937167399596)
+# predict_voicing: two-state Gaussian HMM over the confidence ([MEM]: start, transition, means, variances; state 1 = voiced)
+VOICING_START = (0.7472, 0.2528)
+VOICING_TRANS = ((0.9991, 0.0009), (0.0025, 0.9975))
+VOICING_MEANS = (0.0795, 0.6278)
+VOICING_VARS = (0.0181, 0.0454)
+
+
+def multiplier(capacity) -> int:
+    """'tiny' .. 'full' -> 4 .. 32; an int is taken as the multiplier itself (1 .. 32; tests use reduced ones)."""
+    if isinstance(capacity, str):
+        if capacity not in CAPACITIES:
+            raise ValueError('unknown CREPE capacity %r (one of %s)' % (capacity, ', '.join(CAPACITIES)))
+        return CAPACITIES[capacity]
+    m = int(capacity)
+    if not 1 <= m <= 32:
+        raise ValueError('CREPE capacity multiplier %d out of range 1 .. 32' % m)
+    return m
+
+
+def channels(m: int) -> List[int]:
+    return [f * m for f in FILTERS]
+
+
+def param_list(m: int) -> List[Tuple[str, Tuple[int, ...]]]:
+    """Keys and shapes in blob order (`ry_crepe_create`), named after the PyTorch fork's state dict ([MEM])."""
+    out, cin = [], 1
+    for i, (c, w) in enumerate(zip(channels(m), WIDTHS), 1):
+        out += [('conv%d.weight' % i, (c, cin, w)), ('conv%d.bias' % i, (c,))]
+        out += [('conv%d_BN.%s' % (i, k), (c,)) for k in ('weight', 'bias', 'running_mean', 'running_var')]
+        cin = c
+    return out + [('classifier.weight', (BINS, 4 * cin)), ('classifier.bias', (BINS,))]
+
+
+def param_count(m: int) -> int:
+    return sum(int(numpy.prod(s)) for _, s in param_list(m))
+
+
+def synthetic_params(capacity, seed: int = 0) -> Dict[str, numpy.ndarray]:
+    """Seeded stand-in weights: He-scaled filters, small biases, BatchNorm statistics whose gamma is negative for every eighth channel
+    (so BN cannot be folded into the filters and the pool must compare values after BN)."""
+    m = multiplier(capacity)
+    rng = numpy.random.default_rng(seed)
+    P = {}
+    for key, shape in param_list(m):
+        if key.endswith('.weight') and len(shape) > 1:
+            fan_in = int(numpy.prod(shape[1:]))
+            a = rng.normal(0.0, numpy.sqrt((2.0 if key.startswith('conv') else 1.0) / fan_in), shape)
+        elif key.endswith('_BN.weight'):
+            a = rng.normal(0.8, 0.4, shape)
+            a[::8] = -numpy.abs(a[::8])
+        elif key.endswith('_BN.running_mean'):
+            a = rng.uniform(0.0, 0.5, shape)
+        elif key.endswith('_BN.running_var'):
+            a = rng.uniform(0.5, 1.5, shape)
+        else:                                                    # conv / BN / classifier biases
+            a = rng.normal(0.0, 0.1, shape)
+        P[key] = a.astype(numpy.float32)
+    return P
+
+
+def validate_params(m: int, P: Dict[str, numpy.ndarray]) -> Dict[str, numpy.ndarray]:
+    """Exactly the keys of `param_list(m)` (a torch state dict may also carry `num_batches_tracked`), conv filters (Cout, Cin, W) or the
+    fork's (Cout, Cin, W, 1).  Returns the float32 arrays in the canonical shapes; refuses anything else."""
+    want = dict(param_list(m))
+    have = {k: v for k, v in P.items() if not k.endswith('num_batches_tracked')}
+    missing, extra = sorted(set(want) - set(have)), sorted(set(have) - set(want))
+    if missing or extra:
+        raise ValueError('CREPE weight keys do not match capacity %d: missing=%s unexpected=%s' % (m, missing, extra))
+    out = {}
+    for k, shape in want.items():
+        a = numpy.asarray(have[k])
+        if a.shape != shape and not (len(shape) == 3 and a.shape == shape + (1,)):
+            raise ValueError('CREPE weight %s has shape %s, capacity %d needs %s' % (k, a.shape, m, shape))
+        if not numpy.issubdtype(a.dtype, numpy.floating):
+            raise ValueError('CREPE weight %s has dtype %s' % (k, a.dtype))
+        out[k] = numpy.ascontiguousarray(a.reshape(shape), dtype=numpy.float32)
+    return out
+
+
+def capacity_of(P: Dict[str, numpy.ndarray]) -> int:
+    """The multiplier a weight set was built for (conv1 has 32 m filters)."""
+    if 'conv1.weight' not in P:
+        raise ValueError('CREPE weights without conv1.weight')
+    c = int(numpy.asarray(P['conv1.weight']).shape[0])
+    if c % 32:
+        raise ValueError('conv1.weight has %d filters, not a multiple of 32' % c)
+    return c // 32
+
+
+def load_weights(path, capacity=None) -> Tuple[int, Dict[str, numpy.ndarray]]:
+    """A `.npz` (keys of `param_list`) or a torch state dict (`.pt` / `.pth`, tensors under the same keys) -> (multiplier, weights)."""
+    path = Path(path)
+    if path.suffix == '.npz':
+        with numpy.load(str(path)) as z:
+            P = {k: numpy.asarray(z[k]) for k in z.files}
+    else:
+        import torch
+        sd = torch.load(str(path), map_location='cpu', weights_only=True)
+        if not isinstance(sd, dict):
+            raise ValueError('%s: expected a state dict, got %s' % (path, type(sd).__name__))
+        P = {k: v.detach().cpu().numpy() if hasattr(v, 'detach') else numpy.asarray(v) for k, v in sd.items()}
+    m = capacity_of(P) if capacity is None else multiplier(capacity)
+    return m, validate_params(m, P)
+
+
+def save_weights(path, P: Dict[str, numpy.ndarray]) -> None:
+    numpy.savez(str(path), **P)
+
+
+def flatten_params(m: int, P: Dict[str, numpy.ndarray]) -> numpy.ndarray:
+    P = validate_params(m, P)
+    return numpy.concatenate([P[k].ravel() for k, _ in param_list(m)])
+
+
+# ---- framing, decode tables, resampling, voicing (host, float64) ---------------------------------------------------------------
+def n_frames(n_samples: int, hop: int, center: bool = True) -> int:
+    return 1 + (int(n_samples) + (FRAME if center else 0) - FRAME) // int(hop)
+
+
+def hop_length(step_size) -> int:
+    """`int(16000 * step_size / 1000)`: 80 samples for the reference's 5 ms."""
+    return int(MODEL_SRATE * step_size / 1000)
+
+
+def viterbi_tables():
+    """(logT [360][360], logE [360][360], logS [360]) in float64 with numpy's log: uniform start, T[i][j] ~ max(12 - |i - j|, 0) per row,
+    emission 0.1 I + 0.9 / 360.  Uploaded to the device so that its Viterbi path equals the numpy restatement's bit for bit."""
+    xx, yy = numpy.meshgrid(range(BINS), range(BINS))
+    T = numpy.maximum(12 - abs(xx - yy), 0)
+    T = T / numpy.sum(T, axis=1)[:, None]
+    E = numpy.eye(BINS) * 0.1 + numpy.ones((BINS, BINS)) * (0.9 / BINS)
+    with numpy.errstate(divide='ignore'):
+        return numpy.log(T), numpy.log(E), numpy.log(numpy.ones(BINS) / BINS)
+
+
+def cents_mapping() -> numpy.ndarray:
+    return numpy.linspace(0, 7180, BINS) + CENTS_OFFSET
+
+
+def _kaiser_best_window():
+    k = KAISER_BEST
+    n = (2 ** k['precision']) * k['num_zeros']
+    sinc = k['rolloff'] * numpy.sinc(k['rolloff'] * numpy.linspace(0, k['num_zeros'], num=n + 1, endpoint=True))
+    return numpy.kaiser(2 * n + 1, k['beta'])[n:] * sinc, 2 ** k['precision']
+
+
+def resample(x, sr_orig: int, sr_new: int = MODEL_SRATE) -> numpy.ndarray:
+    """Band-limited windowed-sinc interpolation with resampy's 'kaiser_best' parameters ([MEM]; the interpolation loop of
+    resampy.resample_f, every output a sum over the taps on both sides of its time), in float64; returns float32.  Output length
+    int(len * sr_new / sr_orig)."""
+    x = numpy.asarray(x, dtype=numpy.float64)
+    if sr_orig == sr_new:
+        return x.astype(numpy.float32)
+    ratio = float(sr_new) / sr_orig
+    win, num_table = _kaiser_best_window()
+    if ratio < 1:
+        win = win * ratio
+    delta = numpy.zeros_like(win)
+    delta[:-1] = numpy.diff(win)
+    n_out = int(x.shape[0] * ratio)
+    y = numpy.zeros(n_out)
+    if n_out == 0:
+        return y.astype(numpy.float32)
+    scale = min(1.0, ratio)
+    step = int(scale * num_table)
+    tr = numpy.concatenate([[0.0], numpy.cumsum(numpy.full(n_out - 1, 1.0 / ratio))])     # time_register += increment, in order
+    n = tr.astype(numpy.int64)
+    nwin = win.shape[0]
+    for side in (0, 1):
+        frac = scale * (tr - n)
+        if side:
+            frac = scale - frac
+        index_frac = frac * num_table
+        offset = index_frac.astype(numpy.int64)
+        eta = index_frac - offset
+        lim = (nwin - offset) // step
+        cap = numpy.minimum(n + 1, lim) if side == 0 else numpy.minimum(x.shape[0] - n - 1, lim)
+        for i in range(int(cap.max()) if cap.size else 0):
+            live = i < cap
+            idx = offset[live] + i * step
+            src = n[live] - i if side == 0 else n[live] + i + 1
+            y[live] += (win[idx] + eta[live] * delta[idx]) * x[src]
+    return y.astype(numpy.float32)
+
+
+def predict_voicing(confidence) -> numpy.ndarray:
+    """Voiced (1) / unvoiced (0) per frame: Viterbi path of a two-state Gaussian HMM over the confidence, float64, lowest state on ties
+    (the fork's `predict_voicing` with fixed constants, [MEM])."""
+    x = numpy.asarray(confidence, dtype=numpy.float64).ravel()
+    if x.size == 0:
+        return numpy.zeros(0, numpy.int64)
+    mu, var = numpy.asarray(VOICING_MEANS), numpy.asarray(VOICING_VARS)
+    logp = -0.5 * (numpy.log(2 * numpy.pi * var)[None, :] + (x[:, None] - mu[None, :]) ** 2 / var[None, :])
+    logT = numpy.log(numpy.asarray(VOICING_TRANS))
+    lat = numpy.log(numpy.asarray(VOICING_START)) + logp[0]
+    bp = numpy.zeros((x.size, 2), numpy.int64)
+    for t in range(1, x.size):
+        s = lat[:, None] + logT
+        bp[t] = numpy.argmax(s, axis=0)
+        lat = s[bp[t], [0, 1]] + logp[t]
+    path = numpy.zeros(x.size, numpy.int64)
+    path[-1] = int(numpy.argmax(lat))
+    for t in range(x.size - 1, 0, -1):
+        path[t - 1] = bp[t, path[t]]
+    return path
+
+
+# ---- the device model ---------------------------------------------------------------------------------------------------------
+class CrepeModel(object):
+    """CREPE on the MI355X (`ry_crepe_*`).  Picklable and fork-safe: the GPU context and the device weights are created lazily in the
+    process that first predicts; the host copy of the weights travels with the object.  `ctx` (tests) is a context over another build
+    of the library -- the emulator -- used instead of the product's context of `device`."""
+
+    def __init__(self, capacity='full', params: Optional[Dict[str, numpy.ndarray]] = None, device: Optional[int] = None,
+                 bn_eps: float = BN_EPS, ctx=None, seed: Optional[int] = None):
+        self.m = multiplier(capacity)
+        if params is None:
+            if seed is None:
+                raise ValueError('CrepeModel needs weights: pass params (load_weights / synthetic_params) or a seed for synthetic ones')
+            params = synthetic_params(self.m, seed)
+        self.blob = flatten_params(self.m, params)
+        self.device = int(os.environ.get('RY_DEVICE', '0')) if device is None else int(device)
+        self.bn_eps = float(bn_eps)
+        self._ctx = ctx
+        self._given_ctx = ctx
+        self._handle = None
+        self._pid = None
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        d['_handle'] = None
+        d['_pid'] = None
+        d['_ctx'] = None
+        d['_given_ctx'] = None
+        return d
+
+    def _get(self):
+        if self._handle is None or self._pid != os.getpid():
+            from . import engine
+            given = self._given_ctx is not None and self._given_ctx.pid == os.getpid()
+            self._ctx = self._given_ctx if given else engine.get_context(self.device)
+            lib = self._ctx.lib
+            h = ctypes.c_void_p()
+            lib.check(lib.dll.ry_crepe_create(self._ctx.handle, self.m, _lib._fptr(self.blob), self.blob.size, self.bn_eps, ctypes.byref(h)))
+            self._handle, self._pid = h, os.getpid()
+            dp = ctypes.POINTER(ctypes.c_double)
+            tabs = [numpy.ascontiguousarray(t, dtype=numpy.float64) for t in viterbi_tables()]
+            lib.check(lib.dll.ry_crepe_set_viterbi_tables(self._handle, *[t.ctypes.data_as(dp) for t in tabs]))
+        return self._ctx.lib, self._handle
+
+    def predict16k(self, audio, hop: int, center: bool = True, viterbi: bool = True, activation: bool = True):
+        """audio: float32 samples at 16 kHz -> (f0 float32 Hz, confidence float32, activation [frames][360] float32 or None)."""
+        lib, h = self._get()
+        x = numpy.ascontiguousarray(audio, dtype=numpy.float32).ravel()
+        n = n_frames(x.size, hop, center)
+        if x.size < 1 or n < 1:
+            raise ValueError('CREPE needs at least %d samples (center=False) or one sample, got %d' % (FRAME if not center else 1, x.size))
+        f0 = numpy.empty(n, numpy.float32)
+        conf = numpy.empty(n, numpy.float32)
+        act = numpy.empty((n, BINS), numpy.float32) if activation else None
+        lib.check(lib.dll.ry_crepe_predict(h, _lib._fptr(x), x.size, int(hop), int(bool(center)), int(bool(viterbi)),
+                                           _lib._fptr(f0), _lib._fptr(conf), _lib._fptr(act), 0))
+        return f0, conf, act
+
+    def decode(self, activation, viterbi: bool = True):
+        """The decode alone on a host activation (frames, 360) -> (f0, confidence, centre bin per frame) (`ry_crepe_decode`)."""
+        lib, h = self._get()
+        a = numpy.ascontiguousarray(activation, dtype=numpy.float32)
+        if a.ndim != 2 or a.shape[1] != BINS or a.shape[0] < 1:
+            raise ValueError('activation must be (frames, %d), got %s' % (BINS, a.shape))
+        n = a.shape[0]
+        f0, conf, path = numpy.empty(n, numpy.float32), numpy.empty(n, numpy.float32), numpy.empty(n, numpy.int32)
+        lib.check(lib.dll.ry_crepe_decode(h, _lib._fptr(a), n, int(bool(viterbi)), _lib._fptr(f0), _lib._fptr(conf),
+                                          path.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return f0, conf, path
+
+    def debug_layer(self, layer: int, frames: int) -> numpy.ndarray:
+        """The last pass's buffer `layer` (0 frames, 1 .. 6 pooled conv outputs, 7 logits) for its `frames` frames (`ry_crepe_debug_layer`)."""
+        lib, h = self._get()
+        c = channels(self.m)
+        shape = {0: (frames, FRAME), 7: (frames, BINS)}.get(layer) or (frames, (FRAME // 4) >> layer, c[layer - 1])
+        out = numpy.empty(shape, numpy.float32)
+        lib.check(lib.dll.ry_crepe_debug_layer(h, int(layer), _lib._fptr(out)))
+        return out
+
+    def splits(self) -> List[int]:
+        lib, h = self._get()
+        s = (ctypes.c_int * 7)()
+        lib.check(lib.dll.ry_crepe_debug_splits(h, s))
+        return list(s)
+
+    def close(self):
+        if self._handle is not None and self._pid == os.getpid() and self._ctx is not None and self._ctx.handle is not None:
+            self._ctx.lib.dll.ry_crepe_destroy(self._handle)
+        self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

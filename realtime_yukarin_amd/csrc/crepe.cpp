@@ -1,0 +1,360 @@
+// crepe.cpp -- the CREPE pitch tracker of libry355.so (`crepe.predict(..., viterbi=True)`, called by the reference's
+// CrepeAcousticFeatureWrapper.extract_f0): framing -> conv1 .. conv6 (conv -> ReLU -> BN -> max-pool 2, one implicit-GEMM kernel each,
+// split-K where the grid is short) -> dense + sigmoid -> argmax / Viterbi / local-average cents.  Kernels: crepe_kernels.h.
+// The frames of a call run in passes of at most CHUNK frames; the activation of every frame is kept for the decode, which runs once.
+#include "crepe_kernels.h"
+#include "ry_host.h"
+
+namespace {
+const int MULT_MAX = 32;                            // capacities: tiny 4, small 8, medium 16, large 24, full 32 (any 1 .. 32 is accepted)
+const int NCONV = 6;
+const int FILTERS[NCONV] = {32, 4, 4, 4, 8, 16};    // x multiplier
+const int WIDTHS[NCONV] = {512, 64, 64, 64, 64, 64};
+const int STRIDES[NCONV] = {4, 1, 1, 1, 1, 1};
+const int PAD_L = 31, PAD_R = 32;                   // Keras 'same' for width 64 (conv1: 254 / 254, stored in the frame row)
+const int CHUNK = 256;                              // frames per pass through the network
+const int PLAN_FRAMES = 201;                        // split-K counts are planned for one second at 5 ms and then fixed per layer:
+                                                    // every frame's sums run in the same order whatever the length of the call
+const int PLAN_WORKGROUPS = 1000;
+
+struct CLayer {
+    int cin = 0, cout = 0, width = 0, stride = 1;
+    int lin = 0, lout = 0, K = 0;                   // lout: positions before the pool (dense: 1)
+    int splits = 1;
+    int in_fstride = 0, in_rstride = 0;             // input frame stride / window step (floats)
+    int out_fstride = 0, out_off = 0;               // pooled output: frame stride / offset of position 0 (floats)
+    float *w = nullptr, *b = nullptr, *sc = nullptr, *sh = nullptr;
+};
+
+size_t param_count(int m) {
+    size_t n = 0;
+    int cin = 1;
+    for (int i = 0; i < NCONV; ++i) {
+        const size_t c = (size_t)FILTERS[i] * m;
+        n += c * cin * WIDTHS[i] + 5 * c;
+        cin = (int)c;
+    }
+    return n + (size_t)CREPE_BINS * 4 * cin + CREPE_BINS;
+}
+}  // namespace
+
+struct ry_crepe {
+    ry_ctx* ctx = nullptr;
+    int m = 0;
+    CLayer L[NCONV + 1];                            // conv1 .. conv6, dense
+    Arena weights;
+    double *logT = nullptr, *logE = nullptr, *logS = nullptr;
+    // pass buffers (CHUNK frames at most): frame rows, the padded input of each conv layer after the first, the dense input, logits, slabs
+    Arena bufs;
+    int cap_chunk = 0;
+    float* act_in[NCONV + 1] = {};                  // act_in[0] = frames, act_in[i] = input of layer i (conv i + 1 / dense)
+    float* logits = nullptr;
+    float* slabs = nullptr;
+    int last_chunk = 0;                             // frames of the last pass (ry_crepe_debug_layer)
+    // call buffers (every frame of a call)
+    Arena call;
+    int cap_frames = 0, cap_samples = 0;
+    float *audio = nullptr, *act = nullptr, *conf = nullptr, *f0 = nullptr;
+    int *obs = nullptr, *bp = nullptr, *path = nullptr;
+};
+
+namespace {
+int ensure_chunk(ry_crepe* c, int nf) {
+    if (nf <= c->cap_chunk) return RY_OK;
+    const int cap = nf;
+    RT_TRY(rt::stream_sync(c->ctx->stream));                   // a call still in flight may use the old buffers
+    c->bufs.release();
+    size_t slab = 0;
+    for (int i = 0; i <= NCONV; ++i) {
+        const CLayer& l = c->L[i];
+        const size_t in_floats = (size_t)cap * l.in_fstride;
+        RY_TRY(c->bufs.alloc(&c->act_in[i], in_floats));
+        RT_TRY(rt::dmemset(c->act_in[i], 0, in_floats * sizeof(float), c->ctx->stream));       // the padding rows stay zero
+        if (l.splits > 1) slab = std::max(slab, (size_t)l.splits * cap * l.lout * l.cout);
+    }
+    RY_TRY(c->bufs.alloc(&c->logits, (size_t)cap * CREPE_BINS));
+    RY_TRY(c->bufs.alloc(&c->slabs, std::max(slab, (size_t)1)));
+    c->cap_chunk = cap;
+    return RY_OK;
+}
+
+int ensure_call(ry_crepe* c, int n_frames, int n_samples) {
+    if (n_frames > c->cap_frames || n_samples > c->cap_samples) {
+        RT_TRY(rt::stream_sync(c->ctx->stream));
+        c->call.release();
+        c->cap_frames = std::max(n_frames, c->cap_frames);
+        c->cap_samples = std::max(n_samples, c->cap_samples);
+        const size_t F = (size_t)c->cap_frames;
+        float* q = nullptr;
+        RY_TRY(c->call.alloc(&c->audio, (size_t)c->cap_samples));
+        RY_TRY(c->call.alloc(&c->act, F * CREPE_BINS));
+        RY_TRY(c->call.alloc(&c->conf, F));
+        RY_TRY(c->call.alloc(&c->f0, F));
+        RY_TRY(c->call.alloc(&q, F)); c->obs = (int*)q;
+        RY_TRY(c->call.alloc(&q, F)); c->path = (int*)q;
+        RY_TRY(c->call.alloc(&q, F * CREPE_BINS)); c->bp = (int*)q;
+    }
+    return RY_OK;
+}
+
+int launch_layer(ry_crepe* c, int i, int nf) {
+    const CLayer& l = c->L[i];
+    const bool dense = i == NCONV;
+    CrepeGemmParams p;
+    p.x = c->act_in[i]; p.w = l.w; p.bias = l.b; p.scale = l.sc; p.shift = l.sh;
+    p.M = nf * l.lout; p.N = l.cout; p.K = l.K; p.lout = l.lout;
+    p.in_fstride = l.in_fstride; p.in_rstride = l.in_rstride;
+    p.out_fstride = l.out_fstride; p.out_off = l.out_off; p.splits = l.splits;
+    float* out = dense ? nullptr : c->act_in[i + 1];
+    float* act = c->act;                                        // set by the caller to this pass's rows (ry_crepe_predict)
+    dim3 grid((unsigned)((l.cout + CREPE_BN - 1) / CREPE_BN), (unsigned)((p.M + CREPE_BM - 1) / CREPE_BM), (unsigned)l.splits);
+    const ry_stream_t s = c->ctx->stream;
+    const int epi = l.splits > 1 ? CREPE_EPI_RAW : dense ? CREPE_EPI_SIG : CREPE_EPI_POOL;
+    p.y = epi == CREPE_EPI_RAW ? c->slabs : dense ? act : out;
+    p.y2 = epi == CREPE_EPI_SIG ? c->logits : nullptr;
+    switch (i * 3 + epi) {
+#define CREPE_CASE(L, E) case (L) * 3 + (E): RY_LAUNCH((crepe_igemm<E, L + 1>), grid, 256, s, p); break;
+        CREPE_CASE(0, CREPE_EPI_POOL) CREPE_CASE(1, CREPE_EPI_POOL) CREPE_CASE(2, CREPE_EPI_POOL)
+        CREPE_CASE(3, CREPE_EPI_POOL) CREPE_CASE(4, CREPE_EPI_POOL) CREPE_CASE(5, CREPE_EPI_POOL)
+        CREPE_CASE(0, CREPE_EPI_RAW) CREPE_CASE(1, CREPE_EPI_RAW) CREPE_CASE(2, CREPE_EPI_RAW) CREPE_CASE(3, CREPE_EPI_RAW)
+        CREPE_CASE(4, CREPE_EPI_RAW) CREPE_CASE(5, CREPE_EPI_RAW) CREPE_CASE(6, CREPE_EPI_RAW) CREPE_CASE(6, CREPE_EPI_SIG)
+#undef CREPE_CASE
+        default: return fail(RY_EINVAL, "crepe layer %d epilogue %d", i, epi);
+    }
+    RT_TRY(rt::last_error());
+    if (epi != CREPE_EPI_RAW) return RY_OK;
+    if (dense) {
+        CrepeReduceSigParams r;
+        r.slabs = c->slabs; r.bias = l.b; r.act = act; r.logits = c->logits; r.M = p.M; r.N = l.cout; r.splits = l.splits;
+        dim3 g((unsigned)(((long long)p.M * l.cout + 255) / 256));
+        RY_LAUNCH(crepe_reduce_sig, g, 256, s, r);
+    } else {
+        CrepeReducePoolParams r;
+        r.slabs = c->slabs; r.bias = l.b; r.scale = l.sc; r.shift = l.sh; r.y = out;
+        r.M = p.M; r.N = l.cout; r.lout = l.lout; r.out_fstride = l.out_fstride; r.out_off = l.out_off; r.splits = l.splits;
+        dim3 g((unsigned)(((long long)(p.M / 2) * l.cout + 255) / 256));
+        RY_LAUNCH(crepe_reduce_pool, g, 256, s, r);
+    }
+    RT_TRY(rt::last_error());
+    return RY_OK;
+}
+
+int launch_decode(ry_crepe* c, const float* act, int nf, int viterbi) {
+    const ry_stream_t s = c->ctx->stream;
+    CrepeArgmaxParams ap;
+    ap.act = act; ap.n_frames = nf; ap.obs = c->obs; ap.conf = c->conf;
+    RY_LAUNCH(crepe_argmax, dim3((unsigned)((nf + 3) / 4)), 256, s, ap);
+    RT_TRY(rt::last_error());
+    CrepeDecodeParams dp;
+    dp.act = act; dp.obs = c->obs; dp.n_frames = nf; dp.viterbi = viterbi ? 1 : 0;
+    dp.logT = c->logT; dp.logE = c->logE; dp.logS = c->logS; dp.bp = c->bp; dp.path = c->path; dp.f0 = c->f0;
+    RY_LAUNCH(crepe_decode, dim3(1), 384, s, dp);
+    RT_TRY(rt::last_error());
+    return RY_OK;
+}
+
+int upload_doubles(Arena& a, ry_ctx* ctx, const double* h, size_t n, double** d) {
+    float* q = nullptr;
+    RY_TRY(a.alloc(&q, 2 * n));
+    RT_TRY(rt::h2d(q, h, n * sizeof(double), ctx->stream));
+    RT_TRY(rt::stream_sync(ctx->stream));
+    *d = (double*)q;
+    return RY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t ry_crepe_param_count(int capacity) {
+    if (capacity < 1 || capacity > MULT_MAX) {
+        fail(RY_EINVAL, "crepe capacity multiplier %d out of range (1 .. %d; tiny 4, small 8, medium 16, large 24, full 32)", capacity, MULT_MAX);
+        return 0;
+    }
+    return param_count(capacity);
+}
+
+int ry_crepe_set_viterbi_tables(ry_crepe* c, const double* logT, const double* logE, const double* logS) {
+    if (!c || !logT || !logE || !logS) return fail(RY_EINVAL, "bad argument");
+    RT_TRY(rt::set_device(c->ctx->device));
+    RT_TRY(rt::stream_sync(c->ctx->stream));                   // the tables may be in use by a call still in flight
+    RT_TRY(rt::h2d(c->logT, logT, sizeof(double) * CREPE_BINS * CREPE_BINS, c->ctx->stream));
+    RT_TRY(rt::h2d(c->logE, logE, sizeof(double) * CREPE_BINS * CREPE_BINS, c->ctx->stream));
+    RT_TRY(rt::h2d(c->logS, logS, sizeof(double) * CREPE_BINS, c->ctx->stream));
+    RT_TRY(rt::stream_sync(c->ctx->stream));
+    return RY_OK;
+}
+
+int ry_crepe_create(ry_ctx* ctx, int capacity, const float* weights, size_t n_floats, float bn_eps, ry_crepe** out) {
+    if (!out) return fail(RY_EINVAL, "null out pointer");
+    *out = nullptr;
+    if (!ctx || !weights) return fail(RY_EINVAL, "bad argument");
+    const size_t want = ry_crepe_param_count(capacity);
+    if (want == 0) return RY_EINVAL;
+    if (n_floats != want) return fail(RY_EINVAL, "crepe weight blob has %zu floats, capacity %d needs %zu", n_floats, capacity, want);
+    if (!(bn_eps > 0.f)) return fail(RY_EINVAL, "bn_eps must be positive");
+    RT_TRY(rt::set_device(ctx->device));
+    std::unique_ptr<ry_crepe> c(new ry_crepe());
+    c->ctx = ctx;
+    c->m = capacity;
+    const float* src = weights;
+    int cin = 1, lin = CREPE_FRAME;
+    for (int i = 0; i <= NCONV; ++i) {
+        CLayer& l = c->L[i];
+        if (i < NCONV) {
+            l.cin = cin; l.cout = FILTERS[i] * capacity; l.width = WIDTHS[i]; l.stride = STRIDES[i];
+            l.lin = lin; l.lout = lin / l.stride; l.K = l.width * l.cin;
+            l.in_fstride = i == 0 ? CREPE_FRAME_ROW : (lin + PAD_L + PAD_R) * cin;
+            l.in_rstride = l.stride * cin;
+            const int pooled = l.lout / 2;
+            l.out_fstride = i + 1 < NCONV ? (pooled + PAD_L + PAD_R) * l.cout : pooled * l.cout;
+            l.out_off = i + 1 < NCONV ? PAD_L * l.cout : 0;
+            // torch layout W (Cout, Cin, width) -> [n][tap][ci]; BN (gamma, beta, mean, var) -> scale / shift after the ReLU
+            std::vector<float> w((size_t)l.cout * l.K), sc(l.cout), sh(l.cout), b(l.cout);
+            for (int n = 0; n < l.cout; ++n)
+                for (int ci = 0; ci < l.cin; ++ci)
+                    for (int t = 0; t < l.width; ++t)
+                        w[(size_t)n * l.K + (size_t)t * l.cin + ci] = src[((size_t)n * l.cin + ci) * l.width + t];
+            src += (size_t)l.cout * l.K;
+            const float* bias = src; const float* g = src + l.cout; const float* be = src + 2 * l.cout;
+            const float* mu = src + 3 * l.cout; const float* var = src + 4 * l.cout;
+            for (int n = 0; n < l.cout; ++n) {
+                const double s = (double)g[n] / std::sqrt((double)var[n] + (double)bn_eps);
+                sc[n] = (float)s; sh[n] = (float)((double)be[n] - (double)mu[n] * s); b[n] = bias[n];
+            }
+            src += 5 * (size_t)l.cout;
+            RY_TRY(upload(c->weights, ctx, w, &l.w)); RY_TRY(upload(c->weights, ctx, b, &l.b));
+            RY_TRY(upload(c->weights, ctx, sc, &l.sc)); RY_TRY(upload(c->weights, ctx, sh, &l.sh));
+            cin = l.cout; lin = pooled;
+        } else {                                                    // dense: classifier.weight (360, 4 C6) is already [n][k]
+            l.cin = 4 * cin; l.cout = CREPE_BINS; l.width = 1; l.lin = 1; l.lout = 1; l.K = 4 * cin;
+            l.in_fstride = 4 * cin; l.in_rstride = 0;
+            std::vector<float> w(src, src + (size_t)CREPE_BINS * l.K), b(src + (size_t)CREPE_BINS * l.K, src + (size_t)CREPE_BINS * (l.K + 1));
+            src += (size_t)CREPE_BINS * (l.K + 1);
+            RY_TRY(upload(c->weights, ctx, w, &l.w)); RY_TRY(upload(c->weights, ctx, b, &l.b));
+        }
+        // split-K: enough workgroups at one second of audio; at least 16 chunks of K per split (the dense layer: 4 -- its 6 tiles
+        // would otherwise leave most of the chip idle)
+        const long long tiles = (long long)((PLAN_FRAMES * l.lout + CREPE_BM - 1) / CREPE_BM) * ((l.cout + CREPE_BN - 1) / CREPE_BN);
+        const int nch = l.K / CREPE_BK;
+        l.splits = (int)std::max(1LL, std::min((long long)(nch / (i == NCONV ? 4 : 16)), (PLAN_WORKGROUPS + tiles - 1) / tiles));
+    }
+    // the HMM of the decode: uniform start, T[i][j] ~ max(12 - |i - j|, 0) per row, E = 0.1 I + 0.9 / 360 (logs in float64;
+    // the Python layer replaces them by numpy's own values, ry_crepe_set_viterbi_tables)
+    std::vector<double> lt((size_t)CREPE_BINS * CREPE_BINS), le((size_t)CREPE_BINS * CREPE_BINS), ls(CREPE_BINS);
+    for (int i = 0; i < CREPE_BINS; ++i) {
+        double sum = 0;
+        for (int j = 0; j < CREPE_BINS; ++j) sum += std::max(12 - std::abs(i - j), 0);
+        for (int j = 0; j < CREPE_BINS; ++j) {
+            lt[(size_t)i * CREPE_BINS + j] = std::log(std::max(12 - std::abs(i - j), 0) / sum);
+            le[(size_t)i * CREPE_BINS + j] = std::log((i == j ? 0.1 : 0.0) + 0.9 / CREPE_BINS);
+        }
+        ls[i] = std::log(1.0 / CREPE_BINS);
+    }
+    RY_TRY(upload_doubles(c->weights, ctx, lt.data(), lt.size(), &c->logT));
+    RY_TRY(upload_doubles(c->weights, ctx, le.data(), le.size(), &c->logE));
+    RY_TRY(upload_doubles(c->weights, ctx, ls.data(), ls.size(), &c->logS));
+    *out = c.release();
+    return RY_OK;
+}
+
+void ry_crepe_destroy(ry_crepe* c) {
+    if (!c) return;
+    rt::set_device(c->ctx->device);
+    rt::stream_sync(c->ctx->stream);
+    delete c;
+}
+
+int ry_crepe_predict(ry_crepe* c, const float* audio, int n_samples, int hop, int center, int viterbi,
+                     float* f0, float* confidence, float* activation, int on_device) {
+    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    if (!audio || !f0 || !confidence || n_samples < 1 || hop < 1) return fail(RY_EINVAL, "bad argument");
+    if (!center && n_samples < CREPE_FRAME) return fail(RY_EINVAL, "center = 0 needs at least %d samples, got %d", CREPE_FRAME, n_samples);
+    const long long nfl = 1 + ((long long)n_samples + (center ? CREPE_FRAME : 0) - CREPE_FRAME) / hop;
+    if (nfl > (1LL << 24)) return fail(RY_EINVAL, "%lld frames", nfl);
+    const int nf = (int)nfl;
+    ry_ctx* ctx = c->ctx;
+    const ry_stream_t s = ctx->stream;
+    RT_TRY(rt::set_device(ctx->device));
+    RY_TRY(ensure_chunk(c, std::min(nf, CHUNK)));
+    RY_TRY(ensure_call(c, nf, on_device ? 0 : n_samples));
+    const float* d_audio = audio;
+    if (!on_device) {
+        RT_TRY(rt::h2d(c->audio, audio, (size_t)n_samples * sizeof(float), s));
+        d_audio = c->audio;
+    }
+    float* act_all = c->act;
+    for (int f = 0; f < nf; f += CHUNK) {
+        const int n = std::min(CHUNK, nf - f);
+        CrepeFrameParams fp;
+        fp.audio = d_audio; fp.n = n_samples; fp.hop = hop; fp.center = center; fp.frame0 = f; fp.n_frames = n; fp.out = c->act_in[0];
+        RY_LAUNCH(crepe_frames, dim3((unsigned)n), 256, s, fp);
+        RT_TRY(rt::last_error());
+        c->act = act_all + (size_t)f * CREPE_BINS;                 // the dense layer writes this pass's rows
+        int rc = RY_OK;
+        for (int i = 0; i <= NCONV && rc == RY_OK; ++i) rc = launch_layer(c, i, n);
+        c->act = act_all;
+        RY_TRY(rc);
+        c->last_chunk = n;
+    }
+    RY_TRY(launch_decode(c, act_all, nf, viterbi));
+    if (on_device) {
+        RT_TRY(rt::d2d(f0, c->f0, (size_t)nf * sizeof(float), s));
+        RT_TRY(rt::d2d(confidence, c->conf, (size_t)nf * sizeof(float), s));
+        if (activation) RT_TRY(rt::d2d(activation, act_all, (size_t)nf * CREPE_BINS * sizeof(float), s));
+        return RY_OK;
+    }
+    RT_TRY(rt::d2h(f0, c->f0, (size_t)nf * sizeof(float), s));
+    RT_TRY(rt::d2h(confidence, c->conf, (size_t)nf * sizeof(float), s));
+    if (activation) RT_TRY(rt::d2h(activation, act_all, (size_t)nf * CREPE_BINS * sizeof(float), s));
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+int ry_crepe_decode(ry_crepe* c, const float* activation, int n_frames, int viterbi, float* f0, float* confidence, int* path) {
+    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    if (!activation || !f0 || !confidence || n_frames < 1 || n_frames > (1 << 24)) return fail(RY_EINVAL, "bad argument");
+    const ry_stream_t s = c->ctx->stream;
+    RT_TRY(rt::set_device(c->ctx->device));
+    RY_TRY(ensure_call(c, n_frames, 0));
+    RT_TRY(rt::h2d(c->act, activation, (size_t)n_frames * CREPE_BINS * sizeof(float), s));
+    RY_TRY(launch_decode(c, c->act, n_frames, viterbi));
+    RT_TRY(rt::d2h(f0, c->f0, (size_t)n_frames * sizeof(float), s));
+    RT_TRY(rt::d2h(confidence, c->conf, (size_t)n_frames * sizeof(float), s));
+    if (path) RT_TRY(rt::d2h(path, viterbi ? c->path : c->obs, (size_t)n_frames * sizeof(int), s));
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+int ry_crepe_debug_layer(ry_crepe* c, int layer, float* out) {
+    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    if (!out || layer < 0 || layer > NCONV + 1) return fail(RY_EINVAL, "bad argument (layer %d: 0 frames, 1 .. 6 conv outputs, 7 logits)", layer);
+    if (c->last_chunk < 1) return fail(RY_ESTATE, "no ry_crepe_predict has run");
+    const ry_stream_t s = c->ctx->stream;
+    RT_TRY(rt::set_device(c->ctx->device));
+    const int n = c->last_chunk;
+    if (layer == NCONV + 1) {
+        RT_TRY(rt::d2h(out, c->logits, (size_t)n * CREPE_BINS * sizeof(float), s));
+        RT_TRY(rt::stream_sync(s));
+        return RY_OK;
+    }
+    // the interior rows of the padded buffer
+    const CLayer& dst = c->L[layer];                                // the layer that reads this buffer (dense for layer 6)
+    int rows, cols, off;
+    if (layer == 0) { rows = CREPE_FRAME; cols = 1; off = CREPE_CONV1_PAD; }
+    else if (layer == NCONV) { rows = 4; cols = c->L[NCONV - 1].cout; off = 0; }
+    else { rows = dst.lin; cols = dst.cin; off = PAD_L * dst.cin; }
+    std::vector<float> h((size_t)n * dst.in_fstride);
+    RT_TRY(rt::d2h(h.data(), c->act_in[layer], h.size() * sizeof(float), s));
+    RT_TRY(rt::stream_sync(s));
+    for (int f = 0; f < n; ++f)
+        memcpy(out + (size_t)f * rows * cols, h.data() + (size_t)f * dst.in_fstride + off, (size_t)rows * cols * sizeof(float));
+    return RY_OK;
+}
+
+int ry_crepe_debug_splits(ry_crepe* c, int* splits) {
+    if (!c || !splits) return fail(RY_EINVAL, "bad argument");
+    for (int i = 0; i <= NCONV; ++i) splits[i] = c->L[i].splits;
+    return RY_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,351 @@
+// crepe_kernels.h -- the kernels of the CREPE pitch tracker (crepe.cpp): framing, one implicit-GEMM 1-D convolution family on
+// v_mfma_f32_32x32x2_f32 (conv1 .. conv6 and the dense classifier), the split-K reduction with the same epilogues, and the decode
+// (per-frame argmax / max, the 360-state Viterbi pass in float64, the local-average cents).
+// Semantics restated from the public crepe package and its PyTorch fork ([MEM]; INTEGRATION.md section 9 lists what is unpinned).
+//
+// Activations are channels-last with every frame's 'same' padding stored as zero rows, so the kernels never test an edge:
+//   frames   [frame][254 + 1024 + 258]          (conv1: stride 4, 254 left; the row is 1536 floats so float4 loads stay aligned)
+//   layer i  [frame][31 + L_i + 32][C_i]        (input of a width-64 layer; the pooled output of layer i - 1 fills the interior)
+//   conv6    [frame][4][C6]                     (= the dense layer's input row: index position * C6 + channel, Keras Permute + Flatten)
+// For an output row m = (frame, position) the K index k = tap * Cin + ci addresses input element (position * stride + tap) * Cin + ci
+// of the frame's padded block, i.e. ONE contiguous window of taps * Cin floats per row: the A operand is a strided row gather.
+#pragma once
+#include "ry_dev.h"
+
+#ifdef RY_HOST_EMU
+#include <cmath>
+#define CREPE_ISNAN(x) std::isnan(x)
+#else
+#define CREPE_ISNAN(x) __builtin_isnan(x)
+#endif
+
+#define CREPE_FRAME 1024          // samples per frame
+#define CREPE_FRAME_ROW 1536      // padded frame row (254 zeros | 1024 samples | 258 zeros)
+#define CREPE_CONV1_PAD 254
+#define CREPE_BINS 360
+#define CREPE_BAND 11             // transition T[i][j] > 0 only for |i - j| <= 11 (max(12 - |i - j|, 0))
+
+// ---------------------------------------------------------------------------------------------
+// Framing: frame f starts at sample f * hop - (center ? 512 : 0) of the 16 kHz signal (zeros outside it).  Each frame has its own mean
+// subtracted and is divided by its population standard deviation, both taken in float64; the divisor is clamped at 1e-10 so that a
+// digitally silent frame gives zeros, not NaN (the one deliberate difference from the original).
+// ---------------------------------------------------------------------------------------------
+struct CrepeFrameParams { const float* audio; int n, hop, center, frame0, n_frames; float* out; };
+
+RY_KERNEL(256) void crepe_frames(CrepeFrameParams p) {
+    __shared__ double red[256];
+    const int tid = (int)threadIdx.x;
+    const int f = p.frame0 + (int)blockIdx.x;
+    const long long s0 = (long long)f * p.hop - (p.center ? CREPE_FRAME / 2 : 0) + 4 * tid;
+    float v[4];
+    double s = 0.0;
+    for (int i = 0; i < 4; ++i) {
+        const long long s_i = s0 + i;
+        v[i] = (s_i >= 0 && s_i < p.n) ? p.audio[s_i] : 0.f;
+        s += (double)v[i];
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) red[tid] += red[tid + w]; __syncthreads(); }
+    const double mean = red[0] / CREPE_FRAME;
+    __syncthreads();
+    double q = 0.0;
+    for (int i = 0; i < 4; ++i) { const double d = (double)v[i] - mean; q += d * d; }
+    red[tid] = q;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) red[tid] += red[tid + w]; __syncthreads(); }
+    double sd = sqrt(red[0] / CREPE_FRAME);
+    if (!(sd > 1e-10)) sd = 1e-10;
+    float* o = p.out + (size_t)blockIdx.x * CREPE_FRAME_ROW + CREPE_CONV1_PAD + 4 * tid;
+    for (int i = 0; i < 4; ++i) o[i] = (float)(((double)v[i] - mean) / sd);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Implicit GEMM: D[m][n] = sum_k A[m][k] W[n][k], tile 128 x 128 x 32, four waves of 64 x 64 (2 x 2 blocks of 32 x 32), one
+// v_mfma_f32_32x32x2_f32 per block and K step.  Both operands sit k-contiguous in the LDS ([row][32 + 4]); K step s of a chunk gives
+// lane half h the index k = 16 h + s (A and B agree, so the sum is the same), which lets every lane fetch four steps with one 16-byte
+// LDS read.  The next chunk's global loads are issued before the current chunk's MFMAs (register prefetch, one LDS buffer).
+// grid = (N tiles, M tiles, splits); split z covers chunks [z * nch / splits, (z + 1) * nch / splits).
+// Epilogues:  CREPE_EPI_POOL  bias -> ReLU -> BN affine -> max of the row pair (2 p, 2 p + 1) -> pooled row p of the padded output
+//             CREPE_EPI_SIG   bias -> logits and sigmoid(logits) (the dense classifier)
+//             CREPE_EPI_RAW   the split's raw sums into its slab [z][M][N] (crepe_reduce finishes them in a fixed order)
+// Rows m, m + 1 of a pair are registers r, r + 1 of the same lane (D row = (r & 3) + 8 (r >> 2) + 4 h), so the pool is in-register.
+// ---------------------------------------------------------------------------------------------
+enum { CREPE_EPI_RAW = 0, CREPE_EPI_POOL = 1, CREPE_EPI_SIG = 2 };
+
+struct CrepeGemmParams {
+    const float* x;            // input activations (padded frames)
+    const float* w;            // [N][K], k = tap * Cin + ci
+    const float *bias, *scale, *shift;   // [N] (scale / shift: the BN affine; unused by the dense layer)
+    float* y;                  // POOL: padded output / SIG: activation [M][N] / RAW: slabs [splits][M][N]
+    float* y2;                 // SIG: logits [M][N]
+    int M, N, K;
+    int lout;                  // output positions per frame (before the pool)
+    int in_fstride;            // floats per input frame
+    int in_rstride;            // floats between the windows of consecutive positions (stride * Cin)
+    int out_fstride, out_off;  // POOL: floats per output frame, offset of position 0 (left padding rows * N)
+    int splits;
+};
+
+#define CREPE_BM 128
+#define CREPE_BN 128
+#define CREPE_BK 32
+#define CREPE_LDS_ROW (CREPE_BK + 4)
+
+RY_DEV float crepe_act(float acc, float b, float sc, float sh) {
+    const float v = fmaxf(acc + b, 0.f);
+    return v * sc + sh;
+}
+
+// LAYER (1 .. 6 conv, 7 dense) only names the instantiation, so that a kernel trace tells the layers apart
+template <int EPI, int LAYER>
+RY_KERNEL(256) void crepe_igemm(CrepeGemmParams p) {
+    __shared__ float As[CREPE_BM * CREPE_LDS_ROW];
+    __shared__ float Bs[CREPE_BN * CREPE_LDS_ROW];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int r = lane & 31, h = lane >> 5;
+    const int m0 = (int)blockIdx.y * CREPE_BM, n0 = (int)blockIdx.x * CREPE_BN;
+    const int nch = p.K / CREPE_BK;
+    const int z = (int)blockIdx.z;
+    const int c_lo = (int)((long long)z * nch / p.splits), c_hi = (int)((long long)(z + 1) * nch / p.splits);
+
+    // this thread's four A rows / four B rows (row = idx >> 3, 16-byte piece kq = idx & 7 of the 32-wide chunk)
+    const float* ga[4];
+    const float* gb[4];
+    bool va[4], vb[4];
+    int lrow[4], lq[4];
+    for (int i = 0; i < 4; ++i) {
+        const int idx = tid + 256 * i;
+        lrow[i] = idx >> 3; lq[i] = idx & 7;
+        const int m = m0 + lrow[i], n = n0 + lrow[i];
+        va[i] = m < p.M;
+        vb[i] = n < p.N;
+        const int mm = va[i] ? m : 0;
+        const int fr = mm / p.lout, pos = mm - fr * p.lout;
+        ga[i] = p.x + (size_t)fr * p.in_fstride + (size_t)pos * p.in_rstride + 4 * lq[i];
+        gb[i] = p.w + (size_t)(vb[i] ? n : 0) * p.K + 4 * lq[i];
+    }
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 ra[4], rb[4];
+    auto load = [&](int c) {
+        const int k0 = c * CREPE_BK;
+        for (int i = 0; i < 4; ++i) {
+            ra[i] = va[i] ? ry_ld4(ga[i] + k0) : zero4;
+            rb[i] = vb[i] ? ry_ld4(gb[i] + k0) : zero4;
+        }
+    };
+    auto stash = [&]() {
+        for (int i = 0; i < 4; ++i) {
+            ry_st4(&As[lrow[i] * CREPE_LDS_ROW + 4 * lq[i]], ra[i]);
+            ry_st4(&Bs[lrow[i] * CREPE_LDS_ROW + 4 * lq[i]], rb[i]);
+        }
+    };
+
+    f32x16 acc[2][2];
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j)
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    if (c_lo < c_hi) {
+        load(c_lo);
+        stash();
+        __syncthreads();
+    }
+    for (int c = c_lo; c < c_hi; ++c) {
+        if (c + 1 < c_hi) load(c + 1);
+        const float* pa0 = &As[(wm * 64 + r) * CREPE_LDS_ROW + 16 * h];
+        const float* pa1 = pa0 + 32 * CREPE_LDS_ROW;
+        const float* pb0 = &Bs[(wn * 64 + r) * CREPE_LDS_ROW + 16 * h];
+        const float* pb1 = pb0 + 32 * CREPE_LDS_ROW;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 a0 = ry_ld4(pa0 + 4 * q), a1 = ry_ld4(pa1 + 4 * q);
+            const f32x4 b0 = ry_ld4(pb0 + 4 * q), b1 = ry_ld4(pb1 + 4 * q);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                acc[0][0] = ry_mfma_32x32x2(a0[e], b0[e], acc[0][0]);
+                acc[0][1] = ry_mfma_32x32x2(a0[e], b1[e], acc[0][1]);
+                acc[1][0] = ry_mfma_32x32x2(a1[e], b0[e], acc[1][0]);
+                acc[1][1] = ry_mfma_32x32x2(a1[e], b1[e], acc[1][1]);
+            }
+        }
+        __syncthreads();
+        if (c + 1 < c_hi) {
+            stash();
+            __syncthreads();
+        }
+    }
+
+    for (int j = 0; j < 2; ++j) {
+        const int n = n0 + wn * 64 + j * 32 + r;
+        if (n >= p.N) continue;
+        float b = 0.f, sc = 1.f, sh = 0.f;
+        if (EPI != CREPE_EPI_RAW) b = p.bias[n];
+        if (EPI == CREPE_EPI_POOL) { sc = p.scale[n]; sh = p.shift[n]; }
+        for (int i = 0; i < 2; ++i) {
+            const int mb = m0 + wm * 64 + i * 32 + 4 * h;
+            for (int e = 0; e < 16; e += 2) {
+                const int m = mb + (e & 3) + 8 * (e >> 2);
+                if (m >= p.M) continue;
+                if (EPI == CREPE_EPI_POOL) {                          // conv layers: M is even, the pair is in or out together
+                    const float v = fmaxf(crepe_act(acc[i][j][e], b, sc, sh), crepe_act(acc[i][j][e + 1], b, sc, sh));
+                    const int pr = m >> 1, half = p.lout >> 1;
+                    const int fr = pr / half, pos = pr - fr * half;
+                    p.y[(size_t)fr * p.out_fstride + p.out_off + (size_t)pos * p.N + n] = v;
+                } else {
+                    for (int u = 0; u < 2 && m + u < p.M; ++u) {      // the dense layer: M = frames may be odd
+                        const float a = acc[i][j][e + u];
+                        const size_t o = (size_t)(m + u) * p.N + n;
+                        if (EPI == CREPE_EPI_RAW) {
+                            p.y[(size_t)z * p.M * p.N + o] = a;
+                        } else {
+                            const float l = a + b;
+                            p.y2[o] = l;
+                            p.y[o] = 1.f / (1.f + expf(-l));
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// The split-K sums (slab 0 + slab 1 + ... in that order) and the layer's epilogue: one thread per pooled output (POOL, M / 2 x N) or
+// per output (SIG, M x N).
+struct CrepeReducePoolParams { const float* slabs; const float *bias, *scale, *shift; float* y; int M, N, lout, out_fstride, out_off, splits; };
+
+RY_KERNEL(256) void crepe_reduce_pool(CrepeReducePoolParams p) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)(p.M >> 1) * p.N) return;
+    const int n = (int)(idx % p.N), pr = (int)(idx / p.N);
+    const size_t slab = (size_t)p.M * p.N;
+    const float* s = p.slabs + (size_t)(2 * pr) * p.N + n;
+    float a0 = 0.f, a1 = 0.f;
+    for (int z = 0; z < p.splits; ++z) { a0 += s[z * slab]; a1 += s[z * slab + p.N]; }
+    const float v = fmaxf(crepe_act(a0, p.bias[n], p.scale[n], p.shift[n]), crepe_act(a1, p.bias[n], p.scale[n], p.shift[n]));
+    const int half = p.lout >> 1;
+    const int fr = pr / half, pos = pr - fr * half;
+    p.y[(size_t)fr * p.out_fstride + p.out_off + (size_t)pos * p.N + n] = v;
+}
+
+struct CrepeReduceSigParams { const float* slabs; const float* bias; float* act; float* logits; int M, N, splits; };
+
+RY_KERNEL(256) void crepe_reduce_sig(CrepeReduceSigParams p) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)p.M * p.N) return;
+    const int n = (int)(idx % p.N);
+    const size_t slab = (size_t)p.M * p.N;
+    float a = 0.f;
+    for (int z = 0; z < p.splits; ++z) a += p.slabs[z * slab + idx];
+    const float l = a + p.bias[n];
+    p.logits[idx] = l;
+    p.act[idx] = 1.f / (1.f + expf(-l));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Decode.  crepe_argmax: one wave per frame, observation = argmax (lowest index on ties), confidence = max.
+// crepe_decode: ONE workgroup.  viterbi = 1: the 360-state Viterbi pass over all frames in float64 with the host's tables
+//   lat[0][j] = logS[j] + logE[j][obs 0];  lat[t][j] = max_i (lat[t - 1][i] + logT[i][j]) + logE[j][obs t]   (lowest i wins a tie)
+//   -- the additions of the numpy restatement in its order; only |i - j| <= 11 is visited (logT is -inf elsewhere and the lattice is
+//   finite, so the maximum and its index are the same) -- back-pointers in global memory, the backtrack by one lane.
+//   Then, per frame, the local weighted average of cents over bins [c - 4, c + 5) around the path (viterbi = 0: around the observation),
+//   f0 = 10 * 2^(cents / 1200), NaN -> 0.
+// ---------------------------------------------------------------------------------------------
+struct CrepeArgmaxParams { const float* act; int n_frames; int* obs; float* conf; };
+
+RY_KERNEL(256) void crepe_argmax(CrepeArgmaxParams p) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int t = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (t >= p.n_frames) return;                                   // wave-uniform
+    const float* a = p.act + (size_t)t * CREPE_BINS;
+    float best = a[lane];
+    float bi = (float)lane;
+    for (int j = lane + 64; j < CREPE_BINS; j += 64)
+        if (a[j] > best) { best = a[j]; bi = (float)j; }
+    for (int mask = 32; mask > 0; mask >>= 1) {
+        const float ob = ry_shfl_xor(best, mask), oi = ry_shfl_xor(bi, mask);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if (lane == 0) { p.obs[t] = (int)bi; p.conf[t] = best; }
+}
+
+struct CrepeDecodeParams {
+    const float* act; const int* obs; int n_frames; int viterbi;
+    const double* logT;        // [360][360]
+    const double* logE;        // [360][360]
+    const double* logS;        // [360]
+    int* bp;                   // [n_frames][360] back-pointers
+    int* path;                 // [n_frames]
+    float* f0;
+};
+
+RY_KERNEL(384) void crepe_decode(CrepeDecodeParams p) {
+    __shared__ double lat[2][CREPE_BINS];
+    __shared__ double tb[(2 * CREPE_BAND + 1) * CREPE_BINS];      // logT[j - 11 + d][j] at [d][j]: a wave reads consecutive doubles
+    const int tid = (int)threadIdx.x;
+    const int n = p.n_frames;
+    if (p.viterbi) {
+        const int j = tid;
+        const bool live = j < CREPE_BINS;
+        const double* le = p.logE + (size_t)(live ? j : 0) * CREPE_BINS;
+        if (live) {
+            for (int d = 0; d <= 2 * CREPE_BAND; ++d) {
+                const int i = j - CREPE_BAND + d;
+                tb[d * CREPE_BINS + j] = (i >= 0 && i < CREPE_BINS) ? p.logT[(size_t)i * CREPE_BINS + j] : 0.0;
+            }
+            lat[0][j] = p.logS[j] + le[p.obs[0]];
+        }
+        // the emission term of frame t + 1 and the observation of frame t + 2 are requested one step ahead; the barrier of each step waits
+        // for the LDS only (ry_lds_barrier), so these loads stay in flight across it
+        double e_next = (live && n > 1) ? le[p.obs[1]] : 0.0;
+        int o_next = n > 2 ? p.obs[2] : 0;
+        ry_lds_barrier();
+        for (int t = 1; t < n; ++t) {
+            const double e = e_next;
+            if (live && t + 1 < n) e_next = le[o_next];
+            if (t + 2 < n) o_next = p.obs[t + 2];
+            const double* prev = lat[(t - 1) & 1];
+            if (live) {
+                double best = 0.0;
+                int bi = -1;
+#pragma unroll
+                for (int d = 0; d <= 2 * CREPE_BAND; ++d) {
+                    const int i = j - CREPE_BAND + d;
+                    if (i >= 0 && i < CREPE_BINS) {
+                        const double v = prev[i] + tb[d * CREPE_BINS + j];
+                        if (bi < 0 || v > best) { best = v; bi = i; }
+                    }
+                }
+                lat[t & 1][j] = best + e;
+                p.bp[(size_t)t * CREPE_BINS + j] = bi;
+            }
+            ry_lds_barrier();
+        }
+        __syncthreads();                                           // the back-pointers of every wave are visible to lane 0
+        if (tid == 0) {
+            const double* last = lat[(n - 1) & 1];
+            int st = 0;
+            for (int i = 1; i < CREPE_BINS; ++i)
+                if (last[i] > last[st]) st = i;
+            p.path[n - 1] = st;
+            for (int t = n - 1; t > 0; --t) {
+                st = p.bp[(size_t)t * CREPE_BINS + st];
+                p.path[t - 1] = st;
+            }
+        }
+        __syncthreads();
+    }
+    for (int t = tid; t < n; t += 384) {
+        const int c = p.viterbi ? p.path[t] : p.obs[t];
+        const int b0 = c - 4 < 0 ? 0 : c - 4, b1 = c + 5 > CREPE_BINS ? CREPE_BINS : c + 5;
+        const float* a = p.act + (size_t)t * CREPE_BINS;
+        double ps = 0.0, ws = 0.0;
+        for (int b = b0; b < b1; ++b) {
+            ps += (double)a[b] * ((double)b * 20.0 + 1997.3794084376191);
+            ws += (double)a[b];
+        }
+        const double f = 10.0 * exp2((ps / ws) / 1200.0);
+        p.f0[t] = CREPE_ISNAN(f) ? 0.f : (float)f;
+    }
+}
