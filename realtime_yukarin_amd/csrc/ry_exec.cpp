@@ -91,10 +91,16 @@ static int launch_rep_rows(Launcher& Lc, const Layer& l, const LayerPlan& lp, in
     return RY_OK;
 }
 
-// sum of the raw split-K slabs of a launch + folded BN + activation (Ho_run = the output rows per image the launch covered, oo = their float offset)
-static int launch_reduce(Launcher& Lc, const Layer& l, const LayerPlan& lp, int B, int Ho_run, size_t oo, long long slab_stride, float slope) {
+// float offset of a launch's first output row: a cropped launch starts crop_lo rows (2 x for the sub-pixel form) into every image
+static size_t out_offset(const Layer& l, const LayerPlan& lp) {
+    return lp.crop_hi > 0 ? (size_t)(l.deconv ? 2 : 1) * lp.crop_lo * lp.Wo * l.cout : 0;
+}
+
+// sum of the raw split-K slabs of a launch + folded BN + activation (Ho_run = the output rows per image the launch covered)
+static int launch_reduce(Launcher& Lc, const Layer& l, const LayerPlan& lp, int B, int Ho_run, float slope) {
     RyReduceParams r;
-    const size_t ro = B == 1 ? oo : 0;                                    // one window: only the rows this launch wrote
+    const long long slab_stride = (long long)B * lp.Ho * lp.Wo * l.cout;
+    const size_t ro = B == 1 ? out_offset(l, lp) : 0;                     // one window: only the rows this launch wrote
     r.slabs = lp.slabs + ro; r.splits = lp.splits; r.slab_stride = slab_stride;
     r.scale = l.scale; r.shift = l.shift; r.out = lp.w32 ? lp.out + ro : nullptr; r.out16 = lp.w16 ? lp.out16 + ro * (lp.o16x3 ? 2 : 1) : nullptr;
     r.x3 = lp.o16x3 ? 1 : 0;
@@ -113,52 +119,81 @@ static int launch_reduce(Launcher& Lc, const Layer& l, const LayerPlan& lp, int 
     return Lc.end();
 }
 
+// The tile schedule of a stage-2 GEMM launch (RyTileSched), for both LDS-DMA kernels: M-tiles of bm rows of the Mh x Mw grid, 2-D blocks of
+// bm / tw x tw (tw > 0, from plan_tile_rows) with the hole rows of the plan left out, or bm consecutive rows in raster order (tw = 0); `ntiles`
+// N-tiles, `units` K units split lp.splits ways; wbytes = the filter bytes of one launch (the XCD split weighs them against the source bytes).
+static int fill_sched(RyTileSched& s, const Layer& l, const LayerPlan& lp, const RyConvGeom& g, int B, int bm, int tw, int ntiles, int units, double wbytes) {
+    memset(&s, 0, sizeof s);
+    s.ntiles = ntiles; s.splits = lp.splits;
+    s.hole_ty = 1 << 30;
+    s.tcols = 1; s.trows = 1; s.inv_tcols = 1.f; s.inv_trows = 1.f;
+    // the planner chose the hole by the same rule (enqueue_forward): a refusal here is a bug
+    if (lp.hole_n > 0 && !plan_hole_ok(l, lp, lp.hole_lo, lp.hole_n))
+        return fail(RY_ESTATE, "%s: rows %d..%d cannot be left out of this launch", l.name, lp.hole_lo, lp.hole_lo + lp.hole_n - 1);
+    if (tw > 0) {
+        const int th = bm / tw;
+        if (lp.hole_n > 0) { s.hole_ty = lp.hole_lo / th; s.hole_nt = lp.hole_n / th; }
+        s.tcols = g.Mw / tw; s.trows = g.Mh / th - s.hole_nt;
+        s.mtiles = B * s.trows * s.tcols;
+        s.inv_tcols = 1.f / s.tcols; s.inv_trows = 1.f / s.trows;
+    } else {
+        s.mtiles = (B * g.Mh * g.Mw + bm - 1) / bm;
+    }
+    // operands of ry_fdiv stay below 2^24
+    const int nsl = lp.splits * ntiles * g.nphases;
+    if ((long long)s.mtiles * nsl >= (1 << 24) || (long long)B * g.Mh * g.Mw >= (1 << 24))
+        return fail(RY_EINVAL, "%s: more than 2^24 output rows or tiles in one launch; lower the batch", l.name);
+    // the kernels' source offsets (the zero tails zoff1 / zoff2 of fill_geom, the lane offsets) are 32-bit byte offsets
+    const size_t esize = lp.path == PATH_IGEMM_BF16 ? 2 : 4;
+    if (((size_t)B * lp.Hi * lp.Wi * (size_t)(g.S1 > g.S2 ? g.S1 : g.S2) + ZTAIL) * esize >= ((size_t)1 << 32))
+        return fail(RY_EINVAL, "%s: a source of 4 GiB or more does not fit the kernel's 32-bit offsets", l.name);
+    s.inv_nphases = 1.f / g.nphases; s.inv_ntiles = 1.f / ntiles; s.inv_nsl = 1.f / nsl;
+    // XCD grouping: gm M-tile groups x gs slice groups (gm * gs = 8 L2s); every filter byte is fetched by gm L2s, every input byte by gs -- pick
+    // the split with the least L2 miss traffic among those that divide evenly
+    s.xcd_gs = 0; s.xcd_gs_shift = 0; s.xcd_nsg = 1; s.xcd_mtg = 1; s.inv_xcd_nsg = 1.f;
+    const double abytes = (double)B * lp.Hi * lp.Wi * (g.C1 + g.C2);
+    double best = 1e300;
+    for (int sh = 0; sh <= 3; ++sh) {
+        const int gs = 1 << sh, gm = 8 >> sh;
+        if (nsl % gs != 0 || s.mtiles % gm != 0) continue;
+        const double cost = gm * wbytes + gs * abytes;
+        if (cost < best) { best = cost; s.xcd_gs = gs; s.xcd_gs_shift = sh; s.xcd_nsg = nsl / gs; s.xcd_mtg = s.mtiles / gm; }
+    }
+    if (s.xcd_gs) s.inv_xcd_nsg = 1.f / s.xcd_nsg;
+    s.kq = units / lp.splits; s.krem = units % lp.splits;
+    return RY_OK;
+}
+
+// behind a stage-2 GEMM launch: the split-K reduce (it writes whatever the slab memory of the rows left out of the grid holds), then the copies
+// of those rows (Ho_run = the output rows per image the launch covered)
+static int launch_tail(Launcher& Lc, const Layer& l, const LayerPlan& lp, int B, int Ho_run, float slope) {
+    if (lp.splits > 1) RY_TRY(launch_reduce(Lc, l, lp, B, Ho_run, slope));
+    if (lp.hole_n > 0) RY_TRY(launch_rep_rows(Lc, l, lp, B));
+    return RY_OK;
+}
+
 static int launch_wino(Launcher& Lc, const Layer& l, const LayerPlan& lp, const float* wwin, int B, const float* s1, int C1, const float* s2, int C2, float slope) {
-    RyConvGeom g;
-    fill_geom(g, l, lp, B, s1, C1, s2, C2);
+    RyWinoParams p;
+    memset(&p, 0, sizeof p);
+    fill_geom(p.g, l, lp, B, s1, C1, s2, C2);
+    const RyConvGeom& g = p.g;
     int wm, wn, nsl;
     if (!wwin || !wino_eligible(l, 2) || !wino_cfg_dims(lp.wino_cfg, &wm, &wn, &nsl) || lp.wino_mbw < 1 || lp.wino_mbw > wm || (wm % lp.wino_mbw))
         return fail(RY_ESTATE, "%s: not a layer / plan for the Winograd kernel (cfg %d, %d blocks per tile row)", l.name, lp.wino_cfg, lp.wino_mbw);
-    int th, tw; wino_tile_hw(lp.wino_cfg, lp.wino_mbw, &th, &tw);
-    if (g.Mh % th || g.Mw % tw) return fail(RY_ESTATE, "%s: the %d x %d grid is not a multiple of the %d x %d Winograd tile", l.name, g.Mh, g.Mw, th, tw);
-    RyWinoParams p;
-    memset(&p, 0, sizeof p);
-    p.g = g; p.wt = wwin; p.scale = l.scale; p.shift = l.shift;
-    p.splits = lp.splits; p.act = l.act; p.slope = slope;
+    int th, tw;
+    if (!plan_tile_rows(lp, g.Mh, g.Mw, &th, &tw))
+        return fail(RY_ESTATE, "%s: the %d x %d grid is not a multiple of the %d x %d Winograd tile", l.name, g.Mh, g.Mw, th, tw);
+    p.wt = wwin; p.scale = l.scale; p.shift = l.shift;
+    p.act = l.act; p.slope = slope;
     p.slab_stride = (long long)B * lp.Ho * lp.Wo * l.cout;
-    // output rows start (2 x for the sub-pixel form) crop_lo rows into every image
-    const size_t oo = lp.crop_hi > 0 ? (size_t)(l.deconv ? 2 : 1) * lp.crop_lo * lp.Wo * l.cout : 0;
+    const size_t oo = out_offset(l, lp);
     p.out = lp.splits > 1 ? lp.slabs + oo : lp.out + oo;
     if (!p.out) return fail(RY_ESTATE, "%s: no output buffer", l.name);
-    p.mbw = lp.wino_mbw; p.tcols = g.Mw / tw; p.trows = g.Mh / th;
-    p.hole_ty = 1 << 30; p.hole_nt = 0;
-    if (lp.hole_n > 0) {
-        if (l.deconv || lp.crop_hi > 0 || lp.hole_lo % th || lp.hole_n % th || lp.hole_lo + lp.hole_n > g.Mh)
-            return fail(RY_ESTATE, "%s: rows %d..%d cannot be left out of this launch", l.name, lp.hole_lo, lp.hole_lo + lp.hole_n - 1);
-        p.hole_ty = lp.hole_lo / th; p.hole_nt = lp.hole_n / th; p.trows -= p.hole_nt;
-    }
-    p.mtiles = B * p.trows * p.tcols; p.ntiles = l.cout / (32 * wn);
+    p.mbw = lp.wino_mbw; p.inv_pw = 1.f / (float)(tw + 1);
     p.npatches = (l.deconv ? 1 : 4) * ((C1 + C2) / 16);
     if (lp.splits < 1 || lp.splits > p.npatches) return fail(RY_ESTATE, "%s: %d splits for %d patches", l.name, lp.splits, p.npatches);
-    p.kq = p.npatches / lp.splits; p.krem = p.npatches % lp.splits;
-    const int nsl_ = lp.splits * p.ntiles * g.nphases;
-    if ((long long)p.mtiles * nsl_ >= (1 << 24) || (long long)B * g.Mh * g.Mw >= (1 << 24)) return fail(RY_EINVAL, "%s: more than 2^24 output rows or tiles in one launch; lower the batch", l.name);
-    p.inv_nphases = 1.f / g.nphases; p.inv_ntiles = 1.f / p.ntiles; p.inv_tcols = 1.f / p.tcols; p.inv_trows = 1.f / p.trows; p.inv_pw = 1.f / (float)(tw + 1);
-    p.inv_nsl = 1.f / nsl_;
-    p.xcd_gs = 0; p.xcd_gs_shift = 0; p.xcd_nsg = 1; p.xcd_mtg = 1; p.inv_xcd_nsg = 1.f;
-    {   // XCD grouping as the implicit GEMM: gm M-tile groups x gs slice groups, the split with the least L2 miss traffic among those that divide evenly
-        const double wbytes = 2.25 * g.nphases * l.cout * 4.0 * (C1 + C2), abytes = (double)B * lp.Hi * lp.Wi * (C1 + C2);
-        double best = 1e300;
-        for (int sh = 0; sh <= 3; ++sh) {
-            const int gs = 1 << sh, gm = 8 >> sh;
-            if (nsl_ % gs != 0 || p.mtiles % gm != 0) continue;
-            const double cost = gm * wbytes + gs * abytes;
-            if (cost < best) { best = cost; p.xcd_gs = gs; p.xcd_gs_shift = sh; p.xcd_nsg = nsl_ / gs; p.xcd_mtg = p.mtiles / gm; }
-        }
-        if (p.xcd_gs) p.inv_xcd_nsg = 1.f / p.xcd_nsg;
-    }
-    const int total_tiles = p.mtiles * nsl_;
-    dim3 grid((unsigned)(((total_tiles + 7) / 8) * 8));
+    RY_TRY(fill_sched(p.s, l, lp, g, B, th * tw, tw, l.cout / (32 * wn), p.npatches, 2.25 * g.nphases * l.cout * 4.0 * (C1 + C2)));
+    dim3 grid((unsigned)(((p.s.mtiles * lp.splits * p.s.ntiles * g.nphases + 7) / 8) * 8));
     const int mode = l.deconv ? 1 : 2;
     RY_TRY(Lc.begin(wino_name(lp.wino_cfg, mode), l.name, lp.flops, lp.bytes, grid, lp.flops * 9.0 / 16.0));
     if (lp.wino_cfg == 1) {
@@ -169,125 +204,77 @@ static int launch_wino(Launcher& Lc, const Layer& l, const LayerPlan& lp, const 
         else RY_LAUNCH((ry_wino_ldsdma<4, 2, 2, 2>), grid, 512, Lc.stream, p);
     }
     RY_TRY(Lc.end());
-    // (with an external split the rows left out of the grid have no slabs: the reduce node writes whatever their slab memory holds, the copy node
-    // behind it fills them in)
-    if (lp.splits > 1) RY_TRY(launch_reduce(Lc, l, lp, B, g.Ho, oo, p.slab_stride, slope));
-    if (p.hole_nt > 0) RY_TRY(launch_rep_rows(Lc, l, lp, B));
-    return RY_OK;
+    return launch_tail(Lc, l, lp, B, g.Ho, slope);
+}
+
+static int launch_igemm(Launcher& Lc, const Layer& l, const LayerPlan& lp, int B, const float* s1, int C1, const float* s2, int C2, float slope) {
+    const bool bf16 = lp.path == PATH_IGEMM_BF16;       // s1 / s2 then point to bf16 activations
+    RyIgemmParams p;
+    memset(&p, 0, sizeof p);
+    fill_geom(p.g, l, lp, B, s1, C1, s2, C2);
+    const RyConvGeom& g = p.g;
+    if (bf16 && lp.x3) { C1 *= 3; C2 *= 3; }            // split-bf16: the K axis the kernel walks (g.C1 / g.C2)
+    p.wt = bf16 ? (lp.x3 ? l.wigx3 : l.wig16) : l.wig; p.scale = l.scale; p.shift = l.shift;
+    p.x3 = lp.o16x3 ? 1 : 0;
+    p.act = l.act; p.slope = slope;
+    p.slab_stride = (long long)B * lp.Ho * lp.Wo * l.cout;
+    const size_t oo = out_offset(l, lp);
+    p.out = lp.splits > 1 ? lp.slabs + oo : (lp.w32 ? lp.out + oo : nullptr);
+    p.out16 = (lp.splits == 1 && lp.w16) ? lp.out16 + oo * (lp.o16x3 ? 2 : 1) : nullptr;
+    int bm, bn; tile_dims(lp.tile, &bm, &bn);
+    // 2-D M-tiles when the row grid divides evenly, else BM consecutive rows in raster order
+    int th = 0, tw = 0;
+    if (!plan_tile_rows(lp, g.Mh, g.Mw, &th, &tw)) tw = 0;
+    const int M = B * g.Mh * g.Mw;
+    const int ck = bf16 ? 64 : 32, cpt = (C1 + C2) / ck, nkc = g.ntaps * cpt;
+    // patch variants of the kernel on 16-pixel-wide 2-D tiles (K units = whole channel chunks): 1: sub-pixel deconvolution, one patch per channel
+    // chunk; 2: k4 s2 p1 convolution, one patch per (chunk, input parity).  Small layers: the longer set-up costs more than the reuse saves
+    // (measured at M = 192).
+    int patch = 0;
+    if (tw == 16 && (M >= 512 || lp.any_m_patch)) {
+        if (g.ostride == 2 && lp.splits * lp.kg <= cpt) patch = 1;
+        else if (!l.deconv && l.k == 4 && l.stride == 2 && l.pad == 1 && l.dil == 1 && lp.splits * lp.kg <= 4 * cpt) patch = 2;
+    }
+    const int units = patch == 1 ? cpt : patch == 2 ? 4 * cpt : nkc;
+    RY_TRY(fill_sched(p.s, l, lp, g, B, bm, tw, l.cout / bn, units, (double)g.nphases * l.cout * g.ntaps * (C1 + C2)));
+    // prologue helpers of the kernel (ry_fdiv reciprocals)
+    p.inv_Mimg = 1.f / (float)(g.Mh * g.Mw); p.inv_Mw = 1.f / g.Mw; p.inv_cpt = 1.f / cpt; p.inv_kw = 1.f / g.kw;
+    p.tw = tw; p.tw_shift = 0; p.th = 1;
+    if (tw > 0) {
+        while ((1 << p.tw_shift) < tw) ++p.tw_shift;
+        p.th = th;
+    }
+    dim3 grid((unsigned)(((p.s.mtiles * p.s.ntiles * g.nphases * lp.splits + 7) / 8) * 8));
+    RY_TRY(Lc.begin(tile_name(lp.tile, lp.kg, bf16, patch), l.name, lp.flops, lp.bytes, grid));
+#define RY_IGEMM_LAUNCH(BM_, BN_, WM_, WN_, BF16_)                                                                                        \
+    do {                                                                                                                                 \
+        if (patch == 1 && lp.kg == 2) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 2, BF16_, 1>), grid, 512, Lc.stream, p);            \
+        else if (patch == 1) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 1, BF16_, 1>), grid, 256, Lc.stream, p);                     \
+        else if (patch == 2 && lp.kg == 2) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 2, BF16_, 2>), grid, 512, Lc.stream, p);       \
+        else if (patch == 2) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 1, BF16_, 2>), grid, 256, Lc.stream, p);                     \
+        else if (lp.kg == 2) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 2, BF16_, 0>), grid, 512, Lc.stream, p);                     \
+        else RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 1, BF16_, 0>), grid, 256, Lc.stream, p);                                     \
+    } while (0)
+#define RY_IGEMM_TILES(BF16_)                                                   \
+    switch (lp.tile) {                                                          \
+        case TILE_128x128: RY_IGEMM_LAUNCH(128, 128, 2, 2, BF16_); break;       \
+        case TILE_96x128: RY_IGEMM_LAUNCH(96, 128, 1, 4, BF16_); break;         \
+        case TILE_64x128: RY_IGEMM_LAUNCH(64, 128, 1, 4, BF16_); break;         \
+        case TILE_128x64: RY_IGEMM_LAUNCH(128, 64, 4, 1, BF16_); break;         \
+        default: RY_IGEMM_LAUNCH(32, 128, 1, 4, BF16_); break;                  \
+    }
+    if (bf16) RY_IGEMM_TILES(true) else RY_IGEMM_TILES(false)
+#undef RY_IGEMM_TILES
+#undef RY_IGEMM_LAUNCH
+    RY_TRY(Lc.end());
+    return launch_tail(Lc, l, lp, B, g.Ho, slope);
 }
 
 static int launch_conv2d(Launcher& Lc, const Layer& l, const LayerPlan& lp, int B, const float* s1, int C1, const float* s2, int C2, float slope) {
     if (lp.path == PATH_OS2D) return launch_c2d_os(Lc, l, lp, B, s1, C1, s2, C2, slope);
     if (lp.path == PATH_WINO) return launch_wino(Lc, l, lp, l.wwin, B, s1, C1, s2, C2, slope);
-    RyConvGeom g;
-    fill_geom(g, l, lp, B, s1, C1, s2, C2);
-    const int M = B * g.Mh * g.Mw;
-    if (lp.path == PATH_IGEMM || lp.path == PATH_IGEMM_BF16) {
-        const bool bf16 = lp.path == PATH_IGEMM_BF16;       // s1 / s2 then point to bf16 activations
-        if (bf16 && lp.x3) { C1 *= 3; C2 *= 3; }            // split-bf16: the K axis the kernel walks (g.C1 / g.C2)
-        RyIgemmParams p;
-        p.g = g; p.wt = bf16 ? (lp.x3 ? l.wigx3 : l.wig16) : l.wig; p.scale = l.scale; p.shift = l.shift;
-        p.x3 = lp.o16x3 ? 1 : 0;
-        p.splits = lp.splits; p.act = l.act; p.slope = slope;
-        p.slab_stride = (long long)B * lp.Ho * lp.Wo * l.cout;
-        // output rows start (2 x for the sub-pixel form) crop_lo rows into every image
-        const size_t oo = lp.crop_hi > 0 ? (size_t)(l.deconv ? 2 : 1) * lp.crop_lo * lp.Wo * l.cout : 0;
-        p.out = lp.splits > 1 ? lp.slabs + oo : (lp.w32 ? lp.out + oo : nullptr);
-        p.out16 = (lp.splits == 1 && lp.w16) ? lp.out16 + oo * (lp.o16x3 ? 2 : 1) : nullptr;
-        int bm, bn; tile_dims(lp.tile, &bm, &bn);
-        p.mtiles = (M + bm - 1) / bm; p.ntiles = l.cout / bn;
-        p.tw = 0;
-        for (int tw = 16; tw >= 4; tw >>= 1)           // 2-D M-tiles when the row grid divides evenly, else BM consecutive rows in raster order
-            if (bm % tw == 0 && g.Mw % tw == 0 && g.Mh % (bm / tw) == 0) { p.tw = tw; break; }
-        p.hole_ty = 1 << 30; p.hole_nt = 0;
-        if (lp.hole_n > 0) {                            // whole tile rows inside the stretch of identical padding rows are left out (ry_rep_rows fills them in)
-            const int th = p.tw > 0 ? bm / p.tw : 0;
-            if (p.tw == 0 || l.deconv || lp.splits != 1 || lp.crop_hi > 0 || lp.hole_lo % th || lp.hole_n % th || lp.hole_lo + lp.hole_n > g.Mh)
-                return fail(RY_ESTATE, "%s: rows %d..%d cannot be left out of this launch", l.name, lp.hole_lo, lp.hole_lo + lp.hole_n - 1);
-            p.hole_ty = lp.hole_lo / th; p.hole_nt = lp.hole_n / th;
-            p.mtiles -= B * p.hole_nt * (g.Mw / p.tw);
-        }
-        int patch = 0;
-        {   // prologue helpers of the LDS-DMA kernel (ry_fdiv reciprocals; operands stay below 2^24, checked here)
-            const int ck = bf16 ? 64 : 32, cpt = (C1 + C2) / ck, nkc = g.ntaps * cpt;
-            if ((long long)p.mtiles * p.ntiles * g.nphases * lp.splits >= (1 << 24) || M >= (1 << 24))
-                return fail(RY_EINVAL, "%s: more than 2^24 output rows or tiles in one launch; lower the batch", l.name);
-            p.inv_nphases = 1.f / g.nphases; p.inv_ntiles = 1.f / p.ntiles; p.inv_mtiles = 1.f / p.mtiles;
-            // XCD grouping: gm M-tile groups x gs slice groups (gm * gs = 8 L2s); every filter byte is fetched by gm L2s, every
-            // input byte by gs -- pick the split with the least L2 miss traffic among those that divide evenly
-            const int nsl = lp.splits * p.ntiles * g.nphases;
-            p.inv_nsl = 1.f / nsl;
-            p.xcd_gs = 0; p.xcd_gs_shift = 0; p.xcd_nsg = 1; p.xcd_mtg = 1; p.inv_xcd_nsg = 1.f;
-            {
-                const double wbytes = (double)g.nphases * l.cout * g.ntaps * (C1 + C2), abytes = (double)B * lp.Hi * lp.Wi * (C1 + C2);
-                double best = 1e300;
-                for (int sh = 0; sh <= 3; ++sh) {
-                    const int gs = 1 << sh, gm = 8 >> sh;
-                    if (nsl % gs != 0 || p.mtiles % gm != 0) continue;
-                    const double cost = gm * wbytes + gs * abytes;
-                    if (cost < best) { best = cost; p.xcd_gs = gs; p.xcd_gs_shift = sh; p.xcd_nsg = nsl / gs; p.xcd_mtg = p.mtiles / gm; }
-                }
-                if (p.xcd_gs) p.inv_xcd_nsg = 1.f / p.xcd_nsg;
-            }
-            p.inv_Mimg = 1.f / (float)(g.Mh * g.Mw); p.inv_Mw = 1.f / g.Mw; p.inv_cpt = 1.f / cpt; p.inv_kw = 1.f / g.kw;
-            p.tw_shift = 0; p.th = 1; p.tcols = 1; p.trows = 1; p.inv_tcols = 1.f; p.inv_trows = 1.f;
-            if (p.tw > 0) {
-                while ((1 << p.tw_shift) < p.tw) ++p.tw_shift;
-                p.th = bm / p.tw; p.tcols = g.Mw / p.tw; p.trows = g.Mh / p.th - p.hole_nt;
-                p.inv_tcols = 1.f / p.tcols; p.inv_trows = 1.f / p.trows;
-            }
-            // sub-pixel deconvolution on 16-pixel-wide 2-D tiles: the patch variant of the kernel (K units = whole channel chunks)
-            // 1: sub-pixel deconvolution, one patch per channel chunk; 2: k4 s2 p1 convolution, one patch per (chunk, input parity)
-            if (p.tw == 16 && (M >= 512 || lp.any_m_patch)) {   // small layers: the longer set-up costs more than the reuse saves (measured at M = 192)
-                if (g.ostride == 2 && (g_patch & 1) && lp.splits * lp.kg <= cpt) patch = 1;
-                else if (!l.deconv && l.k == 4 && l.stride == 2 && l.pad == 1 && l.dil == 1 && (g_patch & 2) && lp.splits * lp.kg <= 4 * cpt) patch = 2;
-            }
-            const int units = patch == 1 ? cpt : patch == 2 ? 4 * cpt : nkc;
-            p.kq = units / lp.splits; p.krem = units % lp.splits;
-        }
-        const int total_tiles = p.mtiles * p.ntiles * g.nphases * lp.splits;
-        dim3 grid((unsigned)(((total_tiles + 7) / 8) * 8));
-        RY_TRY(Lc.begin(tile_name(lp.tile, lp.kg, bf16, patch), l.name, lp.flops, lp.bytes, grid));
-    #define RY_IGEMM_LAUNCH(BM_, BN_, WM_, WN_)                                                                    \
-    do {                                                                                                    \
-        if (patch == 1 && lp.kg == 2) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 2, false, 1>), grid, 512, Lc.stream, p); \
-        else if (patch == 1) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 1, false, 1>), grid, 256, Lc.stream, p);          \
-        else if (patch == 2 && lp.kg == 2) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 2, false, 2>), grid, 512, Lc.stream, p); \
-        else if (patch == 2) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 1, false, 2>), grid, 256, Lc.stream, p);          \
-        else if (lp.kg == 2) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 2, false, 0>), grid, 512, Lc.stream, p);          \
-        else RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 1, false, 0>), grid, 256, Lc.stream, p);                          \
-    } while (0)
-#define RY_IGEMM16_LAUNCH(BM_, BN_, WM_, WN_)                                                                  \
-    do {                                                                                                    \
-        if (patch == 1 && lp.kg == 2) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 2, true, 1>), grid, 512, Lc.stream, p); \
-        else if (patch == 1) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 1, true, 1>), grid, 256, Lc.stream, p);          \
-        else if (patch == 2 && lp.kg == 2) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 2, true, 2>), grid, 512, Lc.stream, p); \
-        else if (patch == 2) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 1, true, 2>), grid, 256, Lc.stream, p);          \
-        else if (lp.kg == 2) RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 2, true, 0>), grid, 512, Lc.stream, p);          \
-        else RY_LAUNCH((ry_igemm_ldsdma<BM_, BN_, WM_, WN_, 1, true, 0>), grid, 256, Lc.stream, p);                          \
-    } while (0)
-        if (bf16) {
-            switch (lp.tile) {
-                case TILE_128x128: RY_IGEMM16_LAUNCH(128, 128, 2, 2); break;
-                case TILE_96x128: RY_IGEMM16_LAUNCH(96, 128, 1, 4); break;
-                case TILE_64x128: RY_IGEMM16_LAUNCH(64, 128, 1, 4); break;
-                case TILE_128x64: RY_IGEMM16_LAUNCH(128, 64, 4, 1); break;
-                default: RY_IGEMM16_LAUNCH(32, 128, 1, 4); break;
-            }
-#undef RY_IGEMM16_LAUNCH
-        } else
-        switch (lp.tile) {
-            case TILE_128x128: RY_IGEMM_LAUNCH(128, 128, 2, 2); break;
-            case TILE_64x128: RY_IGEMM_LAUNCH(64, 128, 1, 4); break;
-            case TILE_128x64: RY_IGEMM_LAUNCH(128, 64, 4, 1); break;
-            case TILE_96x128: RY_IGEMM_LAUNCH(96, 128, 1, 4); break;
-            default: RY_IGEMM_LAUNCH(32, 128, 1, 4); break;
-        }
-#undef RY_IGEMM_LAUNCH
-        RY_TRY(Lc.end());
-        if (p.hole_nt > 0) RY_TRY(launch_rep_rows(Lc, l, lp, B));
-        if (lp.splits > 1) RY_TRY(launch_reduce(Lc, l, lp, B, g.Ho, oo, p.slab_stride, slope));
-    } else if (lp.path == PATH_FIRST) {
+    if (lp.path == PATH_IGEMM || lp.path == PATH_IGEMM_BF16) return launch_igemm(Lc, l, lp, B, s1, C1, s2, C2, slope);
+    if (lp.path == PATH_FIRST) {
         RySrFirstParams p;
         p.x = s1; p.w = l.wdir; p.scale = l.scale; p.shift = l.shift; p.out16 = lp.w16 ? lp.out16 : nullptr;
         p.out = (lp.w32 || !p.out16) ? lp.out : nullptr;          // split-bf16 mode: the fp32 copy only if a consumer reads it
@@ -326,7 +313,10 @@ static int launch_conv2d(Launcher& Lc, const Layer& l, const LayerPlan& lp, int 
         RY_TRY(Lc.end());
     } else {
         RyDirectParams p;
-        p.g = g; p.wd = l.wdir; p.scale = l.scale; p.shift = l.shift; p.out = lp.out; p.act = l.act; p.slope = slope;
+        fill_geom(p.g, l, lp, B, s1, C1, s2, C2);
+        const RyConvGeom& g = p.g;
+        const int M = B * g.Mh * g.Mw;
+        p.wd = l.wdir; p.scale = l.scale; p.shift = l.shift; p.out = lp.out; p.act = l.act; p.slope = slope;
         const long long total = (long long)M * l.cout;
         dim3 grid((unsigned)((total + 255) / 256), (unsigned)g.nphases);
         RY_TRY(Lc.begin("ry_conv_direct", l.name, lp.flops, lp.bytes, grid));
@@ -462,9 +452,7 @@ static int enqueue_forward(ry_net* net, Plan& P, Launcher& Lc) {
     for (int i = 0; i < 16; ++i) crop[i] = crop0[i] = 0;
     int k0 = 0, k1 = P.n_frames;
     if (nd == 2 && P.mode == 1 && P.lp[15].path == PATH_LAST) {
-        k0 = P.disc_front < P.n_frames ? P.disc_front : 0;
-        k1 = P.n_frames - P.disc_back > k0 ? P.n_frames - P.disc_back : P.n_frames;
-        if (k1 <= k0) { k0 = 0; k1 = P.n_frames; }
+        keep_rows(P.n_frames, P.disc_front, P.disc_back, &k0, &k1);
     }
     if (nd == 2 && P.mode == 1 && g_s2_crop && P.lp[15].path == PATH_LAST && net->layers[15].src_a == 14) {
         int need0 = k0 > 0 ? k0 - 1 : 0, need1 = k1 + 1;             // correct rows [need0, need1) wanted from layer i's output
@@ -514,11 +502,10 @@ static int enqueue_forward(ry_net* net, Plan& P, Launcher& Lc) {
             a = (a + l.pad + l.stride - 1) / l.stride; b = top / l.stride;
             if (b >= lp.Ho) b = lp.Ho - 1;
             if (b - a < 1) break;
-            if ((lp.path != PATH_IGEMM && lp.path != PATH_IGEMM_BF16 && lp.path != PATH_WINO) || (lp.splits != 1 && lp.path != PATH_WINO) || crop[i] > 0 || (lp.Wo * l.cout) % 8) continue;
-            int th = 1, tw = 0;
-            if (!plan_tile_rows(lp, lp.Ho, lp.Wo, &th, &tw) || (lp.path != PATH_WINO && tw != 16)) continue;
+            int th = 1;
+            if (!plan_tile_rows(lp, lp.Ho, lp.Wo, &th)) continue;
             const int r0 = (a + 1 + th - 1) / th * th, r1 = (b + 1) / th * th;      // rows [r0, r1) are whole tile rows and copies of row r0 - 1 >= a
-            if (r1 - r0 >= th) { hole_lo[i] = r0; hole_n[i] = r1 - r0; }
+            if (r1 - r0 >= th && plan_hole_ok(l, lp, r0, r1 - r0)) { hole_lo[i] = r0; hole_n[i] = r1 - r0; }
         }
     }
     for (int i = lo; i < hi; ++i) {

@@ -219,6 +219,13 @@ struct LayerPlan {
     double flops_exec = 0;                    // MFMA flops the launch executes when they differ from the algorithmic ones (Winograd: 9 / 16); 0 = the same
 };
 
+// Rows [k0, k1) of an n_frames window that are kept when the caller throws away its first disc_front / last disc_back frames (discards that
+// would leave nothing keep every row)
+inline void keep_rows(int n_frames, int disc_front, int disc_back, int* k0, int* k1) {
+    *k0 = disc_front < n_frames ? disc_front : 0;
+    *k1 = n_frames - disc_back > *k0 ? n_frames - disc_back : n_frames;
+}
+
 struct Plan {
     int B = 0, T = 0;
     int mode = 0;                             // 0 = forward, 1 = convert wrapper

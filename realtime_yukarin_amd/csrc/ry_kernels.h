@@ -15,6 +15,9 @@
 //                       (the bf16 form also runs the split-bf16 mode: sources [pixel][hi | lo], K axis [hi | lo | hi] against
 //                       filters [w_hi | w_hi | w_lo] = three bf16 products per fp32 product, fp32 accumulate -- DESIGN.md 5.1)
 //                       (a hole of whole tile rows can be left out of the grid: the encoder's padding rows that equal the row above, copied by ry_rep_rows)
+//   ry_wino_ldsdma      the k4 s2 p1 stage-2 layers in Winograd F(2x2, 2x2) form on v_mfma_f32_32x32x2_f32 (9 / 16 of the direct form's MFMA work);
+//                       shares with ry_igemm_ldsdma the tile schedule (RyTileSched: ry_tile_decode / ry_tile_pos / ry_split_range) and the
+//                       32 x 32 epilogue (ry_tile_epilogue)
 //   ry_c2d_os           stage-2 layers with a handful of output pixels and megabytes of filters, output-stationary on v_mfma_f32_4x4x1_16B_f32
 //                       (sixteen K positions per instruction): one node per layer, no slabs; pixels by LDS-DMA with explicit waits
 //   ry_c1d_os           stage-1 layer, output-stationary: lanes over the input channels, every load before the first FMA, DPP reduce-scatter
@@ -110,29 +113,129 @@ struct RyConvGeom {
     signed char pdy[4], pdx[4];
 };
 
+// ---------------------------------------------------------------------------------------------
+// What the two stage-2 GEMM kernels (ry_igemm_ldsdma, ry_wino_ldsdma) share: the tile schedule of the 1-D grid, the 2-D M-tile position, the K
+// split and the epilogue of a 32 x 32 accumulator tile.  The host fills RyTileSched in one place (ry_exec.cpp, fill_sched).
+// ---------------------------------------------------------------------------------------------
+struct RyTileSched {
+    int mtiles, ntiles, splits;  // logical tile id = ((split * mtiles + mt) * ntiles + nt) * nphases + phase; a slice is (split, N-tile, phase)
+    // XCD grouping: gs slice groups of xcd_nsg slices x 8 / gs M-tile groups of xcd_mtg tiles (xcd_gs = gs; 0 = contiguous runs per XCD)
+    int xcd_gs, xcd_gs_shift, xcd_nsg, xcd_mtg;
+    float inv_xcd_nsg, inv_nsl, inv_nphases, inv_ntiles;   // reciprocals for ry_fdiv (nsl = splits * ntiles * nphases)
+    int kq, krem;               // K units per split: split s takes kq + (s < krem) units starting at s * kq + min(s, krem)
+    // 2-D M-tiles: tile rows hole_ty .. hole_ty + hole_nt - 1 of every image are not computed (`trows` counts the computed ones): rows of the
+    // padding that equal the row above them, filled in by ry_rep_rows (hole_nt = 0: none)
+    int hole_ty, hole_nt;
+    int tcols, trows;           // 2-D M-tiles per row of the grid, computed tile rows per image
+    float inv_tcols, inv_trows;
+};
+
+// Workgroup blockIdx.x -> (M-tile mt, phase, split, N-tile nt); false: an idle workgroup (the grid is rounded up to whole XCD rounds).
+// Workgroup b runs on XCD b % 8 (one L2 each).  A tile is (M-tile mt, filter slice sl = (split, N-tile, phase)): M-tiles share filters, slices
+// share input pixels.  The host splits the 8 XCDs into gm x gs groups (xcd_gs = gs) so that the L2 miss traffic gm * (filter bytes) + gs * (input
+// bytes) is smallest: XCD (xm, xs) owns M-tile block xm and slice block xs.
+RY_DEV bool ry_tile_decode(const RyTileSched& s, int nphases, int& mt, int& phase, int& split, int& nt) {
+    int sl;
+    if (s.xcd_gs > 0) {
+        const int xcd = (int)blockIdx.x & 7, j = (int)blockIdx.x >> 3;
+        const int xm = xcd >> s.xcd_gs_shift, xs = xcd & (s.xcd_gs - 1);
+        const int mtl = ry_fdiv(j, s.xcd_nsg, s.inv_xcd_nsg);
+        if (mtl >= s.xcd_mtg) return false;
+        mt = xm * s.xcd_mtg + mtl;
+        sl = xs * s.xcd_nsg + (j - mtl * s.xcd_nsg);
+    } else {                                               // no even split: contiguous runs of (mt, slice) pairs per XCD, the slice fastest
+        const int total_tiles = s.splits * s.mtiles * s.ntiles * nphases;
+        const int per_xcd = (total_tiles + 7) >> 3;
+        const int lid = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
+        if (lid >= total_tiles) return false;
+        const int nsl = s.splits * s.ntiles * nphases;
+        mt = ry_fdiv(lid, nsl, s.inv_nsl);
+        sl = lid - mt * nsl;
+    }
+    const int q = ry_fdiv(sl, nphases, s.inv_nphases);
+    phase = sl - q * nphases;
+    split = ry_fdiv(q, s.ntiles, s.inv_ntiles);
+    nt = q - split * s.ntiles;
+    return true;
+}
+
+// 2-D M-tile mt -> image b, tile row ty (the rows left out of the grid skipped), tile column tx
+RY_DEV void ry_tile_pos(const RyTileSched& s, int mt, int& b, int& ty, int& tx) {
+    const int trow = ry_fdiv(mt, s.tcols, s.inv_tcols);    // tile row counted over the whole batch
+    tx = mt - trow * s.tcols;
+    b = ry_fdiv(trow, s.trows, s.inv_trows);
+    const int tyc = trow - b * s.trows;
+    ty = tyc + (tyc >= s.hole_ty ? s.hole_nt : 0);
+}
+
+// K range of a split: `n` units starting at `begin`
+RY_DEV void ry_split_range(const RyTileSched& s, int split, int& begin, int& n) {
+    begin = split * s.kq + (split < s.krem ? split : s.krem);
+    n = s.kq + (split < s.krem ? 1 : 0);
+}
+
+// Epilogue of one 32 x 32 accumulator tile, v[r] = (row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31) as v_mfma_f32_32x32 leaves it:
+// folded BN (sc / sh of this lane's column) + activation when the launch is final, then the tile is transposed through the wave's 4-KiB LDS
+// scratch T so that a lane holds 4 consecutive channels of one pixel: 4 x 16-byte stores per tile instead of 16 x 4-byte ones, one row lookup
+// per store.  (The scalar-store epilogue was ~60 instructions per store and ~10 us of a 125 us layer: all workgroups reach it together.)
+// Tile row r goes to pixel rows[r] + dpix (rows[r] < 0: nowhere), channels nbase .. nbase + 31 of N.  COPY16: out may be null for a final
+// launch, and a final launch also writes the bf16 copy out16 (x3: split-bf16 [pixel][hi | lo]) when it is not null.
+template <bool COPY16>
+RY_DEV void ry_tile_epilogue(float (&v)[16], float* T, int lane, bool final_, float sc, float sh, int act, float slope, const int* rows, int dpix,
+                             int N, int nbase, float* out, unsigned short* out16, int x3) {
+    const int lr = lane & 31, lh = lane >> 5;
+    const int erow = lane >> 3, eslot = lane & 7;            // store role: row erow + 8 q of the tile, channels 4 eslot .. + 3
+    if (final_) {
+        if (act == RY_ACT_LRELU) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { const float x = fmaf(v[r], sc, sh); v[r] = x >= 0.f ? x : x * slope; }
+        } else if (act == RY_ACT_RELU) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { const float x = fmaf(v[r], sc, sh); v[r] = x > 0.f ? x : 0.f; }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) v[r] = fmaf(v[r], sc, sh);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+        T[row * 32 + ((((lr >> 2) ^ (row & 7)) << 2) | (lr & 3))] = v[r];
+    }
+    ry_wave_sync();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int row = erow + 8 * q;
+        const f32x4 o = ry_ld4(T + row * 32 + ((eslot ^ (row & 7)) << 2));
+        const int ob = rows[row];
+        if (ob >= 0) {
+            const size_t pix = (size_t)(ob + dpix);
+            const size_t oi = pix * N + nbase + eslot * 4;
+            if (!COPY16 || !final_ || out) ry_st4(out + oi, o);
+            if (COPY16 && final_ && out16) {
+                if (x3) ry_st4_bf16_x3(out16, pix, N, nbase + eslot * 4, o);
+                else ry_st4_bf16(out16 + oi, o);
+            }
+        }
+    }
+    ry_wave_sync();
+}
+
 struct RyIgemmParams {
     RyConvGeom g;
+    RyTileSched s;              // K units: channel chunks x taps, or whole patches (PATCH)
     const float* wt;            // [phase][N/64][tap][(C1+C2)/32][64][32]: every (64 couts x 32 k) chunk is one contiguous 8 KB block
     const float* scale;         // [N] folded BN scale (1 when no BN)
     const float* shift;         // [N] folded bias/BN shift
     float* out;                 // splits==1: NHWC output (may be null when only out16 is wanted); else slabs [split][B*Ho*Wo][N] of raw sums
     unsigned short* out16;      // splits==1: optional bf16 copy of the activated output (consumers on the bf16 path), else unused
     int x3;                     // out16 format: 0 = [pixel][N] bf16; 1 = split-bf16 [pixel][hi (N) | lo (N)], lo = bf16(v - hi)
-    int splits;
     int act;
     float slope;
     long long slab_stride;
-    int mtiles, ntiles;         // 1-D XCD-aware grid: logical id = ((split*mtiles + mt)*ntiles + nt)*nphases + phase
-    // host-side helpers of the LDS-DMA kernel's prologue (reciprocals for ry_fdiv, the 2-D tile grid, the K split)
-    float inv_nphases, inv_ntiles, inv_mtiles, inv_Mimg, inv_Mw, inv_cpt, inv_kw, inv_tcols, inv_trows;
-    int tw_shift, th, tcols, trows;   // 2-D M-tiles: tw = 1 << tw_shift columns x th rows, tcols x trows tiles per image
-    // LDS-DMA kernel: XCD grouping (gs slice groups of xcd_nsg slices x 8/gs M-tile groups of xcd_mtg tiles); 0 = contiguous runs
-    int xcd_gs, xcd_gs_shift, xcd_nsg, xcd_mtg;
-    float inv_xcd_nsg, inv_nsl; // reciprocals of xcd_nsg and of the slice count splits * ntiles * nphases
-    int kq, krem;               // K chunks per split: split s takes kq + (s < krem) chunks starting at s * kq + min(s, krem)
-    // 2-D M-tiles: tile rows hole_ty .. hole_ty + hole_nt - 1 of every image are not computed (`trows` counts the computed ones): rows of the
-    // padding that equal the row above them, filled in by ry_rep_rows (hole_nt = 0: none)
-    int hole_ty, hole_nt;
+    // host-side helpers of the prologue (reciprocals for ry_fdiv of the raster rows and of the taps)
+    float inv_Mimg, inv_Mw, inv_cpt, inv_kw;
+    int tw_shift, th;           // 2-D M-tiles: tw = 1 << tw_shift columns x th rows
     int tw;                     // > 0: an M-tile is a 2-D block of (BM/tw) x tw rows of the Mh x Mw grid (compact input footprint:
                                 //      overlapping taps hit L2); 0: BM consecutive rows in raster order
 };
@@ -193,31 +296,8 @@ RY_KERNEL(256 * KG, 2) void ry_igemm_ldsdma(RyIgemmParams p) {
 
     const RyConvGeom& g = p.g;
     const int tid = (int)threadIdx.x;
-    // Workgroup b runs on XCD b % 8 (one L2 each).  A tile is (M-tile mt, filter slice sl = (split, N-tile, phase)): M-tiles
-    // share filters, slices share input pixels.  The host splits the 8 XCDs into gm x gs groups (xcd_gs = gs) so that the L2
-    // miss traffic gm * (filter bytes) + gs * (input bytes) is smallest: XCD (xm, xs) owns M-tile block xm and slice block xs.
-    const int total_tiles = p.splits * p.mtiles * p.ntiles * p.g.nphases;
-    int mt, sl;
-    if (p.xcd_gs > 0) {
-        const int xcd = (int)blockIdx.x & 7, j = (int)blockIdx.x >> 3;
-        const int xm = xcd >> p.xcd_gs_shift, xs = xcd & (p.xcd_gs - 1);
-        const int mtl = ry_fdiv(j, p.xcd_nsg, p.inv_xcd_nsg);
-        if (mtl >= p.xcd_mtg) return;
-        mt = xm * p.xcd_mtg + mtl;
-        sl = xs * p.xcd_nsg + (j - mtl * p.xcd_nsg);
-    } else {                                               // no even split: contiguous runs of (mt, slice) pairs per XCD
-        const int per_xcd = (total_tiles + 7) >> 3;
-        const int lid = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
-        if (lid >= total_tiles) return;
-        const int nsl = p.splits * p.ntiles * p.g.nphases;
-        const int q0 = ry_fdiv(lid, nsl, p.inv_nsl);
-        const int msl = lid - q0 * nsl;                     // (mt, slice) with the slice fastest ...
-        sl = msl; mt = q0;                                  // ... = the old order for split-free launches
-    }
-    int q_ = ry_fdiv(sl, p.g.nphases, p.inv_nphases);
-    const int phase = sl - q_ * p.g.nphases; sl = q_;
-    const int split = ry_fdiv(sl, p.ntiles, p.inv_ntiles);
-    const int nt = sl - split * p.ntiles;
+    int mt, phase, split, nt;
+    if (!ry_tile_decode(p.s, g.nphases, mt, phase, split, nt)) return;
     const int m0 = mt * BM;
     const int n0 = nt * BN;
     const int Ctot = g.C1 + g.C2;
@@ -241,8 +321,8 @@ RY_KERNEL(256 * KG, 2) void ry_igemm_ldsdma(RyIgemmParams p) {
     const int cpt = Ctot / CK;
     // K ranges are counted in units of one chunk (PATCH: one patch = four taps, so that every K group starts at tap 0)
     constexpr int KU = PATCH != 0 ? 4 : 1;
-    const int kc_begin = split * p.kq + (split < p.krem ? split : p.krem);
-    const int wg_units = p.kq + (split < p.krem ? 1 : 0);
+    int kc_begin, wg_units;
+    ry_split_range(p.s, split, kc_begin, wg_units);
     const int g_begin = (kc_begin + (KG > 1 ? (wg_units >> 1) * grp : 0)) * KU;   // this K group's share: the first floor(n / 2) units, the rest
     const int nchunks = (KG > 1 ? (grp ? wg_units - (wg_units >> 1) : (wg_units >> 1)) : wg_units) * KU;
     const int max_chunks = ((wg_units + KG - 1) / KG) * KU;                // barrier count is the same for both groups
@@ -269,11 +349,8 @@ RY_KERNEL(256 * KG, 2) void ry_igemm_ldsdma(RyIgemmParams p) {
         bool live = m < M;
         int b = 0, ry = 0, rx = 0;
         if (p.tw > 0) {
-            const int trow = ry_fdiv(mt, p.tcols, p.inv_tcols);              // tile row counted over the whole batch
-            const int tx = mt - trow * p.tcols;
-            b = ry_fdiv(trow, p.trows, p.inv_trows);
-            const int tyc = trow - b * p.trows;
-            const int ty = tyc + (tyc >= p.hole_ty ? p.hole_nt : 0);
+            int ty, tx;
+            ry_tile_pos(p.s, mt, b, ty, tx);
             ry = ty * p.th + (r >> p.tw_shift); rx = tx * p.tw + (r & (p.tw - 1));
             live = b < g.B;
         } else if (live) {
@@ -299,11 +376,8 @@ RY_KERNEL(256 * KG, 2) void ry_igemm_ldsdma(RyIgemmParams p) {
         // patch pixel of this lane in each piece it fills: its input coordinates (ayb / axb; far outside the image for rows
         // past the patch or the batch) and its element offsets into the two sources; a fetch adds the uniform parity shift
         // (PATCH = 2) and tests the image borders -- misses are fetched from the zeroed tail of the source
-        const int trow = ry_fdiv(mt, p.tcols, p.inv_tcols);
-        const int tx = mt - trow * p.tcols;
-        const int bimg = ry_fdiv(trow, p.trows, p.inv_trows);
-        const int tyc = trow - bimg * p.trows;
-        const int ty = tyc + (tyc >= p.hole_ty ? p.hole_nt : 0);
+        int bimg, ty, tx;
+        ry_tile_pos(p.s, mt, bimg, ty, tx);
         // input pixel of patch (0, 0): deconvolution: taps reach one pixel up / left of the phase; convolution: the parity-(1, 1)
         // pixel 2 * (first output row / column of the tile)
         const int oy0 = PATCH == 1 ? ty * (BM / 16) + pdy - 1 : 2 * ty * (BM / 16);
@@ -584,15 +658,12 @@ RY_KERNEL(256 * KG, 2) void ry_igemm_ldsdma(RyIgemmParams p) {
         ry_wave_sync();                        // the epilogue reuses this wave's region as its transposition scratch
     }
 
-    // ---- epilogue: folded BN + activation in registers, then every 32 x 32 accumulator tile is transposed through a
-    // 4-KiB per-wave LDS scratch (the operand buffers are idle now) so that a lane holds 4 consecutive channels of one
-    // pixel: 4 x 16-byte stores per tile instead of 16 x 4-byte ones, one row lookup per store.  (The scalar-store
-    // epilogue was ~60 instructions per store and ~10 us of a 125 us layer: all workgroups reach it together.)
-    float* outp = p.out + (p.splits > 1 ? (size_t)split * (size_t)p.slab_stride : (size_t)0);
+    // ---- epilogue: folded BN + activation, every 32 x 32 accumulator tile transposed through a 4-KiB per-wave LDS scratch (the operand buffers
+    // are idle now), 16-byte stores ----
+    float* outp = p.out + (p.s.splits > 1 ? (size_t)split * (size_t)p.slab_stride : (size_t)0);
     float* T = (wave < 2 ? Bs0 : Bs1) + (wave & 1) * (KG > 1 ? TM * TN * 16 * 64 : 1024);
     static_assert(BN * BK >= 2048, "two waves' transposition scratch fits one B buffer");
-    const bool final_ = p.splits == 1;
-    const int erow = lane >> 3, eslot = lane & 7;            // store role: row erow + 8 q of the tile, channels 4 eslot .. + 3
+    const bool final_ = p.s.splits == 1;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int nbase = n0 + (wn * TN + j) * 32;
@@ -603,39 +674,7 @@ RY_KERNEL(256 * KG, 2) void ry_igemm_ldsdma(RyIgemmParams p) {
             float v[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] = acc[i][j][r];
-            if (final_) {
-                if (p.act == RY_ACT_LRELU) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { const float x = fmaf(v[r], sc, sh); v[r] = x >= 0.f ? x : x * p.slope; }
-                } else if (p.act == RY_ACT_RELU) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { const float x = fmaf(v[r], sc, sh); v[r] = x > 0.f ? x : 0.f; }
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) v[r] = fmaf(v[r], sc, sh);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                T[row * 32 + ((((lr >> 2) ^ (row & 7)) << 2) | (lr & 3))] = v[r];
-            }
-            ry_wave_sync();
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int row = erow + 8 * q;
-                const f32x4 o = ry_ld4(T + row * 32 + ((eslot ^ (row & 7)) << 2));
-                const int ob = rO[(wm * TM + i) * 32 + row];
-                if (ob >= 0) {
-                    const size_t oi = (size_t)ob * g.N + nbase + eslot * 4;
-                    if (!final_ || p.out) ry_st4(outp + oi, o);
-                    if (final_ && p.out16) {
-                        if (p.x3) ry_st4_bf16_x3(p.out16, (size_t)ob, g.N, nbase + eslot * 4, o);
-                        else ry_st4_bf16(p.out16 + oi, o);
-                    }
-                }
-            }
-            ry_wave_sync();
+            ry_tile_epilogue<true>(v, T, lane, final_, sc, sh, p.act, p.slope, rO + (wm * TM + i) * 32, 0, g.N, nbase, outp, p.out16, p.x3);
         }
     }
 }
@@ -664,23 +703,17 @@ RY_KERNEL(256 * KG, 2) void ry_igemm_ldsdma(RyIgemmParams p) {
 // ---------------------------------------------------------------------------------------------
 struct RyWinoParams {
     RyConvGeom g;               // src1 / src2, C1 / C2 (S1 = C1, S2 = C2), B, Hi, Wi, Hs, Ho, Wo, Hos, Mh, Mw, ostride, nphases, N, zoff1 / zoff2, pdy / pdx
+    RyTileSched s;              // K units: patches
     const float* wt;            // transformed filters (relayout_wino)
     const float* scale;
     const float* shift;
     float* out;                 // splits == 1: NHWC output; else slabs [split][B * Ho * Wo][N] of raw sums
-    int splits;
     int act;
     float slope;
     long long slab_stride;
-    int mtiles, ntiles;         // 1-D XCD-aware grid as ry_igemm_ldsdma: logical id = ((split * mtiles + mt) * ntiles + nt) * nphases + phase
     int mbw;                    // M-blocks per tile row: a tile is (WM / mbw) x mbw blocks of 8 x 16 pixels
-    int tcols, trows;           // M-tiles per row of the grid, computed tile rows per image
-    float inv_nphases, inv_ntiles, inv_tcols, inv_trows, inv_pw;
-    int xcd_gs, xcd_gs_shift, xcd_nsg, xcd_mtg;
-    float inv_xcd_nsg, inv_nsl;
+    float inv_pw;
     int npatches;               // K axis in patches of 16 channels (MODE 2: x 4 parities, parity fastest)
-    int kq, krem;               // patches per split: split s takes kq + (s < krem) patches starting at s * kq + min(s, krem)
-    int hole_ty, hole_nt;       // as RyIgemmParams
 };
 
 template <int WM, int WN, int NSL, int MODE>
@@ -707,27 +740,8 @@ RY_KERNEL(64 * WM * WN, 2) void ry_wino_ldsdma(RyWinoParams p) {
 
     const RyConvGeom& g = p.g;
     const int tid = (int)threadIdx.x;
-    const int total_tiles = p.splits * p.mtiles * p.ntiles * g.nphases;
-    int mt, sl;
-    if (p.xcd_gs > 0) {                                    // XCD (xm, xs) owns M-tile block xm and slice block xs (see ry_igemm_ldsdma)
-        const int xcd = (int)blockIdx.x & 7, j = (int)blockIdx.x >> 3;
-        const int xm = xcd >> p.xcd_gs_shift, xs = xcd & (p.xcd_gs - 1);
-        const int mtl = ry_fdiv(j, p.xcd_nsg, p.inv_xcd_nsg);
-        if (mtl >= p.xcd_mtg) return;
-        mt = xm * p.xcd_mtg + mtl;
-        sl = xs * p.xcd_nsg + (j - mtl * p.xcd_nsg);
-    } else {
-        const int per_xcd = (total_tiles + 7) >> 3;
-        const int lid = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
-        if (lid >= total_tiles) return;
-        const int nsl = p.splits * p.ntiles * g.nphases;
-        mt = ry_fdiv(lid, nsl, p.inv_nsl);
-        sl = lid - mt * nsl;
-    }
-    int q_ = ry_fdiv(sl, g.nphases, p.inv_nphases);
-    const int phase = sl - q_ * g.nphases; sl = q_;
-    const int split = ry_fdiv(sl, p.ntiles, p.inv_ntiles);
-    const int nt = sl - split * p.ntiles;
+    int mt, phase, split, nt;
+    if (!ry_tile_decode(p.s, g.nphases, mt, phase, split, nt)) return;
     const int n0 = nt * (32 * WN);
     const int pdy = MODE == 1 ? (phase >> 1) : 0, pdx = MODE == 1 ? (phase & 1) : 0;
 
@@ -738,11 +752,11 @@ RY_KERNEL(64 * WM * WN, 2) void ry_wino_ldsdma(RyWinoParams p) {
     const int PW = 2 * TTW + 1, PH = 2 * TTH + 1, NE = TTW + 1;   // patch size in pixels; even columns per patch row
 
     // K range of this workgroup, in patches and in iterations
-    const int pbeg = split * p.kq + (split < p.krem ? split : p.krem);
-    const int npat = p.kq + (split < p.krem ? 1 : 0);
+    int pbeg, npat;
+    ry_split_range(p.s, split, pbeg, npat);
     const int nit = npat * (2 / NSL);
     // filters of this (phase, N-tile): consecutive slices are consecutive runs of BSL floats
-    const float* wt_it = p.wt + ((size_t)(phase * p.ntiles + nt) * (size_t)(2 * p.npatches) + (size_t)(2 * pbeg)) * BSL;
+    const float* wt_it = p.wt + ((size_t)(phase * p.s.ntiles + nt) * (size_t)(2 * p.npatches) + (size_t)(2 * pbeg)) * BSL;
     auto b_item = [&](int j, float* Bd) {
         const int gi = j * NW + wave;
         // (uniform base + 32-bit lane offset: the scalar-base addressing mode)
@@ -755,11 +769,8 @@ RY_KERNEL(64 * WM * WN, 2) void ry_wino_ldsdma(RyWinoParams p) {
     }
 
     // ---- the M-tile ----
-    const int trow = ry_fdiv(mt, p.tcols, p.inv_tcols);
-    const int txt = mt - trow * p.tcols;
-    const int bimg = ry_fdiv(trow, p.trows, p.inv_trows);
-    const int tyc = trow - bimg * p.trows;
-    const int tyt = tyc + (tyc >= p.hole_ty ? p.hole_nt : 0);
+    int bimg, tyt, txt;
+    ry_tile_pos(p.s, mt, bimg, tyt, txt);
     const int ry0 = tyt * (2 * TTH), rx0 = txt * (2 * TTW);          // first row / column of the tile on the stencil's output grid
     if (tid < WM * 32) {                                    // output pixel of (a, b) = (0, 0) of every Winograd tile (epilogue)
         const int blk = tid >> 5, lr_ = tid & 31;
@@ -935,11 +946,10 @@ RY_KERNEL(64 * WM * WN, 2) void ry_wino_ldsdma(RyWinoParams p) {
         if (k + 3 < nit) run_it(RyConst<3>(), k + 3);
     }
 
-    // ---- epilogue: Y = A^T M A per lane, folded BN + activation, 32 x 32 transposition through a 4-KiB per-wave scratch, 16-byte stores ----
-    float* outp = p.out + (p.splits > 1 ? (size_t)split * (size_t)p.slab_stride : (size_t)0);
+    // ---- epilogue: Y = A^T M A per lane, then ry_tile_epilogue per output position (a, b) of the Winograd tiles ----
+    float* outp = p.out + (p.s.splits > 1 ? (size_t)split * (size_t)p.slab_stride : (size_t)0);
     float* T = Bs0 + wave * 1024;
-    const bool final_ = p.splits == 1;
-    const int erow = lane >> 3, eslot = lane & 7;
+    const bool final_ = p.s.splits == 1;
     const int nbase = n0 + wn * 32;
     float sc = 1.f, sh = 0.f;
     if (final_) { sc = p.scale[nbase + lr]; sh = p.shift[nbase + lr]; }
@@ -954,33 +964,8 @@ RY_KERNEL(64 * WM * WN, 2) void ry_wino_ldsdma(RyWinoParams p) {
             const float bot = acc[3 * a + 3 + b][r] + acc[3 * a + 3 + b + 1][r];
             v[r] = top + bot;
         }
-        if (final_) {
-            if (p.act == RY_ACT_LRELU) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { const float x = fmaf(v[r], sc, sh); v[r] = x >= 0.f ? x : x * p.slope; }
-            } else if (p.act == RY_ACT_RELU) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { const float x = fmaf(v[r], sc, sh); v[r] = x > 0.f ? x : 0.f; }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) v[r] = fmaf(v[r], sc, sh);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-            T[row * 32 + ((((lr >> 2) ^ (row & 7)) << 2) | (lr & 3))] = v[r];
-        }
-        ry_wave_sync();
         const int dpix = (a * g.Wo + b) * g.ostride;             // output pixel of (a, b) relative to (0, 0) of the tile
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int row = erow + 8 * q;
-            const f32x4 o = ry_ld4(T + row * 32 + ((eslot ^ (row & 7)) << 2));
-            const int ob = rO[wm * 32 + row];
-            if (ob >= 0) ry_st4(outp + (size_t)(ob + dpix) * g.N + nbase + eslot * 4, o);
-        }
-        ry_wave_sync();
+        ry_tile_epilogue<false>(v, T, lane, final_, sc, sh, p.act, p.slope, rO + wm * 32, dpix, g.N, nbase, outp, nullptr, 0);
     }
 }
 

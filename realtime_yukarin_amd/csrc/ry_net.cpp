@@ -240,8 +240,8 @@ static int convert_common(ry_net* net, int want_ndim, const float* x, float* y, 
     P->disc_front = disc_front; P->disc_back = disc_back;
     RY_TRY(run_plan(net, *P, x, y, on_device));
     if (!on_device && want_ndim == 2 && (disc_front > 0 || disc_back > 0)) {       // host arrays: the rows that were not computed come back as zeros
-        const int k0 = disc_front < n_frames ? disc_front : 0;
-        const int k1 = n_frames - disc_back > k0 ? n_frames - disc_back : n_frames;
+        int k0, k1;
+        keep_rows(n_frames, disc_front, disc_back, &k0, &k1);
         const size_t cols = (size_t)net->desc.width + 1;
         for (int b = 0; b < batch; ++b) {
             float* yb = y + (size_t)b * n_frames * cols;

@@ -623,7 +623,8 @@ static int ensure_wwin(ry_net* net, int i, const float** out) {
     return RY_OK;
 }
 
-// rows of the 2-D pixel tiles a layer's launch walks (the dead-row crop and the copied padding rows round to whole tile rows); false: raster tiles
+// The 2-D pixel tiles a stage-2 GEMM layer's launch walks over its Mh x Mw grid: th rows x tw columns (the launchers take them from here; the
+// dead-row crop and the copied padding rows round to whole tile rows); false: raster tiles (the implicit GEMM) / no Winograd tile fits
 bool plan_tile_rows(const LayerPlan& lp, int Mh, int Mw, int* th, int* tw_out) {
     if (lp.path == PATH_WINO) {
         int tw; wino_tile_hw(lp.wino_cfg, lp.wino_mbw, th, &tw);
@@ -634,6 +635,17 @@ bool plan_tile_rows(const LayerPlan& lp, int Mh, int Mw, int* th, int* tw_out) {
     for (int tw = 16; tw >= 4; tw >>= 1)
         if (bm % tw == 0 && Mw % tw == 0 && Mh % (bm / tw) == 0) { *th = bm / tw; if (tw_out) *tw_out = tw; return true; }
     return false;
+}
+
+// May the launch of this layer leave output rows [lo, lo + n) out of its grid (ry_rep_rows fills them with copies of row lo - 1)?  Whole tile
+// rows of a convolution launched whole (no crop), 16-byte rows for the copy; the implicit GEMM: 16-pixel-wide tiles and no external split (the
+// Winograd launch runs its reduce before the copies).  The planner picks holes by this rule (enqueue_forward), the launchers assert it.
+bool plan_hole_ok(const Layer& l, const LayerPlan& lp, int lo, int n) {
+    const bool igemm = lp.path == PATH_IGEMM || lp.path == PATH_IGEMM_BF16;
+    if ((!igemm && lp.path != PATH_WINO) || (igemm && lp.splits != 1) || l.deconv || lp.crop_hi > 0 || (lp.Wo * l.cout) % 8) return false;
+    int th = 1, tw = 0;
+    if (!plan_tile_rows(lp, lp.Ho, lp.Wo, &th, &tw) || (igemm && tw != 16)) return false;
+    return n > 0 && lo >= 1 && lo % th == 0 && n % th == 0 && lo + n <= lp.Ho;
 }
 
 // ------------------------------------------------------------------------------------------------

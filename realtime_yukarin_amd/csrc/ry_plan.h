@@ -51,8 +51,6 @@ static void relayout_wino(const Layer& l, F w, std::vector<float>& out) {
 // from there (RyConvGeom::zoff1 / zoff2); nothing ever writes them.
 // (round 5: a whole zeroed PIXEL of up to 2048 channels -- ry_c2d_os fetches out-of-image taps from it at any channel offset)
 static const size_t ZTAIL = 2048;
-// bit 0 = input-patch reuse in the deconvolution layers, bit 1 = in the k4 s2 convolution layers (DESIGN.md 5.1 + section 9: A/B measured, both on)
-static const int g_patch = 3;
 
 // ---- stage-2 output-stationary layers (ry_c2d_os) ----
 // (MT4, NT4, WAVES, DEPTH): tile of 4 MT4 rows x 4 NT4 output channels per workgroup, WAVES waves that deal the K units among them in rounds
@@ -105,6 +103,7 @@ int c1d_mode(const Layer& l);
 int c1d_tile_len(int mode);
 int choose_splits_1d(const Layer& l, int B, int rows, int mode);
 bool plan_tile_rows(const LayerPlan& lp, int Mh, int Mw, int* th, int* tw_out = nullptr);
+bool plan_hole_ok(const Layer& l, const LayerPlan& lp, int lo, int n);
 int build_plan(ry_net* net, Plan& P);
 int autotune_plan(ry_net* net, Plan& P);
 int get_plan(ry_net* net, int B, int T, int mode, int n_frames, Plan** out);

@@ -180,12 +180,6 @@ static int vc_check(const ry_vc* vc, const int* row_of, int n_eff, int n_frames,
     return RY_OK;
 }
 
-// the rows of a window's spectrogram that are computed under the current ry_vc_set_discard (the same clipping as enqueue_forward)
-static void vc_keep_rows(const ry_vc* vc, int n_frames, int* k0, int* k1) {
-    *k0 = vc->disc_front < n_frames ? vc->disc_front : 0;
-    *k1 = n_frames - vc->disc_back > *k0 ? n_frames - vc->disc_back : n_frames;
-}
-
 extern "C" {
 
 int ry_vc_create(ry_net* s1, ry_net* s2, const float* mtx, int M, int F, ry_vc** out) {
@@ -289,7 +283,7 @@ int ry_vc_submit(ry_vc* vc, const float* x_eff, const int* row_of, int n_eff, in
     RT_TRY(rt::event_record(sl.ev_mid, st1));
     RT_TRY(rt::stream_wait_event(st2, sl.ev_mid));                                      // stage-2 starts when the spectrogram is ready
     RY_TRY(vc_run_stage2(vc, s2, sl.d_sp, sl.d_out, n_frames));
-    vc_keep_rows(vc, n_frames, &sl.k0, &sl.k1);
+    keep_rows(n_frames, vc->disc_front, vc->disc_back, &sl.k0, &sl.k1);     // the rows computed under ry_vc_set_discard
     RT_TRY(rt::d2h(sl.h_sp + (size_t)sl.k0 * F, sl.d_out + (size_t)sl.k0 * F, (size_t)(sl.k1 - sl.k0) * F * sizeof(float), st2));
     RT_TRY(rt::event_record(sl.ev_done, st2));
     sl.used = true; sl.ticket = t; sl.n_eff = n_eff; sl.n_frames = n_frames; sl.gated = false;
@@ -428,7 +422,7 @@ int ry_vc_submit_wave(ry_vc* vc, const float* wave, int n_samples, int hop, int 
     RT_TRY(rt::event_record(sl.ev_mid, st1));
     RT_TRY(rt::stream_wait_event(st2, sl.ev_mid));
     RY_TRY(vc_run_stage2(vc, s2, sl.d_sp, sl.d_out, n_frames));
-    vc_keep_rows(vc, n_frames, &sl.k0, &sl.k1);
+    keep_rows(n_frames, vc->disc_front, vc->disc_back, &sl.k0, &sl.k1);     // the rows computed under ry_vc_set_discard
     RT_TRY(rt::d2h(sl.h_sp + (size_t)sl.k0 * F, sl.d_out + (size_t)sl.k0 * F, (size_t)(sl.k1 - sl.k0) * F * sizeof(float), st2));
     RT_TRY(rt::event_record(sl.ev_done, st2));
     sl.used = true; sl.ticket = t; sl.n_eff = n_eff; sl.n_frames = n_frames; sl.gated = true;
@@ -619,7 +613,7 @@ int ry_vc_stage2_from_mc(ry_vc* vc, const int* row_of, int n_eff, int n_frames, 
     RT_TRY(rt::event_record(sl.ev_mid, vc->s1->stream));
     RT_TRY(rt::stream_wait_event(s2->stream, sl.ev_mid));
     int k0 = 0, k1 = n_frames;
-    vc_keep_rows(vc, n_frames, &k0, &k1);                       // ry_vc_set_discard: the rows the caller throws away are not computed
+    keep_rows(n_frames, vc->disc_front, vc->disc_back, &k0, &k1);   // ry_vc_set_discard: the rows the caller throws away are not computed
     const size_t F = (size_t)vc->F;
     RY_TRY(ry_sr_convert_rows(s2, sl.d_sp, sl.d_out, 1, n_frames, vc->disc_front, vc->disc_back, 1));
     RT_TRY(rt::d2h(sl.h_sp + (size_t)k0 * F, sl.d_out + (size_t)k0 * F, (size_t)(k1 - k0) * F * sizeof(float), s2->stream));
