@@ -639,7 +639,10 @@ int autotune_plan(ry_net* net, Plan& P) {
         if (rc != RY_OK) break;
         if (g_autotune_pick >= 0) best = g_autotune_pick < (int)cands.size() ? g_autotune_pick : (int)cands.size() - 1;   // tests: exercise the replacement
         const Cand& w = cands[best];
-        if (w.splits > 1 && w.splits > lp.splits) rc = P.arena.alloc(&lp.slabs, out_elems * (size_t)w.splits);
+        if (w.splits > 1 && w.splits > lp.splits) {
+            rc = P.arena.alloc(&lp.slabs, out_elems * (size_t)w.splits);
+            if (rc == RY_OK) rc = poison_fill(net->ctx, lp.slabs, out_elems * (size_t)w.splits);
+        }
         lp.tile = w.tile; lp.kg = w.kg; lp.splits = w.splits;
     }
     rt::event_destroy(e0); rt::event_destroy(e1);
@@ -846,6 +849,8 @@ int ry_conv1d(ry_ctx* ctx, const float* x, int B, int L, int Cin, const float* W
     RY_TRY(arena.alloc(&lp.raw, out_elems * lp.splits));
     const int Cy = act == RY_ACT_GLU ? Cout / 2 : Cout;
     RY_TRY(arena.alloc(&dy, (size_t)B * lp.Wo * Cy));
+    RY_TRY(poison_fill(ctx, lp.raw, out_elems * lp.splits));               // RY_POISON: what the launches leave unwritten reads as NaN
+    RY_TRY(poison_fill(ctx, dy, (size_t)B * lp.Wo * Cy));
     RT_TRY(rt::h2d(dx, x, (size_t)B * L * Cin * sizeof(float), ctx->stream));
     Launcher Lc{nullptr, ctx, ctx->stream, nullptr, nullptr};
     RySrc1d sa, sb;
@@ -964,6 +969,9 @@ int ry_conv2d_dilated(ry_ctx* ctx, const float* x, int B, int H, int Wd, int Cin
     float* dx = nullptr;
     RY_TRY(alloc_ztail(ctx, arena, &dx, (size_t)B * H * Wd * Cin));
     RY_TRY(arena.alloc(&lp.out, out_elems));
+    // RY_POISON: an output element or a slab row the launch leaves unwritten reads as NaN instead of the previous call's result
+    RY_TRY(poison_fill(ctx, lp.out, out_elems));
+    if (lp.splits > 1 && lp.slabs) RY_TRY(poison_fill(ctx, lp.slabs, out_elems * lp.splits));
     Launcher Lc{nullptr, ctx, ctx->stream, nullptr, nullptr};
     if (lp.path == PATH_LAST) {
         // exercise the un-materialised skip concat: the channels are handed over as two half-width sources

@@ -248,9 +248,16 @@ int prepare_layer(ry_ctx* ctx, Arena& arena, Layer& l, int ndim, float eps, cons
     return RY_OK;
 }
 
-// RY_POISON=1 (diagnostics): fresh activation buffers are filled with NaN patterns, so that a kernel that reads a row / pixel its producer
-// never wrote shows up as NaN in the result instead of depending on what the allocator handed out
+// RY_POISON=1 (diagnostics): fresh activation buffers, split-K slabs and the outputs of the single operators are filled with NaN patterns, so
+// that a kernel that reads a row / pixel its producer never wrote, or a launch that leaves an output element unwritten, shows up as NaN in the
+// result instead of depending on what the allocator handed out
 static int g_poison = 0;
+int poison_fill(ry_ctx* ctx, float* p, size_t nfloats) {
+    if (!g_poison || !p || !nfloats) return RY_OK;
+    RT_TRY(rt::dmemset(p, 0xFF, nfloats * sizeof(float), ctx->stream));
+    RT_TRY(rt::stream_sync(ctx->stream));
+    return RY_OK;
+}
 int alloc_ztail(ry_ctx* ctx, Arena& arena, float** p, size_t nfloats) {
     RY_TRY(arena.alloc(p, nfloats + ZTAIL));
     if (g_poison) RT_TRY(rt::dmemset(*p, 0xFF, nfloats * sizeof(float), ctx->stream));
@@ -767,7 +774,10 @@ int build_plan(ry_net* net, Plan& P) {
                         return fail(RY_EINVAL, "RY_WINO: no Winograd plan %d:%d:%d for %s", c[0], c[1], c[2], l.name);
                     }
                 }
-                if (lp.splits > 1) RY_TRY(P.arena.alloc(&lp.slabs, out_elems * lp.splits));
+                if (lp.splits > 1) {
+                    RY_TRY(P.arena.alloc(&lp.slabs, out_elems * lp.splits));
+                    RY_TRY(poison_fill(net->ctx, lp.slabs, out_elems * lp.splits));
+                }
             } else {
                 lp.path = PATH_DIRECT; lp.splits = 1;
                 if (!l.deconv && l.k == 3 && l.stride == 1 && l.pad == 1) {

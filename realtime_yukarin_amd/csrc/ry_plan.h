@@ -82,6 +82,7 @@ void relayout_igemm(const Layer& l, const float* W, std::vector<float>& out);
 bool wino_eligible(const Layer& l, int ndim);
 int prepare_layer(ry_ctx* ctx, Arena& arena, Layer& l, int ndim, float eps, const float* W, const float* b, const float* bn, bool want_os2 = false);
 int alloc_ztail(ry_ctx* ctx, Arena& arena, float** p, size_t nfloats);
+int poison_fill(ry_ctx* ctx, float* p, size_t nfloats);       // RY_POISON: NaN patterns over a buffer a launch is about to write (else nothing)
 void tile_dims(int tile, int* bm, int* bn);
 extern int g_s2_hole;
 extern int g_s2_crop;

@@ -342,3 +342,185 @@ def wino_properties(ctx, shape, transposed):
     e_eq = float(numpy.abs(ys[:, so + m:-m, so + m:-m] - y1[:, m:-so - m, m:-so - m]).max()) / scale
     e_split = float(numpy.abs(f(x1, splits=3) - y1).max()) / scale
     return e_aff, e_eq, e_split
+
+
+# ---- float64 reference with an element-wise error scale (tests/test_gemm_oracle.py) ----
+
+def ref_conv2d_f64(x, W, b, bn, stride, pad, transposed, act):
+    """The 2-D operator in float64 on the CPU: torch conv2d / conv_transpose2d, then the oracle's batch_norm_inference and apply_act.
+    x (B, H, W, Cin) channels-last; W (Cout, Cin, k, k), or (Cin, Cout, k, k) when transposed (the layouts of ops_numpy).
+    -> (r, bound), both (B, Ho, Wo, Cout) float64: bound = |s| (conv(|x|, |W|) + |b|) + |r| with s the folded BN scale (ReLU and leaky ReLU
+    are 1-Lipschitz), the scale against which any fp32 summation order of the same sum is judged element by element."""
+    import torch
+    f = torch.nn.functional.conv_transpose2d if transposed else torch.nn.functional.conv2d
+    xt = torch.from_numpy(numpy.ascontiguousarray(numpy.asarray(x, numpy.float64).transpose(0, 3, 1, 2)))
+    wt = torch.from_numpy(numpy.asarray(W, numpy.float64))
+    cout = W.shape[1] if transposed else W.shape[0]
+    bb = numpy.zeros(cout) if b is None else numpy.asarray(b, numpy.float64)
+    with torch.no_grad():
+        c = f(xt, wt, torch.from_numpy(bb), stride=stride, padding=pad).numpy()
+        ca = f(xt.abs(), wt.abs(), torch.from_numpy(numpy.abs(bb)), stride=stride, padding=pad).numpy()
+    if bn is not None:
+        bn64 = [numpy.asarray(v, numpy.float64) for v in bn]
+        c = ops.batch_norm_inference(c, *bn64)
+        s = numpy.abs(bn64[0] / numpy.sqrt(bn64[3] + ops.BN_EPS)).reshape(1, -1, 1, 1)
+    else:
+        s = 1.0
+    r = ops.apply_act(c, act)
+    bound = s * ca + numpy.abs(r)
+    return r.transpose(0, 2, 3, 1), bound.transpose(0, 2, 3, 1)
+
+
+def assert_close_elementwise(y, r, bound, tol, what=''):
+    """Every element of y within tol * bound of the float64 reference r, and no NaN / Inf.  -> the worst ratio |y - r| / bound."""
+    y = numpy.asarray(y, numpy.float64)
+    assert y.shape == r.shape == bound.shape, (what, y.shape, r.shape, bound.shape)
+    nonfinite = int((~numpy.isfinite(y)).sum())
+    ratio = numpy.abs(y - r) / numpy.maximum(bound, 1e-300)
+    ratio[~numpy.isfinite(y)] = numpy.inf
+    i = numpy.unravel_index(int(numpy.argmax(ratio)), ratio.shape)
+    worst = float(ratio[i])
+    assert nonfinite == 0 and worst <= tol, ('%s: worst |y - r| / bound = %.3g > %.3g at (b, h, w, c) = %s (y %r, r %r, bound %.3g); %d NaN / Inf elements'
+                                             % (what, worst, tol, tuple(int(v) for v in i), float(y[i]), float(r[i]), float(bound[i]), nonfinite))
+    return worst
+
+
+class poisoned(object):
+    """with poisoned(ctx, monkeypatch): RY_POISON=1 for the block -- every output, slab and activation buffer the library allocates starts as NaN
+    patterns, so an element the launch does not write in THIS call shows as NaN instead of a value left behind by an earlier call."""
+
+    def __init__(self, ctx, monkeypatch):
+        self.ctx, self.mp = ctx, monkeypatch
+
+    def __enter__(self):
+        self.mp.setenv('RY_POISON', '1'); self.ctx.reload_env()
+        return self
+
+    def __exit__(self, *exc):
+        self.mp.delenv('RY_POISON', raising=False); self.ctx.reload_env()
+        return False
+
+
+def trained_like_operands(rng, B, H, W_, Cin, Cout, k, transposed):
+    """Inputs behind a ReLU, filters ~ N(0, 0.02), bias ~ N(0, 0.1) and BatchNormalization statistics (conftest.bn_params)."""
+    from conftest import bn_params
+    x = numpy.maximum(rng.normal(size=(B, H, W_, Cin)), 0).astype('f4')
+    Wt = rng.normal(0, 0.02, size=(Cin, Cout, k, k) if transposed else (Cout, Cin, k, k)).astype('f4')
+    b = rng.normal(0, 0.1, Cout).astype('f4')
+    return x, Wt, b, bn_params(rng, Cout)
+
+
+# ---- which branches of the shared tile schedule a launch takes: labels for the case lists only, never used by a correctness assertion ----
+# A restatement of fill_sched (ry_exec.cpp): the XCD grouping xcd_gs of ry_tile_decode (0 = no even split), the K units per split kq / krem of
+# ry_split_range, and the M-tiles walked by ry_tile_pos (2-D tiles of th x tw pixels, or raster tiles of bm rows when tw = 0), for launches whose
+# tile and external split are forced (the planner's choices are not restated).
+
+def sched_of(case):
+    """case of the CONV2D_CASES form with path 'wino' (tile (cfg, mbw)) or 'igemm' (fp32; tile name), tile and splits given."""
+    B, H, W_, Cin, Cout, k, s, p, tr, act, path, tile, splits = case
+    assert tile is not None and splits > 0, case
+    Ho, Wo = (2 * H, 2 * W_) if tr else ((H + 2 * p - k) // s + 1, (W_ + 2 * p - k) // s + 1)
+    Mh, Mw = (H, W_) if tr else (Ho, Wo)
+    nphases, ntaps = (4, 4) if tr else (1, k * k)
+    if path == 'wino':
+        cfg, mbw = tile
+        wm = 2 if cfg == 1 else 4
+        th, tw = 8 * (wm // mbw), 16 * mbw
+        bm, ntiles = th * tw, Cout // 64
+        units = (1 if tr else 4) * (Cin // 16)
+        wbytes = 2.25 * nphases * Cout * 4.0 * Cin
+    else:
+        bm, bn = (int(v) for v in tile.split('k')[0].split('x'))
+        kg = 2 if tile.endswith('k2') else 1                     # (a forced split leaves the automatic K groups at one)
+        cpt = Cin // 32
+        nk = ntaps * cpt
+        if splits * kg > nk:
+            kg, splits = 1, min(splits, nk)
+        tw = next((t for t in (16, 8, 4) if bm % t == 0 and Mw % t == 0 and Mh % (bm // t) == 0), 0)
+        th = bm // tw if tw else 1
+        patch = 0
+        if tw == 16:
+            if tr and splits * kg <= cpt:
+                patch = 1
+            elif not tr and k == 4 and s == 2 and p == 1 and splits * kg <= 4 * cpt:
+                patch = 2
+        units = cpt if patch == 1 else 4 * cpt if patch == 2 else nk
+        ntiles = Cout // bn
+        wbytes = float(nphases * Cout * ntaps * Cin)
+    mtiles = B * (Mh // th) * (Mw // tw) if tw else -(-B * Mh * Mw // bm)
+    nsl = splits * ntiles * nphases
+    abytes = float(B * H * W_ * Cin)
+    gs, best = 0, 1e300
+    for sh in range(4):
+        g, gm = 1 << sh, 8 >> sh
+        if nsl % g or mtiles % gm:
+            continue
+        cost = gm * wbytes + g * abytes
+        if cost < best:
+            best, gs = cost, g
+    return dict(kernel=path, xcd_gs=gs, kq=units // splits, krem=units % splits, splits=splits, units=units, tw=tw, B=B,
+                ragged=(tw == 0 and (B * Mh * Mw) % bm != 0), mtiles=mtiles)
+
+
+def sched_branches(case):
+    """-> the set of schedule branches a case takes (see SCHED_BRANCHES)"""
+    q = sched_of(case)
+    out = {'xcd_gs=%d' % q['xcd_gs'], 'krem=0' if q['krem'] == 0 else 'krem>0'}
+    if q['splits'] == q['units']:
+        out.add('one unit per split')
+    if q['B'] == 2 and q['tw'] > 0:
+        out.add('batch 2 on 2-D tiles')
+    if q['ragged']:
+        out.add('ragged raster tile')
+    return out
+
+
+SCHED_BRANCHES = {'xcd_gs=0', 'xcd_gs=1', 'xcd_gs=2', 'xcd_gs=4', 'xcd_gs=8', 'krem=0', 'krem>0', 'one unit per split', 'batch 2 on 2-D tiles'}
+
+
+# The case lists of the schedule branches on the emulator (tests/test_gemm_oracle.py): every branch of fill_sched / ry_tile_decode / ry_split_range
+# for both LDS-DMA kernels, tile and external split forced (the labels of SCHED_BRANCHES come from sched_branches above)
+SCHED_WINO_CASES = [
+    (1, 8, 32, 16, 64, 4, 2, 1, True, 'relu', 'wino', (1, 2), 1),      # one patch, one split: contiguous runs per XCD (xcd_gs 0)
+    (1, 24, 32, 64, 64, 4, 2, 1, True, None, 'wino', (1, 2), 4),       # four patches over four splits: one unit per split, 3 tile rows, xcd_gs 8
+    (1, 16, 64, 16, 64, 4, 2, 1, False, 'lrelu', 'wino', (1, 2), 3),   # four (chunk, parity) patches over three splits: 2 + 1 + 1 (krem 1)
+    (2, 64, 64, 16, 64, 4, 2, 1, False, 'lrelu', 'wino', (1, 1), 1),   # batch 2, eight M-tiles: xcd_gs 1 (eight M-tile groups)
+    (1, 64, 64, 16, 64, 4, 2, 1, False, None, 'wino', (1, 1), 2),      # four M-tiles x two splits: xcd_gs 2
+    (1, 8, 64, 16, 64, 4, 2, 1, True, 'lrelu', 'wino', (1, 2), 1),     # two M-tiles x four phases: xcd_gs 4
+    (1, 8, 32, 16, 128, 4, 2, 1, True, 'lrelu', 'wino', (1, 2), 1),    # one M-tile, eight slices: xcd_gs 8
+    (2, 32, 64, 48, 64, 4, 2, 1, False, None, 'wino', (2, 2), 5),      # eight waves, batch 2, twelve patches over five splits (krem 2)
+    (2, 16, 32, 48, 128, 4, 2, 1, True, 'lrelu', 'wino', (2, 2), 2),   # eight waves, batch 2, three patches over two splits, xcd_gs 8
+    (1, 32, 16, 32, 64, 4, 2, 1, True, None, 'wino', (2, 1), 2),       # eight waves, 32 x 16 tile, one patch per split
+]
+SCHED_IGEMM_CASES = [
+    (1, 4, 8, 32, 64, 4, 2, 1, False, 'lrelu', 'igemm', '128x64', 3),  # 8 rows of one 128-row raster tile, 16 chunks over three splits (krem 1)
+    (1, 4, 32, 32, 128, 4, 2, 1, False, None, 'igemm', '32x128', 4),   # 2 x 16 tile, 4 (chunk, parity) patches over four splits: one unit per split
+    (2, 4, 8, 32, 128, 3, 1, 1, False, 'lrelu', 'igemm', '32x128', 1), # batch 2 on 4 x 8 tiles
+    (1, 4, 64, 32, 128, 3, 1, 1, False, 'lrelu', 'igemm', '32x128', 1),# eight 2 x 16 tiles: xcd_gs 1
+    (1, 4, 32, 32, 128, 3, 1, 1, False, None, 'igemm', '32x128', 2),   # four tiles x two splits of 9 taps (5 + 4): xcd_gs 2
+    (1, 4, 12, 32, 128, 3, 1, 1, False, 'lrelu', 'igemm', '32x128', 4),# 48 rows on two raster tiles (ragged), 9 taps over four splits: xcd_gs 4
+    (1, 4, 8, 32, 64, 4, 2, 1, False, None, 'igemm', '128x64', 8),     # one ragged raster tile x eight splits: xcd_gs 8
+    (2, 8, 16, 64, 128, 4, 2, 1, True, 'lrelu', 'igemm', '64x128', 2), # sub-pixel deconvolution, batch 2 on 4 x 16 tiles, two patches over two splits
+    (1, 6, 8, 64, 256, 4, 2, 1, True, None, 'igemm', '96x128k2', 3),   # two K groups x three splits, deconvolution on a ragged raster tile
+    (2, 16, 32, 64, 128, 4, 2, 1, False, 'lrelu', 'igemm', '96x128', 3),  # batch 2 on raster tiles that cross the image boundary, 32 chunks / 3
+]
+
+
+# the full-size layers of SYN-64 at the 300-frame window (T = 384) the GPU suite runs (tests/test_gpu_parity.py, tests/test_gemm_oracle.py)
+OS_FULL_SIZE = [          # the weight-streaming bottom, planner's slice (B, H, W, Cin, Cout, k, s, p, transposed, act, path, tile, splits)
+    (1, 6, 8, 512, 512, 4, 2, 1, False, 'lrelu', 'os', None, 0),          # encoder c7: 12 pixels, 16.8 MB of filters
+    (1, 12, 16, 512, 512, 4, 2, 1, False, 'lrelu', 'os', None, 0),        # encoder c6: 48 pixels
+    (1, 3, 4, 512, 512, 4, 2, 1, True, 'relu', 'os', None, 0),            # decoder c0
+    (1, 6, 8, 1024, 512, 4, 2, 1, True, 'relu', 'os', None, 0),           # decoder c1: two sources of 512 channels, 33.5 MB
+]
+
+WINO_FULL_SIZE = [        # the eight MFMA-bound layers, the planner's plan: B, H, W, Cin, Cout, transposed
+    (1, 384, 512, 64, 128, False), (1, 192, 256, 128, 256, False), (1, 96, 128, 256, 512, False), (1, 48, 64, 512, 512, False),      # encoder c1 .. c4
+    (1, 24, 32, 1024, 512, True), (1, 48, 64, 1024, 256, True), (1, 96, 128, 512, 128, True), (1, 192, 256, 256, 64, True),          # decoder c3 .. c6
+    (2, 48, 64, 1024, 256, True),                                                                                                     # two windows per call
+]
+
+X3_FULL_SIZE = [
+    (1, 48, 64, 1024, 256, 4, 2, 1, True, 'relu', None, 0),        # decoder c4 (planner's tile / splits)
+    (1, 96, 128, 256, 512, 4, 2, 1, False, 'relu', None, 0),       # encoder c3
+]

@@ -71,27 +71,24 @@ def test_conv2d_os_every_slice_gpu(gpu_ctx, one_round):
     assert not bad, bad
 
 
-OS_FULL_SIZE = [          # the weight-streaming bottom of SYN-64 at the 300-frame window, planner's slice (B, H, W, Cin, Cout, k, s, p, transposed, act, path, tile, splits)
-    (1, 6, 8, 512, 512, 4, 2, 1, False, 'lrelu', 'os', None, 0),          # encoder c7: 12 pixels, 16.8 MB of filters
-    (1, 12, 16, 512, 512, 4, 2, 1, False, 'lrelu', 'os', None, 0),        # encoder c6: 48 pixels
-    (1, 3, 4, 512, 512, 4, 2, 1, True, 'relu', 'os', None, 0),            # decoder c0
-    (1, 6, 8, 1024, 512, 4, 2, 1, True, 'relu', 'os', None, 0),           # decoder c1: two sources of 512 channels, 33.5 MB
-]
+OS_FULL_SIZE = cases.OS_FULL_SIZE
 
 
 @pytest.mark.parametrize('case', OS_FULL_SIZE, ids=lambda c: 'x'.join(str(v) for v in c))
-def test_conv2d_os_full_size_gpu(gpu_ctx, case):
+def test_conv2d_os_full_size_gpu(gpu_ctx, monkeypatch, case):
     """BASELINE layer sizes: against the implicit-GEMM path of the same operator (other summation order only: 1e-5) and, where the
-    numpy oracle finishes in seconds, against the oracle; run twice: deterministic."""
+    numpy oracle finishes in seconds, against the oracle; run twice: deterministic.  Outputs and slabs poisoned (RY_POISON): every element
+    of each result was written by its own call."""
     B, H, W_, Cin, Cout, k, s, p, tr, act, path, tile, splits = case
     rng = numpy.random.default_rng(31)
     x = rng.normal(size=(B, H, W_, Cin)).astype('f4')
     Wt = rng.normal(0, 0.02, size=(Cin, Cout, k, k) if tr else (Cout, Cin, k, k)).astype('f4')
     b = rng.normal(0, 0.1, Cout).astype('f4')
     bn = bn_params(rng, Cout)
-    y = gpu_ctx.conv2d(x, Wt, b, bn, stride=s, pad=p, transposed=tr, act=act, path='os', tile=tile)
-    y2 = gpu_ctx.conv2d(x, Wt, b, bn, stride=s, pad=p, transposed=tr, act=act, path='os', tile=tile)
-    yi = gpu_ctx.conv2d(x, Wt, b, bn, stride=s, pad=p, transposed=tr, act=act, path='igemm')
+    with cases.poisoned(gpu_ctx, monkeypatch):
+        y = gpu_ctx.conv2d(x, Wt, b, bn, stride=s, pad=p, transposed=tr, act=act, path='os', tile=tile)
+        y2 = gpu_ctx.conv2d(x, Wt, b, bn, stride=s, pad=p, transposed=tr, act=act, path='os', tile=tile)
+        yi = gpu_ctx.conv2d(x, Wt, b, bn, stride=s, pad=p, transposed=tr, act=act, path='igemm')
     assert numpy.array_equal(y, y2)
     assert rel_max(y, yi) < 1e-5
     if H * W_ <= 12:
@@ -116,25 +113,23 @@ def test_conv2d_wino_vs_direct_gpu(gpu_ctx, transposed):
 
 @pytest.mark.parametrize('shape,transposed', [((1, 96, 128, 512, 128), True), ((1, 48, 64, 1024, 256), True), ((1, 192, 256, 128, 256), False), ((2, 96, 128, 256, 512), False)],
                          ids=['decoder_c5', 'decoder_c4', 'encoder_c2', 'encoder_c3_two_windows'])
-def test_conv2d_wino_properties_full_size_gpu(gpu_ctx, shape, transposed):
+def test_conv2d_wino_properties_full_size_gpu(gpu_ctx, monkeypatch, shape, transposed):
     """Size-independent properties at BASELINE layer sizes (where the float64 oracle takes minutes): the Winograd operator is affine in its input, commutes
     with shifts of the image (every pixel then sits on another position of its 2 x 2 tile or on another tile) and does not depend on the external split
     beyond the summation order."""
-    e_aff, e_eq, e_split = cases.wino_properties(gpu_ctx, shape, transposed)
+    with cases.poisoned(gpu_ctx, monkeypatch):
+        e_aff, e_eq, e_split = cases.wino_properties(gpu_ctx, shape, transposed)
     assert e_aff < 1e-5 and e_eq < 1e-5 and e_split < 1e-5, (e_aff, e_eq, e_split)        # (four float32 results of K = 2048 .. 4096 products each: measured 1.5e-6 .. 3.2e-6)
 
 
-WINO_FULL_SIZE = [        # the eight MFMA-bound layers of SYN-64 at the 300-frame window (T = 384), the planner's plan: B, H, W, Cin, Cout, transposed
-    (1, 384, 512, 64, 128, False), (1, 192, 256, 128, 256, False), (1, 96, 128, 256, 512, False), (1, 48, 64, 512, 512, False),      # encoder c1 .. c4
-    (1, 24, 32, 1024, 512, True), (1, 48, 64, 1024, 256, True), (1, 96, 128, 512, 128, True), (1, 192, 256, 256, 64, True),          # decoder c3 .. c6
-    (2, 48, 64, 1024, 256, True),                                                                                                     # two windows per call
-]
+WINO_FULL_SIZE = cases.WINO_FULL_SIZE
 
 
 @pytest.mark.parametrize('case', WINO_FULL_SIZE, ids=lambda c: 'x'.join(str(v) for v in c))
-def test_conv2d_wino_full_size_gpu(gpu_ctx, case):
+def test_conv2d_wino_full_size_gpu(gpu_ctx, monkeypatch, case):
     """BASELINE layer sizes on trained-like magnitudes (inputs behind a ReLU, filters ~ N(0, 0.02), BatchNormalization): against the direct implicit
-    GEMM of the same operator (1e-5: the verdict's bar for the Winograd form), both workgroup shapes; run twice: deterministic."""
+    GEMM of the same operator (1e-5: the verdict's bar for the Winograd form), both workgroup shapes; run twice: deterministic.  Outputs and slabs
+    poisoned (RY_POISON): a tile the Winograd launch skipped cannot inherit the implicit GEMM's result of the previous call."""
     B, H, W_, Cin, Cout, tr = case
     rng = numpy.random.default_rng(61)
     x = numpy.maximum(rng.normal(size=(B, H, W_, Cin)), 0).astype('f4')
@@ -142,16 +137,17 @@ def test_conv2d_wino_full_size_gpu(gpu_ctx, case):
     b = rng.normal(0, 0.1, Cout).astype('f4')
     bn = bn_params(rng, Cout)
     kw = dict(stride=2, pad=1, transposed=tr, act='relu' if tr else 'lrelu')
-    yd = gpu_ctx.conv2d(x, Wt, b, bn, path='igemm', **kw)
-    for tile in (None, (1, 0), (2, 0)):
-        try:
-            y = gpu_ctx.conv2d(x, Wt, b, bn, path='wino', tile=tile, **kw)
-        except RuntimeError as e:                  # (no tile of that workgroup shape divides the grid: 24 x 32 has no 16-row tile of the eight-wave shape)
-            assert 'no Winograd plan' in str(e) and tile == (2, 0) and (H if tr else H // 2) % 16, (case, tile, e)
-            continue
-        y2 = gpu_ctx.conv2d(x, Wt, b, bn, path='wino', tile=tile, **kw)
-        assert numpy.array_equal(y, y2)
-        assert rel_max(y, yd) < 1e-5, (case, tile, rel_max(y, yd))
+    with cases.poisoned(gpu_ctx, monkeypatch):
+        yd = gpu_ctx.conv2d(x, Wt, b, bn, path='igemm', **kw)
+        for tile in (None, (1, 0), (2, 0)):
+            try:
+                y = gpu_ctx.conv2d(x, Wt, b, bn, path='wino', tile=tile, **kw)
+            except RuntimeError as e:                  # (no tile of that workgroup shape divides the grid: 24 x 32 has no 16-row tile of the eight-wave shape)
+                assert 'no Winograd plan' in str(e) and tile == (2, 0) and (H if tr else H // 2) % 16, (case, tile, e)
+                continue
+            y2 = gpu_ctx.conv2d(x, Wt, b, bn, path='wino', tile=tile, **kw)
+            assert numpy.array_equal(y, y2)
+            assert rel_max(y, yd) < 1e-5, (case, tile, rel_max(y, yd))
 
 
 def test_mfma_4x4x1_block_map_is_transpose_detecting(gpu_ctx):
@@ -161,10 +157,7 @@ def test_mfma_4x4x1_block_map_is_transpose_detecting(gpu_ctx):
     assert numpy.array_equal(y, ref)
 
 
-X3_FULL_SIZE = [
-    (1, 48, 64, 1024, 256, 4, 2, 1, True, 'relu', None, 0),        # decoder c4 of SYN-64 at the 300-frame window (planner's tile / splits)
-    (1, 96, 128, 256, 512, 4, 2, 1, False, 'relu', None, 0),       # encoder c3 at the same window
-]
+X3_FULL_SIZE = cases.X3_FULL_SIZE
 
 
 @pytest.mark.parametrize('case', cases.CONV2D_X3_CASES[:2] + X3_FULL_SIZE, ids=lambda c: 'x'.join(str(v) for v in c))
@@ -265,6 +258,7 @@ def test_stage2_dead_row_crop_is_bit_identical(syn64, gpu_ctx, monkeypatch, n_fr
     sp = synth.stage2_input(n_frames)[0]
     reread = lambda: gpu_ctx.reload_env()
     monkeypatch.setenv('RY_WINOGRAD', wino)                            # (round 6: in Winograd form -- the default -- and with the direct kernels)
+    monkeypatch.setenv('RY_POISON', '1')                               # every mode starts from NaN buffers: an uncomputed row cannot borrow the last mode's
     try:
         out, out3 = {}, []
         for mode in ('0', '1', '2'):
@@ -280,7 +274,7 @@ def test_stage2_dead_row_crop_is_bit_identical(syn64, gpu_ctx, monkeypatch, n_fr
             assert numpy.array_equal(o, out3[0]) and numpy.array_equal(o[2], o[0])
             assert float(numpy.abs(o[0] / out['0'] - 1).max()) < 1e-5          # a batch may run under another plan: summation order only
     finally:
-        monkeypatch.delenv('RY_S2_CROP', raising=False); monkeypatch.delenv('RY_WINOGRAD', raising=False)
+        monkeypatch.delenv('RY_S2_CROP', raising=False); monkeypatch.delenv('RY_WINOGRAD', raising=False); monkeypatch.delenv('RY_POISON', raising=False)
         reread(); n2.set_dtype('f32')
 
 
@@ -295,6 +289,7 @@ def test_stage2_identical_padding_rows_are_copied_bit_identical(syn64, gpu_ctx, 
     sp = synth.stage2_input(n_frames)[0]
     reread = lambda: gpu_ctx.reload_env()
     monkeypatch.setenv('RY_WINOGRAD', wino)                            # (round 6: in Winograd form -- the default -- and with the direct kernels)
+    monkeypatch.setenv('RY_POISON', '1')                               # every mode starts from NaN buffers: an uncomputed row cannot borrow the last mode's
     try:
         out, out3, grids = {}, {}, {}
         for mode in ('0', '1'):
@@ -326,7 +321,7 @@ def test_stage2_identical_padding_rows_are_copied_bit_identical(syn64, gpu_ctx, 
                 for layer in ('encoder/c1', 'encoder/c2'):
                     assert grids['1'][(layer, 'ry_wino_ldsdma')] < grids['0'][(layer, 'ry_wino_ldsdma')], (layer, grids)
     finally:
-        monkeypatch.delenv('RY_S2_HOLE', raising=False); monkeypatch.delenv('RY_WINOGRAD', raising=False)
+        monkeypatch.delenv('RY_S2_HOLE', raising=False); monkeypatch.delenv('RY_WINOGRAD', raising=False); monkeypatch.delenv('RY_POISON', raising=False)
         reread(); n2.set_dtype('f32')
 
 

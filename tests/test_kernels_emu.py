@@ -44,23 +44,27 @@ def test_conv2d_os_identity_rows_emu(emu_ctx):
 
 
 @pytest.mark.parametrize('case', cases.CONV2D_WINO_CASES, ids=lambda c: 'x'.join(str(v) for v in c))
-def test_conv2d_wino_emu(emu_ctx, case):
-    """the Winograd F(2x2, 2x2) kernel (ry_wino_ldsdma): patch layout + swizzle, in-register input transform, nine accumulator blocks, output transform"""
-    y, r = cases.run_conv2d(emu_ctx, numpy.random.default_rng(23), case, bn_params)
+def test_conv2d_wino_emu(emu_ctx, monkeypatch, case):
+    """the Winograd F(2x2, 2x2) kernel (ry_wino_ldsdma): patch layout + swizzle, in-register input transform, nine accumulator blocks, output transform
+    (output and slabs poisoned: every element is written by this call)"""
+    with cases.poisoned(emu_ctx, monkeypatch):
+        y, r = cases.run_conv2d(emu_ctx, numpy.random.default_rng(23), case, bn_params)
     assert rel_max(y, r) < 1e-5
 
 
 @pytest.mark.parametrize('transposed', [True, False])
-def test_conv2d_wino_vs_direct_emu(emu_ctx, transposed):
-    err, scale = cases.wino_vs_direct(emu_ctx, transposed)
+def test_conv2d_wino_vs_direct_emu(emu_ctx, monkeypatch, transposed):
+    with cases.poisoned(emu_ctx, monkeypatch):
+        err, scale = cases.wino_vs_direct(emu_ctx, transposed)
     assert err < 1e-5 and scale > 0.1, (err, scale)
 
 
 @pytest.mark.parametrize('transposed', [True, False])
-def test_conv2d_wino_properties_emu(emu_ctx, transposed):
+def test_conv2d_wino_properties_emu(emu_ctx, monkeypatch, transposed):
     """affinity, shift equivariance and split invariance of the Winograd operator (small size; `-m gpu` runs the BASELINE layer sizes)"""
     shape = (1, 16, 32, 48, 64) if transposed else (1, 32, 64, 32, 64)
-    e = cases.wino_properties(emu_ctx, shape, transposed)
+    with cases.poisoned(emu_ctx, monkeypatch):
+        e = cases.wino_properties(emu_ctx, shape, transposed)
     assert max(e) < 2e-6, e
 
 
@@ -231,6 +235,7 @@ def test_stage2_identical_padding_rows_emu(emu_ctx, monkeypatch):
     P = synthetic_params(d, 451, bias_std=0.05)
     sp = numpy.exp(numpy.random.default_rng(72).normal(-6.0, 1.5, (70, 65))).astype('f4')
     try:
+        monkeypatch.setenv('RY_POISON', '1')                                 # every mode starts from NaN buffers: an uncomputed row cannot borrow the last mode's
         monkeypatch.setenv('RY_PLAN', '1:3:1:1,2:4:1:1'); reread()          # encoder c1 / c2 without split-K (as at full size), 64- and 32-row tiles
         net = engine.Net(emu_ctx, d, flatten_params(d, P), width=64)
         y1 = net.convert(sp)
@@ -247,7 +252,7 @@ def test_stage2_identical_padding_rows_emu(emu_ctx, monkeypatch):
         assert numpy.array_equal(net.convert(numpy.stack([sp, sp[::-1]])), two)
         net.close()
     finally:
-        monkeypatch.delenv('RY_S2_HOLE', raising=False); monkeypatch.delenv('RY_PLAN', raising=False); reread()
+        monkeypatch.delenv('RY_S2_HOLE', raising=False); monkeypatch.delenv('RY_PLAN', raising=False); monkeypatch.delenv('RY_POISON', raising=False); reread()
 
 
 def test_stage2_winograd_layers_emu(emu_ctx, monkeypatch):
@@ -374,6 +379,7 @@ def test_stage2_dead_row_crop_emu(emu_ctx, monkeypatch):
     net = engine.Net(emu_ctx, d, flatten_params(d, P), width=16)
     reread = lambda: emu_ctx.reload_env()
     try:
+        monkeypatch.setenv('RY_POISON', '1')                                 # every mode starts from NaN buffers: an uncomputed row cannot borrow the last mode's
         for n in (11,):
             sp = numpy.exp(numpy.random.default_rng(40 + n).normal(-6.0, 1.5, (n, 17))).astype('f4')
             monkeypatch.setenv('RY_S2_CROP', '0'); reread()
@@ -391,7 +397,7 @@ def test_stage2_dead_row_crop_emu(emu_ctx, monkeypatch):
             fewer = [k for k in g_whole if g_crop[k][0] < g_whole[k][0]]
             assert 'decoder/c6' in fewer and all(k.startswith('decoder/') for k in fewer), (n, fewer)
     finally:
-        monkeypatch.delenv('RY_S2_CROP', raising=False)
+        monkeypatch.delenv('RY_S2_CROP', raising=False); monkeypatch.delenv('RY_POISON', raising=False)
         reread()
     net.close()
 
