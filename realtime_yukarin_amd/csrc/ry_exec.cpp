@@ -172,18 +172,18 @@ static int launch_tail(Launcher& Lc, const Layer& l, const LayerPlan& lp, int B,
     return RY_OK;
 }
 
-static int launch_wino(Launcher& Lc, const Layer& l, const LayerPlan& lp, const float* wwin, int B, const float* s1, int C1, const float* s2, int C2, float slope) {
+static int launch_wino(Launcher& Lc, const Layer& l, const LayerPlan& lp, int B, const float* s1, int C1, const float* s2, int C2, float slope) {
     RyWinoParams p;
     memset(&p, 0, sizeof p);
     fill_geom(p.g, l, lp, B, s1, C1, s2, C2);
     const RyConvGeom& g = p.g;
     int wm, wn, nsl;
-    if (!wwin || !wino_eligible(l, 2) || !wino_cfg_dims(lp.wino_cfg, &wm, &wn, &nsl) || lp.wino_mbw < 1 || lp.wino_mbw > wm || (wm % lp.wino_mbw))
+    if (!lp.wwin || !wino_eligible(l, 2) || !wino_cfg_dims(lp.wino_cfg, &wm, &wn, &nsl) || lp.wino_mbw < 1 || lp.wino_mbw > wm || (wm % lp.wino_mbw))
         return fail(RY_ESTATE, "%s: not a layer / plan for the Winograd kernel (cfg %d, %d blocks per tile row)", l.name, lp.wino_cfg, lp.wino_mbw);
     int th, tw;
     if (!plan_tile_rows(lp, g.Mh, g.Mw, &th, &tw))
         return fail(RY_ESTATE, "%s: the %d x %d grid is not a multiple of the %d x %d Winograd tile", l.name, g.Mh, g.Mw, th, tw);
-    p.wt = wwin; p.scale = l.scale; p.shift = l.shift;
+    p.wt = lp.wwin; p.scale = l.scale; p.shift = l.shift;
     p.act = l.act; p.slope = slope;
     p.slab_stride = (long long)B * lp.Ho * lp.Wo * l.cout;
     const size_t oo = out_offset(l, lp);
@@ -272,7 +272,7 @@ static int launch_igemm(Launcher& Lc, const Layer& l, const LayerPlan& lp, int B
 
 static int launch_conv2d(Launcher& Lc, const Layer& l, const LayerPlan& lp, int B, const float* s1, int C1, const float* s2, int C2, float slope) {
     if (lp.path == PATH_OS2D) return launch_c2d_os(Lc, l, lp, B, s1, C1, s2, C2, slope);
-    if (lp.path == PATH_WINO) return launch_wino(Lc, l, lp, l.wwin, B, s1, C1, s2, C2, slope);
+    if (lp.path == PATH_WINO) return launch_wino(Lc, l, lp, B, s1, C1, s2, C2, slope);
     if (lp.path == PATH_IGEMM || lp.path == PATH_IGEMM_BF16) return launch_igemm(Lc, l, lp, B, s1, C1, s2, C2, slope);
     if (lp.path == PATH_FIRST) {
         RySrFirstParams p;
@@ -440,74 +440,7 @@ static int enqueue_forward(ry_net* net, Plan& P, Launcher& Lc) {
         else RY_LAUNCH(ry_pad_min_rows<16>, pg, 256, Lc.stream, q);
         RY_TRY(Lc.end());
     }
-    // Stage 2, convert wrapper: the wrapper pads every window to T rows and keeps n_frames of the result (SuperResolution.convert crops);
-    // a caller that will itself throw away the first / last frames of the window (ConvertStream.process picks the middle of what it
-    // converted) can say so (ry_sr_convert_rows).  The last layer then computes output rows [k0, k1) only, reads rows [k0 - 1, k1 + 1) of
-    // decoder c6, and nothing ever reads the other rows.  Walking back through the decoder: correct output rows [a, b) of a k4 s2 p1
-    // deconvolution need input rows [floor((a - 1) / 2), floor(b / 2) + 1) (output row 2m takes input rows m - 1 and m, row 2m + 1 rows m
-    // and m + 1).  Rows are the outermost axis of the NHWC buffers, so a layer simply runs on a row RANGE of the same buffers
-    // (LayerPlan::crop_lo / crop_hi; the rows next to the range read as zero padding, which only reaches rows that are not needed).
-    // Every layer demands from its producer exactly the (tile-rounded) rows it reads.  The encoder feeds the bottom of the U-Net and stays whole.
-    int crop[16], crop0[16];
-    for (int i = 0; i < 16; ++i) crop[i] = crop0[i] = 0;
-    int k0 = 0, k1 = P.n_frames;
-    if (nd == 2 && P.mode == 1 && P.lp[15].path == PATH_LAST) {
-        keep_rows(P.n_frames, P.disc_front, P.disc_back, &k0, &k1);
-    }
-    if (nd == 2 && P.mode == 1 && g_s2_crop && P.lp[15].path == PATH_LAST && net->layers[15].src_a == 14) {
-        int need0 = k0 > 0 ? k0 - 1 : 0, need1 = k1 + 1;             // correct rows [need0, need1) wanted from layer i's output
-        for (int i = 14; i >= 8; --i) {
-            const Layer& l = net->layers[i];
-            const LayerPlan& lp = P.lp[i];
-            if (need1 > lp.Ho) need1 = lp.Ho;
-            if (need0 <= 0 && need1 >= lp.Ho) break;
-            if (lp.path != PATH_IGEMM && lp.path != PATH_IGEMM_BF16 && lp.path != PATH_WINO) break;
-            if (l.src_a != i - 1) break;
-            int r0, r1;
-            if (l.deconv) { r0 = need0 > 0 ? (need0 - 1) / 2 : 0; r1 = need1 / 2 + 1; }
-            else if (l.k == 1 && l.stride == 1) { r0 = need0; r1 = need1; }
-            else break;
-            const int Mw = l.deconv ? lp.Wi : lp.Wo, Mh = l.deconv ? lp.Hi : lp.Ho;
-            int th = 1;
-            // keep the 2-D pixel tiles of the launch: whole tile rows
-            if (plan_tile_rows(lp, Mh, Mw, &th)) { r0 = r0 / th * th; r1 = (r1 + th - 1) / th * th; }
-            if (r1 > lp.Hi) r1 = lp.Hi;
-            if (r0 <= 0 && r1 >= lp.Hi) break;
-            // measured at 300 frames (round 2, interleaved A/B on one box): decoder c6 (1536 -> 1216 workgroups, six per CU -> five) 208 -> 177 us, decoder c5
-            // (512 -> 416, two per CU) 198 -> 193 us, decoder c4 (256 -> 224, one per CU) 196 -> 194 us: a grid of one workgroup per CU
-            // gains nothing by itself, but the CUs it leaves idle go to the window on the other lane (ry_vc_set_lanes): 1.160 -> 1.137 ms
-            // per window with two lanes, so it is cropped too (RY_S2_CROP=1 keeps such grids whole)
-            int bm = 256, bn = 64;
-            if (lp.path == PATH_WINO) { if (lp.wino_cfg == 2) bm = 512; } else tile_dims(lp.tile, &bm, &bn);
-            const long wgs = (long)(((long)B * Mh * Mw + bm - 1) / bm) * (l.cout / bn) * (l.deconv ? 4 : 1) * lp.splits;
-            if (g_s2_crop >= 2 || wgs > 256) { crop0[i] = r0; crop[i] = r1 - r0; need0 = r0; need1 = r1; }
-            else { need0 = 0; need1 = lp.Hi; }                      // this layer runs whole: it reads every row of its producer
-        }
-    }
-    // Stage 2, convert wrapper: rows n_frames .. T - 1 of the padded window are copies of ONE row (the column minima, ry_pad_min_rows), so down the
-    // encoder every layer has a stretch of output rows that are equal bit for bit (same operands, same order): identical input rows [a, b] give
-    // identical output rows [ceil((a + pad) / stride), floor((b - (k - 1) dil + pad) / stride)] -- at 300 of 384 frames 40 of 192 rows of encoder c1,
-    // 19 of 96 of c2.  The implicit GEMM leaves the whole tile rows inside the stretch out of its grid and ry_rep_rows copies the row above them:
-    // the MFMA time of those tiles goes to the window on the other lane (RY_S2_HOLE=0 computes them; results are bit-identical either way).
-    int hole_lo[16], hole_n[16];
-    for (int i = 0; i < 16; ++i) hole_lo[i] = hole_n[i] = 0;
-    if (nd == 2 && P.mode == 1 && g_s2_hole && P.n_frames < P.T - 2) {
-        int a = P.n_frames, b = P.T - 1;
-        for (int i = 0; i < 8; ++i) {
-            const Layer& l = net->layers[i];
-            const LayerPlan& lp = P.lp[i];
-            if (l.deconv || l.src_b >= 0 || l.src_a != i - 1) break;
-            const int top = b - (l.k - 1) * l.dil + l.pad;
-            if (top < 0) break;
-            a = (a + l.pad + l.stride - 1) / l.stride; b = top / l.stride;
-            if (b >= lp.Ho) b = lp.Ho - 1;
-            if (b - a < 1) break;
-            int th = 1;
-            if (!plan_tile_rows(lp, lp.Ho, lp.Wo, &th)) continue;
-            const int r0 = (a + 1 + th - 1) / th * th, r1 = (b + 1) / th * th;      // rows [r0, r1) are whole tile rows and copies of row r0 - 1 >= a
-            if (r1 - r0 >= th && plan_hole_ok(l, lp, r0, r1 - r0)) { hole_lo[i] = r0; hole_n[i] = r1 - r0; }
-        }
-    }
+    const WindowRows rows = plan_window_rows(net, P);      // kept rows, dead-row crop, copied padding rows
     for (int i = lo; i < hi; ++i) {
         const Layer& l = net->layers[i];
         const LayerPlan& lp = P.lp[i];
@@ -526,16 +459,14 @@ static int enqueue_forward(ry_net* net, Plan& P, Launcher& Lc) {
             const float* s2 = l.src_b < 0 ? nullptr : in16 ? reinterpret_cast<const float*>(P.lp[l.src_b].out16) : P.lp[l.src_b].out;
             LayerPlan lq = lp;
             if (i == 15 && (P.mode == 0 || lp.path == PATH_LAST)) lq.out = P.cur_out;   // last layer writes the caller's block
-            if (i == 15 && P.mode == 1 && lp.path == PATH_LAST) { lq.last_rows = k1 - k0; lq.last_row0 = k0; lq.last_out_rows = P.n_frames; lq.flops = lp.flops * (k1 - k0) / lp.Ho; }
-            if (hole_n[i] > 0) { lq.hole_lo = hole_lo[i]; lq.hole_n = hole_n[i]; lq.flops = lp.flops * (lp.Ho - hole_n[i]) / lp.Ho; }
-            if (crop[i] > 0) { lq.crop_hi = crop[i]; lq.crop_lo = crop0[i]; lq.flops = lp.flops * crop[i] / lp.Hi; lq.bytes = lp.bytes * crop[i] / lp.Hi; }
-            if (lq.path == PATH_WINO) {
-                auto it = net->weights->lazy.find(i);
-                if (it == net->weights->lazy.end()) return fail(RY_ESTATE, "%s: the Winograd filters of this plan are gone", l.name);
-                RY_TRY(launch_wino(Lc, l, lq, it->second, B, s1, l.cin_a, s2, l.cin_b, slope));
-            } else {
-                RY_TRY(launch_conv2d(Lc, l, lq, B, s1, l.cin_a, s2, l.cin_b, slope));
+            if (i == 15 && P.mode == 1 && lp.path == PATH_LAST) {
+                lq.last_rows = rows.k1 - rows.k0; lq.last_row0 = rows.k0; lq.last_out_rows = P.n_frames; lq.flops = lp.flops * (rows.k1 - rows.k0) / lp.Ho;
             }
+            if (rows.hole_n[i] > 0) { lq.hole_lo = rows.hole_lo[i]; lq.hole_n = rows.hole_n[i]; lq.flops = lp.flops * (lp.Ho - rows.hole_n[i]) / lp.Ho; }
+            if (rows.crop_hi[i] > 0) {
+                lq.crop_hi = rows.crop_hi[i]; lq.crop_lo = rows.crop_lo[i]; lq.flops = lp.flops * rows.crop_hi[i] / lp.Hi; lq.bytes = lp.bytes * rows.crop_hi[i] / lp.Hi;
+            }
+            RY_TRY(launch_conv2d(Lc, l, lq, B, s1, l.cin_a, s2, l.cin_b, slope));
         }
     }
     if (nd == 1 && P.s1_os) {
@@ -580,7 +511,7 @@ int autotune_plan(ry_net* net, Plan& P) {
     for (int i = 0; i < 16 && rc == RY_OK; ++i) {
         LayerPlan& lp = P.lp[i];
         if (lp.path != PATH_IGEMM && lp.path != PATH_IGEMM_BF16) continue;
-        if (g_force[i][0] || g_force[i][1] || g_force[i][2]) continue;         // RY_PLAN fixes this layer
+        if (layer_plan_fixed(i)) continue;                                      // RY_PLAN fixes this layer
         const Layer& l = net->layers[i];
         if (l.src_a < 0) continue;
         const bool b16 = lp.path == PATH_IGEMM_BF16;
@@ -902,79 +833,39 @@ int ry_conv2d_dilated(ry_ctx* ctx, const float* x, int B, int H, int Wd, int Cin
     if (path == PATH_FIRST && !(k3 && Cin == 1 && Cout % 4 == 0)) return fail(RY_EINVAL, "'first' path is the 1 -> N (N %% 4 == 0) 3x3 layer");
     if (path == PATH_LAST && !(k3 && Cout == 1 && Cin % 128 == 0)) return fail(RY_EINVAL, "'last' path is the C -> 1 (C %% 128 == 0) 3x3 layer");
     if ((path == PATH_IGEMM_BF16 || path == PATH_IGEMM_X3) && !(l.wig && Cin % 64 == 0)) return fail(RY_EINVAL, "bf16 implicit-GEMM path needs Cin %% 64 == 0 and Cout %% 64 == 0");
-    lp.path = path ? path : (l.wig ? PATH_IGEMM : PATH_DIRECT);
-    if (path == PATH_IGEMM_X3) { lp.path = PATH_IGEMM_BF16; lp.x3 = true; }
+    // the caller's path, tile and splits as the planner's override record (auto: the implicit GEMM, or the direct kernel without its layout)
+    LayerForce f;
+    f.path = path ? path : (l.wig ? PATH_IGEMM : PATH_DIRECT);
     if (path == PATH_WINO) {                 // `tile` = cfg + 16 mbw (zeros: the planner's choice); `splits` external split-K (0: the planner's)
         if (!wino_eligible(l, 2)) return fail(RY_EINVAL, "the Winograd path is the k4 s2 p1 layer with Cin %% 16 == 0 and Cout %% 64 == 0");
-        const int Mh = transposed ? H : lp.Ho, Mw = transposed ? Wd : lp.Wo;
-        int c[3] = {tile & 15, (tile >> 4) & 15, splits};
-        if (!choose_wino(Mh, Mw, Cout, transposed ? 4 : 1, (transposed ? 1 : 4) * (Cin / 16), B, &c[0], &c[1], &c[2]))
-            return fail(RY_EINVAL, "no Winograd plan %d:%d:%d for a %d x %d grid", c[0], c[1], c[2], Mh, Mw);
-        lp.wino_cfg = c[0]; lp.wino_mbw = c[1]; splits = c[2];
-        std::vector<float> w;
-        relayout_wino(l, [&](int n, int cc, int ky, int kx) { return (double)w2d_at(l, Wt, n, cc, ky, kx); }, w);
-        RY_TRY(upload(arena, ctx, w, &l.wwin));
-        tile = 0;
-    }
-    if (path == PATH_OS2D) {                 // `tile` = mt4 + 16 nt4 + 256 waves + 8192 depth (zeros: the planner's choice)
+        f.wino_set = true; f.wino[0] = tile & 15; f.wino[1] = (tile >> 4) & 15; f.wino[2] = splits;
+    } else if (path == PATH_OS2D) {          // `tile` = mt4 + 16 nt4 + 256 waves + 8192 depth (zeros: the planner's choice)
         if (!l.w2os) return fail(RY_EINVAL, "output-stationary path needs Cin %% 256 == 0 and Cout %% 4 == 0");
-        const TapTable t = make_taps(l);
-        const int M = B * (transposed ? H * Wd : lp.Ho * lp.Wo);
-        int c[4] = {tile & 15, (tile >> 4) & 15, (tile >> 8) & 31, (tile >> 13) & 15};
-        if (!choose_os2(M, Cout, t.nphases, t.ntaps * (Cin / 64), &c[0], &c[1], &c[2], &c[3]))
-            return fail(RY_EINVAL, "no output-stationary slice %d:%d:%d:%d for this shape", c[0], c[1], c[2], c[3]);
-        lp.os2_mt4 = c[0]; lp.os2_nt4 = c[1]; lp.os2_waves = c[2]; lp.os2_depth = c[3];
-        tile = 0;
+        f.os2_set = true; f.os2[0] = tile & 15; f.os2[1] = (tile >> 4) & 15; f.os2[2] = (tile >> 8) & 31; f.os2[3] = (tile >> 13) & 15;
+    } else if (f.path == PATH_IGEMM || f.path == PATH_IGEMM_BF16 || f.path == PATH_IGEMM_X3) {
+        f.kg = (tile & 16) ? 2 : ((tile & 32) ? 1 : 0);                    // +16: two K groups per workgroup, +32: one, else automatic
+        f.tile = tile & 15; f.splits = splits;
+        if (f.tile < 0 || f.tile > TILE_96x128 || f.tile == 2) return fail(RY_EINVAL, "unknown tile");
+        if (f.tile == TILE_128x64 ? Cout % 64 : (f.tile != 0 && Cout % 128)) return fail(RY_EINVAL, "tile does not divide Cout");
     }
+    const int dtype = path == PATH_IGEMM_X3 ? 2 : path == PATH_IGEMM_BF16 ? 1 : 0;
+    if (dtype != 0) RY_TRY(prepare_bf16(ctx, arena, l, dtype));          // the filters a predictor's layer gets from ry_net_set_dtype
+    RY_TRY(plan_s2_layer(ctx, arena, l, lp, B, dtype, f, false, false, 0));
+    if (lp.path == PATH_WINO) {
+        float* w = nullptr;
+        RY_TRY(upload_wwin(ctx, arena, l, &w));
+        lp.wwin = w;
+    }
+    lp.any_m_patch = true;
     const size_t out_elems = (size_t)B * lp.Ho * lp.Wo * Cout;
-    lp.splits = path == PATH_WINO ? splits : 1;
-    lp.last_rows = lp.Ho; lp.last_cols = lp.Wo; lp.last_exp = 0;
-    if (path == PATH_WINO && lp.splits > 1) RY_TRY(arena.alloc(&lp.slabs, out_elems * lp.splits));
-    if (lp.path == PATH_IGEMM || lp.path == PATH_IGEMM_BF16) {
-        const TapTable t = make_taps(l);
-        const int M = B * (transposed ? H * Wd : lp.Ho * lp.Wo);
-        lp.kg = (tile & 16) ? 2 : ((tile & 32) ? 1 : 0);                    // +16: two K groups per workgroup, +32: one, else automatic
-        lp.any_m_patch = true;
-        tile &= 15;
-        lp.tile = tile; lp.splits = splits;
-        if (tile < 0 || tile > TILE_96x128 || tile == 2) return fail(RY_EINVAL, "unknown tile");
-        if (tile == TILE_128x64 ? Cout % 64 : (tile != 0 && Cout % 128)) return fail(RY_EINVAL, "tile does not divide Cout");
-        const bool op16 = lp.path == PATH_IGEMM_BF16;
-        choose_igemm(l, M, t.nphases, t.ntaps * (lp.x3 ? 3 * Cin / 64 : Cin / (op16 ? 64 : 32)), &lp.tile, &lp.splits, &lp.kg, lp.x3 ? 2 : (op16 ? 1 : 0));
-        if (lp.x3) {
-            std::vector<float> w32;
-            relayout_igemm(l, Wt, w32);
-            std::vector<unsigned short> wx;
-            build_wigx3(l, w32, wx);
-            RY_TRY(arena.alloc(&l.wigx3, (wx.size() + 1) / 2));
-            RT_TRY(rt::h2d(l.wigx3, wx.data(), wx.size() * sizeof(unsigned short), ctx->stream));
-            RT_TRY(rt::stream_sync(ctx->stream));
-        } else if (op16) {
-            // bf16 filters of this single layer
-            const size_t n = (size_t)t.nphases * Cout * t.ntaps * Cin;
-            std::vector<float> w32;
-            relayout_igemm(l, Wt, w32);
-            std::vector<unsigned short> w16(n);
-            const size_t outer = (size_t)t.nphases * (Cout / 64) * t.ntaps;
-            for (size_t o = 0; o < outer; ++o)
-                for (int c = 0; c < Cin; ++c)
-                    for (int nl = 0; nl < 64; ++nl)
-                        w16[(o * (Cin / 64) + c / 64) * 4096 + wig16_inblock(nl, c % 64)] = host_f2bf(w32[(o * (Cin / 32) + c / 32) * 2048 + wig_inblock(nl, c % 32)]);
-            RY_TRY(arena.alloc(&l.wig16, (n + 1) / 2));
-            RT_TRY(rt::h2d(l.wig16, w16.data(), n * sizeof(unsigned short), ctx->stream));
-            RT_TRY(rt::stream_sync(ctx->stream));
-        }
-        if (lp.splits > 1) RY_TRY(arena.alloc(&lp.slabs, out_elems * lp.splits));
-    }
     float* dx = nullptr;
     RY_TRY(alloc_ztail(ctx, arena, &dx, (size_t)B * H * Wd * Cin));
     RY_TRY(arena.alloc(&lp.out, out_elems));
-    // RY_POISON: an output element or a slab row the launch leaves unwritten reads as NaN instead of the previous call's result
+    // RY_POISON: an output element the launch leaves unwritten reads as NaN instead of the previous call's result (the slabs: plan_s2_layer)
     RY_TRY(poison_fill(ctx, lp.out, out_elems));
-    if (lp.splits > 1 && lp.slabs) RY_TRY(poison_fill(ctx, lp.slabs, out_elems * lp.splits));
     Launcher Lc{nullptr, ctx, ctx->stream, nullptr, nullptr};
-    if (lp.path == PATH_LAST) {
-        // exercise the un-materialised skip concat: the channels are handed over as two half-width sources
+    if (lp.path == PATH_LAST || (lp.path == PATH_OS2D && Cin % 512 == 0) || (lp.path == PATH_WINO && Cin % 32 == 0)) {
+        // exercise the un-materialised skip concat: the channels are handed over as two half-width sources, each followed by its zero pixel
         const int Ch = Cin / 2;
         const size_t npix = (size_t)B * H * Wd;
         std::vector<float> ha(npix * Ch), hb(npix * Ch);
@@ -983,10 +874,12 @@ int ry_conv2d_dilated(ry_ctx* ctx, const float* x, int B, int H, int Wd, int Cin
             memcpy(&hb[q * Ch], x + q * Cin + Ch, Ch * sizeof(float));
         }
         float* dx2 = nullptr;
-        RY_TRY(arena.alloc(&dx2, npix * Ch));
+        RY_TRY(alloc_ztail(ctx, arena, &dx2, npix * Ch));
+        RT_TRY(rt::dmemset(dx + npix * Ch, 0, ZTAIL * sizeof(float), ctx->stream));      // the first half ends inside dx: its zero pixel right behind it
         RT_TRY(rt::h2d(dx, ha.data(), npix * Ch * sizeof(float), ctx->stream));
         RT_TRY(rt::h2d(dx2, hb.data(), npix * Ch * sizeof(float), ctx->stream));
         RT_TRY(rt::stream_sync(ctx->stream));
+        l.cin_a = Ch; l.cin_b = Ch;
         RY_TRY(launch_conv2d(Lc, l, lp, B, dx, Ch, dx2, Ch, 0.2f));
     } else if (lp.path == PATH_IGEMM_BF16) {
         // the bf16 kernel reads bf16 activations (in a predictor the producing layer writes them): round the input here
@@ -1006,23 +899,6 @@ int ry_conv2d_dilated(ry_ctx* ctx, const float* x, int B, int H, int Wd, int Cin
         RT_TRY(rt::h2d(dx, x16.data(), x16.size() * sizeof(unsigned short), ctx->stream));
         RT_TRY(rt::stream_sync(ctx->stream));
         RY_TRY(launch_conv2d(Lc, l, lp, B, dx, Cin, nullptr, 0, 0.2f));
-    } else if ((lp.path == PATH_OS2D && Cin % 512 == 0) || (lp.path == PATH_WINO && Cin % 32 == 0)) {
-        // exercise the un-materialised skip concat: the channels are handed over as two half-width sources, each followed by its zero pixel
-        const int Ch = Cin / 2;
-        const size_t npix = (size_t)B * H * Wd;
-        std::vector<float> ha(npix * Ch), hb(npix * Ch);
-        for (size_t q = 0; q < npix; ++q) {
-            memcpy(&ha[q * Ch], x + q * Cin, Ch * sizeof(float));
-            memcpy(&hb[q * Ch], x + q * Cin + Ch, Ch * sizeof(float));
-        }
-        float* dx2 = nullptr;
-        RY_TRY(alloc_ztail(ctx, arena, &dx2, npix * Ch));
-        RT_TRY(rt::dmemset(dx + npix * Ch, 0, ZTAIL * sizeof(float), ctx->stream));      // the first half ends inside dx: its zero pixel right behind it
-        RT_TRY(rt::h2d(dx, ha.data(), npix * Ch * sizeof(float), ctx->stream));
-        RT_TRY(rt::h2d(dx2, hb.data(), npix * Ch * sizeof(float), ctx->stream));
-        RT_TRY(rt::stream_sync(ctx->stream));
-        l.cin_a = Ch; l.cin_b = Ch;
-        RY_TRY(launch_conv2d(Lc, l, lp, B, dx, Ch, dx2, Ch, 0.2f));
     } else {
         RT_TRY(rt::h2d(dx, x, (size_t)B * H * Wd * Cin * sizeof(float), ctx->stream));
         RY_TRY(launch_conv2d(Lc, l, lp, B, dx, Cin, nullptr, 0, 0.2f));

@@ -169,9 +169,6 @@ struct Layer {
     float* wig16 = nullptr;
     // stage-2 output-stationary kernel ry_c2d_os: [phase][N/4][tap][Ctot/64][lane][4], see relayout_c2d_os() (the weight-streaming layers only)
     float* w2os = nullptr;
-    // stage-2 Winograd F(2x2, 2x2) filters [phase][N/64][slice of 8 channels][position 9][n/32][lane][4], see relayout_wino() (op-level calls;
-    // predictors: Arena::lazy)
-    float* wwin = nullptr;
     // split-bf16 blocks [phase][N/64][tap][3 Ctot/64][fragment order]: K runs over [hi | hi | lo] per source, see build_wigx3()
     float* wigx3 = nullptr;
     int cin() const { return cin_a + cin_b; }
@@ -200,6 +197,9 @@ struct LayerPlan {
     int os2_mt4 = 0, os2_nt4 = 0, os2_waves = 0, os2_depth = 0;
     // PATH_WINO: workgroup shape (1 = 2 x 2 waves, one 8-channel slice per iteration; 2 = 4 x 2 waves, two slices) and M-blocks per tile row
     int wino_cfg = 0, wino_mbw = 0;
+    // PATH_WINO: the F(2x2, 2x2) filters [phase][N/64][slice of 8 channels][position 9][n/32][lane][4], see relayout_wino() (predictors: built once
+    // per layer in Arena::lazy; single operators: the operator's arena)
+    const float* wwin = nullptr;
     int kg = 1;                               // K groups inside a workgroup (LDS-DMA implicit GEMM): 2 = split-K summed through the LDS
     float* out = nullptr;                     // NHWC activation, fp32
     unsigned short* out16 = nullptr;          // NHWC activation, bf16 copy for consumers on the bf16 path (bf16 / split-bf16 mode only)

@@ -173,48 +173,11 @@ int ry_net_set_dtype(ry_net* net, int dtype) {
     ry_ctx* ctx = net->ctx;
     RT_TRY(rt::set_device(ctx->device));
     RT_TRY(rt::stream_sync(net->stream));
-    if (dtype == 1) {
-        for (Layer& l : net->layers) {
-            if (!l.wig || l.wig16 || l.cin_a % 64 != 0 || l.cin_b % 64 != 0) continue;
-            const TapTable t = make_taps(l);
-            const int C = l.cin(), N = l.cout;
-            const size_t n = (size_t)t.nphases * N * t.ntaps * C;
-            std::vector<float> w32(n);
-            RT_TRY(rt::d2h(w32.data(), l.wig, n * sizeof(float), ctx->stream));
-            RT_TRY(rt::stream_sync(ctx->stream));
-            // fp32 blocks [..][C/32][64][32]  ->  bf16 blocks [..][C/64][64][64]
-            std::vector<unsigned short> w16(n);
-            const size_t outer = (size_t)t.nphases * (N / 64) * t.ntaps;
-            for (size_t o = 0; o < outer; ++o)
-                for (int c = 0; c < C; ++c)
-                    for (int nl = 0; nl < 64; ++nl)
-                        w16[(o * (C / 64) + c / 64) * 4096 + wig16_inblock(nl, c % 64)] = host_f2bf(w32[(o * (C / 32) + c / 32) * 2048 + wig_inblock(nl, c % 32)]);
-            float* d = nullptr;
-            RY_TRY(net->weights->alloc(&d, (n + 1) / 2));
-            RT_TRY(rt::h2d(d, w16.data(), n * sizeof(unsigned short), ctx->stream));
-            RT_TRY(rt::stream_sync(ctx->stream));
-            l.wig16 = d;
-        }
-    }
     RY_TRY(read_plan_env());
-    if (dtype == 2) {
+    if (dtype == 2)
         if (const char* e = getenv("RY_X3_MINM")) g_x3_min_m = atoi(e);      // read again here so that a test / sweep can move it per call
-        for (Layer& l : net->layers) {
-            if (!l.wig || l.wigx3 || l.cin_a % 64 != 0 || l.cin_b % 64 != 0) continue;
-            const TapTable t = make_taps(l);
-            const size_t n = (size_t)t.nphases * l.cout * t.ntaps * l.cin();
-            std::vector<float> w32(n);
-            RT_TRY(rt::d2h(w32.data(), l.wig, n * sizeof(float), ctx->stream));
-            RT_TRY(rt::stream_sync(ctx->stream));
-            std::vector<unsigned short> wx;
-            build_wigx3(l, w32, wx);
-            float* d = nullptr;
-            RY_TRY(net->weights->alloc(&d, (wx.size() + 1) / 2));
-            RT_TRY(rt::h2d(d, wx.data(), wx.size() * sizeof(unsigned short), ctx->stream));
-            RT_TRY(rt::stream_sync(ctx->stream));
-            l.wigx3 = d;
-        }
-    }
+    if (dtype != 0)
+        for (Layer& l : net->layers) RY_TRY(prepare_bf16(ctx, *net->weights, l, dtype));
     net->dtype = dtype;
     net->plans.clear();                              // launch plans (and captured graphs) depend on the kernel choice
     return RY_OK;

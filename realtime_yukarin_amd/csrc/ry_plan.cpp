@@ -1,6 +1,7 @@
 // ry_plan.cpp -- the planner of libry355.so: U-Net topology, filter re-layout at predictor creation (BN folded to scale / shift), the per-layer choice of
-// kernel family, tile, split-K and K groups (stage 2: implicit GEMM / Winograd / output-stationary; stage 1: output-stationary slices), the launch plan of a
-// (batch, frames) window with its activation buffers, and the environment switches.  No device code: the launchers are ry_exec.cpp.
+// kernel family, tile, split-K and K groups (stage 2: implicit GEMM / Winograd / output-stationary, for predictors and the single operator ry_conv2d; stage 1:
+// output-stationary slices), the launch plan of a (batch, frames) window with its activation buffers, the rows each enqueue computes, and the environment
+// switches.  No device code: the launchers are ry_exec.cpp.
 #include "ry_plan.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -66,6 +67,7 @@ int check_desc(const ry_net_desc* d) {
 }
 
 static const int DECONV_DY[2][2] = {{0, -1}, {1, 0}};  // output parity p, tap t -> input offset
+static const int DECONV_KY[2][2] = {{1, 3}, {0, 2}};   // output parity p, tap t -> kernel index
 
 static void fold_scale_shift(const Layer& l, const float* b, const float* bn, float eps,
                              std::vector<float>& scale, std::vector<float>& shift) {
@@ -131,7 +133,7 @@ TapTable make_taps(const Layer& l) {
 }
 
 // stage-2 filters: conv W (N, C, k, k); deconv W (C, N, 4, 4)
-float w2d_at(const Layer& l, const float* W, int n, int c, int ky, int kx) {
+static float w2d_at(const Layer& l, const float* W, int n, int c, int ky, int kx) {
     const int C = l.cin(), N = l.cout, K = l.k;
     return l.deconv ? W[(((size_t)c * N + n) * K + ky) * K + kx] : W[(((size_t)n * C + c) * K + ky) * K + kx];
 }
@@ -143,17 +145,17 @@ float w2d_at(const Layer& l, const float* W, int n, int c, int ky, int kx) {
 // stored in MFMA FRAGMENT ORDER [n/32 : 2][s : 4][lane : 64][t : 4] with lane = 32 * lh + (n % 32) and k = 8 s + 4 lh + t:
 // the 16 bytes lane `lane` feeds to the four v_mfma_f32_32x32x2_f32 of K step s are contiguous, one (n/32, s) piece is
 // 1 KiB in lane order -- a wave loads its B fragments straight into registers (or a piece into LDS) fully coalesced.
-size_t wig_inblock(int nl, int k) {
+static size_t wig_inblock(int nl, int k) {
     return (size_t)(nl >> 5) * 1024 + (size_t)(k >> 3) * 256 + (size_t)((((k >> 2) & 1) * 32 + (nl & 31)) * 4) + (size_t)(k & 3);
 }
 
 // bf16 blocks of 64 output channels x 64 input channels, same idea: [n/32 : 2][s : 4][lane : 64][j : 8] with
 // lane = 32 * lh + (n % 32) and k = 16 s + 8 lh + j (the 8 bf16 a lane feeds to one v_mfma_f32_32x32x16_bf16); index in bf16 units.
-size_t wig16_inblock(int nl, int k) {
+static size_t wig16_inblock(int nl, int k) {
     return (size_t)(nl >> 5) * 2048 + (size_t)(k >> 4) * 512 + (size_t)((((k >> 3) & 1) * 32 + (nl & 31)) * 8) + (size_t)(k & 7);
 }
 
-void relayout_igemm(const Layer& l, const float* W, std::vector<float>& out) {
+static void relayout_igemm(const Layer& l, const float* W, std::vector<float>& out) {
     const TapTable t = make_taps(l);
     const int C = l.cin(), N = l.cout, cpt = C / 32;
     out.resize((size_t)t.nphases * N * t.ntaps * C);
@@ -213,6 +215,55 @@ static void relayout_c2d_os(const Layer& l, const float* W, std::vector<float>& 
 bool wino_eligible(const Layer& l, int ndim) {
     return ndim == 2 && l.k == 4 && l.stride == 2 && l.pad == 1 && l.dil == 1 && l.cin_a % 16 == 0 && l.cin_b % 16 == 0 && l.cout % 64 == 0 &&
            l.cin_a > 0 && l.cin_a <= 2032 && l.cin_b <= 2032;     // (the channel offset of a patch rides on the base of its zero-tail fetches: ZTAIL floats)
+}
+
+// wd = the layer's direct layout [phase][tap][C][N] (relayout_direct), which holds every filter element once
+static void relayout_wino(const Layer& l, const std::vector<float>& wd, std::vector<float>& out) {
+    const TapTable t = make_taps(l);
+    const int C = l.cin(), N = l.cout;
+    int where[4][4];
+    for (int ph = 0; ph < t.nphases; ++ph)
+        for (int tt = 0; tt < t.ntaps; ++tt) where[t.ky[ph][tt]][t.kx[ph][tt]] = ph * t.ntaps + tt;
+    auto w = [&](int n, int c, int ky, int kx) { return (double)wd[((size_t)where[ky][kx] * C + c) * N + n]; };
+    const int nph = l.deconv ? 4 : 1, nsl = l.deconv ? C / 8 : (C / 16) * 8;
+    out.assign((size_t)nph * N * nsl * 72, 0.f);
+    static const double G[3][2] = {{1, 0}, {1, 1}, {0, 1}};
+    for (int ph = 0; ph < nph; ++ph)
+        for (int n = 0; n < N; ++n)
+            for (int ks = 0; ks < nsl; ++ks)
+                for (int cc = 0; cc < 8; ++cc) {
+                    int c; double g[2][2];
+                    if (l.deconv) {
+                        c = ks * 8 + cc;
+                        for (int a = 0; a < 2; ++a)
+                            for (int b = 0; b < 2; ++b) g[a][b] = w(n, c, DECONV_KY[ph >> 1][1 - a], DECONV_KY[ph & 1][1 - b]);
+                    } else {
+                        const int par = (ks >> 1) & 3;
+                        c = (ks >> 3) * 16 + (ks & 1) * 8 + cc;
+                        for (int a = 0; a < 2; ++a)
+                            for (int b = 0; b < 2; ++b) g[a][b] = w(n, c, 2 * a + (par >> 1), 2 * b + (par & 1));
+                    }
+                    for (int i = 0; i < 3; ++i)
+                        for (int j = 0; j < 3; ++j) {
+                            double u = 0.0;
+                            for (int a = 0; a < 2; ++a)
+                                for (int b = 0; b < 2; ++b) u += G[i][a] * g[a][b] * G[j][b];
+                            const size_t piece = ((((size_t)ph * (N / 64) + n / 64) * nsl + ks) * 9 + (i * 3 + j)) * 2 + (n % 64) / 32;
+                            out[piece * 256 + (size_t)((32 * (cc >> 2) + n % 32) * 4 + (cc & 3))] = (float)u;
+                        }
+                }
+}
+
+// The Winograd filters of a layer, uploaded into `arena` (2.25 x the floats of its filters): read the direct layout back, transform.  Never called under
+// stream capture (plans are built before their first run).
+int upload_wwin(ry_ctx* ctx, Arena& arena, const Layer& l, float** out) {
+    if (!l.wdir || !wino_eligible(l, 2)) return fail(RY_ESTATE, "%s: no Winograd form of this layer", l.name);
+    const TapTable t = make_taps(l);
+    std::vector<float> wd((size_t)t.nphases * t.ntaps * l.cin() * l.cout), w;
+    RT_TRY(rt::d2h(wd.data(), l.wdir, wd.size() * sizeof(float), ctx->stream));
+    RT_TRY(rt::stream_sync(ctx->stream));
+    relayout_wino(l, wd, w);
+    return upload(arena, ctx, w, out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -279,11 +330,14 @@ void tile_dims(int tile, int* bm, int* bn) {
 
 // Process-wide switches (INTEGRATION.md section 6 lists every one).  Round 3 removed the A/B switches of closed experiments (register-staged
 // kernel, 256-row tiles, burst loads, raster tiles, two-graph cut + stagger, stage-1 tuning aids, ...): their measurements are in DESIGN.md.
-int g_s2_hole = 1;     // RY_S2_HOLE=0: the encoder computes the identical padding rows behind the real frames instead of copying them (A/B, bit-identity tests)
+static int g_s2_hole = 1;     // RY_S2_HOLE=0: the encoder computes the identical padding rows behind the real frames instead of copying them (A/B, bit-identity tests)
 // RY_S2_CROP=0: every decoder layer of the convert wrapper computes all padded rows (A/B of the dead-row crop, used by the bit-identity tests); 1:
 // only grids of more than one workgroup per CU
-int g_s2_crop = 2;
-int g_force[16][3];    // RY_PLAN="layer:tile:splits:kgroups,...": tuning aid, fixes the stage-2 plan of single layers (0 = planner's choice)
+static int g_s2_crop = 2;
+// RY_PLAN="layer:tile:splits:kgroups,...", RY_WINO="layer:cfg:mbw:splits,..." and RY_OS2="layer:mt4:nt4:waves:depth,...": tuning aids that fix the
+// stage-2 plan of single layers (0 = planner's choice; "layer:0" keeps that layer off the Winograd form / on the implicit GEMM)
+static LayerForce g_force[16];
+bool layer_plan_fixed(int i) { return g_force[i].fixed(); }
 // RY_X3_MINM: split-bf16 mode runs a layer on the bf16 pipe from this many GEMM rows (per phase) up (measured at 300 frames: 1 / 32 / 64 / 128 / 512
 // / 2048 -> 0.861 / 0.865 / 0.867 / 0.864 vs 0.840 / 0.928 ms per step on two boxes; 128 beat 512 by 1 % in the same-box A/B)
 int g_x3_min_m = 128;
@@ -439,9 +493,6 @@ static bool os2_has_config(int mt4, int nt4, int waves, int depth) {
 // Fitted: encoder c6 / decoder c1 at 300 frames (4096) win by 2-4 us, encoder c5 at 300 frames (10240) and
 // decoder c2 at 100 frames (8192) lose by 8-11
 static int g_os2_maxcost = 4608;
-// RY_OS2="layer:mt4:nt4:waves:depth,...": tuning aid, fixes the slice of single layers ("layer:0" keeps that layer on the implicit GEMM)
-static int g_os2_force[16][4];
-static bool g_os2_forced[16];
 
 // Slice of one layer, by a cost fitted to the slice sweeps on the MI355X (profiles/r05/e_os_sweep_n{300,100}.txt): a workgroup pulls K x (rows +
 // channels) of its tile through its CU's L1, the pixel rows at about half the rate of the filter rows (a wave-load of pixels is four
@@ -491,9 +542,6 @@ static int g_wino = 1;                 // RY_WINOGRAD=0: every layer keeps the d
 // RY_WINO_MINM: rows (pixels of one phase) from which an eligible layer takes the Winograd form (512 -> 256: encoder c4 / decoder c3 of the 100-frame
 // window, 231.8 -> 240.9 k frames/s)
 static int g_wino_min_m = 256;
-// RY_WINO="layer:cfg:mbw:splits,...": tuning aid, fixes the Winograd plan of single layers ("layer:0" keeps that layer on the direct kernel)
-static int g_wino_force[16][3];
-static bool g_wino_forced[16];
 
 bool wino_cfg_dims(int cfg, int* wm, int* wn, int* nsl) {
     if (cfg == 1) { *wm = 2; *wn = 2; *nsl = 1; return true; }
@@ -603,27 +651,13 @@ static void choose_os(const Layer& l, int B, int rows, int* cb, int* tp) {
     *cb = CF[best][0]; *tp = CF[best][1];
 }
 
-// The Winograd filters of predictor layer i, built when a plan first takes the layer onto that path (2.25 x the floats of the layer's filters, kept in the
-// arena the clones of the predictor share): the direct layout [phase][tap][C][N] holds every filter element once -- read it back, transform, upload.
-// Never called under stream capture (plans are built before their first run).
+// The Winograd filters of predictor layer i, built when a plan first takes the layer onto that path and kept in the arena the clones of the predictor share
 static int ensure_wwin(ry_net* net, int i, const float** out) {
     auto& lazy = net->weights->lazy;
     auto it = lazy.find(i);
     if (it == lazy.end()) {
-        const Layer& l = net->layers[i];
-        if (!l.wdir || !wino_eligible(l, net->desc.ndim)) return fail(RY_ESTATE, "%s: no Winograd form of this layer", l.name);
-        const TapTable t = make_taps(l);
-        const int C = l.cin(), N = l.cout;
-        std::vector<float> wd((size_t)t.nphases * t.ntaps * C * N);
-        RT_TRY(rt::d2h(wd.data(), l.wdir, wd.size() * sizeof(float), net->ctx->stream));
-        RT_TRY(rt::stream_sync(net->ctx->stream));
-        int where[4][4];
-        for (int ph = 0; ph < t.nphases; ++ph)
-            for (int tt = 0; tt < t.ntaps; ++tt) where[t.ky[ph][tt]][t.kx[ph][tt]] = ph * t.ntaps + tt;
-        std::vector<float> w;
-        relayout_wino(l, [&](int n, int c, int ky, int kx) { return (double)wd[((size_t)where[ky][kx] * C + c) * N + n]; }, w);
         float* d = nullptr;
-        RY_TRY(upload(*net->weights, net->ctx, w, &d));
+        RY_TRY(upload_wwin(net->ctx, *net->weights, net->layers[i], &d));
         it = lazy.emplace(i, d).first;
     }
     *out = it->second;
@@ -655,9 +689,153 @@ bool plan_hole_ok(const Layer& l, const LayerPlan& lp, int lo, int n) {
     return n > 0 && lo >= 1 && lo % th == 0 && n % th == 0 && lo + n <= lp.Ho;
 }
 
+WindowRows plan_window_rows(const ry_net* net, const Plan& P) {
+    const int nd = net->desc.ndim, B = P.B;
+    WindowRows w;
+    // Stage 2, convert wrapper: the wrapper pads every window to T rows and keeps n_frames of the result (SuperResolution.convert crops);
+    // a caller that will itself throw away the first / last frames of the window (ConvertStream.process picks the middle of what it
+    // converted) can say so (ry_sr_convert_rows).  The last layer then computes output rows [k0, k1) only, reads rows [k0 - 1, k1 + 1) of
+    // decoder c6, and nothing ever reads the other rows.  Walking back through the decoder: correct output rows [a, b) of a k4 s2 p1
+    // deconvolution need input rows [floor((a - 1) / 2), floor(b / 2) + 1) (output row 2m takes input rows m - 1 and m, row 2m + 1 rows m
+    // and m + 1).  Rows are the outermost axis of the NHWC buffers, so a layer simply runs on a row RANGE of the same buffers
+    // (LayerPlan::crop_lo / crop_hi; the rows next to the range read as zero padding, which only reaches rows that are not needed).
+    // Every layer demands from its producer exactly the (tile-rounded) rows it reads.  The encoder feeds the bottom of the U-Net and stays whole.
+    w.k1 = P.n_frames;
+    if (nd == 2 && P.mode == 1 && P.lp[15].path == PATH_LAST) {
+        keep_rows(P.n_frames, P.disc_front, P.disc_back, &w.k0, &w.k1);
+    }
+    if (nd == 2 && P.mode == 1 && g_s2_crop && P.lp[15].path == PATH_LAST && net->layers[15].src_a == 14) {
+        int need0 = w.k0 > 0 ? w.k0 - 1 : 0, need1 = w.k1 + 1;         // correct rows [need0, need1) wanted from layer i's output
+        for (int i = 14; i >= 8; --i) {
+            const Layer& l = net->layers[i];
+            const LayerPlan& lp = P.lp[i];
+            if (need1 > lp.Ho) need1 = lp.Ho;
+            if (need0 <= 0 && need1 >= lp.Ho) break;
+            if (lp.path != PATH_IGEMM && lp.path != PATH_IGEMM_BF16 && lp.path != PATH_WINO) break;
+            if (l.src_a != i - 1) break;
+            int r0, r1;
+            if (l.deconv) { r0 = need0 > 0 ? (need0 - 1) / 2 : 0; r1 = need1 / 2 + 1; }
+            else if (l.k == 1 && l.stride == 1) { r0 = need0; r1 = need1; }
+            else break;
+            const int Mw = l.deconv ? lp.Wi : lp.Wo, Mh = l.deconv ? lp.Hi : lp.Ho;
+            int th = 1;
+            // keep the 2-D pixel tiles of the launch: whole tile rows
+            if (plan_tile_rows(lp, Mh, Mw, &th)) { r0 = r0 / th * th; r1 = (r1 + th - 1) / th * th; }
+            if (r1 > lp.Hi) r1 = lp.Hi;
+            if (r0 <= 0 && r1 >= lp.Hi) break;
+            // measured at 300 frames (round 2, interleaved A/B on one box): decoder c6 (1536 -> 1216 workgroups, six per CU -> five) 208 -> 177 us, decoder c5
+            // (512 -> 416, two per CU) 198 -> 193 us, decoder c4 (256 -> 224, one per CU) 196 -> 194 us: a grid of one workgroup per CU
+            // gains nothing by itself, but the CUs it leaves idle go to the window on the other lane (ry_vc_set_lanes): 1.160 -> 1.137 ms
+            // per window with two lanes, so it is cropped too (RY_S2_CROP=1 keeps such grids whole)
+            int bm = 256, bn = 64;
+            if (lp.path == PATH_WINO) { if (lp.wino_cfg == 2) bm = 512; } else tile_dims(lp.tile, &bm, &bn);
+            const long wgs = (long)(((long)B * Mh * Mw + bm - 1) / bm) * (l.cout / bn) * (l.deconv ? 4 : 1) * lp.splits;
+            if (g_s2_crop >= 2 || wgs > 256) { w.crop_lo[i] = r0; w.crop_hi[i] = r1 - r0; need0 = r0; need1 = r1; }
+            else { need0 = 0; need1 = lp.Hi; }                      // this layer runs whole: it reads every row of its producer
+        }
+    }
+    // Stage 2, convert wrapper: rows n_frames .. T - 1 of the padded window are copies of ONE row (the column minima, ry_pad_min_rows), so down the
+    // encoder every layer has a stretch of output rows that are equal bit for bit (same operands, same order): identical input rows [a, b] give
+    // identical output rows [ceil((a + pad) / stride), floor((b - (k - 1) dil + pad) / stride)] -- at 300 of 384 frames 40 of 192 rows of encoder c1,
+    // 19 of 96 of c2.  The implicit GEMM leaves the whole tile rows inside the stretch out of its grid and ry_rep_rows copies the row above them:
+    // the MFMA time of those tiles goes to the window on the other lane (RY_S2_HOLE=0 computes them; results are bit-identical either way).
+    if (nd == 2 && P.mode == 1 && g_s2_hole && P.n_frames < P.T - 2) {
+        int a = P.n_frames, b = P.T - 1;
+        for (int i = 0; i < 8; ++i) {
+            const Layer& l = net->layers[i];
+            const LayerPlan& lp = P.lp[i];
+            if (l.deconv || l.src_b >= 0 || l.src_a != i - 1) break;
+            const int top = b - (l.k - 1) * l.dil + l.pad;
+            if (top < 0) break;
+            a = (a + l.pad + l.stride - 1) / l.stride; b = top / l.stride;
+            if (b >= lp.Ho) b = lp.Ho - 1;
+            if (b - a < 1) break;
+            int th = 1;
+            if (!plan_tile_rows(lp, lp.Ho, lp.Wo, &th)) continue;
+            const int r0 = (a + 1 + th - 1) / th * th, r1 = (b + 1) / th * th;      // rows [r0, r1) are whole tile rows and copies of row r0 - 1 >= a
+            if (r1 - r0 >= th && plan_hole_ok(l, lp, r0, r1 - r0)) { w.hole_lo[i] = r0; w.hole_n[i] = r1 - r0; }
+        }
+    }
+    return w;
+}
+
 // ------------------------------------------------------------------------------------------------
 // plan construction
 // ------------------------------------------------------------------------------------------------
+// The launch plan of one stage-2 layer whose geometry lp holds: path, tile, split-K and K groups, the Winograd / output-stationary shape, the fused end
+// of PATH_LAST (out_layer: the predictor's last layer; mode: the plan's), and the split-K slabs in `arena`.  src16: every producer writes a bf16 copy
+// of its output.  f: the layer's override record; a path it names (the single operator) runs as it is -- the process-wide switches, the producer
+// rule and the row minima of the Winograd / split-bf16 forms do not apply to it.
+int plan_s2_layer(ry_ctx* ctx, Arena& arena, const Layer& l, LayerPlan& lp, int B, int dtype, const LayerForce& f, bool src16, bool out_layer, int mode) {
+    const TapTable t = make_taps(l);
+    const int M = B * (l.deconv ? lp.Hi * lp.Wi : lp.Ho * lp.Wo);
+    const bool x3 = dtype == 2;
+    if (f.path ? f.path == PATH_IGEMM || f.path == PATH_IGEMM_BF16 || f.path == PATH_IGEMM_X3 : l.wig != nullptr) {
+        lp.path = PATH_IGEMM; lp.tile = f.tile; lp.splits = f.splits; lp.kg = f.kg;
+        if (lp.tile != 0) {                                  // RY_PLAN: refuse a tile that does not divide the output channels
+            int fbm, fbn; tile_dims(lp.tile, &fbm, &fbn);
+            if (l.cout % fbn != 0) return fail(RY_EINVAL, "RY_PLAN: tile %dx%d does not divide the %d output channels of %s", fbm, fbn, l.cout, l.name);
+            if (dtype != 0 && fbm > 128) return fail(RY_EINVAL, "RY_PLAN: no bf16 instantiation of the %dx%d tile (%s)", fbm, fbn, l.name);
+        }
+        // bf16 mode: a layer runs on bf16 operands when its filters were converted and every producer it reads can
+        // write a bf16 copy of its output (the first layer, implicit-GEMM layers and their reduce kernels can)
+        // split-bf16 mode: the same, for the layers with enough rows to be bound by the matrix pipe (the weight-streaming
+        // layers at the bottom of the U-Net would read 1.5 x the filter bytes: they stay exact fp32)
+        const bool want16 = f.path ? f.path != PATH_IGEMM : src16 && (x3 ? (l.wigx3 && M >= g_x3_min_m) : (dtype == 1 && l.wig16));
+        if (want16) {
+            lp.path = PATH_IGEMM_BF16; lp.x3 = x3;
+            choose_igemm(l, M, t.nphases, t.ntaps * ((x3 ? 3 : 1) * l.cin() / 64), &lp.tile, &lp.splits, &lp.kg, x3 ? 2 : 1);
+        } else {
+            choose_igemm(l, M, t.nphases, t.ntaps * (l.cin() / 32), &lp.tile, &lp.splits, &lp.kg);
+        }
+    }
+    // the weight-streaming layers with few rows: output-stationary, one node, no slabs (ry_c2d_os) -- exact fp32 layers only
+    if (f.path ? f.path == PATH_OS2D : lp.path == PATH_IGEMM && l.w2os && !(f.os2_set && f.os2[0] == 0)) {
+        int c[4] = {f.os2[0], f.os2[1], f.os2[2], f.os2[3]};
+        const int U = t.ntaps * (l.cin() / 64);
+        double cost = 0.0;
+        if (choose_os2(M, l.cout, t.nphases, U, &c[0], &c[1], &c[2], &c[3], &cost) && (f.os2_set || cost * U <= (double)g_os2_maxcost)) {
+            lp.path = PATH_OS2D; lp.splits = 1; lp.kg = 1;
+            lp.os2_mt4 = c[0]; lp.os2_nt4 = c[1]; lp.os2_waves = c[2]; lp.os2_depth = c[3];
+        } else if (f.os2_set) {
+            if (f.path) return fail(RY_EINVAL, "no output-stationary slice %d:%d:%d:%d for this shape", c[0], c[1], c[2], c[3]);
+            return fail(RY_EINVAL, "RY_OS2: no output-stationary slice %d:%d:%d:%d for %s", c[0], c[1], c[2], c[3], l.name);
+        }
+    }
+    // the MFMA-bound k4 s2 p1 layers: Winograd F(2x2, 2x2), 9 / 16 of the matrix-pipe work -- exact-fp32 mode only (RY_WINOGRAD=0: the
+    // direct kernels, bit-exact reference; a layer whose direct plan RY_PLAN fixes stays direct)
+    if (f.path ? f.path == PATH_WINO
+               : lp.path == PATH_IGEMM && dtype == 0 && g_wino && wino_eligible(l, 2) && !(f.wino_set && f.wino[0] == 0) && !f.fixed()) {
+        const int Mh = l.deconv ? lp.Hi : lp.Ho, Mw = l.deconv ? lp.Wi : lp.Wo;
+        int c[3] = {f.wino[0], f.wino[1], f.wino[2]};
+        const int npatches = (l.deconv ? 1 : 4) * (l.cin() / 16);
+        if ((f.wino_set || M >= g_wino_min_m) && choose_wino(Mh, Mw, l.cout, t.nphases, npatches, B, &c[0], &c[1], &c[2])) {
+            lp.path = PATH_WINO; lp.wino_cfg = c[0]; lp.wino_mbw = c[1]; lp.splits = c[2]; lp.kg = 1; lp.tile = 0;
+        } else if (f.wino_set) {
+            if (f.path) return fail(RY_EINVAL, "no Winograd plan %d:%d:%d for a %d x %d grid", c[0], c[1], c[2], Mh, Mw);
+            return fail(RY_EINVAL, "RY_WINO: no Winograd plan %d:%d:%d for %s", c[0], c[1], c[2], l.name);
+        }
+    }
+    if (lp.path == 0) {                                      // no implicit-GEMM layout
+        lp.path = f.path ? f.path : PATH_DIRECT; lp.splits = 1;
+        if (!f.path && !l.deconv && l.k == 3 && l.stride == 1 && l.pad == 1) {
+            if (l.src_a < 0 && l.cin() == 1 && l.cout % 4 == 0) lp.path = PATH_FIRST;
+            if (out_layer && l.cout == 1 && l.cin() % 128 == 0 && l.cin_a % 4 == 0) lp.path = PATH_LAST;   // exp / edge-pad / crop of SuperResolution.convert fused into the last layer
+        }
+        if (lp.path == PATH_LAST) {
+            lp.last_rows = lp.Ho;             // convert mode: overwritten with n_frames at enqueue time
+            lp.last_cols = mode == 1 ? lp.Wo + 1 : lp.Wo;
+            lp.last_exp = mode == 1;
+        }
+    }
+    if (lp.splits > 1) {
+        const size_t out_elems = (size_t)B * lp.Ho * lp.Wo * l.cout;
+        RY_TRY(arena.alloc(&lp.slabs, out_elems * lp.splits));
+        RY_TRY(poison_fill(ctx, lp.slabs, out_elems * lp.splits));
+    }
+    return RY_OK;
+}
+
 int build_plan(ry_net* net, Plan& P) {
     const ry_net_desc& d = net->desc;
     const int nd = d.ndim, B = P.B;
@@ -715,81 +893,13 @@ int build_plan(ry_net* net, Plan& P) {
             RY_TRY(P.arena.alloc(&lp.raw, out_elems * lp.splits));
         } else {
             RY_TRY(alloc_ztail(net->ctx, P.arena, &lp.out, out_elems));
-            if (l.wig) {
-                const TapTable t = make_taps(l);
-                const int M = B * (l.deconv ? lp.Hi * lp.Wi : lp.Ho * lp.Wo);
-                const int nk = t.ntaps * (l.cin() / 32);
-                lp.path = PATH_IGEMM; lp.tile = 0; lp.splits = 0; lp.kg = 0;
-                { lp.tile = g_force[i][0]; lp.splits = g_force[i][1]; lp.kg = g_force[i][2]; }
-                if (lp.tile != 0) {                                  // RY_PLAN: refuse a tile that does not divide the output channels
-                    int fbm, fbn; tile_dims(lp.tile, &fbm, &fbn);
-                    if (l.cout % fbn != 0) return fail(RY_EINVAL, "RY_PLAN: tile %dx%d does not divide the %d output channels of %s", fbm, fbn, l.cout, l.name);
-                    if (net->dtype != 0 && fbm > 128) return fail(RY_EINVAL, "RY_PLAN: no bf16 instantiation of the %dx%d tile (%s)", fbm, fbn, l.name);
-                }
-                // bf16 mode: a layer runs on bf16 operands when its filters were converted and every producer it reads can
-                // write a bf16 copy of its output (the first layer, implicit-GEMM layers and their reduce kernels can)
-                // split-bf16 mode: the same, for the layers with enough rows to be bound by the matrix pipe (the weight-streaming
-                // layers at the bottom of the U-Net would read 1.5 x the filter bytes: they stay exact fp32)
-                const bool x3 = net->dtype == 2;
-                bool want16 = x3 ? (l.wigx3 && M >= g_x3_min_m) : (net->dtype == 1 && l.wig16);
-                for (int src : {l.src_a, l.src_b}) {
-                    if (src < 0) continue;
-                    const LayerPlan& sp = P.lp[src];
-                    // that producer cannot write a bf16 copy
-                    if (sp.path != PATH_FIRST && sp.path != PATH_IGEMM && sp.path != PATH_IGEMM_BF16 && sp.path != PATH_OS2D) want16 = false;
-                }
-                if (l.src_a < 0) want16 = false;
-                if (want16) {
-                    lp.path = PATH_IGEMM_BF16; lp.x3 = x3;
-                    choose_igemm(l, M, t.nphases, t.ntaps * ((x3 ? 3 : 1) * l.cin() / 64), &lp.tile, &lp.splits, &lp.kg, x3 ? 2 : 1);
-                } else {
-                    choose_igemm(l, M, t.nphases, nk, &lp.tile, &lp.splits, &lp.kg);
-                }
-                // the weight-streaming layers with few rows: output-stationary, one node, no slabs (ry_c2d_os) -- exact fp32 layers only
-                if (lp.path == PATH_IGEMM && l.w2os && !(g_os2_forced[i] && g_os2_force[i][0] == 0)) {
-                    int c[4] = {0, 0, 0, 0};
-                    if (g_os2_forced[i]) for (int q = 0; q < 4; ++q) c[q] = g_os2_force[i][q];
-                    const int U = t.ntaps * (l.cin() / 64);
-                    double cost = 0.0;
-                    if (choose_os2(M, l.cout, t.nphases, U, &c[0], &c[1], &c[2], &c[3], &cost) && (g_os2_forced[i] || cost * U <= (double)g_os2_maxcost)) {
-                        lp.path = PATH_OS2D; lp.splits = 1; lp.kg = 1;
-                        lp.os2_mt4 = c[0]; lp.os2_nt4 = c[1]; lp.os2_waves = c[2]; lp.os2_depth = c[3];
-                    } else if (g_os2_forced[i]) {
-                        return fail(RY_EINVAL, "RY_OS2: no output-stationary slice %d:%d:%d:%d for %s", c[0], c[1], c[2], c[3], l.name);
-                    }
-                }
-                // the MFMA-bound k4 s2 p1 layers: Winograd F(2x2, 2x2), 9 / 16 of the matrix-pipe work -- exact-fp32 mode only (RY_WINOGRAD=0: the
-                // direct kernels, bit-exact reference)
-                if (lp.path == PATH_IGEMM && net->dtype == 0 && g_wino && wino_eligible(l, 2) && !(g_wino_forced[i] && g_wino_force[i][0] == 0) &&
-                    !(g_force[i][0] || g_force[i][1] || g_force[i][2])) {                  // (a layer whose direct plan RY_PLAN fixes stays direct)
-                    const int Mh = l.deconv ? lp.Hi : lp.Ho, Mw = l.deconv ? lp.Wi : lp.Wo;
-                    int c[3] = {0, 0, 0};
-                    if (g_wino_forced[i]) { c[0] = g_wino_force[i][0]; c[1] = g_wino_force[i][1]; c[2] = g_wino_force[i][2]; }
-                    const int npatches = (l.deconv ? 1 : 4) * (l.cin() / 16);
-                    if ((g_wino_forced[i] || M >= g_wino_min_m) && choose_wino(Mh, Mw, l.cout, t.nphases, npatches, B, &c[0], &c[1], &c[2])) {
-                        lp.path = PATH_WINO; lp.wino_cfg = c[0]; lp.wino_mbw = c[1]; lp.splits = c[2]; lp.kg = 1; lp.tile = 0;
-                        const float* ww = nullptr;
-                        RY_TRY(ensure_wwin(net, i, &ww));
-                    } else if (g_wino_forced[i]) {
-                        return fail(RY_EINVAL, "RY_WINO: no Winograd plan %d:%d:%d for %s", c[0], c[1], c[2], l.name);
-                    }
-                }
-                if (lp.splits > 1) {
-                    RY_TRY(P.arena.alloc(&lp.slabs, out_elems * lp.splits));
-                    RY_TRY(poison_fill(net->ctx, lp.slabs, out_elems * lp.splits));
-                }
-            } else {
-                lp.path = PATH_DIRECT; lp.splits = 1;
-                if (!l.deconv && l.k == 3 && l.stride == 1 && l.pad == 1) {
-                    if (l.src_a < 0 && l.cin() == 1 && l.cout % 4 == 0) lp.path = PATH_FIRST;
-                    if (i == 15 && l.cout == 1 && l.cin() % 128 == 0 && l.cin_a % 4 == 0) {
-                        lp.path = PATH_LAST;      // exp / edge-pad / crop of SuperResolution.convert fused into the last layer
-                        lp.last_rows = lp.Ho;             // convert mode: overwritten with n_frames at enqueue time
-                        lp.last_cols = P.mode == 1 ? lp.Wo + 1 : lp.Wo;
-                        lp.last_exp = P.mode == 1;
-                    }
-                }
+            bool src16 = l.src_a >= 0;                       // the network input has no bf16 copy, nor has the output of a direct layer
+            for (int src : {l.src_a, l.src_b}) {
+                const int sp = src >= 0 ? P.lp[src].path : 0;
+                if (src >= 0 && sp != PATH_FIRST && sp != PATH_IGEMM && sp != PATH_IGEMM_BF16 && sp != PATH_OS2D) src16 = false;
             }
+            RY_TRY(plan_s2_layer(net->ctx, P.arena, l, lp, B, net->dtype, g_force[i], src16, i == 15, P.mode));
+            if (lp.path == PATH_WINO) RY_TRY(ensure_wwin(net, i, &lp.wwin));
         }
     }
     // bf16 mode: which copies of each activation are needed (fp32 for fp32 consumers and the caller, bf16 for bf16 consumers)
@@ -827,54 +937,46 @@ int build_plan(ry_net* net, Plan& P) {
     return RY_OK;
 }
 
+// RY_PLAN / RY_WINO / RY_OS2: comma-separated "layer:v1[:v2 ...]" entries, at least one value (the missing ones: 0); `take` checks the values and
+// stores them in the layer's record
+static int parse_force(const char* var, const char* syntax, bool (*take)(LayerForce& f, const int* v)) {
+    const char* e = getenv(var);
+    for (const char* q = e; q && *q; q = strchr(q, ',') ? strchr(q, ',') + 1 : nullptr) {
+        int i = -1, v[4] = {0, 0, 0, 0};
+        if (sscanf(q, "%d:%d:%d:%d:%d", &i, &v[0], &v[1], &v[2], &v[3]) < 2 || i < 0 || i >= 16 || !take(g_force[i], v))
+            return fail(RY_EINVAL, "%s: expected %s", var, syntax);
+    }
+    return RY_OK;
+}
+
 // process-wide A/B and diagnostic switches, read when a context is created
-// RY_PLAN="layer:tile:splits:kgroups,...": read when a context is created and again at every ry_net_set_dtype (which drops
-// the launch plans), so that one process can sweep plans (scripts/gpu_x3_plansweep.py, scripts/gpu_lanesweep.py)
+// RY_PLAN / RY_WINO / RY_OS2: read when a context is created and again at every ry_net_set_dtype (which drops the launch plans), so that one process can
+// sweep plans (scripts/gpu_x3_plansweep.py, scripts/gpu_lanesweep.py)
 int read_plan_env() {
-    memset(g_force, 0, sizeof(g_force));
-    memset(g_os2_force, 0, sizeof(g_os2_force)); memset(g_os2_forced, 0, sizeof(g_os2_forced));
+    for (LayerForce& f : g_force) f = LayerForce();
     g_os2_maxcost = 4608; g_os2_min_filter = (size_t)1 << 21;
     if (const char* e = getenv("RY_OS2_MAXCOST")) g_os2_maxcost = atoi(e);
     if (const char* e = getenv("RY_OS2_MINW")) g_os2_min_filter = (size_t)atoll(e);
-    memset(g_wino_force, 0, sizeof(g_wino_force)); memset(g_wino_forced, 0, sizeof(g_wino_forced));
     g_wino = 1; g_wino_min_m = 256;
     if (const char* e = getenv("RY_WINOGRAD")) g_wino = atoi(e);
     if (const char* e = getenv("RY_WINO_MINM")) g_wino_min_m = atoi(e);
-    if (const char* e = getenv("RY_WINO")) {
-        for (const char* q = e; q && *q; q = strchr(q, ',') ? strchr(q, ',') + 1 : nullptr) {
-            int i = -1, a = 0, b = 0, c = 0;
-            const int got = sscanf(q, "%d:%d:%d:%d", &i, &a, &b, &c);
-            if (got >= 2 && i >= 0 && i < 16 && a >= 0 && a <= 2 && b >= 0 && c >= 0) {
-                g_wino_forced[i] = true; g_wino_force[i][0] = a; g_wino_force[i][1] = got >= 3 ? b : 0; g_wino_force[i][2] = got >= 4 ? c : 0;
-            } else {
-                return fail(RY_EINVAL, "RY_WINO: expected layer:cfg[:mbw[:splits]][,...]");
-            }
-        }
-    }
+    RY_TRY(parse_force("RY_WINO", "layer:cfg[:mbw[:splits]][,...]", [](LayerForce& f, const int* v) {
+        if (v[0] < 0 || v[0] > 2 || v[1] < 0 || v[2] < 0) return false;
+        f.wino_set = true; f.wino[0] = v[0]; f.wino[1] = v[1]; f.wino[2] = v[2];
+        return true;
+    }));
     g_poison = 0;
     if (const char* e = getenv("RY_POISON")) g_poison = atoi(e);
-    if (const char* e = getenv("RY_OS2")) {
-        for (const char* q = e; q && *q; q = strchr(q, ',') ? strchr(q, ',') + 1 : nullptr) {
-            int i = -1, a = 0, b = 0, c = 0, d = 0;
-            const int got = sscanf(q, "%d:%d:%d:%d:%d", &i, &a, &b, &c, &d);
-            if (got >= 2 && i >= 0 && i < 16 && a >= 0 && b >= 0 && c >= 0 && d >= 0) {
-                g_os2_forced[i] = true; g_os2_force[i][0] = a; g_os2_force[i][1] = got >= 3 ? b : 0; g_os2_force[i][2] = got >= 4 ? c : 0; g_os2_force[i][3] = got >= 5 ? d : 0;
-            } else {
-                return fail(RY_EINVAL, "RY_OS2: expected layer:mt4[:nt4[:waves[:depth]]][,...]");
-            }
-        }
-    }
-    if (const char* e = getenv("RY_PLAN")) {
-        for (const char* q = e; q && *q; q = strchr(q, ',') ? strchr(q, ',') + 1 : nullptr) {
-            int i = -1, t = 0, sp = 0, kg = 0;
-            if (sscanf(q, "%d:%d:%d:%d", &i, &t, &sp, &kg) >= 2 && i >= 0 && i < 16 && t >= 0 && t <= TILE_96x128 && t != 2 && sp >= 0 && kg >= 0 && kg <= 2) {
-                g_force[i][0] = t; g_force[i][1] = sp; g_force[i][2] = kg;
-            } else {
-                return fail(RY_EINVAL, "RY_PLAN: expected layer:tile:splits:kgroups[,...]");
-            }
-        }
-    }
-    return RY_OK;
+    RY_TRY(parse_force("RY_OS2", "layer:mt4[:nt4[:waves[:depth]]][,...]", [](LayerForce& f, const int* v) {
+        if (v[0] < 0 || v[1] < 0 || v[2] < 0 || v[3] < 0) return false;
+        f.os2_set = true; f.os2[0] = v[0]; f.os2[1] = v[1]; f.os2[2] = v[2]; f.os2[3] = v[3];
+        return true;
+    }));
+    return parse_force("RY_PLAN", "layer:tile:splits:kgroups[,...]", [](LayerForce& f, const int* v) {
+        if (v[0] < 0 || v[0] > TILE_96x128 || v[0] == 2 || v[1] < 0 || v[2] < 0 || v[2] > 2) return false;
+        f.tile = v[0]; f.splits = v[1]; f.kg = v[2];
+        return true;
+    });
 }
 
 int read_env_switches() {
@@ -902,10 +1004,22 @@ unsigned short host_f2bf(float f) {
 
 float host_bf2f(unsigned short h) { const unsigned u = (unsigned)h << 16; float f; memcpy(&f, &u, 4); return f; }
 
+// bf16 filters of one layer from its fp32 fragment-order blocks (wig layout): blocks [..][C/32][64][32] -> [..][C/64][64][64], RNE
+static void build_wig16(const Layer& l, const std::vector<float>& w32, std::vector<unsigned short>& out) {
+    const TapTable t = make_taps(l);
+    const int C = l.cin(), N = l.cout;
+    const size_t outer = (size_t)t.nphases * (N / 64) * t.ntaps;
+    out.assign(outer * (size_t)C * 64, 0);
+    for (size_t o = 0; o < outer; ++o)
+        for (int c = 0; c < C; ++c)
+            for (int nl = 0; nl < 64; ++nl)
+                out[(o * (C / 64) + c / 64) * 4096 + wig16_inblock(nl, c % 64)] = host_f2bf(w32[(o * (C / 32) + c / 32) * 2048 + wig_inblock(nl, c % 32)]);
+}
+
 // Split-bf16 filters of one layer from its fp32 fragment-order blocks (wig layout): the K axis of each source (C channels) becomes
 // [W_hi | W_hi | W_lo] (3 C), matching the activations' [x_hi | x_lo | x_hi]: the kernel's plain bf16 contraction over that axis is
 // x_hi W_hi + x_lo W_hi + x_hi W_lo.  hi = bf16(w), lo = bf16(w - hi), both RNE.
-void build_wigx3(const Layer& l, const std::vector<float>& w32, std::vector<unsigned short>& out) {
+static void build_wigx3(const Layer& l, const std::vector<float>& w32, std::vector<unsigned short>& out) {
     const TapTable t = make_taps(l);
     const int C = l.cin(), N = l.cout, K3 = 3 * C;
     const size_t outer = (size_t)t.nphases * (N / 64) * t.ntaps;
@@ -923,3 +1037,21 @@ void build_wigx3(const Layer& l, const std::vector<float>& w32, std::vector<unsi
         }
 }
 
+// The bf16 (dtype 1: Layer::wig16) or split-bf16 (dtype 2: Layer::wigx3) filters of a stage-2 implicit-GEMM layer whose sources are whole 64-channel
+// chunks, built once from its fp32 blocks into `arena` (ry_net_set_dtype for predictors, ry_conv2d for the single operator)
+int prepare_bf16(ry_ctx* ctx, Arena& arena, Layer& l, int dtype) {
+    float*& dst = dtype == 2 ? l.wigx3 : l.wig16;
+    if (!l.wig || dst || l.cin_a % 64 != 0 || l.cin_b % 64 != 0) return RY_OK;
+    const TapTable t = make_taps(l);
+    std::vector<float> w32((size_t)t.nphases * l.cout * t.ntaps * l.cin());
+    RT_TRY(rt::d2h(w32.data(), l.wig, w32.size() * sizeof(float), ctx->stream));
+    RT_TRY(rt::stream_sync(ctx->stream));
+    std::vector<unsigned short> w16;
+    (dtype == 2 ? build_wigx3 : build_wig16)(l, w32, w16);
+    float* d = nullptr;
+    RY_TRY(arena.alloc(&d, (w16.size() + 1) / 2));
+    RT_TRY(rt::h2d(d, w16.data(), w16.size() * sizeof(unsigned short), ctx->stream));
+    RT_TRY(rt::stream_sync(ctx->stream));
+    dst = d;
+    return RY_OK;
+}

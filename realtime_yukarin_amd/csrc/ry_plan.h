@@ -8,44 +8,10 @@
 // ------------------------------------------------------------------------------------------------
 // host-side filter re-layout and BatchNormalization folding (once, at creation)
 // ------------------------------------------------------------------------------------------------
-static const int DECONV_KY[2][2] = {{1, 3}, {0, 2}};   // output parity p, tap t -> kernel index
 struct TapTable {
     int nphases = 1, ntaps = 1;
     int dy[4][16], dx[4][16], ky[4][16], kx[4][16], pdy[4], pdx[4];
 };
-
-// w(n, c, ky, kx) = the layer's filter element (any accessor: the Chainer blob, or the device's direct layout read back)
-template <class F>
-static void relayout_wino(const Layer& l, F w, std::vector<float>& out) {
-    const int C = l.cin(), N = l.cout;
-    const int nph = l.deconv ? 4 : 1, nsl = l.deconv ? C / 8 : (C / 16) * 8;
-    out.assign((size_t)nph * N * nsl * 72, 0.f);
-    static const double G[3][2] = {{1, 0}, {1, 1}, {0, 1}};
-    for (int ph = 0; ph < nph; ++ph)
-        for (int n = 0; n < N; ++n)
-            for (int ks = 0; ks < nsl; ++ks)
-                for (int cc = 0; cc < 8; ++cc) {
-                    int c; double g[2][2];
-                    if (l.deconv) {
-                        c = ks * 8 + cc;
-                        for (int a = 0; a < 2; ++a)
-                            for (int b = 0; b < 2; ++b) g[a][b] = w(n, c, DECONV_KY[ph >> 1][1 - a], DECONV_KY[ph & 1][1 - b]);
-                    } else {
-                        const int par = (ks >> 1) & 3;
-                        c = (ks >> 3) * 16 + (ks & 1) * 8 + cc;
-                        for (int a = 0; a < 2; ++a)
-                            for (int b = 0; b < 2; ++b) g[a][b] = w(n, c, 2 * a + (par >> 1), 2 * b + (par & 1));
-                    }
-                    for (int i = 0; i < 3; ++i)
-                        for (int j = 0; j < 3; ++j) {
-                            double u = 0.0;
-                            for (int a = 0; a < 2; ++a)
-                                for (int b = 0; b < 2; ++b) u += G[i][a] * g[a][b] * G[j][b];
-                            const size_t piece = ((((size_t)ph * (N / 64) + n / 64) * nsl + ks) * 9 + (i * 3 + j)) * 2 + (n % 64) / 32;
-                            out[piece * 256 + (size_t)((32 * (cc >> 2) + n % 32) * 4 + (cc & 3))] = (float)u;
-                        }
-                }
-}
 
 // Activation buffers that an implicit-GEMM layer may read end in ZTAIL zeroed floats: the LDS-DMA kernel fetches its padding
 // from there (RyConvGeom::zoff1 / zoff2); nothing ever writes them.
@@ -69,28 +35,41 @@ static const size_t ZTAIL = 2048;
 // (what the other window lane's kernels leave free on a CU).
 static constexpr bool os2_xl_ok(int mt4, int waves, int depth) { return depth == 2 && mt4 * waves <= 32; }
 
+// One layer's override of the stage-2 planner: RY_PLAN / RY_WINO / RY_OS2 for the layers of a predictor (read_plan_env), the path and tile
+// arguments of ry_conv2d for the single operator.  Zeros: the planner's choice.
+struct LayerForce {
+    int tile = 0, splits = 0, kg = 0;                   // RY_PLAN: implicit-GEMM tile, external splits, K groups
+    bool wino_set = false; int wino[3] = {0, 0, 0};     // RY_WINO: cfg (0: the layer stays off the Winograd form), M-blocks per tile row, splits
+    bool os2_set = false; int os2[4] = {0, 0, 0, 0};    // RY_OS2: mt4 (0: the layer stays on the implicit GEMM), nt4, waves, depth
+    int path = 0;                                       // ry_conv2d: the path the caller names, run whatever the switches say (0: the planner's)
+    bool fixed() const { return tile || splits || kg; } // RY_PLAN fixes the layer's implicit-GEMM plan
+};
+
+// The rows one enqueue of a plan computes (plan_window_rows): rows [k0, k1) of the window are kept; layer i runs on crop_hi[i] input rows from
+// crop_lo[i] (0: all) and leaves output rows [hole_lo[i], hole_lo[i] + hole_n[i]) to ry_rep_rows (0: none)
+struct WindowRows {
+    int k0 = 0, k1 = 0;
+    int crop_lo[16] = {}, crop_hi[16] = {}, hole_lo[16] = {}, hole_n[16] = {};
+};
+
 // ---- what the units share (definitions: ry_plan.cpp / ry_exec.cpp) ----
 std::vector<Layer> build_topology(const ry_net_desc& d);
 size_t ipow(size_t b, int e);
 size_t layer_param_count(const Layer& l, int ndim);
 int check_desc(const ry_net_desc* d);
 TapTable make_taps(const Layer& l);
-float w2d_at(const Layer& l, const float* W, int n, int c, int ky, int kx);
-size_t wig_inblock(int nl, int k);
-size_t wig16_inblock(int nl, int k);
-void relayout_igemm(const Layer& l, const float* W, std::vector<float>& out);
 bool wino_eligible(const Layer& l, int ndim);
 int prepare_layer(ry_ctx* ctx, Arena& arena, Layer& l, int ndim, float eps, const float* W, const float* b, const float* bn, bool want_os2 = false);
+int prepare_bf16(ry_ctx* ctx, Arena& arena, Layer& l, int dtype);
+int upload_wwin(ry_ctx* ctx, Arena& arena, const Layer& l, float** out);
 int alloc_ztail(ry_ctx* ctx, Arena& arena, float** p, size_t nfloats);
 int poison_fill(ry_ctx* ctx, float* p, size_t nfloats);       // RY_POISON: NaN patterns over a buffer a launch is about to write (else nothing)
 void tile_dims(int tile, int* bm, int* bn);
-extern int g_s2_hole;
-extern int g_s2_crop;
-extern int g_force[16][3];
 extern int g_x3_min_m;
 extern int g_autotune;
 extern int g_autotune_reps, g_autotune_max;
 extern int g_autotune_pick;
+bool layer_plan_fixed(int i);
 const char* tile_name(int tile, int kg, bool bf16, int patch);
 int tile_occ(int tile, int kg);
 double est_time(long blocks, int bm, int bn, int s, int occ, int kg, int M, int N, int nk);
@@ -105,6 +84,8 @@ int c1d_tile_len(int mode);
 int choose_splits_1d(const Layer& l, int B, int rows, int mode);
 bool plan_tile_rows(const LayerPlan& lp, int Mh, int Mw, int* th, int* tw_out = nullptr);
 bool plan_hole_ok(const Layer& l, const LayerPlan& lp, int lo, int n);
+int plan_s2_layer(ry_ctx* ctx, Arena& arena, const Layer& l, LayerPlan& lp, int B, int dtype, const LayerForce& f, bool src16, bool out_layer, int mode);
+WindowRows plan_window_rows(const ry_net* net, const Plan& P);
 int build_plan(ry_net* net, Plan& P);
 int autotune_plan(ry_net* net, Plan& P);
 int get_plan(ry_net* net, int B, int T, int mode, int n_frames, Plan** out);
@@ -113,5 +94,4 @@ int read_plan_env();
 int read_env_switches();
 unsigned short host_f2bf(float f);
 float host_bf2f(unsigned short h);
-void build_wigx3(const Layer& l, const std::vector<float>& w32, std::vector<unsigned short>& out);
 int profile_plan(ry_net* net, Plan* P, int reps, ry_kernel_stat* stats, int max_stats, int* n_stats);
