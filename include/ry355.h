@@ -105,6 +105,14 @@ int ry_sr_convert_rows(ry_net* net, const float* sp, float* out, int batch, int 
  * (4*Cout floats) or NULL.  k <= 4; transposed requires k4 s2 p1.  splits = 0 lets the library choose. */
 int ry_conv1d(ry_ctx* ctx, const float* x, int B, int L, int Cin, const float* W, const float* bias, const float* bn,
               int Cout, int k, int stride, int pad, int dilate, int transposed, int act, int splits, float* y);
+/* the same layer on the output-stationary stage-1 kernel of the predictors (ry_c1d_os), one launch.  xa [B][rows][Ca] with rows = Lin, or
+ * n_real when n_real > 0 (the fused pad of the convert wrapper: rows n_real .. Lin - 1 are the per-channel minimum of the real rows; one source
+ * of at most 64 channels into a stride-1 layer); xb [B][Lin][Cb] the second source of a skip concat, or NULL with Cb = 0.  W over Ca + Cb input
+ * channels as in ry_conv1d, k <= 4, no dilation; the kernel takes k4 s2 p1 (de)convolutions and stride-1 convolutions with pad <= 3, no GLU.
+ * Slice cb x tp: 4x8, 4x4, 2x8 or 2x4 (no 4x8 for a deconvolution; 2x4 only when Cb > 0 and Ca % 64 != 0), 0 / 0 = the planner's pick.
+ * keep: rows stored per window, 0 = all Lout.  y [B][keep][Cout].  Other inputs are refused with RY_EINVAL. */
+int ry_conv1d_os(ry_ctx* ctx, const float* xa, const float* xb, int B, int Lin, int Ca, int Cb, const float* W, const float* bias, const float* bn,
+                 int Cout, int k, int stride, int pad, int transposed, int act, int cb, int tp, int n_real, int keep, float* y);
 /* L.Convolution2D / L.Deconvolution2D.  x [B][H][W][Cin] -> y [B][Ho][Wo][Cout].  path: 0 auto, 1 implicit-GEMM (MFMA),
  * 2 direct (VALU), 3 SR first layer (1 -> N, 3x3), 4 SR last layer (C -> 1, 3x3, channels read as two sources), 5 implicit-GEMM with bf16 operands,
  * 6 implicit-GEMM in split-bf16 form (x_hi w_hi + x_lo w_hi + x_hi w_lo, fp32 accumulate; the input is split on the host here); tile: 0 auto, 1 = 128x128, 3 = 64x128, 4 = 32x128, 5 = 128x64, 6 = 96x128 (+16: two K groups per workgroup, +32: one). */

@@ -803,6 +803,52 @@ int ry_conv1d(ry_ctx* ctx, const float* x, int B, int L, int Cin, const float* W
     return RY_OK;
 }
 
+int ry_conv1d_os(ry_ctx* ctx, const float* xa, const float* xb, int B, int Lin, int Ca, int Cb, const float* W, const float* bias, const float* bn,
+                 int Cout, int k, int stride, int pad, int transposed, int act, int cb, int tp, int n_real, int keep, float* y) {
+    if (!ctx || !xa || !W || !y || (Cb > 0 && !xb)) return fail(RY_EINVAL, "null argument");
+    if (B < 1 || Lin < 1 || Ca < 1 || Cb < 0 || Cout < 1 || k < 1 || stride < 1 || pad < 0 || n_real < 0 || keep < 0 || act < RY_ACT_NONE || act > RY_ACT_GLU)
+        return fail(RY_EINVAL, "bad conv1d_os shape");
+    if (transposed && !(k == 4 && stride == 2 && pad == 1)) return fail(RY_EINVAL, "transposed conv1d supports k4 s2 p1 only");
+    Layer l;
+    snprintf(l.name, sizeof l.name, "conv1d_os");
+    l.deconv = transposed != 0; l.bn = bn != nullptr; l.k = k; l.stride = stride; l.pad = pad; l.dil = 1;
+    l.cin_a = Ca; l.cin_b = Cb; l.cout = Cout; l.act = act;
+    if (!c1d_os_capable(l)) return fail(RY_EINVAL, "the output-stationary kernel takes k4 s2 p1 (de)convolutions and stride-1 convolutions with k <= 4 and pad <= 3, without GLU");
+    const int mode = c1d_mode(l);
+    LayerPlan lp;
+    lp.Wi = Lin;
+    lp.Wo = transposed ? 2 * Lin : (Lin + 2 * pad - (k - 1) - 1) / stride + 1;
+    if (lp.Wo < 1) return fail(RY_EINVAL, "conv1d_os output would be empty");
+    if (keep == 0) keep = lp.Wo;
+    if (keep > lp.Wo) return fail(RY_EINVAL, "keep %d exceeds the %d output rows", keep, lp.Wo);
+    if (n_real > 0 && (mode != RY_C1D_S1 || Ca > 64 || Cb > 0 || n_real > Lin))
+        return fail(RY_EINVAL, "the fused pad takes one source of at most 64 channels into a stride-1 layer, n_real <= Lin");
+    // the planner's slice, or the caller's: every slice with an instantiation
+    plan_s1_os(l, lp, B);
+    if (cb != 0 || tp != 0) {
+        if (!((cb == 4 || cb == 2) && (tp == 8 || tp == 4)) || (transposed && cb * tp == 32))
+            return fail(RY_EINVAL, "no ry_c1d_os instantiation for slice %dx%d%s", cb, tp, transposed ? " of a deconvolution" : "");
+        if (Cb > 0 && Ca % 64 != 0 && !(cb == 2 && tp == 4)) return fail(RY_EINVAL, "sources that split inside a wave run the 2x4 slice only");
+        lp.os_cb = cb; lp.os_tp = tp;
+    }
+    RT_TRY(rt::set_device(ctx->device));
+    Arena arena;
+    RY_TRY(prepare_layer(ctx, arena, l, 1, 2e-5f, W, bias, bn));
+    const size_t na = (size_t)B * (n_real > 0 ? n_real : Lin) * Ca, nb = (size_t)B * Lin * Cb, ny = (size_t)B * keep * Cout;
+    float *da = nullptr, *db = nullptr, *dy = nullptr;
+    RY_TRY(arena.alloc(&da, na));
+    if (Cb > 0) RY_TRY(arena.alloc(&db, nb));
+    RY_TRY(arena.alloc(&dy, ny));
+    RY_TRY(poison_fill(ctx, dy, ny));                                       // RY_POISON: an output element the launch leaves unwritten reads as NaN
+    RT_TRY(rt::h2d(da, xa, na * sizeof(float), ctx->stream));
+    if (Cb > 0) RT_TRY(rt::h2d(db, xb, nb * sizeof(float), ctx->stream));
+    Launcher Lc{nullptr, ctx, ctx->stream, nullptr, nullptr};
+    RY_TRY(launch_c1d_os(Lc, l, lp, B, da, Ca, db, Cb, dy, keep, 0.2f, n_real));
+    RT_TRY(rt::d2h(y, dy, ny * sizeof(float), ctx->stream));
+    RT_TRY(rt::stream_sync(ctx->stream));
+    return RY_OK;
+}
+
 int ry_conv2d(ry_ctx* ctx, const float* x, int B, int H, int Wd, int Cin, const float* Wt, const float* bias, const float* bn,
               int Cout, int k, int stride, int pad, int transposed, int act, int path, int tile, int splits, float* y) {
     return ry_conv2d_dilated(ctx, x, B, H, Wd, Cin, Wt, bias, bn, Cout, k, stride, pad, 1, transposed, act, path, tile, splits, y);

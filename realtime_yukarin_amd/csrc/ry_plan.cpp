@@ -626,7 +626,7 @@ int choose_splits_1d(const Layer& l, int B, int rows, int mode) {
 // 0.116 ms)
 static const int g_s1_units = 256;
 
-static bool c1d_os_capable(const Layer& l) {
+bool c1d_os_capable(const Layer& l) {
     const int mode = c1d_mode(l);
     return mode != RY_C1D_GEN && l.act != RY_ACT_GLU && l.k <= 4;
 }
@@ -649,6 +649,14 @@ static void choose_os(const Layer& l, int B, int rows, int* cb, int* tp) {
         if (units > best_units || (units == best_units && waste < best_waste)) { best = c; best_units = units; best_waste = waste; }
     }
     *cb = CF[best][0]; *tp = CF[best][1];
+}
+
+// the launch shape of one stage-1 layer in output-stationary form (Wi / Wo set), for predictors (build_plan) and the single operator (ry_conv1d_os)
+void plan_s1_os(const Layer& l, LayerPlan& lp, int B) {
+    lp.os_kt = c1d_os_ktw(l.cin());
+    choose_os(l, B, l.deconv ? lp.Wi : lp.Wo, &lp.os_cb, &lp.os_tp);
+    // sources split inside a wave: the per-lane form exists for this slice only
+    if (l.cin_b > 0 && l.cin_a % 64 != 0) { lp.os_cb = 2; lp.os_tp = 4; }
 }
 
 // The Winograd filters of predictor layer i, built when a plan first takes the layer onto that path and kept in the arena the clones of the predictor share
@@ -880,17 +888,17 @@ int build_plan(ry_net* net, Plan& P) {
         LayerPlan& lp = P.lp[i];
         const size_t out_elems = (size_t)B * lp.Ho * lp.Wo * l.cout;
         if (nd == 1 && P.s1_os) {
-            const int mode = c1d_mode(l);
-            lp.os_kt = c1d_os_ktw(l.cin());
-            choose_os(l, B, mode == RY_C1D_DECONV ? lp.Wi : lp.Wo, &lp.os_cb, &lp.os_tp);
-            // sources split inside a wave: the per-lane form exists for this slice only
-            if (l.cin_b > 0 && l.cin_a % 64 != 0) { lp.os_cb = 2; lp.os_tp = 4; }
-            if (i < 15) RY_TRY(P.arena.alloc(&lp.out, out_elems));          // the last layer stores straight into the caller's block
+            plan_s1_os(l, lp, B);
+            if (i < 15) {                                                    // the last layer stores straight into the caller's block
+                RY_TRY(P.arena.alloc(&lp.out, out_elems));
+                RY_TRY(poison_fill(net->ctx, lp.out, out_elems));
+            }
         } else if (nd == 1) {
             const int mode = c1d_mode(l);
             lp.splits = choose_splits_1d(l, B, mode == RY_C1D_DECONV ? lp.Wi : lp.Wo, mode);
             lp.slab_stride = (long long)out_elems;
             RY_TRY(P.arena.alloc(&lp.raw, out_elems * lp.splits));
+            RY_TRY(poison_fill(net->ctx, lp.raw, out_elems * lp.splits));
         } else {
             RY_TRY(alloc_ztail(net->ctx, P.arena, &lp.out, out_elems));
             bool src16 = l.src_a >= 0;                       // the network input has no bf16 copy, nor has the output of a direct layer
@@ -931,6 +939,7 @@ int build_plan(ry_net* net, Plan& P) {
     RY_TRY(P.arena.alloc(&P.user_out, P.user_out_floats));
     if (P.mode == 1) {
         RY_TRY(P.arena.alloc(&P.x_in, (size_t)B * P.T * (nd == 1 ? d.in_ch : d.width)));
+        RY_TRY(poison_fill(net->ctx, P.x_in, (size_t)B * P.T * (nd == 1 ? d.in_ch : d.width)));
     } else {
         P.x_in = nullptr;                      // raw forward reads the caller's block directly (cur_in)
     }

@@ -82,6 +82,8 @@ bool choose_wino(int Mh, int Mw, int N, int nphases, int npatches, int B, int* c
 int c1d_mode(const Layer& l);
 int c1d_tile_len(int mode);
 int choose_splits_1d(const Layer& l, int B, int rows, int mode);
+bool c1d_os_capable(const Layer& l);
+void plan_s1_os(const Layer& l, LayerPlan& lp, int B);        // ry_c1d_os: ci waves per position group (os_kt) and the slice (os_cb x os_tp) of a stage-1 layer
 bool plan_tile_rows(const LayerPlan& lp, int Mh, int Mw, int* th, int* tw_out = nullptr);
 bool plan_hole_ok(const Layer& l, const LayerPlan& lp, int lo, int n);
 int plan_s2_layer(ry_ctx* ctx, Arena& arena, const Layer& l, LayerPlan& lp, int B, int dtype, const LayerForce& f, bool src16, bool out_layer, int mode);

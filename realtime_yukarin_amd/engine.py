@@ -98,6 +98,30 @@ class Context(object):
                                               Cout, k, stride, pad, dilate, int(bool(transposed)), a, int(splits), _lib._fptr(y)))
         return y
 
+    def conv1d_os(self, xa, W, b=None, bn=None, stride=1, pad=0, transposed=False, act=None, xb=None, tile=None, pad_to=0, keep=0):
+        """The layer of `conv1d` on the predictors' output-stationary stage-1 kernel (ry_c1d_os), one launch.  xa (B, L, Ca) and xb (B, L, Cb) or
+        None: the two sources of a skip concat, W over Ca + Cb input channels.  tile = (cb, tp) slice, None = the planner's pick.  pad_to > 0: the
+        fused pad of the convert wrapper -- xa holds the n_real = xa.shape[1] real rows of each window, the kernel reads rows n_real .. pad_to - 1
+        as the per-channel minimum of the real rows (L = pad_to).  keep: rows stored per window (0 = all).  -> (B, keep or Lout, Cout)."""
+        xa = numpy.ascontiguousarray(xa, dtype=numpy.float32)
+        W = numpy.ascontiguousarray(W, dtype=numpy.float32)
+        B, rows, Ca = xa.shape
+        xbv = None if xb is None else numpy.ascontiguousarray(xb, dtype=numpy.float32)
+        Cb = 0 if xbv is None else xbv.shape[2]
+        L = int(pad_to) if pad_to else rows
+        assert xbv is None or xbv.shape[:2] == (B, L), (xa.shape, xbv.shape)
+        Cout = W.shape[1] if transposed else W.shape[0]
+        k = W.shape[2]
+        Lout = 2 * L if transposed else (L + 2 * pad - k) // stride + 1
+        y = numpy.empty((B, max(keep or Lout, 0), Cout), dtype=numpy.float32)
+        bnv = None if bn is None else numpy.ascontiguousarray(numpy.concatenate([numpy.ravel(v) for v in bn]), dtype=numpy.float32)
+        bv = None if b is None else numpy.ascontiguousarray(b, dtype=numpy.float32)
+        cb, tp = tile or (0, 0)
+        self.lib.check(self.lib.dll.ry_conv1d_os(self.handle, _lib._fptr(xa), _lib._fptr(xbv), B, L, Ca, Cb, _lib._fptr(W), _lib._fptr(bv),
+                                                 _lib._fptr(bnv), Cout, k, stride, pad, int(bool(transposed)), _lib.ACTS[act], int(cb), int(tp),
+                                                 rows if pad_to else 0, int(keep), _lib._fptr(y)))
+        return y
+
     def conv2d(self, x, W, b=None, bn=None, stride=1, pad=0, transposed=False, act=None, path='auto', tile=None, splits=0, dilate=1):
         """x (B, H, W, Cin) -> (B, Ho, Wo, Cout).  W (Cout,Cin,k,k) or transposed (Cin,Cout,k,k)."""
         x = numpy.ascontiguousarray(x, dtype=numpy.float32)

@@ -265,12 +265,17 @@ def x3_scaling_property(ctx, rng, case):
     return f(x, Wt), f(4.0 * x, Wt), f(x, Wt / 8.0)
 
 
-def run_conv1d(ctx, rng, case, bn_params):
+def conv1d_operands(rng, case, bn_params):
     B, L, Cin, Cout, k, s, p, d, tr, act, splits = case
     x = rng.normal(size=(B, L, Cin)).astype('f4')
     W = rng.normal(0, 0.1, size=(Cin, Cout, k) if tr else (Cout, Cin, k)).astype('f4')
     b = rng.normal(0, 0.1, Cout).astype('f4')
-    bn = bn_params(rng, Cout)
+    return x, W, b, bn_params(rng, Cout)
+
+
+def run_conv1d(ctx, rng, case, bn_params, operands=None):
+    B, L, Cin, Cout, k, s, p, d, tr, act, splits = case
+    x, W, b, bn = operands or conv1d_operands(rng, case, bn_params)
     y = ctx.conv1d(x, W, b, bn, stride=s, pad=p, dilate=d, transposed=tr, act=act, splits=splits)
     xn = x.transpose(0, 2, 1)
     r = ops.deconv_nd(xn, W, b, stride=s, pad=p) if tr else ops.conv_nd(xn, W, b, stride=s, pad=p, dilate=d)
@@ -524,3 +529,205 @@ X3_FULL_SIZE = [
     (1, 48, 64, 1024, 256, 4, 2, 1, True, 'relu', None, 0),        # decoder c4 (planner's tile / splits)
     (1, 96, 128, 256, 512, 4, 2, 1, False, 'relu', None, 0),       # encoder c3
 ]
+
+
+# ---- stage 1: the float64 reference of a 1-D layer and the branches of ry_c1d_os (tests/test_stage1_oracle.py) ----
+
+def ref_conv1d_f64(xa, xb, W, b, bn, stride, pad, dilate, transposed, act, n_real=0, keep=0):
+    """The 1-D operator in float64 on the CPU, the counterpart of ref_conv2d_f64: torch conv1d / conv_transpose1d on concat(xa, xb) over the
+    channels, the oracle's batch_norm_inference and apply_act.  xa (B, L, Ca), xb (B, L, Cb) or None, channels-last; W (Cout, Cin, k), or
+    (Cin, Cout, k) when transposed.  n_real > 0: the fused pad -- rows n_real .. L - 1 of xa are replaced by the column minimum of its real rows
+    (what xa holds there is ignored).  keep > 0: the first keep output rows.  -> (r, bound), both (B, keep or Lout, Cout') float64, Cout' = Cout / 2
+    for GLU.  bound = |s| (conv(|x|, |W|) + |b|) + |r| per element (s the folded BN scale); for GLU y = a sigmoid(g) it is B_a + |a| B_g / 4 + |y|
+    with B_a, B_g the pre-activation bounds of the two halves (sigmoid is 1/4-Lipschitz and below 1)."""
+    import torch
+    x = numpy.asarray(xa, numpy.float64)
+    if n_real > 0:
+        x = x.copy()
+        x[:, n_real:] = x[:, :n_real].min(axis=1, keepdims=True)
+    if xb is not None:
+        x = numpy.concatenate([x, numpy.asarray(xb, numpy.float64)], axis=2)
+    f = torch.nn.functional.conv_transpose1d if transposed else torch.nn.functional.conv1d
+    xt = torch.from_numpy(numpy.ascontiguousarray(x.transpose(0, 2, 1)))
+    wt = torch.from_numpy(numpy.asarray(W, numpy.float64))
+    cout = W.shape[1] if transposed else W.shape[0]
+    bb = numpy.zeros(cout) if b is None else numpy.asarray(b, numpy.float64)
+    kw = dict(stride=stride, padding=pad) if transposed else dict(stride=stride, padding=pad, dilation=dilate)
+    with torch.no_grad():
+        c = f(xt, wt, torch.from_numpy(bb), **kw).numpy()
+        ca = f(xt.abs(), wt.abs(), torch.from_numpy(numpy.abs(bb)), **kw).numpy()
+    if bn is not None:
+        bn64 = [numpy.asarray(v, numpy.float64) for v in bn]
+        c = ops.batch_norm_inference(c, *bn64)
+        s = numpy.abs(bn64[0] / numpy.sqrt(bn64[3] + ops.BN_EPS)).reshape(1, -1, 1)
+    else:
+        s = 1.0
+    pre = s * ca                                                   # bound of each pre-activation element
+    r = ops.apply_act(c, act)
+    if act == 'glu':
+        h = cout // 2
+        bound = pre[:, :h] + numpy.abs(c[:, :h]) * pre[:, h:] / 4 + numpy.abs(r)
+    else:
+        bound = pre + numpy.abs(r)
+    r, bound = r.transpose(0, 2, 1), bound.transpose(0, 2, 1)
+    if keep:
+        r, bound = r[:, :keep], bound[:, :keep]
+    return r, bound
+
+
+def stage1_operands(rng, B, L, Ca, Cb, Cout, k, transposed, trained=True):
+    """Sources, filters over Ca + Cb channels, bias and BN of one stage-1 layer.  trained: inputs behind a ReLU and filters ~ N(0, 0.02) as in
+    trained_like_operands; else signed inputs (a first layer's features) and filters ~ N(0, 0.1)."""
+    from conftest import bn_params
+    xa = rng.normal(size=(B, L, Ca)); xb = rng.normal(size=(B, L, Cb)) if Cb else None
+    if trained:
+        xa = numpy.maximum(xa, 0); xb = None if xb is None else numpy.maximum(xb, 0)
+    C = Ca + Cb
+    W = rng.normal(0, 0.02 if trained else 0.1, size=(C, Cout, k) if transposed else (Cout, C, k)).astype('f4')
+    return (xa.astype('f4'), None if xb is None else xb.astype('f4'), W, rng.normal(0, 0.1, Cout).astype('f4'), bn_params(rng, Cout))
+
+
+# Which instantiation and which loops of ry_c1d_os (ry_kernels.h) a launch takes, restated from the kernel and launch_c1d_os (ry_exec.cpp): labels for
+# the case lists only, never used by a correctness assertion.  Case form (B, L, Ca, Cb, Cout, k, stride, pad, transposed, act, (cb, tp), n_real, keep):
+# L = rows per window of the sources (the padded length when n_real > 0), the slice forced.
+
+def os1_of(case):
+    B, L, Ca, Cb, Cout, k, s, p, tr, act, tile, n_real, keep = case
+    mode = 2 if tr else 0 if (k, s, p) == (4, 2, 1) else 1
+    assert mode != 1 or (s == 1 and p <= 3), case
+    cb, tp = tile
+    ctot = Ca + Cb
+    kt = 1 if ctot <= 64 else 2 if ctot <= 128 else 4
+    pg = 4 // kt
+    tpo = 2 * tp if mode == 2 else tp
+    np_ = 2 * tp + 2 if mode == 0 else tp + 2 if mode == 2 else tp + 3
+    quad = (np_ + 4 * cb) * 4 + cb * tpo <= 200                    # the register budget of four channel sets in flight
+    lout = 2 * L if tr else (L + 2 * p - k) // s + 1
+    rows = L if tr else lout                                       # the axis the position tiles walk
+    loops = set()
+    for kw in range(kt):                                           # the channel-set loops of each ci wave
+        c0, step, seen = kw * 64, kt * 64, False
+        while quad and c0 + 3 * step < ctot:
+            c0 += 4 * step; loops.add('quad'); seen = True
+        while c0 + step < ctot:
+            c0 += 2 * step; loops.add('pair'); seen = True
+        if c0 < ctot:
+            loops.add('single'); seen = True
+        if not seen:
+            loops.add('empty wave')
+    usrc = Cb == 0 or Ca % 64 == 0
+    return dict(inst='<%d,%d,%d,%s,%s>' % (mode, cb, tp, 'true' if n_real else 'false', 'true' if usrc else 'false'), mode=mode, kt=kt,
+                loops=loops, lout=lout, ragged_tile=rows % (pg * tp) != 0, ctot=ctot)
+
+
+def os1_branches(case):
+    B, L, Ca, Cb, Cout, k, s, p, tr, act, tile, n_real, keep = case
+    o = os1_of(case)
+    out = {'inst ' + o['inst'], 'kt=%d' % o['kt']} | o['loops']
+    if Cout == 9:
+        out.add('Cout 9')
+    if Cout % tile[0]:
+        out.add('Cout %% %d != 0' % tile[0])
+    if o['ctot'] in (9, 65, 129, 523):
+        out.add('Ctot %d' % o['ctot'])
+    if o['ragged_tile']:
+        out.add('ragged last tile')
+    if B == 2:
+        out.add('B=2')
+    if keep and keep < o['lout']:
+        out.add('keep < Lout')
+    if o['mode'] == 0 and L == 2:
+        out.add('stride 2 from 2 rows to 1')
+    if o['mode'] == 2 and L == 1:
+        out.add('deconvolution from 1 row to 2')
+    if o['mode'] == 1:
+        out.add('S1 k=%d pad %d' % (k, p))
+    if Cb:
+        out.add('two sources, Ca %% 64 %s 0' % ('==' if Ca % 64 == 0 else '!='))
+    return out
+
+
+# what the forced-slice list must reach (tests/test_stage1_oracle.py::test_os1_cases_cover_every_branch)
+OS1_INSTANTIATIONS = {'inst <0,%d,%d,false,true>' % t for t in ((4, 8), (4, 4), (2, 8), (2, 4))} | {'inst <0,2,4,false,false>'} | \
+    {'inst <1,%d,%d,%s,true>' % (c, t, pm) for c, t in ((4, 8), (4, 4), (2, 8), (2, 4)) for pm in ('false', 'true')} | {'inst <1,2,4,false,false>'} | \
+    {'inst <2,%d,%d,false,true>' % t for t in ((4, 4), (2, 8), (2, 4))} | {'inst <2,2,4,false,false>'}
+OS1_BRANCHES = OS1_INSTANTIATIONS | {'kt=1', 'kt=2', 'kt=4', 'quad', 'pair', 'single', 'empty wave', 'Cout 9', 'Cout % 2 != 0', 'Cout % 4 != 0',
+                                     'Ctot 9', 'Ctot 65', 'Ctot 129', 'Ctot 523', 'ragged last tile', 'B=2', 'keep < Lout',
+                                     'stride 2 from 2 rows to 1', 'deconvolution from 1 row to 2',
+                                     'two sources, Ca % 64 == 0', 'two sources, Ca % 64 != 0'} | \
+    {'S1 k=%d pad %d' % (k, p) for k in (1, 3) for p in range(4)}
+
+# B, L, Ca, Cb, Cout, k, stride, pad, transposed, act, (cb, tp), n_real, keep
+OS1_CASES = [
+    # k4 s2 p1 convolution (mode 0)
+    (2, 66, 9, 0, 9, 4, 2, 1, False, 'lrelu', (4, 8), 0, 0),        # Ctot 9, Cout 9 on CB 4, batch 2, 33 rows on 32-row tiles
+    (1, 40, 65, 0, 10, 4, 2, 1, False, 'relu', (4, 4), 0, 0),       # Ctot 65: two ci waves of one set each; 20 rows on 8-row tiles
+    (1, 34, 129, 0, 7, 4, 2, 1, False, 'lrelu', (2, 8), 0, 0),      # Ctot 129: four ci waves, the last one without a channel set; Cout 7 on CB 2
+    (1, 2, 64, 0, 16, 4, 2, 1, False, 'lrelu', (2, 4), 0, 0),       # the U-Net's deepest encoder layer: 2 rows -> 1
+    (1, 20, 40, 30, 12, 4, 2, 1, False, 'lrelu', (2, 4), 0, 0),     # two sources split inside a wave (the per-lane form)
+    (1, 24, 1100, 0, 6, 4, 2, 1, False, None, (4, 4), 0, 5),        # 1100 channels: four sets in flight, then one; keep 5 of 12
+    # stride-1 convolution (mode 1): k 1 / 3, pad 0 .. 3
+    (1, 37, 9, 0, 9, 3, 1, 1, False, 'lrelu', (4, 8), 0, 0),        # encoder c0 shape, 37 rows on 32-row tiles
+    (2, 21, 64, 0, 64, 1, 1, 0, False, 'relu', (4, 4), 0, 0),       # a 'same' decoder layer
+    (1, 19, 9, 0, 9, 3, 1, 0, False, None, (2, 8), 0, 0),
+    (1, 13, 16, 0, 10, 3, 1, 2, False, 'lrelu', (2, 4), 0, 0),
+    (1, 11, 523, 0, 9, 3, 1, 3, False, 'lrelu', (4, 8), 0, 0),      # the 523-channel input: four ci waves, a pair and a single set
+    (1, 9, 65, 0, 11, 1, 1, 1, False, None, (4, 8), 0, 0),
+    (1, 15, 129, 0, 9, 1, 1, 2, False, 'relu', (2, 8), 0, 0),
+    (1, 10, 9, 0, 5, 1, 1, 3, False, 'lrelu', (2, 4), 0, 0),
+    (2, 30, 64, 64, 9, 3, 1, 1, False, None, (4, 4), 0, 27),        # decoder c7 shape: two sources on a wave boundary, keep < Lout
+    (1, 30, 40, 25, 9, 3, 1, 1, False, None, (2, 4), 0, 0),         # two sources split inside a wave
+    # k4 s2 p1 deconvolution (mode 2)
+    (1, 1, 64, 0, 16, 4, 2, 1, True, 'relu', (4, 4), 0, 0),         # the U-Net's deepest decoder layer: 1 row -> 2
+    (2, 11, 128, 64, 9, 4, 2, 1, True, 'relu', (2, 8), 0, 0),       # two sources on a wave boundary, 11 rows on 8-row tiles
+    (1, 7, 64, 64, 13, 4, 2, 1, True, 'relu', (2, 4), 0, 0),
+    (1, 5, 512, 512, 10, 4, 2, 1, True, 'relu', (4, 4), 0, 0),      # decoder c1's channels: four sets in flight per ci wave
+    (1, 9, 30, 35, 7, 4, 2, 1, True, 'relu', (2, 4), 0, 0),         # two sources split inside a wave
+]
+
+# the fused pad of the convert wrapper (mode 1, PADMIN): n_real real rows padded to L = n_real + 128 - n_real % 128 (netspec.pad_frames)
+OS1_PAD_CASES = [
+    (1, 128, 9, 0, 64, 3, 1, 1, False, 'lrelu', (4, 8), 1, 0),      # fewer real rows than the four row groups of the minimum
+    (1, 128, 1, 0, 16, 3, 1, 1, False, 'lrelu', (4, 4), 2, 0),
+    (1, 128, 64, 0, 9, 3, 1, 1, False, 'lrelu', (2, 8), 3, 0),
+    (2, 128, 9, 0, 64, 3, 1, 1, False, 'lrelu', (2, 4), 63, 0),     # around the 64-row stride of the minimum loop
+    (1, 128, 64, 0, 9, 1, 1, 0, False, None, (4, 8), 64, 0),
+    (1, 256, 1, 0, 10, 3, 1, 1, False, 'lrelu', (4, 4), 65, 0),
+    (1, 384, 9, 0, 64, 3, 1, 1, False, 'lrelu', (4, 8), 300, 0),    # encoder c0 of the 300-frame window
+    (1, 384, 64, 0, 12, 3, 1, 2, False, 'relu', (2, 8), 300, 0),
+]
+
+
+def syn64_stage1_layers(frames, stage1_in=9):
+    """[(case, name)] of the 16 layers of the SYN-64 stage-1 predictor in a convert of `frames` frames (T = frames + netspec.pad_frames(frames) rows),
+    in the case form of OS1_CASES with the planner's slice (None), shapes from netspec.param_list: encoder c0 takes the fused pad (n_real = frames),
+    decoder c1 .. c7 two sources (the decoder chain, the encoder skip), decoder c7 keeps the real frames."""
+    from realtime_yukarin_amd import netspec, synth
+    d = synth.model_descs('SYN-64', stage1_in)[0]
+    assert not d.glu
+    W = dict(netspec.param_list(d))
+    T = frames + netspec.pad_frames(frames)
+    out, enc_len, L = [], [], T
+    for i in range(8):
+        name = 'encoder/c%d' % i
+        co, ci, k = W[name + ('/W' if i == 0 else '/c/W')]
+        s, p = (1, k // 2) if i == 0 else (2, 1) if netspec.enc_sample(d, i) == 'down' else (1, 0)
+        out.append(((1, L, ci, 0, co, k, s, p, False, 'lrelu', None, frames if i == 0 else 0, 0), name))
+        L = (L + 2 * p - k) // s + 1
+        enc_len.append(L)
+    for j in range(8):
+        name = 'decoder/c%d' % j
+        if j == 7:
+            co, ci, k = W[name + '/W']
+            up, s, p = False, 1, k // 2
+        else:
+            up = netspec.dec_sample(d, j) == 'up'
+            w = W[name + '/c/W']
+            (ci, co, k), (s, p) = (w, (2, 1)) if up else ((w[1], w[0], w[2]), (1, 0))
+        cb = 0 if j == 0 else (d.base if j == 7 else netspec.ENC_CH[7 - j] * d.base)
+        assert cb == 0 or enc_len[7 - j if j < 7 else 0] == L, (name, L)
+        act = None if j == 7 else 'relu'
+        out.append(((1, L, ci - cb, cb, co, k, s, p, up, act, None, 0, frames if j == 7 else 0), name))
+        L = 2 * L if up else (L + 2 * p - k) // s + 1
+    assert L == T
+    return out

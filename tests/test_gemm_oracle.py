@@ -60,11 +60,17 @@ def test_sched_case_against_f64_emu(emu_ctx, monkeypatch, case):
 
 @pytest.mark.parametrize('case', cases.CONV1D_CASES, ids=_ids)
 def test_conv1d_poisoned_emu(emu_ctx, monkeypatch, case):
-    """ry_conv1d with its split-K slabs and output poisoned: every slab element the materialize step sums was written by the launch"""
+    """ry_conv1d (ry_conv1d_ws + ry_materialize: GLU, the generic mode) with its split-K slabs and output poisoned: every slab element the
+    materialize step sums was written by the launch, and every output element is within F32_TOL of float64 (tests/test_stage1_oracle.py: ry_c1d_os)"""
     from conftest import bn_params
+    ops = cases.conv1d_operands(numpy.random.default_rng(11), case, bn_params)
     with cases.poisoned(emu_ctx, monkeypatch):
-        y, r = cases.run_conv1d(emu_ctx, numpy.random.default_rng(11), case, bn_params)
+        y, r = cases.run_conv1d(emu_ctx, None, case, bn_params, operands=ops)
     assert numpy.isfinite(y).all() and rel_max(y, r) < cases.TOL
+    B, L, Cin, Cout, k, s, p, d, tr, act, splits = case
+    x, W, b, bn = ops
+    r64, bound = cases.ref_conv1d_f64(x, None, W, b, bn, s, p, d, tr, act)
+    _check('%s ry_conv1d' % _ids(case), y, r64, bound, F32_TOL, cases.TOL)
 
 
 # ---- GPU: the SYN-64 layers at full size ----
