@@ -285,6 +285,38 @@ int ry_crepe_debug_layer(ry_crepe* crepe, int layer, float* out);
 /* diagnostics: the split-K count of conv1 .. conv6 and the dense layer (7 ints). */
 int ry_crepe_debug_splits(ry_crepe* crepe, int* splits);
 
+/* ---- WORLD synthesizer (`pyworld.synthesize(f0, sp, ap, fs, frame_period)` in the reference's Vocoder.decode and world4py's realtime
+ * synthesizer in RealtimeVocoder.decode, yukarin_wrapper/vocoder.py:50-120).  Semantics: INTEGRATION.md section 10 and
+ * tests/world_synth_ref.py (WORLD's Synthesis restated; counter-based noise of `seed`, phase wrapped at every step).
+ * fft_size: 1024 (CheapTrick's size at 16 and 24 kHz) -- anything else is refused.  Frames: f0 [n_frames] float64 on the HOST (Hz; below
+ * fs / fft_size + 1 = unvoiced), sp / ap [n_frames][bins] float32 with bins = fft_size / 2 + 1, host pointers or, with on_device = 1, device
+ * pointers on the context's GPU (the rows stage 2 leaves there).  y: float64 samples on the HOST; every call returns after its samples are
+ * in y.  Refused: n_frames < 1, bins != fft_size / 2 + 1, a y too small, f0 that is not finite. */
+typedef struct ry_synth ry_synth;
+int ry_synth_create(ry_ctx* ctx, int fs, double frame_period_ms, int fft_size, unsigned seed, ry_synth** out);
+void ry_synth_destroy(ry_synth* synth);
+/* samples of a signal of n_frames frames: int((n_frames - 1) * frame_period / 1000 * fs) + 1 (negative: error) */
+int ry_synth_length(ry_synth* synth, int n_frames);
+/* One shot: the whole signal (ry_synth_length samples).  Drops a stream in progress. */
+int ry_synth_run(ry_synth* synth, const double* f0, const float* sp, const float* ap, int n_frames, int bins, int on_device,
+                 double* y, int y_capacity, int* n_out);
+/* Stream: after pushes of N1, N2, ... frames and a flush the concatenated output equals ry_synth_run on the concatenated frames bit for
+ * bit, for any cut.  A push returns only samples that can no longer change -- every pulse within fft_size / 2 behind them has a successor,
+ * and the frame after the last pushed one is not needed -- so the output lags the input by about fft_size / 2 samples + one frame + one
+ * pulse period.  y must hold what the call MAY return: ry_synth_bound(synth, n_frames, final) samples (n_frames about to be pushed; final = 1:
+ * for the flush after them).  ry_synth_flush ends the signal with the frames pushed so far and resets the stream. */
+int ry_synth_bound(ry_synth* synth, int n_frames, int final);
+int ry_synth_push(ry_synth* synth, const double* f0, const float* sp, const float* ap, int n_frames, int bins, int on_device,
+                  double* y, int y_capacity, int* n_out);
+int ry_synth_flush(ry_synth* synth, double* y, int y_capacity, int* n_out);
+int ry_synth_reset(ry_synth* synth);
+/* tests: the pulses the last run / push / flush found: sample index, fractional shift in samples [0, 1), voiced flag.  All three arrays
+ * null: the count alone. */
+int ry_synth_debug_pulses(ry_synth* synth, long long* index, double* shift, int* voiced, int capacity, int* n);
+/* tests: fills every scratch buffer and the unused part of the frame window with NaN bit patterns: a later call that reads anything it
+ * did not write shows it in its output. */
+int ry_synth_debug_poison(ry_synth* synth);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,8 @@ ABI_SYMBOLS = (
     'ry_dev_alloc', 'ry_dev_free', 'ry_dev_upload', 'ry_dev_download',
     'ry_crepe_param_count', 'ry_crepe_create', 'ry_crepe_destroy', 'ry_crepe_predict', 'ry_crepe_decode', 'ry_crepe_set_viterbi_tables',
     'ry_crepe_debug_layer', 'ry_crepe_debug_splits',
+    'ry_synth_create', 'ry_synth_destroy', 'ry_synth_length', 'ry_synth_run', 'ry_synth_bound', 'ry_synth_push', 'ry_synth_flush', 'ry_synth_reset',
+    'ry_synth_debug_pulses', 'ry_synth_debug_poison',
 )
 
 
@@ -174,6 +176,18 @@ class Ry355Lib(object):
         d.ry_crepe_set_viterbi_tables.argtypes = [_VP, _DP, _DP, _DP]
         d.ry_crepe_debug_layer.argtypes = [_VP, ctypes.c_int, _FP]
         d.ry_crepe_debug_splits.argtypes = [_VP, ctypes.POINTER(ctypes.c_int)]
+        _CI = ctypes.c_int
+        d.ry_synth_create.argtypes = [_VP, _CI, ctypes.c_double, _CI, ctypes.c_uint, ctypes.POINTER(_VP)]
+        d.ry_synth_destroy.argtypes = [_VP]
+        d.ry_synth_destroy.restype = None
+        d.ry_synth_length.argtypes = [_VP, _CI]
+        d.ry_synth_bound.argtypes = [_VP, _CI, _CI]
+        d.ry_synth_run.argtypes = [_VP, _DP, _FP, _FP, _CI, _CI, _CI, _DP, _CI, _IP]
+        d.ry_synth_push.argtypes = [_VP, _DP, _FP, _FP, _CI, _CI, _CI, _DP, _CI, _IP]
+        d.ry_synth_flush.argtypes = [_VP, _DP, _CI, _IP]
+        d.ry_synth_reset.argtypes = [_VP]
+        d.ry_synth_debug_pulses.argtypes = [_VP, ctypes.POINTER(ctypes.c_longlong), _DP, _IP, _CI, _IP]
+        d.ry_synth_debug_poison.argtypes = [_VP]
         d.ry_net_profile_window.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RyKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
 
     def check(self, rc):

@@ -1,0 +1,394 @@
+// synth.cpp -- the WORLD synthesizer of libry355.so (`pyworld.synthesize` / world4py's realtime synthesizer, called by the reference's
+// Vocoder.decode / RealtimeVocoder.decode): f0 / spectrogram / aperiodicity frames -> float64 waveform.  Kernels: synth_kernels.h.
+// One code path serves the one-shot call and the stream: frames are appended to a window on the device, `advance` scans the samples whose
+// two neighbouring frames are there, computes the response of every pulse that has a successor and emits the samples no later pulse can
+// reach.  Nothing but the wrapped phase, the pulse list and the frame window is carried from one push to the next: responses of pulses that
+// straddle a push boundary are computed again from the same inputs (the same bits), so any cut of a stream equals the one-shot call.
+#include "synth_kernels.h"
+#include "ry_host.h"
+
+struct ry_synth {
+    ry_ctx* ctx = nullptr;
+    int fs = 0;
+    double frame_period = 0, spf = 0, lowest_f0 = 0;
+    unsigned seed = 0, seed_hash = 0;
+    Arena tables;
+    sy_c* tw = nullptr;
+    double* dc = nullptr;
+    SynthScanState* st = nullptr;
+    // the stream
+    long long n_frames = 0;                  // frames pushed since the last reset
+    long long frame0 = 0;                    // absolute index of row 0 of the window
+    std::vector<double> f0;                  // thresholded f0 of the window's frames
+    long long scanned = 0, done = 0;         // samples whose phase is known / samples emitted
+    struct Pulse { long long idx; double shift; int voiced; };
+    std::vector<Pulse> live;                 // pulses that can still reach an unemitted sample, and the last one found
+    std::vector<Pulse> last_call;            // ry_synth_debug_pulses: the pulses the last call found
+    // device buffers: the frame window (two sets: the live rows move to the other set when frames are appended), scratch of a call
+    Arena win[2];
+    float *sp[2] = {}, *ap[2] = {};
+    long long win_cap[2] = {0, 0};
+    int cur = 0;
+    Arena scratch;
+    double* d_f0 = nullptr; long long cap_f0 = 0;
+    long long* d_pidx = nullptr; double* d_pshift = nullptr; int* d_pvoiced = nullptr; long long cap_p = 0;
+    double* d_resp = nullptr; long long cap_resp = 0;
+    double* d_y = nullptr; long long cap_y = 0;
+};
+
+namespace {
+template <typename T>
+int alloc_as(Arena& a, T** p, size_t n) {
+    float* q = nullptr;
+    RY_TRY(a.alloc(&q, (n * sizeof(T) + sizeof(float) - 1) / sizeof(float)));
+    *p = (T*)q;
+    return RY_OK;
+}
+
+template <typename T>
+int grow(ry_synth* s, T** p, long long* cap, long long need) {
+    if (need <= *cap) return RY_OK;
+    RT_TRY(rt::stream_sync(s->ctx->stream));                       // work in flight may use the old buffer
+    if (*p) s->scratch.free_one(*p);
+    *p = nullptr; *cap = 0;
+    const long long n = need + need / 2 + 64;
+    RY_TRY(alloc_as(s->scratch, p, (size_t)n));
+    *cap = n;
+    return RY_OK;
+}
+
+void reset_stream(ry_synth* s) {
+    s->n_frames = 0; s->frame0 = 0; s->f0.clear();
+    s->scanned = 0; s->done = 0; s->live.clear();
+}
+
+long long y_length(const ry_synth* s, long long n) { return (long long)((double)(n - 1) * s->frame_period / 1000 * s->fs) + 1; }
+
+// samples n with n / spf < m - 1: both frames of their interpolation are among the first m
+long long known_samples(const ry_synth* s, long long m) {
+    if (m < 2) return 0;
+    long long n = (long long)std::ceil((double)(m - 1) * s->spf);
+    while (n > 0 && !((double)(n - 1) / s->spf < (double)(m - 1))) --n;
+    while ((double)n / s->spf < (double)(m - 1)) ++n;
+    return n;
+}
+
+long long frame_of(const ry_synth* s, long long sample) { return sample <= 0 ? 0 : (long long)std::floor((double)sample / s->spf); }
+
+int check_frames(const ry_synth* s, const double* f0, const float* sp, const float* ap, int n_frames) {
+    if (!f0 || !sp || !ap) return fail(RY_EINVAL, "null f0 / sp / ap");
+    if (n_frames < 1) return fail(RY_EINVAL, "n_frames = %d: at least one frame", n_frames);
+    if (n_frames > (1 << 22)) return fail(RY_EINVAL, "%d frames in one call", n_frames);
+    for (int i = 0; i < n_frames; ++i)
+        if (!std::isfinite(f0[i])) return fail(RY_EINVAL, "f0[%d] is not finite", i);
+    (void)s;
+    return RY_OK;
+}
+
+// appends frames to the window; rows before `keep_from` (absolute) are dropped on the way
+int append_frames(ry_synth* s, const double* f0, const float* sp, const float* ap, int n, int on_device, long long keep_from) {
+    const ry_stream_t st = s->ctx->stream;
+    keep_from = std::max(keep_from, s->frame0);
+    const long long old_rows = s->frame0 + (long long)s->f0.size() - keep_from;     // live rows
+    const long long rows = old_rows + n;
+    const int from = s->cur, to = 1 - s->cur;
+    if (rows > s->win_cap[to]) {
+        RT_TRY(rt::stream_sync(st));
+        s->win[to].release();
+        s->sp[to] = s->ap[to] = nullptr; s->win_cap[to] = 0;
+        const long long cap = rows + rows / 2 + 16;
+        RY_TRY(s->win[to].alloc(&s->sp[to], (size_t)cap * SYNTH_BINS));
+        RY_TRY(s->win[to].alloc(&s->ap[to], (size_t)cap * SYNTH_BINS));
+        s->win_cap[to] = cap;
+    }
+    const size_t row = SYNTH_BINS * sizeof(float);
+    if (old_rows > 0) {
+        const size_t off = (size_t)(keep_from - s->frame0) * SYNTH_BINS;
+        RT_TRY(rt::d2d(s->sp[to], s->sp[from] + off, (size_t)old_rows * row, st));
+        RT_TRY(rt::d2d(s->ap[to], s->ap[from] + off, (size_t)old_rows * row, st));
+    }
+    float* dsp = s->sp[to] + (size_t)old_rows * SYNTH_BINS;
+    float* dap = s->ap[to] + (size_t)old_rows * SYNTH_BINS;
+    if (on_device) {
+        RT_TRY(rt::d2d(dsp, sp, (size_t)n * row, st));
+        RT_TRY(rt::d2d(dap, ap, (size_t)n * row, st));
+    } else {
+        RT_TRY(rt::h2d(dsp, sp, (size_t)n * row, st));
+        RT_TRY(rt::h2d(dap, ap, (size_t)n * row, st));
+        RT_TRY(rt::stream_sync(st));                               // the caller's arrays are free when the call returns
+    }
+    s->f0.erase(s->f0.begin(), s->f0.begin() + (keep_from - s->frame0));
+    for (int i = 0; i < n; ++i) s->f0.push_back(f0[i] < s->lowest_f0 ? 0.0 : f0[i]);
+    s->frame0 = keep_from;
+    s->cur = to;
+    s->n_frames += n;
+    return RY_OK;
+}
+
+// the first frame a later call can still read: the frames of the oldest live pulse and of the next sample to scan
+long long first_needed_frame(const ry_synth* s) {
+    long long f = frame_of(s, s->scanned);
+    if (!s->live.empty()) f = std::min(f, frame_of(s, s->live.front().idx));
+    return std::max(0LL, f - 1);
+}
+
+// scans what can be scanned, emits what can be emitted.  final: the signal ends with the frames pushed so far.
+int advance(ry_synth* s, bool final, double* y, long long y_capacity, long long* n_out) {
+    const ry_stream_t st = s->ctx->stream;
+    const long long m = s->n_frames;
+    const long long k1 = std::max(final ? y_length(s, m) : known_samples(s, m), s->scanned);
+    if (final && y_length(s, m) < s->scanned) return fail(RY_ESTATE, "stream state: %lld samples scanned, the signal has %lld", s->scanned, y_length(s, m));
+    if (k1 - s->done > y_capacity)
+        return fail(RY_EINVAL, "y holds %lld samples, this call may return up to %lld", y_capacity, k1 - s->done);
+    const long long n_new = k1 - s->scanned;
+    const long long n_old = (long long)s->live.size();
+    if (n_old + n_new + 1 > (1LL << 30)) return fail(RY_EINVAL, "%lld samples in one call", n_new);
+    // the pulse arrays: the live pulses, then what the scan appends (at most one pulse per sample)
+    if (n_old + n_new + 1 > s->cap_p) {
+        RT_TRY(rt::stream_sync(st));
+        const long long cap = (n_old + n_new + 1) * 3 / 2 + 64;
+        if (s->d_pidx) { s->scratch.free_one(s->d_pidx); s->scratch.free_one(s->d_pshift); s->scratch.free_one(s->d_pvoiced); }
+        s->d_pidx = nullptr; s->d_pshift = nullptr; s->d_pvoiced = nullptr; s->cap_p = 0;
+        RY_TRY(alloc_as(s->scratch, &s->d_pidx, (size_t)cap));
+        RY_TRY(alloc_as(s->scratch, &s->d_pshift, (size_t)cap));
+        RY_TRY(alloc_as(s->scratch, &s->d_pvoiced, (size_t)cap));
+        s->cap_p = cap;
+    }
+    RY_TRY(grow(s, &s->d_f0, &s->cap_f0, (long long)s->f0.size()));
+    std::vector<long long> hidx(n_old); std::vector<double> hshift(n_old); std::vector<int> hvo(n_old);
+    for (long long i = 0; i < n_old; ++i) { hidx[i] = s->live[i].idx; hshift[i] = s->live[i].shift; hvo[i] = s->live[i].voiced; }
+    if (n_old) {
+        RT_TRY(rt::h2d(s->d_pidx, hidx.data(), n_old * sizeof(long long), st));
+        RT_TRY(rt::h2d(s->d_pshift, hshift.data(), n_old * sizeof(double), st));
+        RT_TRY(rt::h2d(s->d_pvoiced, hvo.data(), n_old * sizeof(int), st));
+    }
+    RT_TRY(rt::h2d(s->d_f0, s->f0.data(), s->f0.size() * sizeof(double), st));
+    RT_TRY(rt::stream_sync(st));                                   // hidx / hshift / hvo are reused below
+    SynthScanState hs;
+    long long total = n_old;
+    s->last_call.clear();
+    if (n_new > 0) {
+        const int n_old_i = (int)n_old;
+        RT_TRY(rt::h2d(&s->st->n_pulses, &n_old_i, sizeof(int), st));
+        SynthScanParams sp;
+        sp.f0 = s->d_f0; sp.frame0 = s->frame0; sp.last_frame = m - 1; sp.n0 = s->scanned; sp.n1 = k1; sp.spf = s->spf; sp.fs = (double)s->fs;
+        sp.st = s->st; sp.pidx = s->d_pidx; sp.pshift = s->d_pshift; sp.pvoiced = s->d_pvoiced; sp.cap = (int)s->cap_p;
+        RY_LAUNCH(synth_scan, dim3(1), 256, st, sp);
+        RT_TRY(rt::last_error());
+        RT_TRY(rt::d2h(&hs, s->st, sizeof hs, st));
+        RT_TRY(rt::stream_sync(st));
+        if (hs.overflow) return fail(RY_ESTATE, "pulse list overflow (%d)", hs.overflow);
+        total = hs.n_pulses;
+        const long long added = total - n_old;
+        if (added > 0) {
+            hidx.resize(added); hshift.resize(added); hvo.resize(added);
+            RT_TRY(rt::d2h(hidx.data(), s->d_pidx + n_old, added * sizeof(long long), st));
+            RT_TRY(rt::d2h(hshift.data(), s->d_pshift + n_old, added * sizeof(double), st));
+            RT_TRY(rt::d2h(hvo.data(), s->d_pvoiced + n_old, added * sizeof(int), st));
+            RT_TRY(rt::stream_sync(st));
+            for (long long i = 0; i < added; ++i) {
+                ry_synth::Pulse p = {hidx[i], hshift[i], hvo[i]};
+                s->live.push_back(p);
+                s->last_call.push_back(p);
+            }
+        }
+        s->scanned = k1;
+    }
+    // what can be emitted: everything (final), or the samples the last pulse found -- the one without a successor -- cannot reach
+    const long long complete = final ? total : std::max(0LL, total - 1);
+    long long fin = final ? k1 : (total > 0 ? std::max(s->done, s->live.back().idx - SYNTH_HALF + 1) : s->done);
+    fin = std::min(fin, k1);
+    const long long n_emit = fin - s->done;
+    if (n_emit > 0) {
+        if (complete > 0) {
+            RY_TRY(grow(s, &s->d_resp, &s->cap_resp, complete * SYNTH_FFT));
+            SynthPulseParams pp;
+            pp.pidx = s->d_pidx; pp.pshift = s->d_pshift; pp.pvoiced = s->d_pvoiced; pp.n_pulses = (int)total; pp.n_complete = (int)complete;
+            pp.sp = s->sp[s->cur]; pp.ap = s->ap[s->cur]; pp.frame0 = s->frame0; pp.last_frame = m - 1; pp.spf = s->spf;
+            pp.seed_hash = s->seed_hash; pp.tw = s->tw; pp.dc = s->dc; pp.resp = s->d_resp;
+            RY_LAUNCH(synth_pulse, dim3((unsigned)complete), 256, st, pp);
+            RT_TRY(rt::last_error());
+        }
+        RY_TRY(grow(s, &s->d_y, &s->cap_y, n_emit));
+        SynthOverlapParams op;
+        op.pidx = s->d_pidx; op.n_complete = (int)complete; op.resp = s->d_resp; op.s0 = s->done; op.s1 = fin; op.y = s->d_y;
+        RY_LAUNCH(synth_overlap, dim3((unsigned)((n_emit + 255) / 256)), 256, st, op);
+        RT_TRY(rt::last_error());
+        RT_TRY(rt::d2h(y, s->d_y, (size_t)n_emit * sizeof(double), st));
+        RT_TRY(rt::stream_sync(st));
+        s->done = fin;
+    }
+    *n_out = n_emit;
+    // pulses that cannot reach an unemitted sample leave the list (the last one stays: it has no successor yet)
+    size_t drop = 0;
+    while (drop + 1 < s->live.size() && s->live[drop].idx < s->done - SYNTH_HALF) ++drop;
+    s->live.erase(s->live.begin(), s->live.begin() + (long)drop);
+    return RY_OK;
+}
+
+int reset_device_state(ry_synth* s) {
+    SynthScanState z;
+    memset(&z, 0, sizeof z);
+    RT_TRY(rt::h2d(s->st, &z, sizeof z, s->ctx->stream));
+    RT_TRY(rt::stream_sync(s->ctx->stream));
+    return RY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ry_synth_create(ry_ctx* ctx, int fs, double frame_period_ms, int fft_size, unsigned seed, ry_synth** out) {
+    if (!out) return fail(RY_EINVAL, "null out pointer");
+    *out = nullptr;
+    if (!ctx) return fail(RY_EINVAL, "null context");
+    if (fs < 1000 || fs > 384000) return fail(RY_EINVAL, "sampling rate %d", fs);
+    if (!(frame_period_ms > 0) || !std::isfinite(frame_period_ms)) return fail(RY_EINVAL, "frame period %g ms", frame_period_ms);
+    if (fft_size != SYNTH_FFT) return fail(RY_EINVAL, "fft_size %d: the transforms are built for %d (CheapTrick's size at 16 and 24 kHz)", fft_size, SYNTH_FFT);
+    const double spf = fs * frame_period_ms / 1000;
+    if (!(spf >= 1.0)) return fail(RY_EINVAL, "a frame of %g ms at %d Hz is shorter than a sample", frame_period_ms, fs);
+    RT_TRY(rt::set_device(ctx->device));
+    std::unique_ptr<ry_synth> s(new ry_synth());
+    s->ctx = ctx; s->fs = fs; s->frame_period = frame_period_ms; s->spf = spf; s->lowest_f0 = (double)fs / fft_size + 1.0;
+    s->seed = seed;
+    unsigned h = seed;                                              // synth_hash32 on the host
+    h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
+    s->seed_hash = h;
+    std::vector<double> tw(2 * SYNTH_FFT), dc(SYNTH_FFT);
+    for (int k = 0; k < SYNTH_FFT; ++k) {
+        tw[2 * k] = std::cos(SYNTH_TWO_PI * k / SYNTH_FFT);
+        tw[2 * k + 1] = std::sin(SYNTH_TWO_PI * k / SYNTH_FFT);
+    }
+    double sum = 0;
+    for (int i = 0; i < SYNTH_HALF; ++i) {
+        dc[i] = 0.5 - 0.5 * std::cos(SYNTH_TWO_PI * (i + 1.0) / (1.0 + SYNTH_FFT));
+        dc[SYNTH_FFT - 1 - i] = dc[i];
+        sum += 2 * dc[i];
+    }
+    for (int i = 0; i < SYNTH_FFT; ++i) dc[i] /= sum;
+    RY_TRY(alloc_as(s->tables, &s->tw, (size_t)SYNTH_FFT));
+    RY_TRY(alloc_as(s->tables, &s->dc, (size_t)SYNTH_FFT));
+    RY_TRY(alloc_as(s->tables, &s->st, (size_t)1));
+    RT_TRY(rt::h2d(s->tw, tw.data(), tw.size() * sizeof(double), ctx->stream));
+    RT_TRY(rt::h2d(s->dc, dc.data(), dc.size() * sizeof(double), ctx->stream));
+    RT_TRY(rt::stream_sync(ctx->stream));
+    RY_TRY(reset_device_state(s.get()));
+    *out = s.release();
+    return RY_OK;
+}
+
+void ry_synth_destroy(ry_synth* s) {
+    if (!s) return;
+    rt::set_device(s->ctx->device);
+    rt::stream_sync(s->ctx->stream);
+    delete s;
+}
+
+int ry_synth_reset(ry_synth* s) {
+    if (!s) return fail(RY_ESTATE, "null synthesizer handle");
+    RT_TRY(rt::set_device(s->ctx->device));
+    reset_stream(s);
+    return reset_device_state(s);
+}
+
+int ry_synth_length(ry_synth* s, int n_frames) {
+    if (!s || n_frames < 1) return fail(RY_EINVAL, "bad argument");
+    return (int)y_length(s, n_frames);
+}
+
+int ry_synth_bound(ry_synth* s, int n_frames, int final) {
+    if (!s || n_frames < 0) return fail(RY_EINVAL, "bad argument");
+    const long long m = s->n_frames + n_frames;
+    if (m < 1) return 0;
+    const long long k = final ? y_length(s, m) : known_samples(s, m);
+    return (int)std::max(0LL, std::max(k, s->scanned) - s->done);
+}
+
+int ry_synth_push(ry_synth* s, const double* f0, const float* sp, const float* ap, int n_frames, int bins, int on_device,
+                  double* y, int y_capacity, int* n_out) {
+    if (!s) return fail(RY_ESTATE, "null synthesizer handle");
+    if (n_out) *n_out = 0;
+    if (!y || !n_out || y_capacity < 0) return fail(RY_EINVAL, "bad output arguments");
+    if (bins != SYNTH_BINS) return fail(RY_EINVAL, "%d bins per frame, fft_size / 2 + 1 = %d expected", bins, SYNTH_BINS);
+    RY_TRY(check_frames(s, f0, sp, ap, n_frames));
+    const long long m = s->n_frames + n_frames;
+    const long long may = std::max(known_samples(s, m), s->scanned) - s->done;
+    if (may > y_capacity) return fail(RY_EINVAL, "y holds %d samples, this push may return up to %lld (ry_synth_bound)", y_capacity, may);
+    RT_TRY(rt::set_device(s->ctx->device));
+    RY_TRY(append_frames(s, f0, sp, ap, n_frames, on_device, first_needed_frame(s)));
+    long long n = 0;
+    RY_TRY(advance(s, false, y, y_capacity, &n));
+    *n_out = (int)n;
+    return RY_OK;
+}
+
+int ry_synth_flush(ry_synth* s, double* y, int y_capacity, int* n_out) {
+    if (!s) return fail(RY_ESTATE, "null synthesizer handle");
+    if (n_out) *n_out = 0;
+    if (!y || !n_out || y_capacity < 0) return fail(RY_EINVAL, "bad output arguments");
+    if (s->n_frames < 1) return fail(RY_ESTATE, "flush of an empty stream");
+    RT_TRY(rt::set_device(s->ctx->device));
+    long long n = 0;
+    RY_TRY(advance(s, true, y, y_capacity, &n));
+    *n_out = (int)n;
+    return ry_synth_reset(s);
+}
+
+int ry_synth_run(ry_synth* s, const double* f0, const float* sp, const float* ap, int n_frames, int bins, int on_device,
+                 double* y, int y_capacity, int* n_out) {
+    if (!s) return fail(RY_ESTATE, "null synthesizer handle");
+    if (n_out) *n_out = 0;
+    if (!y || !n_out || y_capacity < 0) return fail(RY_EINVAL, "bad output arguments");
+    if (bins != SYNTH_BINS) return fail(RY_EINVAL, "%d bins per frame, fft_size / 2 + 1 = %d expected", bins, SYNTH_BINS);
+    RY_TRY(check_frames(s, f0, sp, ap, n_frames));
+    if (y_length(s, n_frames) > y_capacity) return fail(RY_EINVAL, "y holds %d samples, %d frames give %lld", y_capacity, n_frames, y_length(s, n_frames));
+    RY_TRY(ry_synth_reset(s));
+    RY_TRY(append_frames(s, f0, sp, ap, n_frames, on_device, 0));
+    long long n = 0;
+    const int rc = advance(s, true, y, y_capacity, &n);
+    *n_out = (int)n;
+    const int rc2 = ry_synth_reset(s);
+    return rc != RY_OK ? rc : rc2;
+}
+
+int ry_synth_debug_pulses(ry_synth* s, long long* index, double* shift, int* voiced, int capacity, int* n) {
+    if (!s || !n) return fail(RY_EINVAL, "bad argument");
+    *n = (int)s->last_call.size();
+    if (!index && !shift && !voiced) return RY_OK;                 // the count alone
+    if (capacity < *n) return fail(RY_EINVAL, "%d pulses, room for %d", *n, capacity);
+    for (int i = 0; i < *n; ++i) {
+        if (index) index[i] = s->last_call[i].idx;
+        if (shift) shift[i] = s->last_call[i].shift;
+        if (voiced) voiced[i] = s->last_call[i].voiced;
+    }
+    return RY_OK;
+}
+
+int ry_synth_debug_poison(ry_synth* s) {
+    if (!s) return fail(RY_ESTATE, "null synthesizer handle");
+    const ry_stream_t st = s->ctx->stream;
+    RT_TRY(rt::set_device(s->ctx->device));
+    RT_TRY(rt::stream_sync(st));
+    // every scratch buffer and the set of the frame window that is not in use: all bits set (NaN as a float or a double, -1 as an index)
+    if (s->d_f0) RT_TRY(rt::dmemset(s->d_f0, 0xff, (size_t)s->cap_f0 * sizeof(double), st));
+    if (s->d_pidx) {
+        RT_TRY(rt::dmemset(s->d_pidx, 0xff, (size_t)s->cap_p * sizeof(long long), st));
+        RT_TRY(rt::dmemset(s->d_pshift, 0xff, (size_t)s->cap_p * sizeof(double), st));
+        RT_TRY(rt::dmemset(s->d_pvoiced, 0xff, (size_t)s->cap_p * sizeof(int), st));
+    }
+    if (s->d_resp) RT_TRY(rt::dmemset(s->d_resp, 0xff, (size_t)s->cap_resp * sizeof(double), st));
+    if (s->d_y) RT_TRY(rt::dmemset(s->d_y, 0xff, (size_t)s->cap_y * sizeof(double), st));
+    const int idle = 1 - s->cur;
+    if (s->sp[idle]) {
+        RT_TRY(rt::dmemset(s->sp[idle], 0xff, (size_t)s->win_cap[idle] * SYNTH_BINS * sizeof(float), st));
+        RT_TRY(rt::dmemset(s->ap[idle], 0xff, (size_t)s->win_cap[idle] * SYNTH_BINS * sizeof(float), st));
+    }
+    if (s->sp[s->cur]) {                                            // behind the live rows of the set in use
+        const size_t used = s->f0.size() * SYNTH_BINS, cap = (size_t)s->win_cap[s->cur] * SYNTH_BINS;
+        RT_TRY(rt::dmemset(s->sp[s->cur] + used, 0xff, (cap - used) * sizeof(float), st));
+        RT_TRY(rt::dmemset(s->ap[s->cur] + used, 0xff, (cap - used) * sizeof(float), st));
+    }
+    RT_TRY(rt::stream_sync(st));
+    return RY_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,247 @@
+"""WORLD synthesis on the MI355X: `Synthesizer`, the handle over `ry_synth_*` (include/ry355.h), and the two `decode` bodies that bind it
+over the reference's `Vocoder.decode` / `RealtimeVocoder.decode` (realtime_voice_conversion/yukarin_wrapper/vocoder.py:50-120):
+
+    from realtime_yukarin_amd import world_synth
+    Vocoder.decode = world_synth.decode
+    RealtimeVocoder.decode = world_synth.decode_realtime
+    RealtimeVocoder.create_synthesizer = world_synth.create_synthesizer
+
+`pyworld` / `world4py` are never imported on this path and never shadowed.  The arithmetic is WORLD's `Synthesis` restated
+(tests/world_synth_ref.py); it deviates from `pyworld` in two stated ways -- the noise is a counter-based function of (seed, sample
+position) instead of a process-global xorshift sequence, and the pulse phase is wrapped at every step instead of once at the end -- and
+parity at the `pyworld` boundary is unpinned: the package cannot be installed where this was built.
+
+Spectrogram and aperiodicity travel as float32 `[frames][513]` rows (what stage 2 writes); `DeviceRows` -- rows already on the card,
+e.g. a stage-2 output left there -- are read where they are, without a host round trip (a `fusion.LazySpectrogram` stands for the INPUT
+of stage 2 and is materialised).  f0 goes in and the float64 wave comes out through the host."""
+import ctypes
+import os
+from typing import Optional
+
+import numpy
+
+from . import _lib
+
+FFT_SIZE = 1024
+BINS = FFT_SIZE // 2 + 1
+_DP = ctypes.POINTER(ctypes.c_double)
+
+
+def cheaptrick_fft_size(fs, f0_floor: float = 71.0) -> int:
+    return int(2 ** (1 + int(numpy.log2(3.0 * fs / f0_floor + 1))))
+
+
+class DeviceRows(object):
+    """`[frames][513]` float32 rows that are already on the GPU of the synthesizer's context (e.g. a stage-2 output left there)."""
+
+    def __init__(self, address: int, frames: int, keep=None):
+        self.address, self.frames, self.keep = int(address), int(frames), keep
+        self.shape = (self.frames, BINS)
+
+
+class Synthesizer(object):
+    """WORLD synthesis on the device (`ry_synth_*`).  One-shot `synthesize`, or a stream: `push` returns the samples that can no longer
+    change (it lags the input by about fft_size / 2 samples + one frame + one pulse period), `flush` the rest; the concatenation equals
+    `synthesize` on the concatenated frames bit for bit, for any cut.  `ctx` (tests): a context over another build of the library."""
+
+    def __init__(self, fs: int, frame_period: float = 5.0, seed: int = 0, ctx=None, device: Optional[int] = None):
+        self.fs, self.frame_period, self.seed = int(fs), float(frame_period), int(seed) & 0xffffffff
+        self.fft_size = cheaptrick_fft_size(self.fs)
+        self.device = int(os.environ.get('RY_DEVICE', '0')) if device is None else int(device)
+        self._given_ctx = ctx
+        self._ctx = None
+        self._handle = None
+        self._pid = None
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        d.update(_handle=None, _pid=None, _ctx=None, _given_ctx=None)
+        return d
+
+    def _get(self):
+        if self._handle is None or self._pid != os.getpid():
+            from . import engine
+            given = self._given_ctx is not None and self._given_ctx.pid == os.getpid()
+            self._ctx = self._given_ctx if given else engine.get_context(self.device)
+            lib = self._ctx.lib
+            h = ctypes.c_void_p()
+            lib.check(lib.dll.ry_synth_create(self._ctx.handle, self.fs, self.frame_period, self.fft_size, self.seed, ctypes.byref(h)))
+            self._handle, self._pid = h, os.getpid()
+        return self._ctx.lib, self._handle
+
+    # ---- arguments
+    @staticmethod
+    def _rows(a, n, name):
+        """-> (pointer, on_device, keep-alive)."""
+        if isinstance(a, DeviceRows):
+            if a.frames != n:
+                raise ValueError('%s has %d device rows, f0 has %d frames' % (name, a.frames, n))
+            return _lib._fptr(a.address), True, a
+        h = numpy.ascontiguousarray(a, dtype=numpy.float32)
+        if h.ndim != 2 or h.shape[0] != n:
+            raise ValueError('%s must be (%d, bins), got %s' % (name, n, h.shape))
+        return _lib._fptr(h), False, h
+
+    def _frames(self, f0, sp, ap):
+        f0 = numpy.ascontiguousarray(numpy.asarray(f0, dtype=numpy.float64).reshape(-1))
+        n = f0.size
+        from . import fusion
+        if isinstance(sp, fusion.LazySpectrogram):
+            sp = device_spectrogram(sp)
+        psp, dsp, ksp = self._rows(sp, n, 'sp')
+        pap, dap, kap = self._rows(ap, n, 'ap')
+        bins = int(sp.shape[1]) if not dsp else BINS
+        if not dap and ap.shape[1] != bins:
+            raise ValueError('sp has %d bins, ap %d' % (bins, ap.shape[1]))
+        if dsp != dap:                                             # one flag in the ABI: bring the host side over
+            if not dsp:
+                ksp = _upload(self._ctx, ksp)
+                psp = _lib._fptr(ksp.address)
+            else:
+                kap = _upload(self._ctx, kap)
+                pap = _lib._fptr(kap.address)
+            dsp = dap = True
+        return f0, n, psp, pap, bins, int(dsp), (ksp, kap)
+
+    # ---- calls
+    def length(self, n_frames: int) -> int:
+        return int((int(n_frames) - 1) * self.frame_period / 1000 * self.fs) + 1
+
+    def synthesize(self, f0, sp, ap) -> numpy.ndarray:
+        lib, h = self._get()
+        f0, n, psp, pap, bins, dev, keep = self._frames(f0, sp, ap)
+        y = numpy.empty(max(self.length(n), 1) if n > 0 else 1, numpy.float64)
+        got = ctypes.c_int()
+        lib.check(lib.dll.ry_synth_run(h, f0.ctypes.data_as(_DP), psp, pap, n, bins, dev, y.ctypes.data_as(_DP), y.size, ctypes.byref(got)))
+        return y[:got.value]
+
+    def push(self, f0, sp, ap) -> numpy.ndarray:
+        lib, h = self._get()
+        f0, n, psp, pap, bins, dev, keep = self._frames(f0, sp, ap)
+        y = numpy.empty(max(int(lib.dll.ry_synth_bound(h, max(n, 0), 0)), 1), numpy.float64)
+        got = ctypes.c_int()
+        lib.check(lib.dll.ry_synth_push(h, f0.ctypes.data_as(_DP), psp, pap, n, bins, dev, y.ctypes.data_as(_DP), y.size, ctypes.byref(got)))
+        return y[:got.value].copy()
+
+    def flush(self) -> numpy.ndarray:
+        lib, h = self._get()
+        y = numpy.empty(max(int(lib.dll.ry_synth_bound(h, 0, 1)), 1), numpy.float64)
+        got = ctypes.c_int()
+        lib.check(lib.dll.ry_synth_flush(h, y.ctypes.data_as(_DP), y.size, ctypes.byref(got)))
+        return y[:got.value].copy()
+
+    def reset(self) -> None:
+        lib, h = self._get()
+        lib.check(lib.dll.ry_synth_reset(h))
+
+    def pulses(self):
+        """(index int64, shift float64 in samples, voiced bool) of the pulses the last call found (`ry_synth_debug_pulses`)."""
+        lib, h = self._get()
+        n = ctypes.c_int()
+        lib.check(lib.dll.ry_synth_debug_pulses(h, None, None, None, 0, ctypes.byref(n)))
+        idx, sh, vo = numpy.empty(n.value, numpy.int64), numpy.empty(n.value, numpy.float64), numpy.empty(n.value, numpy.int32)
+        lib.check(lib.dll.ry_synth_debug_pulses(h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), sh.ctypes.data_as(_DP),
+                                                vo.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n.value, ctypes.byref(n)))
+        return idx, sh, vo != 0
+
+    def poison(self) -> None:
+        lib, h = self._get()
+        lib.check(lib.dll.ry_synth_debug_poison(h))
+
+    def lag_samples(self, f0: float = 500.0) -> int:
+        """What `push` holds back at most: half a transform, one frame, one pulse period (of `f0`; 500 Hz: unvoiced)."""
+        return self.fft_size // 2 + int(numpy.ceil(self.fs * self.frame_period / 1000)) + int(numpy.ceil(self.fs / f0))
+
+    def close(self):
+        if self._handle is not None and self._pid == os.getpid() and self._ctx is not None and self._ctx.handle is not None:
+            self._ctx.lib.dll.ry_synth_destroy(self._handle)
+        self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _DeviceBuffer(object):
+    """A `ry_dev_alloc` buffer that frees itself."""
+
+    def __init__(self, ctx, n_floats):
+        self.ctx = ctx
+        p = _lib._FP()
+        ctx.lib.check(ctx.lib.dll.ry_dev_alloc(ctx.handle, int(n_floats), ctypes.byref(p)))
+        self.ptr = p
+        self.address = ctypes.cast(p, ctypes.c_void_p).value
+
+    def __del__(self):
+        try:
+            if self.ctx.handle is not None and self.ptr:
+                self.ctx.lib.dll.ry_dev_free(self.ctx.handle, self.ptr)
+        except Exception:
+            pass
+
+
+def _upload(ctx, host: numpy.ndarray) -> DeviceRows:
+    buf = _DeviceBuffer(ctx, host.size)
+    ctx.lib.check(ctx.lib.dll.ry_dev_upload(ctx.handle, buf.ptr, _lib._fptr(host), host.size))
+    return DeviceRows(buf.address, host.shape[0], keep=buf)
+
+
+def to_device(ctx, rows) -> DeviceRows:
+    """Host `[frames][513]` rows -> `DeviceRows` on the GPU of `ctx` (tests, callers without a tensor library)."""
+    h = numpy.ascontiguousarray(rows, dtype=numpy.float32)
+    if h.ndim != 2 or h.shape[1] != BINS:
+        raise ValueError('rows must be (frames, %d), got %s' % (BINS, h.shape))
+    return _upload(ctx, h)
+
+
+def device_spectrogram(sp):
+    """A `fusion.LazySpectrogram` stays what it is until somebody looks at it; this asks for its float32 array (the device rows it stands
+    for are the INPUT of stage 2 -- the synthesizer wants the output, which the caller hands over as an array or as `DeviceRows`)."""
+    return numpy.asarray(sp, dtype=numpy.float32)
+
+
+# ---- the reference's methods ---------------------------------------------------------------------------------------------------------
+class engine_for_tests(object):
+    """tests: `ctx`, a context over another build of the library (the emulator), for the synthesizers the bindings below create."""
+    ctx = None
+
+
+def _new_synth(vocoder) -> Synthesizer:
+    return Synthesizer(vocoder.out_sampling_rate, vocoder.acoustic_param.frame_period, seed=int(os.environ.get('RY_SYNTH_SEED', '0')),
+                       ctx=engine_for_tests.ctx)
+
+
+def _synth_of(self, key='_ry_synth'):
+    s = getattr(self, key, None)
+    if s is None:
+        s = _new_synth(self)
+        setattr(self, key, s)
+    return s
+
+
+def decode(self, acoustic_feature):
+    """Drop-in body of `Vocoder.decode` (vocoder.py:50-62): `pyworld.synthesize` of the whole feature -> `Wave` (float64)."""
+    from yukarin import Wave
+    f = acoustic_feature
+    out = _synth_of(self).synthesize(numpy.asarray(f.f0).ravel(), f.sp, f.ap)
+    return Wave(out, sampling_rate=self.out_sampling_rate)
+
+
+def create_synthesizer(self, buffer_size: int, number_of_pointers: int):
+    """Drop-in body of `RealtimeVocoder.create_synthesizer` (vocoder.py:72-87): world4py's ring of `number_of_pointers` parameter sets and
+    its `buffer_size` output block have no counterpart -- the device stream takes pushes of any size and returns what is final."""
+    assert self._synthesizer is None
+    self._synthesizer = _new_synth(self)
+    self._synthesizer.buffer_size = int(buffer_size)
+    self._synthesizer.number_of_pointers = int(number_of_pointers)
+
+
+def decode_realtime(self, acoustic_feature):
+    """Drop-in body of `RealtimeVocoder.decode` (vocoder.py:89-120): the frames go to the stream, the samples that are final come back."""
+    from yukarin import Wave
+    assert self._synthesizer is not None
+    f = acoustic_feature
+    out = self._synthesizer.push(numpy.asarray(f.f0).ravel(), f.sp, f.ap)
+    return Wave(wave=out, sampling_rate=self.out_sampling_rate)
