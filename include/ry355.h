@@ -317,6 +317,31 @@ int ry_synth_debug_pulses(ry_synth* synth, long long* index, double* shift, int*
  * did not write shows it in its output. */
 int ry_synth_debug_poison(ry_synth* synth);
 
+/* ---- WORLD analysis that feeds the networks (`pyworld.cheaptrick(x, f0, t, fs)` and `pysptk.sp2mc(sp, order, alpha)` in the reference's
+ * AcousticFeature.extract, reached from Vocoder.encode).  Semantics: INTEGRATION.md section 11 and tests/world_analysis_ref.py (CheapTrick
+ * and sp2mc restated; WORLD's two randn() terms are counter-based functions of (seed, centre sample, index), so a frame's rows depend on
+ * (x, f0, t, seed) only).  fft_size: 1024 -- anything else is refused; order: 0 .. 63.  x [x_len] float64, f0 [n] (Hz; at or below
+ * max(f0_floor, 3 fs / (fft_size - 3)) = unvoiced, analysed at 500 Hz) and t [n] (seconds) float64, all on the HOST.  Outputs, any may be
+ * null: sp64_out [n][513] float64 and mc_out [n][order + 1] float64 on the HOST, sp32_dev_out [n][513] float32 on the DEVICE (the rows
+ * ry_synth_* and stage 2 read; = (float)sp64, left on the card).  The call returns after everything is written.  n = 0 or x_len = 0: success,
+ * nothing written.  Refused: n < 0, x_len < 0, a null wave / f0 / t with n > 0, f0 or t that is not finite, f0 >= fs / 2. */
+typedef struct ry_analysis ry_analysis;
+int ry_analysis_create(ry_ctx* ctx, int fs, int fft_size, int order, double alpha, double q1, double f0_floor, unsigned seed, ry_analysis** out);
+void ry_analysis_destroy(ry_analysis* analysis);
+int ry_analysis_run(ry_analysis* analysis, const double* x, long long x_len, const double* f0, const double* t, int n,
+                    double* sp64_out, float* sp32_dev_out, double* mc_out);
+/* sp2mc of a spectrogram that comes from elsewhere: on_device = 0: sp is [n][513] float64 on the host; 1: [n][513] float32 on the device.
+ * mc_out [n][order + 1] float64 on the host. */
+int ry_analysis_sp2mc(ry_analysis* analysis, const void* sp, int n, int on_device, double* mc_out);
+/* tests: on = 1: every later ry_analysis_run also stores and downloads the integers it decided (off by default: one store per frame and one
+ * copy the product path does not pay for). */
+int ry_analysis_debug_record(ry_analysis* analysis, int on);
+/* tests: the integers the last recorded ry_analysis_run decided, [n][4]: window half length, centre sample, DC-correction bin limit,
+ * smoothing boundary (none when recording is off).  out null: the count alone. */
+int ry_analysis_debug_ints(ry_analysis* analysis, long long* out, int capacity, int* n);
+/* tests: fills every buffer the calls grow with NaN bit patterns. */
+int ry_analysis_debug_poison(ry_analysis* analysis);
+
 #ifdef __cplusplus
 }
 #endif

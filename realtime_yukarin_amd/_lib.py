@@ -61,6 +61,7 @@ ABI_SYMBOLS = (
     'ry_crepe_debug_layer', 'ry_crepe_debug_splits',
     'ry_synth_create', 'ry_synth_destroy', 'ry_synth_length', 'ry_synth_run', 'ry_synth_bound', 'ry_synth_push', 'ry_synth_flush', 'ry_synth_reset',
     'ry_synth_debug_pulses', 'ry_synth_debug_poison',
+    'ry_analysis_create', 'ry_analysis_destroy', 'ry_analysis_run', 'ry_analysis_sp2mc', 'ry_analysis_debug_record', 'ry_analysis_debug_ints', 'ry_analysis_debug_poison',
 )
 
 
@@ -188,6 +189,15 @@ class Ry355Lib(object):
         d.ry_synth_reset.argtypes = [_VP]
         d.ry_synth_debug_pulses.argtypes = [_VP, ctypes.POINTER(ctypes.c_longlong), _DP, _IP, _CI, _IP]
         d.ry_synth_debug_poison.argtypes = [_VP]
+        _LL = ctypes.c_longlong
+        d.ry_analysis_create.argtypes = [_VP, _CI, _CI, _CI, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_uint, ctypes.POINTER(_VP)]
+        d.ry_analysis_destroy.argtypes = [_VP]
+        d.ry_analysis_destroy.restype = None
+        d.ry_analysis_run.argtypes = [_VP, _DP, _LL, _DP, _DP, _CI, _DP, _FP, _DP]
+        d.ry_analysis_sp2mc.argtypes = [_VP, _VP, _CI, _CI, _DP]
+        d.ry_analysis_debug_record.argtypes = [_VP, _CI]
+        d.ry_analysis_debug_ints.argtypes = [_VP, ctypes.POINTER(_LL), _CI, _IP]
+        d.ry_analysis_debug_poison.argtypes = [_VP]
         d.ry_net_profile_window.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RyKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
 
     def check(self, rc):
