@@ -342,6 +342,26 @@ int ry_analysis_debug_ints(ry_analysis* analysis, long long* out, int capacity, 
 /* tests: fills every buffer the calls grow with NaN bit patterns. */
 int ry_analysis_debug_poison(ry_analysis* analysis);
 
+/* ---- D4C, the band aperiodicity of the same stage (`pyworld.d4c(x, f0, t, fs, threshold)` + `pyworld.code_aperiodicity(ap, fs)`).  Semantics:
+ * tests/world_d4c_ref.py (D4C restated; its randn() term is counter-based like CheapTrick's, with keys of its own).  Inputs and refusals as
+ * ry_analysis_run, and t >= -1 s.  A frame with f0 == 0 or whose Love-Train ratio is <= threshold is off: its row is 1 - 1e-12; only the
+ * other frames pay for the general body.  Outputs, any may be null: ap64_out [n][513] float64 and coded_out [n][B] float64 (dB at 3000 i Hz,
+ * B = ry_analysis_d4c_bands) on the HOST, ap32_dev_out [n][513] float32 on the DEVICE (= (float)ap64; the rows ry_synth_* read).  Built for the
+ * rates whose D4C transforms are 2048 points and whose band centres are bins of the row (16 and 24 kHz): other rates are refused here (the
+ * handle itself is still good for ry_analysis_run). */
+int ry_analysis_d4c(ry_analysis* analysis, const double* x, long long x_len, const double* f0, const double* t, int n, double threshold,
+                    double* ap64_out, float* ap32_dev_out, double* coded_out);
+/* ry_analysis_run and ry_analysis_d4c over one upload of the wave and the track: the same bits as the two calls. */
+int ry_analysis_extract(ry_analysis* analysis, const double* x, long long x_len, const double* f0, const double* t, int n, double threshold,
+                        double* sp64_out, float* sp32_dev_out, double* mc_out, double* ap64_out, float* ap32_dev_out, double* coded_out);
+/* the number of bands B (1 at 16 kHz, 3 at 24 kHz); negative (an error code) where D4C is not built for the handle's rate */
+int ry_analysis_d4c_bands(ry_analysis* analysis);
+/* tests: what the last recorded (ry_analysis_debug_record) D4C run decided.  ints_out [n][9]: half length of the Love-Train window, of the other
+ * windows, origin sample of the window at t - 0.25 / f, at t, at t + 0.25 / f, DC-correction bin limit, smoothing boundary of width f, of width
+ * f / 2, on (1) / off (0); values_out [n][4]: the Love-Train ratio a0 and the coarse dB values of bands 1 .. 3 (0 where there is none).  Both
+ * null: the count alone. */
+int ry_analysis_debug_d4c(ry_analysis* analysis, long long* ints_out, double* values_out, int capacity, int* n);
+
 #ifdef __cplusplus
 }
 #endif

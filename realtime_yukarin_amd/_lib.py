@@ -62,6 +62,7 @@ ABI_SYMBOLS = (
     'ry_synth_create', 'ry_synth_destroy', 'ry_synth_length', 'ry_synth_run', 'ry_synth_bound', 'ry_synth_push', 'ry_synth_flush', 'ry_synth_reset',
     'ry_synth_debug_pulses', 'ry_synth_debug_poison',
     'ry_analysis_create', 'ry_analysis_destroy', 'ry_analysis_run', 'ry_analysis_sp2mc', 'ry_analysis_debug_record', 'ry_analysis_debug_ints', 'ry_analysis_debug_poison',
+    'ry_analysis_d4c', 'ry_analysis_extract', 'ry_analysis_d4c_bands', 'ry_analysis_debug_d4c',
 )
 
 
@@ -198,6 +199,10 @@ class Ry355Lib(object):
         d.ry_analysis_debug_record.argtypes = [_VP, _CI]
         d.ry_analysis_debug_ints.argtypes = [_VP, ctypes.POINTER(_LL), _CI, _IP]
         d.ry_analysis_debug_poison.argtypes = [_VP]
+        d.ry_analysis_d4c.argtypes = [_VP, _DP, _LL, _DP, _DP, _CI, ctypes.c_double, _DP, _FP, _DP]
+        d.ry_analysis_extract.argtypes = [_VP, _DP, _LL, _DP, _DP, _CI, ctypes.c_double, _DP, _FP, _DP, _DP, _FP, _DP]
+        d.ry_analysis_d4c_bands.argtypes = [_VP]
+        d.ry_analysis_debug_d4c.argtypes = [_VP, ctypes.POINTER(_LL), _DP, _CI, _IP]
         d.ry_net_profile_window.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RyKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
 
     def check(self, rc):

@@ -2,7 +2,9 @@
 // AcousticFeature.extract, reached from Vocoder.encode): wave + f0 track -> spectral envelope rows and mel-cepstrum rows.  Kernels:
 // analysis_kernels.h.  Stateless per frame: a call uploads the wave, f0 and the frame times, launches one workgroup per frame and copies
 // back what was asked for; the float32 rows go to a device buffer of the caller (world_synth.DeviceRows, stage 2) and never leave the card.
+// D4C (`pyworld.d4c` + `pyworld.code_aperiodicity`: ap and coded_ap; kernel: d4c_kernels.h) runs over the same uploaded wave.
 #include "analysis_kernels.h"
+#include "d4c_kernels.h"
 #include "ry_host.h"
 
 #include <algorithm>
@@ -24,6 +26,16 @@ struct ry_analysis {
     AnalysisFrameInts* d_ints = nullptr; long long cap_ints = 0;
     bool record = false;                              // ry_analysis_debug_record: keep the decisions of a run (tests; off the product path)
     std::vector<AnalysisFrameInts> last_ints;         // ry_analysis_debug_ints: the decisions of the last recorded run
+    // D4C: built for the rates whose transform sizes are 2048 and whose band centres are bins of the row (16 and 24 kHz); d4c_why says why not
+    bool d4c_ok = false;
+    std::string d4c_why;
+    int n_bands = 0, band_half = 0, band_centre[D4C_MAX_BANDS] = {0, 0, 0}, lt[3] = {0, 0, 0};
+    sy_c* tw2 = nullptr;                              // [1025]
+    double* nuttall = nullptr;                        // [2 band_half + 1]
+    double* d_ap = nullptr; long long cap_ap = 0;
+    double* d_coded = nullptr; long long cap_coded = 0;
+    D4cFrameRecord* d_rec = nullptr; long long cap_rec = 0;
+    std::vector<D4cFrameRecord> last_rec;             // ry_analysis_debug_d4c: a0, on / off, integers and coarse values of the last recorded run
 };
 
 namespace {
@@ -70,6 +82,125 @@ int check_handle(ry_analysis* s) {
     RT_TRY(rt::set_device(s->ctx->device));
     return RY_OK;
 }
+
+int pow2_above(double v) { return 1 << (1 + (int)std::floor(std::log2(v))); }
+
+// sizes, bands and tables of D4C at this rate; rates it is not built for leave d4c_ok false and the reason in d4c_why
+int d4c_setup(ry_analysis* s) {
+    const int fs = s->fs;
+    char why[160];
+    const int n = pow2_above(4.0 * fs / D4C_FLOOR_F0 + 1.0), n_lt = pow2_above(3.0 * fs / D4C_LOVE_TRAIN_FLOOR + 1.0);
+    const int bands = (int)std::floor(std::min(15000.0, fs / 2.0 - 3000.0) / 3000.0);
+    if (n != D4C_FFT || n_lt != D4C_FFT || bands < 1 || bands > D4C_MAX_BANDS || (3000ll * SYNTH_FFT) % fs != 0) {
+        std::snprintf(why, sizeof why, "D4C at %d Hz needs transforms of %d / %d points and %d bands: built for 2048 / 2048 points, 1 .. %d bands "
+                      "whose centres are bins of the row (16 and 24 kHz)", fs, n, n_lt, bands, D4C_MAX_BANDS);
+        s->d4c_why = why;
+        return RY_OK;
+    }
+    s->n_bands = bands;
+    s->band_half = (int)(3000ll * D4C_FFT / fs);
+    for (int i = 0; i < bands; ++i) s->band_centre[i] = (int)(3000ll * (i + 1) * D4C_FFT / fs);
+    if (s->band_centre[0] - s->band_half < 0 || s->band_centre[bands - 1] + s->band_half > D4C_HALF || 2 * s->band_half + 1 > D4C_MAX_NUTTALL)
+        return fail(RY_ESTATE, "D4C band table at %d Hz", fs);
+    const long long hz[3] = {100, 4000, 7900};
+    for (int i = 0; i < 3; ++i) s->lt[i] = (int)((hz[i] * D4C_FFT + fs - 1) / fs);
+    std::vector<double> tw2(2 * D4C_BINS), nut((size_t)2 * s->band_half + 1);
+    for (int k = 0; k < D4C_BINS; ++k) {
+        tw2[2 * k] = std::cos(SYNTH_TWO_PI * k / D4C_FFT);
+        tw2[2 * k + 1] = std::sin(SYNTH_TWO_PI * k / D4C_FFT);
+    }
+    for (size_t i = 0; i < nut.size(); ++i) {
+        const double tmp = (double)i / (double)(nut.size() - 1);
+        nut[i] = 0.355768 - 0.487396 * std::cos(SYNTH_TWO_PI * tmp) + 0.144232 * std::cos(2.0 * SYNTH_TWO_PI * tmp) - 0.012604 * std::cos(3.0 * SYNTH_TWO_PI * tmp);
+    }
+    RY_TRY(alloc_as(s->tables, &s->tw2, (size_t)D4C_BINS));
+    RY_TRY(alloc_as(s->tables, &s->nuttall, nut.size()));
+    RT_TRY(rt::h2d(s->tw2, tw2.data(), tw2.size() * sizeof(double), s->ctx->stream));
+    RT_TRY(rt::h2d(s->nuttall, nut.data(), nut.size() * sizeof(double), s->ctx->stream));
+    RT_TRY(rt::stream_sync(s->ctx->stream));
+    s->d4c_ok = true;
+    return RY_OK;
+}
+
+struct Outputs {
+    double* sp64 = nullptr; float* sp32_dev = nullptr; double* mc = nullptr;
+    bool d4c = false; double threshold = 0.85;
+    double* ap64 = nullptr; float* ap32_dev = nullptr; double* coded = nullptr;
+};
+
+// one upload of the wave and the track, then CheapTrick + sp2mc (when `cheaptrick`) and / or D4C (when o.d4c) over it
+int run_frames(ry_analysis* s, const double* x, long long x_len, const double* f0, const double* t, int n, bool cheaptrick, const Outputs& o) {
+    RY_TRY(check_handle(s));
+    if (n < 0) return fail(RY_EINVAL, "n = %d frames", n);
+    if (x_len < 0) return fail(RY_EINVAL, "x_len = %lld", x_len);
+    if (n > (1 << 22)) return fail(RY_EINVAL, "%d frames in one call", n);
+    if (o.d4c && !s->d4c_ok) return fail(RY_EINVAL, "%s", s->d4c_why.c_str());
+    if (o.d4c && !std::isfinite(o.threshold)) return fail(RY_EINVAL, "threshold %g", o.threshold);
+    if (n == 0 || x_len == 0) {                                             // nothing to analyse: nothing is written
+        if (cheaptrick) s->last_ints.clear();
+        if (o.d4c) s->last_rec.clear();
+        return RY_OK;
+    }
+    if (!x) return fail(RY_EINVAL, "null wave");
+    if (!f0 || !t) return fail(RY_EINVAL, "null f0 / t");
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(f0[i]) || !(f0[i] < 0.5 * s->fs)) return fail(RY_EINVAL, "f0[%d] = %g: finite and below fs / 2", i, f0[i]);
+        if (!std::isfinite(t[i]) || std::fabs(t[i]) > 1e9) return fail(RY_EINVAL, "t[%d] = %g", i, t[i]);
+        if (o.d4c && t[i] < -1.0) return fail(RY_EINVAL, "t[%d] = %g: D4C takes frames from -1 s on", i, t[i]);
+    }
+    const ry_stream_t st = s->ctx->stream;
+    RY_TRY(grow(s, &s->d_x, &s->cap_x, x_len));
+    RY_TRY(grow(s, &s->d_f0, &s->cap_f0, (long long)n));
+    RY_TRY(grow(s, &s->d_t, &s->cap_t, (long long)n));
+    if (cheaptrick) {
+        if (s->record) RY_TRY(grow(s, &s->d_ints, &s->cap_ints, (long long)n));
+        if (o.sp64) RY_TRY(grow(s, &s->d_sp, &s->cap_sp, (long long)n * SYNTH_BINS));
+        if (o.mc) RY_TRY(grow(s, &s->d_mc, &s->cap_mc, (long long)n * (s->order + 1)));
+    }
+    if (o.d4c) {
+        if (s->record) RY_TRY(grow(s, &s->d_rec, &s->cap_rec, (long long)n));
+        if (o.ap64) RY_TRY(grow(s, &s->d_ap, &s->cap_ap, (long long)n * SYNTH_BINS));
+        if (o.coded) RY_TRY(grow(s, &s->d_coded, &s->cap_coded, (long long)n * s->n_bands));
+    }
+    RT_TRY(rt::h2d(s->d_x, x, (size_t)x_len * sizeof(double), st));
+    RT_TRY(rt::h2d(s->d_f0, f0, (size_t)n * sizeof(double), st));
+    RT_TRY(rt::h2d(s->d_t, t, (size_t)n * sizeof(double), st));
+    if (cheaptrick) {
+        AnalysisParams p;
+        p.x = s->d_x; p.x_len = x_len; p.f0 = s->d_f0; p.t = s->d_t;
+        p.fs = (double)s->fs; p.floor_f0 = s->floor_f0; p.q1 = s->q1; p.seed_hash = s->seed_hash;
+        p.tw = s->tw; p.S = s->S; p.n_mc = s->order + 1;
+        p.sp64 = o.sp64 ? s->d_sp : nullptr; p.sp32 = o.sp32_dev; p.mc = o.mc ? s->d_mc : nullptr; p.ints = s->record ? s->d_ints : nullptr;
+        RY_LAUNCH(analysis_frame, dim3((unsigned)n), 256, st, p);
+        RT_TRY(rt::last_error());
+    }
+    if (o.d4c) {
+        D4cParams p;
+        p.x = s->d_x; p.x_len = x_len; p.f0 = s->d_f0; p.t = s->d_t;
+        p.fs = (double)s->fs; p.threshold = o.threshold; p.seed_hash = s->seed_hash;
+        p.tw = s->tw; p.tw2 = s->tw2; p.nuttall = s->nuttall;
+        p.n_bands = s->n_bands; p.band_half = s->band_half;
+        for (int i = 0; i < D4C_MAX_BANDS; ++i) p.band_centre[i] = s->band_centre[i];
+        p.lt0 = s->lt[0]; p.lt1 = s->lt[1]; p.lt2 = s->lt[2];
+        p.ap64 = o.ap64 ? s->d_ap : nullptr; p.ap32 = o.ap32_dev; p.coded = o.coded ? s->d_coded : nullptr; p.rec = s->record ? s->d_rec : nullptr;
+        RY_LAUNCH(d4c_frame, dim3((unsigned)n), 256, st, p);
+        RT_TRY(rt::last_error());
+    }
+    if (cheaptrick) {
+        s->last_ints.resize(s->record ? (size_t)n : 0);
+        if (s->record) RT_TRY(rt::d2h(s->last_ints.data(), s->d_ints, (size_t)n * sizeof(AnalysisFrameInts), st));
+        if (o.sp64) RT_TRY(rt::d2h(o.sp64, s->d_sp, (size_t)n * SYNTH_BINS * sizeof(double), st));
+        if (o.mc) RT_TRY(rt::d2h(o.mc, s->d_mc, (size_t)n * (s->order + 1) * sizeof(double), st));
+    }
+    if (o.d4c) {
+        s->last_rec.resize(s->record ? (size_t)n : 0);
+        if (s->record) RT_TRY(rt::d2h(s->last_rec.data(), s->d_rec, (size_t)n * sizeof(D4cFrameRecord), st));
+        if (o.ap64) RT_TRY(rt::d2h(o.ap64, s->d_ap, (size_t)n * SYNTH_BINS * sizeof(double), st));
+        if (o.coded) RT_TRY(rt::d2h(o.coded, s->d_coded, (size_t)n * s->n_bands * sizeof(double), st));
+    }
+    RT_TRY(rt::stream_sync(st));                                   // the caller's arrays are free, the float32 rows are written
+    return RY_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -101,6 +232,7 @@ int ry_analysis_create(ry_ctx* ctx, int fs, int fft_size, int order, double alph
     RT_TRY(rt::h2d(s->tw, tw.data(), tw.size() * sizeof(double), ctx->stream));
     RT_TRY(rt::h2d(s->S, S.data(), S.size() * sizeof(double), ctx->stream));
     RT_TRY(rt::stream_sync(ctx->stream));
+    RY_TRY(d4c_setup(s.get()));
     *out = s.release();
     return RY_OK;
 }
@@ -114,40 +246,30 @@ void ry_analysis_destroy(ry_analysis* s) {
 
 int ry_analysis_run(ry_analysis* s, const double* x, long long x_len, const double* f0, const double* t, int n,
                     double* sp64_out, float* sp32_dev_out, double* mc_out) {
-    RY_TRY(check_handle(s));
-    if (n < 0) return fail(RY_EINVAL, "n = %d frames", n);
-    if (x_len < 0) return fail(RY_EINVAL, "x_len = %lld", x_len);
-    if (n > (1 << 22)) return fail(RY_EINVAL, "%d frames in one call", n);
-    if (n == 0 || x_len == 0) { s->last_ints.clear(); return RY_OK; }      // nothing to analyse: nothing is written
-    if (!x) return fail(RY_EINVAL, "null wave");
-    if (!f0 || !t) return fail(RY_EINVAL, "null f0 / t");
-    for (int i = 0; i < n; ++i) {
-        if (!std::isfinite(f0[i]) || !(f0[i] < 0.5 * s->fs)) return fail(RY_EINVAL, "f0[%d] = %g: finite and below fs / 2", i, f0[i]);
-        if (!std::isfinite(t[i]) || std::fabs(t[i]) > 1e9) return fail(RY_EINVAL, "t[%d] = %g", i, t[i]);
-    }
-    const ry_stream_t st = s->ctx->stream;
-    RY_TRY(grow(s, &s->d_x, &s->cap_x, x_len));
-    RY_TRY(grow(s, &s->d_f0, &s->cap_f0, (long long)n));
-    RY_TRY(grow(s, &s->d_t, &s->cap_t, (long long)n));
-    if (s->record) RY_TRY(grow(s, &s->d_ints, &s->cap_ints, (long long)n));
-    if (sp64_out) RY_TRY(grow(s, &s->d_sp, &s->cap_sp, (long long)n * SYNTH_BINS));
-    if (mc_out) RY_TRY(grow(s, &s->d_mc, &s->cap_mc, (long long)n * (s->order + 1)));
-    RT_TRY(rt::h2d(s->d_x, x, (size_t)x_len * sizeof(double), st));
-    RT_TRY(rt::h2d(s->d_f0, f0, (size_t)n * sizeof(double), st));
-    RT_TRY(rt::h2d(s->d_t, t, (size_t)n * sizeof(double), st));
-    AnalysisParams p;
-    p.x = s->d_x; p.x_len = x_len; p.f0 = s->d_f0; p.t = s->d_t;
-    p.fs = (double)s->fs; p.floor_f0 = s->floor_f0; p.q1 = s->q1; p.seed_hash = s->seed_hash;
-    p.tw = s->tw; p.S = s->S; p.n_mc = s->order + 1;
-    p.sp64 = sp64_out ? s->d_sp : nullptr; p.sp32 = sp32_dev_out; p.mc = mc_out ? s->d_mc : nullptr; p.ints = s->record ? s->d_ints : nullptr;
-    RY_LAUNCH(analysis_frame, dim3((unsigned)n), 256, st, p);
-    RT_TRY(rt::last_error());
-    s->last_ints.resize(s->record ? (size_t)n : 0);
-    if (s->record) RT_TRY(rt::d2h(s->last_ints.data(), s->d_ints, (size_t)n * sizeof(AnalysisFrameInts), st));
-    if (sp64_out) RT_TRY(rt::d2h(sp64_out, s->d_sp, (size_t)n * SYNTH_BINS * sizeof(double), st));
-    if (mc_out) RT_TRY(rt::d2h(mc_out, s->d_mc, (size_t)n * (s->order + 1) * sizeof(double), st));
-    RT_TRY(rt::stream_sync(st));                                   // the caller's arrays are free, the float32 rows are written
-    return RY_OK;
+    Outputs o;
+    o.sp64 = sp64_out; o.sp32_dev = sp32_dev_out; o.mc = mc_out;
+    return run_frames(s, x, x_len, f0, t, n, true, o);
+}
+
+int ry_analysis_d4c(ry_analysis* s, const double* x, long long x_len, const double* f0, const double* t, int n, double threshold,
+                    double* ap64_out, float* ap32_dev_out, double* coded_out) {
+    Outputs o;
+    o.d4c = true; o.threshold = threshold; o.ap64 = ap64_out; o.ap32_dev = ap32_dev_out; o.coded = coded_out;
+    return run_frames(s, x, x_len, f0, t, n, false, o);
+}
+
+int ry_analysis_extract(ry_analysis* s, const double* x, long long x_len, const double* f0, const double* t, int n, double threshold,
+                        double* sp64_out, float* sp32_dev_out, double* mc_out, double* ap64_out, float* ap32_dev_out, double* coded_out) {
+    Outputs o;
+    o.sp64 = sp64_out; o.sp32_dev = sp32_dev_out; o.mc = mc_out;
+    o.d4c = true; o.threshold = threshold; o.ap64 = ap64_out; o.ap32_dev = ap32_dev_out; o.coded = coded_out;
+    return run_frames(s, x, x_len, f0, t, n, true, o);
+}
+
+int ry_analysis_d4c_bands(ry_analysis* s) {
+    if (!s) return fail(RY_ESTATE, "null analysis handle");
+    if (!s->d4c_ok) return fail(RY_EINVAL, "%s", s->d4c_why.c_str());
+    return s->n_bands;
 }
 
 int ry_analysis_sp2mc(ry_analysis* s, const void* sp, int n, int on_device, double* mc_out) {
@@ -177,7 +299,26 @@ int ry_analysis_sp2mc(ry_analysis* s, const void* sp, int n, int on_device, doub
 int ry_analysis_debug_record(ry_analysis* s, int on) {
     if (!s) return fail(RY_ESTATE, "null analysis handle");
     s->record = on != 0;
-    if (!s->record) s->last_ints.clear();
+    if (!s->record) { s->last_ints.clear(); s->last_rec.clear(); }
+    return RY_OK;
+}
+
+int ry_analysis_debug_d4c(ry_analysis* s, long long* ints_out, double* values_out, int capacity, int* n) {
+    if (!s || !n) return fail(RY_EINVAL, "bad argument");
+    *n = (int)s->last_rec.size();
+    if (!ints_out && !values_out) return RY_OK;                    // the count alone
+    if (capacity < *n) return fail(RY_EINVAL, "%d frames, room for %d", *n, capacity);
+    for (int i = 0; i < *n; ++i) {
+        const D4cFrameRecord& r = s->last_rec[i];
+        if (ints_out) {
+            const long long v[9] = {r.v.h3, r.v.h4, r.v.om, r.v.oc, r.v.op, r.v.L, r.v.b1, r.v.b2, r.on};
+            for (int j = 0; j < 9; ++j) ints_out[9 * i + j] = v[j];
+        }
+        if (values_out) {
+            values_out[4 * i] = r.a0;
+            for (int j = 0; j < D4C_MAX_BANDS; ++j) values_out[4 * i + 1 + j] = r.coarse[j];
+        }
+    }
     return RY_OK;
 }
 
@@ -204,6 +345,9 @@ int ry_analysis_debug_poison(ry_analysis* s) {
     if (s->d_sp) RT_TRY(rt::dmemset(s->d_sp, 0xff, (size_t)s->cap_sp * sizeof(double), st));
     if (s->d_mc) RT_TRY(rt::dmemset(s->d_mc, 0xff, (size_t)s->cap_mc * sizeof(double), st));
     if (s->d_ints) RT_TRY(rt::dmemset(s->d_ints, 0xff, (size_t)s->cap_ints * sizeof(AnalysisFrameInts), st));
+    if (s->d_ap) RT_TRY(rt::dmemset(s->d_ap, 0xff, (size_t)s->cap_ap * sizeof(double), st));
+    if (s->d_coded) RT_TRY(rt::dmemset(s->d_coded, 0xff, (size_t)s->cap_coded * sizeof(double), st));
+    if (s->d_rec) RT_TRY(rt::dmemset(s->d_rec, 0xff, (size_t)s->cap_rec * sizeof(D4cFrameRecord), st));
     RT_TRY(rt::stream_sync(st));
     return RY_OK;
 }

@@ -11,8 +11,15 @@ where this was built.  The one deliberate deviation from `pyworld`: WORLD's two 
 power spectrum) are counter-based functions of (seed, centre sample of the frame, index) instead of draws from a process-global sequence, so a
 frame's rows depend on (x, f0, t, seed) only and not on which other frames share the call.
 
-Limits: fft_size 1024 only (16 and 24 kHz); D4C is NOT built -- `ap` / `coded_ap` come from `aperiodicity`, a module-level callable whose
-default tries `pyworld` and otherwise raises `NotImplementedError`."""
+D4C (`ap`, `coded_ap`) is on the device too (`Analyzer.d4c`, `d4c`, `code_aperiodicity`; restated in tests/world_d4c_ref.py, the same counter-based
+noise with keys of its own), but `extract` takes it only when asked to: `ap` / `coded_ap` come from `aperiodicity`, a module-level callable whose
+default still tries `pyworld` and otherwise raises `NotImplementedError`.  The device path is opted into with
+
+    world_analysis.aperiodicity = world_analysis.device_aperiodicity
+
+after which `extract` makes one `Analyzer.run` for sp, mc, ap and coded_ap (one upload of the wave).
+
+Limits: fft_size 1024 only (16 and 24 kHz), for D4C as well."""
 import ctypes
 import os
 from typing import Optional
@@ -64,12 +71,22 @@ class Analyzer(object):
             self._handle, self._pid = h, os.getpid()
         return self._ctx.lib, self._handle
 
-    def run(self, x, f0, t, want=('sp', 'mc'), device_rows: bool = False):
-        """-> tuple in the order of `want`: 'sp' [frames][513] float64 (with device_rows: `DeviceRows`, the float32 rows left on the card),
-        'mc' [frames][order + 1] float64, 'sp64' the float64 rows whatever `device_rows` says.  No frames: empty arrays; frames but an empty wave:
-        ValueError (the C ABI would succeed and write nothing, and the rows would no longer match `f0`)."""
+    def bands(self) -> int:
+        """The number of D4C bands at this rate (columns of `coded_ap`): 1 at 16 kHz, 3 at 24 kHz."""
         lib, h = self._get()
-        unknown = set(want) - {'sp', 'mc', 'sp64'}
+        b = lib.dll.ry_analysis_d4c_bands(h)
+        if b < 0:
+            lib.check(b)
+        return b
+
+    def run(self, x, f0, t, want=('sp', 'mc'), device_rows: bool = False, threshold: float = 0.85):
+        """-> tuple in the order of `want`: 'sp' [frames][513] float64 (with device_rows: `DeviceRows`, the float32 rows left on the card),
+        'mc' [frames][order + 1] float64, 'sp64' the float64 rows whatever `device_rows` says; D4C (`threshold`): 'ap' [frames][513] float64 (with
+        device_rows: `DeviceRows`), 'ap64', 'coded_ap' [frames][bands] float64.  CheapTrick and D4C asked for together share one upload of the wave.
+        No frames: empty arrays; frames but an empty wave: ValueError (the C ABI would succeed and write nothing, and the rows would no longer
+        match `f0`)."""
+        lib, h = self._get()
+        unknown = set(want) - {'sp', 'mc', 'sp64', 'ap', 'ap64', 'coded_ap'}
         if unknown:
             raise ValueError('want: %s' % sorted(unknown))
         x = numpy.ascontiguousarray(numpy.asarray(x, dtype=numpy.float64).reshape(-1))
@@ -82,14 +99,43 @@ class Analyzer(object):
             raise ValueError('an empty wave cannot be analysed at %d frames' % n)
         sp64 = numpy.empty((n, BINS), numpy.float64) if ('sp64' in want or ('sp' in want and not device_rows)) else None
         mc = numpy.empty((n, self.order + 1), numpy.float64) if 'mc' in want else None
-        rows = None
-        if device_rows and 'sp' in want:
+        d4c = bool(set(want) & {'ap', 'ap64', 'coded_ap'})
+        cheaptrick = bool(set(want) & {'sp', 'sp64', 'mc'}) or not d4c
+        ap64 = numpy.empty((n, BINS), numpy.float64) if ('ap64' in want or ('ap' in want and not device_rows)) else None
+        coded = numpy.empty((n, self.bands()), numpy.float64) if 'coded_ap' in want else None
+
+        def device(key):
+            if not (device_rows and key in want):
+                return None
             buf = _DeviceBuffer(self._ctx, max(n, 1) * BINS)
-            rows = DeviceRows(buf.address, n, keep=buf)
-        lib.check(lib.dll.ry_analysis_run(h, _dptr(x), x.size, _dptr(f0), _dptr(t), n, _dptr(sp64), _lib._fptr(rows.address if rows else None),
-                                          _dptr(mc)))
-        got = {'sp': rows if device_rows else sp64, 'sp64': sp64, 'mc': mc}
+            return DeviceRows(buf.address, n, keep=buf)
+        rows, rows_ap = device('sp'), device('ap')
+        head = (h, _dptr(x), x.size, _dptr(f0), _dptr(t), n)
+        out_sp = (_dptr(sp64), _lib._fptr(rows.address if rows else None), _dptr(mc))
+        out_ap = (_dptr(ap64), _lib._fptr(rows_ap.address if rows_ap else None), _dptr(coded))
+        if not d4c:
+            lib.check(lib.dll.ry_analysis_run(*(head + out_sp)))
+        elif not cheaptrick:
+            lib.check(lib.dll.ry_analysis_d4c(*(head + (float(threshold),) + out_ap)))
+        else:
+            lib.check(lib.dll.ry_analysis_extract(*(head + (float(threshold),) + out_sp + out_ap)))
+        got = {'sp': rows if device_rows else sp64, 'sp64': sp64, 'mc': mc, 'ap': rows_ap if device_rows else ap64, 'ap64': ap64, 'coded_ap': coded}
         return tuple(got[k] for k in want)
+
+    def d4c(self, x, f0, t, threshold: float = 0.85) -> numpy.ndarray:
+        """`pyworld.d4c` of this analyzer's rate: -> aperiodicity [frames][513] float64."""
+        return self.run(x, f0, t, want=('ap',), threshold=threshold)[0]
+
+    def d4c_record(self):
+        """tests: what the last D4C run after `record_integers()` decided -> (integers [frames][8] int64: half length of the Love-Train window, of the
+        other windows, origins of the windows at t - 0.25 / f, t, t + 0.25 / f, DC-correction bin limit, smoothing boundaries of width f and f / 2;
+        on [frames] bool; a0 [frames]; coarse dB [frames][bands])."""
+        lib, h = self._get()
+        n = ctypes.c_int()
+        lib.check(lib.dll.ry_analysis_debug_d4c(h, None, None, 0, ctypes.byref(n)))
+        ints, vals = numpy.empty((n.value, 9), numpy.int64), numpy.empty((n.value, 4), numpy.float64)
+        lib.check(lib.dll.ry_analysis_debug_d4c(h, ints.ctypes.data_as(_LLP), _dptr(vals), n.value, ctypes.byref(n)))
+        return ints[:, :8], ints[:, 8] != 0, vals[:, 0], vals[:, 1:1 + self.bands()]
 
     def sp2mc(self, sp) -> numpy.ndarray:
         """Mel-cepstrum of a spectrogram that comes from elsewhere: [frames][513] host rows (taken as float64) or `DeviceRows` (float32)."""
@@ -167,8 +213,8 @@ def sp2mc(sp, order, alpha):
 
 
 def aperiodicity(x, f0, t, fs, fft_size):
-    """(ap, coded_ap) of the frames.  D4C is the stage of the analysis that is not built here: this default hands it to `pyworld` where that
-    package exists; assign another callable of the same signature to `world_analysis.aperiodicity` to replace it."""
+    """(ap, coded_ap) of the frames.  This default hands D4C to `pyworld` where that package exists; assign another callable of the same
+    signature to `world_analysis.aperiodicity` to replace it -- `device_aperiodicity` for D4C on the device."""
     try:
         import pyworld
         ap = pyworld.d4c(x, f0, t, fs, fft_size=fft_size)
@@ -178,16 +224,44 @@ def aperiodicity(x, f0, t, fs, fft_size):
                                   'assign a callable (x, f0, t, fs, fft_size) -> (ap, coded_ap) to world_analysis.aperiodicity') from e
 
 
+def d4c(x, f0, temporal_positions, fs, threshold=0.85, fft_size=None):
+    """`pyworld.d4c`: -> aperiodicity [frames][fft_size / 2 + 1] float64 (fft_size 1024 only)."""
+    return _analyzer(fs, fft_size, 0, 0.0).d4c(x, f0, temporal_positions, threshold)
+
+
+def code_aperiodicity(ap, fs):
+    """`pyworld.code_aperiodicity`: aperiodicity [frames][513] -> its dB values at 3000 i Hz, [frames][bands] float64.  A read of the columns
+    that are those frequencies (bins 192 i at 16 kHz, 128 i at 24 kHz): host arithmetic, no kernel."""
+    ap = numpy.atleast_2d(numpy.asarray(ap, dtype=numpy.float64))
+    if ap.shape[1] != BINS:
+        raise ValueError('ap must be (frames, %d), got %s' % (BINS, ap.shape))
+    fs = int(fs)
+    bands = int(min(15000.0, fs / 2.0 - 3000.0) / 3000.0)
+    if bands < 1 or (3000 * FFT_SIZE) % fs:
+        raise ValueError('code_aperiodicity at %d Hz: built for the rates whose band centres are bins of the row (16 and 24 kHz)' % fs)
+    return 20.0 * numpy.log10(ap[:, [3000 * i * FFT_SIZE // fs for i in range(1, bands + 1)]])
+
+
+def device_aperiodicity(x, f0, t, fs, fft_size):
+    """(ap, coded_ap) of the frames from the device: assign it to `world_analysis.aperiodicity` to take D4C from the card."""
+    ap, coded = _analyzer(fs, fft_size, 0, 0.0).run(x, f0, t, want=('ap', 'coded_ap'))
+    return ap, coded
+
+
 def extract(cls, wave, frame_period, f0_floor, f0_ceil, fft_length, order, alpha, dtype):
     """Drop-in body of `AcousticFeature.extract`: f0 from `cls.extract_f0` (so a bound CREPE wrapper keeps working), `sp` / `mc` from the
-    device, `ap` / `coded_ap` from `world_analysis.aperiodicity`.  Returns the plain `AcousticFeature` container whatever `cls` is, like the original."""
+    device, `ap` / `coded_ap` from `world_analysis.aperiodicity` (when that is `device_aperiodicity`: all four from one `Analyzer.run`).
+    Returns the plain `AcousticFeature` container whatever `cls` is, like the original."""
     x = wave.wave.astype(numpy.float64)
     fs = wave.sampling_rate
     f0, t = cls.extract_f0(x=x, fs=fs, frame_period=frame_period, f0_floor=f0_floor, f0_ceil=f0_ceil)
     f0, t = numpy.asarray(f0, numpy.float64), numpy.asarray(t, numpy.float64)
     fft_size = int(fft_length) if fft_length else cheaptrick_fft_size(fs)
-    sp, mc = _analyzer(fs, fft_size, order, float(alpha)).run(x, f0, t, want=('sp', 'mc'))
-    ap, coded_ap = aperiodicity(x, f0, t, fs, fft_size)
+    if aperiodicity is device_aperiodicity:
+        sp, mc, ap, coded_ap = _analyzer(fs, fft_size, order, float(alpha)).run(x, f0, t, want=('sp', 'mc', 'ap', 'coded_ap'))
+    else:
+        sp, mc = _analyzer(fs, fft_size, order, float(alpha)).run(x, f0, t, want=('sp', 'mc'))
+        ap, coded_ap = aperiodicity(x, f0, t, fs, fft_size)
     voiced = ~(f0 == 0)
     # the plain container, as the body this replaces builds it: `cls` may be a wrapper whose constructor takes more (the reference's
     # AcousticFeatureWrapper needs `wave` and builds itself from this result's __dict__)
