@@ -279,9 +279,14 @@ int ry_crepe_decode(ry_crepe* crepe, const float* activation, int n_frames, int 
  * ry_crepe_create builds them with the C library's log; a caller whose decode must match its own restatement bit for bit uploads
  * that restatement's values (realtime_yukarin_amd/crepe.py uploads numpy's). */
 int ry_crepe_set_viterbi_tables(ry_crepe* crepe, const double* logT, const double* logE, const double* logS);
-/* tests: the buffers of the last pass of ry_crepe_predict (its last <= 256 frames): layer 0 the normalised frames [n][1024],
- * 1 .. 6 the pooled conv outputs [n][positions][channels], 7 the logits [n][360]. */
-int ry_crepe_debug_layer(ry_crepe* crepe, int layer, float* out);
+/* tests: the first n_frames rows of the buffers of the last pass of ry_crepe_predict (its last <= 256 frames): layer 0 the normalised
+ * frames [n][1024], 1 .. 6 the pooled conv outputs [n][positions][channels], 7 the logits [n][360].  n_frames may exceed the frames of
+ * that pass, up to the largest pass the handle has run: the rows behind it hold what an earlier call or ry_crepe_debug_poison left. */
+int ry_crepe_debug_layer(ry_crepe* crepe, int layer, int n_frames, float* out);
+/* tests: fills every element the next ry_crepe_predict / ry_crepe_decode must write with NaN bit patterns (all bits set; -1 as an index) --
+ * the samples of the frame rows, the interior rows of every layer's input, logits, split-K slabs, activation, confidence, f0, observations,
+ * back-pointers and path -- and leaves the zero padding rows as they are: a later call that reads anything it did not write shows it. */
+int ry_crepe_debug_poison(ry_crepe* crepe);
 /* diagnostics: the split-K count of conv1 .. conv6 and the dense layer (7 ints). */
 int ry_crepe_debug_splits(ry_crepe* crepe, int* splits);
 

@@ -307,13 +307,19 @@ class CrepeModel(object):
         return f0, conf, path
 
     def debug_layer(self, layer: int, frames: int) -> numpy.ndarray:
-        """The last pass's buffer `layer` (0 frames, 1 .. 6 pooled conv outputs, 7 logits) for its `frames` frames (`ry_crepe_debug_layer`)."""
+        """The first `frames` rows of the last pass's buffer `layer` (0 frames, 1 .. 6 pooled conv outputs, 7 logits); rows behind the
+        frames of that pass are what an earlier call or `poison` left (`ry_crepe_debug_layer`)."""
         lib, h = self._get()
         c = channels(self.m)
         shape = {0: (frames, FRAME), 7: (frames, BINS)}.get(layer) or (frames, (FRAME // 4) >> layer, c[layer - 1])
         out = numpy.empty(shape, numpy.float32)
-        lib.check(lib.dll.ry_crepe_debug_layer(h, int(layer), _lib._fptr(out)))
+        lib.check(lib.dll.ry_crepe_debug_layer(h, int(layer), int(frames), _lib._fptr(out)))
         return out
+
+    def poison(self) -> None:
+        """Tests: NaN bit patterns in everything the next `predict16k` / `decode` must write (`ry_crepe_debug_poison`)."""
+        lib, h = self._get()
+        lib.check(lib.dll.ry_crepe_debug_poison(h))
 
     def splits(self) -> List[int]:
         lib, h = self._get()

@@ -50,6 +50,7 @@ struct ry_crepe {
     float* act_in[NCONV + 1] = {};                  // act_in[0] = frames, act_in[i] = input of layer i (conv i + 1 / dense)
     float* logits = nullptr;
     float* slabs = nullptr;
+    size_t slab_floats = 0;
     int last_chunk = 0;                             // frames of the last pass (ry_crepe_debug_layer)
     // call buffers (every frame of a call)
     Arena call;
@@ -73,7 +74,8 @@ int ensure_chunk(ry_crepe* c, int nf) {
         if (l.splits > 1) slab = std::max(slab, (size_t)l.splits * cap * l.lout * l.cout);
     }
     RY_TRY(c->bufs.alloc(&c->logits, (size_t)cap * CREPE_BINS));
-    RY_TRY(c->bufs.alloc(&c->slabs, std::max(slab, (size_t)1)));
+    c->slab_floats = std::max(slab, (size_t)1);
+    RY_TRY(c->bufs.alloc(&c->slabs, c->slab_floats));
     c->cap_chunk = cap;
     return RY_OK;
 }
@@ -325,13 +327,14 @@ int ry_crepe_decode(ry_crepe* c, const float* activation, int n_frames, int vite
     return RY_OK;
 }
 
-int ry_crepe_debug_layer(ry_crepe* c, int layer, float* out) {
+int ry_crepe_debug_layer(ry_crepe* c, int layer, int n_frames, float* out) {
     if (!c) return fail(RY_ESTATE, "null crepe handle");
     if (!out || layer < 0 || layer > NCONV + 1) return fail(RY_EINVAL, "bad argument (layer %d: 0 frames, 1 .. 6 conv outputs, 7 logits)", layer);
     if (c->last_chunk < 1) return fail(RY_ESTATE, "no ry_crepe_predict has run");
+    if (n_frames < 1 || n_frames > c->cap_chunk) return fail(RY_EINVAL, "%d frames asked for, the pass buffers hold %d", n_frames, c->cap_chunk);
     const ry_stream_t s = c->ctx->stream;
     RT_TRY(rt::set_device(c->ctx->device));
-    const int n = c->last_chunk;
+    const int n = n_frames;
     if (layer == NCONV + 1) {
         RT_TRY(rt::d2h(out, c->logits, (size_t)n * CREPE_BINS * sizeof(float), s));
         RT_TRY(rt::stream_sync(s));
@@ -348,6 +351,36 @@ int ry_crepe_debug_layer(ry_crepe* c, int layer, float* out) {
     RT_TRY(rt::stream_sync(s));
     for (int f = 0; f < n; ++f)
         memcpy(out + (size_t)f * rows * cols, h.data() + (size_t)f * dst.in_fstride + off, (size_t)rows * cols * sizeof(float));
+    return RY_OK;
+}
+
+int ry_crepe_debug_poison(ry_crepe* c) {
+    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    const ry_stream_t s = c->ctx->stream;
+    RT_TRY(rt::set_device(c->ctx->device));
+    RT_TRY(rt::stream_sync(s));
+    // all bits set (NaN as a float, -1 as an index) in everything the next call must write; the padding rows keep their zeros
+    for (int i = 0; i <= NCONV && c->cap_chunk > 0; ++i) {
+        const CLayer& l = c->L[i];
+        const size_t off = i == 0 ? CREPE_CONV1_PAD : i == NCONV ? 0 : (size_t)PAD_L * l.cin;
+        const size_t n = i == 0 ? CREPE_FRAME : i == NCONV ? (size_t)l.in_fstride : (size_t)l.lin * l.cin;
+        for (int f = 0; f < c->cap_chunk; ++f)
+            RT_TRY(rt::dmemset(c->act_in[i] + (size_t)f * l.in_fstride + off, 0xff, n * sizeof(float), s));
+    }
+    if (c->cap_chunk > 0) {
+        RT_TRY(rt::dmemset(c->logits, 0xff, (size_t)c->cap_chunk * CREPE_BINS * sizeof(float), s));
+        RT_TRY(rt::dmemset(c->slabs, 0xff, c->slab_floats * sizeof(float), s));
+    }
+    if (c->cap_frames > 0) {
+        const size_t F = (size_t)c->cap_frames;
+        RT_TRY(rt::dmemset(c->act, 0xff, F * CREPE_BINS * sizeof(float), s));
+        RT_TRY(rt::dmemset(c->conf, 0xff, F * sizeof(float), s));
+        RT_TRY(rt::dmemset(c->f0, 0xff, F * sizeof(float), s));
+        RT_TRY(rt::dmemset(c->obs, 0xff, F * sizeof(int), s));
+        RT_TRY(rt::dmemset(c->path, 0xff, F * sizeof(int), s));
+        RT_TRY(rt::dmemset(c->bp, 0xff, F * CREPE_BINS * sizeof(int), s));
+    }
+    RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }
 

@@ -5,6 +5,7 @@ from oracle import ops_numpy as ops
 from oracle import unet
 
 TOL = 1e-4   # BASELINE.json north_star: "within 1e-4 relative fp32"
+F32_TOL = 1e-5   # element-wise against float64, in units of the bound of a sum: any fp32 summation order of the same products (the oracle files)
 
 # B, L, Cin, Cout, k, stride, pad, dilate, transposed, act, splits
 CONV1D_CASES = [

@@ -12,6 +12,7 @@ import numpy
 import pytest
 
 import crepe_ref
+from crepe_cases import tie_activations
 from realtime_yukarin_amd import _lib, build, crepe
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -89,25 +90,6 @@ def test_split_k_path_is_used(models):
 
 
 # ---- decode ---------------------------------------------------------------------------------------------------------------------
-def tie_activations(n, seed):
-    """Activations with many exact ties: flat rows, rows with two equal maxima, plateaus, and a wandering peak."""
-    rng = numpy.random.default_rng(seed)
-    a = numpy.zeros((n, 360), numpy.float32)
-    for t in range(n):
-        kind = t % 4
-        if kind == 0:
-            a[t] = 0.5
-        elif kind == 1:
-            i, j = rng.integers(0, 360, 2)
-            a[t, i] = a[t, j] = 0.75
-        elif kind == 2:
-            c = int(rng.integers(20, 340))
-            a[t, c - 6:c + 6] = 0.6
-        else:
-            a[t] = rng.integers(0, 4, 360) / 4.0
-    return a
-
-
 @pytest.mark.parametrize('seed', [0, 1])
 def test_viterbi_path_bit_identical_with_ties(models, seed):
     model = models[1][0]

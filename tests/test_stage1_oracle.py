@@ -14,7 +14,7 @@ import pytest
 from conftest import rel_max
 import cases
 
-F32_TOL = 1e-5          # fp32: any summation order of the same products
+F32_TOL = cases.F32_TOL  # fp32: any summation order of the same products
 SLICES = ((4, 8), (4, 4), (2, 8), (2, 4))
 
 
