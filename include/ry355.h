@@ -289,6 +289,16 @@ int ry_crepe_debug_layer(ry_crepe* crepe, int layer, int n_frames, float* out);
 int ry_crepe_debug_poison(ry_crepe* crepe);
 /* diagnostics: the split-K count of conv1 .. conv6 and the dense layer (7 ints). */
 int ry_crepe_debug_splits(ry_crepe* crepe, int* splits);
+/* tests (the predictors' counterpart of ry_crepe_debug_layer): one buffer of the launch plan that ran last on this handle (ry_net_forward, ry_ac_convert,
+ * ry_sr_convert, ry_sr_convert_rows), copied to the host once its stream has drained.  layer -1, kind 0: the convert wrapper's padded input
+ * [batch][T][cols] (stage 1: in_ch columns; stage 2: log of the spectrogram without its last bin, width columns).  layer 0 .. 15 (stage 2), kind 0:
+ * that layer's fp32 output [batch][Ho][Wo][Cout]; kind 1: its 16-bit copy as raw uint16, plain bf16 [pixel][Cout] or split-bf16 [pixel][hi (Cout) |
+ * lo (Cout)].  Rows a cropped window did not compute hold what the allocation (RY_POISON=1: NaN patterns) or an earlier run left.
+ * dims[5] = batch, rows, columns, elements per pixel, format (0 fp32, 1 bf16, 2 split-bf16); out = NULL returns the dims alone, else out_bytes must
+ * be the block's exact size.  RY_EINVAL when the plan has no such buffer or nothing wrote it: a copy no consumer reads, the last layer when it stores
+ * into the caller's block (the raw forward; the fused 3x3 end layer of a convert), the padded input of a raw forward or of a stage-1 window whose
+ * first layer pads for itself.  Adds nothing to the forward / convert path: the handle only remembers which plan ran. */
+int ry_net_debug_activation(ry_net* net, int layer, int kind, void* out, size_t out_bytes, int* dims);
 
 /* ---- WORLD synthesizer (`pyworld.synthesize(f0, sp, ap, fs, frame_period)` in the reference's Vocoder.decode and world4py's realtime
  * synthesizer in RealtimeVocoder.decode, yukarin_wrapper/vocoder.py:50-120).  Semantics: INTEGRATION.md section 10 and

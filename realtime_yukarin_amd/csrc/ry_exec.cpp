@@ -304,7 +304,6 @@ static int launch_conv2d(Launcher& Lc, const Layer& l, const LayerPlan& lp, int 
             const long long nb = (strips + 7) / 8;
             dim3 sg((unsigned)(((nb + 7) / 8) * 8));
             RY_TRY(Lc.begin("ry_sr_last<false>", l.name, lp.flops, lp.bytes, sg));
-            p.x3 = 0;
             RY_LAUNCH(ry_sr_last<false>, sg, 256, Lc.stream, p);
         } else {
             RY_TRY(Lc.begin("ry_sr_last_gather", l.name, lp.flops, lp.bytes, grid));
@@ -421,10 +420,7 @@ static int enqueue_forward(ry_net* net, Plan& P, Launcher& Lc) {
     const int lo = 0, hi = 16;
     const int nd = d.ndim, B = P.B;
     const float slope = d.lrelu_slope;
-    // the fused pad takes the column minimum inside the workgroups that reach the padding: one chain of n_frames / 8 load rounds, worth
-    // it while the window is short (measured: 300 frames -3 us, 1000 frames +14 us against the separate ry_pad_min_rows node)
-    // [r5] (the cooperative minimum: one round of loads per 1024 frames; was 512 with the per-lane walk)
-    const bool padfuse_now = nd == 1 && P.s1_padfuse && P.n_frames <= 2048;
+    const bool padfuse_now = plan_padfuse_now(net, P);     // (ry_plan.h)
     if (P.mode == 1 && !padfuse_now) {
         const int cols_in = nd == 1 ? d.in_ch : d.width + 1;
         const int cols_out = nd == 1 ? d.in_ch : d.width;
@@ -587,7 +583,7 @@ int get_plan(ry_net* net, int B, int T, int mode, int n_frames, Plan** out) {
     if (it == net->plans.end()) {
         if (net->plans.size() >= 16) {                         // bounded cache; queued work may still use the old plans' buffers
             RT_TRY(rt::stream_sync(net->stream));
-            net->plans.clear();
+            net->plans.clear(); net->last_plan = nullptr;
         }
         std::unique_ptr<Plan> P(new Plan());
         P->B = B; P->T = T; P->mode = mode; P->n_frames = n_frames;
@@ -610,6 +606,7 @@ int run_plan(ry_net* net, Plan& P, const float* x, float* y, int on_device) {
     const float* want_in = on_device ? x : P.user_in;
     float* want_out = on_device ? y : P.user_out;
     P.cur_in = want_in; P.cur_out = want_out;
+    net->last_plan = &P;
     if (!on_device) RT_TRY(rt::h2d(P.user_in, x, in_bytes, net->stream));
     Launcher Lc{net, ctx, net->stream, nullptr, nullptr};
 #ifndef RY_HOST_EMU

@@ -270,6 +270,7 @@ struct ry_net {
     std::vector<Layer> layers;
     std::shared_ptr<Arena> weights = std::make_shared<Arena>();   // filters, scale / shift: shared by the clones of a predictor (ry_net_clone)
     std::map<std::tuple<int, int, int, int>, std::unique_ptr<Plan>> plans;
+    Plan* last_plan = nullptr;               // the plan run_plan ran last (ry_net_debug_activation); null whenever `plans` is emptied
     bool use_graph = true;
     // profiling hook
     std::vector<KernelRec>* rec = nullptr;

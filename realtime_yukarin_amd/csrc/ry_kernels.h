@@ -1420,7 +1420,6 @@ struct RySrLastParams {
     int out_rows;               // rows per image of `out` (the real frames of the window)
     int out_cols;               // W, or W + 1 with the last bin repeated (pad mode 'edge')
     int do_exp;
-    int x3;                     // sources are split-bf16 copies [pixel][hi | lo] (rolling form only)
     int xcd_band;               // rolling form: 1 = each XCD takes a contiguous band of output rows (the grid is then padded to 8 x ceil(blocks / 8))
 };
 
@@ -1466,11 +1465,12 @@ RY_KERNEL(256) void ry_sr_last_gather(RySrLastParams p) {
 // lane = 4 channels.  Every input pixel vector of the 3 x 18 halo is loaded ONCE, multiplied by the three
 // kx taps of its row and accumulated into the outputs it touches; the 16 per-lane partial sums are then
 // reduced across the 32 lanes with a transposing (reduce-scatter) butterfly: 15 + 1 shuffles instead of 80.
-// X3 = true (split-bf16 mode): the two sources are the producers' split-bf16 copies [pixel][hi (Cs) | lo (Cs)] (ry_st4_bf16_x3) and a
-// lane rebuilds its four channels as hi + lo -- the same bytes per pixel as fp32, and neither producer has to write an fp32
-// copy for this layer alone.
+// The sources are fp32 in every dtype mode (build_plan keeps the fp32 copies of both producers for this layer).  X3 = true was a form that read
+// the producers' split-bf16 copies; no launch ever took it and it is gone -- the parameter stays so that the kernel keeps the
+// name the profiles of every round carry, ry_sr_last<false>.
 template <bool X3>
 RY_KERNEL(256, 2) void ry_sr_last(RySrLastParams p) {
+    static_assert(!X3, "ry_sr_last reads fp32 sources only");
     constexpr int SW = 16;
     const int l = (int)threadIdx.x & 31;
     const int strips = p.W / SW;
@@ -1495,18 +1495,7 @@ RY_KERNEL(256, 2) void ry_sr_last(RySrLastParams p) {
     const int Cs = first ? p.C1 : p.C2;
     const float* src = first ? p.src1 : p.src2;
     const int cl = first ? c : c - p.C1;            // this lane's first channel inside its source
-    // four channels of pixel `px` of a source row: fp32 -> one 16-byte load; split-bf16 -> hi and lo halves, 8 bytes each
-    auto ldpx = [&](const float* row, int px) -> f32x4 {
-        if (X3) {
-            const unsigned short* q = reinterpret_cast<const unsigned short*>(row) + (size_t)px * (size_t)(2 * Cs) + cl;
-            const u16x4 h = *reinterpret_cast<const u16x4*>(q), lo = *reinterpret_cast<const u16x4*>(q + Cs);
-            f32x4 v;
-            v[0] = ry_bf2f(h[0]) + ry_bf2f(lo[0]); v[1] = ry_bf2f(h[1]) + ry_bf2f(lo[1]);
-            v[2] = ry_bf2f(h[2]) + ry_bf2f(lo[2]); v[3] = ry_bf2f(h[3]) + ry_bf2f(lo[3]);
-            return v;
-        }
-        return ry_ld4(row + (size_t)px * Cs + cl);
-    };
+    auto ldpx = [&](const float* row, int px) -> f32x4 { return ry_ld4(row + (size_t)px * Cs + cl); };      // four channels of pixel `px` of a source row
     float acc[SW + 2];                             // acc[j] = output column x0 - 1 + j (two halo slots are discarded)
 #pragma unroll
     for (int j = 0; j < SW + 2; ++j) acc[j] = 0.f;
@@ -1521,7 +1510,7 @@ RY_KERNEL(256, 2) void ry_sr_last(RySrLastParams p) {
             f32x4 w1 = ry_ld4(p.w + (size_t)(ky * 3 + 1) * 128 + c);
             f32x4 w2 = ry_ld4(p.w + (size_t)(ky * 3 + 2) * 128 + c);
             w0 *= rz; w1 *= rz; w2 *= rz;
-            const float* row = src + ((size_t)b * p.H + iyc) * p.W * Cs;      // a split-bf16 pixel is 2 Cs bf16 = Cs floats too
+            const float* row = src + ((size_t)b * p.H + iyc) * p.W * Cs;
             // interior columns x0 .. x0+SW-1 are always inside the image (W % SW == 0): no tests, loads batch freely
 #pragma unroll
             for (int j = 1; j <= SW; ++j) {

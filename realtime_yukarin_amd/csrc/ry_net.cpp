@@ -160,7 +160,7 @@ void ry_net_destroy(ry_net* net) {
     auto& v = net->ctx->nets;
     for (size_t i = 0; i < v.size(); ++i)
         if (v[i] == net) { v.erase(v.begin() + i); break; }
-    net->plans.clear();
+    net->plans.clear(); net->last_plan = nullptr;
     if (net->has_done) rt::event_destroy(net->done);
     rt::stream_destroy(net->stream);
     delete net;
@@ -179,7 +179,7 @@ int ry_net_set_dtype(ry_net* net, int dtype) {
     if (dtype != 0)
         for (Layer& l : net->layers) RY_TRY(prepare_bf16(ctx, *net->weights, l, dtype));
     net->dtype = dtype;
-    net->plans.clear();                              // launch plans (and captured graphs) depend on the kernel choice
+    net->plans.clear(); net->last_plan = nullptr;    // launch plans (and captured graphs) depend on the kernel choice
     return RY_OK;
 }
 
@@ -243,6 +243,50 @@ int ry_net_profile_window(ry_net* net, int n_frames, int reps, ry_kernel_stat* s
     RY_TRY(get_plan(net, 1, n_frames + (128 - n_frames % 128), 1, n_frames, &P));
     P->disc_front = P->disc_back = 0;
     return profile_plan(net, P, reps, stats, max_stats, n_stats);
+}
+
+// tests: one buffer of the plan that ran last on this handle, copied to the host after the stream has drained -- no node, no copy and no flag on
+// the forward / convert path itself (run_plan only remembers the plan's address).  layer -1: the padded input x_in of the convert wrapper
+// [B][T][cols]; layer 0 .. 15: kind 0 the fp32 output [B][Ho][Wo][Cout], kind 1 its 16-bit copy as raw uint16, plain bf16 [pixel][Cout] or split-bf16
+// [pixel][hi (Cout) | lo (Cout)].  dims = {B, H, W, elements per pixel, format (0 fp32, 1 bf16, 2 split-bf16)}; out may be null (dims only), else
+// out_bytes must be the exact size.  RY_EINVAL when this plan has no such buffer or nothing wrote it: a copy no consumer reads (w32 / w16), a last
+// layer that stores into the caller's block, x_in of a raw forward or of a stage-1 window whose first layer pads for itself.
+int ry_net_debug_activation(ry_net* net, int layer, int kind, void* out, size_t out_bytes, int* dims) {
+    if (!net || !dims) return fail(RY_EINVAL, "null argument");
+    const Plan* P = net->last_plan;
+    if (!P) return fail(RY_EINVAL, "no forward or convert has run on this handle since its plans were dropped");
+    const int nd = net->desc.ndim;
+    const void* src = nullptr;
+    size_t esize = 4;
+    if (layer == -1 && kind == 0) {
+        if (P->mode != 1 || !P->x_in) return fail(RY_EINVAL, "the raw forward has no padded input: it reads the caller's block");
+        if (plan_padfuse_now(net, *P)) return fail(RY_EINVAL, "the first layer of this window padded the caller's block itself: x_in was not written");
+        dims[0] = P->B; dims[1] = P->T; dims[2] = nd == 1 ? net->desc.in_ch : net->desc.width; dims[3] = 1; dims[4] = 0;
+        src = P->x_in;
+    } else if (layer >= 0 && layer < 16 && (kind == 0 || kind == 1)) {
+        if (nd != 2) return fail(RY_EINVAL, "layer buffers are handed back for the stage-2 predictor only");
+        const LayerPlan& lp = P->lp[layer];
+        const int N = net->layers[layer].cout;
+        dims[0] = P->B; dims[1] = lp.Ho; dims[2] = lp.Wo;
+        if (kind == 0) {
+            if (layer == 15 && (P->mode == 0 || lp.path == PATH_LAST)) return fail(RY_EINVAL, "%s stored into the caller's block", net->layers[layer].name);
+            if (!lp.w32 && lp.w16) return fail(RY_EINVAL, "%s writes no fp32 copy in this plan", net->layers[layer].name);
+            dims[3] = N; dims[4] = 0; src = lp.out;
+        } else {
+            if (!lp.w16 || !lp.out16) return fail(RY_EINVAL, "%s writes no 16-bit copy in this plan", net->layers[layer].name);
+            dims[3] = lp.o16x3 ? 2 * N : N; dims[4] = lp.o16x3 ? 2 : 1; src = lp.out16; esize = 2;
+        }
+    } else {
+        return fail(RY_EINVAL, "layer must be -1 (kind 0) or 0 .. 15 with kind 0 (fp32) or 1 (16-bit copy); got %d, %d", layer, kind);
+    }
+    if (!out) return RY_OK;
+    const size_t want = (size_t)dims[0] * dims[1] * dims[2] * dims[3] * esize;
+    if (out_bytes != want) return fail(RY_EINVAL, "the buffer holds %zu bytes, this block has %zu", out_bytes, want);
+    RT_TRY(rt::set_device(net->ctx->device));
+    RT_TRY(rt::stream_sync(net->stream));
+    RT_TRY(rt::d2h(out, src, want, net->stream));
+    RT_TRY(rt::stream_sync(net->stream));
+    return RY_OK;
 }
 
 // diagnostics / tests: read the process-wide RY_* switches again (they are otherwise read when a context is created; launch plans built before keep

@@ -88,6 +88,10 @@ bool plan_tile_rows(const LayerPlan& lp, int Mh, int Mw, int* th, int* tw_out = 
 bool plan_hole_ok(const Layer& l, const LayerPlan& lp, int lo, int n);
 int plan_s2_layer(ry_ctx* ctx, Arena& arena, const Layer& l, LayerPlan& lp, int B, int dtype, const LayerForce& f, bool src16, bool out_layer, int mode);
 WindowRows plan_window_rows(const ry_net* net, const Plan& P);
+// Does the first stage-1 layer of this enqueue pad the caller's block itself (no ry_pad_min_rows node, Plan::x_in stays unwritten)?  The fused pad
+// takes the column minimum inside the workgroups that reach the padding: one chain of n_frames / 8 load rounds, worth it while the window is
+// short (measured: 300 frames -3 us, 1000 frames +14 us against the separate node; the cooperative minimum: one round of loads per 1024 frames)
+inline bool plan_padfuse_now(const ry_net* net, const Plan& P) { return net->desc.ndim == 1 && P.s1_padfuse && P.n_frames <= 2048; }
 int build_plan(ry_net* net, Plan& P);
 int autotune_plan(ry_net* net, Plan& P);
 int get_plan(ry_net* net, int B, int T, int mode, int n_frames, Plan** out);

@@ -7,6 +7,7 @@
 // are driven through the C ABI of ry_net.cpp (ry_ac_convert, ry_sr_convert_rows, ry_net_clone).
 #include "ry_vc_kernels.h"
 #include "ry_host.h"
+#include "ry_plan.h"
 
 // ---- device-resident VoiceChanger core -----------------------------------------------------------
 
@@ -66,7 +67,7 @@ struct ry_vc {
     static ry_net* follow(ry_net* n, ry_net* src) {
         if (n != src && n->dtype != src->dtype) {
             rt::stream_sync(n->stream);
-            n->layers = src->layers; n->dtype = src->dtype; n->plans.clear();
+            n->layers = src->layers; n->dtype = src->dtype; n->plans.clear(); n->last_plan = nullptr;
         }
         return n;
     }
@@ -653,6 +654,7 @@ int ry_mc2sp(ry_ctx* ctx, const float* mc, const float* mtx, int n, int m, int b
     Arena a;
     float *dmc = nullptr, *dmtx = nullptr, *dsp = nullptr;
     RY_TRY(a.alloc(&dmc, (size_t)n * m)); RY_TRY(a.alloc(&dmtx, (size_t)m * bins)); RY_TRY(a.alloc(&dsp, (size_t)n * bins));
+    RY_TRY(poison_fill(ctx, dsp, (size_t)n * bins));                       // RY_POISON: an element the launch leaves out comes back as NaN
     RT_TRY(rt::h2d(dmc, mc, (size_t)n * m * sizeof(float), ctx->stream));
     RT_TRY(rt::h2d(dmtx, mtx, (size_t)m * bins * sizeof(float), ctx->stream));
     RyMc2spParams mp;

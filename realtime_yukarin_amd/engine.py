@@ -461,6 +461,20 @@ class Net(object):
         fn = self.ctx.lib.dll.ry_ac_convert if self.desc.ndim == 1 else self.ctx.lib.dll.ry_sr_convert
         self.ctx.lib.check(fn(self.handle, _lib._fptr(int(x_ptr)), _lib._fptr(int(y_ptr)), batch, n_frames, 1))
 
+    def debug_activation(self, layer: int, kind: int = 0) -> numpy.ndarray:
+        """Tests: one buffer of the plan that ran last on this handle (`ry_net_debug_activation`).  layer -1: the convert wrapper's padded input
+        (B, T, cols) float32; layer 0 .. 15 (stage 2): kind 0 the fp32 output (B, Ho, Wo, Cout), kind 1 its 16-bit copy as raw uint16, (B, Ho, Wo, Cout)
+        plain bf16 or (B, Ho, Wo, 2, Cout) split-bf16 [hi | lo].  Raises `Ry355Error` when the plan has no such buffer."""
+        lib = self.ctx.lib
+        dims = (ctypes.c_int * 5)()
+        lib.check(lib.dll.ry_net_debug_activation(self.handle, int(layer), int(kind), None, 0, dims))
+        B, H, W, C, fmt = (int(v) for v in dims)
+        out = numpy.empty((B, H, W, C), dtype=numpy.float32 if fmt == 0 else numpy.uint16)
+        lib.check(lib.dll.ry_net_debug_activation(self.handle, int(layer), int(kind), out.ctypes.data_as(ctypes.c_void_p), out.nbytes, dims))
+        if layer < 0:
+            return out[..., 0]
+        return out.reshape(B, H, W, 2, C // 2) if fmt == 2 else out
+
     def profile(self, batch: int, frames: int, reps: int = 5, window: bool = False) -> List[dict]:
         """Per-launch timings of the raw forward at `frames` padded rows, or (window=True) of the convert wrapper on one window
         of `frames` real frames -- what the window call runs."""

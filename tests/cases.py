@@ -6,6 +6,8 @@ from oracle import unet
 
 TOL = 1e-4   # BASELINE.json north_star: "within 1e-4 relative fp32"
 F32_TOL = 1e-5   # element-wise against float64, in units of the bound of a sum: any fp32 summation order of the same products (the oracle files)
+X3_TOL = 3e-5    # ... split-bf16 against the fp32-operand reference (the dropped lo * lo term and the 16-bit split)
+BF16_TOL = 1e-5  # ... plain bf16 against the reference on bf16-rounded operands (exact products, fp32 accumulation)
 
 # B, L, Cin, Cout, k, stride, pad, dilate, transposed, act, splits
 CONV1D_CASES = [
@@ -732,3 +734,253 @@ def syn64_stage1_layers(frames, stage1_in=9):
         L = 2 * L if up else (L + 2 * p - k) // s + 1
     assert L == T
     return out
+
+
+# ---- the stage-2 convert graph, node by node (tests/test_stage2_graph_oracle.py) ----
+# Every layer is restated in float64 on the sources the DEVICE read (engine.Net.debug_activation after the run), so errors do not chain and the bar of a
+# layer is one layer's summation error; a poisoned element a node should have written is NaN at that node.
+
+def s2_layers(desc):
+    """The 16 layers of a stage-2 predictor restated from oracle/unet.py (never from the library): name, parameter key, stencil, activation, sources
+    (-1: the padded input; None: no second source)."""
+    e = int(desc.extensive_layers)
+    ek = 3 if e > 0 else 1
+    L = [dict(name='encoder/c0', key='encoder/c0', k=ek, s=1, p=ek // 2, tr=False, act='lrelu', bn=None, src=(-1, None))]
+    for i in range(1, 8):
+        dn = i < e
+        L.append(dict(name='encoder/c%d' % i, key='encoder/c%d/c' % i, k=4 if dn else 1, s=2 if dn else 1, p=1 if dn else 0, tr=False, act='lrelu',
+                      bn='encoder/c%d/batchnorm/' % i, src=(i - 1, None)))
+    for j in range(7):
+        up = (7 - j) < e
+        L.append(dict(name='decoder/c%d' % j, key='decoder/c%d/c' % j, k=4 if up else 1, s=2 if up else 1, p=1 if up else 0, tr=up, act='relu',
+                      bn='decoder/c%d/batchnorm/' % j, src=(7, None) if j == 0 else (7 + j, 7 - j)))
+    L.append(dict(name='decoder/c7', key='decoder/c7', k=ek, s=1, p=ek // 2, tr=False, act=None, bn=None, src=(14, 0)))
+    return L
+
+
+def s2_rows_read(spec, a, b, Hi):
+    """Input rows [lo, hi) that output rows [a, b) of a layer read, from the operator's stencil: a convolution's output row o reads input rows
+    o s - p .. o s - p + k - 1; a k4 s2 p1 transposed convolution's input row i feeds output rows o = 2 i - 1 + k', k' = 0 .. 3, so output row o reads
+    the input rows i with 0 <= o + 1 - 2 i <= 3."""
+    if b <= a:
+        return 0, 0
+    if spec['tr']:
+        lo, hi = -((2 - a) // 2), b // 2 + 1                       # ceil((a - 2) / 2) .. floor(b / 2)
+    else:
+        lo, hi = a * spec['s'] - spec['p'], (b - 1) * spec['s'] - spec['p'] + spec['k']
+    return max(lo, 0), min(hi, Hi)
+
+
+def s2_needed_rows(specs, heights, k0, k1):
+    """Output rows [a, b) of every layer that the kept frames [k0, k1) of a window depend on: the last layer writes rows [k0, k1); walking the decoder chain
+    back, a layer's needed rows are what its consumer reads of it; the encoder (it feeds the bottom of the U-Net) and with it the skip sources are needed
+    whole.  heights[i] = output rows of layer i."""
+    need = [(0, heights[i]) for i in range(16)]
+    need[15] = (k0, k1)
+    for i in range(15, 8, -1):
+        Hi = heights[specs[i]['src'][0]]
+        need[i - 1] = s2_rows_read(specs[i], need[i][0], need[i][1], Hi)
+    return need
+
+
+def bf16_bits_to_f32(u):
+    return (numpy.asarray(u, numpy.uint16).astype(numpy.uint32) << 16).view(numpy.float32)
+
+
+def f32_to_bf16_bits(a):
+    return (numpy.ascontiguousarray(a, numpy.float32).view(numpy.uint32) >> 16).astype(numpy.uint16)
+
+
+def s2_value16(u):
+    """The value a consumer rebuilds from a 16-bit copy (Net.debug_activation kind 1): bf16, or hi + lo of the split form (B, H, W, 2, C) -> float64"""
+    f = bf16_bits_to_f32(u).astype(numpy.float64)
+    return f[..., 0, :] + f[..., 1, :] if u.ndim == 5 else f
+
+
+def s2_fetch(net, layer, kind):
+    """-> the buffer, or None when this plan has none (the library refuses with RY_EINVAL and says which copy is missing)"""
+    from realtime_yukarin_amd import _lib
+    try:
+        return net.debug_activation(layer, kind)
+    except _lib.Ry355Error as e:
+        assert any(w in str(e) for w in ('writes no', "caller's block", 'was not written', 'no padded input')), e
+        return None
+
+
+def s2_layer_params(P, spec, bf16):
+    W, b = P[spec['key'] + '/W'], P[spec['key'] + '/b']
+    bn = None if spec['bn'] is None else tuple(P[spec['bn'] + n] for n in ('gamma', 'beta', 'avg_mean', 'avg_var'))
+    return (bf16_round(W) if bf16 else W), b, bn
+
+
+def nan_rows(a):
+    """rows (axis 1) of a (B, H, ...) block that hold a NaN in any window"""
+    a = numpy.asarray(a)
+    return numpy.isnan(a.reshape(a.shape[0], a.shape[1], -1)).any(axis=(0, 2))
+
+
+def s2_reads_16bit(prof):
+    """{layer name: True} for the layers whose kernel reads the producers' 16-bit copies: the implicit GEMM instantiated with BF16 = true (the sixth
+    template argument of its name in Net.profile).  Which of the two 16-bit formats it reads is what the producer's copy says."""
+    return {q['layer'] for q in prof if q['name'].startswith('ry_igemm_ldsdma<') and q['name'][:-1].split(',')[5] == 'true'}
+
+
+def s2_walk(net, desc, P, n_frames, y, discard=(0, 0), prof=(), refs=True, cache=None, out=None, what=''):
+    """After y = net.convert(sp, discard) on a fresh, poisoned plan: every layer of the graph against float64 on the device's own sources.
+    refs: True = every layer; False = finiteness of the needed rows only (the caller checks the last layer).  cache: {layer: (sources, r, bound)} of an
+    earlier run of the same window and mode -- its reference is taken over for a layer whose sources are bit-equal on every row the needed rows read.
+    -> dict(layers=[per-layer report], need, bufs={layer: value array}, fused)"""
+    specs = s2_layers(desc)
+    B = y.shape[0]
+    k0 = discard[0] if discard[0] < n_frames else 0
+    k1 = n_frames - discard[1] if n_frames - discard[1] > k0 else n_frames
+    reads16 = s2_reads_16bit(prof)
+    x_in = s2_fetch(net, -1, 0)
+    assert x_in is not None
+    T = x_in.shape[1]
+    raw = {}
+    for i in range(16):
+        raw[i] = (s2_fetch(net, i, 0), s2_fetch(net, i, 1))
+    fused = raw[15][0] is None                                    # the 3x3 end layer wrote exp / edge bin / crop into the caller's block itself
+    heights = [(raw[i][0] if raw[i][0] is not None else raw[i][1]).shape[1] if i < 15 or not fused else T for i in range(16)]
+    assert heights[15] == T and heights[0] == T
+    need = s2_needed_rows(specs, heights, k0, k1)
+    if not fused:
+        need[15] = (0, n_frames)                                  # ry_sr_post reads every real row; the discard is cut by the host call
+        for i in range(15, 8, -1):
+            need[i - 1] = s2_rows_read(specs[i], need[i][0], need[i][1], heights[specs[i]['src'][0]])
+    rep = []
+    for i, spec in enumerate(specs):
+        o32, o16 = raw[i]
+        a, b = need[i]
+        is16 = spec['name'] in reads16
+        srcs, fmts = [], []
+        for sidx in spec['src']:
+            if sidx is None:
+                continue
+            if sidx < 0:
+                srcs.append(x_in[..., None].astype(numpy.float64)); fmts.append('f32'); continue
+            s32, s16 = raw[sidx]
+            if is16:
+                assert s16 is not None, (what, spec['name'], 'reads a 16-bit copy that layer %d does not write' % sidx)
+                srcs.append(s2_value16(s16)); fmts.append('x3' if s16.ndim == 5 else 'bf16')
+            else:
+                assert s32 is not None, (what, spec['name'], 'reads an fp32 copy that layer %d does not write' % sidx)
+                srcs.append(s32.astype(numpy.float64)); fmts.append('f32')
+        assert len(set(fmts)) == 1, (what, spec['name'], fmts)
+        fmt = fmts[0]
+        tol = dict(f32=F32_TOL, bf16=BF16_TOL, x3=X3_TOL)[fmt]
+        q = dict(layer=spec['name'], fmt=fmt, need=(a, b), worst=None, worst16=None, nan32=None, nan16=None, reused=False)
+        if i == 15 and fused:
+            rep.append(q)
+            continue
+        for kind, o in (('nan32', o32), ('nan16', o16)):
+            if o is None:
+                continue
+            nr = nan_rows(o if kind == 'nan32' else s2_value16(o))
+            q[kind] = int(nr.sum())
+            assert not nr[a:b].any(), (what, spec['name'], kind, 'needed rows %d .. %d hold NaN: rows %s' % (a, b - 1, numpy.nonzero(nr[a:b])[0][:8] + a))
+        if o32 is not None and o16 is not None:                   # the 16-bit copy is the rounding of its fp32 twin, bit for bit (NaN rows: both NaN)
+            ok = ~numpy.isnan(o32)
+            if o16.ndim == 5:
+                hi, lo = bf16_split(numpy.where(ok, o32, 0))
+                want = numpy.stack([f32_to_bf16_bits(hi), f32_to_bf16_bits(lo)], axis=3)
+                okk = ok[:, :, :, None, :]
+            else:
+                want = f32_to_bf16_bits(bf16_round(numpy.where(ok, o32, 0))); okk = ok
+            bad = (want != o16) & okk
+            assert not bad.any(), (what, spec['name'], '%d elements of the 16-bit copy are not the rounding of the fp32 copy' % int(bad.sum()))
+            assert numpy.isnan(s2_value16(o16))[~ok].all(), (what, spec['name'], 'the 16-bit copy holds values where the fp32 copy is NaN')
+        if not refs:
+            rep.append(q)
+            continue
+        Hi = srcs[0].shape[1]
+        ra, rb = s2_rows_read(spec, a, b, Hi)
+        hit = cache.get(i) if cache is not None else None
+        if hit is not None and len(hit[0]) == len(srcs) and all(numpy.array_equal(u[:, ra:rb], v[:, ra:rb]) for u, v in zip(hit[0], srcs)):
+            r, bound = hit[1], hit[2]; q['reused'] = True
+        else:
+            W, bb, bn = s2_layer_params(P, spec, fmt == 'bf16')
+            xs = numpy.concatenate(srcs, axis=3) if len(srcs) > 1 else srcs[0]
+            r, bound = ref_conv2d_f64(xs, W, bb, bn, spec['s'], spec['p'], spec['tr'], spec['act'])
+            if cache is not None:
+                cache[i] = (srcs, r, bound)
+        rr, bd = r[:, a:b], bound[:, a:b]
+        assert numpy.isfinite(rr).all(), (what, spec['name'], 'the reference of a needed row read a NaN source row')
+        if o32 is not None:
+            q['worst'] = assert_close_elementwise(o32[:, a:b], rr, bd, tol, '%s %s fp32' % (what, spec['name']))
+        else:
+            v = s2_value16(o16)[:, a:b]
+            if o16.ndim == 5:      # hi + lo rebuilds the fp32 value to 2^-17 of it (lo = bf16(v - hi), |v - hi| <= 2^-9 |v|, rounded to 8 bits again)
+                q['worst16'] = assert_close_elementwise(v, rr, bd + (2.0 ** -17 / tol) * numpy.abs(rr), tol, '%s %s split copy' % (what, spec['name']))
+            else:                  # rounding is monotone: the stored bf16 lies between the roundings of the two ends of the fp32 value's interval
+                lo_, hi_ = bf16_round((rr - tol * bd).astype(numpy.float32)), bf16_round((rr + tol * bd).astype(numpy.float32))
+                lo_ = numpy.minimum(lo_, bf16_round(numpy.nextafter((rr - tol * bd).astype(numpy.float32), numpy.float32(-numpy.inf))))   # (float64 -> float32 may round inwards)
+                hi_ = numpy.maximum(hi_, bf16_round(numpy.nextafter((rr + tol * bd).astype(numpy.float32), numpy.float32(numpy.inf))))
+                bad = ~((v >= lo_) & (v <= hi_))
+                assert not bad.any(), ('%s %s bf16 copy: %d elements outside bf16([r - tol bound, r + tol bound])' % (what, spec['name'], int(bad.sum())))
+                q['worst16'] = float((numpy.abs(v - rr) / numpy.maximum(bd, 1e-300)).max())
+        rep.append(q)
+    return dict(layers=rep, need=need, raw=raw, x_in=x_in, fused=fused, k=(k0, k1), specs=specs)
+
+
+def s2_check_end(walk, P, y, n_frames, E, what=''):
+    """The end of a convert against float64.  Fused end layer (ry_sr_last / ry_sr_last_gather): |log y - r| <= F32_TOL bound + E on the kept rows, r the 3x3
+    layer on the device's own fp32 sources, E the allowance of expf relative to its result.  Separate end (ry_conv_direct + ry_sr_post): the layer was held
+    like every other in s2_walk; here |log y - v| <= E on the device's own pre-activation v.  Both: the edge bin repeats the last one bit for bit.
+    -> worst |log y - r| / (F32_TOL bound + E)"""
+    k0, k1 = walk['k']
+    spec = walk['specs'][15]
+    Wd = y.shape[2] - 1
+    assert numpy.isfinite(y[:, k0:k1]).all() and (y[:, k0:k1] > 0).all(), (what, 'kept rows')
+    assert numpy.array_equal(y[:, k0:k1, -1], y[:, k0:k1, -2]), (what, "pad(mode='edge') repeats the last predicted bin")
+    ly = numpy.log(y[:, k0:k1, :Wd].astype(numpy.float64))
+    if walk['fused']:
+        srcs = [walk['raw'][sidx][0].astype(numpy.float64) for sidx in spec['src']]
+        W, b, _ = s2_layer_params(P, spec, False)
+        r, bound = ref_conv2d_f64(numpy.concatenate(srcs, axis=3), W, b, None, 1, spec['p'], False, None)
+        r, bound = r[:, k0:k1, :, 0], bound[:, k0:k1, :, 0]
+        bar = F32_TOL * bound + E
+    else:
+        r = walk['raw'][15][0][:, k0:k1, :, 0].astype(numpy.float64)
+        bar = numpy.full_like(r, E)
+    assert numpy.isfinite(r).all(), (what, 'the reference of a kept row read a NaN source row')
+    assert float(numpy.abs(r).max()) <= EXP_ARG_MAX, (what, 'outside the arguments the expf allowance was measured on')
+    ratio = numpy.abs(ly - r) / bar
+    i = numpy.unravel_index(int(numpy.argmax(ratio)), ratio.shape)
+    assert ratio[i] <= 1.0, ('%s: |log y - r| = %.3g > %.3g at (b, row, bin) = %s' % (what, abs(ly[i] - r[i]), bar[i], i))
+    return float(ratio[i])
+
+
+EXP_ARG_MAX = 40.0      # scripts/stage2_graph_tolerance.py measures expf on [-40, 40] and logf on exp([-40, 10])
+
+
+def s2_tolerances():
+    """(E, E_log): the allowances of the device's expf / logf relative to the result, read from profiles/r12/stage2_graph_tolerance.txt"""
+    from pathlib import Path
+    t = (Path(__file__).resolve().parent.parent / 'profiles' / 'r12' / 'stage2_graph_tolerance.txt').read_text().splitlines()
+    get = lambda key: float([l for l in t if l.startswith(key + ' =')][0].split()[-1])
+    return get('E'), get('E_log')
+
+
+def s2_check_pad(x_in, x, n_frames, take_log, E_log, what=''):
+    """The padded input of a convert (layer -1) against numpy.pad(mode='minimum') of the caller's block x (B, n, cols >= x_in's): the minimum is numpy's
+    on the float32 input; pad rows equal each other and the device's own value in the real row that holds the column's minimum, bit for bit (same
+    function, same argument); stage 1 (no log): the whole block is bit-equal to numpy.pad; stage 2: |x_in - log x| <= E_log |log x| on the real rows.
+    -> worst relative error of the log"""
+    B, T, C = x_in.shape
+    assert not numpy.isnan(x_in).any(), (what, 'NaN in the padded input')
+    xs = x[:, :, :C]
+    if not take_log:
+        assert numpy.array_equal(x_in, numpy.pad(xs, [(0, 0), (0, T - n_frames), (0, 0)], mode='minimum')), what
+        return 0.0
+    pad = x_in[:, n_frames:]
+    assert (pad.view(numpy.uint32) == pad[:, :1].view(numpy.uint32)).all(), (what, 'pad rows differ from each other')
+    amin = xs.argmin(axis=1)                                              # (B, C): the row of each column's minimum
+    at_min = numpy.take_along_axis(x_in[:, :n_frames], amin[:, None, :], axis=1)[:, 0]
+    assert numpy.array_equal(pad[:, 0].view(numpy.uint32), at_min.view(numpy.uint32)), (what, 'pad rows are not the log of the column minimum')
+    r = numpy.log(xs.astype(numpy.float64))
+    assert float(r.min()) >= -EXP_ARG_MAX and float(r.max()) <= 10.0
+    err = numpy.abs(x_in[:, :n_frames] - r) / numpy.maximum(numpy.abs(r), 1e-300)
+    assert float(err.max()) <= E_log, (what, float(err.max()), E_log)
+    return float(err.max())

@@ -12,8 +12,8 @@ from conftest import rel_max
 import cases
 
 F32_TOL = cases.F32_TOL  # fp32 paths: any summation order of the same products
-X3_TOL = 3e-5           # split-bf16 against the fp32-operand reference (the dropped lo * lo term and the 16-bit split)
-BF16_TOL = 1e-5         # plain bf16 against the reference on bf16-rounded operands
+X3_TOL = cases.X3_TOL   # split-bf16 against the fp32-operand reference (the dropped lo * lo term and the 16-bit split)
+BF16_TOL = cases.BF16_TOL  # plain bf16 against the reference on bf16-rounded operands
 BF16_F32_TOL = 1e-2     # ... and against the fp32-operand reference (two operands rounded to 8 bits)
 
 
