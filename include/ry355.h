@@ -272,6 +272,24 @@ void ry_crepe_destroy(ry_crepe* crepe);
  * 0: the argmax of each frame.  on_device = 1: every pointer is a device pointer, the call only enqueues on the context stream. */
 int ry_crepe_predict(ry_crepe* crepe, const float* audio16k, int n_samples, int hop, int center, int viterbi,
                      float* f0, float* confidence, float* activation, int on_device);
+/* Audio at another rate.  The resampler is resampy's 'kaiser_best' interpolation, one device thread per 16 kHz sample, float64 sums in the
+ * order of realtime_yukarin_amd.crepe.resample: the float32 result has that function's bits.  Two tables per input rate come from the caller:
+ * win [n_win], the half filter (Kaiser window x sinc, num_table entries per zero crossing, scaled by 16000 / sr when sr > 16000; the
+ * interpolation slope is taken as win[j + 1] - win[j]), walked in steps of `step` = int(min(1, 16000 / sr) * num_table) entries; and
+ * time_register [n_times], the input time of every output: 0, then the running float64 sum of sr / 16000 (summed one by one: any other
+ * order rounds differently).  The first call for a rate needs both; a later call may pass win = NULL and a longer time register only.
+ * Several rates may be installed on one handle.  Refused: sr < 1, a time register that is negative, decreasing or not finite. */
+int ry_crepe_set_resampler(ry_crepe* crepe, int sr, const double* win, int n_win, int num_table, int step,
+                           const double* time_register, int n_times);
+/* The resampler alone: n_samples at sr -> int(n_samples * (16000.0 / sr)) samples at 16 kHz in out16k (on_device = 1: both are device
+ * pointers, the call only enqueues).  Refused before anything is launched: no tables for sr, a time register shorter than the output,
+ * an empty output. */
+int ry_crepe_resample(ry_crepe* crepe, const float* audio, int n_samples, int sr, float* out16k, int on_device);
+/* ry_crepe_predict on audio at sr: resampled on the context stream into the handle's 16 kHz buffer, then exactly what ry_crepe_predict
+ * runs on it (frames are counted on the resampled length).  sr = 16000 is ry_crepe_predict itself.  Refusals: those of
+ * ry_crepe_resample and of ry_crepe_predict (center = 0 with fewer than 1024 resampled samples). */
+int ry_crepe_predict_sr(ry_crepe* crepe, const float* audio, int n_samples, int sr, int hop, int center, int viterbi,
+                        float* f0, float* confidence, float* activation, int on_device);
 /* The decode alone on a host activation [n_frames][360]: f0, confidence and (may be null) the centre bin of every frame -- the Viterbi
  * path, or with viterbi = 0 the argmax. */
 int ry_crepe_decode(ry_crepe* crepe, const float* activation, int n_frames, int viterbi, float* f0, float* confidence, int* path);
@@ -285,7 +303,7 @@ int ry_crepe_set_viterbi_tables(ry_crepe* crepe, const double* logT, const doubl
 int ry_crepe_debug_layer(ry_crepe* crepe, int layer, int n_frames, float* out);
 /* tests: fills every element the next ry_crepe_predict / ry_crepe_decode must write with NaN bit patterns (all bits set; -1 as an index) --
  * the samples of the frame rows, the interior rows of every layer's input, logits, split-K slabs, activation, confidence, f0, observations,
- * back-pointers and path -- and leaves the zero padding rows as they are: a later call that reads anything it did not write shows it. */
+ * back-pointers, path and the 16 kHz audio buffer (the resampler's output) -- and leaves the zero padding rows as they are: a later call that reads anything it did not write shows it. */
 int ry_crepe_debug_poison(ry_crepe* crepe);
 /* diagnostics: the split-K count of conv1 .. conv6 and the dense layer (7 ints). */
 int ry_crepe_debug_splits(ry_crepe* crepe, int* splits);

@@ -1,8 +1,9 @@
 """`crepe` on the MI355X: the functions of the crepe package (and its PyTorch fork) that the reference calls --
 `predict(audio, sr, viterbi, model_capacity, center, step_size, verbose)` and `predict_voicing(confidence)`
 (realtime-yukarin: realtime_voice_conversion/yukarin_wrapper/acoustic_feature_wrapper.py:65-80) -- plus `get_activation` and
-`load_model`.  The network, the decode and the Viterbi pass run in libry355 (`ry_crepe_*`); resampling to 16 kHz and
-`predict_voicing` run on the host.
+`load_model`.  Resampling to 16 kHz, the network, the decode and the Viterbi pass run in libry355 (`ry_crepe_*`); the mono average,
+the float32 cast and `predict_voicing` run on the host.  RY_CREPE_RESAMPLE=host resamples with the host statement of the same
+arithmetic instead (`realtime_yukarin_amd.crepe.resample`: the same bits, far slower); a rate that is not a whole number of Hz always does.
 
 Weights: `load_model(path, capacity)` or the file named by RY_CREPE_MODEL (`.npz` or torch state dict, keys in INTEGRATION.md
 section 9).  Without either, every call raises: there are no built-in or random weights."""
@@ -46,19 +47,26 @@ def _model(model_capacity):
     return _models[m]
 
 
-def _audio16k(audio, sr):
+def _mono(audio):
     audio = numpy.asarray(audio)
     if audio.ndim == 2:
         audio = audio.mean(1)                                   # make mono
-    audio = audio.astype(numpy.float32)
-    if sr != model_srate:
-        audio = _crepe.resample(audio, sr, model_srate)
-    return audio
+    return audio.astype(numpy.float32)
+
+
+def _resample_on_host(sr):
+    mode = os.environ.get('RY_CREPE_RESAMPLE', 'device')
+    if mode not in ('device', 'host'):
+        raise RuntimeError('crepe: RY_CREPE_RESAMPLE=%s (device or host)' % mode)
+    return mode == 'host' or int(sr) != sr
 
 
 def _run(audio, sr, model_capacity, center, step_size, viterbi):
     model = _model(model_capacity)
-    return model.predict16k(_audio16k(audio, sr), _crepe.hop_length(step_size), center=center, viterbi=viterbi)
+    audio, hop = _mono(audio), _crepe.hop_length(step_size)
+    if sr != model_srate and _resample_on_host(sr):
+        audio, sr = _crepe.resample(audio, sr, model_srate), model_srate
+    return model.predict(audio, sr, hop, center=center, viterbi=viterbi)
 
 
 def get_activation(audio, sr, model_capacity='full', center=True, step_size=10, verbose=1):

@@ -1,5 +1,6 @@
 """CREPE pitch tracker on the MI355X: network spec, weights (seeded synthetic, or a `.npz` / torch state-dict file), the host-side
-pieces (resampling to 16 kHz, the HMM tables, `predict_voicing`) and `CrepeModel`, the handle over `ry_crepe_*` (include/ry355.h).
+pieces (the resampler's tables and its host statement, the HMM tables, `predict_voicing`) and `CrepeModel`, the handle over `ry_crepe_*`
+(include/ry355.h), which resamples to 16 kHz, runs the network and decodes on the device.
 
 The reference turns CREPE on with `extract_f0_mode: crepe` (realtime-yukarin: realtime_voice_conversion/config.py:8-10); its
 CrepeAcousticFeatureWrapper.extract_f0 calls `crepe.predict(x, fs, viterbi=True, model_capacity='full', step_size=frame_period)` and
@@ -215,6 +216,34 @@ def resample(x, sr_orig: int, sr_new: int = MODEL_SRATE) -> numpy.ndarray:
     return y.astype(numpy.float32)
 
 
+def _rate(sr) -> int:
+    if int(sr) != sr or int(sr) < 1:
+        raise ValueError('the device resampler takes a whole, positive sample rate in Hz, got %r' % (sr,))
+    return int(sr)
+
+
+def resampled_length(n_samples: int, sr) -> int:
+    """Samples at 16 kHz of n_samples at sr, in the form `resample` computes it."""
+    return int(int(n_samples) * (float(MODEL_SRATE) / sr))
+
+
+def resampler_tables(sr):
+    """(win, num_table, step) of `resample(x, sr)`: the half filter (scaled by the ratio when down-sampling), its entries per zero
+    crossing and per input sample.  `ry_crepe_set_resampler` takes them as they are."""
+    ratio = float(MODEL_SRATE) / sr
+    win, num_table = _kaiser_best_window()
+    if ratio < 1:
+        win = win * ratio
+    return numpy.ascontiguousarray(win, dtype=numpy.float64), num_table, int(min(1.0, ratio) * num_table)
+
+
+def time_register(sr, n_out: int) -> numpy.ndarray:
+    """The input time of outputs 0 .. n_out - 1 of `resample(x, sr)`: resampy's `time_register += 1 / ratio`, summed one by one in
+    float64 (the expression `resample` uses; a shorter register is a prefix of a longer one)."""
+    ratio = float(MODEL_SRATE) / sr
+    return numpy.concatenate([[0.0], numpy.cumsum(numpy.full(int(n_out) - 1, 1.0 / ratio))])
+
+
 def predict_voicing(confidence) -> numpy.ndarray:
     """Voiced (1) / unvoiced (0) per frame: Viterbi path of a two-state Gaussian HMM over the confidence, float64, lowest state on ties
     (the fork's `predict_voicing` with fixed constants, [MEM])."""
@@ -257,9 +286,11 @@ class CrepeModel(object):
         self._given_ctx = ctx
         self._handle = None
         self._pid = None
+        self._rs = {}                      # input rate -> entries of the time register the handle holds
 
     def __getstate__(self):
         d = dict(self.__dict__)
+        d['_rs'] = {}
         d['_handle'] = None
         d['_pid'] = None
         d['_ctx'] = None
@@ -275,6 +306,7 @@ class CrepeModel(object):
             h = ctypes.c_void_p()
             lib.check(lib.dll.ry_crepe_create(self._ctx.handle, self.m, _lib._fptr(self.blob), self.blob.size, self.bn_eps, ctypes.byref(h)))
             self._handle, self._pid = h, os.getpid()
+            self._rs = {}
             dp = ctypes.POINTER(ctypes.c_double)
             tabs = [numpy.ascontiguousarray(t, dtype=numpy.float64) for t in viterbi_tables()]
             lib.check(lib.dll.ry_crepe_set_viterbi_tables(self._handle, *[t.ctypes.data_as(dp) for t in tabs]))
@@ -292,6 +324,59 @@ class CrepeModel(object):
         act = numpy.empty((n, BINS), numpy.float32) if activation else None
         lib.check(lib.dll.ry_crepe_predict(h, _lib._fptr(x), x.size, int(hop), int(bool(center)), int(bool(viterbi)),
                                            _lib._fptr(f0), _lib._fptr(conf), _lib._fptr(act), 0))
+        return f0, conf, act
+
+    def _resampler(self, sr: int, n_out: int) -> None:
+        """The tables of rate sr on the handle, with a time register of at least n_out entries: built on first use, the register
+        grown geometrically (its values depend on the rate and the index only)."""
+        lib, h = self._get()
+        have = self._rs.get(sr, 0)
+        if n_out <= have:
+            return
+        dp = ctypes.POINTER(ctypes.c_double)
+        n = max(n_out, 2 * have)
+        tr = numpy.ascontiguousarray(time_register(sr, n), dtype=numpy.float64)
+        if have:
+            lib.check(lib.dll.ry_crepe_set_resampler(h, sr, None, 0, 0, 0, tr.ctypes.data_as(dp), n))
+        else:
+            win, num_table, step = resampler_tables(sr)
+            lib.check(lib.dll.ry_crepe_set_resampler(h, sr, win.ctypes.data_as(dp), win.size, num_table, step, tr.ctypes.data_as(dp), n))
+        self._rs[sr] = n
+
+    def resample(self, audio, sr) -> numpy.ndarray:
+        """audio: float32 samples at sr -> float32 samples at 16 kHz, the bits of `resample(audio, sr)` (`ry_crepe_resample`)."""
+        lib, h = self._get()
+        sr = _rate(sr)
+        x = numpy.ascontiguousarray(audio, dtype=numpy.float32).ravel()
+        if sr == MODEL_SRATE:
+            return x.copy()
+        n_out = resampled_length(x.size, sr)
+        if n_out < 1:
+            raise ValueError('%d samples at %d Hz give no sample at 16 kHz' % (x.size, sr))
+        self._resampler(sr, n_out)
+        y = numpy.empty(n_out, numpy.float32)
+        lib.check(lib.dll.ry_crepe_resample(h, _lib._fptr(x), x.size, sr, _lib._fptr(y), 0))
+        return y
+
+    def predict(self, audio, sr, hop: int, center: bool = True, viterbi: bool = True, activation: bool = True):
+        """audio: float32 samples at sr, resampled to 16 kHz on the device -> what `predict16k` returns for the resampled signal
+        (`ry_crepe_predict_sr`); hop is in samples at 16 kHz."""
+        sr = _rate(sr)
+        if sr == MODEL_SRATE:
+            return self.predict16k(audio, hop, center, viterbi, activation)
+        lib, h = self._get()
+        x = numpy.ascontiguousarray(audio, dtype=numpy.float32).ravel()
+        n_out = resampled_length(x.size, sr)
+        n = n_frames(n_out, hop, center) if n_out >= 1 else 0
+        if n < 1:
+            raise ValueError('CREPE needs at least %d samples at 16 kHz (center=False) or one sample, %d samples at %d Hz give %d'
+                             % (FRAME if not center else 1, x.size, sr, n_out))
+        self._resampler(sr, n_out)
+        f0 = numpy.empty(n, numpy.float32)
+        conf = numpy.empty(n, numpy.float32)
+        act = numpy.empty((n, BINS), numpy.float32) if activation else None
+        lib.check(lib.dll.ry_crepe_predict_sr(h, _lib._fptr(x), x.size, sr, int(hop), int(bool(center)), int(bool(viterbi)),
+                                              _lib._fptr(f0), _lib._fptr(conf), _lib._fptr(act), 0))
         return f0, conf, act
 
     def decode(self, activation, viterbi: bool = True):
@@ -317,7 +402,8 @@ class CrepeModel(object):
         return out
 
     def poison(self) -> None:
-        """Tests: NaN bit patterns in everything the next `predict16k` / `decode` must write (`ry_crepe_debug_poison`)."""
+        """Tests: NaN bit patterns in everything the next `resample` / `predict` / `predict16k` / `decode` must write
+        (`ry_crepe_debug_poison`)."""
         lib, h = self._get()
         lib.check(lib.dll.ry_crepe_debug_poison(h))
 

@@ -2,6 +2,8 @@
 // CrepeAcousticFeatureWrapper.extract_f0): framing -> conv1 .. conv6 (conv -> ReLU -> BN -> max-pool 2, one implicit-GEMM kernel each,
 // split-K where the grid is short) -> dense + sigmoid -> argmax / Viterbi / local-average cents.  Kernels: crepe_kernels.h.
 // The frames of a call run in passes of at most CHUNK frames; the activation of every frame is kept for the decode, which runs once.
+// Audio at another rate is resampled to 16 kHz on the device first (crepe_resample; the filter and the time register of each rate are
+// tables the caller installs, ry_crepe_set_resampler).
 #include "crepe_kernels.h"
 #include "ry_host.h"
 
@@ -36,6 +38,14 @@ size_t param_count(int m) {
     }
     return n + (size_t)CREPE_BINS * 4 * cin + CREPE_BINS;
 }
+
+// the resampler tables of one input rate (ry_crepe_set_resampler)
+struct Resampler {
+    double* win = nullptr;                          // half filter [n_win]
+    double* tr = nullptr;                           // time register [n_times]
+    int n_win = 0, num_table = 0, step = 0, n_times = 0;
+    std::vector<double> tr_host;                    // the same on the host: the input sample each output starts from is checked before a launch
+};
 }  // namespace
 
 struct ry_crepe {
@@ -57,6 +67,11 @@ struct ry_crepe {
     int cap_frames = 0, cap_samples = 0;
     float *audio = nullptr, *act = nullptr, *conf = nullptr, *f0 = nullptr;
     int *obs = nullptr, *bp = nullptr, *path = nullptr;
+    // resampling: tables per input rate, the uploaded input at that rate (the 16 kHz result goes to `audio`)
+    Arena rs_tables, rs_in;
+    std::map<int, Resampler> rs;
+    float* audio_sr = nullptr;
+    int cap_sr = 0;
 };
 
 namespace {
@@ -161,6 +176,88 @@ int upload_doubles(Arena& a, ry_ctx* ctx, const double* h, size_t n, double** d)
     RT_TRY(rt::h2d(q, h, n * sizeof(double), ctx->stream));
     RT_TRY(rt::stream_sync(ctx->stream));
     *d = (double*)q;
+    return RY_OK;
+}
+
+// frames of n_samples at 16 kHz; refuses what ry_crepe_predict refuses
+int frame_count(int n_samples, int hop, int center, int* nf) {
+    if (!center && n_samples < CREPE_FRAME) return fail(RY_EINVAL, "center = 0 needs at least %d samples, got %d", CREPE_FRAME, n_samples);
+    const long long nfl = 1 + ((long long)n_samples + (center ? CREPE_FRAME : 0) - CREPE_FRAME) / hop;
+    if (nfl > (1LL << 24)) return fail(RY_EINVAL, "%lld frames", nfl);
+    *nf = (int)nfl;
+    return RY_OK;
+}
+
+// the network and the decode on n_samples at 16 kHz in device memory, results to the caller (ensure_chunk / ensure_call have run)
+int run_network(ry_crepe* c, const float* d_audio, int n_samples, int hop, int center, int viterbi, int nf,
+                float* f0, float* confidence, float* activation, int on_device) {
+    const ry_stream_t s = c->ctx->stream;
+    float* act_all = c->act;
+    for (int f = 0; f < nf; f += CHUNK) {
+        const int n = std::min(CHUNK, nf - f);
+        CrepeFrameParams fp;
+        fp.audio = d_audio; fp.n = n_samples; fp.hop = hop; fp.center = center; fp.frame0 = f; fp.n_frames = n; fp.out = c->act_in[0];
+        RY_LAUNCH(crepe_frames, dim3((unsigned)n), 256, s, fp);
+        RT_TRY(rt::last_error());
+        c->act = act_all + (size_t)f * CREPE_BINS;                 // the dense layer writes this pass's rows
+        int rc = RY_OK;
+        for (int i = 0; i <= NCONV && rc == RY_OK; ++i) rc = launch_layer(c, i, n);
+        c->act = act_all;
+        RY_TRY(rc);
+        c->last_chunk = n;
+    }
+    RY_TRY(launch_decode(c, act_all, nf, viterbi));
+    if (on_device) {
+        RT_TRY(rt::d2d(f0, c->f0, (size_t)nf * sizeof(float), s));
+        RT_TRY(rt::d2d(confidence, c->conf, (size_t)nf * sizeof(float), s));
+        if (activation) RT_TRY(rt::d2d(activation, act_all, (size_t)nf * CREPE_BINS * sizeof(float), s));
+        return RY_OK;
+    }
+    RT_TRY(rt::d2h(f0, c->f0, (size_t)nf * sizeof(float), s));
+    RT_TRY(rt::d2h(confidence, c->conf, (size_t)nf * sizeof(float), s));
+    if (activation) RT_TRY(rt::d2h(activation, act_all, (size_t)nf * CREPE_BINS * sizeof(float), s));
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+// n_out = int(n_in * (16000.0 / sr)) and the tables of the rate; refuses before anything is launched
+int resample_plan(ry_crepe* c, int n_samples, int sr, const Resampler** r, int* n_out) {
+    if (sr < 1) return fail(RY_EINVAL, "sample rate %d", sr);
+    if (n_samples < 1) return fail(RY_EINVAL, "%d samples", n_samples);
+    const auto it = c->rs.find(sr);
+    if (it == c->rs.end()) return fail(RY_ESTATE, "no resampler tables for %d Hz (ry_crepe_set_resampler)", sr);
+    const double ratio = 16000.0 / sr;
+    const double nd = (double)n_samples * ratio;
+    if (!(nd < 2147483648.0)) return fail(RY_EINVAL, "%d samples at %d Hz are too many at 16 kHz", n_samples, sr);
+    const int n = (int)nd;
+    if (n < 1) return fail(RY_EINVAL, "%d samples at %d Hz give no sample at 16 kHz", n_samples, sr);
+    if (n > it->second.n_times) return fail(RY_ESTATE, "the time table for %d Hz holds %d outputs, the call needs %d", sr, it->second.n_times, n);
+    // the register never decreases (checked when it was installed): every output starts inside the signal when the last one does
+    if ((long long)it->second.tr_host[(size_t)n - 1] >= n_samples)
+        return fail(RY_EINVAL, "the time table for %d Hz puts output %d at input sample %lld of %d", sr, n - 1, (long long)it->second.tr_host[(size_t)n - 1], n_samples);
+    *r = &it->second;
+    *n_out = n;
+    return RY_OK;
+}
+
+int ensure_sr(ry_crepe* c, int n_samples) {
+    if (n_samples <= c->cap_sr) return RY_OK;
+    RT_TRY(rt::stream_sync(c->ctx->stream));
+    c->rs_in.release();
+    c->cap_sr = 0;
+    RY_TRY(c->rs_in.alloc(&c->audio_sr, (size_t)n_samples));
+    c->cap_sr = n_samples;
+    return RY_OK;
+}
+
+int launch_resample(ry_crepe* c, const Resampler& r, const float* d_in, int n_in, int sr, float* d_out, int n_out) {
+    CrepeResampleParams p;
+    p.x = d_in; p.n_in = n_in; p.win = r.win; p.n_win = r.n_win; p.tr = r.tr;
+    const double ratio = 16000.0 / sr;
+    p.scale = ratio < 1.0 ? ratio : 1.0;
+    p.num_table = r.num_table; p.step = r.step; p.y = d_out; p.n_out = n_out;
+    RY_LAUNCH(crepe_resample, dim3((unsigned)((n_out + 255) / 256)), 256, c->ctx->stream, p);
+    RT_TRY(rt::last_error());
     return RY_OK;
 }
 }  // namespace
@@ -270,10 +367,8 @@ int ry_crepe_predict(ry_crepe* c, const float* audio, int n_samples, int hop, in
                      float* f0, float* confidence, float* activation, int on_device) {
     if (!c) return fail(RY_ESTATE, "null crepe handle");
     if (!audio || !f0 || !confidence || n_samples < 1 || hop < 1) return fail(RY_EINVAL, "bad argument");
-    if (!center && n_samples < CREPE_FRAME) return fail(RY_EINVAL, "center = 0 needs at least %d samples, got %d", CREPE_FRAME, n_samples);
-    const long long nfl = 1 + ((long long)n_samples + (center ? CREPE_FRAME : 0) - CREPE_FRAME) / hop;
-    if (nfl > (1LL << 24)) return fail(RY_EINVAL, "%lld frames", nfl);
-    const int nf = (int)nfl;
+    int nf = 0;
+    RY_TRY(frame_count(n_samples, hop, center, &nf));
     ry_ctx* ctx = c->ctx;
     const ry_stream_t s = ctx->stream;
     RT_TRY(rt::set_device(ctx->device));
@@ -284,32 +379,76 @@ int ry_crepe_predict(ry_crepe* c, const float* audio, int n_samples, int hop, in
         RT_TRY(rt::h2d(c->audio, audio, (size_t)n_samples * sizeof(float), s));
         d_audio = c->audio;
     }
-    float* act_all = c->act;
-    for (int f = 0; f < nf; f += CHUNK) {
-        const int n = std::min(CHUNK, nf - f);
-        CrepeFrameParams fp;
-        fp.audio = d_audio; fp.n = n_samples; fp.hop = hop; fp.center = center; fp.frame0 = f; fp.n_frames = n; fp.out = c->act_in[0];
-        RY_LAUNCH(crepe_frames, dim3((unsigned)n), 256, s, fp);
-        RT_TRY(rt::last_error());
-        c->act = act_all + (size_t)f * CREPE_BINS;                 // the dense layer writes this pass's rows
-        int rc = RY_OK;
-        for (int i = 0; i <= NCONV && rc == RY_OK; ++i) rc = launch_layer(c, i, n);
-        c->act = act_all;
-        RY_TRY(rc);
-        c->last_chunk = n;
+    return run_network(c, d_audio, n_samples, hop, center, viterbi, nf, f0, confidence, activation, on_device);
+}
+
+int ry_crepe_set_resampler(ry_crepe* c, int sr, const double* win, int n_win, int num_table, int step, const double* time_register, int n_times) {
+    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    if (sr < 1 || !time_register || n_times < 1) return fail(RY_EINVAL, "bad argument");
+    const bool known = c->rs.count(sr) != 0;
+    if (!win && !known) return fail(RY_EINVAL, "the first call for %d Hz needs the filter table", sr);
+    if (win && (n_win < 2 || num_table < 1 || step < 1)) return fail(RY_EINVAL, "filter table: %d entries, %d per zero crossing, step %d", n_win, num_table, step);
+    if (!(time_register[0] >= 0.0)) return fail(RY_EINVAL, "the time register starts at %g", time_register[0]);
+    for (int i = 1; i < n_times; ++i)
+        if (!(time_register[i] >= time_register[i - 1]) || !(time_register[i] < 2147483648.0))
+            return fail(RY_EINVAL, "the time register is not a non-decreasing sequence of sample times at entry %d", i);
+    RT_TRY(rt::set_device(c->ctx->device));
+    RT_TRY(rt::stream_sync(c->ctx->stream));                   // the tables may be in use by a call still in flight
+    Resampler r = known ? c->rs[sr] : Resampler();
+    if (win) {
+        double* d = nullptr;
+        RY_TRY(upload_doubles(c->rs_tables, c->ctx, win, (size_t)n_win, &d));
+        if (r.win) c->rs_tables.free_one(r.win);
+        r.win = d; r.n_win = n_win; r.num_table = num_table; r.step = step;
     }
-    RY_TRY(launch_decode(c, act_all, nf, viterbi));
-    if (on_device) {
-        RT_TRY(rt::d2d(f0, c->f0, (size_t)nf * sizeof(float), s));
-        RT_TRY(rt::d2d(confidence, c->conf, (size_t)nf * sizeof(float), s));
-        if (activation) RT_TRY(rt::d2d(activation, act_all, (size_t)nf * CREPE_BINS * sizeof(float), s));
-        return RY_OK;
-    }
-    RT_TRY(rt::d2h(f0, c->f0, (size_t)nf * sizeof(float), s));
-    RT_TRY(rt::d2h(confidence, c->conf, (size_t)nf * sizeof(float), s));
-    if (activation) RT_TRY(rt::d2h(activation, act_all, (size_t)nf * CREPE_BINS * sizeof(float), s));
+    double* d = nullptr;
+    RY_TRY(upload_doubles(c->rs_tables, c->ctx, time_register, (size_t)n_times, &d));
+    if (r.tr) c->rs_tables.free_one(r.tr);
+    r.tr = d; r.n_times = n_times;
+    r.tr_host.assign(time_register, time_register + n_times);
+    c->rs[sr] = std::move(r);
+    return RY_OK;
+}
+
+int ry_crepe_resample(ry_crepe* c, const float* audio, int n_samples, int sr, float* out16k, int on_device) {
+    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    if (!audio || !out16k) return fail(RY_EINVAL, "bad argument");
+    const Resampler* r = nullptr;
+    int n_out = 0;
+    RY_TRY(resample_plan(c, n_samples, sr, &r, &n_out));
+    const ry_stream_t s = c->ctx->stream;
+    RT_TRY(rt::set_device(c->ctx->device));
+    if (on_device) return launch_resample(c, *r, audio, n_samples, sr, out16k, n_out);
+    RY_TRY(ensure_call(c, 1, n_out));
+    RY_TRY(ensure_sr(c, n_samples));
+    RT_TRY(rt::h2d(c->audio_sr, audio, (size_t)n_samples * sizeof(float), s));
+    RY_TRY(launch_resample(c, *r, c->audio_sr, n_samples, sr, c->audio, n_out));
+    RT_TRY(rt::d2h(out16k, c->audio, (size_t)n_out * sizeof(float), s));
     RT_TRY(rt::stream_sync(s));
     return RY_OK;
+}
+
+int ry_crepe_predict_sr(ry_crepe* c, const float* audio, int n_samples, int sr, int hop, int center, int viterbi,
+                        float* f0, float* confidence, float* activation, int on_device) {
+    if (sr == 16000) return ry_crepe_predict(c, audio, n_samples, hop, center, viterbi, f0, confidence, activation, on_device);
+    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    if (!audio || !f0 || !confidence || hop < 1) return fail(RY_EINVAL, "bad argument");
+    const Resampler* r = nullptr;
+    int n_out = 0, nf = 0;
+    RY_TRY(resample_plan(c, n_samples, sr, &r, &n_out));
+    RY_TRY(frame_count(n_out, hop, center, &nf));
+    const ry_stream_t s = c->ctx->stream;
+    RT_TRY(rt::set_device(c->ctx->device));
+    RY_TRY(ensure_chunk(c, std::min(nf, CHUNK)));
+    RY_TRY(ensure_call(c, nf, n_out));
+    const float* d_in = audio;
+    if (!on_device) {
+        RY_TRY(ensure_sr(c, n_samples));
+        RT_TRY(rt::h2d(c->audio_sr, audio, (size_t)n_samples * sizeof(float), s));
+        d_in = c->audio_sr;
+    }
+    RY_TRY(launch_resample(c, *r, d_in, n_samples, sr, c->audio, n_out));
+    return run_network(c, c->audio, n_out, hop, center, viterbi, nf, f0, confidence, activation, on_device);
 }
 
 int ry_crepe_decode(ry_crepe* c, const float* activation, int n_frames, int viterbi, float* f0, float* confidence, int* path) {
@@ -371,6 +510,7 @@ int ry_crepe_debug_poison(ry_crepe* c) {
         RT_TRY(rt::dmemset(c->logits, 0xff, (size_t)c->cap_chunk * CREPE_BINS * sizeof(float), s));
         RT_TRY(rt::dmemset(c->slabs, 0xff, c->slab_floats * sizeof(float), s));
     }
+    if (c->cap_samples > 0) RT_TRY(rt::dmemset(c->audio, 0xff, (size_t)c->cap_samples * sizeof(float), s));   // the resampler's output
     if (c->cap_frames > 0) {
         const size_t F = (size_t)c->cap_frames;
         RT_TRY(rt::dmemset(c->act, 0xff, F * CREPE_BINS * sizeof(float), s));

@@ -61,6 +61,54 @@ RY_KERNEL(256) void crepe_frames(CrepeFrameParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Resampling to 16 kHz: band-limited interpolation with resampy's 'kaiser_best' table ([MEM]), the statement of crepe.resample
+// (realtime_yukarin_amd/crepe.py) per output sample.  Output t sits at time tr[t] of the input (the sequentially summed time register,
+// a table per rate built on the host: a parallel sum would round differently), n = int(tr[t]).  Side 0 walks the taps x[n], x[n - 1], ..
+// and side 1 the taps x[n + 1], x[n + 2], .., each through the half filter `win` in steps of `step` entries from its own fractional
+// offset, linearly interpolated with delta[j] = win[j + 1] - win[j] (0 behind the last entry).  One thread per output adds the terms
+// (win[j] + eta * delta[j]) * x[src] in that order in float64, every operation rounded on its own (no fma): the float32 result has the
+// bits of the host function.  The tap counts are cut by the table's end and by both ends of the signal, so no index leaves win or x
+// as long as 0 <= n < n_in, which the host checks on its copy of the table before it launches (crepe.cpp: resample_plan).
+// ---------------------------------------------------------------------------------------------
+struct CrepeResampleParams {
+    const float* x; int n_in;          // input at the caller's rate
+    const double* win; int n_win;      // half filter, scaled by the ratio when down-sampling
+    const double* tr;                  // time register [n_out]
+    double scale;                      // min(1, ratio)
+    int num_table, step;               // table entries per zero crossing; entries per input sample = int(scale * num_table)
+    float* y; int n_out;
+};
+
+RY_KERNEL(256) void crepe_resample(CrepeResampleParams p) {
+#pragma clang fp contract(off)
+    const int t = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (t >= p.n_out) return;
+    const double tr = p.tr[t];
+    const int n = (int)tr;                                         // 0 <= tr < 2^31 (ry_crepe_set_resampler)
+    const double frac0 = p.scale * (tr - (double)n);
+    double acc = 0.0;
+    for (int side = 0; side < 2; ++side) {
+        const double frac = side ? p.scale - frac0 : frac0;
+        const double index_frac = frac * (double)p.num_table;
+        const int offset = (int)index_frac;                        // 0 .. num_table
+        const double eta = index_frac - (double)offset;
+        const int lim = (p.n_win - offset) / p.step;
+        const int room = side ? p.n_in - n - 1 : n + 1;
+        const int cap = room < lim ? room : lim;
+        const float* xs = p.x + (side ? n + 1 : n);
+        const double* w = p.win + offset;
+        const int dir = side ? 1 : -1;
+        for (int i = 0; i < cap; ++i) {
+            const int j = i * p.step;                              // offset + j < n_win <= 2^31 - 1 by the cut at lim
+            const double w0 = w[j];
+            const double d = offset + j + 1 < p.n_win ? w[j + 1] - w0 : 0.0;
+            acc += (w0 + eta * d) * (double)xs[dir * i];
+        }
+    }
+    p.y[t] = (float)acc;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Implicit GEMM: D[m][n] = sum_k A[m][k] W[n][k], tile 128 x 128 x 32, four waves of 64 x 64 (2 x 2 blocks of 32 x 32), one
 // v_mfma_f32_32x32x2_f32 per block and K step.  Both operands sit k-contiguous in the LDS ([row][32 + 4]); K step s of a chunk gives
 // lane half h the index k = 16 h + s (A and B agree, so the sum is the same), which lets every lane fetch four steps with one 16-byte
