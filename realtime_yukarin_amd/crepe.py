@@ -9,13 +9,13 @@ CrepeAcousticFeatureWrapper.extract_f0 calls `crepe.predict(x, fs, viterbi=True,
 trained weights, crepe, resampy or hmmlearn exist to pin it against.
 """
 import ctypes
-import os
 from pathlib import Path
 from typing import Dict, List, Optional, Tuple
 
 import numpy
 
 from . import _lib
+from ._handle import DeviceHandle, _dptr
 
 # ---- the network ([MEM], one place) --------------------------------------------------------------------------------------------
 CAPACITIES = {'tiny': 4, 'small': 8, 'medium': 16, 'large': 24, 'full': 32}
@@ -267,7 +267,7 @@ def predict_voicing(confidence) -> numpy.ndarray:
 
 
 # ---- the device model ---------------------------------------------------------------------------------------------------------
-class CrepeModel(object):
+class CrepeModel(DeviceHandle):
     """CREPE on the MI355X (`ry_crepe_*`).  Picklable and fork-safe: the GPU context and the device weights are created lazily in the
     process that first predicts; the host copy of the weights travels with the object.  `ctx` (tests) is a context over another build
     of the library -- the emulator -- used instead of the product's context of `device`."""
@@ -280,37 +280,24 @@ class CrepeModel(object):
                 raise ValueError('CrepeModel needs weights: pass params (load_weights / synthetic_params) or a seed for synthetic ones')
             params = synthetic_params(self.m, seed)
         self.blob = flatten_params(self.m, params)
-        self.device = int(os.environ.get('RY_DEVICE', '0')) if device is None else int(device)
         self.bn_eps = float(bn_eps)
-        self._ctx = ctx
-        self._given_ctx = ctx
-        self._handle = None
-        self._pid = None
         self._rs = {}                      # input rate -> entries of the time register the handle holds
+        DeviceHandle.__init__(self, ctx, device)
+
+    _destroy = 'ry_crepe_destroy'
 
     def __getstate__(self):
-        d = dict(self.__dict__)
+        d = DeviceHandle.__getstate__(self)
         d['_rs'] = {}
-        d['_handle'] = None
-        d['_pid'] = None
-        d['_ctx'] = None
-        d['_given_ctx'] = None
         return d
 
-    def _get(self):
-        if self._handle is None or self._pid != os.getpid():
-            from . import engine
-            given = self._given_ctx is not None and self._given_ctx.pid == os.getpid()
-            self._ctx = self._given_ctx if given else engine.get_context(self.device)
-            lib = self._ctx.lib
-            h = ctypes.c_void_p()
-            lib.check(lib.dll.ry_crepe_create(self._ctx.handle, self.m, _lib._fptr(self.blob), self.blob.size, self.bn_eps, ctypes.byref(h)))
-            self._handle, self._pid = h, os.getpid()
-            self._rs = {}
-            dp = ctypes.POINTER(ctypes.c_double)
-            tabs = [numpy.ascontiguousarray(t, dtype=numpy.float64) for t in viterbi_tables()]
-            lib.check(lib.dll.ry_crepe_set_viterbi_tables(self._handle, *[t.ctypes.data_as(dp) for t in tabs]))
-        return self._ctx.lib, self._handle
+    def _create(self, lib, ctx):
+        h = ctypes.c_void_p()
+        lib.check(lib.dll.ry_crepe_create(ctx.handle, self.m, _lib._fptr(self.blob), self.blob.size, self.bn_eps, ctypes.byref(h)))
+        self._rs = {}
+        tabs = [numpy.ascontiguousarray(t, dtype=numpy.float64) for t in viterbi_tables()]
+        lib.check(lib.dll.ry_crepe_set_viterbi_tables(h, *[_dptr(t) for t in tabs]))
+        return h
 
     def predict16k(self, audio, hop: int, center: bool = True, viterbi: bool = True, activation: bool = True):
         """audio: float32 samples at 16 kHz -> (f0 float32 Hz, confidence float32, activation [frames][360] float32 or None)."""
@@ -333,14 +320,13 @@ class CrepeModel(object):
         have = self._rs.get(sr, 0)
         if n_out <= have:
             return
-        dp = ctypes.POINTER(ctypes.c_double)
         n = max(n_out, 2 * have)
         tr = numpy.ascontiguousarray(time_register(sr, n), dtype=numpy.float64)
         if have:
-            lib.check(lib.dll.ry_crepe_set_resampler(h, sr, None, 0, 0, 0, tr.ctypes.data_as(dp), n))
+            lib.check(lib.dll.ry_crepe_set_resampler(h, sr, None, 0, 0, 0, _dptr(tr), n))
         else:
             win, num_table, step = resampler_tables(sr)
-            lib.check(lib.dll.ry_crepe_set_resampler(h, sr, win.ctypes.data_as(dp), win.size, num_table, step, tr.ctypes.data_as(dp), n))
+            lib.check(lib.dll.ry_crepe_set_resampler(h, sr, _dptr(win), win.size, num_table, step, _dptr(tr), n))
         self._rs[sr] = n
 
     def resample(self, audio, sr) -> numpy.ndarray:
@@ -412,14 +398,3 @@ class CrepeModel(object):
         s = (ctypes.c_int * 7)()
         lib.check(lib.dll.ry_crepe_debug_splits(h, s))
         return list(s)
-
-    def close(self):
-        if self._handle is not None and self._pid == os.getpid() and self._ctx is not None and self._ctx.handle is not None:
-            self._ctx.lib.dll.ry_crepe_destroy(self._handle)
-        self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

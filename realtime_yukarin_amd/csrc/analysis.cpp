@@ -17,13 +17,9 @@ struct ry_analysis {
     Arena tables;
     sy_c* tw = nullptr;
     double* S = nullptr;                     // [513][order + 1]
-    Arena scratch;
-    double* d_x = nullptr; long long cap_x = 0;
-    double* d_f0 = nullptr; long long cap_f0 = 0;
-    double* d_t = nullptr; long long cap_t = 0;
-    double* d_sp = nullptr; long long cap_sp = 0;
-    double* d_mc = nullptr; long long cap_mc = 0;
-    AnalysisFrameInts* d_ints = nullptr; long long cap_ints = 0;
+    DevBufList scratch;                               // every buffer a call grows
+    DevBuf<double> d_x{scratch}, d_f0{scratch}, d_t{scratch}, d_sp{scratch}, d_mc{scratch};
+    DevBuf<AnalysisFrameInts> d_ints{scratch};
     bool record = false;                              // ry_analysis_debug_record: keep the decisions of a run (tests; off the product path)
     std::vector<AnalysisFrameInts> last_ints;         // ry_analysis_debug_ints: the decisions of the last recorded run
     // D4C: built for the rates whose transform sizes are 2048 and whose band centres are bins of the row (16 and 24 kHz); d4c_why says why not
@@ -32,33 +28,12 @@ struct ry_analysis {
     int n_bands = 0, band_half = 0, band_centre[D4C_MAX_BANDS] = {0, 0, 0}, lt[3] = {0, 0, 0};
     sy_c* tw2 = nullptr;                              // [1025]
     double* nuttall = nullptr;                        // [2 band_half + 1]
-    double* d_ap = nullptr; long long cap_ap = 0;
-    double* d_coded = nullptr; long long cap_coded = 0;
-    D4cFrameRecord* d_rec = nullptr; long long cap_rec = 0;
+    DevBuf<double> d_ap{scratch}, d_coded{scratch};
+    DevBuf<D4cFrameRecord> d_rec{scratch};
     std::vector<D4cFrameRecord> last_rec;             // ry_analysis_debug_d4c: a0, on / off, integers and coarse values of the last recorded run
 };
 
 namespace {
-template <typename T>
-int alloc_as(Arena& a, T** p, size_t n) {
-    float* q = nullptr;
-    RY_TRY(a.alloc(&q, (n * sizeof(T) + sizeof(float) - 1) / sizeof(float)));
-    *p = (T*)q;
-    return RY_OK;
-}
-
-template <typename T>
-int grow(ry_analysis* s, T** p, long long* cap, long long need) {
-    if (need <= *cap) return RY_OK;
-    RT_TRY(rt::stream_sync(s->ctx->stream));                       // work in flight may use the old buffer
-    if (*p) s->scratch.free_one(*p);
-    *p = nullptr; *cap = 0;
-    const long long n = need + need / 2 + 64;
-    RY_TRY(alloc_as(s->scratch, p, (size_t)n));
-    *cap = n;
-    return RY_OK;
-}
-
 // freqt is linear in the cepstrum: S[i] = freqt(unit vector i), the SPTK recursion in long double, rounded once
 void freqt_matrix(int order, double alpha, std::vector<double>* S) {
     const int M = order + 1;
@@ -75,12 +50,6 @@ void freqt_matrix(int order, double alpha, std::vector<double>* S) {
         }
         for (int j = 0; j < M; ++j) (*S)[(size_t)u * M + j] = (double)g[j];
     }
-}
-
-int check_handle(ry_analysis* s) {
-    if (!s) return fail(RY_ESTATE, "null analysis handle");
-    RT_TRY(rt::set_device(s->ctx->device));
-    return RY_OK;
 }
 
 int pow2_above(double v) { return 1 << (1 + (int)std::floor(std::log2(v))); }
@@ -104,20 +73,14 @@ int d4c_setup(ry_analysis* s) {
         return fail(RY_ESTATE, "D4C band table at %d Hz", fs);
     const long long hz[3] = {100, 4000, 7900};
     for (int i = 0; i < 3; ++i) s->lt[i] = (int)((hz[i] * D4C_FFT + fs - 1) / fs);
-    std::vector<double> tw2(2 * D4C_BINS), nut((size_t)2 * s->band_half + 1);
-    for (int k = 0; k < D4C_BINS; ++k) {
-        tw2[2 * k] = std::cos(SYNTH_TWO_PI * k / D4C_FFT);
-        tw2[2 * k + 1] = std::sin(SYNTH_TWO_PI * k / D4C_FFT);
-    }
+    const std::vector<double> tw2 = twiddles(D4C_FFT, D4C_BINS);
+    std::vector<double> nut((size_t)2 * s->band_half + 1);
     for (size_t i = 0; i < nut.size(); ++i) {
         const double tmp = (double)i / (double)(nut.size() - 1);
         nut[i] = 0.355768 - 0.487396 * std::cos(SYNTH_TWO_PI * tmp) + 0.144232 * std::cos(2.0 * SYNTH_TWO_PI * tmp) - 0.012604 * std::cos(3.0 * SYNTH_TWO_PI * tmp);
     }
-    RY_TRY(alloc_as(s->tables, &s->tw2, (size_t)D4C_BINS));
-    RY_TRY(alloc_as(s->tables, &s->nuttall, nut.size()));
-    RT_TRY(rt::h2d(s->tw2, tw2.data(), tw2.size() * sizeof(double), s->ctx->stream));
-    RT_TRY(rt::h2d(s->nuttall, nut.data(), nut.size() * sizeof(double), s->ctx->stream));
-    RT_TRY(rt::stream_sync(s->ctx->stream));
+    RY_TRY(upload_table(s->tables, s->ctx, (const sy_c*)tw2.data(), (size_t)D4C_BINS, &s->tw2));
+    RY_TRY(upload_table(s->tables, s->ctx, nut.data(), nut.size(), &s->nuttall));
     s->d4c_ok = true;
     return RY_OK;
 }
@@ -130,7 +93,7 @@ struct Outputs {
 
 // one upload of the wave and the track, then CheapTrick + sp2mc (when `cheaptrick`) and / or D4C (when o.d4c) over it
 int run_frames(ry_analysis* s, const double* x, long long x_len, const double* f0, const double* t, int n, bool cheaptrick, const Outputs& o) {
-    RY_TRY(check_handle(s));
+    RY_TRY(check_handle(s, "analysis"));
     if (n < 0) return fail(RY_EINVAL, "n = %d frames", n);
     if (x_len < 0) return fail(RY_EINVAL, "x_len = %lld", x_len);
     if (n > (1 << 22)) return fail(RY_EINVAL, "%d frames in one call", n);
@@ -149,54 +112,54 @@ int run_frames(ry_analysis* s, const double* x, long long x_len, const double* f
         if (o.d4c && t[i] < -1.0) return fail(RY_EINVAL, "t[%d] = %g: D4C takes frames from -1 s on", i, t[i]);
     }
     const ry_stream_t st = s->ctx->stream;
-    RY_TRY(grow(s, &s->d_x, &s->cap_x, x_len));
-    RY_TRY(grow(s, &s->d_f0, &s->cap_f0, (long long)n));
-    RY_TRY(grow(s, &s->d_t, &s->cap_t, (long long)n));
+    RY_TRY(s->d_x.grow(s->ctx, x_len));
+    RY_TRY(s->d_f0.grow(s->ctx, (long long)n));
+    RY_TRY(s->d_t.grow(s->ctx, (long long)n));
     if (cheaptrick) {
-        if (s->record) RY_TRY(grow(s, &s->d_ints, &s->cap_ints, (long long)n));
-        if (o.sp64) RY_TRY(grow(s, &s->d_sp, &s->cap_sp, (long long)n * SYNTH_BINS));
-        if (o.mc) RY_TRY(grow(s, &s->d_mc, &s->cap_mc, (long long)n * (s->order + 1)));
+        if (s->record) RY_TRY(s->d_ints.grow(s->ctx, (long long)n));
+        if (o.sp64) RY_TRY(s->d_sp.grow(s->ctx, (long long)n * SYNTH_BINS));
+        if (o.mc) RY_TRY(s->d_mc.grow(s->ctx, (long long)n * (s->order + 1)));
     }
     if (o.d4c) {
-        if (s->record) RY_TRY(grow(s, &s->d_rec, &s->cap_rec, (long long)n));
-        if (o.ap64) RY_TRY(grow(s, &s->d_ap, &s->cap_ap, (long long)n * SYNTH_BINS));
-        if (o.coded) RY_TRY(grow(s, &s->d_coded, &s->cap_coded, (long long)n * s->n_bands));
+        if (s->record) RY_TRY(s->d_rec.grow(s->ctx, (long long)n));
+        if (o.ap64) RY_TRY(s->d_ap.grow(s->ctx, (long long)n * SYNTH_BINS));
+        if (o.coded) RY_TRY(s->d_coded.grow(s->ctx, (long long)n * s->n_bands));
     }
-    RT_TRY(rt::h2d(s->d_x, x, (size_t)x_len * sizeof(double), st));
-    RT_TRY(rt::h2d(s->d_f0, f0, (size_t)n * sizeof(double), st));
-    RT_TRY(rt::h2d(s->d_t, t, (size_t)n * sizeof(double), st));
+    RT_TRY(rt::h2d(s->d_x.ptr(), x, (size_t)x_len * sizeof(double), st));
+    RT_TRY(rt::h2d(s->d_f0.ptr(), f0, (size_t)n * sizeof(double), st));
+    RT_TRY(rt::h2d(s->d_t.ptr(), t, (size_t)n * sizeof(double), st));
     if (cheaptrick) {
         AnalysisParams p;
-        p.x = s->d_x; p.x_len = x_len; p.f0 = s->d_f0; p.t = s->d_t;
+        p.x = s->d_x.ptr(); p.x_len = x_len; p.f0 = s->d_f0.ptr(); p.t = s->d_t.ptr();
         p.fs = (double)s->fs; p.floor_f0 = s->floor_f0; p.q1 = s->q1; p.seed_hash = s->seed_hash;
         p.tw = s->tw; p.S = s->S; p.n_mc = s->order + 1;
-        p.sp64 = o.sp64 ? s->d_sp : nullptr; p.sp32 = o.sp32_dev; p.mc = o.mc ? s->d_mc : nullptr; p.ints = s->record ? s->d_ints : nullptr;
+        p.sp64 = o.sp64 ? s->d_sp.ptr() : nullptr; p.sp32 = o.sp32_dev; p.mc = o.mc ? s->d_mc.ptr() : nullptr; p.ints = s->record ? s->d_ints.ptr() : nullptr;
         RY_LAUNCH(analysis_frame, dim3((unsigned)n), 256, st, p);
         RT_TRY(rt::last_error());
     }
     if (o.d4c) {
         D4cParams p;
-        p.x = s->d_x; p.x_len = x_len; p.f0 = s->d_f0; p.t = s->d_t;
+        p.x = s->d_x.ptr(); p.x_len = x_len; p.f0 = s->d_f0.ptr(); p.t = s->d_t.ptr();
         p.fs = (double)s->fs; p.threshold = o.threshold; p.seed_hash = s->seed_hash;
         p.tw = s->tw; p.tw2 = s->tw2; p.nuttall = s->nuttall;
         p.n_bands = s->n_bands; p.band_half = s->band_half;
         for (int i = 0; i < D4C_MAX_BANDS; ++i) p.band_centre[i] = s->band_centre[i];
         p.lt0 = s->lt[0]; p.lt1 = s->lt[1]; p.lt2 = s->lt[2];
-        p.ap64 = o.ap64 ? s->d_ap : nullptr; p.ap32 = o.ap32_dev; p.coded = o.coded ? s->d_coded : nullptr; p.rec = s->record ? s->d_rec : nullptr;
+        p.ap64 = o.ap64 ? s->d_ap.ptr() : nullptr; p.ap32 = o.ap32_dev; p.coded = o.coded ? s->d_coded.ptr() : nullptr; p.rec = s->record ? s->d_rec.ptr() : nullptr;
         RY_LAUNCH(d4c_frame, dim3((unsigned)n), 256, st, p);
         RT_TRY(rt::last_error());
     }
     if (cheaptrick) {
         s->last_ints.resize(s->record ? (size_t)n : 0);
-        if (s->record) RT_TRY(rt::d2h(s->last_ints.data(), s->d_ints, (size_t)n * sizeof(AnalysisFrameInts), st));
-        if (o.sp64) RT_TRY(rt::d2h(o.sp64, s->d_sp, (size_t)n * SYNTH_BINS * sizeof(double), st));
-        if (o.mc) RT_TRY(rt::d2h(o.mc, s->d_mc, (size_t)n * (s->order + 1) * sizeof(double), st));
+        if (s->record) RT_TRY(rt::d2h(s->last_ints.data(), s->d_ints.ptr(), (size_t)n * sizeof(AnalysisFrameInts), st));
+        if (o.sp64) RT_TRY(rt::d2h(o.sp64, s->d_sp.ptr(), (size_t)n * SYNTH_BINS * sizeof(double), st));
+        if (o.mc) RT_TRY(rt::d2h(o.mc, s->d_mc.ptr(), (size_t)n * (s->order + 1) * sizeof(double), st));
     }
     if (o.d4c) {
         s->last_rec.resize(s->record ? (size_t)n : 0);
-        if (s->record) RT_TRY(rt::d2h(s->last_rec.data(), s->d_rec, (size_t)n * sizeof(D4cFrameRecord), st));
-        if (o.ap64) RT_TRY(rt::d2h(o.ap64, s->d_ap, (size_t)n * SYNTH_BINS * sizeof(double), st));
-        if (o.coded) RT_TRY(rt::d2h(o.coded, s->d_coded, (size_t)n * s->n_bands * sizeof(double), st));
+        if (s->record) RT_TRY(rt::d2h(s->last_rec.data(), s->d_rec.ptr(), (size_t)n * sizeof(D4cFrameRecord), st));
+        if (o.ap64) RT_TRY(rt::d2h(o.ap64, s->d_ap.ptr(), (size_t)n * SYNTH_BINS * sizeof(double), st));
+        if (o.coded) RT_TRY(rt::d2h(o.coded, s->d_coded.ptr(), (size_t)n * s->n_bands * sizeof(double), st));
     }
     RT_TRY(rt::stream_sync(st));                                   // the caller's arrays are free, the float32 rows are written
     return RY_OK;
@@ -218,20 +181,12 @@ int ry_analysis_create(ry_ctx* ctx, int fs, int fft_size, int order, double alph
     std::unique_ptr<ry_analysis> s(new ry_analysis());
     s->ctx = ctx; s->fs = fs; s->order = order; s->alpha = alpha; s->q1 = q1;
     s->floor_f0 = std::max(f0_floor, 3.0 * fs / (fft_size - 3.0));
-    unsigned h = seed;                                              // synth_hash32 on the host
-    h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
-    s->seed_hash = h;
-    std::vector<double> tw(2 * SYNTH_FFT), S;
-    for (int k = 0; k < SYNTH_FFT; ++k) {
-        tw[2 * k] = std::cos(SYNTH_TWO_PI * k / SYNTH_FFT);
-        tw[2 * k + 1] = std::sin(SYNTH_TWO_PI * k / SYNTH_FFT);
-    }
+    s->seed_hash = synth_hash32(seed);
+    const std::vector<double> tw = twiddles(SYNTH_FFT);
+    std::vector<double> S;
     freqt_matrix(order, alpha, &S);
-    RY_TRY(alloc_as(s->tables, &s->tw, (size_t)SYNTH_FFT));
-    RY_TRY(alloc_as(s->tables, &s->S, S.size()));
-    RT_TRY(rt::h2d(s->tw, tw.data(), tw.size() * sizeof(double), ctx->stream));
-    RT_TRY(rt::h2d(s->S, S.data(), S.size() * sizeof(double), ctx->stream));
-    RT_TRY(rt::stream_sync(ctx->stream));
+    RY_TRY(upload_table(s->tables, ctx, (const sy_c*)tw.data(), (size_t)SYNTH_FFT, &s->tw));
+    RY_TRY(upload_table(s->tables, ctx, S.data(), S.size(), &s->S));
     RY_TRY(d4c_setup(s.get()));
     *out = s.release();
     return RY_OK;
@@ -273,25 +228,25 @@ int ry_analysis_d4c_bands(ry_analysis* s) {
 }
 
 int ry_analysis_sp2mc(ry_analysis* s, const void* sp, int n, int on_device, double* mc_out) {
-    RY_TRY(check_handle(s));
+    RY_TRY(check_handle(s, "analysis"));
     if (n < 0) return fail(RY_EINVAL, "n = %d frames", n);
     if (n > (1 << 22)) return fail(RY_EINVAL, "%d frames in one call", n);
     if (n == 0) return RY_OK;
     if (!sp || !mc_out) return fail(RY_EINVAL, "null sp / mc");
     const ry_stream_t st = s->ctx->stream;
-    RY_TRY(grow(s, &s->d_mc, &s->cap_mc, (long long)n * (s->order + 1)));
+    RY_TRY(s->d_mc.grow(s->ctx, (long long)n * (s->order + 1)));
     AnalysisSp2mcParams p;
     p.sp64 = nullptr; p.sp32 = nullptr;
     if (on_device) p.sp32 = (const float*)sp;
     else {
-        RY_TRY(grow(s, &s->d_sp, &s->cap_sp, (long long)n * SYNTH_BINS));
-        RT_TRY(rt::h2d(s->d_sp, sp, (size_t)n * SYNTH_BINS * sizeof(double), st));
-        p.sp64 = s->d_sp;
+        RY_TRY(s->d_sp.grow(s->ctx, (long long)n * SYNTH_BINS));
+        RT_TRY(rt::h2d(s->d_sp.ptr(), sp, (size_t)n * SYNTH_BINS * sizeof(double), st));
+        p.sp64 = s->d_sp.ptr();
     }
-    p.tw = s->tw; p.S = s->S; p.n_mc = s->order + 1; p.mc = s->d_mc;
+    p.tw = s->tw; p.S = s->S; p.n_mc = s->order + 1; p.mc = s->d_mc.ptr();
     RY_LAUNCH(analysis_sp2mc, dim3((unsigned)n), 256, st, p);
     RT_TRY(rt::last_error());
-    RT_TRY(rt::d2h(mc_out, s->d_mc, (size_t)n * (s->order + 1) * sizeof(double), st));
+    RT_TRY(rt::d2h(mc_out, s->d_mc.ptr(), (size_t)n * (s->order + 1) * sizeof(double), st));
     RT_TRY(rt::stream_sync(st));
     return RY_OK;
 }
@@ -335,19 +290,10 @@ int ry_analysis_debug_ints(ry_analysis* s, long long* out, int capacity, int* n)
 }
 
 int ry_analysis_debug_poison(ry_analysis* s) {
-    RY_TRY(check_handle(s));
+    RY_TRY(check_handle(s, "analysis"));
     const ry_stream_t st = s->ctx->stream;
     RT_TRY(rt::stream_sync(st));
-    // every buffer a call grows: all bits set (NaN as a double, -1 as an integer)
-    if (s->d_x) RT_TRY(rt::dmemset(s->d_x, 0xff, (size_t)s->cap_x * sizeof(double), st));
-    if (s->d_f0) RT_TRY(rt::dmemset(s->d_f0, 0xff, (size_t)s->cap_f0 * sizeof(double), st));
-    if (s->d_t) RT_TRY(rt::dmemset(s->d_t, 0xff, (size_t)s->cap_t * sizeof(double), st));
-    if (s->d_sp) RT_TRY(rt::dmemset(s->d_sp, 0xff, (size_t)s->cap_sp * sizeof(double), st));
-    if (s->d_mc) RT_TRY(rt::dmemset(s->d_mc, 0xff, (size_t)s->cap_mc * sizeof(double), st));
-    if (s->d_ints) RT_TRY(rt::dmemset(s->d_ints, 0xff, (size_t)s->cap_ints * sizeof(AnalysisFrameInts), st));
-    if (s->d_ap) RT_TRY(rt::dmemset(s->d_ap, 0xff, (size_t)s->cap_ap * sizeof(double), st));
-    if (s->d_coded) RT_TRY(rt::dmemset(s->d_coded, 0xff, (size_t)s->cap_coded * sizeof(double), st));
-    if (s->d_rec) RT_TRY(rt::dmemset(s->d_rec, 0xff, (size_t)s->cap_rec * sizeof(D4cFrameRecord), st));
+    for (DevBufBase* b : s->scratch) RY_TRY(b->poison(st));            // all bits set: NaN as a double, -1 as an integer
     RT_TRY(rt::stream_sync(st));
     return RY_OK;
 }

@@ -62,16 +62,14 @@ struct ry_crepe {
     float* slabs = nullptr;
     size_t slab_floats = 0;
     int last_chunk = 0;                             // frames of the last pass (ry_crepe_debug_layer)
-    // call buffers (every frame of a call)
-    Arena call;
-    int cap_frames = 0, cap_samples = 0;
-    float *audio = nullptr, *act = nullptr, *conf = nullptr, *f0 = nullptr;
-    int *obs = nullptr, *bp = nullptr, *path = nullptr;
-    // resampling: tables per input rate, the uploaded input at that rate (the 16 kHz result goes to `audio`)
-    Arena rs_tables, rs_in;
+    // call buffers, each as long as the longest call so far needed it: the audio at 16 kHz (uploaded, or the resampler's output), the uploaded
+    // input at another rate, and one entry / one row per frame of a call
+    DevBufList call;
+    DevBuf<float> audio{call}, audio_sr{call}, act{call}, conf{call}, f0{call};
+    DevBuf<int> obs{call}, bp{call}, path{call};
+    // resampling: tables per input rate
+    Arena rs_tables;
     std::map<int, Resampler> rs;
-    float* audio_sr = nullptr;
-    int cap_sr = 0;
 };
 
 namespace {
@@ -95,26 +93,21 @@ int ensure_chunk(ry_crepe* c, int nf) {
     return RY_OK;
 }
 
+// the buffers of a call of n_frames frames over n_samples samples at 16 kHz in `audio` (0: the caller's device pointer is read): exact sizes
 int ensure_call(ry_crepe* c, int n_frames, int n_samples) {
-    if (n_frames > c->cap_frames || n_samples > c->cap_samples) {
-        RT_TRY(rt::stream_sync(c->ctx->stream));
-        c->call.release();
-        c->cap_frames = std::max(n_frames, c->cap_frames);
-        c->cap_samples = std::max(n_samples, c->cap_samples);
-        const size_t F = (size_t)c->cap_frames;
-        float* q = nullptr;
-        RY_TRY(c->call.alloc(&c->audio, (size_t)c->cap_samples));
-        RY_TRY(c->call.alloc(&c->act, F * CREPE_BINS));
-        RY_TRY(c->call.alloc(&c->conf, F));
-        RY_TRY(c->call.alloc(&c->f0, F));
-        RY_TRY(c->call.alloc(&q, F)); c->obs = (int*)q;
-        RY_TRY(c->call.alloc(&q, F)); c->path = (int*)q;
-        RY_TRY(c->call.alloc(&q, F * CREPE_BINS)); c->bp = (int*)q;
-    }
+    const long long F = n_frames;
+    RY_TRY(c->audio.reserve(c->ctx, n_samples));
+    RY_TRY(c->act.reserve(c->ctx, F * CREPE_BINS));
+    RY_TRY(c->conf.reserve(c->ctx, F));
+    RY_TRY(c->f0.reserve(c->ctx, F));
+    RY_TRY(c->obs.reserve(c->ctx, F));
+    RY_TRY(c->path.reserve(c->ctx, F));
+    RY_TRY(c->bp.reserve(c->ctx, F * CREPE_BINS));
     return RY_OK;
 }
 
-int launch_layer(ry_crepe* c, int i, int nf) {
+// layer i on the nf frames of a pass; `act`: the rows of this pass in the call's activation, written by the dense layer
+int launch_layer(ry_crepe* c, int i, int nf, float* act) {
     const CLayer& l = c->L[i];
     const bool dense = i == NCONV;
     CrepeGemmParams p;
@@ -123,7 +116,6 @@ int launch_layer(ry_crepe* c, int i, int nf) {
     p.in_fstride = l.in_fstride; p.in_rstride = l.in_rstride;
     p.out_fstride = l.out_fstride; p.out_off = l.out_off; p.splits = l.splits;
     float* out = dense ? nullptr : c->act_in[i + 1];
-    float* act = c->act;                                        // set by the caller to this pass's rows (ry_crepe_predict)
     dim3 grid((unsigned)((l.cout + CREPE_BN - 1) / CREPE_BN), (unsigned)((p.M + CREPE_BM - 1) / CREPE_BM), (unsigned)l.splits);
     const ry_stream_t s = c->ctx->stream;
     const int epi = l.splits > 1 ? CREPE_EPI_RAW : dense ? CREPE_EPI_SIG : CREPE_EPI_POOL;
@@ -159,23 +151,14 @@ int launch_layer(ry_crepe* c, int i, int nf) {
 int launch_decode(ry_crepe* c, const float* act, int nf, int viterbi) {
     const ry_stream_t s = c->ctx->stream;
     CrepeArgmaxParams ap;
-    ap.act = act; ap.n_frames = nf; ap.obs = c->obs; ap.conf = c->conf;
+    ap.act = act; ap.n_frames = nf; ap.obs = c->obs.ptr(); ap.conf = c->conf.ptr();
     RY_LAUNCH(crepe_argmax, dim3((unsigned)((nf + 3) / 4)), 256, s, ap);
     RT_TRY(rt::last_error());
     CrepeDecodeParams dp;
-    dp.act = act; dp.obs = c->obs; dp.n_frames = nf; dp.viterbi = viterbi ? 1 : 0;
-    dp.logT = c->logT; dp.logE = c->logE; dp.logS = c->logS; dp.bp = c->bp; dp.path = c->path; dp.f0 = c->f0;
+    dp.act = act; dp.obs = c->obs.ptr(); dp.n_frames = nf; dp.viterbi = viterbi ? 1 : 0;
+    dp.logT = c->logT; dp.logE = c->logE; dp.logS = c->logS; dp.bp = c->bp.ptr(); dp.path = c->path.ptr(); dp.f0 = c->f0.ptr();
     RY_LAUNCH(crepe_decode, dim3(1), 384, s, dp);
     RT_TRY(rt::last_error());
-    return RY_OK;
-}
-
-int upload_doubles(Arena& a, ry_ctx* ctx, const double* h, size_t n, double** d) {
-    float* q = nullptr;
-    RY_TRY(a.alloc(&q, 2 * n));
-    RT_TRY(rt::h2d(q, h, n * sizeof(double), ctx->stream));
-    RT_TRY(rt::stream_sync(ctx->stream));
-    *d = (double*)q;
     return RY_OK;
 }
 
@@ -192,29 +175,25 @@ int frame_count(int n_samples, int hop, int center, int* nf) {
 int run_network(ry_crepe* c, const float* d_audio, int n_samples, int hop, int center, int viterbi, int nf,
                 float* f0, float* confidence, float* activation, int on_device) {
     const ry_stream_t s = c->ctx->stream;
-    float* act_all = c->act;
+    float* act_all = c->act.ptr();
     for (int f = 0; f < nf; f += CHUNK) {
         const int n = std::min(CHUNK, nf - f);
         CrepeFrameParams fp;
         fp.audio = d_audio; fp.n = n_samples; fp.hop = hop; fp.center = center; fp.frame0 = f; fp.n_frames = n; fp.out = c->act_in[0];
         RY_LAUNCH(crepe_frames, dim3((unsigned)n), 256, s, fp);
         RT_TRY(rt::last_error());
-        c->act = act_all + (size_t)f * CREPE_BINS;                 // the dense layer writes this pass's rows
-        int rc = RY_OK;
-        for (int i = 0; i <= NCONV && rc == RY_OK; ++i) rc = launch_layer(c, i, n);
-        c->act = act_all;
-        RY_TRY(rc);
+        for (int i = 0; i <= NCONV; ++i) RY_TRY(launch_layer(c, i, n, act_all + (size_t)f * CREPE_BINS));
         c->last_chunk = n;
     }
     RY_TRY(launch_decode(c, act_all, nf, viterbi));
     if (on_device) {
-        RT_TRY(rt::d2d(f0, c->f0, (size_t)nf * sizeof(float), s));
-        RT_TRY(rt::d2d(confidence, c->conf, (size_t)nf * sizeof(float), s));
+        RT_TRY(rt::d2d(f0, c->f0.ptr(), (size_t)nf * sizeof(float), s));
+        RT_TRY(rt::d2d(confidence, c->conf.ptr(), (size_t)nf * sizeof(float), s));
         if (activation) RT_TRY(rt::d2d(activation, act_all, (size_t)nf * CREPE_BINS * sizeof(float), s));
         return RY_OK;
     }
-    RT_TRY(rt::d2h(f0, c->f0, (size_t)nf * sizeof(float), s));
-    RT_TRY(rt::d2h(confidence, c->conf, (size_t)nf * sizeof(float), s));
+    RT_TRY(rt::d2h(f0, c->f0.ptr(), (size_t)nf * sizeof(float), s));
+    RT_TRY(rt::d2h(confidence, c->conf.ptr(), (size_t)nf * sizeof(float), s));
     if (activation) RT_TRY(rt::d2h(activation, act_all, (size_t)nf * CREPE_BINS * sizeof(float), s));
     RT_TRY(rt::stream_sync(s));
     return RY_OK;
@@ -237,16 +216,6 @@ int resample_plan(ry_crepe* c, int n_samples, int sr, const Resampler** r, int* 
         return fail(RY_EINVAL, "the time table for %d Hz puts output %d at input sample %lld of %d", sr, n - 1, (long long)it->second.tr_host[(size_t)n - 1], n_samples);
     *r = &it->second;
     *n_out = n;
-    return RY_OK;
-}
-
-int ensure_sr(ry_crepe* c, int n_samples) {
-    if (n_samples <= c->cap_sr) return RY_OK;
-    RT_TRY(rt::stream_sync(c->ctx->stream));
-    c->rs_in.release();
-    c->cap_sr = 0;
-    RY_TRY(c->rs_in.alloc(&c->audio_sr, (size_t)n_samples));
-    c->cap_sr = n_samples;
     return RY_OK;
 }
 
@@ -274,7 +243,7 @@ size_t ry_crepe_param_count(int capacity) {
 
 int ry_crepe_set_viterbi_tables(ry_crepe* c, const double* logT, const double* logE, const double* logS) {
     if (!c || !logT || !logE || !logS) return fail(RY_EINVAL, "bad argument");
-    RT_TRY(rt::set_device(c->ctx->device));
+    RY_TRY(check_handle(c, "crepe"));
     RT_TRY(rt::stream_sync(c->ctx->stream));                   // the tables may be in use by a call still in flight
     RT_TRY(rt::h2d(c->logT, logT, sizeof(double) * CREPE_BINS * CREPE_BINS, c->ctx->stream));
     RT_TRY(rt::h2d(c->logE, logE, sizeof(double) * CREPE_BINS * CREPE_BINS, c->ctx->stream));
@@ -349,9 +318,9 @@ int ry_crepe_create(ry_ctx* ctx, int capacity, const float* weights, size_t n_fl
         }
         ls[i] = std::log(1.0 / CREPE_BINS);
     }
-    RY_TRY(upload_doubles(c->weights, ctx, lt.data(), lt.size(), &c->logT));
-    RY_TRY(upload_doubles(c->weights, ctx, le.data(), le.size(), &c->logE));
-    RY_TRY(upload_doubles(c->weights, ctx, ls.data(), ls.size(), &c->logS));
+    RY_TRY(upload_table(c->weights, ctx, lt.data(), lt.size(), &c->logT));
+    RY_TRY(upload_table(c->weights, ctx, le.data(), le.size(), &c->logE));
+    RY_TRY(upload_table(c->weights, ctx, ls.data(), ls.size(), &c->logS));
     *out = c.release();
     return RY_OK;
 }
@@ -365,25 +334,24 @@ void ry_crepe_destroy(ry_crepe* c) {
 
 int ry_crepe_predict(ry_crepe* c, const float* audio, int n_samples, int hop, int center, int viterbi,
                      float* f0, float* confidence, float* activation, int on_device) {
-    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    RY_TRY(check_handle(c, "crepe"));
     if (!audio || !f0 || !confidence || n_samples < 1 || hop < 1) return fail(RY_EINVAL, "bad argument");
     int nf = 0;
     RY_TRY(frame_count(n_samples, hop, center, &nf));
     ry_ctx* ctx = c->ctx;
     const ry_stream_t s = ctx->stream;
-    RT_TRY(rt::set_device(ctx->device));
     RY_TRY(ensure_chunk(c, std::min(nf, CHUNK)));
     RY_TRY(ensure_call(c, nf, on_device ? 0 : n_samples));
     const float* d_audio = audio;
     if (!on_device) {
-        RT_TRY(rt::h2d(c->audio, audio, (size_t)n_samples * sizeof(float), s));
-        d_audio = c->audio;
+        RT_TRY(rt::h2d(c->audio.ptr(), audio, (size_t)n_samples * sizeof(float), s));
+        d_audio = c->audio.ptr();
     }
     return run_network(c, d_audio, n_samples, hop, center, viterbi, nf, f0, confidence, activation, on_device);
 }
 
 int ry_crepe_set_resampler(ry_crepe* c, int sr, const double* win, int n_win, int num_table, int step, const double* time_register, int n_times) {
-    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    RY_TRY(check_handle(c, "crepe"));
     if (sr < 1 || !time_register || n_times < 1) return fail(RY_EINVAL, "bad argument");
     const bool known = c->rs.count(sr) != 0;
     if (!win && !known) return fail(RY_EINVAL, "the first call for %d Hz needs the filter table", sr);
@@ -392,17 +360,16 @@ int ry_crepe_set_resampler(ry_crepe* c, int sr, const double* win, int n_win, in
     for (int i = 1; i < n_times; ++i)
         if (!(time_register[i] >= time_register[i - 1]) || !(time_register[i] < 2147483648.0))
             return fail(RY_EINVAL, "the time register is not a non-decreasing sequence of sample times at entry %d", i);
-    RT_TRY(rt::set_device(c->ctx->device));
     RT_TRY(rt::stream_sync(c->ctx->stream));                   // the tables may be in use by a call still in flight
     Resampler r = known ? c->rs[sr] : Resampler();
     if (win) {
         double* d = nullptr;
-        RY_TRY(upload_doubles(c->rs_tables, c->ctx, win, (size_t)n_win, &d));
+        RY_TRY(upload_table(c->rs_tables, c->ctx, win, (size_t)n_win, &d));
         if (r.win) c->rs_tables.free_one(r.win);
         r.win = d; r.n_win = n_win; r.num_table = num_table; r.step = step;
     }
     double* d = nullptr;
-    RY_TRY(upload_doubles(c->rs_tables, c->ctx, time_register, (size_t)n_times, &d));
+    RY_TRY(upload_table(c->rs_tables, c->ctx, time_register, (size_t)n_times, &d));
     if (r.tr) c->rs_tables.free_one(r.tr);
     r.tr = d; r.n_times = n_times;
     r.tr_host.assign(time_register, time_register + n_times);
@@ -411,19 +378,18 @@ int ry_crepe_set_resampler(ry_crepe* c, int sr, const double* win, int n_win, in
 }
 
 int ry_crepe_resample(ry_crepe* c, const float* audio, int n_samples, int sr, float* out16k, int on_device) {
-    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    RY_TRY(check_handle(c, "crepe"));
     if (!audio || !out16k) return fail(RY_EINVAL, "bad argument");
     const Resampler* r = nullptr;
     int n_out = 0;
     RY_TRY(resample_plan(c, n_samples, sr, &r, &n_out));
     const ry_stream_t s = c->ctx->stream;
-    RT_TRY(rt::set_device(c->ctx->device));
     if (on_device) return launch_resample(c, *r, audio, n_samples, sr, out16k, n_out);
-    RY_TRY(ensure_call(c, 1, n_out));
-    RY_TRY(ensure_sr(c, n_samples));
-    RT_TRY(rt::h2d(c->audio_sr, audio, (size_t)n_samples * sizeof(float), s));
-    RY_TRY(launch_resample(c, *r, c->audio_sr, n_samples, sr, c->audio, n_out));
-    RT_TRY(rt::d2h(out16k, c->audio, (size_t)n_out * sizeof(float), s));
+    RY_TRY(c->audio.reserve(c->ctx, n_out));
+    RY_TRY(c->audio_sr.reserve(c->ctx, n_samples));
+    RT_TRY(rt::h2d(c->audio_sr.ptr(), audio, (size_t)n_samples * sizeof(float), s));
+    RY_TRY(launch_resample(c, *r, c->audio_sr.ptr(), n_samples, sr, c->audio.ptr(), n_out));
+    RT_TRY(rt::d2h(out16k, c->audio.ptr(), (size_t)n_out * sizeof(float), s));
     RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }
@@ -431,48 +397,45 @@ int ry_crepe_resample(ry_crepe* c, const float* audio, int n_samples, int sr, fl
 int ry_crepe_predict_sr(ry_crepe* c, const float* audio, int n_samples, int sr, int hop, int center, int viterbi,
                         float* f0, float* confidence, float* activation, int on_device) {
     if (sr == 16000) return ry_crepe_predict(c, audio, n_samples, hop, center, viterbi, f0, confidence, activation, on_device);
-    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    RY_TRY(check_handle(c, "crepe"));
     if (!audio || !f0 || !confidence || hop < 1) return fail(RY_EINVAL, "bad argument");
     const Resampler* r = nullptr;
     int n_out = 0, nf = 0;
     RY_TRY(resample_plan(c, n_samples, sr, &r, &n_out));
     RY_TRY(frame_count(n_out, hop, center, &nf));
     const ry_stream_t s = c->ctx->stream;
-    RT_TRY(rt::set_device(c->ctx->device));
     RY_TRY(ensure_chunk(c, std::min(nf, CHUNK)));
     RY_TRY(ensure_call(c, nf, n_out));
     const float* d_in = audio;
     if (!on_device) {
-        RY_TRY(ensure_sr(c, n_samples));
-        RT_TRY(rt::h2d(c->audio_sr, audio, (size_t)n_samples * sizeof(float), s));
-        d_in = c->audio_sr;
+        RY_TRY(c->audio_sr.reserve(c->ctx, n_samples));
+        RT_TRY(rt::h2d(c->audio_sr.ptr(), audio, (size_t)n_samples * sizeof(float), s));
+        d_in = c->audio_sr.ptr();
     }
-    RY_TRY(launch_resample(c, *r, d_in, n_samples, sr, c->audio, n_out));
-    return run_network(c, c->audio, n_out, hop, center, viterbi, nf, f0, confidence, activation, on_device);
+    RY_TRY(launch_resample(c, *r, d_in, n_samples, sr, c->audio.ptr(), n_out));
+    return run_network(c, c->audio.ptr(), n_out, hop, center, viterbi, nf, f0, confidence, activation, on_device);
 }
 
 int ry_crepe_decode(ry_crepe* c, const float* activation, int n_frames, int viterbi, float* f0, float* confidence, int* path) {
-    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    RY_TRY(check_handle(c, "crepe"));
     if (!activation || !f0 || !confidence || n_frames < 1 || n_frames > (1 << 24)) return fail(RY_EINVAL, "bad argument");
     const ry_stream_t s = c->ctx->stream;
-    RT_TRY(rt::set_device(c->ctx->device));
     RY_TRY(ensure_call(c, n_frames, 0));
-    RT_TRY(rt::h2d(c->act, activation, (size_t)n_frames * CREPE_BINS * sizeof(float), s));
-    RY_TRY(launch_decode(c, c->act, n_frames, viterbi));
-    RT_TRY(rt::d2h(f0, c->f0, (size_t)n_frames * sizeof(float), s));
-    RT_TRY(rt::d2h(confidence, c->conf, (size_t)n_frames * sizeof(float), s));
-    if (path) RT_TRY(rt::d2h(path, viterbi ? c->path : c->obs, (size_t)n_frames * sizeof(int), s));
+    RT_TRY(rt::h2d(c->act.ptr(), activation, (size_t)n_frames * CREPE_BINS * sizeof(float), s));
+    RY_TRY(launch_decode(c, c->act.ptr(), n_frames, viterbi));
+    RT_TRY(rt::d2h(f0, c->f0.ptr(), (size_t)n_frames * sizeof(float), s));
+    RT_TRY(rt::d2h(confidence, c->conf.ptr(), (size_t)n_frames * sizeof(float), s));
+    if (path) RT_TRY(rt::d2h(path, viterbi ? c->path.ptr() : c->obs.ptr(), (size_t)n_frames * sizeof(int), s));
     RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }
 
 int ry_crepe_debug_layer(ry_crepe* c, int layer, int n_frames, float* out) {
-    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    RY_TRY(check_handle(c, "crepe"));
     if (!out || layer < 0 || layer > NCONV + 1) return fail(RY_EINVAL, "bad argument (layer %d: 0 frames, 1 .. 6 conv outputs, 7 logits)", layer);
     if (c->last_chunk < 1) return fail(RY_ESTATE, "no ry_crepe_predict has run");
     if (n_frames < 1 || n_frames > c->cap_chunk) return fail(RY_EINVAL, "%d frames asked for, the pass buffers hold %d", n_frames, c->cap_chunk);
     const ry_stream_t s = c->ctx->stream;
-    RT_TRY(rt::set_device(c->ctx->device));
     const int n = n_frames;
     if (layer == NCONV + 1) {
         RT_TRY(rt::d2h(out, c->logits, (size_t)n * CREPE_BINS * sizeof(float), s));
@@ -494,9 +457,8 @@ int ry_crepe_debug_layer(ry_crepe* c, int layer, int n_frames, float* out) {
 }
 
 int ry_crepe_debug_poison(ry_crepe* c) {
-    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    RY_TRY(check_handle(c, "crepe"));
     const ry_stream_t s = c->ctx->stream;
-    RT_TRY(rt::set_device(c->ctx->device));
     RT_TRY(rt::stream_sync(s));
     // all bits set (NaN as a float, -1 as an index) in everything the next call must write; the padding rows keep their zeros
     for (int i = 0; i <= NCONV && c->cap_chunk > 0; ++i) {
@@ -510,16 +472,7 @@ int ry_crepe_debug_poison(ry_crepe* c) {
         RT_TRY(rt::dmemset(c->logits, 0xff, (size_t)c->cap_chunk * CREPE_BINS * sizeof(float), s));
         RT_TRY(rt::dmemset(c->slabs, 0xff, c->slab_floats * sizeof(float), s));
     }
-    if (c->cap_samples > 0) RT_TRY(rt::dmemset(c->audio, 0xff, (size_t)c->cap_samples * sizeof(float), s));   // the resampler's output
-    if (c->cap_frames > 0) {
-        const size_t F = (size_t)c->cap_frames;
-        RT_TRY(rt::dmemset(c->act, 0xff, F * CREPE_BINS * sizeof(float), s));
-        RT_TRY(rt::dmemset(c->conf, 0xff, F * sizeof(float), s));
-        RT_TRY(rt::dmemset(c->f0, 0xff, F * sizeof(float), s));
-        RT_TRY(rt::dmemset(c->obs, 0xff, F * sizeof(int), s));
-        RT_TRY(rt::dmemset(c->path, 0xff, F * sizeof(int), s));
-        RT_TRY(rt::dmemset(c->bp, 0xff, F * CREPE_BINS * sizeof(int), s));
-    }
+    for (DevBufBase* b : c->call) RY_TRY(b->poison(s));
     RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }

@@ -49,7 +49,7 @@ RY_DEV void synth_fft(sy_c* a, sy_c* b, const sy_c* tw, double sign) {
 }
 
 // counter-based noise: sample k of seed's noise = (sum of twelve 24-bit uniforms) 2^-24 - 6, the uniforms from lowbias32 over (seed, 12 k + j)
-RY_DEV unsigned synth_hash32(unsigned x) {
+RY_HOST_DEV unsigned synth_hash32(unsigned x) {
     x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
     return x;
 }

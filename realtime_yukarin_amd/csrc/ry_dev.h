@@ -9,6 +9,7 @@
 
 #ifdef RY_HOST_EMU
 #include "ry_emu.h"
+#define RY_HOST_DEV RY_DEV                                    // the emulator's RY_DEV is plain `static inline`: callable from anywhere
 #else
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define RY_DEV __device__ __forceinline__
+#define RY_HOST_DEV __host__ __device__ __forceinline__      // the few functions the host calls too (synth_hash32: the seed of a handle)
 #define RY_DEV_STATIC static __device__ __forceinline__      // static member functions (the emulator build spells RY_DEV "static inline")
 #define RY_KERNEL(...) __global__ __launch_bounds__(__VA_ARGS__)
 

@@ -5,6 +5,10 @@
 //   ry_net.cpp   the predictor C ABI: context / predictor lifetime, dtype modes, forward / convert entry points, debug hooks
 //   ry_vc.cpp    the window call (ring slots, lanes, silence gate, batch) = VoiceChanger.convert_from_acoustic_feature on the device
 //   ry_comm.cpp  RCCL bound at run time (weight broadcast, barrier, max) and plain device buffers for callers without a tensor library
+//   crepe.cpp    the CREPE pitch tracker (crepe_kernels.h): resampler, network passes, decode
+//   synth.cpp    the WORLD synthesizer (synth_kernels.h): one-shot and stream
+//   analysis.cpp the WORLD analysis (analysis_kernels.h, d4c_kernels.h): CheapTrick, sp2mc, D4C
+// The three audio units share DevBuf (growable call buffers), upload_table, twiddles and check_handle below.
 #pragma once
 #include "ry_dev.h"
 
@@ -147,6 +151,43 @@ struct Arena {
     ~Arena() { release(); }
 };
 
+// One growable device buffer of a handle.  The handle keeps a DevBufList and builds every DevBuf<T> member over it -- there is no other
+// constructor -- so what walks the list (ry_*_debug_poison) reaches every buffer the struct has.  Handles live on the heap and never move.
+struct DevBufBase;
+typedef std::vector<DevBufBase*> DevBufList;
+struct DevBufBase {
+    void* raw = nullptr;
+    long long cap = 0;                       // elements
+    const size_t elem;                       // bytes per element
+    DevBufBase(DevBufList& owner, size_t elem_bytes) : elem(elem_bytes) { owner.push_back(this); }
+    DevBufBase(const DevBufBase&) = delete;
+    DevBufBase& operator=(const DevBufBase&) = delete;
+    ~DevBufBase() { if (raw) rt::dfree(raw); }
+    // room for `need` elements: a buffer that is too small is replaced by one of `grown` elements (0: exactly `need`); contents are not kept
+    int reserve(ry_ctx* ctx, long long need, long long grown = 0) {
+        if (need <= cap) return RY_OK;
+        RT_TRY(rt::stream_sync(ctx->stream));                      // work in flight may use the old buffer
+        if (raw) rt::dfree(raw);
+        raw = nullptr; cap = 0;
+        const size_t n = (size_t)(grown > need ? grown : need);
+        rt::err_t e = rt::dmalloc(&raw, n * elem);
+        if (e != 0) { raw = nullptr; return fail(RY_ENOMEM, "device allocation of %zu bytes failed: %s", n * elem, rt::err_str(e)); }
+        cap = (long long)n;
+        return RY_OK;
+    }
+    // the WORLD units' amount: half as much again, so calls that get a little longer each time do not reallocate each time
+    int grow(ry_ctx* ctx, long long need) { return reserve(ctx, need, need + need / 2 + 64); }
+    int poison(ry_stream_t st) {                                    // all bits set: NaN as a float or a double, -1 as an integer
+        if (raw) RT_TRY(rt::dmemset(raw, 0xff, (size_t)cap * elem, st));
+        return RY_OK;
+    }
+};
+template <typename T>
+struct DevBuf : DevBufBase {
+    explicit DevBuf(DevBufList& owner) : DevBufBase(owner, sizeof(T)) {}
+    T* ptr() const { return (T*)raw; }
+};
+
 // ------------------------------------------------------------------------------------------------
 // one layer of a predictor (topology + device parameters), its launch plan, a plan of the whole forward, the predictor
 // ------------------------------------------------------------------------------------------------
@@ -277,10 +318,34 @@ struct ry_net {
     std::vector<std::pair<rt::Event, rt::Event>>* rec_events = nullptr;
 };
 
-static int upload(Arena& a, ry_ctx* ctx, const std::vector<float>& h, float** d) {
-    RY_TRY(a.alloc(d, h.size()));
-    RT_TRY(rt::h2d(*d, h.data(), h.size() * sizeof(float), ctx->stream));
-    RT_TRY(rt::stream_sync(ctx->stream));      // h is a temporary
+// a host table of n elements to a buffer of the arena: allocate, copy, wait (the host array is usually a temporary)
+template <typename T>
+static int upload_table(Arena& a, ry_ctx* ctx, const T* host, size_t n, T** dev) {
+    float* q = nullptr;
+    RY_TRY(a.alloc(&q, (n * sizeof(T) + sizeof(float) - 1) / sizeof(float)));
+    *dev = (T*)q;
+    RT_TRY(rt::h2d(q, host, n * sizeof(T), ctx->stream));
+    RT_TRY(rt::stream_sync(ctx->stream));
+    return RY_OK;
+}
+static int upload(Arena& a, ry_ctx* ctx, const std::vector<float>& h, float** d) { return upload_table(a, ctx, h.data(), h.size(), d); }
+
+// (cos, sin)(2 pi k / n) for k = 0 .. count - 1 (0: n), interleaved: the transforms' twiddle tables (the constant is lds_fft.h's SYNTH_TWO_PI)
+static std::vector<double> twiddles(int n, int count = 0) {
+    if (count == 0) count = n;
+    std::vector<double> tw(2 * (size_t)count);
+    for (int k = 0; k < count; ++k) {
+        tw[2 * k] = std::cos(6.283185307179586476925286766559 * k / n);
+        tw[2 * k + 1] = std::sin(6.283185307179586476925286766559 * k / n);
+    }
+    return tw;
+}
+
+// entry points of anything with a `ctx` member: refuse a null handle (`what` names it in the message), select its device
+template <typename H>
+static int check_handle(H* h, const char* what) {
+    if (!h) return fail(RY_ESTATE, "null %s handle", what);
+    RT_TRY(rt::set_device(h->ctx->device));
     return RY_OK;
 }
 

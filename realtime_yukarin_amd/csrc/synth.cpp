@@ -29,34 +29,13 @@ struct ry_synth {
     float *sp[2] = {}, *ap[2] = {};
     long long win_cap[2] = {0, 0};
     int cur = 0;
-    Arena scratch;
-    double* d_f0 = nullptr; long long cap_f0 = 0;
-    long long* d_pidx = nullptr; double* d_pshift = nullptr; int* d_pvoiced = nullptr; long long cap_p = 0;
-    double* d_resp = nullptr; long long cap_resp = 0;
-    double* d_y = nullptr; long long cap_y = 0;
+    DevBufList scratch;
+    DevBuf<double> d_f0{scratch}, d_pshift{scratch}, d_resp{scratch}, d_y{scratch};
+    DevBuf<long long> d_pidx{scratch};                // d_pidx / d_pshift / d_pvoiced: the pulse list, grown together
+    DevBuf<int> d_pvoiced{scratch};
 };
 
 namespace {
-template <typename T>
-int alloc_as(Arena& a, T** p, size_t n) {
-    float* q = nullptr;
-    RY_TRY(a.alloc(&q, (n * sizeof(T) + sizeof(float) - 1) / sizeof(float)));
-    *p = (T*)q;
-    return RY_OK;
-}
-
-template <typename T>
-int grow(ry_synth* s, T** p, long long* cap, long long need) {
-    if (need <= *cap) return RY_OK;
-    RT_TRY(rt::stream_sync(s->ctx->stream));                       // work in flight may use the old buffer
-    if (*p) s->scratch.free_one(*p);
-    *p = nullptr; *cap = 0;
-    const long long n = need + need / 2 + 64;
-    RY_TRY(alloc_as(s->scratch, p, (size_t)n));
-    *cap = n;
-    return RY_OK;
-}
-
 void reset_stream(ry_synth* s) {
     s->n_frames = 0; s->frame0 = 0; s->f0.clear();
     s->scanned = 0; s->done = 0; s->live.clear();
@@ -144,25 +123,19 @@ int advance(ry_synth* s, bool final, double* y, long long y_capacity, long long*
     const long long n_old = (long long)s->live.size();
     if (n_old + n_new + 1 > (1LL << 30)) return fail(RY_EINVAL, "%lld samples in one call", n_new);
     // the pulse arrays: the live pulses, then what the scan appends (at most one pulse per sample)
-    if (n_old + n_new + 1 > s->cap_p) {
-        RT_TRY(rt::stream_sync(st));
-        const long long cap = (n_old + n_new + 1) * 3 / 2 + 64;
-        if (s->d_pidx) { s->scratch.free_one(s->d_pidx); s->scratch.free_one(s->d_pshift); s->scratch.free_one(s->d_pvoiced); }
-        s->d_pidx = nullptr; s->d_pshift = nullptr; s->d_pvoiced = nullptr; s->cap_p = 0;
-        RY_TRY(alloc_as(s->scratch, &s->d_pidx, (size_t)cap));
-        RY_TRY(alloc_as(s->scratch, &s->d_pshift, (size_t)cap));
-        RY_TRY(alloc_as(s->scratch, &s->d_pvoiced, (size_t)cap));
-        s->cap_p = cap;
-    }
-    RY_TRY(grow(s, &s->d_f0, &s->cap_f0, (long long)s->f0.size()));
+    const long long n_p = n_old + n_new + 1;                       // (grow's n_p + n_p / 2 + 64 is the n_p * 3 / 2 + 64 these have always had)
+    RY_TRY(s->d_pidx.grow(s->ctx, n_p));
+    RY_TRY(s->d_pshift.grow(s->ctx, n_p));
+    RY_TRY(s->d_pvoiced.grow(s->ctx, n_p));
+    RY_TRY(s->d_f0.grow(s->ctx, (long long)s->f0.size()));
     std::vector<long long> hidx(n_old); std::vector<double> hshift(n_old); std::vector<int> hvo(n_old);
     for (long long i = 0; i < n_old; ++i) { hidx[i] = s->live[i].idx; hshift[i] = s->live[i].shift; hvo[i] = s->live[i].voiced; }
     if (n_old) {
-        RT_TRY(rt::h2d(s->d_pidx, hidx.data(), n_old * sizeof(long long), st));
-        RT_TRY(rt::h2d(s->d_pshift, hshift.data(), n_old * sizeof(double), st));
-        RT_TRY(rt::h2d(s->d_pvoiced, hvo.data(), n_old * sizeof(int), st));
+        RT_TRY(rt::h2d(s->d_pidx.ptr(), hidx.data(), n_old * sizeof(long long), st));
+        RT_TRY(rt::h2d(s->d_pshift.ptr(), hshift.data(), n_old * sizeof(double), st));
+        RT_TRY(rt::h2d(s->d_pvoiced.ptr(), hvo.data(), n_old * sizeof(int), st));
     }
-    RT_TRY(rt::h2d(s->d_f0, s->f0.data(), s->f0.size() * sizeof(double), st));
+    RT_TRY(rt::h2d(s->d_f0.ptr(), s->f0.data(), s->f0.size() * sizeof(double), st));
     RT_TRY(rt::stream_sync(st));                                   // hidx / hshift / hvo are reused below
     SynthScanState hs;
     long long total = n_old;
@@ -171,8 +144,8 @@ int advance(ry_synth* s, bool final, double* y, long long y_capacity, long long*
         const int n_old_i = (int)n_old;
         RT_TRY(rt::h2d(&s->st->n_pulses, &n_old_i, sizeof(int), st));
         SynthScanParams sp;
-        sp.f0 = s->d_f0; sp.frame0 = s->frame0; sp.last_frame = m - 1; sp.n0 = s->scanned; sp.n1 = k1; sp.spf = s->spf; sp.fs = (double)s->fs;
-        sp.st = s->st; sp.pidx = s->d_pidx; sp.pshift = s->d_pshift; sp.pvoiced = s->d_pvoiced; sp.cap = (int)s->cap_p;
+        sp.f0 = s->d_f0.ptr(); sp.frame0 = s->frame0; sp.last_frame = m - 1; sp.n0 = s->scanned; sp.n1 = k1; sp.spf = s->spf; sp.fs = (double)s->fs;
+        sp.st = s->st; sp.pidx = s->d_pidx.ptr(); sp.pshift = s->d_pshift.ptr(); sp.pvoiced = s->d_pvoiced.ptr(); sp.cap = (int)s->d_pidx.cap;
         RY_LAUNCH(synth_scan, dim3(1), 256, st, sp);
         RT_TRY(rt::last_error());
         RT_TRY(rt::d2h(&hs, s->st, sizeof hs, st));
@@ -182,9 +155,9 @@ int advance(ry_synth* s, bool final, double* y, long long y_capacity, long long*
         const long long added = total - n_old;
         if (added > 0) {
             hidx.resize(added); hshift.resize(added); hvo.resize(added);
-            RT_TRY(rt::d2h(hidx.data(), s->d_pidx + n_old, added * sizeof(long long), st));
-            RT_TRY(rt::d2h(hshift.data(), s->d_pshift + n_old, added * sizeof(double), st));
-            RT_TRY(rt::d2h(hvo.data(), s->d_pvoiced + n_old, added * sizeof(int), st));
+            RT_TRY(rt::d2h(hidx.data(), s->d_pidx.ptr() + n_old, added * sizeof(long long), st));
+            RT_TRY(rt::d2h(hshift.data(), s->d_pshift.ptr() + n_old, added * sizeof(double), st));
+            RT_TRY(rt::d2h(hvo.data(), s->d_pvoiced.ptr() + n_old, added * sizeof(int), st));
             RT_TRY(rt::stream_sync(st));
             for (long long i = 0; i < added; ++i) {
                 ry_synth::Pulse p = {hidx[i], hshift[i], hvo[i]};
@@ -201,20 +174,20 @@ int advance(ry_synth* s, bool final, double* y, long long y_capacity, long long*
     const long long n_emit = fin - s->done;
     if (n_emit > 0) {
         if (complete > 0) {
-            RY_TRY(grow(s, &s->d_resp, &s->cap_resp, complete * SYNTH_FFT));
+            RY_TRY(s->d_resp.grow(s->ctx, complete * SYNTH_FFT));
             SynthPulseParams pp;
-            pp.pidx = s->d_pidx; pp.pshift = s->d_pshift; pp.pvoiced = s->d_pvoiced; pp.n_pulses = (int)total; pp.n_complete = (int)complete;
+            pp.pidx = s->d_pidx.ptr(); pp.pshift = s->d_pshift.ptr(); pp.pvoiced = s->d_pvoiced.ptr(); pp.n_pulses = (int)total; pp.n_complete = (int)complete;
             pp.sp = s->sp[s->cur]; pp.ap = s->ap[s->cur]; pp.frame0 = s->frame0; pp.last_frame = m - 1; pp.spf = s->spf;
-            pp.seed_hash = s->seed_hash; pp.tw = s->tw; pp.dc = s->dc; pp.resp = s->d_resp;
+            pp.seed_hash = s->seed_hash; pp.tw = s->tw; pp.dc = s->dc; pp.resp = s->d_resp.ptr();
             RY_LAUNCH(synth_pulse, dim3((unsigned)complete), 256, st, pp);
             RT_TRY(rt::last_error());
         }
-        RY_TRY(grow(s, &s->d_y, &s->cap_y, n_emit));
+        RY_TRY(s->d_y.grow(s->ctx, n_emit));
         SynthOverlapParams op;
-        op.pidx = s->d_pidx; op.n_complete = (int)complete; op.resp = s->d_resp; op.s0 = s->done; op.s1 = fin; op.y = s->d_y;
+        op.pidx = s->d_pidx.ptr(); op.n_complete = (int)complete; op.resp = s->d_resp.ptr(); op.s0 = s->done; op.s1 = fin; op.y = s->d_y.ptr();
         RY_LAUNCH(synth_overlap, dim3((unsigned)((n_emit + 255) / 256)), 256, st, op);
         RT_TRY(rt::last_error());
-        RT_TRY(rt::d2h(y, s->d_y, (size_t)n_emit * sizeof(double), st));
+        RT_TRY(rt::d2h(y, s->d_y.ptr(), (size_t)n_emit * sizeof(double), st));
         RT_TRY(rt::stream_sync(st));
         s->done = fin;
     }
@@ -249,15 +222,9 @@ int ry_synth_create(ry_ctx* ctx, int fs, double frame_period_ms, int fft_size, u
     RT_TRY(rt::set_device(ctx->device));
     std::unique_ptr<ry_synth> s(new ry_synth());
     s->ctx = ctx; s->fs = fs; s->frame_period = frame_period_ms; s->spf = spf; s->lowest_f0 = (double)fs / fft_size + 1.0;
-    s->seed = seed;
-    unsigned h = seed;                                              // synth_hash32 on the host
-    h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
-    s->seed_hash = h;
-    std::vector<double> tw(2 * SYNTH_FFT), dc(SYNTH_FFT);
-    for (int k = 0; k < SYNTH_FFT; ++k) {
-        tw[2 * k] = std::cos(SYNTH_TWO_PI * k / SYNTH_FFT);
-        tw[2 * k + 1] = std::sin(SYNTH_TWO_PI * k / SYNTH_FFT);
-    }
+    s->seed = seed; s->seed_hash = synth_hash32(seed);
+    const std::vector<double> tw = twiddles(SYNTH_FFT);
+    std::vector<double> dc(SYNTH_FFT);
     double sum = 0;
     for (int i = 0; i < SYNTH_HALF; ++i) {
         dc[i] = 0.5 - 0.5 * std::cos(SYNTH_TWO_PI * (i + 1.0) / (1.0 + SYNTH_FFT));
@@ -265,13 +232,11 @@ int ry_synth_create(ry_ctx* ctx, int fs, double frame_period_ms, int fft_size, u
         sum += 2 * dc[i];
     }
     for (int i = 0; i < SYNTH_FFT; ++i) dc[i] /= sum;
-    RY_TRY(alloc_as(s->tables, &s->tw, (size_t)SYNTH_FFT));
-    RY_TRY(alloc_as(s->tables, &s->dc, (size_t)SYNTH_FFT));
-    RY_TRY(alloc_as(s->tables, &s->st, (size_t)1));
-    RT_TRY(rt::h2d(s->tw, tw.data(), tw.size() * sizeof(double), ctx->stream));
-    RT_TRY(rt::h2d(s->dc, dc.data(), dc.size() * sizeof(double), ctx->stream));
-    RT_TRY(rt::stream_sync(ctx->stream));
-    RY_TRY(reset_device_state(s.get()));
+    SynthScanState z;
+    memset(&z, 0, sizeof z);
+    RY_TRY(upload_table(s->tables, ctx, (const sy_c*)tw.data(), (size_t)SYNTH_FFT, &s->tw));
+    RY_TRY(upload_table(s->tables, ctx, dc.data(), dc.size(), &s->dc));
+    RY_TRY(upload_table(s->tables, ctx, &z, (size_t)1, &s->st));
     *out = s.release();
     return RY_OK;
 }
@@ -284,8 +249,7 @@ void ry_synth_destroy(ry_synth* s) {
 }
 
 int ry_synth_reset(ry_synth* s) {
-    if (!s) return fail(RY_ESTATE, "null synthesizer handle");
-    RT_TRY(rt::set_device(s->ctx->device));
+    RY_TRY(check_handle(s, "synthesizer"));
     reset_stream(s);
     return reset_device_state(s);
 }
@@ -305,7 +269,7 @@ int ry_synth_bound(ry_synth* s, int n_frames, int final) {
 
 int ry_synth_push(ry_synth* s, const double* f0, const float* sp, const float* ap, int n_frames, int bins, int on_device,
                   double* y, int y_capacity, int* n_out) {
-    if (!s) return fail(RY_ESTATE, "null synthesizer handle");
+    RY_TRY(check_handle(s, "synthesizer"));
     if (n_out) *n_out = 0;
     if (!y || !n_out || y_capacity < 0) return fail(RY_EINVAL, "bad output arguments");
     if (bins != SYNTH_BINS) return fail(RY_EINVAL, "%d bins per frame, fft_size / 2 + 1 = %d expected", bins, SYNTH_BINS);
@@ -313,7 +277,6 @@ int ry_synth_push(ry_synth* s, const double* f0, const float* sp, const float* a
     const long long m = s->n_frames + n_frames;
     const long long may = std::max(known_samples(s, m), s->scanned) - s->done;
     if (may > y_capacity) return fail(RY_EINVAL, "y holds %d samples, this push may return up to %lld (ry_synth_bound)", y_capacity, may);
-    RT_TRY(rt::set_device(s->ctx->device));
     RY_TRY(append_frames(s, f0, sp, ap, n_frames, on_device, first_needed_frame(s)));
     long long n = 0;
     RY_TRY(advance(s, false, y, y_capacity, &n));
@@ -322,11 +285,10 @@ int ry_synth_push(ry_synth* s, const double* f0, const float* sp, const float* a
 }
 
 int ry_synth_flush(ry_synth* s, double* y, int y_capacity, int* n_out) {
-    if (!s) return fail(RY_ESTATE, "null synthesizer handle");
+    RY_TRY(check_handle(s, "synthesizer"));
     if (n_out) *n_out = 0;
     if (!y || !n_out || y_capacity < 0) return fail(RY_EINVAL, "bad output arguments");
     if (s->n_frames < 1) return fail(RY_ESTATE, "flush of an empty stream");
-    RT_TRY(rt::set_device(s->ctx->device));
     long long n = 0;
     RY_TRY(advance(s, true, y, y_capacity, &n));
     *n_out = (int)n;
@@ -335,7 +297,7 @@ int ry_synth_flush(ry_synth* s, double* y, int y_capacity, int* n_out) {
 
 int ry_synth_run(ry_synth* s, const double* f0, const float* sp, const float* ap, int n_frames, int bins, int on_device,
                  double* y, int y_capacity, int* n_out) {
-    if (!s) return fail(RY_ESTATE, "null synthesizer handle");
+    RY_TRY(check_handle(s, "synthesizer"));
     if (n_out) *n_out = 0;
     if (!y || !n_out || y_capacity < 0) return fail(RY_EINVAL, "bad output arguments");
     if (bins != SYNTH_BINS) return fail(RY_EINVAL, "%d bins per frame, fft_size / 2 + 1 = %d expected", bins, SYNTH_BINS);
@@ -364,19 +326,11 @@ int ry_synth_debug_pulses(ry_synth* s, long long* index, double* shift, int* voi
 }
 
 int ry_synth_debug_poison(ry_synth* s) {
-    if (!s) return fail(RY_ESTATE, "null synthesizer handle");
+    RY_TRY(check_handle(s, "synthesizer"));
     const ry_stream_t st = s->ctx->stream;
-    RT_TRY(rt::set_device(s->ctx->device));
     RT_TRY(rt::stream_sync(st));
     // every scratch buffer and the set of the frame window that is not in use: all bits set (NaN as a float or a double, -1 as an index)
-    if (s->d_f0) RT_TRY(rt::dmemset(s->d_f0, 0xff, (size_t)s->cap_f0 * sizeof(double), st));
-    if (s->d_pidx) {
-        RT_TRY(rt::dmemset(s->d_pidx, 0xff, (size_t)s->cap_p * sizeof(long long), st));
-        RT_TRY(rt::dmemset(s->d_pshift, 0xff, (size_t)s->cap_p * sizeof(double), st));
-        RT_TRY(rt::dmemset(s->d_pvoiced, 0xff, (size_t)s->cap_p * sizeof(int), st));
-    }
-    if (s->d_resp) RT_TRY(rt::dmemset(s->d_resp, 0xff, (size_t)s->cap_resp * sizeof(double), st));
-    if (s->d_y) RT_TRY(rt::dmemset(s->d_y, 0xff, (size_t)s->cap_y * sizeof(double), st));
+    for (DevBufBase* b : s->scratch) RY_TRY(b->poison(st));
     const int idle = 1 - s->cur;
     if (s->sp[idle]) {
         RT_TRY(rt::dmemset(s->sp[idle], 0xff, (size_t)s->win_cap[idle] * SYNTH_BINS * sizeof(float), st));

@@ -27,17 +27,13 @@ from typing import Optional
 import numpy
 
 from . import _lib, sptk
+from ._handle import DeviceHandle, EngineForTests, _dptr
 from .world_synth import BINS, FFT_SIZE, DeviceRows, _DeviceBuffer, cheaptrick_fft_size
 
-_DP = ctypes.POINTER(ctypes.c_double)
 _LLP = ctypes.POINTER(ctypes.c_longlong)
 
 
-def _dptr(a):
-    return a.ctypes.data_as(_DP) if a is not None else ctypes.cast(ctypes.c_void_p(0), _DP)
-
-
-class Analyzer(object):
+class Analyzer(DeviceHandle):
     """CheapTrick + sp2mc on the device (`ry_analysis_*`): one workgroup per frame, stateless.  `ctx` (tests): a context over another build of
     the library."""
 
@@ -48,28 +44,14 @@ class Analyzer(object):
         self.order = int(order)
         self.alpha = float(sptk.mcepalpha(self.fs) if alpha is None else alpha)
         self.q1, self.f0_floor, self.seed = float(q1), float(f0_floor), int(seed) & 0xffffffff
-        self.device = int(os.environ.get('RY_DEVICE', '0')) if device is None else int(device)
-        self._given_ctx = ctx
-        self._ctx = None
-        self._handle = None
-        self._pid = None
+        DeviceHandle.__init__(self, ctx, device)
 
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d.update(_handle=None, _pid=None, _ctx=None, _given_ctx=None)
-        return d
+    _destroy = 'ry_analysis_destroy'
 
-    def _get(self):
-        if self._handle is None or self._pid != os.getpid():
-            from . import engine
-            given = self._given_ctx is not None and self._given_ctx.pid == os.getpid()
-            self._ctx = self._given_ctx if given else engine.get_context(self.device)
-            lib = self._ctx.lib
-            h = ctypes.c_void_p()
-            lib.check(lib.dll.ry_analysis_create(self._ctx.handle, self.fs, self.fft_size, self.order, self.alpha, self.q1, self.f0_floor, self.seed,
-                                                 ctypes.byref(h)))
-            self._handle, self._pid = h, os.getpid()
-        return self._ctx.lib, self._handle
+    def _create(self, lib, ctx):
+        h = ctypes.c_void_p()
+        lib.check(lib.dll.ry_analysis_create(ctx.handle, self.fs, self.fft_size, self.order, self.alpha, self.q1, self.f0_floor, self.seed, ctypes.byref(h)))
+        return h
 
     def bands(self) -> int:
         """The number of D4C bands at this rate (columns of `coded_ap`): 1 at 16 kHz, 3 at 24 kHz."""
@@ -170,22 +152,9 @@ class Analyzer(object):
         lib, h = self._get()
         lib.check(lib.dll.ry_analysis_debug_poison(h))
 
-    def close(self):
-        if self._handle is not None and self._pid == os.getpid() and self._ctx is not None and self._ctx.handle is not None:
-            self._ctx.lib.dll.ry_analysis_destroy(self._handle)
-        self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- the packages' functions ---------------------------------------------------------------------------------------------------------
-class engine_for_tests(object):
-    """tests: `ctx`, a context over another build of the library (the emulator), for the analyzers the functions below create."""
-    ctx = None
+engine_for_tests = EngineForTests()           # for the analyzers the functions below create
 
 
 _analyzers = {}

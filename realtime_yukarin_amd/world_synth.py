@@ -21,10 +21,10 @@ from typing import Optional
 import numpy
 
 from . import _lib
+from ._handle import _DP, DeviceHandle, EngineForTests
 
 FFT_SIZE = 1024
 BINS = FFT_SIZE // 2 + 1
-_DP = ctypes.POINTER(ctypes.c_double)
 
 
 def cheaptrick_fft_size(fs, f0_floor: float = 71.0) -> int:
@@ -39,7 +39,7 @@ class DeviceRows(object):
         self.shape = (self.frames, BINS)
 
 
-class Synthesizer(object):
+class Synthesizer(DeviceHandle):
     """WORLD synthesis on the device (`ry_synth_*`).  One-shot `synthesize`, or a stream: `push` returns the samples that can no longer
     change (it lags the input by about fft_size / 2 samples + one frame + one pulse period), `flush` the rest; the concatenation equals
     `synthesize` on the concatenated frames bit for bit, for any cut.  `ctx` (tests): a context over another build of the library."""
@@ -47,27 +47,14 @@ class Synthesizer(object):
     def __init__(self, fs: int, frame_period: float = 5.0, seed: int = 0, ctx=None, device: Optional[int] = None):
         self.fs, self.frame_period, self.seed = int(fs), float(frame_period), int(seed) & 0xffffffff
         self.fft_size = cheaptrick_fft_size(self.fs)
-        self.device = int(os.environ.get('RY_DEVICE', '0')) if device is None else int(device)
-        self._given_ctx = ctx
-        self._ctx = None
-        self._handle = None
-        self._pid = None
+        DeviceHandle.__init__(self, ctx, device)
 
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d.update(_handle=None, _pid=None, _ctx=None, _given_ctx=None)
-        return d
+    _destroy = 'ry_synth_destroy'
 
-    def _get(self):
-        if self._handle is None or self._pid != os.getpid():
-            from . import engine
-            given = self._given_ctx is not None and self._given_ctx.pid == os.getpid()
-            self._ctx = self._given_ctx if given else engine.get_context(self.device)
-            lib = self._ctx.lib
-            h = ctypes.c_void_p()
-            lib.check(lib.dll.ry_synth_create(self._ctx.handle, self.fs, self.frame_period, self.fft_size, self.seed, ctypes.byref(h)))
-            self._handle, self._pid = h, os.getpid()
-        return self._ctx.lib, self._handle
+    def _create(self, lib, ctx):
+        h = ctypes.c_void_p()
+        lib.check(lib.dll.ry_synth_create(ctx.handle, self.fs, self.frame_period, self.fft_size, self.seed, ctypes.byref(h)))
+        return h
 
     # ---- arguments
     @staticmethod
@@ -152,17 +139,6 @@ class Synthesizer(object):
         """What `push` holds back at most: half a transform, one frame, one pulse period (of `f0`; 500 Hz: unvoiced)."""
         return self.fft_size // 2 + int(numpy.ceil(self.fs * self.frame_period / 1000)) + int(numpy.ceil(self.fs / f0))
 
-    def close(self):
-        if self._handle is not None and self._pid == os.getpid() and self._ctx is not None and self._ctx.handle is not None:
-            self._ctx.lib.dll.ry_synth_destroy(self._handle)
-        self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class _DeviceBuffer(object):
     """A `ry_dev_alloc` buffer that frees itself."""
@@ -203,9 +179,7 @@ def device_spectrogram(sp):
 
 
 # ---- the reference's methods ---------------------------------------------------------------------------------------------------------
-class engine_for_tests(object):
-    """tests: `ctx`, a context over another build of the library (the emulator), for the synthesizers the bindings below create."""
-    ctx = None
+engine_for_tests = EngineForTests()           # for the synthesizers the bindings below create
 
 
 def _new_synth(vocoder) -> Synthesizer:
