@@ -324,7 +324,9 @@ int ry_net_debug_activation(ry_net* net, int layer, int kind, void* out, size_t 
  * fft_size: 1024 (CheapTrick's size at 16 and 24 kHz) -- anything else is refused.  Frames: f0 [n_frames] float64 on the HOST (Hz; below
  * fs / fft_size + 1 = unvoiced), sp / ap [n_frames][bins] float32 with bins = fft_size / 2 + 1, host pointers or, with on_device = 1, device
  * pointers on the context's GPU (the rows stage 2 leaves there).  y: float64 samples on the HOST; every call returns after its samples are
- * in y.  Refused: n_frames < 1, bins != fft_size / 2 + 1, a y too small, f0 that is not finite. */
+ * in y.  Domain: 8000 <= fs <= 48000, fs * frame_period_ms / 1000 >= 1 (a frame is at least one sample), f0 finite and below fs / 2 (negative:
+ * unvoiced).  Refused: a rate or a frame period outside that, n_frames < 1, bins != fft_size / 2 + 1, a y too small, f0 that is not finite or
+ * not below fs / 2 (a phase step of 2 pi or more per sample has no pulse train). */
 typedef struct ry_synth ry_synth;
 int ry_synth_create(ry_ctx* ctx, int fs, double frame_period_ms, int fft_size, unsigned seed, ry_synth** out);
 void ry_synth_destroy(ry_synth* synth);
@@ -353,11 +355,13 @@ int ry_synth_debug_poison(ry_synth* synth);
 /* ---- WORLD analysis that feeds the networks (`pyworld.cheaptrick(x, f0, t, fs)` and `pysptk.sp2mc(sp, order, alpha)` in the reference's
  * AcousticFeature.extract, reached from Vocoder.encode).  Semantics: INTEGRATION.md section 11 and tests/world_analysis_ref.py (CheapTrick
  * and sp2mc restated; WORLD's two randn() terms are counter-based functions of (seed, centre sample, index), so a frame's rows depend on
- * (x, f0, t, seed) only).  fft_size: 1024 -- anything else is refused; order: 0 .. 63.  x [x_len] float64, f0 [n] (Hz; at or below
+ * (x, f0, t, seed) only).  fft_size: 1024 -- anything else is refused; 8000 <= fs <= 48000; order: 0 .. 63; -0.9 <= alpha <= 0.9;
+ * -0.4 <= q1 <= 0; 1 <= f0_floor <= 1000 (Hz) -- outside: refused at ry_analysis_create.  x [x_len] float64, f0 [n] (Hz; at or below
  * max(f0_floor, 3 fs / (fft_size - 3)) = unvoiced, analysed at 500 Hz) and t [n] (seconds) float64, all on the HOST.  Outputs, any may be
  * null: sp64_out [n][513] float64 and mc_out [n][order + 1] float64 on the HOST, sp32_dev_out [n][513] float32 on the DEVICE (the rows
  * ry_synth_* and stage 2 read; = (float)sp64, left on the card).  The call returns after everything is written.  n = 0 or x_len = 0: success,
- * nothing written.  Refused: n < 0, x_len < 0, a null wave / f0 / t with n > 0, f0 or t that is not finite, f0 >= fs / 2. */
+ * nothing written.  Refused: n < 0, x_len < 0, a null wave / f0 / t with n > 0, f0 that is not finite, f0 >= fs / 2, t outside -1 .. 1e6 s
+ * (CheapTrick and D4C alike). */
 typedef struct ry_analysis ry_analysis;
 int ry_analysis_create(ry_ctx* ctx, int fs, int fft_size, int order, double alpha, double q1, double f0_floor, unsigned seed, ry_analysis** out);
 void ry_analysis_destroy(ry_analysis* analysis);

@@ -108,8 +108,7 @@ int run_frames(ry_analysis* s, const double* x, long long x_len, const double* f
     if (!f0 || !t) return fail(RY_EINVAL, "null f0 / t");
     for (int i = 0; i < n; ++i) {
         if (!std::isfinite(f0[i]) || !(f0[i] < 0.5 * s->fs)) return fail(RY_EINVAL, "f0[%d] = %g: finite and below fs / 2", i, f0[i]);
-        if (!std::isfinite(t[i]) || std::fabs(t[i]) > 1e9) return fail(RY_EINVAL, "t[%d] = %g", i, t[i]);
-        if (o.d4c && t[i] < -1.0) return fail(RY_EINVAL, "t[%d] = %g: D4C takes frames from -1 s on", i, t[i]);
+        if (!(t[i] >= -1.0 && t[i] <= 1e6)) return fail(RY_EINVAL, "t[%d] = %g: -1 .. 1e6 s", i, t[i]);
     }
     const ry_stream_t st = s->ctx->stream;
     RY_TRY(s->d_x.grow(s->ctx, x_len));
@@ -175,8 +174,9 @@ int ry_analysis_create(ry_ctx* ctx, int fs, int fft_size, int order, double alph
     if (fs < 8000 || fs > 48000) return fail(RY_EINVAL, "sampling rate %d", fs);
     if (fft_size != SYNTH_FFT) return fail(RY_EINVAL, "fft_size %d: the transforms are built for %d (CheapTrick's size at 16 and 24 kHz)", fft_size, SYNTH_FFT);
     if (order < 0 || order + 1 > ANALYSIS_MAX_MC) return fail(RY_EINVAL, "order %d: 0 .. %d", order, ANALYSIS_MAX_MC - 1);
-    if (!(std::fabs(alpha) < 1.0)) return fail(RY_EINVAL, "alpha %g", alpha);
-    if (!std::isfinite(q1) || !std::isfinite(f0_floor)) return fail(RY_EINVAL, "q1 %g / f0_floor %g", q1, f0_floor);
+    if (!(std::fabs(alpha) <= 0.9)) return fail(RY_EINVAL, "alpha %g: -0.9 .. 0.9", alpha);
+    if (!(q1 >= -0.4 && q1 <= 0.0)) return fail(RY_EINVAL, "q1 %g: -0.4 .. 0", q1);
+    if (!(f0_floor >= 1.0 && f0_floor <= 1000.0)) return fail(RY_EINVAL, "f0_floor %g: 1 .. 1000 Hz", f0_floor);
     RT_TRY(rt::set_device(ctx->device));
     std::unique_ptr<ry_analysis> s(new ry_analysis());
     s->ctx = ctx; s->fs = fs; s->order = order; s->alpha = alpha; s->q1 = q1;

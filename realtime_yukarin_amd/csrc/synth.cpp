@@ -59,8 +59,7 @@ int check_frames(const ry_synth* s, const double* f0, const float* sp, const flo
     if (n_frames < 1) return fail(RY_EINVAL, "n_frames = %d: at least one frame", n_frames);
     if (n_frames > (1 << 22)) return fail(RY_EINVAL, "%d frames in one call", n_frames);
     for (int i = 0; i < n_frames; ++i)
-        if (!std::isfinite(f0[i])) return fail(RY_EINVAL, "f0[%d] is not finite", i);
-    (void)s;
+        if (!std::isfinite(f0[i]) || !(f0[i] < 0.5 * s->fs)) return fail(RY_EINVAL, "f0[%d] = %g: finite and below fs / 2", i, f0[i]);
     return RY_OK;
 }
 
@@ -214,7 +213,7 @@ int ry_synth_create(ry_ctx* ctx, int fs, double frame_period_ms, int fft_size, u
     if (!out) return fail(RY_EINVAL, "null out pointer");
     *out = nullptr;
     if (!ctx) return fail(RY_EINVAL, "null context");
-    if (fs < 1000 || fs > 384000) return fail(RY_EINVAL, "sampling rate %d", fs);
+    if (fs < 8000 || fs > 48000) return fail(RY_EINVAL, "sampling rate %d: 8000 .. 48000", fs);
     if (!(frame_period_ms > 0) || !std::isfinite(frame_period_ms)) return fail(RY_EINVAL, "frame period %g ms", frame_period_ms);
     if (fft_size != SYNTH_FFT) return fail(RY_EINVAL, "fft_size %d: the transforms are built for %d (CheapTrick's size at 16 and 24 kHz)", fft_size, SYNTH_FFT);
     const double spf = fs * frame_period_ms / 1000;

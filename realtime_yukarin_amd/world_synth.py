@@ -42,11 +42,13 @@ class DeviceRows(object):
 class Synthesizer(DeviceHandle):
     """WORLD synthesis on the device (`ry_synth_*`).  One-shot `synthesize`, or a stream: `push` returns the samples that can no longer
     change (it lags the input by about fft_size / 2 samples + one frame + one pulse period), `flush` the rest; the concatenation equals
-    `synthesize` on the concatenated frames bit for bit, for any cut.  `ctx` (tests): a context over another build of the library."""
+    `synthesize` on the concatenated frames bit for bit, for any cut.  `fft_size=None` is CheapTrick's size at `fs`; the kernels are built for
+    1024, so rates other than 16 to 24 kHz (8 .. 48 kHz are accepted) need `fft_size=1024` rows.  `ctx` (tests): a context over another build
+    of the library."""
 
-    def __init__(self, fs: int, frame_period: float = 5.0, seed: int = 0, ctx=None, device: Optional[int] = None):
+    def __init__(self, fs: int, frame_period: float = 5.0, seed: int = 0, ctx=None, device: Optional[int] = None, fft_size: Optional[int] = None):
         self.fs, self.frame_period, self.seed = int(fs), float(frame_period), int(seed) & 0xffffffff
-        self.fft_size = cheaptrick_fft_size(self.fs)
+        self.fft_size = int(fft_size) if fft_size else cheaptrick_fft_size(self.fs)
         DeviceHandle.__init__(self, ctx, device)
 
     _destroy = 'ry_synth_destroy'

@@ -89,3 +89,62 @@ def test_the_longdouble_transform_is_a_transform():
     a = numpy.random.default_rng(1).normal(size=1024)
     got = R.fft_any(a.astype(numpy.longdouble), numpy.longdouble)
     assert numpy.abs(got - numpy.fft.fft(a)).max() <= 1e-11
+
+
+# ---- the inputs at the edges of the domain (tests/world_domain_cases.py, run by tests/test_world_domain_*.py) ----
+import world_domain_cases as DC
+
+DEFAULT_F0 = 500.0
+DOMAIN_FRAMES = sorted(set(DC.FRAMES_GPU) | set(DC.FRAMES_EMU))
+
+
+def _margins(f0_k, t_k, fs, floor):
+    """`rounding_margins`, with the exception of the first test of this file: a 500 Hz frame whose f0 fft_size / fs is a whole number in integers."""
+    m = list(R.rounding_margins(f0_k, t_k, fs, 1024, floor))
+    used = R.frame_integers(f0_k, t_k, fs, 1024, floor)[0]
+    if m[2] < 1e-6 and used == DEFAULT_F0 and exact(500 * 1024, fs):
+        m[2] = numpy.inf
+    return m
+
+
+@pytest.mark.parametrize('fs', DC.RATES)
+@pytest.mark.parametrize('kind', DC.TRACKS)
+def test_every_domain_frame_is_clear_of_its_rounding_flips(fs, kind):
+    """The same condition, the same 1e-6, on the `lowest` / `high` / `offgrid` frames at every rate, none excluded."""
+    worst = [numpy.inf] * 4
+    for n in DOMAIN_FRAMES:
+        for a, b in zip(DC.f0_track(kind, n, fs), DC.times(kind, n)):
+            worst = [min(p, q) for p, q in zip(worst, _margins(a, b, fs, DC.FLOOR))]
+    print(fs, kind, worst)
+    assert min(worst) >= 1e-6, worst
+
+
+@pytest.mark.parametrize('floor', DC.FLOORS + (DC.FLOOR,))
+def test_the_glide_frames_are_clear_of_their_flips_at_the_other_floors(floor):
+    for n in DOMAIN_FRAMES:
+        for a, b in zip(C.f0_track('glide', n), C.times(n)):
+            assert min(_margins(a, b, 16000, floor)) >= 1e-6
+
+
+@pytest.mark.parametrize('fs', DC.RATES)
+def test_the_domain_tracks_reach_the_bounds_they_are_there_for(fs):
+    floor = R.effective_floor(fs, 1024, DC.FLOOR)
+    for n in DOMAIN_FRAMES:
+        low = [R.frame_integers(f, 0.0, fs, 1024, DC.FLOOR) for f in DC.f0_track('lowest', n, fs)]
+        assert all(v[0] != 500.0 and v[0] < floor * 1.002 for v in low)                         # voiced, within 0.2 % of the floor in force
+        if fs >= 16000:
+            assert all(2 * v[1] + 1 == 1021 for v in low)                                       # the longest window there is
+        f0, h, centre, L, b, u = R.frame_integers(DC.f0_track('high', n, fs)[0], 0.0, fs, 1024, DC.FLOOR)
+        assert f0 < 0.5 * fs and f0 * 1024 / fs > 511.5 and L == 511 and b == 342 and 513 + 2 * b <= 1280
+        t = DC.times('offgrid', n)
+        assert t[0] == -1.0 and t.min() >= -1.0 and t.max() <= 1e6 and (n < 2 or t[-1] == 1e6)
+    t = DC.times('offgrid', 13)
+    assert (t[1:3] < 0).all() and t[1:].min() > -0.013 and (t[-3:] > 3.0).all()
+    assert numpy.abs((t[1:-3] / C.FRAME_PERIOD) % 1 - 0.5).max() < 0.5                          # off the 5 ms grid
+    assert max(abs(a) for a in DC.ALPHAS) == 0.9 and min(DC.Q1) == -0.4 and max(DC.Q1) == 0.0 and set(DC.ORDERS) >= {0, 63}
+
+
+def test_sp2mc_rows_is_sp2mc_bit_for_bit():
+    for order, alpha in ((0, 0.0), (1, -0.9), (8, 0.41), (63, 0.9)):
+        sp = DC.sp2mc_rows(order, alpha)[:3]
+        assert numpy.array_equal(R.sp2mc_rows(sp, order, alpha), R.sp2mc(sp, order, alpha))

@@ -82,3 +82,45 @@ def test_rounding_and_noise_keys():
     x, f0, t = C.case('zeros', 'alternating', 12, 16000)
     a, b = R.d4c(x, f0, t, 16000, seed=1, details=True), R.d4c(x, f0, t, 16000, seed=2, details=True)
     assert numpy.isfinite(a[0]).all() and not numpy.array_equal(a[1], b[1])     # the noise term is live
+
+
+# ---- the inputs at the edges of the domain (tests/world_domain_cases.py, run by tests/test_world_domain_*.py) ----
+import world_domain_cases as DC
+
+DOMAIN_FRAMES = sorted(set(DC.FRAMES_GPU) | set(DC.FRAMES_EMU))
+
+
+@pytest.mark.parametrize('fs', DC.D4C_RATES)
+@pytest.mark.parametrize('kind', DC.D4C_TRACKS)
+def test_every_domain_frame_is_clear_of_its_rounding_flips(fs, kind):
+    worst = [numpy.inf] * 7
+    for n in DOMAIN_FRAMES:
+        for a, b in zip(DC.f0_track(kind, n, fs), DC.times(kind, n)):
+            worst = [min(p, q) for p, q in zip(worst, R.rounding_margins(a, b, fs))]
+    print(fs, kind, worst)
+    assert min(worst) >= D.MARGIN, worst
+
+
+@pytest.mark.parametrize('fs', DC.D4C_RATES)
+@pytest.mark.parametrize('wk', DC.WAVES)
+def test_every_domain_frame_is_clear_of_the_threshold(fs, wk):
+    worst = numpy.inf
+    for tk in DC.D4C_TRACKS:
+        for n in DOMAIN_FRAMES:
+            x, f0, t = DC.case(wk, tk, n, fs)
+            for a, b in zip(f0, t):
+                worst = min(worst, abs(float(R.love_train(x, a, b, fs, seed=DC.SEED)) - DC.threshold(tk)))
+    print(fs, wk, 'closest |a0 - threshold|', worst)
+    assert worst >= D.MARGIN, worst
+
+
+@pytest.mark.parametrize('fs', DC.D4C_RATES)
+def test_the_domain_tracks_reach_the_bounds_they_are_there_for(fs):
+    h3, h4, om, oc, op, L, b1, b2 = R.frame_integers(DC.f0_track('high', 1, fs)[0], 0.0, fs)
+    assert (L, b1, b2) == (1023, 1024, 512) and 1025 + 2 * b1 == 3073
+    low = DC.f0_track('lowest47', 13, fs)
+    assert (low[0::2] > 47.0).all() and (low[0::2] < 47.1).all() and (low[1::2] > 40.0).all() and (low[1::2] < 47.0).all()
+    assert 2 * R.frame_integers(low[1], 0.0, 24000)[1] + 1 == 2043                              # of 2048
+    on = [R.d4c(*DC.case('glide', tk, 13, fs), fs, threshold=DC.threshold(tk), seed=DC.SEED, details=True)[2] for tk in DC.D4C_TRACKS]
+    print(fs, 'frames on:', [int(o.sum()) for o in on])
+    assert sum(int(o.sum()) for o in on) >= 13 and on[1][0] and not on[1].all()                                  # the general body is live, at the top of `high` too

@@ -131,3 +131,52 @@ def test_gpu_tracks_keep_clear_of_the_wrap_threshold(kind, fs):
         assert not all(p[2] for p in pulses) and (cf0 == 0).any()
     if kind == 'above':
         assert (cf0 > 0).all()
+
+
+# ---- the inputs at the edges of the domain (tests/world_domain_cases.py, run by tests/test_world_domain_*.py) ----
+import world_domain_cases as DC
+
+
+@pytest.mark.parametrize('fs,fp', DC.CONFIGS)
+@pytest.mark.parametrize('kind', DC.SYNTH_TRACKS)
+def test_domain_tracks_keep_clear_of_the_wrap_threshold(kind, fs, fp):
+    """Every (track, rate, frame period, frame count) tests/test_world_domain_*.py runs: no wrap decision within 1e-9 rad of 2 pi, none excluded."""
+    spf = fs * fp / 1000
+    for n in sorted(set(DC.SYNTH_FRAMES_GPU) | set(DC.SYNTH_FRAMES_EMU)):
+        n = DC.synth_frames(n, fs, fp)
+        f0 = DC.synth_f0(kind, n, fs)
+        assert (f0 < 0.5 * fs).all()
+        cf0 = R.coarse_f0(f0, fs, 1024)
+        f, v = R.sample_f0(cf0, 0, R.y_length(n, fs, fp), fs, fp, n - 1)
+        scan = R.PulseScan(fs)
+        pulses = scan.feed(f, v)
+        assert scan.min_margin > 1e-9, (n, scan.min_margin)
+        if n >= 40:
+            assert len(pulses) >= 2
+            if kind == 'high':
+                assert {2, 3} <= set(numpy.diff([p[0] for p in pulses]).tolist())
+            if kind == 'below':
+                assert (cf0 == 0).any() and (cf0 != 0).any()
+            if kind == 'above':
+                assert (cf0 > 0).all()
+    assert DC.synth_frames(12, 16000, 0.0625) == 881 == R.y_length(12, 16000, 5.0) and spf >= 1.0
+
+
+@pytest.mark.parametrize('fs,fp', DC.CONFIGS)
+def test_the_restated_stream_equals_one_shot_at_inexact_frame_lengths(fs, fp):
+    n = DC.synth_frames(12, fs, fp)
+    f0, sp, ap = DC.synth_case('glide', n, fs)
+    want = R.synthesize(f0, sp, ap, fs, fp, seed=9, fft_size=1024)
+    for cuts in ([1] * n, [5, n - 5]):
+        s = R.Stream(fs, fp, seed=9, fft_size=1024)
+        out, i = [], 0
+        for c in cuts:
+            out.append(s.push(f0[i:i + c], sp[i:i + c], ap[i:i + c]))
+            i += c
+        out.append(s.flush())
+        assert numpy.array_equal(numpy.concatenate(out), want)
+
+
+def test_a_frame_count_whose_last_sample_wraps_exists():
+    n = DC.frames_ending_on_a_wrap()
+    assert 200 <= n < 232 and R.y_length(n, 16000, 0.0625) == n

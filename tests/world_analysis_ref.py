@@ -202,3 +202,25 @@ def sp2mc(sp, order, alpha, dtype=numpy.float64, all_values=False):
         c[0] = c[0] / 2
         out[k] = freqt(c if all_values else c[:sp.shape[1]], order, alpha)
     return out
+
+
+def sp2mc_rows(sp, order, alpha, dtype=numpy.float64):
+    """`sp2mc` with the frames as the vector axis: per frame the same operations in the same order (the same bits; tests/test_world_analysis_ref.py),
+    for the case sets whose recursion in plain Python would take minutes (order 63 over hundreds of rows)."""
+    sp = numpy.atleast_2d(sp)
+    ft = numpy.dtype(dtype).type
+    lg = numpy.log(sp.astype(dtype))
+    n = 2 * (sp.shape[1] - 1)
+    c = (fft_any(numpy.concatenate([lg, lg[:, -2:0:-1]], axis=1), dtype).real / n).astype(dtype)[:, :sp.shape[1]]
+    c[:, 0] = c[:, 0] / 2
+    a = ft(alpha)
+    beta = ft(1) - a * a
+    g = [numpy.zeros(sp.shape[0], dtype) for _ in range(order + 1)]
+    for i in range(c.shape[1] - 1, -1, -1):
+        d = list(g)
+        g[0] = c[:, i] + a * d[0]
+        if order >= 1:
+            g[1] = beta * d[0] + a * d[1]
+        for j in range(2, order + 1):
+            g[j] = d[j - 1] + a * (d[j] - g[j - 1])
+    return numpy.stack(g, axis=1)
