@@ -266,6 +266,13 @@ typedef struct ry_crepe ry_crepe;
 size_t ry_crepe_param_count(int capacity);         /* 0 (and ry_last_error) for a bad capacity */
 int ry_crepe_create(ry_ctx* ctx, int capacity, const float* weights, size_t n_floats, float bn_eps, ry_crepe** out);
 void ry_crepe_destroy(ry_crepe* crepe);
+/* The arithmetic of the seven GEMMs (conv1 .. conv6, dense), numbered as ry_net_set_dtype: 0 (default) fp32 MFMA; 2 split-bf16 -- every fp32
+ * product x w runs as x_lo w_hi + x_hi w_lo + x_hi w_hi on the bf16 MFMA with fp32 accumulation (hi = bf16(v), lo = bf16(v - hi)): fp32-class
+ * results (bars: INTEGRATION.md section 9), not the bits of mode 0.  Activations stay fp32 in memory; the filters are split into two bf16 planes
+ * on the device at the first switch to 2 and kept until ry_crepe_destroy.  May be called between calls; back in 0 the results have the bits of a
+ * handle that never switched.  Framing, resampling and the decode do not depend on it.  Refused (RY_EINVAL, the handle keeps its mode): 1 (there is
+ * no plain bf16 form) and every other value. */
+int ry_crepe_set_dtype(ry_crepe* crepe, int dtype);
 /* audio16k: float32 samples at 16 kHz.  Frames: 1 + (n_samples + (center ? 1024 : 0) - 1024) / hop, each 1024 samples from
  * frame * hop - (center ? 512 : 0), mean / std normalised (std clamped at 1e-10).  f0 [frames] (Hz, 0 where the average is undefined),
  * confidence [frames] (max of the activation), activation [frames][360] (may be null).  viterbi = 1: the 360-state Viterbi path;
@@ -305,7 +312,7 @@ int ry_crepe_debug_layer(ry_crepe* crepe, int layer, int n_frames, float* out);
  * the samples of the frame rows, the interior rows of every layer's input, logits, split-K slabs, activation, confidence, f0, observations,
  * back-pointers, path and the 16 kHz audio buffer (the resampler's output) -- and leaves the zero padding rows as they are: a later call that reads anything it did not write shows it. */
 int ry_crepe_debug_poison(ry_crepe* crepe);
-/* diagnostics: the split-K count of conv1 .. conv6 and the dense layer (7 ints). */
+/* diagnostics: the split-K count of conv1 .. conv6 and the dense layer (7 ints) in the mode in force (ry_crepe_set_dtype). */
 int ry_crepe_debug_splits(ry_crepe* crepe, int* splits);
 /* tests (the predictors' counterpart of ry_crepe_debug_layer): one buffer of the launch plan that ran last on this handle (ry_net_forward, ry_ac_convert,
  * ry_sr_convert, ry_sr_convert_rows), copied to the host once its stream has drained.  layer -1, kind 0: the convert wrapper's padded input

@@ -59,7 +59,7 @@ ABI_SYMBOLS = (
     'ry_dev_alloc', 'ry_dev_free', 'ry_dev_upload', 'ry_dev_download',
     'ry_crepe_param_count', 'ry_crepe_create', 'ry_crepe_destroy', 'ry_crepe_predict', 'ry_crepe_decode', 'ry_crepe_set_viterbi_tables',
     'ry_crepe_debug_layer', 'ry_crepe_debug_splits', 'ry_crepe_debug_poison',
-    'ry_crepe_set_resampler', 'ry_crepe_resample', 'ry_crepe_predict_sr',
+    'ry_crepe_set_resampler', 'ry_crepe_resample', 'ry_crepe_predict_sr', 'ry_crepe_set_dtype',
     'ry_synth_create', 'ry_synth_destroy', 'ry_synth_length', 'ry_synth_run', 'ry_synth_bound', 'ry_synth_push', 'ry_synth_flush', 'ry_synth_reset',
     'ry_synth_debug_pulses', 'ry_synth_debug_poison',
     'ry_analysis_create', 'ry_analysis_destroy', 'ry_analysis_run', 'ry_analysis_sp2mc', 'ry_analysis_debug_record', 'ry_analysis_debug_ints', 'ry_analysis_debug_poison',
@@ -182,6 +182,7 @@ class Ry355Lib(object):
         d.ry_crepe_predict_sr.argtypes = [_VP, _FP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _FP, _FP, _FP, ctypes.c_int]
         d.ry_crepe_debug_layer.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _FP]
         d.ry_crepe_debug_poison.argtypes = [_VP]
+        d.ry_crepe_set_dtype.argtypes = [_VP, ctypes.c_int]
         d.ry_crepe_debug_splits.argtypes = [_VP, ctypes.POINTER(ctypes.c_int)]
         _CI = ctypes.c_int
         d.ry_synth_create.argtypes = [_VP, _CI, ctypes.c_double, _CI, ctypes.c_uint, ctypes.POINTER(_VP)]

@@ -4,6 +4,7 @@
 `load_model`.  Resampling to 16 kHz, the network, the decode and the Viterbi pass run in libry355 (`ry_crepe_*`); the mono average,
 the float32 cast and `predict_voicing` run on the host.  RY_CREPE_RESAMPLE=host resamples with the host statement of the same
 arithmetic instead (`realtime_yukarin_amd.crepe.resample`: the same bits, far slower); a rate that is not a whole number of Hz always does.
+RY_CREPE_DTYPE=bf16x3 (default f32) runs the network's GEMMs in split-bf16 form (`CrepeModel.set_dtype`); it is read when a model is built.
 
 Weights: `load_model(path, capacity)` or the file named by RY_CREPE_MODEL (`.npz` or torch state dict, keys in INTEGRATION.md
 section 9).  Without either, every call raises: there are no built-in or random weights."""
@@ -43,8 +44,15 @@ def _model(model_capacity):
         if got != m:
             raise RuntimeError('crepe: RY_CREPE_MODEL=%s holds capacity multiplier %d, the call asks for %r (%d)' % (path, got, model_capacity, m))
         _weights[m] = P
-    _models[m] = _crepe.CrepeModel(m, _weights[m])
+    _models[m] = _crepe.CrepeModel(m, _weights[m], dtype=_dtype())
     return _models[m]
+
+
+def _dtype():
+    dtype = os.environ.get('RY_CREPE_DTYPE', 'f32')
+    if dtype not in _crepe.DTYPES:
+        raise RuntimeError('crepe: RY_CREPE_DTYPE=%s (f32 or bf16x3)' % dtype)
+    return dtype
 
 
 def _mono(audio):

@@ -9,6 +9,7 @@ CrepeAcousticFeatureWrapper.extract_f0 calls `crepe.predict(x, fs, viterbi=True,
 trained weights, crepe, resampy or hmmlearn exist to pin it against.
 """
 import ctypes
+import os
 from pathlib import Path
 from typing import Dict, List, Optional, Tuple
 
@@ -36,6 +37,8 @@ VOICING_START = (0.7472, 0.2528)
 VOICING_TRANS = ((0.9991, 0.0009), (0.0025, 0.9975))
 VOICING_MEANS = (0.0795, 0.6278)
 VOICING_VARS = (0.0181, 0.0454)
+# arithmetic of the network's GEMMs (`ry_crepe_set_dtype`, numbered as `ry_net_set_dtype`): fp32 MFMA, or three bf16 products per fp32 product
+DTYPES = {'f32': 0, 'bf16x3': 2}
 
 
 def multiplier(capacity) -> int:
@@ -270,11 +273,13 @@ def predict_voicing(confidence) -> numpy.ndarray:
 class CrepeModel(DeviceHandle):
     """CREPE on the MI355X (`ry_crepe_*`).  Picklable and fork-safe: the GPU context and the device weights are created lazily in the
     process that first predicts; the host copy of the weights travels with the object.  `ctx` (tests) is a context over another build
-    of the library -- the emulator -- used instead of the product's context of `device`."""
+    of the library -- the emulator -- used instead of the product's context of `device`.  `dtype`: 'f32' (default) or 'bf16x3', the
+    split-bf16 form of the GEMMs (`set_dtype`); it travels with the object and is applied to every handle the object creates."""
 
     def __init__(self, capacity='full', params: Optional[Dict[str, numpy.ndarray]] = None, device: Optional[int] = None,
-                 bn_eps: float = BN_EPS, ctx=None, seed: Optional[int] = None):
+                 bn_eps: float = BN_EPS, ctx=None, seed: Optional[int] = None, dtype: str = 'f32'):
         self.m = multiplier(capacity)
+        self.dtype = self._dtype_name(dtype)
         if params is None:
             if seed is None:
                 raise ValueError('CrepeModel needs weights: pass params (load_weights / synthetic_params) or a seed for synthetic ones')
@@ -297,7 +302,24 @@ class CrepeModel(DeviceHandle):
         self._rs = {}
         tabs = [numpy.ascontiguousarray(t, dtype=numpy.float64) for t in viterbi_tables()]
         lib.check(lib.dll.ry_crepe_set_viterbi_tables(h, *[_dptr(t) for t in tabs]))
+        if self.dtype != 'f32':
+            lib.check(lib.dll.ry_crepe_set_dtype(h, DTYPES[self.dtype]))
         return h
+
+    @staticmethod
+    def _dtype_name(dtype) -> str:
+        if dtype not in DTYPES:
+            raise ValueError('unknown CREPE dtype %r (one of %s)' % (dtype, ', '.join(DTYPES)))
+        return dtype
+
+    def set_dtype(self, dtype: str) -> None:
+        """'f32' or 'bf16x3' for the calls that follow (`ry_crepe_set_dtype`).  A handle that exists is switched now; one created later
+        (first use, after unpickling, in a forked child) is created in the mode."""
+        dtype = self._dtype_name(dtype)
+        if self._handle is not None and self._pid == os.getpid():
+            lib, h = self._get()
+            lib.check(lib.dll.ry_crepe_set_dtype(h, DTYPES[dtype]))
+        self.dtype = dtype
 
     def predict16k(self, audio, hop: int, center: bool = True, viterbi: bool = True, activation: bool = True):
         """audio: float32 samples at 16 kHz -> (f0 float32 Hz, confidence float32, activation [frames][360] float32 or None)."""

@@ -4,6 +4,7 @@
 // The frames of a call run in passes of at most CHUNK frames; the activation of every frame is kept for the decode, which runs once.
 // Audio at another rate is resampled to 16 kHz on the device first (crepe_resample; the filter and the time register of each rate are
 // tables the caller installs, ry_crepe_set_resampler).
+// ry_crepe_set_dtype(2) runs the seven GEMMs in split-bf16 form (crepe_igemm_x3) on filters split once into two bf16 planes; everything else is shared.
 #include "crepe_kernels.h"
 #include "ry_host.h"
 
@@ -22,7 +23,9 @@ const int PLAN_WORKGROUPS = 1000;
 struct CLayer {
     int cin = 0, cout = 0, width = 0, stride = 1;
     int lin = 0, lout = 0, K = 0;                   // lout: positions before the pool (dense: 1)
-    int splits = 1;
+    int splits = 1;                                 // split-K count of the fp32 kernel (chunks of CREPE_BK)
+    int splits_x3 = 1;                              // ... of the split-bf16 kernel (chunks of CREPE_X3_BK)
+    size_t w_off = 0;                               // this layer's filters in the bf16 planes w_hi / w_lo (elements)
     int in_fstride = 0, in_rstride = 0;             // input frame stride / window step (floats)
     int out_fstride = 0, out_off = 0;               // pooled output: frame stride / offset of position 0 (floats)
     float *w = nullptr, *b = nullptr, *sc = nullptr, *sh = nullptr;
@@ -70,6 +73,13 @@ struct ry_crepe {
     // resampling: tables per input rate
     Arena rs_tables;
     std::map<int, Resampler> rs;
+    // ry_crepe_set_dtype: 0 = fp32 MFMA, 2 = split-bf16.  The filters of every layer as two bf16 planes (layer i at L[i].w_off), built at the
+    // first switch to 2.  They are weights: a list of their own, which ry_crepe_debug_poison does not walk.
+    int dtype = 0;
+    DevBufList planes;
+    DevBuf<unsigned short> w_hi{planes}, w_lo{planes};
+    bool planes_built = false;
+    int splits_of(int i) const { return dtype == 2 ? L[i].splits_x3 : L[i].splits; }
 };
 
 namespace {
@@ -84,7 +94,8 @@ int ensure_chunk(ry_crepe* c, int nf) {
         const size_t in_floats = (size_t)cap * l.in_fstride;
         RY_TRY(c->bufs.alloc(&c->act_in[i], in_floats));
         RT_TRY(rt::dmemset(c->act_in[i], 0, in_floats * sizeof(float), c->ctx->stream));       // the padding rows stay zero
-        if (l.splits > 1) slab = std::max(slab, (size_t)l.splits * cap * l.lout * l.cout);
+        const int sp = std::max(l.splits, l.splits_x3);            // one slab buffer serves both modes
+        if (sp > 1) slab = std::max(slab, (size_t)sp * cap * l.lout * l.cout);
     }
     RY_TRY(c->bufs.alloc(&c->logits, (size_t)cap * CREPE_BINS));
     c->slab_floats = std::max(slab, (size_t)1);
@@ -110,19 +121,26 @@ int ensure_call(ry_crepe* c, int n_frames, int n_samples) {
 int launch_layer(ry_crepe* c, int i, int nf, float* act) {
     const CLayer& l = c->L[i];
     const bool dense = i == NCONV;
+    const bool x3 = c->dtype == 2;
+    const int splits = c->splits_of(i);
     CrepeGemmParams p;
     p.x = c->act_in[i]; p.w = l.w; p.bias = l.b; p.scale = l.sc; p.shift = l.sh;
     p.M = nf * l.lout; p.N = l.cout; p.K = l.K; p.lout = l.lout;
     p.in_fstride = l.in_fstride; p.in_rstride = l.in_rstride;
-    p.out_fstride = l.out_fstride; p.out_off = l.out_off; p.splits = l.splits;
+    p.out_fstride = l.out_fstride; p.out_off = l.out_off; p.splits = splits;
     float* out = dense ? nullptr : c->act_in[i + 1];
-    dim3 grid((unsigned)((l.cout + CREPE_BN - 1) / CREPE_BN), (unsigned)((p.M + CREPE_BM - 1) / CREPE_BM), (unsigned)l.splits);
+    dim3 grid((unsigned)((l.cout + CREPE_BN - 1) / CREPE_BN), (unsigned)((p.M + CREPE_BM - 1) / CREPE_BM), (unsigned)splits);
     const ry_stream_t s = c->ctx->stream;
-    const int epi = l.splits > 1 ? CREPE_EPI_RAW : dense ? CREPE_EPI_SIG : CREPE_EPI_POOL;
+    const int epi = splits > 1 ? CREPE_EPI_RAW : dense ? CREPE_EPI_SIG : CREPE_EPI_POOL;
     p.y = epi == CREPE_EPI_RAW ? c->slabs : dense ? act : out;
     p.y2 = epi == CREPE_EPI_SIG ? c->logits : nullptr;
+    CrepeX3Params px;
+    px.g = p; px.w_hi = x3 ? c->w_hi.ptr() + l.w_off : nullptr; px.w_lo = x3 ? c->w_lo.ptr() + l.w_off : nullptr;
     switch (i * 3 + epi) {
-#define CREPE_CASE(L, E) case (L) * 3 + (E): RY_LAUNCH((crepe_igemm<E, L + 1>), grid, 256, s, p); break;
+#define CREPE_CASE(L, E) case (L) * 3 + (E):                                          \
+        if (x3) RY_LAUNCH((crepe_igemm_x3<E, L + 1>), grid, 256, s, px);              \
+        else RY_LAUNCH((crepe_igemm<E, L + 1>), grid, 256, s, p);                     \
+        break;
         CREPE_CASE(0, CREPE_EPI_POOL) CREPE_CASE(1, CREPE_EPI_POOL) CREPE_CASE(2, CREPE_EPI_POOL)
         CREPE_CASE(3, CREPE_EPI_POOL) CREPE_CASE(4, CREPE_EPI_POOL) CREPE_CASE(5, CREPE_EPI_POOL)
         CREPE_CASE(0, CREPE_EPI_RAW) CREPE_CASE(1, CREPE_EPI_RAW) CREPE_CASE(2, CREPE_EPI_RAW) CREPE_CASE(3, CREPE_EPI_RAW)
@@ -134,13 +152,13 @@ int launch_layer(ry_crepe* c, int i, int nf, float* act) {
     if (epi != CREPE_EPI_RAW) return RY_OK;
     if (dense) {
         CrepeReduceSigParams r;
-        r.slabs = c->slabs; r.bias = l.b; r.act = act; r.logits = c->logits; r.M = p.M; r.N = l.cout; r.splits = l.splits;
+        r.slabs = c->slabs; r.bias = l.b; r.act = act; r.logits = c->logits; r.M = p.M; r.N = l.cout; r.splits = splits;
         dim3 g((unsigned)(((long long)p.M * l.cout + 255) / 256));
         RY_LAUNCH(crepe_reduce_sig, g, 256, s, r);
     } else {
         CrepeReducePoolParams r;
         r.slabs = c->slabs; r.bias = l.b; r.scale = l.sc; r.shift = l.sh; r.y = out;
-        r.M = p.M; r.N = l.cout; r.lout = l.lout; r.out_fstride = l.out_fstride; r.out_off = l.out_off; r.splits = l.splits;
+        r.M = p.M; r.N = l.cout; r.lout = l.lout; r.out_fstride = l.out_fstride; r.out_off = l.out_off; r.splits = splits;
         dim3 g((unsigned)(((long long)(p.M / 2) * l.cout + 255) / 256));
         RY_LAUNCH(crepe_reduce_pool, g, 256, s, r);
     }
@@ -305,6 +323,11 @@ int ry_crepe_create(ry_ctx* ctx, int capacity, const float* weights, size_t n_fl
         const long long tiles = (long long)((PLAN_FRAMES * l.lout + CREPE_BM - 1) / CREPE_BM) * ((l.cout + CREPE_BN - 1) / CREPE_BN);
         const int nch = l.K / CREPE_BK;
         l.splits = (int)std::max(1LL, std::min((long long)(nch / (i == NCONV ? 4 : 16)), (PLAN_WORKGROUPS + tiles - 1) / tiles));
+        // the split-bf16 kernel: the same plan in its chunks of 64 (the floor is 8 / 2 chunks, the same span of K)
+        if (l.K % CREPE_X3_BK) return fail(RY_EINVAL, "crepe layer %d: K = %d is not a multiple of %d", i, l.K, CREPE_X3_BK);
+        const int nch3 = l.K / CREPE_X3_BK;
+        l.splits_x3 = (int)std::max(1LL, std::min((long long)(nch3 / (i == NCONV ? 2 : 8)), (PLAN_WORKGROUPS + tiles - 1) / tiles));
+        l.w_off = i == 0 ? 0 : c->L[i - 1].w_off + (size_t)c->L[i - 1].cout * c->L[i - 1].K;
     }
     // the HMM of the decode: uniform start, T[i][j] ~ max(12 - |i - j|, 0) per row, E = 0.1 I + 0.9 / 360 (logs in float64;
     // the Python layer replaces them by numpy's own values, ry_crepe_set_viterbi_tables)
@@ -330,6 +353,27 @@ void ry_crepe_destroy(ry_crepe* c) {
     rt::set_device(c->ctx->device);
     rt::stream_sync(c->ctx->stream);
     delete c;
+}
+
+int ry_crepe_set_dtype(ry_crepe* c, int dtype) {
+    RY_TRY(check_handle(c, "crepe"));
+    if (dtype != 0 && dtype != 2) return fail(RY_EINVAL, "crepe dtype %d (0 = fp32, 2 = split-bf16; there is no plain bf16 form of this network)", dtype);
+    if (dtype == 2 && !c->planes_built) {
+        const CLayer& last = c->L[NCONV];
+        const long long total = (long long)(last.w_off + (size_t)last.cout * last.K);
+        RY_TRY(c->w_hi.reserve(c->ctx, total));
+        RY_TRY(c->w_lo.reserve(c->ctx, total));
+        for (int i = 0; i <= NCONV; ++i) {
+            const CLayer& l = c->L[i];
+            CrepeSplitWParams sp;
+            sp.w = l.w; sp.hi = c->w_hi.ptr() + l.w_off; sp.lo = c->w_lo.ptr() + l.w_off; sp.n8 = (long long)l.cout * l.K / 8;
+            RY_LAUNCH(crepe_split_w, dim3((unsigned)((sp.n8 + 255) / 256)), 256, c->ctx->stream, sp);
+            RT_TRY(rt::last_error());
+        }
+        c->planes_built = true;
+    }
+    c->dtype = dtype;                                               // the launches of later calls follow it; the stream keeps them in order
+    return RY_OK;
 }
 
 int ry_crepe_predict(ry_crepe* c, const float* audio, int n_samples, int hop, int center, int viterbi,
@@ -479,7 +523,7 @@ int ry_crepe_debug_poison(ry_crepe* c) {
 
 int ry_crepe_debug_splits(ry_crepe* c, int* splits) {
     if (!c || !splits) return fail(RY_EINVAL, "bad argument");
-    for (int i = 0; i <= NCONV; ++i) splits[i] = c->L[i].splits;
+    for (int i = 0; i <= NCONV; ++i) splits[i] = c->splits_of(i);
     return RY_OK;
 }
 

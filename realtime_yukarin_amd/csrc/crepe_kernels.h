@@ -1,5 +1,6 @@
 // crepe_kernels.h -- the kernels of the CREPE pitch tracker (crepe.cpp): framing, one implicit-GEMM 1-D convolution family on
-// v_mfma_f32_32x32x2_f32 (conv1 .. conv6 and the dense classifier), the split-K reduction with the same epilogues, and the decode
+// v_mfma_f32_32x32x2_f32 (conv1 .. conv6 and the dense classifier) and its split-bf16 form on v_mfma_f32_32x32x16_bf16, the split-K reduction with the
+// same epilogues, and the decode
 // (per-frame argmax / max, the 360-state Viterbi pass in float64, the local-average cents).
 // Semantics restated from the public crepe package and its PyTorch fork ([MEM]; INTEGRATION.md section 9 lists what is unpinned).
 //
@@ -145,6 +146,43 @@ RY_DEV float crepe_act(float acc, float b, float sc, float sh) {
     return v * sc + sh;
 }
 
+// the epilogue of a workgroup's 128 x 128 tile, shared by the fp32 and the split-bf16 kernel: wave (wm, wn) holds 2 x 2 accumulator blocks
+template <int EPI>
+RY_DEV void crepe_epilogue(const CrepeGemmParams& p, const f32x16 (&acc)[2][2], int m0, int n0, int wm, int wn, int r, int h, int z) {
+    for (int j = 0; j < 2; ++j) {
+        const int n = n0 + wn * 64 + j * 32 + r;
+        if (n >= p.N) continue;
+        float b = 0.f, sc = 1.f, sh = 0.f;
+        if (EPI != CREPE_EPI_RAW) b = p.bias[n];
+        if (EPI == CREPE_EPI_POOL) { sc = p.scale[n]; sh = p.shift[n]; }
+        for (int i = 0; i < 2; ++i) {
+            const int mb = m0 + wm * 64 + i * 32 + 4 * h;
+            for (int e = 0; e < 16; e += 2) {
+                const int m = mb + (e & 3) + 8 * (e >> 2);
+                if (m >= p.M) continue;
+                if (EPI == CREPE_EPI_POOL) {                          // conv layers: M is even, the pair is in or out together
+                    const float v = fmaxf(crepe_act(acc[i][j][e], b, sc, sh), crepe_act(acc[i][j][e + 1], b, sc, sh));
+                    const int pr = m >> 1, half = p.lout >> 1;
+                    const int fr = pr / half, pos = pr - fr * half;
+                    p.y[(size_t)fr * p.out_fstride + p.out_off + (size_t)pos * p.N + n] = v;
+                } else {
+                    for (int u = 0; u < 2 && m + u < p.M; ++u) {      // the dense layer: M = frames may be odd
+                        const float a = acc[i][j][e + u];
+                        const size_t o = (size_t)(m + u) * p.N + n;
+                        if (EPI == CREPE_EPI_RAW) {
+                            p.y[(size_t)z * p.M * p.N + o] = a;
+                        } else {
+                            const float l = a + b;
+                            p.y2[o] = l;
+                            p.y[o] = 1.f / (1.f + expf(-l));
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
 // LAYER (1 .. 6 conv, 7 dense) only names the instantiation, so that a kernel trace tells the layers apart
 template <int EPI, int LAYER>
 RY_KERNEL(256) void crepe_igemm(CrepeGemmParams p) {
@@ -225,38 +263,146 @@ RY_KERNEL(256) void crepe_igemm(CrepeGemmParams p) {
         }
     }
 
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn * 64 + j * 32 + r;
-        if (n >= p.N) continue;
-        float b = 0.f, sc = 1.f, sh = 0.f;
-        if (EPI != CREPE_EPI_RAW) b = p.bias[n];
-        if (EPI == CREPE_EPI_POOL) { sc = p.scale[n]; sh = p.shift[n]; }
-        for (int i = 0; i < 2; ++i) {
-            const int mb = m0 + wm * 64 + i * 32 + 4 * h;
-            for (int e = 0; e < 16; e += 2) {
-                const int m = mb + (e & 3) + 8 * (e >> 2);
-                if (m >= p.M) continue;
-                if (EPI == CREPE_EPI_POOL) {                          // conv layers: M is even, the pair is in or out together
-                    const float v = fmaxf(crepe_act(acc[i][j][e], b, sc, sh), crepe_act(acc[i][j][e + 1], b, sc, sh));
-                    const int pr = m >> 1, half = p.lout >> 1;
-                    const int fr = pr / half, pos = pr - fr * half;
-                    p.y[(size_t)fr * p.out_fstride + p.out_off + (size_t)pos * p.N + n] = v;
-                } else {
-                    for (int u = 0; u < 2 && m + u < p.M; ++u) {      // the dense layer: M = frames may be odd
-                        const float a = acc[i][j][e + u];
-                        const size_t o = (size_t)(m + u) * p.N + n;
-                        if (EPI == CREPE_EPI_RAW) {
-                            p.y[(size_t)z * p.M * p.N + o] = a;
-                        } else {
-                            const float l = a + b;
-                            p.y2[o] = l;
-                            p.y[o] = 1.f / (1.f + expf(-l));
-                        }
-                    }
-                }
+    crepe_epilogue<EPI>(p, acc, m0, n0, wm, wn, r, h, z);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The split-bf16 form of the same GEMM (ry_crepe_set_dtype 2): every fp32 product x w becomes x_lo w_hi + x_hi w_lo + x_hi w_hi on
+// v_mfma_f32_32x32x16_bf16 with fp32 accumulation, hi = bf16(v), lo = bf16(v - hi) (ry_split_bf16).  Same tile, grid, waves and epilogues as
+// crepe_igemm; K runs in chunks of 64.  Activations stay fp32 in memory and are split while they are staged (global fp32 -> registers -> two bf16
+// planes in the LDS); the filters come split, w_hi / w_lo [N][K] bf16 (crepe_split_w).  An LDS row holds the 64 bf16 of a chunk and 8 of padding:
+// K step s (16 wide) of lane half h is the 16 bytes at 32 s + 16 h of the row, one ds_read_b128, and the 144-byte row stride sends the 16 rows
+// of a read's lane group (distinct mod 16) to the 16 different 16-byte slots of the 256-byte bank row (144 / 16 = 9 is odd): no conflict.
+// Four planes of 128 x 72 bf16 = 72 KiB: two workgroups per CU.
+// Order of the products, per K step of 16 and accumulator block: lo hi, hi lo, hi hi (x first); the K steps of a chunk and the chunks of a split
+// follow in rising k.
+// ---------------------------------------------------------------------------------------------
+#define CREPE_X3_BK 64
+#define CREPE_X3_ROW (CREPE_X3_BK + 8)
+
+struct CrepeX3Params { CrepeGemmParams g; const unsigned short *w_hi, *w_lo; };   // g.w is not read
+
+template <int EPI, int LAYER>
+RY_KERNEL(256, 2) void crepe_igemm_x3(CrepeX3Params px) {      // two workgroups per CU: the LDS holds two, so the registers must too
+    __shared__ __attribute__((aligned(16))) unsigned short Ah[CREPE_BM * CREPE_X3_ROW];
+    __shared__ __attribute__((aligned(16))) unsigned short Al[CREPE_BM * CREPE_X3_ROW];
+    __shared__ __attribute__((aligned(16))) unsigned short Bh[CREPE_BN * CREPE_X3_ROW];
+    __shared__ __attribute__((aligned(16))) unsigned short Bl[CREPE_BN * CREPE_X3_ROW];
+    const CrepeGemmParams& p = px.g;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int r = lane & 31, h = lane >> 5;
+    const int m0 = (int)blockIdx.y * CREPE_BM, n0 = (int)blockIdx.x * CREPE_BN;
+    const int nch = p.K / CREPE_X3_BK;
+    const int z = (int)blockIdx.z;
+    const int c_lo = (int)((long long)z * nch / p.splits), c_hi = (int)((long long)(z + 1) * nch / p.splits);
+
+    // this thread's four A rows / four B rows (row = idx >> 3, piece kq = idx & 7 of eight k of the 64-wide chunk)
+    const float* ga[4];
+    const unsigned short* gbh[4];
+    const unsigned short* gbl[4];
+    bool va[4], vb[4];
+    int lofs[4];
+    for (int i = 0; i < 4; ++i) {
+        const int idx = tid + 256 * i;
+        const int row = idx >> 3, kq = idx & 7;
+        lofs[i] = row * CREPE_X3_ROW + 8 * kq;
+        const int m = m0 + row, n = n0 + row;
+        va[i] = m < p.M;
+        vb[i] = n < p.N;
+        const int mm = va[i] ? m : 0;
+        const int fr = mm / p.lout, pos = mm - fr * p.lout;
+        ga[i] = p.x + (size_t)fr * p.in_fstride + (size_t)pos * p.in_rstride + 8 * kq;
+        const size_t wo = (size_t)(vb[i] ? n : 0) * p.K + 8 * kq;
+        gbh[i] = px.w_hi + wo;
+        gbl[i] = px.w_lo + wo;
+    }
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    const u16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    f32x4 ra[4][2];
+    u16x8 rbh[4], rbl[4];
+    auto load = [&](int c) {
+        const int k0 = c * CREPE_X3_BK;
+        for (int i = 0; i < 4; ++i) {
+            ra[i][0] = va[i] ? ry_ld4(ga[i] + k0) : zero4;
+            ra[i][1] = va[i] ? ry_ld4(ga[i] + k0 + 4) : zero4;
+            rbh[i] = vb[i] ? ry_ld8h(gbh[i] + k0) : zero8;
+            rbl[i] = vb[i] ? ry_ld8h(gbl[i] + k0) : zero8;
+        }
+    };
+    auto stash = [&]() {
+        for (int i = 0; i < 4; ++i) {
+            u16x8 xh, xl;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                unsigned short hi, lo;
+                ry_split_bf16(ra[i][u >> 2][u & 3], &hi, &lo);
+                xh[u] = hi; xl[u] = lo;
             }
+            ry_st8h(&Ah[lofs[i]], xh);
+            ry_st8h(&Al[lofs[i]], xl);
+            ry_st8h(&Bh[lofs[i]], rbh[i]);
+            ry_st8h(&Bl[lofs[i]], rbl[i]);
+        }
+    };
+
+    f32x16 acc[2][2];
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j)
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    if (c_lo < c_hi) {
+        load(c_lo);
+        stash();
+        __syncthreads();
+    }
+    const int oa = (wm * 64 + r) * CREPE_X3_ROW + 8 * h, ob = (wn * 64 + r) * CREPE_X3_ROW + 8 * h;
+    for (int c = c_lo; c < c_hi; ++c) {
+        if (c + 1 < c_hi) load(c + 1);
+#pragma unroll
+        for (int s = 0; s < CREPE_X3_BK / 16; ++s) {
+            u16x8 ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                ah[i] = ry_ld8h(&Ah[oa + i * 32 * CREPE_X3_ROW + 16 * s]);
+                al[i] = ry_ld8h(&Al[oa + i * 32 * CREPE_X3_ROW + 16 * s]);
+                bh[i] = ry_ld8h(&Bh[ob + i * 32 * CREPE_X3_ROW + 16 * s]);
+                bl[i] = ry_ld8h(&Bl[ob + i * 32 * CREPE_X3_ROW + 16 * s]);
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    acc[i][j] = ry_mfma_32x32x16_bf16(al[i], bh[j], acc[i][j]);
+                    acc[i][j] = ry_mfma_32x32x16_bf16(ah[i], bl[j], acc[i][j]);
+                    acc[i][j] = ry_mfma_32x32x16_bf16(ah[i], bh[j], acc[i][j]);
+                }
+        }
+        __syncthreads();
+        if (c + 1 < c_hi) {
+            stash();
+            __syncthreads();
         }
     }
+    crepe_epilogue<EPI>(p, acc, m0, n0, wm, wn, r, h, z);
+}
+
+// the filters of a layer, split once: eight values per thread, n8 = N K / 8 (K is a multiple of 64)
+struct CrepeSplitWParams { const float* w; unsigned short *hi, *lo; long long n8; };
+
+RY_KERNEL(256) void crepe_split_w(CrepeSplitWParams p) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= p.n8) return;
+    const f32x4 v0 = ry_ld4(p.w + 8 * t), v1 = ry_ld4(p.w + 8 * t + 4);
+    u16x8 xh, xl;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        unsigned short hi, lo;
+        ry_split_bf16(u < 4 ? v0[u & 3] : v1[u & 3], &hi, &lo);
+        xh[u] = hi; xl[u] = lo;
+    }
+    ry_st8h(p.hi + 8 * t, xh);
+    ry_st8h(p.lo + 8 * t, xl);
 }
 
 // The split-K sums (slab 0 + slab 1 + ... in that order) and the layer's epilogue: one thread per pooled output (POOL, M / 2 x N) or

@@ -107,6 +107,14 @@ typedef hipStream_t ry_stream_t;
 
 RY_DEV f32x4 ry_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 RY_DEV void ry_st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+RY_DEV float ry_bf2f(unsigned short h) { return __builtin_bit_cast(float, (unsigned)h << 16); }
+// the split-bf16 form of one fp32 value: hi = bf16(v), lo = bf16(v - hi), both RNE (v - hi is exact in fp32): hi + lo carries 16 mantissa bits of v
+RY_DEV void ry_split_bf16(float v, unsigned short* hi, unsigned short* lo) {
+    *hi = ry_f2bf(v);
+    *lo = ry_f2bf(v - ry_bf2f(*hi));
+}
+RY_DEV u16x8 ry_ld8h(const unsigned short* p) { return *reinterpret_cast<const u16x8*>(p); }
+RY_DEV void ry_st8h(unsigned short* p, u16x8 v) { *reinterpret_cast<u16x8*>(p) = v; }
 
 // constants the host planner (ry_plan.cpp) and the kernels share: epilogue activations, forms of a stage-1 layer
 enum { RY_ACT_NONE = 0, RY_ACT_LRELU = 1, RY_ACT_RELU = 2, RY_ACT_GLU = 3 };

@@ -72,14 +72,13 @@ RY_DEV void ry_st4_bf16(unsigned short* q, f32x4 v) {
     h[0] = ry_f2bf(v[0]); h[1] = ry_f2bf(v[1]); h[2] = ry_f2bf(v[2]); h[3] = ry_f2bf(v[3]);
     *reinterpret_cast<u16x4*>(q) = h;
 }
-RY_DEV float ry_bf2f(unsigned short h) { return __builtin_bit_cast(float, (unsigned)h << 16); }
 // Split-bf16 copy of four channels n .. n + 3 of pixel `pix` (N channels): the pixel keeps [hi (N) | lo (N)] with
 // hi = bf16(v), lo = bf16(v - hi) (both RNE; v - hi is exact in fp32), so that hi + lo carries 16 mantissa bits of v.
 // The implicit GEMM then runs hi*hi + lo*hi + hi*lo on the bf16 matrix pipe with fp32 accumulation (split-bf16).
 RY_DEV void ry_st4_bf16_x3(unsigned short* base, size_t pix, int N, int n, f32x4 v) {
     u16x4 h, l;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) { h[u] = ry_f2bf(v[u]); l[u] = ry_f2bf(v[u] - ry_bf2f(h[u])); }
+    for (int u = 0; u < 4; ++u) { unsigned short hi, lo; ry_split_bf16(v[u], &hi, &lo); h[u] = hi; l[u] = lo; }
     unsigned short* q = base + pix * (size_t)(2 * N) + n;
     *reinterpret_cast<u16x4*>(q) = h;
     *reinterpret_cast<u16x4*>(q + N) = l;
