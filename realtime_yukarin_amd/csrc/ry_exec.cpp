@@ -478,11 +478,15 @@ static int enqueue_forward(ry_net* net, Plan& P, Launcher& Lc) {
         RY_LAUNCH(ry_materialize, mg, 256, Lc.stream, m);
         RY_TRY(Lc.end());
     } else if (P.mode == 1 && P.lp[15].path != PATH_LAST) {
+        // the separate end layer computed every row; only the rows the caller keeps go into its block (ry_sr_convert_rows: the others are
+        // left untouched, as the fused end layer leaves them)
+        int k0 = 0, k1 = P.n_frames;
+        keep_rows(P.n_frames, P.disc_front, P.disc_back, &k0, &k1);
         RySrPostParams q;
-        q.y = P.lp[15].out; q.out = P.cur_out; q.rows = P.n_frames; q.cols_in = d.width; q.cols_out = d.width + 1;
+        q.y = P.lp[15].out; q.out = P.cur_out; q.row0 = k0; q.rows = k1 - k0; q.cols_in = d.width; q.cols_out = d.width + 1;
         q.y_bstride = (long long)P.T * d.width; q.out_bstride = (long long)P.n_frames * (d.width + 1);
-        dim3 pg((unsigned)(((long long)P.n_frames * (d.width + 1) + 255) / 256), (unsigned)B);
-        RY_TRY(Lc.begin("ry_sr_post", "post", 0, 8.0 * B * P.n_frames * (d.width + 1), pg));
+        dim3 pg((unsigned)(((long long)(k1 - k0) * (d.width + 1) + 255) / 256), (unsigned)B);
+        RY_TRY(Lc.begin("ry_sr_post", "post", 0, 8.0 * B * (k1 - k0) * (d.width + 1), pg));
         RY_LAUNCH(ry_sr_post, pg, 256, Lc.stream, q);
         RY_TRY(Lc.end());
     }

@@ -2135,14 +2135,15 @@ RY_KERNEL(16 * G) void ry_pad_min_rows(RyPadRowsParams p) {   // blockIdx.y = wi
     for (int r = p.rows_in + grp; r < p.rows_out; r += G) out[(size_t)r * p.cols_out + c] = fill;
 }
 
-struct RySrPostParams { const float* y; float* out; int rows, cols_in, cols_out; long long y_bstride, out_bstride; };
+// rows row0 .. row0 + rows - 1 of every window: the rows the caller keeps (ry_sr_convert_rows); the others are neither read nor written
+struct RySrPostParams { const float* y; float* out; int row0, rows, cols_in, cols_out; long long y_bstride, out_bstride; };
 
 RY_KERNEL(256) void ry_sr_post(RySrPostParams p) {   // out[r][f] = exp(y[r][min(f, cols_in-1)]), blockIdx.y = window
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)p.rows * p.cols_out) return;
     const int f = (int)(idx % p.cols_out);
-    const int r = (int)(idx / p.cols_out);
+    const int r = p.row0 + (int)(idx / p.cols_out);
     const int fi = f < p.cols_in ? f : p.cols_in - 1;
-    p.out[(size_t)blockIdx.y * (size_t)p.out_bstride + idx] =
+    p.out[(size_t)blockIdx.y * (size_t)p.out_bstride + (size_t)p.row0 * p.cols_out + idx] =
         expf(p.y[(size_t)blockIdx.y * (size_t)p.y_bstride + (size_t)r * p.cols_in + fi]);
 }

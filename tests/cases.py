@@ -846,7 +846,7 @@ def s2_walk(net, desc, P, n_frames, y, discard=(0, 0), prof=(), refs=True, cache
     assert heights[15] == T and heights[0] == T
     need = s2_needed_rows(specs, heights, k0, k1)
     if not fused:
-        need[15] = (0, n_frames)                                  # ry_sr_post reads every real row; the discard is cut by the host call
+        need[15] = (0, n_frames)                                  # the separate end layer computes every real row (ry_sr_post then stores the kept ones)
         for i in range(15, 8, -1):
             need[i - 1] = s2_rows_read(specs[i], need[i][0], need[i][1], heights[specs[i]['src'][0]])
     rep = []

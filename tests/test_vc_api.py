@@ -1,6 +1,8 @@
-"""The window-call API of the C ABI (`ry_vc_*`, include/ry355.h) on the emulator: tickets, the six-slot ring, the split calls and
+"""The window-call API of the C ABI (`ry_vc_*`, include/ry355.h): tickets, the six-slot ring, the split calls and
 their error behaviour -- every misuse returns a negative code with a message (`Ry355Error`), nothing aborts, and the handle stays usable
-(the reference's worker loop dies on any exception, convert_worker.py:45-59: errors must be reported, not fatal)."""
+(the reference's worker loop dies on any exception, convert_worker.py:45-59: errors must be reported, not fatal).
+Every scenario is a `check_*` function over a context or a core: the emulator runs them all, and the `_gpu` twins run the same bodies on the
+card, where the events, the stream waits and the asynchronous copies of the ring are real (on the emulator they are no-ops and memcpy)."""
 import ctypes
 
 import numpy
@@ -10,14 +12,23 @@ from realtime_yukarin_amd import _lib, engine, gate, sptk, synth
 from realtime_yukarin_amd.weights import flatten_params
 
 
-@pytest.fixture(scope='module')
-def core(emu_ctx):
+def _core_on(ctx):
     (d1, P1), (d2, P2) = synth.model_params('SYN-8')
-    n1 = engine.Net(emu_ctx, d1, flatten_params(d1, P1))
-    n2 = engine.Net(emu_ctx, d2, flatten_params(d2, P2), width=128)
+    n1 = engine.Net(ctx, d1, flatten_params(d1, P1))
+    n2 = engine.Net(ctx, d2, flatten_params(d2, P2), width=128)
     c = engine.VcCore(n1, n2, sptk.mc2sp_matrix(8, sptk.mcepalpha(16000), 256))
     yield c
     c.close(); n1.close(); n2.close()
+
+
+@pytest.fixture(scope='module')
+def core(emu_ctx):
+    yield from _core_on(emu_ctx)
+
+
+@pytest.fixture(scope='module')
+def gpu_core(gpu_ctx):
+    yield from _core_on(gpu_ctx)
 
 
 def window(n, seed, keep=0.7):
@@ -27,7 +38,7 @@ def window(n, seed, keep=0.7):
     return x, eff
 
 
-def test_tickets_come_back_in_any_order_and_only_once(core):
+def check_tickets_come_back_in_any_order_and_only_once(core):
     (xa, ea), (xb, eb), (xc, ec) = window(20, 1), window(33, 2), window(20, 3)
     ref = [core.convert(x[e], e) for x, e in ((xa, ea), (xb, eb), (xc, ec))]
     ta, tb, tc = core.submit(xa[ea], ea), core.submit(xb[eb], eb), core.submit(xc[ec], ec)
@@ -45,6 +56,15 @@ def test_tickets_come_back_in_any_order_and_only_once(core):
         core.wait(ta)                                                               # a ticket is good for one wait
     mc, sp = core.convert(xa[ea], ea)                                               # ... and the handle is still usable
     assert numpy.array_equal(sp, ref[0][1])
+
+
+def test_tickets_come_back_in_any_order_and_only_once(core):
+    check_tickets_come_back_in_any_order_and_only_once(core)
+
+
+@pytest.mark.gpu
+def test_tickets_come_back_in_any_order_and_only_once_gpu(gpu_core):
+    check_tickets_come_back_in_any_order_and_only_once(gpu_core)
 
 
 def test_bad_arguments_are_reported(core):
@@ -71,7 +91,7 @@ def test_bad_arguments_are_reported(core):
     assert sp.shape == (16, core.F)
 
 
-def test_split_calls_follow_the_order_of_the_reference_steps(core):
+def check_split_calls_follow_the_order_of_the_reference_steps(core):
     x, e = window(24, 7)
     whole = core.convert(x[e], e)
     y1 = core.convert_stage1(x[e])
@@ -90,7 +110,16 @@ def test_split_calls_follow_the_order_of_the_reference_steps(core):
         core.stage2_from_mc(e, 1e-16)
 
 
-def test_stream_generator_depth(core):
+def test_split_calls_follow_the_order_of_the_reference_steps(core):
+    check_split_calls_follow_the_order_of_the_reference_steps(core)
+
+
+@pytest.mark.gpu
+def test_split_calls_follow_the_order_of_the_reference_steps_gpu(gpu_core):
+    check_split_calls_follow_the_order_of_the_reference_steps(gpu_core)
+
+
+def check_stream_generator_depth(core):
     wins = [window(12 + i, 20 + i) for i in range(4)]
     core.reserve(40)
     ref = [core.convert(x[e], e) for x, e in wins]
@@ -101,7 +130,16 @@ def test_stream_generator_depth(core):
         list(core.convert_stream([], depth=7))
 
 
-def test_batch_call_equals_the_windows_one_by_one(core):
+def test_stream_generator_depth(core):
+    check_stream_generator_depth(core)
+
+
+@pytest.mark.gpu
+def test_stream_generator_depth_gpu(gpu_core):
+    check_stream_generator_depth(gpu_core)
+
+
+def check_batch_call_equals_the_windows_one_by_one(core):
     """`ry_vc_enqueue_device_batch` (several windows of one length per call: stage 2 as one batch): every window of the result is the
     single-window call on that window -- ragged effective counts (stage 1 window by window), equal counts (stage 1 as one batch), an
     all-silent window in the middle, and a bad argument is refused with a message."""
@@ -139,7 +177,16 @@ def test_batch_call_equals_the_windows_one_by_one(core):
     assert numpy.array_equal(mc, one[0][0]) and numpy.array_equal(sp, one[0][1])
 
 
-def test_lanes_run_the_same_arithmetic(core):
+def test_batch_call_equals_the_windows_one_by_one(core):
+    check_batch_call_equals_the_windows_one_by_one(core)
+
+
+@pytest.mark.gpu
+def test_batch_call_equals_the_windows_one_by_one_gpu(gpu_core):
+    check_batch_call_equals_the_windows_one_by_one(gpu_core)
+
+
+def check_lanes_run_the_same_arithmetic(core):
     """`ry_vc_set_lanes`: ring slot k on its own clone of the predictor pair (shared filters, own streams / plans / activations).  The
     windows of a stream come back bit-identical with 1, 2 and 3 lanes; the lane count cannot change under a window in flight; a clone
     follows the arithmetic mode of the handle it was made from."""
@@ -171,28 +218,46 @@ def test_lanes_run_the_same_arithmetic(core):
         core.set_lanes(2)
 
 
-def test_a_clone_shares_the_filters(emu_ctx):
+def test_lanes_run_the_same_arithmetic(core):
+    check_lanes_run_the_same_arithmetic(core)
+
+
+@pytest.mark.gpu
+def test_lanes_run_the_same_arithmetic_gpu(gpu_core):
+    check_lanes_run_the_same_arithmetic(gpu_core)
+
+
+def check_a_clone_shares_the_filters(ctx):
     (d1, P1), _ = synth.model_params('SYN-8')
-    n1 = engine.Net(emu_ctx, d1, flatten_params(d1, P1))
+    n1 = engine.Net(ctx, d1, flatten_params(d1, P1))
     h = ctypes.c_void_p()
-    emu_ctx.lib.check(emu_ctx.lib.dll.ry_net_clone(n1.handle, ctypes.byref(h)))
+    ctx.lib.check(ctx.lib.dll.ry_net_clone(n1.handle, ctypes.byref(h)))
     x = synth.stage1_input(40, seed=3)[0]
     y = n1.convert(x)
     y2 = numpy.empty_like(y)
-    emu_ctx.lib.check(emu_ctx.lib.dll.ry_ac_convert(h, _lib._fptr(x), _lib._fptr(y2), 1, 40, 0))
+    ctx.lib.check(ctx.lib.dll.ry_ac_convert(h, _lib._fptr(x), _lib._fptr(y2), 1, 40, 0))
     assert numpy.array_equal(y, y2)
     n1.close()                                                                  # the clone keeps the filters alive
-    emu_ctx.lib.check(emu_ctx.lib.dll.ry_ac_convert(h, _lib._fptr(x), _lib._fptr(y2), 1, 40, 0))
+    ctx.lib.check(ctx.lib.dll.ry_ac_convert(h, _lib._fptr(x), _lib._fptr(y2), 1, 40, 0))
     assert numpy.array_equal(y, y2)
-    emu_ctx.lib.dll.ry_net_destroy(h)
+    ctx.lib.dll.ry_net_destroy(h)
 
 
-def test_a_longer_window_may_arrive_while_others_are_in_flight(emu_ctx):
+def test_a_clone_shares_the_filters(emu_ctx):
+    check_a_clone_shares_the_filters(emu_ctx)
+
+
+@pytest.mark.gpu
+def test_a_clone_shares_the_filters_gpu(gpu_ctx):
+    check_a_clone_shares_the_filters(gpu_ctx)
+
+
+def check_a_longer_window_may_arrive_while_others_are_in_flight(ctx):
     """Every ring slot owns its buffers and grows on its own: a stream whose windows get longer (the first fetches of a live stream are
     short) keeps its pipeline; `reserve` sizes all slots ahead of time and refuses only under a window in flight that would have to move."""
     (d1, P1), (d2, P2) = synth.model_params('SYN-8')
-    n1 = engine.Net(emu_ctx, d1, flatten_params(d1, P1))
-    n2 = engine.Net(emu_ctx, d2, flatten_params(d2, P2), width=128)
+    n1 = engine.Net(ctx, d1, flatten_params(d1, P1))
+    n2 = engine.Net(ctx, d2, flatten_params(d2, P2), width=128)
     c = engine.VcCore(n1, n2, sptk.mc2sp_matrix(8, sptk.mcepalpha(16000), 256))
     wins = [window(n, 50 + i) for i, n in enumerate((5, 9, 30, 41))]
     ref = [c.convert(x[e], e) for x, e in wins[:1]]                         # the ring starts small
@@ -212,6 +277,15 @@ def test_a_longer_window_may_arrive_while_others_are_in_flight(emu_ctx):
     mc, sp = c.convert(wins[1][0][wins[1][1]], wins[1][1])
     assert numpy.array_equal(sp, got[1][1])
     c.close(); c2.close(); n1.close(); n2.close()
+
+
+def test_a_longer_window_may_arrive_while_others_are_in_flight(emu_ctx):
+    check_a_longer_window_may_arrive_while_others_are_in_flight(emu_ctx)
+
+
+@pytest.mark.gpu
+def test_a_longer_window_may_arrive_while_others_are_in_flight_gpu(gpu_ctx):
+    check_a_longer_window_may_arrive_while_others_are_in_flight(gpu_ctx)
 
 
 def test_closing_a_predictor_takes_its_window_cores_with_it(emu_ctx, monkeypatch):
@@ -245,12 +319,12 @@ def test_closing_a_predictor_takes_its_window_cores_with_it(emu_ctx, monkeypatch
             c.convert(x[e], e)                          # a closed core raises in Python; it never reaches the library with a dangling handle
 
 
-def test_more_than_three_lanes_get_two_ring_slots_each(emu_ctx):
+def check_more_than_three_lanes_get_two_ring_slots_each(ctx):
     """`ry_vc_set_lanes(4 .. 8)`: two ring slots per lane (a throughput setting; eight lanes measured within 1 % of two at 300 frames): the ring,
     the lane rotation and the clones are what is checked here -- the same windows come back, in order, with eight in flight."""
     (d1, P1), (d2, P2) = synth.model_params('SYN-8')
-    n1 = engine.Net(emu_ctx, d1, flatten_params(d1, P1))
-    n2 = engine.Net(emu_ctx, d2, flatten_params(d2, P2), width=128)
+    n1 = engine.Net(ctx, d1, flatten_params(d1, P1))
+    n2 = engine.Net(ctx, d2, flatten_params(d2, P2), width=128)
     mtx = sptk.mc2sp_matrix(8, sptk.mcepalpha(16000), 256)
     wins = [window(8, 80 + i) for i in range(2)]
     one = engine.VcCore(n1, n2, mtx, lanes=1)
@@ -265,3 +339,12 @@ def test_more_than_three_lanes_get_two_ring_slots_each(emu_ctx):
     for i, (mc, sp) in enumerate(got):
         assert numpy.array_equal(mc, ref[i % 2][0]) and numpy.array_equal(sp, ref[i % 2][1])
     c.close(); n1.close(); n2.close()
+
+
+def test_more_than_three_lanes_get_two_ring_slots_each(emu_ctx):
+    check_more_than_three_lanes_get_two_ring_slots_each(emu_ctx)
+
+
+@pytest.mark.gpu
+def test_more_than_three_lanes_get_two_ring_slots_each_gpu(gpu_ctx):
+    check_more_than_three_lanes_get_two_ring_slots_each(gpu_ctx)
