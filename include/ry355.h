@@ -304,13 +304,40 @@ int ry_crepe_decode(ry_crepe* crepe, const float* activation, int n_frames, int 
  * ry_crepe_create builds them with the C library's log; a caller whose decode must match its own restatement bit for bit uploads
  * that restatement's values (realtime_yukarin_amd/crepe.py uploads numpy's). */
 int ry_crepe_set_viterbi_tables(ry_crepe* crepe, const double* logT, const double* logE, const double* logS);
+/* The voicing of a track (`crepe.predict_voicing(confidence)` and the mask the reference's wrapper makes of it): confidence [n] and f0 [n] are the
+ * float32 outputs of ry_crepe_predict / ry_crepe_predict_sr.  voiced [n] (0 / 1) = (path == 1) | (confidence > threshold), where path is the Viterbi
+ * path of the two-state Gaussian HMM over the confidence (float64, the order of realtime_yukarin_amd.crepe.predict_voicing, no fma; the lowest state
+ * wins a tie) and the comparison is strict and made in float32 against (float)threshold -- how numpy evaluates `confidence > 0.1` on a float32 array:
+ * float32(0.1) itself is not above 0.1 --; f0_64 [n] = voiced ? (double)f0 : 0; t_64 [n] = k * step_ms / 1000 in float64, the
+ * time axis of `crepe.predict`.  One workgroup, any n up to 2^24.  on_device = 1: all five are device pointers and the call only enqueues on the
+ * context stream; 0: host pointers, the call returns after the results are written.  Refused: a null pointer, n < 1, a NaN threshold, a step that
+ * is not finite and positive. */
+int ry_crepe_voicing(ry_crepe* crepe, const float* confidence, const float* f0, int n, double threshold, double step_ms,
+                     unsigned char* voiced, double* f0_64, double* t_64, int on_device);
+/* The constants of that HMM, two states each (1 = voiced): c = log(2 pi var), the means, the variances, logT [2][2] (from, to) and the log of the
+ * start probabilities.  ry_crepe_create installs the values of `predict_voicing` with the C library's log; a caller whose mask must match its own
+ * restatement bit for bit uploads that restatement's values (realtime_yukarin_amd/crepe.py uploads numpy's).  The device never takes a logarithm. */
+int ry_crepe_set_voicing_tables(ry_crepe* crepe, const double* c, const double* mu, const double* var, const double* logT, const double* logS);
+/* One enqueue for a window: audio (HOST, float32, at sr; uploaded once) -> ry_crepe_predict_sr with center = 1, viterbi = 1 and no activation
+ * output -> ry_crepe_voicing on its confidence and f0, all on the context stream.  *n_frames: the frames of the call.  The masked track stays in
+ * buffers of the handle (ry_crepe_track_buffers).  on_device_out = 0: voiced / f0_64 / t_64 are host arrays of at least *n_frames entries, written
+ * before the call returns; 1: they are not read (may be null), nothing is copied back and the call does not wait.  Refusals: those of
+ * ry_crepe_predict_sr and of ry_crepe_voicing. */
+int ry_crepe_track(ry_crepe* crepe, const float* audio, int n_samples, int sr, int hop, double step_ms, double threshold, int* n_frames,
+                   unsigned char* voiced, double* f0_64, double* t_64, int on_device_out);
+/* What the last ry_crepe_track left on the card, as device addresses (any pointer may be null): the uploaded float32 wave at the caller's rate and
+ * its length, the frames, voiced [n] (bytes), f0_64 [n], t_64 [n].  They are read in stream order (ry_analysis_extract_dev on the same context) and
+ * hold until the next call on this handle.  RY_ESTATE when no track is there: none has run, or a later call has reused the buffers. */
+int ry_crepe_track_buffers(ry_crepe* crepe, const float** wave_dev, int* n_samples, int* n_frames, const unsigned char** voiced_dev,
+                           const double** f0_dev, const double** t_dev);
 /* tests: the first n_frames rows of the buffers of the last pass of ry_crepe_predict (its last <= 256 frames): layer 0 the normalised
  * frames [n][1024], 1 .. 6 the pooled conv outputs [n][positions][channels], 7 the logits [n][360].  n_frames may exceed the frames of
  * that pass, up to the largest pass the handle has run: the rows behind it hold what an earlier call or ry_crepe_debug_poison left. */
 int ry_crepe_debug_layer(ry_crepe* crepe, int layer, int n_frames, float* out);
-/* tests: fills every element the next ry_crepe_predict / ry_crepe_decode must write with NaN bit patterns (all bits set; -1 as an index) --
- * the samples of the frame rows, the interior rows of every layer's input, logits, split-K slabs, activation, confidence, f0, observations,
- * back-pointers, path and the 16 kHz audio buffer (the resampler's output) -- and leaves the zero padding rows as they are: a later call that reads anything it did not write shows it. */
+/* tests: fills every element the next ry_crepe_predict / ry_crepe_decode / ry_crepe_voicing / ry_crepe_track must write with NaN bit patterns (all
+ * bits set; -1 as an index) -- the samples of the frame rows, the interior rows of every layer's input, logits, split-K slabs, activation, confidence,
+ * f0, observations, back-pointers, path, the 16 kHz audio buffer (the resampler's output), the voicing's back-pointers and the masked track (voiced,
+ * f0_64, t_64; ry_crepe_track_buffers then reports no track) -- and leaves the zero padding rows as they are: a later call that reads anything it did not write shows it. */
 int ry_crepe_debug_poison(ry_crepe* crepe);
 /* diagnostics: the split-K count of conv1 .. conv6 and the dense layer (7 ints) in the mode in force (ry_crepe_set_dtype). */
 int ry_crepe_debug_splits(ry_crepe* crepe, int* splits);
@@ -398,6 +425,13 @@ int ry_analysis_d4c(ry_analysis* analysis, const double* x, long long x_len, con
 /* ry_analysis_run and ry_analysis_d4c over one upload of the wave and the track: the same bits as the two calls. */
 int ry_analysis_extract(ry_analysis* analysis, const double* x, long long x_len, const double* f0, const double* t, int n, double threshold,
                         double* sp64_out, float* sp32_dev_out, double* mc_out, double* ap64_out, float* ap32_dev_out, double* coded_out);
+/* ry_analysis_extract on a wave and a track that are already on the card (what ry_crepe_track left there): x32_dev [x_len] float32, widened on the
+ * device ((double)x is exact: the frame kernels see the bits of the host's float64 copy), f0_dev / t_dev [n] float64 device pointers, read in place.
+ * The refusals ry_analysis_run makes on the host's track are made by a kernel; the host reads its verdict (one wait) BEFORE any frame kernel is
+ * launched, so a refused call (RY_EINVAL: f0 not finite or >= fs / 2, t outside -1 .. 1e6 s) writes no output.  Outputs and everything else as
+ * ry_analysis_extract: the same bits.  The inputs are read in the order of the context stream, which the call drains before it returns. */
+int ry_analysis_extract_dev(ry_analysis* analysis, const float* x32_dev, long long x_len, const double* f0_dev, const double* t_dev, int n, double threshold,
+                            double* sp64_out, float* sp32_dev_out, double* mc_out, double* ap64_out, float* ap32_dev_out, double* coded_out);
 /* the number of bands B (1 at 16 kHz, 3 at 24 kHz); negative (an error code) where D4C is not built for the handle's rate */
 int ry_analysis_d4c_bands(ry_analysis* analysis);
 /* tests: what the last recorded (ry_analysis_debug_record) D4C run decided.  ints_out [n][9]: half length of the Love-Train window, of the other

@@ -2,7 +2,8 @@
 `predict(audio, sr, viterbi, model_capacity, center, step_size, verbose)` and `predict_voicing(confidence)`
 (realtime-yukarin: realtime_voice_conversion/yukarin_wrapper/acoustic_feature_wrapper.py:65-80) -- plus `get_activation` and
 `load_model`.  Resampling to 16 kHz, the network, the decode and the Viterbi pass run in libry355 (`ry_crepe_*`); the mono average,
-the float32 cast and `predict_voicing` run on the host.  RY_CREPE_RESAMPLE=host resamples with the host statement of the same
+the float32 cast and `predict_voicing` run on the host (`predict_voicing` and the wrapper's mask also exist on the device:
+`CrepeModel.voicing`, used by `realtime_yukarin_amd.encode.extract`; this module's functions do not change).  RY_CREPE_RESAMPLE=host resamples with the host statement of the same
 arithmetic instead (`realtime_yukarin_amd.crepe.resample`: the same bits, far slower); a rate that is not a whole number of Hz always does.
 RY_CREPE_DTYPE=bf16x3 (default f32) runs the network's GEMMs in split-bf16 form (`CrepeModel.set_dtype`); it is read when a model is built.
 

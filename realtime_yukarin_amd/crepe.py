@@ -1,6 +1,7 @@
 """CREPE pitch tracker on the MI355X: network spec, weights (seeded synthetic, or a `.npz` / torch state-dict file), the host-side
 pieces (the resampler's tables and its host statement, the HMM tables, `predict_voicing`) and `CrepeModel`, the handle over `ry_crepe_*`
-(include/ry355.h), which resamples to 16 kHz, runs the network and decodes on the device.
+(include/ry355.h), which resamples to 16 kHz, runs the network and decodes on the device; `CrepeModel.voicing` is `predict_voicing` and the
+wrapper's mask on the device, `CrepeModel.track` the whole chain in one call (`encode.extract` builds on it).
 
 The reference turns CREPE on with `extract_f0_mode: crepe` (realtime-yukarin: realtime_voice_conversion/config.py:8-10); its
 CrepeAcousticFeatureWrapper.extract_f0 calls `crepe.predict(x, fs, viterbi=True, model_capacity='full', step_size=frame_period)` and
@@ -16,7 +17,9 @@ from typing import Dict, List, Optional, Tuple
 import numpy
 
 from . import _lib
-from ._handle import DeviceHandle, _dptr
+from ._handle import _DP, DeviceHandle, _dptr
+
+_UBP = ctypes.POINTER(ctypes.c_ubyte)
 
 # ---- the network ([MEM], one place) --------------------------------------------------------------------------------------------
 CAPACITIES = {'tiny': 4, 'small': 8, 'medium': 16, 'large': 24, 'full': 32}
@@ -269,6 +272,27 @@ def predict_voicing(confidence) -> numpy.ndarray:
     return path
 
 
+def voicing_tables():
+    """(c [2], mu [2], var [2], logT [2][2], logS [2]) of `predict_voicing` in float64, the logs by the expressions it uses: what
+    `ry_crepe_set_voicing_tables` takes, so that the device's mask equals the host's bit for bit."""
+    mu, var = numpy.asarray(VOICING_MEANS), numpy.asarray(VOICING_VARS)
+    return numpy.log(2 * numpy.pi * var), mu, var, numpy.log(numpy.asarray(VOICING_TRANS)), numpy.log(numpy.asarray(VOICING_START))
+
+
+class DeviceTrack(object):
+    """What `CrepeModel.track(..., device=True)` left on the card: addresses of the uploaded float32 wave (`samples` of it) and of `voiced`
+    (bytes), `f0` and `t` (float64) of `frames` frames.  They belong to the model's handle and hold until its next call; `ctx` is the
+    context whose stream orders the work that reads them (`Analyzer.run_device`)."""
+
+    def __init__(self, model, ctx, wave, samples, frames, voiced, f0, t):
+        self.model, self.ctx = model, ctx
+        self.wave, self.samples, self.frames, self.voiced, self.f0, self.t = wave, samples, frames, voiced, f0, t
+
+    def download(self) -> numpy.ndarray:
+        """voiced [frames] bool, f0 [frames] float64 (waits for the stream)."""
+        return self.model._download_track(self)
+
+
 # ---- the device model ---------------------------------------------------------------------------------------------------------
 class CrepeModel(DeviceHandle):
     """CREPE on the MI355X (`ry_crepe_*`).  Picklable and fork-safe: the GPU context and the device weights are created lazily in the
@@ -302,6 +326,8 @@ class CrepeModel(DeviceHandle):
         self._rs = {}
         tabs = [numpy.ascontiguousarray(t, dtype=numpy.float64) for t in viterbi_tables()]
         lib.check(lib.dll.ry_crepe_set_viterbi_tables(h, *[_dptr(t) for t in tabs]))
+        tabs = [numpy.ascontiguousarray(t, dtype=numpy.float64) for t in voicing_tables()]
+        lib.check(lib.dll.ry_crepe_set_voicing_tables(h, *[_dptr(t) for t in tabs]))
         if self.dtype != 'f32':
             lib.check(lib.dll.ry_crepe_set_dtype(h, DTYPES[self.dtype]))
         return h
@@ -399,6 +425,71 @@ class CrepeModel(DeviceHandle):
                                           path.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return f0, conf, path
 
+    def voicing(self, confidence, f0, threshold: float = 0.1, step_size=10, device: bool = False):
+        """`(predict_voicing(confidence) == 1) | (confidence > threshold)`, the f0 it masks and the time axis, on the device
+        (`ry_crepe_voicing`): confidence, f0 float32 [n] -> (voiced bool [n], f0 float64 [n], 0 where unvoiced, t float64 [n] =
+        arange(n) * step_size / 1000).  The threshold is compared in float32, as numpy compares a float32 array with a Python float.  device=True (tests): the five arrays pass through device buffers of the caller."""
+        lib, h = self._get()
+        c = numpy.ascontiguousarray(confidence, dtype=numpy.float32).ravel()
+        f = numpy.ascontiguousarray(f0, dtype=numpy.float32).ravel()
+        if c.size != f.size or c.size < 1:
+            raise ValueError('voicing needs confidence and f0 of one length >= 1, got %d and %d' % (c.size, f.size))
+        n = c.size
+        voiced, f64, t64 = numpy.empty(n, numpy.uint8), numpy.empty(n, numpy.float64), numpy.empty(n, numpy.float64)
+        args = (n, float(threshold), float(step_size))
+        if not device:
+            lib.check(lib.dll.ry_crepe_voicing(h, _lib._fptr(c), _lib._fptr(f), *args, voiced.ctypes.data_as(_UBP), _dptr(f64), _dptr(t64), 0))
+            return voiced.astype(bool), f64, t64
+        from .world_synth import _DeviceBuffer
+        ctx, dll = self._ctx, lib.dll
+        host = [c, f, numpy.zeros((n + 3) // 4, numpy.float32), f64.view(numpy.float32), t64.view(numpy.float32)]
+        bufs = [_DeviceBuffer(ctx, a.size) for a in host]
+        for a, b in zip(host[:2], bufs[:2]):
+            lib.check(dll.ry_dev_upload(ctx.handle, b.ptr, _lib._fptr(a), a.size))
+        as_ub, as_d = (lambda b: ctypes.cast(b.ptr, _UBP)), (lambda b: ctypes.cast(b.ptr, _DP))
+        lib.check(dll.ry_crepe_voicing(h, bufs[0].ptr, bufs[1].ptr, *args, as_ub(bufs[2]), as_d(bufs[3]), as_d(bufs[4]), 1))
+        for a, b in zip(host[2:], bufs[2:]):
+            lib.check(dll.ry_dev_download(ctx.handle, _lib._fptr(a), b.ptr, a.size))
+        return host[2].view(numpy.uint8)[:n].astype(bool), f64, t64
+
+    def _frames_at(self, n_samples: int, sr: int, hop: int) -> int:
+        n16 = n_samples if sr == MODEL_SRATE else resampled_length(n_samples, sr)
+        n = n_frames(n16, hop, True) if n16 >= 1 else 0
+        if n < 1:
+            raise ValueError('CREPE needs at least one sample at 16 kHz, %d samples at %d Hz give %d' % (n_samples, sr, n16))
+        if sr != MODEL_SRATE:
+            self._resampler(sr, n16)
+        return n
+
+    def track(self, audio, sr, hop: int, step_size, threshold: float = 0.1, device: bool = False):
+        """`predict(audio, sr, hop)` (centred, Viterbi, no activation) and `voicing` of its result in one enqueue, one upload of the wave
+        (`ry_crepe_track`) -> (voiced bool, f0 float64, 0 where unvoiced, t float64).  device=True: nothing is copied back and nothing is
+        waited for -> `DeviceTrack`, the addresses of the track and of the uploaded wave on the card."""
+        sr = _rate(sr)
+        x = numpy.ascontiguousarray(audio, dtype=numpy.float32).ravel()
+        lib, h = self._get()
+        n = self._frames_at(x.size, sr, hop)
+        nf = ctypes.c_int()
+        head = (h, _lib._fptr(x), x.size, sr, int(hop), float(step_size), float(threshold), ctypes.byref(nf))
+        if not device:
+            voiced, f64, t64 = numpy.empty(n, numpy.uint8), numpy.empty(n, numpy.float64), numpy.empty(n, numpy.float64)
+            lib.check(lib.dll.ry_crepe_track(*head, voiced.ctypes.data_as(_UBP), _dptr(f64), _dptr(t64), 0))
+            assert nf.value == n, (nf.value, n)
+            return voiced.astype(bool), f64, t64
+        lib.check(lib.dll.ry_crepe_track(*head, None, None, None, 1))
+        p = [ctypes.c_void_p() for _ in range(4)]
+        ns, nfr = ctypes.c_int(), ctypes.c_int()
+        lib.check(lib.dll.ry_crepe_track_buffers(h, ctypes.byref(p[0]), ctypes.byref(ns), ctypes.byref(nfr), *[ctypes.byref(q) for q in p[1:]]))
+        return DeviceTrack(self, self._ctx, p[0].value, ns.value, nfr.value, p[1].value, p[2].value, p[3].value)
+
+    def _download_track(self, trk):
+        lib, h = self._get()
+        n = trk.frames
+        words, f64 = numpy.empty((n + 3) // 4, numpy.float32), numpy.empty(n, numpy.float64)
+        lib.check(lib.dll.ry_dev_download(trk.ctx.handle, _lib._fptr(words), _lib._fptr(trk.voiced), (n + 3) // 4))
+        lib.check(lib.dll.ry_dev_download(trk.ctx.handle, _lib._fptr(f64.view(numpy.float32)), _lib._fptr(trk.f0), 2 * n))
+        return words.view(numpy.uint8)[:n].astype(bool), f64
+
     def debug_layer(self, layer: int, frames: int) -> numpy.ndarray:
         """The first `frames` rows of the last pass's buffer `layer` (0 frames, 1 .. 6 pooled conv outputs, 7 logits); rows behind the
         frames of that pass are what an earlier call or `poison` left (`ry_crepe_debug_layer`)."""
@@ -410,8 +501,8 @@ class CrepeModel(DeviceHandle):
         return out
 
     def poison(self) -> None:
-        """Tests: NaN bit patterns in everything the next `resample` / `predict` / `predict16k` / `decode` must write
-        (`ry_crepe_debug_poison`)."""
+        """Tests: NaN bit patterns in everything the next `resample` / `predict` / `predict16k` / `decode` / `voicing` / `track` must
+        write (`ry_crepe_debug_poison`)."""
         lib, h = self._get()
         lib.check(lib.dll.ry_crepe_debug_poison(h))
 

@@ -3,6 +3,8 @@
 // analysis_kernels.h.  Stateless per frame: a call uploads the wave, f0 and the frame times, launches one workgroup per frame and copies
 // back what was asked for; the float32 rows go to a device buffer of the caller (world_synth.DeviceRows, stage 2) and never leave the card.
 // D4C (`pyworld.d4c` + `pyworld.code_aperiodicity`: ap and coded_ap; kernel: d4c_kernels.h) runs over the same uploaded wave.
+// ry_analysis_extract_dev takes the wave (float32) and the track from device memory instead -- what ry_crepe_track left there: the wave is widened
+// on the card, the track is checked by a kernel whose verdict the host reads before it launches the same frame kernels.
 #include "analysis_kernels.h"
 #include "d4c_kernels.h"
 #include "ry_host.h"
@@ -30,6 +32,7 @@ struct ry_analysis {
     double* nuttall = nullptr;                        // [2 band_half + 1]
     DevBuf<double> d_ap{scratch}, d_coded{scratch};
     DevBuf<D4cFrameRecord> d_rec{scratch};
+    DevBuf<int> d_verdict{scratch};                   // ry_analysis_extract_dev: (first refused frame or -1, kind) of the track check
     std::vector<D4cFrameRecord> last_rec;             // ry_analysis_debug_d4c: a0, on / off, integers and coarse values of the last recorded run
 };
 
@@ -91,19 +94,29 @@ struct Outputs {
     double* ap64 = nullptr; float* ap32_dev = nullptr; double* coded = nullptr;
 };
 
-// one upload of the wave and the track, then CheapTrick + sp2mc (when `cheaptrick`) and / or D4C (when o.d4c) over it
-int run_frames(ry_analysis* s, const double* x, long long x_len, const double* f0, const double* t, int n, bool cheaptrick, const Outputs& o) {
+// what every entry refuses before it looks at the wave or the track; *empty: nothing to analyse, nothing is written
+int check_call(ry_analysis* s, long long x_len, int n, bool cheaptrick, const Outputs& o, bool* empty) {
     RY_TRY(check_handle(s, "analysis"));
     if (n < 0) return fail(RY_EINVAL, "n = %d frames", n);
     if (x_len < 0) return fail(RY_EINVAL, "x_len = %lld", x_len);
     if (n > (1 << 22)) return fail(RY_EINVAL, "%d frames in one call", n);
     if (o.d4c && !s->d4c_ok) return fail(RY_EINVAL, "%s", s->d4c_why.c_str());
     if (o.d4c && !std::isfinite(o.threshold)) return fail(RY_EINVAL, "threshold %g", o.threshold);
-    if (n == 0 || x_len == 0) {                                             // nothing to analyse: nothing is written
+    *empty = n == 0 || x_len == 0;
+    if (*empty) {
         if (cheaptrick) s->last_ints.clear();
         if (o.d4c) s->last_rec.clear();
-        return RY_OK;
     }
+    return RY_OK;
+}
+
+int run_kernels(ry_analysis* s, const double* d_x, long long x_len, const double* d_f0, const double* d_t, int n, bool cheaptrick, const Outputs& o);
+
+// one upload of the wave and the track, then CheapTrick + sp2mc (when `cheaptrick`) and / or D4C (when o.d4c) over it
+int run_frames(ry_analysis* s, const double* x, long long x_len, const double* f0, const double* t, int n, bool cheaptrick, const Outputs& o) {
+    bool empty = false;
+    RY_TRY(check_call(s, x_len, n, cheaptrick, o, &empty));
+    if (empty) return RY_OK;
     if (!x) return fail(RY_EINVAL, "null wave");
     if (!f0 || !t) return fail(RY_EINVAL, "null f0 / t");
     for (int i = 0; i < n; ++i) {
@@ -114,6 +127,15 @@ int run_frames(ry_analysis* s, const double* x, long long x_len, const double* f
     RY_TRY(s->d_x.grow(s->ctx, x_len));
     RY_TRY(s->d_f0.grow(s->ctx, (long long)n));
     RY_TRY(s->d_t.grow(s->ctx, (long long)n));
+    RT_TRY(rt::h2d(s->d_x.ptr(), x, (size_t)x_len * sizeof(double), st));
+    RT_TRY(rt::h2d(s->d_f0.ptr(), f0, (size_t)n * sizeof(double), st));
+    RT_TRY(rt::h2d(s->d_t.ptr(), t, (size_t)n * sizeof(double), st));
+    return run_kernels(s, s->d_x.ptr(), x_len, s->d_f0.ptr(), s->d_t.ptr(), n, cheaptrick, o);
+}
+
+// the frame kernels over a wave and a track in device memory, and the copies of what was asked for
+int run_kernels(ry_analysis* s, const double* d_x, long long x_len, const double* d_f0, const double* d_t, int n, bool cheaptrick, const Outputs& o) {
+    const ry_stream_t st = s->ctx->stream;
     if (cheaptrick) {
         if (s->record) RY_TRY(s->d_ints.grow(s->ctx, (long long)n));
         if (o.sp64) RY_TRY(s->d_sp.grow(s->ctx, (long long)n * SYNTH_BINS));
@@ -124,12 +146,9 @@ int run_frames(ry_analysis* s, const double* x, long long x_len, const double* f
         if (o.ap64) RY_TRY(s->d_ap.grow(s->ctx, (long long)n * SYNTH_BINS));
         if (o.coded) RY_TRY(s->d_coded.grow(s->ctx, (long long)n * s->n_bands));
     }
-    RT_TRY(rt::h2d(s->d_x.ptr(), x, (size_t)x_len * sizeof(double), st));
-    RT_TRY(rt::h2d(s->d_f0.ptr(), f0, (size_t)n * sizeof(double), st));
-    RT_TRY(rt::h2d(s->d_t.ptr(), t, (size_t)n * sizeof(double), st));
     if (cheaptrick) {
         AnalysisParams p;
-        p.x = s->d_x.ptr(); p.x_len = x_len; p.f0 = s->d_f0.ptr(); p.t = s->d_t.ptr();
+        p.x = d_x; p.x_len = x_len; p.f0 = d_f0; p.t = d_t;
         p.fs = (double)s->fs; p.floor_f0 = s->floor_f0; p.q1 = s->q1; p.seed_hash = s->seed_hash;
         p.tw = s->tw; p.S = s->S; p.n_mc = s->order + 1;
         p.sp64 = o.sp64 ? s->d_sp.ptr() : nullptr; p.sp32 = o.sp32_dev; p.mc = o.mc ? s->d_mc.ptr() : nullptr; p.ints = s->record ? s->d_ints.ptr() : nullptr;
@@ -138,7 +157,7 @@ int run_frames(ry_analysis* s, const double* x, long long x_len, const double* f
     }
     if (o.d4c) {
         D4cParams p;
-        p.x = s->d_x.ptr(); p.x_len = x_len; p.f0 = s->d_f0.ptr(); p.t = s->d_t.ptr();
+        p.x = d_x; p.x_len = x_len; p.f0 = d_f0; p.t = d_t;
         p.fs = (double)s->fs; p.threshold = o.threshold; p.seed_hash = s->seed_hash;
         p.tw = s->tw; p.tw2 = s->tw2; p.nuttall = s->nuttall;
         p.n_bands = s->n_bands; p.band_half = s->band_half;
@@ -219,6 +238,42 @@ int ry_analysis_extract(ry_analysis* s, const double* x, long long x_len, const 
     o.sp64 = sp64_out; o.sp32_dev = sp32_dev_out; o.mc = mc_out;
     o.d4c = true; o.threshold = threshold; o.ap64 = ap64_out; o.ap32_dev = ap32_dev_out; o.coded = coded_out;
     return run_frames(s, x, x_len, f0, t, n, true, o);
+}
+
+int ry_analysis_extract_dev(ry_analysis* s, const float* x32_dev, long long x_len, const double* f0_dev, const double* t_dev, int n, double threshold,
+                            double* sp64_out, float* sp32_dev_out, double* mc_out, double* ap64_out, float* ap32_dev_out, double* coded_out) {
+    Outputs o;
+    o.sp64 = sp64_out; o.sp32_dev = sp32_dev_out; o.mc = mc_out;
+    o.d4c = true; o.threshold = threshold; o.ap64 = ap64_out; o.ap32_dev = ap32_dev_out; o.coded = coded_out;
+    bool empty = false;
+    RY_TRY(check_call(s, x_len, n, true, o, &empty));
+    if (empty) return RY_OK;
+    if (!x32_dev) return fail(RY_EINVAL, "null wave");
+    if (!f0_dev || !t_dev) return fail(RY_EINVAL, "null f0 / t");
+    const ry_stream_t st = s->ctx->stream;
+    RY_TRY(s->d_x.grow(s->ctx, x_len));
+    RY_TRY(s->d_verdict.reserve(s->ctx, 2));
+    AnalysisCheckParams cp;
+    cp.f0 = f0_dev; cp.t = t_dev; cp.n = n; cp.fs = (double)s->fs; cp.verdict = s->d_verdict.ptr();
+    RY_LAUNCH(analysis_check_track, dim3(1), 256, st, cp);
+    RT_TRY(rt::last_error());
+    int verdict[2] = {0, 0};
+    RT_TRY(rt::d2h(verdict, s->d_verdict.ptr(), sizeof verdict, st));
+    AnalysisWidenParams wp;
+    wp.x32 = x32_dev; wp.x64 = s->d_x.ptr(); wp.n = x_len;
+    RY_LAUNCH(analysis_widen, dim3((unsigned)((x_len + 255) / 256)), 256, st, wp);       // behind the copy: it runs while the host waits for the verdict
+    RT_TRY(rt::last_error());
+    RT_TRY(rt::stream_sync(st));
+    if (verdict[0] >= 0 && verdict[0] < n) {                            // the refusal's values, for the message
+        double v[2] = {0.0, 0.0};
+        RT_TRY(rt::d2h(&v[0], f0_dev + verdict[0], sizeof(double), st));
+        RT_TRY(rt::d2h(&v[1], t_dev + verdict[0], sizeof(double), st));
+        RT_TRY(rt::stream_sync(st));
+        if (verdict[1] == 1) return fail(RY_EINVAL, "f0[%d] = %g: finite and below fs / 2", verdict[0], v[0]);
+        return fail(RY_EINVAL, "t[%d] = %g: -1 .. 1e6 s", verdict[0], v[1]);
+    }
+    if (verdict[0] != -1) return fail(RY_ESTATE, "the track check left %d", verdict[0]);
+    return run_kernels(s, s->d_x.ptr(), x_len, f0_dev, t_dev, n, true, o);
 }
 
 int ry_analysis_d4c_bands(ry_analysis* s) {

@@ -247,3 +247,41 @@ RY_KERNEL(256) void analysis_sp2mc(AnalysisSp2mcParams p) {
     __syncthreads();
     analysis_freqt(cp, p.S, p.n_mc, red, p.mc + (size_t)blockIdx.x * p.n_mc);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Inputs that are already on the card (ry_analysis_extract_dev).
+//   analysis_widen        the float32 wave another unit uploaded -> the analyzer's float64 wave: (double)x is exact, so the frame kernels see
+//                         the bits of the host's `wave.astype(float64)`.
+//   analysis_check_track  the refusals ry_analysis_run makes on the host, on a device track: ONE workgroup finds the first frame whose f0 is
+//                         not finite or not below fs / 2 (kind 1) or whose t is outside -1 .. 1e6 s (kind 2) and leaves (frame, kind), or
+//                         (-1, 0), in verdict[0 .. 1].  The host reads the two words before it launches a frame kernel.
+// ---------------------------------------------------------------------------------------------
+struct AnalysisWidenParams { const float* x32; double* x64; long long n; };
+
+RY_KERNEL(256) void analysis_widen(AnalysisWidenParams p) {
+    const long long i = (long long)blockIdx.x * 256 + (long long)threadIdx.x;
+    if (i < p.n) p.x64[i] = (double)p.x32[i];
+}
+
+struct AnalysisCheckParams { const double* f0; const double* t; int n; double fs; int* verdict; };
+
+RY_KERNEL(256) void analysis_check_track(AnalysisCheckParams p) {
+    __shared__ int first[256];
+    const int tid = (int)threadIdx.x;
+    int bad = p.n;
+    for (int i = tid; i < p.n; i += 256) {
+        const double f = p.f0[i], t = p.t[i];
+        const bool ok = f - f == 0.0 && f < 0.5 * p.fs && t >= -1.0 && t <= 1e6;      // f - f: NaN for NaN and the infinities
+        if (!ok) { bad = i; break; }
+    }
+    first[tid] = bad;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w && first[tid + w] < first[tid]) first[tid] = first[tid + w]; __syncthreads(); }
+    if (tid == 0) {
+        const int k = first[0];
+        int kind = 0;
+        if (k < p.n) { const double f = p.f0[k]; kind = (f - f == 0.0 && f < 0.5 * p.fs) ? 2 : 1; }
+        p.verdict[0] = k < p.n ? k : -1;
+        p.verdict[1] = kind;
+    }
+}

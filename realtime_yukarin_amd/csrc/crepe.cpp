@@ -4,6 +4,8 @@
 // The frames of a call run in passes of at most CHUNK frames; the activation of every frame is kept for the decode, which runs once.
 // Audio at another rate is resampled to 16 kHz on the device first (crepe_resample; the filter and the time register of each rate are
 // tables the caller installs, ry_crepe_set_resampler).
+// ry_crepe_voicing turns the decode's (confidence, f0) into the voiced mask, the masked float64 f0 and the time axis (crepe_voicing: the two-state HMM
+// of `predict_voicing`); ry_crepe_track is predict + voicing in one enqueue, the track left on the card for ry_analysis_extract_dev.
 // ry_crepe_set_dtype(2) runs the seven GEMMs in split-bf16 form (crepe_igemm_x3) on filters split once into two bf16 planes; everything else is shared.
 #include "crepe_kernels.h"
 #include "ry_host.h"
@@ -70,6 +72,13 @@ struct ry_crepe {
     DevBufList call;
     DevBuf<float> audio{call}, audio_sr{call}, act{call}, conf{call}, f0{call};
     DevBuf<int> obs{call}, bp{call}, path{call};
+    // voicing: the HMM's constants (they travel as kernel arguments), its back-pointer bytes, and the masked track of the last call
+    CrepeVoicingTables vt;
+    DevBuf<unsigned char> v_bp{call}, voiced{call};
+    DevBuf<double> f0_64{call}, t_64{call};
+    // what the last ry_crepe_track left on the card (ry_crepe_track_buffers); every other call that writes one of these buffers forgets it
+    const float* trk_wave = nullptr;
+    int trk_samples = 0, trk_frames = 0;
     // resampling: tables per input rate
     Arena rs_tables;
     std::map<int, Resampler> rs;
@@ -204,6 +213,7 @@ int run_network(ry_crepe* c, const float* d_audio, int n_samples, int hop, int c
         c->last_chunk = n;
     }
     RY_TRY(launch_decode(c, act_all, nf, viterbi));
+    if (!f0 && !confidence && !activation) return RY_OK;                // ry_crepe_track: the results stay in the handle's buffers
     if (on_device) {
         RT_TRY(rt::d2d(f0, c->f0.ptr(), (size_t)nf * sizeof(float), s));
         RT_TRY(rt::d2d(confidence, c->conf.ptr(), (size_t)nf * sizeof(float), s));
@@ -245,6 +255,31 @@ int launch_resample(ry_crepe* c, const Resampler& r, const float* d_in, int n_in
     p.num_table = r.num_table; p.step = r.step; p.y = d_out; p.n_out = n_out;
     RY_LAUNCH(crepe_resample, dim3((unsigned)((n_out + 255) / 256)), 256, c->ctx->stream, p);
     RT_TRY(rt::last_error());
+    return RY_OK;
+}
+
+// the voicing of n frames whose confidence / f0 are in device memory, into device buffers (the handle's own, or a device caller's)
+int launch_voicing(ry_crepe* c, const float* conf, const float* f0, int n, double threshold, double step_ms,
+                   unsigned char* voiced, double* f0_64, double* t_64) {
+    RY_TRY(c->v_bp.reserve(c->ctx, n));
+    CrepeVoicingParams p;
+    p.conf = conf; p.f0 = f0; p.n = n; p.threshold = (float)threshold; p.step_ms = step_ms; p.tab = c->vt;
+    p.bp = c->v_bp.ptr(); p.voiced = voiced; p.f0_64 = f0_64; p.t_64 = t_64;
+    RY_LAUNCH(crepe_voicing, dim3(1), 256, c->ctx->stream, p);
+    RT_TRY(rt::last_error());
+    return RY_OK;
+}
+
+int ensure_track(ry_crepe* c, int n) {
+    RY_TRY(c->voiced.reserve(c->ctx, ((long long)n + 3) / 4 * 4));      // whole 32-bit words: ry_dev_download copies those
+    RY_TRY(c->f0_64.reserve(c->ctx, n));
+    RY_TRY(c->t_64.reserve(c->ctx, n));
+    return RY_OK;
+}
+
+int voicing_args(double threshold, double step_ms) {
+    if (std::isnan(threshold)) return fail(RY_EINVAL, "threshold %g", threshold);
+    if (!std::isfinite(step_ms) || !(step_ms > 0.0)) return fail(RY_EINVAL, "step %g ms", step_ms);
     return RY_OK;
 }
 }  // namespace
@@ -344,6 +379,15 @@ int ry_crepe_create(ry_ctx* ctx, int capacity, const float* weights, size_t n_fl
     RY_TRY(upload_table(c->weights, ctx, lt.data(), lt.size(), &c->logT));
     RY_TRY(upload_table(c->weights, ctx, le.data(), le.size(), &c->logE));
     RY_TRY(upload_table(c->weights, ctx, ls.data(), ls.size(), &c->logS));
+    // the HMM of the voicing ([MEM]: start, transition, means, variances of `predict_voicing`; state 1 = voiced), logs from the C library
+    // (the Python layer replaces them by numpy's own values, ry_crepe_set_voicing_tables)
+    const double v_start[2] = {0.7472, 0.2528}, v_trans[2][2] = {{0.9991, 0.0009}, {0.0025, 0.9975}};
+    const double v_mu[2] = {0.0795, 0.6278}, v_var[2] = {0.0181, 0.0454};
+    for (int i = 0; i < 2; ++i) {
+        c->vt.c[i] = std::log(2 * 3.141592653589793 * v_var[i]); c->vt.mu[i] = v_mu[i]; c->vt.var[i] = v_var[i];
+        c->vt.logS[i] = std::log(v_start[i]);
+        for (int j = 0; j < 2; ++j) c->vt.logT[i][j] = std::log(v_trans[i][j]);
+    }
     *out = c.release();
     return RY_OK;
 }
@@ -380,6 +424,7 @@ int ry_crepe_predict(ry_crepe* c, const float* audio, int n_samples, int hop, in
                      float* f0, float* confidence, float* activation, int on_device) {
     RY_TRY(check_handle(c, "crepe"));
     if (!audio || !f0 || !confidence || n_samples < 1 || hop < 1) return fail(RY_EINVAL, "bad argument");
+    c->trk_frames = 0;
     int nf = 0;
     RY_TRY(frame_count(n_samples, hop, center, &nf));
     ry_ctx* ctx = c->ctx;
@@ -424,6 +469,7 @@ int ry_crepe_set_resampler(ry_crepe* c, int sr, const double* win, int n_win, in
 int ry_crepe_resample(ry_crepe* c, const float* audio, int n_samples, int sr, float* out16k, int on_device) {
     RY_TRY(check_handle(c, "crepe"));
     if (!audio || !out16k) return fail(RY_EINVAL, "bad argument");
+    c->trk_frames = 0;
     const Resampler* r = nullptr;
     int n_out = 0;
     RY_TRY(resample_plan(c, n_samples, sr, &r, &n_out));
@@ -443,6 +489,7 @@ int ry_crepe_predict_sr(ry_crepe* c, const float* audio, int n_samples, int sr, 
     if (sr == 16000) return ry_crepe_predict(c, audio, n_samples, hop, center, viterbi, f0, confidence, activation, on_device);
     RY_TRY(check_handle(c, "crepe"));
     if (!audio || !f0 || !confidence || hop < 1) return fail(RY_EINVAL, "bad argument");
+    c->trk_frames = 0;
     const Resampler* r = nullptr;
     int n_out = 0, nf = 0;
     RY_TRY(resample_plan(c, n_samples, sr, &r, &n_out));
@@ -463,6 +510,7 @@ int ry_crepe_predict_sr(ry_crepe* c, const float* audio, int n_samples, int sr, 
 int ry_crepe_decode(ry_crepe* c, const float* activation, int n_frames, int viterbi, float* f0, float* confidence, int* path) {
     RY_TRY(check_handle(c, "crepe"));
     if (!activation || !f0 || !confidence || n_frames < 1 || n_frames > (1 << 24)) return fail(RY_EINVAL, "bad argument");
+    c->trk_frames = 0;
     const ry_stream_t s = c->ctx->stream;
     RY_TRY(ensure_call(c, n_frames, 0));
     RT_TRY(rt::h2d(c->act.ptr(), activation, (size_t)n_frames * CREPE_BINS * sizeof(float), s));
@@ -471,6 +519,88 @@ int ry_crepe_decode(ry_crepe* c, const float* activation, int n_frames, int vite
     RT_TRY(rt::d2h(confidence, c->conf.ptr(), (size_t)n_frames * sizeof(float), s));
     if (path) RT_TRY(rt::d2h(path, viterbi ? c->path.ptr() : c->obs.ptr(), (size_t)n_frames * sizeof(int), s));
     RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+int ry_crepe_set_voicing_tables(ry_crepe* c, const double* cst, const double* mu, const double* var, const double* logT, const double* logS) {
+    if (!c || !cst || !mu || !var || !logT || !logS) return fail(RY_EINVAL, "bad argument");
+    for (int i = 0; i < 2; ++i) {
+        if (!std::isfinite(cst[i]) || !std::isfinite(mu[i]) || !(var[i] > 0.0) || !std::isfinite(var[i]) || std::isnan(logS[i]) || std::isnan(logT[2 * i]) ||
+            std::isnan(logT[2 * i + 1]))
+            return fail(RY_EINVAL, "voicing tables: state %d", i);
+    }
+    for (int i = 0; i < 2; ++i) {                                     // kernel arguments of the calls that follow: nothing in flight reads them
+        c->vt.c[i] = cst[i]; c->vt.mu[i] = mu[i]; c->vt.var[i] = var[i]; c->vt.logS[i] = logS[i];
+        c->vt.logT[i][0] = logT[2 * i]; c->vt.logT[i][1] = logT[2 * i + 1];
+    }
+    return RY_OK;
+}
+
+int ry_crepe_voicing(ry_crepe* c, const float* confidence, const float* f0, int n, double threshold, double step_ms,
+                     unsigned char* voiced, double* f0_64, double* t_64, int on_device) {
+    RY_TRY(check_handle(c, "crepe"));
+    if (!confidence || !f0 || !voiced || !f0_64 || !t_64 || n < 1 || n > (1 << 24)) return fail(RY_EINVAL, "bad argument");
+    RY_TRY(voicing_args(threshold, step_ms));
+    c->trk_frames = 0;
+    if (on_device) return launch_voicing(c, confidence, f0, n, threshold, step_ms, voiced, f0_64, t_64);
+    const ry_stream_t s = c->ctx->stream;
+    RY_TRY(c->conf.reserve(c->ctx, n));
+    RY_TRY(c->f0.reserve(c->ctx, n));
+    RY_TRY(ensure_track(c, n));
+    RT_TRY(rt::h2d(c->conf.ptr(), confidence, (size_t)n * sizeof(float), s));
+    RT_TRY(rt::h2d(c->f0.ptr(), f0, (size_t)n * sizeof(float), s));
+    RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), n, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr()));
+    RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)n, s));
+    RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)n * sizeof(double), s));
+    RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)n * sizeof(double), s));
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+int ry_crepe_track(ry_crepe* c, const float* audio, int n_samples, int sr, int hop, double step_ms, double threshold, int* n_frames,
+                   unsigned char* voiced, double* f0_64, double* t_64, int on_device_out) {
+    RY_TRY(check_handle(c, "crepe"));
+    if (!audio || !n_frames || n_samples < 1 || hop < 1) return fail(RY_EINVAL, "bad argument");
+    if (!on_device_out && (!voiced || !f0_64 || !t_64)) return fail(RY_EINVAL, "null output");
+    RY_TRY(voicing_args(threshold, step_ms));
+    c->trk_frames = 0;
+    const ry_stream_t s = c->ctx->stream;
+    const Resampler* r = nullptr;
+    int n16 = n_samples, nf = 0;
+    if (sr != 16000) RY_TRY(resample_plan(c, n_samples, sr, &r, &n16));
+    RY_TRY(frame_count(n16, hop, 1, &nf));
+    RY_TRY(ensure_chunk(c, std::min(nf, CHUNK)));
+    RY_TRY(ensure_call(c, nf, n16));
+    RY_TRY(ensure_track(c, nf));
+    float* wave = c->audio.ptr();                                    // the one upload: the wave at the caller's rate
+    if (r) {
+        RY_TRY(c->audio_sr.reserve(c->ctx, n_samples));
+        wave = c->audio_sr.ptr();
+    }
+    RT_TRY(rt::h2d(wave, audio, (size_t)n_samples * sizeof(float), s));
+    if (r) RY_TRY(launch_resample(c, *r, wave, n_samples, sr, c->audio.ptr(), n16));
+    RY_TRY(run_network(c, c->audio.ptr(), n16, hop, 1, 1, nf, nullptr, nullptr, nullptr, 1));
+    RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), nf, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr()));
+    c->trk_wave = wave; c->trk_samples = n_samples; c->trk_frames = nf;
+    *n_frames = nf;
+    if (on_device_out) return RY_OK;
+    RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)nf, s));
+    RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)nf * sizeof(double), s));
+    RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)nf * sizeof(double), s));
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+int ry_crepe_track_buffers(ry_crepe* c, const float** wave_dev, int* n_samples, int* n_frames, const unsigned char** voiced_dev,
+                           const double** f0_dev, const double** t_dev) {
+    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    if (c->trk_frames < 1) return fail(RY_ESTATE, "no track on the card: ry_crepe_track has not run, or a later call reused its buffers");
+    if (wave_dev) *wave_dev = c->trk_wave;
+    if (n_samples) *n_samples = c->trk_samples;
+    if (n_frames) *n_frames = c->trk_frames;
+    if (voiced_dev) *voiced_dev = c->voiced.ptr();
+    if (f0_dev) *f0_dev = c->f0_64.ptr();
+    if (t_dev) *t_dev = c->t_64.ptr();
     return RY_OK;
 }
 
@@ -516,7 +646,8 @@ int ry_crepe_debug_poison(ry_crepe* c) {
         RT_TRY(rt::dmemset(c->logits, 0xff, (size_t)c->cap_chunk * CREPE_BINS * sizeof(float), s));
         RT_TRY(rt::dmemset(c->slabs, 0xff, c->slab_floats * sizeof(float), s));
     }
-    for (DevBufBase* b : c->call) RY_TRY(b->poison(s));
+    for (DevBufBase* b : c->call) RY_TRY(b->poison(s));               // the voicing's back-pointers and the masked track are on this list too
+    c->trk_frames = 0;
     RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }

@@ -1,7 +1,8 @@
 // crepe_kernels.h -- the kernels of the CREPE pitch tracker (crepe.cpp): framing, one implicit-GEMM 1-D convolution family on
 // v_mfma_f32_32x32x2_f32 (conv1 .. conv6 and the dense classifier) and its split-bf16 form on v_mfma_f32_32x32x16_bf16, the split-K reduction with the
 // same epilogues, and the decode
-// (per-frame argmax / max, the 360-state Viterbi pass in float64, the local-average cents).
+// (per-frame argmax / max, the 360-state Viterbi pass in float64, the local-average cents), and the voicing of the track (a two-state Viterbi
+// pass over the confidence, the masked float64 f0 and the time axis).
 // Semantics restated from the public crepe package and its PyTorch fork ([MEM]; INTEGRATION.md section 9 lists what is unpinned).
 //
 // Activations are channels-last with every frame's 'same' padding stored as zero rows, so the kernels never test an edge:
@@ -541,5 +542,97 @@ RY_KERNEL(384) void crepe_decode(CrepeDecodeParams p) {
         }
         const double f = 10.0 * exp2((ps / ws) / 1200.0);
         p.f0[t] = CREPE_ISNAN(f) ? 0.f : (float)f;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Voicing (`predict_voicing` of realtime_yukarin_amd/crepe.py and the mask the reference's wrapper makes of it): the Viterbi path of a
+// two-state Gaussian HMM over the confidence, voiced = (path == 1) | (confidence > threshold) -- the comparison in float32 against the threshold
+// rounded to float32, which is how numpy evaluates `confidence > 0.1` on a float32 array -- the masked f0 and the time axis in float64.
+// ONE workgroup; the frames run in chunks of CREPE_VOICING_CHUNK through the LDS, so a call may be of any length:
+//   forward, chunk by chunk: every lane computes logp[t][s] = -0.5 * (c[s] + (x - mu[s]) * (x - mu[s]) / var[s]) of its frames into the LDS; lane 0
+//     walks the chunk -- s[i][j] = lat[i] + logT[i][j], bp[j] = s[1][j] > s[0][j] (the lowest state wins a tie), lat[j] = s[bp[j]][j] + logp[t][j],
+//     the lattice in its registers from chunk to chunk -- and leaves the two back-pointer bits of every frame in the LDS; every lane copies them out
+//     (one byte per frame in global memory).
+//   backward, chunk by chunk from the end: every lane fetches the chunk's back-pointers, lane 0 follows them from the state it arrived with, then
+//     every lane writes voiced, f0_64 = voiced ? (double)f0 : 0 and t_64 = k * step_ms / 1000 of its frames.
+// Float64, every operation rounded on its own and in numpy's order (no fma); the constants are the host's (ry_crepe_set_voicing_tables): no
+// logarithm is taken here.  What lane 0 loads inside its walks does not depend on the lattice, so the loads run ahead of the arithmetic.
+// ---------------------------------------------------------------------------------------------
+#define CREPE_VOICING_CHUNK 1024
+
+struct CrepeVoicingTables { double c[2], mu[2], var[2], logT[2][2], logS[2]; };      // c[s] = log(2 pi var[s]); logT [from][to]
+
+struct CrepeVoicingParams {
+    const float* conf; const float* f0; int n;     // [n]
+    float threshold;                               // compared in float32, as numpy compares a float32 array with a Python float
+    double step_ms;
+    CrepeVoicingTables tab;
+    unsigned char* bp;                             // [n] scratch: bit j of entry t = the state before state j of frame t
+    unsigned char* voiced; double* f0_64; double* t_64;
+};
+
+RY_KERNEL(256) void crepe_voicing(CrepeVoicingParams p) {
+#pragma clang fp contract(off)
+    __shared__ double lp[CREPE_VOICING_CHUNK][2];
+    __shared__ unsigned char bits[CREPE_VOICING_CHUNK];            // forward: back-pointer bits; backward: the same, then the path
+    const int tid = (int)threadIdx.x;
+    const int n = p.n;
+    const CrepeVoicingTables& T = p.tab;
+    double lat0 = 0.0, lat1 = 0.0;                                 // lane 0 only
+    for (int base = 0; base < n; base += CREPE_VOICING_CHUNK) {
+        const int m = n - base < CREPE_VOICING_CHUNK ? n - base : CREPE_VOICING_CHUNK;
+        for (int i = tid; i < m; i += 256) {
+            const double x = (double)p.conf[base + i];
+            const double d0 = x - T.mu[0], d1 = x - T.mu[1];
+            lp[i][0] = -0.5 * (T.c[0] + d0 * d0 / T.var[0]);
+            lp[i][1] = -0.5 * (T.c[1] + d1 * d1 / T.var[1]);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int i = 0;
+            if (base == 0) {
+                lat0 = T.logS[0] + lp[0][0];
+                lat1 = T.logS[1] + lp[0][1];
+                bits[0] = 0;
+                i = 1;
+            }
+            for (; i < m; ++i) {
+                const double s00 = lat0 + T.logT[0][0], s10 = lat1 + T.logT[1][0];
+                const double s01 = lat0 + T.logT[0][1], s11 = lat1 + T.logT[1][1];
+                const bool b0 = s10 > s00, b1 = s11 > s01;
+                lat0 = (b0 ? s10 : s00) + lp[i][0];
+                lat1 = (b1 ? s11 : s01) + lp[i][1];
+                bits[i] = (unsigned char)((b0 ? 1 : 0) | (b1 ? 2 : 0));
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < m; i += 256) p.bp[base + i] = bits[i];
+        __syncthreads();                                           // bits and lp are free for the next chunk; the stores are visible to the workgroup
+    }
+    int carry = lat1 > lat0 ? 1 : 0;                               // lane 0 only: the state of the last frame, then of the frame before the chunk
+    const int last = n > 0 ? (n - 1) / CREPE_VOICING_CHUNK * CREPE_VOICING_CHUNK : -1;
+    for (int base = last; base >= 0; base -= CREPE_VOICING_CHUNK) {
+        const int m = n - base < CREPE_VOICING_CHUNK ? n - base : CREPE_VOICING_CHUNK;
+        for (int i = tid; i < m; i += 256) bits[i] = p.bp[base + i];
+        __syncthreads();
+        if (tid == 0) {
+            int st = carry;
+            for (int i = m - 1; i >= 0; --i) {
+                const int b = bits[i];
+                bits[i] = (unsigned char)st;
+                st = (b >> st) & 1;                                // frame 0 has no predecessor: its bits are 0 and nothing reads the result
+            }
+            carry = st;
+        }
+        __syncthreads();
+        for (int i = tid; i < m; i += 256) {
+            const int k = base + i;
+            const bool v = bits[i] == 1 || p.conf[k] > p.threshold;
+            p.voiced[k] = v ? 1 : 0;
+            p.f0_64[k] = v ? (double)p.f0[k] : 0.0;
+            p.t_64[k] = (double)k * p.step_ms / 1000.0;
+        }
+        __syncthreads();
     }
 }

@@ -27,7 +27,7 @@ from typing import Optional
 import numpy
 
 from . import _lib, sptk
-from ._handle import DeviceHandle, EngineForTests, _dptr
+from ._handle import _DP, DeviceHandle, EngineForTests, _dptr
 from .world_synth import BINS, FFT_SIZE, DeviceRows, _DeviceBuffer, cheaptrick_fft_size
 
 _LLP = ctypes.POINTER(ctypes.c_longlong)
@@ -68,9 +68,7 @@ class Analyzer(DeviceHandle):
         No frames: empty arrays; frames but an empty wave: ValueError (the C ABI would succeed and write nothing, and the rows would no longer
         match `f0`)."""
         lib, h = self._get()
-        unknown = set(want) - {'sp', 'mc', 'sp64', 'ap', 'ap64', 'coded_ap'}
-        if unknown:
-            raise ValueError('want: %s' % sorted(unknown))
+        self._check_want(want)
         x = numpy.ascontiguousarray(numpy.asarray(x, dtype=numpy.float64).reshape(-1))
         f0 = numpy.ascontiguousarray(numpy.asarray(f0, dtype=numpy.float64).reshape(-1))
         t = numpy.ascontiguousarray(numpy.asarray(t, dtype=numpy.float64).reshape(-1))
@@ -79,10 +77,28 @@ class Analyzer(DeviceHandle):
         n = f0.size
         if n > 0 and x.size == 0:
             raise ValueError('an empty wave cannot be analysed at %d frames' % n)
-        sp64 = numpy.empty((n, BINS), numpy.float64) if ('sp64' in want or ('sp' in want and not device_rows)) else None
-        mc = numpy.empty((n, self.order + 1), numpy.float64) if 'mc' in want else None
         d4c = bool(set(want) & {'ap', 'ap64', 'coded_ap'})
         cheaptrick = bool(set(want) & {'sp', 'sp64', 'mc'}) or not d4c
+        got, out_sp, out_ap = self._outputs(n, want, device_rows)
+        head = (h, _dptr(x), x.size, _dptr(f0), _dptr(t), n)
+        if not d4c:
+            lib.check(lib.dll.ry_analysis_run(*(head + out_sp)))
+        elif not cheaptrick:
+            lib.check(lib.dll.ry_analysis_d4c(*(head + (float(threshold),) + out_ap)))
+        else:
+            lib.check(lib.dll.ry_analysis_extract(*(head + (float(threshold),) + out_sp + out_ap)))
+        return tuple(got[k] for k in want)
+
+    @staticmethod
+    def _check_want(want) -> None:
+        unknown = set(want) - {'sp', 'mc', 'sp64', 'ap', 'ap64', 'coded_ap'}
+        if unknown:
+            raise ValueError('want: %s' % sorted(unknown))
+
+    def _outputs(self, n: int, want, device_rows: bool):
+        """The arrays of a call of n frames -> (what `want` names, the CheapTrick output arguments, the D4C output arguments)."""
+        sp64 = numpy.empty((n, BINS), numpy.float64) if ('sp64' in want or ('sp' in want and not device_rows)) else None
+        mc = numpy.empty((n, self.order + 1), numpy.float64) if 'mc' in want else None
         ap64 = numpy.empty((n, BINS), numpy.float64) if ('ap64' in want or ('ap' in want and not device_rows)) else None
         coded = numpy.empty((n, self.bands()), numpy.float64) if 'coded_ap' in want else None
 
@@ -92,16 +108,25 @@ class Analyzer(DeviceHandle):
             buf = _DeviceBuffer(self._ctx, max(n, 1) * BINS)
             return DeviceRows(buf.address, n, keep=buf)
         rows, rows_ap = device('sp'), device('ap')
-        head = (h, _dptr(x), x.size, _dptr(f0), _dptr(t), n)
+        got = {'sp': rows if device_rows else sp64, 'sp64': sp64, 'mc': mc, 'ap': rows_ap if device_rows else ap64, 'ap64': ap64, 'coded_ap': coded}
         out_sp = (_dptr(sp64), _lib._fptr(rows.address if rows else None), _dptr(mc))
         out_ap = (_dptr(ap64), _lib._fptr(rows_ap.address if rows_ap else None), _dptr(coded))
-        if not d4c:
-            lib.check(lib.dll.ry_analysis_run(*(head + out_sp)))
-        elif not cheaptrick:
-            lib.check(lib.dll.ry_analysis_d4c(*(head + (float(threshold),) + out_ap)))
-        else:
-            lib.check(lib.dll.ry_analysis_extract(*(head + (float(threshold),) + out_sp + out_ap)))
-        got = {'sp': rows if device_rows else sp64, 'sp64': sp64, 'mc': mc, 'ap': rows_ap if device_rows else ap64, 'ap64': ap64, 'coded_ap': coded}
+        return got, out_sp, out_ap
+
+    def run_device(self, wave_dev: int, n_samples: int, f0_dev: int, t_dev: int, n: int, want=('sp', 'mc', 'ap', 'coded_ap'), device_rows: bool = False,
+                   threshold: float = 0.85):
+        """`run` on a wave and a track that are already on the card of this analyzer's context (`ry_analysis_extract_dev`): `wave_dev` the address
+        of n_samples float32 samples (widened on the device: the bits of `run` on `wave.astype(float64)`), `f0_dev` / `t_dev` of n float64 entries --
+        what `CrepeModel.track(..., device=True)` left there.  The same `want` keys and the same values as `run`; CheapTrick and D4C both run
+        whatever `want` names.  A track `run` would refuse is refused here too (the device checks it; nothing is written)."""
+        lib, h = self._get()
+        self._check_want(want)
+        n, n_samples = int(n), int(n_samples)
+        if n > 0 and n_samples == 0:
+            raise ValueError('an empty wave cannot be analysed at %d frames' % n)
+        got, out_sp, out_ap = self._outputs(n, want, device_rows)
+        as_d = lambda a: ctypes.cast(ctypes.c_void_p(a), _DP)
+        lib.check(lib.dll.ry_analysis_extract_dev(h, _lib._fptr(int(wave_dev)), n_samples, as_d(f0_dev), as_d(t_dev), n, float(threshold), *(out_sp + out_ap)))
         return tuple(got[k] for k in want)
 
     def d4c(self, x, f0, t, threshold: float = 0.85) -> numpy.ndarray:
