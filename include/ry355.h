@@ -150,6 +150,12 @@ int ry_vc_set_discard(ry_vc* vc, int front, int back);
  * one stage-2 forward after the other.  Same results.  Device-pointer callers (ry_vc_enqueue_device) must then give windows that are in
  * flight together their own output blocks.  No ticket may be in flight when the lane count changes.  Default 1. */
 int ry_vc_set_lanes(ry_vc* vc, int lanes);
+/* Streams of the lanes.  WIDE (0): a stage-1 and a stage-2 stream per lane, 2 x lanes + 2 users of hardware queues with the context and the
+ * null stream.  When GPU_MAX_HW_QUEUES (read in ry_vc_create; absent = 4, HIP's default) is smaller than that, the core enqueues on fewer
+ * streams: one stage-1 stream for all lanes beside a stage-2 stream per lane (2); RY_VC_STREAMS = wide | compact | compact-a | compact-b
+ * forces a form (compact-a, 1: one stream per lane).  Same kernels in the same order per window: the results do not depend on the form.
+ * TESTS ONLY: the form in use and the number of distinct streams the calls have enqueued on since ry_vc_create / ry_vc_set_lanes. */
+int ry_vc_debug_streams(ry_vc* vc, int* form, int* n_streams);
 int ry_vc_wait(ry_vc* vc, int ticket, float* mc_out, float* sp_out);
 /* All pointers on the device, nothing waited for (ry_sync / your own event): consecutive calls pipeline by themselves -- stage-1 of
  * window i + 1 runs on its stream under stage-2 of window i.  bench.py times this. */

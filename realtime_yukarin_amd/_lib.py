@@ -24,13 +24,18 @@ TILES.update({k + 'k2': v + 16 for k, v in list(TILES.items()) if isinstance(k, 
 TILES.update({k + 'k1': v + 32 for k, v in list(TILES.items()) if isinstance(k, str) and k[-2:] != 'k2' and k != 'auto'})           # force one
 
 def ensure_hw_queues() -> None:
-    """The window call runs up to two windows side by side on their own pairs of HIP streams (ry_vc_set_lanes): the streams only overlap when
-    each has a hardware queue of its own.  ROCm hands out 4 by default and folds further streams onto them (measured on MI355X: with a
-    second runtime user in the process two lanes then gain nothing, 1.29 ms per window; with 16 every pair of streams overlaps
-    (scripts/gpu_queues.py) and two lanes run at 1.16 ms).  The HIP runtime reads GPU_MAX_HW_QUEUES when it starts, so the variable is set
-    when the product library is BOUND (`Ry355Lib.__init__`: the first GPU context of the process, `engine.get_context`) -- not at import:
-    importing the package changes nothing.  The entry points (bench.py, the worker processes of `dispatch`) set it themselves before
-    anything else.  A caller's own value is respected; a runtime that is already up gets a warning."""
+    """The window call runs up to two windows side by side on HIP streams of their own (ry_vc_set_lanes): streams only overlap when each
+    has a hardware queue of its own.  ROCm hands out GPU_MAX_HW_QUEUES of them (4 by default) and folds further streams onto queues that
+    are taken, in the order the streams were created.  With 16, every stream of the wide topology (a stage-1 and a stage-2 stream per lane)
+    has a queue.  With 4 and two lanes (measured on MI355X, profiles/r16/queues_parent.txt) the wide topology leaves the second lane's two
+    streams on one queue -- 0.878 against 0.813 ms per window -- so the core then enqueues on three streams (`ry_vc_create` reads the
+    variable; one stage-1 stream for both lanes beside the two stage-2 streams; profiles/r16/queues_ab.txt), which with the context stream
+    fill the four queues: nothing else of the process may hold a queue busy (the null stream of a torch process that launches on it).
+    The HIP runtime reads the variable when it starts, so it is set when the product library is BOUND (`Ry355Lib.__init__`: the first
+    GPU context of the process, `engine.get_context`) -- not at import: importing the package changes nothing.  The entry points
+    (bench.py, the worker processes of `dispatch`) set it themselves before anything else.  A caller's own value is respected.  A runtime
+    that is already up keeps the queues it started with: the variable is then left alone, and the core takes the compact topology of the
+    default 4."""
     if 'GPU_MAX_HW_QUEUES' in os.environ:
         return
     import sys
@@ -39,11 +44,8 @@ def ensure_hw_queues() -> None:
         late = t is not None and t.cuda.is_initialized()
     except Exception:
         late = False
-    if late:
-        import warnings
-        warnings.warn('realtime_yukarin_amd: the HIP runtime of this process started before GPU_MAX_HW_QUEUES=16 could be set; the two window '
-                      'lanes may share hardware queues and serialise (set GPU_MAX_HW_QUEUES=16 in the environment before the first HIP call)')
-    os.environ['GPU_MAX_HW_QUEUES'] = '16'
+    if not late:
+        os.environ['GPU_MAX_HW_QUEUES'] = '16'
 
 
 # every symbol include/ry355.h declares (checked by tests/test_abi.py)
@@ -54,7 +56,7 @@ ABI_SYMBOLS = (
     'ry_timer_start', 'ry_timer_stop', 'ry_net_profile', 'ry_net_profile_window', 'ry_net_debug_activation', 'ry_debug_plan_igemm', 'ry_debug_reload_env', 'ry_debug_stream_overlap', 'ry_debug_plan_igemm_bf16', 'ry_debug_plan_os2', 'ry_debug_plan_wino',
     'ry_vc_create', 'ry_vc_destroy', 'ry_vc_convert', 'ry_mc2sp',
     'ry_vc_submit', 'ry_vc_set_lanes', 'ry_vc_set_discard', 'ry_vc_wait', 'ry_vc_enqueue_device', 'ry_vc_enqueue_device_batch', 'ry_vc_stage1', 'ry_vc_stage2_from_mc', 'ry_vc_mid_sp', 'ry_vc_reserve_frames',
-    'ry_vc_submit_wave', 'ry_vc_wait_wave', 'ry_vc_gate',
+    'ry_vc_submit_wave', 'ry_vc_wait_wave', 'ry_vc_gate', 'ry_vc_debug_streams',
     'ry_comm_unique_id', 'ry_comm_init', 'ry_comm_destroy', 'ry_comm_bcast_weights', 'ry_comm_allreduce_max', 'ry_comm_barrier',
     'ry_dev_alloc', 'ry_dev_free', 'ry_dev_upload', 'ry_dev_download',
     'ry_crepe_param_count', 'ry_crepe_create', 'ry_crepe_destroy', 'ry_crepe_predict', 'ry_crepe_decode', 'ry_crepe_set_viterbi_tables',
@@ -139,6 +141,7 @@ class Ry355Lib(object):
         d.ry_vc_submit.argtypes = [_VP, _FP, _IP, ctypes.c_int, ctypes.c_int, ctypes.c_float, _IP]
         d.ry_vc_wait.argtypes = [_VP, ctypes.c_int, _FP, _FP]
         d.ry_vc_set_lanes.argtypes = [_VP, ctypes.c_int]
+        d.ry_vc_debug_streams.argtypes = [_VP, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
         d.ry_vc_set_discard.argtypes = [_VP, ctypes.c_int, ctypes.c_int]
         d.ry_sr_convert_rows.argtypes = [_VP, _FP, _FP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         d.ry_debug_stream_overlap.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _FP]

@@ -35,8 +35,9 @@ typedef int err_t;
 static const char* err_str(err_t) { return "emu"; }
 static err_t set_device(int) { return 0; }
 static err_t device_count(int* n) { *n = 1; return 0; }
-static err_t stream_create(ry_stream_t* s) { *s = nullptr; return 0; }
-static err_t stream_destroy(ry_stream_t) { return 0; }
+// a stream is a token of its own (never dereferenced): what runs on the same stream and what does not can be counted (ry_vc_debug_streams)
+static err_t stream_create(ry_stream_t* s) { *s = (ry_stream_t)malloc(1); return *s ? 0 : 1; }
+static err_t stream_destroy(ry_stream_t s) { free((void*)s); return 0; }
 static err_t stream_sync(ry_stream_t) { return 0; }
 static err_t dmalloc(void** p, size_t bytes) { *p = aligned_alloc(256, (bytes + 255) / 256 * 256); return *p ? 0 : 1; }
 static err_t dfree(void* p) { free(p); return 0; }
@@ -305,6 +306,7 @@ struct ry_net {
                                              // 2 = split-bf16 (hi*hi + lo*hi + hi*lo on the bf16 pipe, fp32 accumulate: fp32-class results)
     ry_ctx* ctx = nullptr;
     ry_stream_t stream = nullptr;            // each predictor enqueues on its own stream: stage-1 of one window overlaps stage-2 of another
+    bool owns_stream = true;                 // false: a clone that enqueues on another handle's stream (net_clone_on), which outlives it
     rt::Event done;                          // (spare: ry_sync / ry_timer_stop join the predictor streams on the host)
     bool has_done = false;
     ry_net_desc desc;
@@ -317,6 +319,9 @@ struct ry_net {
     std::vector<KernelRec>* rec = nullptr;
     std::vector<std::pair<rt::Event, rt::Event>>* rec_events = nullptr;
 };
+
+// ry_net_clone on a stream that another handle owns: no stream is created (the compact topologies of the window call, ry_vc.cpp)
+int net_clone_on(ry_net* src, ry_stream_t borrowed, ry_net** out);
 
 // a host table of n elements to a buffer of the arena: allocate, copy, wait (the host array is usually a temporary)
 template <typename T>

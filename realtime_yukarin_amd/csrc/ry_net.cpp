@@ -16,6 +16,28 @@
 
 thread_local std::string g_ry_err;
 
+// A second handle on the same predictor: the filters stay where they are (one copy in HBM, freed with the last handle), the clone
+// gets its own launch plans, activation buffers and captured graphs -- what a window needs to run beside another one -- and its own
+// stream, unless the caller names one (`borrowed`: a stream of another handle that outlives the clone; none is created then, because a
+// stream takes a place on a hardware queue when it is created, used or not).
+int net_clone_on(ry_net* src, ry_stream_t borrowed, ry_net** out) {
+    if (!src || !out) return fail(RY_EINVAL, "null argument");
+    *out = nullptr;
+    ry_ctx* ctx = src->ctx;
+    RT_TRY(rt::set_device(ctx->device));
+    std::unique_ptr<ry_net> net(new ry_net());
+    net->ctx = ctx; net->desc = src->desc; net->dtype = src->dtype; net->use_graph = src->use_graph;
+    net->layers = src->layers;                       // device pointers into the shared arena
+    net->weights = src->weights;
+    if (borrowed) { net->stream = borrowed; net->owns_stream = false; }
+    else RT_TRY(rt::stream_create(&net->stream));
+    RT_TRY(rt::event_create_fast(&net->done));
+    net->has_done = true;
+    ctx->nets.push_back(net.get());
+    *out = net.release();
+    return RY_OK;
+}
+
 extern "C" {
 
 
@@ -135,22 +157,7 @@ int ry_net_create(ry_ctx* ctx, const ry_net_desc* desc, const float* weights, si
 
 // A second handle on the same predictor: the filters stay where they are (one copy in HBM, freed with the last handle), the clone
 // gets its own stream, launch plans, activation buffers and captured graphs -- what a window needs to run beside another one.
-int ry_net_clone(ry_net* src, ry_net** out) {
-    if (!src || !out) return fail(RY_EINVAL, "null argument");
-    *out = nullptr;
-    ry_ctx* ctx = src->ctx;
-    RT_TRY(rt::set_device(ctx->device));
-    std::unique_ptr<ry_net> net(new ry_net());
-    net->ctx = ctx; net->desc = src->desc; net->dtype = src->dtype; net->use_graph = src->use_graph;
-    net->layers = src->layers;                       // device pointers into the shared arena
-    net->weights = src->weights;
-    RT_TRY(rt::stream_create(&net->stream));
-    RT_TRY(rt::event_create_fast(&net->done));
-    net->has_done = true;
-    ctx->nets.push_back(net.get());
-    *out = net.release();
-    return RY_OK;
-}
+int ry_net_clone(ry_net* src, ry_net** out) { return net_clone_on(src, nullptr, out); }
 
 void ry_net_destroy(ry_net* net) {
     if (!net) return;
@@ -162,7 +169,7 @@ void ry_net_destroy(ry_net* net) {
         if (v[i] == net) { v.erase(v.begin() + i); break; }
     net->plans.clear(); net->last_plan = nullptr;
     if (net->has_done) rt::event_destroy(net->done);
-    rt::stream_destroy(net->stream);
+    if (net->owns_stream) rt::stream_destroy(net->stream);
     delete net;
 }
 

@@ -194,6 +194,16 @@ class VcCore(object):
         self.lib.check(self.lib.dll.ry_vc_set_lanes(self.handle, int(lanes)))
         self.lanes = int(lanes)
 
+    STREAM_FORMS = ('wide', 'compact-a', 'compact-b')
+
+    def debug_streams(self):
+        """(form, n): the stream topology of the lanes ('wide': two streams per lane; 'compact-a': one per lane; 'compact-b': one stage-1 stream
+        beside a stage-2 stream per lane -- chosen from GPU_MAX_HW_QUEUES / RY_VC_STREAMS when the core was made, `ry_vc_set_lanes`) and the number
+        of distinct streams the calls have enqueued on since (`ry_vc_debug_streams`, tests)."""
+        f, n = ctypes.c_int(-1), ctypes.c_int(-1)
+        self.lib.check(self.lib.dll.ry_vc_debug_streams(self.handle, ctypes.byref(f), ctypes.byref(n)))
+        return self.STREAM_FORMS[f.value], int(n.value)
+
     @property
     def ring(self) -> int:
         """Windows that may be in flight: six ring slots up to three lanes, else two per lane."""
