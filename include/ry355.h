@@ -336,14 +336,42 @@ int ry_crepe_track(ry_crepe* crepe, const float* audio, int n_samples, int sr, i
  * hold until the next call on this handle.  RY_ESTATE when no track is there: none has run, or a later call has reused the buffers. */
 int ry_crepe_track_buffers(ry_crepe* crepe, const float** wave_dev, int* n_samples, int* n_frames, const unsigned char** voiced_dev,
                            const double** f0_dev, const double** t_dev);
+/* ry_crepe_track for n_waves >= 1 waves at one rate in ONE enqueue.  audio (HOST, float32): the waves back to back, wave i of n_samples[i] samples;
+ * they are uploaded once, with one segment table (per wave: first sample and length at sr, the same at 16 kHz, first frame and frame count).  The
+ * resampler runs over all waves in one launch -- an output indexes the rate's time register by its index within its wave and reads that wave's samples
+ * only --; the frames of all waves are packed back to back into the network's passes of 256, each frame centred and padded inside its own wave; the
+ * Viterbi decode and the voicing run one workgroup per wave, each from its own first frame, the time axis counted from it.  Everything written for wave i
+ * has the bits ry_crepe_track writes for wave i alone, in both modes of ry_crepe_set_dtype, whatever the other waves hold and wherever it stands in
+ * the list.  n_frames [n_waves]: the frames of every wave.  The masked tracks stay in the handle, concatenated in wave order
+ * (ry_crepe_track_many_buffers); on_device_out = 0: voiced / f0_64 / t_64 are host arrays of the sum of n_frames entries, written before the call
+ * returns; 1: as in ry_crepe_track.  Refused before anything is launched or written (n_frames included): n_waves < 1, a wave with no sample, a wave
+ * ry_crepe_track refuses (no sample at 16 kHz, a time register too short, ...), a rate without resampler tables (RY_ESTATE), more than 2^24 frames
+ * or 2^31 - 1 samples (at sr or at 16 kHz) in all, and what ry_crepe_voicing refuses. */
+int ry_crepe_track_many(ry_crepe* crepe, const float* audio, const int* n_samples, int n_waves, int sr, int hop, double step_ms, double threshold,
+                        int* n_frames, unsigned char* voiced, double* f0_64, double* t_64, int on_device_out);
+/* What the last ry_crepe_track_many left on the card (any pointer may be null): the device addresses of the uploaded float32 waves (back to back, at
+ * the caller's rate) and of the concatenated voiced (bytes), f0_64 and t_64; the number of waves; and two HOST arrays of n_waves + 1 entries that
+ * belong to the handle: sample_offsets[i] / frame_offsets[i] = the first sample / first frame of wave i, the last entry the total -- what
+ * ry_analysis_extract_many_dev takes.  All hold until the next call on this handle.  RY_ESTATE when no such tracks are there: none has run, or a later
+ * call (ry_crepe_track included) has reused the buffers; ry_crepe_track_buffers in turn reports no track after ry_crepe_track_many.  Unlike
+ * ry_crepe_track, which looks at its arguments first, ry_crepe_track_many forgets the tracks before it validates anything: after ANY refused
+ * ry_crepe_track_many, a null argument included, no track is reported. */
+int ry_crepe_track_many_buffers(ry_crepe* crepe, const float** wave_dev, int* n_waves, const long long** sample_offsets, const int** frame_offsets,
+                                const unsigned char** voiced_dev, const double** f0_dev, const double** t_dev);
+/* ry_crepe_decode / ry_crepe_voicing on n_tracks >= 1 tracks side by side, one workgroup each: the arrays hold the tracks back to back, track i of
+ * n_frames[i] >= 1 frames (at most 2^24 in all); every track gets the bits of the single call on it alone.  Pointers and on_device as in the single
+ * calls. */
+int ry_crepe_decode_many(ry_crepe* crepe, const float* activation, const int* n_frames, int n_tracks, int viterbi, float* f0, float* confidence, int* path);
+int ry_crepe_voicing_many(ry_crepe* crepe, const float* confidence, const float* f0, const int* n_frames, int n_tracks, double threshold, double step_ms,
+                          unsigned char* voiced, double* f0_64, double* t_64, int on_device);
 /* tests: the first n_frames rows of the buffers of the last pass of ry_crepe_predict (its last <= 256 frames): layer 0 the normalised
  * frames [n][1024], 1 .. 6 the pooled conv outputs [n][positions][channels], 7 the logits [n][360].  n_frames may exceed the frames of
  * that pass, up to the largest pass the handle has run: the rows behind it hold what an earlier call or ry_crepe_debug_poison left. */
 int ry_crepe_debug_layer(ry_crepe* crepe, int layer, int n_frames, float* out);
-/* tests: fills every element the next ry_crepe_predict / ry_crepe_decode / ry_crepe_voicing / ry_crepe_track must write with NaN bit patterns (all
+/* tests: fills every element the next ry_crepe_predict / ry_crepe_decode / ry_crepe_voicing / ry_crepe_track (and their _many forms) must write with NaN bit patterns (all
  * bits set; -1 as an index) -- the samples of the frame rows, the interior rows of every layer's input, logits, split-K slabs, activation, confidence,
  * f0, observations, back-pointers, path, the 16 kHz audio buffer (the resampler's output), the voicing's back-pointers and the masked track (voiced,
- * f0_64, t_64; ry_crepe_track_buffers then reports no track) -- and leaves the zero padding rows as they are: a later call that reads anything it did not write shows it. */
+ * f0_64, t_64; ry_crepe_track_buffers and ry_crepe_track_many_buffers then report no track) and the segment table -- and leaves the zero padding rows as they are: a later call that reads anything it did not write shows it. */
 int ry_crepe_debug_poison(ry_crepe* crepe);
 /* diagnostics: the split-K count of conv1 .. conv6 and the dense layer (7 ints) in the mode in force (ry_crepe_set_dtype). */
 int ry_crepe_debug_splits(ry_crepe* crepe, int* splits);
@@ -438,6 +466,16 @@ int ry_analysis_extract(ry_analysis* analysis, const double* x, long long x_len,
  * ry_analysis_extract: the same bits.  The inputs are read in the order of the context stream, which the call drains before it returns. */
 int ry_analysis_extract_dev(ry_analysis* analysis, const float* x32_dev, long long x_len, const double* f0_dev, const double* t_dev, int n, double threshold,
                             double* sp64_out, float* sp32_dev_out, double* mc_out, double* ap64_out, float* ap32_dev_out, double* coded_out);
+/* ry_analysis_extract_dev for the n_waves >= 1 waves and tracks ry_crepe_track_many left on the card.  x32_dev: the waves back to back; f0_dev / t_dev:
+ * the tracks back to back; sample_offsets / frame_offsets: HOST arrays of n_waves + 1 entries, both starting at 0 (ry_crepe_track_many_buffers).  The
+ * wave is widened and the track checked over the whole call, and the host reads ONE verdict (one wait) before any frame kernel is launched; the frame
+ * kernels then run per wave on that wave's samples, so a frame's window is clamped at the ends of its own wave and its noise keys are those of the
+ * single call.  Output rows are concatenated in wave order; rows of wave i have the bits of ry_analysis_extract_dev on wave i alone.  Refused, with
+ * nothing written: n_waves < 1, offsets that do not start at 0, a wave with no sample or no frame, more than 2^22 frames in all, and what
+ * ry_analysis_extract_dev refuses (the frame index in the message counts over the whole call). */
+int ry_analysis_extract_many_dev(ry_analysis* analysis, const float* x32_dev, const long long* sample_offsets, const double* f0_dev, const double* t_dev,
+                                 const int* frame_offsets, int n_waves, double threshold,
+                                 double* sp64_out, float* sp32_dev_out, double* mc_out, double* ap64_out, float* ap32_dev_out, double* coded_out);
 /* the number of bands B (1 at 16 kHz, 3 at 24 kHz); negative (an error code) where D4C is not built for the handle's rate */
 int ry_analysis_d4c_bands(ry_analysis* analysis);
 /* tests: what the last recorded (ry_analysis_debug_record) D4C run decided.  ints_out [n][9]: half length of the Love-Train window, of the other

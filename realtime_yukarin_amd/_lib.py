@@ -63,6 +63,7 @@ ABI_SYMBOLS = (
     'ry_crepe_debug_layer', 'ry_crepe_debug_splits', 'ry_crepe_debug_poison',
     'ry_crepe_set_resampler', 'ry_crepe_resample', 'ry_crepe_predict_sr', 'ry_crepe_set_dtype',
     'ry_crepe_voicing', 'ry_crepe_set_voicing_tables', 'ry_crepe_track', 'ry_crepe_track_buffers',
+    'ry_crepe_track_many', 'ry_crepe_track_many_buffers', 'ry_crepe_decode_many', 'ry_crepe_voicing_many', 'ry_analysis_extract_many_dev',
     'ry_synth_create', 'ry_synth_destroy', 'ry_synth_length', 'ry_synth_run', 'ry_synth_bound', 'ry_synth_push', 'ry_synth_flush', 'ry_synth_reset',
     'ry_synth_debug_pulses', 'ry_synth_debug_poison',
     'ry_analysis_create', 'ry_analysis_destroy', 'ry_analysis_run', 'ry_analysis_sp2mc', 'ry_analysis_debug_record', 'ry_analysis_debug_ints', 'ry_analysis_debug_poison',
@@ -193,6 +194,11 @@ class Ry355Lib(object):
         d.ry_crepe_voicing.argtypes = [_VP, _FP, _FP, ctypes.c_int, ctypes.c_double, ctypes.c_double, _UB, _DP, _DP, ctypes.c_int]
         d.ry_crepe_track.argtypes = [_VP, _FP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _IP, _UB, _DP, _DP, ctypes.c_int]
         d.ry_crepe_track_buffers.argtypes = [_VP, ctypes.POINTER(_VP), _IP, _IP, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP)]
+        _LLPP, _IPP = ctypes.POINTER(ctypes.POINTER(ctypes.c_longlong)), ctypes.POINTER(_IP)
+        d.ry_crepe_track_many.argtypes = [_VP, _FP, _IP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _IP, _UB, _DP, _DP, ctypes.c_int]
+        d.ry_crepe_track_many_buffers.argtypes = [_VP, ctypes.POINTER(_VP), _IP, _LLPP, _IPP, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP)]
+        d.ry_crepe_decode_many.argtypes = [_VP, _FP, _IP, ctypes.c_int, ctypes.c_int, _FP, _FP, _IP]
+        d.ry_crepe_voicing_many.argtypes = [_VP, _FP, _FP, _IP, ctypes.c_int, ctypes.c_double, ctypes.c_double, _UB, _DP, _DP, ctypes.c_int]
         _CI = ctypes.c_int
         d.ry_synth_create.argtypes = [_VP, _CI, ctypes.c_double, _CI, ctypes.c_uint, ctypes.POINTER(_VP)]
         d.ry_synth_destroy.argtypes = [_VP]
@@ -217,6 +223,7 @@ class Ry355Lib(object):
         d.ry_analysis_d4c.argtypes = [_VP, _DP, _LL, _DP, _DP, _CI, ctypes.c_double, _DP, _FP, _DP]
         d.ry_analysis_extract.argtypes = [_VP, _DP, _LL, _DP, _DP, _CI, ctypes.c_double, _DP, _FP, _DP, _DP, _FP, _DP]
         d.ry_analysis_extract_dev.argtypes = [_VP, _FP, _LL, _DP, _DP, _CI, ctypes.c_double, _DP, _FP, _DP, _DP, _FP, _DP]
+        d.ry_analysis_extract_many_dev.argtypes = [_VP, _FP, ctypes.POINTER(_LL), _DP, _DP, _IP, _CI, ctypes.c_double, _DP, _FP, _DP, _DP, _FP, _DP]
         d.ry_analysis_d4c_bands.argtypes = [_VP]
         d.ry_analysis_debug_d4c.argtypes = [_VP, ctypes.POINTER(_LL), _DP, _CI, _IP]
         d.ry_net_profile_window.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RyKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]

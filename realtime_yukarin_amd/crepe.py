@@ -293,6 +293,24 @@ class DeviceTrack(object):
         return self.model._download_track(self)
 
 
+class DeviceTracks(object):
+    """What `CrepeModel.track_many(..., device=True)` left on the card: the addresses of the uploaded float32 waves (back to back) and of the
+    concatenated `voiced` (bytes), `f0` and `t` (float64); `sample_offsets` / `frame_offsets` (int64 / int32, waves + 1 entries): where wave i
+    starts in them.  They belong to the model's handle and hold until its next call (`Analyzer.run_device_many` reads them)."""
+
+    def __init__(self, model, ctx, wave, voiced, f0, t, sample_offsets, frame_offsets):
+        self.model, self.ctx = model, ctx
+        self.wave, self.voiced, self.f0, self.t = wave, voiced, f0, t
+        self.sample_offsets, self.frame_offsets = sample_offsets, frame_offsets
+        self.waves, self.samples, self.frames = sample_offsets.size - 1, int(sample_offsets[-1]), int(frame_offsets[-1])
+
+    def download(self):
+        """[(voiced [frames] bool, f0 [frames] float64)] per wave (waits for the stream)."""
+        voiced, f0 = self.model._download_track(self)
+        o = self.frame_offsets
+        return [(voiced[o[i]:o[i + 1]], f0[o[i]:o[i + 1]]) for i in range(self.waves)]
+
+
 # ---- the device model ---------------------------------------------------------------------------------------------------------
 class CrepeModel(DeviceHandle):
     """CREPE on the MI355X (`ry_crepe_*`).  Picklable and fork-safe: the GPU context and the device weights are created lazily in the
@@ -481,6 +499,88 @@ class CrepeModel(DeviceHandle):
         ns, nfr = ctypes.c_int(), ctypes.c_int()
         lib.check(lib.dll.ry_crepe_track_buffers(h, ctypes.byref(p[0]), ctypes.byref(ns), ctypes.byref(nfr), *[ctypes.byref(q) for q in p[1:]]))
         return DeviceTrack(self, self._ctx, p[0].value, ns.value, nfr.value, p[1].value, p[2].value, p[3].value)
+
+    def track_many(self, waves, sr, hop: int, step_size, threshold: float = 0.1, device: bool = True):
+        """`track` for a list of waves at one rate in one enqueue (`ry_crepe_track_many`): one upload of the waves back to back, the resampler
+        over all of them, their frames packed into the passes of the network, the decode and the voicing one workgroup per wave.  Wave i gets
+        the bits of `track(waves[i], ...)`, whatever else is in the list.  device=True -> `DeviceTracks`; False -> [(voiced, f0, t)] per wave."""
+        sr = _rate(sr)
+        xs = [numpy.ascontiguousarray(w, dtype=numpy.float32).ravel() for w in waves]
+        if not xs:
+            raise ValueError('track_many needs at least one wave')
+        lib, h = self._get()
+        counts = numpy.asarray([x.size for x in xs], numpy.int32)
+        want = [self._frames_at(x.size, sr, hop) for x in xs]
+        audio = numpy.ascontiguousarray(numpy.concatenate(xs))
+        nf = numpy.zeros(len(xs), numpy.int32)
+        _IP = ctypes.POINTER(ctypes.c_int)
+        head = (h, _lib._fptr(audio), counts.ctypes.data_as(_IP), len(xs), sr, int(hop), float(step_size), float(threshold), nf.ctypes.data_as(_IP))
+        if not device:
+            n = int(sum(want))
+            voiced, f64, t64 = numpy.empty(n, numpy.uint8), numpy.empty(n, numpy.float64), numpy.empty(n, numpy.float64)
+            lib.check(lib.dll.ry_crepe_track_many(*head, voiced.ctypes.data_as(_UBP), _dptr(f64), _dptr(t64), 0))
+            assert list(nf) == want, (list(nf), want)
+            o = numpy.concatenate([[0], numpy.cumsum(nf)])
+            return [(voiced[a:b].astype(bool), f64[a:b].copy(), t64[a:b].copy()) for a, b in zip(o[:-1], o[1:])]
+        lib.check(lib.dll.ry_crepe_track_many(*head, None, None, None, 1))
+        return self._tracks_on_card()
+
+    def _tracks_on_card(self) -> DeviceTracks:
+        lib, h = self._get()
+        p = [ctypes.c_void_p() for _ in range(4)]
+        nw = ctypes.c_int()
+        so, fo = ctypes.POINTER(ctypes.c_longlong)(), ctypes.POINTER(ctypes.c_int)()
+        lib.check(lib.dll.ry_crepe_track_many_buffers(h, ctypes.byref(p[0]), ctypes.byref(nw), ctypes.byref(so), ctypes.byref(fo),
+                                                      *[ctypes.byref(q) for q in p[1:]]))
+        sample_offsets = numpy.asarray(so[:nw.value + 1], numpy.int64)          # copies: the handle's arrays change with its next call
+        frame_offsets = numpy.asarray(fo[:nw.value + 1], numpy.int32)
+        return DeviceTracks(self, self._ctx, p[0].value, p[1].value, p[2].value, p[3].value, sample_offsets, frame_offsets)
+
+    def decode_many(self, activations, viterbi: bool = True):
+        """`decode` of several activations side by side, one workgroup each (`ry_crepe_decode_many`) -> [(f0, confidence, centre bins)]."""
+        lib, h = self._get()
+        acts = [numpy.ascontiguousarray(a, dtype=numpy.float32) for a in activations]
+        if not acts or any(a.ndim != 2 or a.shape[1] != BINS or a.shape[0] < 1 for a in acts):
+            raise ValueError('decode_many needs activations of (frames >= 1, %d)' % BINS)
+        counts = numpy.asarray([a.shape[0] for a in acts], numpy.int32)
+        a = numpy.ascontiguousarray(numpy.concatenate(acts))
+        n = a.shape[0]
+        f0, conf, path = numpy.empty(n, numpy.float32), numpy.empty(n, numpy.float32), numpy.empty(n, numpy.int32)
+        _IP = ctypes.POINTER(ctypes.c_int)
+        lib.check(lib.dll.ry_crepe_decode_many(h, _lib._fptr(a), counts.ctypes.data_as(_IP), len(acts), int(bool(viterbi)), _lib._fptr(f0), _lib._fptr(conf),
+                                               path.ctypes.data_as(_IP)))
+        o = numpy.concatenate([[0], numpy.cumsum(counts)])
+        return [(f0[i:j], conf[i:j], path[i:j]) for i, j in zip(o[:-1], o[1:])]
+
+    def voicing_many(self, confidences, f0s, threshold: float = 0.1, step_size=10, device: bool = False):
+        """`voicing` of several tracks side by side, one workgroup each (`ry_crepe_voicing_many`) -> [(voiced, f0 float64, t)] per track.
+        device=True (tests): the five arrays pass through device buffers of the caller."""
+        lib, h = self._get()
+        cs = [numpy.ascontiguousarray(c, dtype=numpy.float32).ravel() for c in confidences]
+        fs = [numpy.ascontiguousarray(f, dtype=numpy.float32).ravel() for f in f0s]
+        if not cs or len(cs) != len(fs) or any(c.size != f.size or c.size < 1 for c, f in zip(cs, fs)):
+            raise ValueError('voicing_many needs as many confidence as f0 arrays, pairwise of one length >= 1')
+        counts = numpy.asarray([c.size for c in cs], numpy.int32)
+        c, f = numpy.concatenate(cs), numpy.concatenate(fs)
+        n = c.size
+        voiced, f64, t64 = numpy.empty(n, numpy.uint8), numpy.empty(n, numpy.float64), numpy.empty(n, numpy.float64)
+        args = (counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(cs), float(threshold), float(step_size))
+        o = numpy.concatenate([[0], numpy.cumsum(counts)])
+        split = lambda v: [(v[i:j].astype(bool), f64[i:j], t64[i:j]) for i, j in zip(o[:-1], o[1:])]
+        if not device:
+            lib.check(lib.dll.ry_crepe_voicing_many(h, _lib._fptr(c), _lib._fptr(f), *args, voiced.ctypes.data_as(_UBP), _dptr(f64), _dptr(t64), 0))
+            return split(voiced)
+        from .world_synth import _DeviceBuffer
+        ctx, dll = self._ctx, lib.dll
+        host = [c, f, numpy.zeros((n + 3) // 4, numpy.float32), f64.view(numpy.float32), t64.view(numpy.float32)]
+        bufs = [_DeviceBuffer(ctx, a.size) for a in host]
+        for a, b in zip(host[:2], bufs[:2]):
+            lib.check(dll.ry_dev_upload(ctx.handle, b.ptr, _lib._fptr(a), a.size))
+        as_ub, as_d = (lambda b: ctypes.cast(b.ptr, _UBP)), (lambda b: ctypes.cast(b.ptr, _DP))
+        lib.check(dll.ry_crepe_voicing_many(h, bufs[0].ptr, bufs[1].ptr, *args, as_ub(bufs[2]), as_d(bufs[3]), as_d(bufs[4]), 1))
+        for a, b in zip(host[2:], bufs[2:]):
+            lib.check(dll.ry_dev_download(ctx.handle, _lib._fptr(a), b.ptr, a.size))
+        return split(host[2].view(numpy.uint8)[:n])
 
     def _download_track(self, trk):
         lib, h = self._get()

@@ -5,6 +5,8 @@
 // D4C (`pyworld.d4c` + `pyworld.code_aperiodicity`: ap and coded_ap; kernel: d4c_kernels.h) runs over the same uploaded wave.
 // ry_analysis_extract_dev takes the wave (float32) and the track from device memory instead -- what ry_crepe_track left there: the wave is widened
 // on the card, the track is checked by a kernel whose verdict the host reads before it launches the same frame kernels.
+// ry_analysis_extract_many_dev does that for the waves and tracks of ry_crepe_track_many: one widening, one check and one verdict for the call, then
+// the frame kernels once per wave on that wave's samples and rows (a frame kernel takes one wave: its clamp at both ends is that wave's).
 #include "analysis_kernels.h"
 #include "d4c_kernels.h"
 #include "ry_host.h"
@@ -110,7 +112,15 @@ int check_call(ry_analysis* s, long long x_len, int n, bool cheaptrick, const Ou
     return RY_OK;
 }
 
-int run_kernels(ry_analysis* s, const double* d_x, long long x_len, const double* d_f0, const double* d_t, int n, bool cheaptrick, const Outputs& o);
+// frames [k0, k0 + n) of a call analyse the wave of x_len samples at x0 of the call's wave buffer
+struct Span { long long x0, x_len; int k0, n; };
+
+int run_spans(ry_analysis* s, const double* d_x, const Span* spans, int n_spans, const double* d_f0, const double* d_t, int n, bool cheaptrick, const Outputs& o);
+
+int run_kernels(ry_analysis* s, const double* d_x, long long x_len, const double* d_f0, const double* d_t, int n, bool cheaptrick, const Outputs& o) {
+    const Span one = {0, x_len, 0, n};
+    return run_spans(s, d_x, &one, 1, d_f0, d_t, n, cheaptrick, o);
+}
 
 // one upload of the wave and the track, then CheapTrick + sp2mc (when `cheaptrick`) and / or D4C (when o.d4c) over it
 int run_frames(ry_analysis* s, const double* x, long long x_len, const double* f0, const double* t, int n, bool cheaptrick, const Outputs& o) {
@@ -133,8 +143,8 @@ int run_frames(ry_analysis* s, const double* x, long long x_len, const double* f
     return run_kernels(s, s->d_x.ptr(), x_len, s->d_f0.ptr(), s->d_t.ptr(), n, cheaptrick, o);
 }
 
-// the frame kernels over a wave and a track in device memory, and the copies of what was asked for
-int run_kernels(ry_analysis* s, const double* d_x, long long x_len, const double* d_f0, const double* d_t, int n, bool cheaptrick, const Outputs& o) {
+// the frame kernels over the waves and the track of n frames in device memory, one launch per wave, and the copies of what was asked for
+int run_spans(ry_analysis* s, const double* d_x, const Span* spans, int n_spans, const double* d_f0, const double* d_t, int n, bool cheaptrick, const Outputs& o) {
     const ry_stream_t st = s->ctx->stream;
     if (cheaptrick) {
         if (s->record) RY_TRY(s->d_ints.grow(s->ctx, (long long)n));
@@ -146,25 +156,32 @@ int run_kernels(ry_analysis* s, const double* d_x, long long x_len, const double
         if (o.ap64) RY_TRY(s->d_ap.grow(s->ctx, (long long)n * SYNTH_BINS));
         if (o.coded) RY_TRY(s->d_coded.grow(s->ctx, (long long)n * s->n_bands));
     }
-    if (cheaptrick) {
+    const size_t n_mc = (size_t)s->order + 1;
+    for (int i = 0; i < n_spans && cheaptrick; ++i) {
+        const Span& sp = spans[i];
+        const size_t k0 = (size_t)sp.k0;
         AnalysisParams p;
-        p.x = d_x; p.x_len = x_len; p.f0 = d_f0; p.t = d_t;
+        p.x = d_x + sp.x0; p.x_len = sp.x_len; p.f0 = d_f0 + k0; p.t = d_t + k0;
         p.fs = (double)s->fs; p.floor_f0 = s->floor_f0; p.q1 = s->q1; p.seed_hash = s->seed_hash;
         p.tw = s->tw; p.S = s->S; p.n_mc = s->order + 1;
-        p.sp64 = o.sp64 ? s->d_sp.ptr() : nullptr; p.sp32 = o.sp32_dev; p.mc = o.mc ? s->d_mc.ptr() : nullptr; p.ints = s->record ? s->d_ints.ptr() : nullptr;
-        RY_LAUNCH(analysis_frame, dim3((unsigned)n), 256, st, p);
+        p.sp64 = o.sp64 ? s->d_sp.ptr() + k0 * SYNTH_BINS : nullptr; p.sp32 = o.sp32_dev ? o.sp32_dev + k0 * SYNTH_BINS : nullptr;
+        p.mc = o.mc ? s->d_mc.ptr() + k0 * n_mc : nullptr; p.ints = s->record ? s->d_ints.ptr() + k0 : nullptr;
+        RY_LAUNCH(analysis_frame, dim3((unsigned)sp.n), 256, st, p);
         RT_TRY(rt::last_error());
     }
-    if (o.d4c) {
+    for (int i = 0; i < n_spans && o.d4c; ++i) {
+        const Span& sp = spans[i];
+        const size_t k0 = (size_t)sp.k0;
         D4cParams p;
-        p.x = d_x; p.x_len = x_len; p.f0 = d_f0; p.t = d_t;
+        p.x = d_x + sp.x0; p.x_len = sp.x_len; p.f0 = d_f0 + k0; p.t = d_t + k0;
         p.fs = (double)s->fs; p.threshold = o.threshold; p.seed_hash = s->seed_hash;
         p.tw = s->tw; p.tw2 = s->tw2; p.nuttall = s->nuttall;
         p.n_bands = s->n_bands; p.band_half = s->band_half;
         for (int i = 0; i < D4C_MAX_BANDS; ++i) p.band_centre[i] = s->band_centre[i];
         p.lt0 = s->lt[0]; p.lt1 = s->lt[1]; p.lt2 = s->lt[2];
-        p.ap64 = o.ap64 ? s->d_ap.ptr() : nullptr; p.ap32 = o.ap32_dev; p.coded = o.coded ? s->d_coded.ptr() : nullptr; p.rec = s->record ? s->d_rec.ptr() : nullptr;
-        RY_LAUNCH(d4c_frame, dim3((unsigned)n), 256, st, p);
+        p.ap64 = o.ap64 ? s->d_ap.ptr() + k0 * SYNTH_BINS : nullptr; p.ap32 = o.ap32_dev ? o.ap32_dev + k0 * SYNTH_BINS : nullptr;
+        p.coded = o.coded ? s->d_coded.ptr() + k0 * (size_t)s->n_bands : nullptr; p.rec = s->record ? s->d_rec.ptr() + k0 : nullptr;
+        RY_LAUNCH(d4c_frame, dim3((unsigned)sp.n), 256, st, p);
         RT_TRY(rt::last_error());
     }
     if (cheaptrick) {
@@ -181,6 +198,36 @@ int run_kernels(ry_analysis* s, const double* d_x, long long x_len, const double
     }
     RT_TRY(rt::stream_sync(st));                                   // the caller's arrays are free, the float32 rows are written
     return RY_OK;
+}
+
+// a float32 wave buffer of x_len samples and a track of n frames on the card: widened and checked once -- ONE verdict, read before any frame kernel --
+// then the frame kernels per span
+int extract_dev(ry_analysis* s, const float* x32_dev, long long x_len, const double* f0_dev, const double* t_dev, int n, const Span* spans, int n_spans,
+                const Outputs& o) {
+    const ry_stream_t st = s->ctx->stream;
+    RY_TRY(s->d_x.grow(s->ctx, x_len));
+    RY_TRY(s->d_verdict.reserve(s->ctx, 2));
+    AnalysisCheckParams cp;
+    cp.f0 = f0_dev; cp.t = t_dev; cp.n = n; cp.fs = (double)s->fs; cp.verdict = s->d_verdict.ptr();
+    RY_LAUNCH(analysis_check_track, dim3(1), 256, st, cp);
+    RT_TRY(rt::last_error());
+    int verdict[2] = {0, 0};
+    RT_TRY(rt::d2h(verdict, s->d_verdict.ptr(), sizeof verdict, st));
+    AnalysisWidenParams wp;
+    wp.x32 = x32_dev; wp.x64 = s->d_x.ptr(); wp.n = x_len;
+    RY_LAUNCH(analysis_widen, dim3((unsigned)((x_len + 255) / 256)), 256, st, wp);       // behind the copy: it runs while the host waits for the verdict
+    RT_TRY(rt::last_error());
+    RT_TRY(rt::stream_sync(st));
+    if (verdict[0] >= 0 && verdict[0] < n) {                            // the refusal's values, for the message
+        double v[2] = {0.0, 0.0};
+        RT_TRY(rt::d2h(&v[0], f0_dev + verdict[0], sizeof(double), st));
+        RT_TRY(rt::d2h(&v[1], t_dev + verdict[0], sizeof(double), st));
+        RT_TRY(rt::stream_sync(st));
+        if (verdict[1] == 1) return fail(RY_EINVAL, "f0[%d] = %g: finite and below fs / 2", verdict[0], v[0]);
+        return fail(RY_EINVAL, "t[%d] = %g: -1 .. 1e6 s", verdict[0], v[1]);
+    }
+    if (verdict[0] != -1) return fail(RY_ESTATE, "the track check left %d", verdict[0]);
+    return run_spans(s, s->d_x.ptr(), spans, n_spans, f0_dev, t_dev, n, true, o);
 }
 }  // namespace
 
@@ -250,30 +297,36 @@ int ry_analysis_extract_dev(ry_analysis* s, const float* x32_dev, long long x_le
     if (empty) return RY_OK;
     if (!x32_dev) return fail(RY_EINVAL, "null wave");
     if (!f0_dev || !t_dev) return fail(RY_EINVAL, "null f0 / t");
-    const ry_stream_t st = s->ctx->stream;
-    RY_TRY(s->d_x.grow(s->ctx, x_len));
-    RY_TRY(s->d_verdict.reserve(s->ctx, 2));
-    AnalysisCheckParams cp;
-    cp.f0 = f0_dev; cp.t = t_dev; cp.n = n; cp.fs = (double)s->fs; cp.verdict = s->d_verdict.ptr();
-    RY_LAUNCH(analysis_check_track, dim3(1), 256, st, cp);
-    RT_TRY(rt::last_error());
-    int verdict[2] = {0, 0};
-    RT_TRY(rt::d2h(verdict, s->d_verdict.ptr(), sizeof verdict, st));
-    AnalysisWidenParams wp;
-    wp.x32 = x32_dev; wp.x64 = s->d_x.ptr(); wp.n = x_len;
-    RY_LAUNCH(analysis_widen, dim3((unsigned)((x_len + 255) / 256)), 256, st, wp);       // behind the copy: it runs while the host waits for the verdict
-    RT_TRY(rt::last_error());
-    RT_TRY(rt::stream_sync(st));
-    if (verdict[0] >= 0 && verdict[0] < n) {                            // the refusal's values, for the message
-        double v[2] = {0.0, 0.0};
-        RT_TRY(rt::d2h(&v[0], f0_dev + verdict[0], sizeof(double), st));
-        RT_TRY(rt::d2h(&v[1], t_dev + verdict[0], sizeof(double), st));
-        RT_TRY(rt::stream_sync(st));
-        if (verdict[1] == 1) return fail(RY_EINVAL, "f0[%d] = %g: finite and below fs / 2", verdict[0], v[0]);
-        return fail(RY_EINVAL, "t[%d] = %g: -1 .. 1e6 s", verdict[0], v[1]);
+    const Span one = {0, x_len, 0, n};
+    return extract_dev(s, x32_dev, x_len, f0_dev, t_dev, n, &one, 1, o);
+}
+
+int ry_analysis_extract_many_dev(ry_analysis* s, const float* x32_dev, const long long* sample_offsets, const double* f0_dev, const double* t_dev,
+                                 const int* frame_offsets, int n_waves, double threshold,
+                                 double* sp64_out, float* sp32_dev_out, double* mc_out, double* ap64_out, float* ap32_dev_out, double* coded_out) {
+    Outputs o;
+    o.sp64 = sp64_out; o.sp32_dev = sp32_dev_out; o.mc = mc_out;
+    o.d4c = true; o.threshold = threshold; o.ap64 = ap64_out; o.ap32_dev = ap32_dev_out; o.coded = coded_out;
+    RY_TRY(check_handle(s, "analysis"));
+    if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
+    if (!sample_offsets || !frame_offsets) return fail(RY_EINVAL, "null offsets");
+    if (sample_offsets[0] != 0 || frame_offsets[0] != 0) return fail(RY_EINVAL, "the offsets start at %lld / %d, not at 0", sample_offsets[0], frame_offsets[0]);
+    std::vector<Span> spans((size_t)n_waves);
+    for (int i = 0; i < n_waves; ++i) {
+        Span& sp = spans[(size_t)i];
+        sp.x0 = sample_offsets[i]; sp.x_len = sample_offsets[i + 1] - sample_offsets[i];
+        sp.k0 = frame_offsets[i]; sp.n = frame_offsets[i + 1] - frame_offsets[i];
+        if (sp.x_len < 1) return fail(RY_EINVAL, "wave %d has %lld samples", i, sp.x_len);
+        if (sp.n < 1) return fail(RY_EINVAL, "wave %d has %d frames", i, sp.n);
+        if (frame_offsets[i + 1] > (1 << 22)) return fail(RY_EINVAL, "%d frames in one call", frame_offsets[i + 1]);
     }
-    if (verdict[0] != -1) return fail(RY_ESTATE, "the track check left %d", verdict[0]);
-    return run_kernels(s, s->d_x.ptr(), x_len, f0_dev, t_dev, n, true, o);
+    const long long x_len = sample_offsets[n_waves];
+    const int n = frame_offsets[n_waves];
+    bool empty = false;
+    RY_TRY(check_call(s, x_len, n, true, o, &empty));                   // never empty: every wave has a sample and a frame
+    if (!x32_dev) return fail(RY_EINVAL, "null wave");
+    if (!f0_dev || !t_dev) return fail(RY_EINVAL, "null f0 / t");
+    return extract_dev(s, x32_dev, x_len, f0_dev, t_dev, n, spans.data(), n_waves, o);
 }
 
 int ry_analysis_d4c_bands(ry_analysis* s) {

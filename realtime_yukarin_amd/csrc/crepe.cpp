@@ -6,6 +6,8 @@
 // tables the caller installs, ry_crepe_set_resampler).
 // ry_crepe_voicing turns the decode's (confidence, f0) into the voiced mask, the masked float64 f0 and the time axis (crepe_voicing: the two-state HMM
 // of `predict_voicing`); ry_crepe_track is predict + voicing in one enqueue, the track left on the card for ry_analysis_extract_dev.
+// ry_crepe_track_many is ry_crepe_track for a list of waves in one enqueue: the waves are uploaded back to back with a segment table (CrepeSeg), the
+// resampler runs over all of them, their frames share the passes of CHUNK, and the decode and the voicing run one workgroup per track.
 // ry_crepe_set_dtype(2) runs the seven GEMMs in split-bf16 form (crepe_igemm_x3) on filters split once into two bf16 planes; everything else is shared.
 #include "crepe_kernels.h"
 #include "ry_host.h"
@@ -79,6 +81,13 @@ struct ry_crepe {
     // what the last ry_crepe_track left on the card (ry_crepe_track_buffers); every other call that writes one of these buffers forgets it
     const float* trk_wave = nullptr;
     int trk_samples = 0, trk_frames = 0;
+    // many waves in one call: the segment table on the card and on the host, and what the last ry_crepe_track_many left (ry_crepe_track_many_buffers):
+    // the first sample / first frame of every wave and one entry behind the last, n_waves + 1 each; trk_waves = 0: no such track
+    DevBuf<CrepeSeg> segs{call};
+    std::vector<CrepeSeg> seg_host;
+    std::vector<long long> trk_sample_off;
+    std::vector<int> trk_frame_off;
+    int trk_waves = 0;
     // resampling: tables per input rate
     Arena rs_tables;
     std::map<int, Resampler> rs;
@@ -92,6 +101,9 @@ struct ry_crepe {
 };
 
 namespace {
+// every call that writes a buffer of the track on the card forgets it
+void forget_track(ry_crepe* c) { c->trk_frames = 0; c->trk_waves = 0; }
+
 int ensure_chunk(ry_crepe* c, int nf) {
     if (nf <= c->cap_chunk) return RY_OK;
     const int cap = nf;
@@ -175,7 +187,8 @@ int launch_layer(ry_crepe* c, int i, int nf, float* act) {
     return RY_OK;
 }
 
-int launch_decode(ry_crepe* c, const float* act, int nf, int viterbi) {
+// `seg` (device) / n_seg: the tracks of a segment table, nf frames in all; null: one track
+int launch_decode(ry_crepe* c, const float* act, int nf, int viterbi, const CrepeSeg* seg = nullptr, int n_seg = 1) {
     const ry_stream_t s = c->ctx->stream;
     CrepeArgmaxParams ap;
     ap.act = act; ap.n_frames = nf; ap.obs = c->obs.ptr(); ap.conf = c->conf.ptr();
@@ -184,7 +197,8 @@ int launch_decode(ry_crepe* c, const float* act, int nf, int viterbi) {
     CrepeDecodeParams dp;
     dp.act = act; dp.obs = c->obs.ptr(); dp.n_frames = nf; dp.viterbi = viterbi ? 1 : 0;
     dp.logT = c->logT; dp.logE = c->logE; dp.logS = c->logS; dp.bp = c->bp.ptr(); dp.path = c->path.ptr(); dp.f0 = c->f0.ptr();
-    RY_LAUNCH(crepe_decode, dim3(1), 384, s, dp);
+    dp.seg = seg;
+    RY_LAUNCH(crepe_decode, dim3((unsigned)n_seg), 384, s, dp);
     RT_TRY(rt::last_error());
     return RY_OK;
 }
@@ -200,19 +214,20 @@ int frame_count(int n_samples, int hop, int center, int* nf) {
 
 // the network and the decode on n_samples at 16 kHz in device memory, results to the caller (ensure_chunk / ensure_call have run)
 int run_network(ry_crepe* c, const float* d_audio, int n_samples, int hop, int center, int viterbi, int nf,
-                float* f0, float* confidence, float* activation, int on_device) {
+                float* f0, float* confidence, float* activation, int on_device, const CrepeSeg* seg = nullptr, int n_seg = 1) {
     const ry_stream_t s = c->ctx->stream;
     float* act_all = c->act.ptr();
     for (int f = 0; f < nf; f += CHUNK) {
         const int n = std::min(CHUNK, nf - f);
         CrepeFrameParams fp;
         fp.audio = d_audio; fp.n = n_samples; fp.hop = hop; fp.center = center; fp.frame0 = f; fp.n_frames = n; fp.out = c->act_in[0];
+        fp.seg = seg; fp.n_seg = n_seg;
         RY_LAUNCH(crepe_frames, dim3((unsigned)n), 256, s, fp);
         RT_TRY(rt::last_error());
         for (int i = 0; i <= NCONV; ++i) RY_TRY(launch_layer(c, i, n, act_all + (size_t)f * CREPE_BINS));
         c->last_chunk = n;
     }
-    RY_TRY(launch_decode(c, act_all, nf, viterbi));
+    RY_TRY(launch_decode(c, act_all, nf, viterbi, seg, n_seg));
     if (!f0 && !confidence && !activation) return RY_OK;                // ry_crepe_track: the results stay in the handle's buffers
     if (on_device) {
         RT_TRY(rt::d2d(f0, c->f0.ptr(), (size_t)nf * sizeof(float), s));
@@ -247,12 +262,13 @@ int resample_plan(ry_crepe* c, int n_samples, int sr, const Resampler** r, int* 
     return RY_OK;
 }
 
-int launch_resample(ry_crepe* c, const Resampler& r, const float* d_in, int n_in, int sr, float* d_out, int n_out) {
+int launch_resample(ry_crepe* c, const Resampler& r, const float* d_in, int n_in, int sr, float* d_out, int n_out, const CrepeSeg* seg = nullptr, int n_seg = 1) {
     CrepeResampleParams p;
     p.x = d_in; p.n_in = n_in; p.win = r.win; p.n_win = r.n_win; p.tr = r.tr;
     const double ratio = 16000.0 / sr;
     p.scale = ratio < 1.0 ? ratio : 1.0;
     p.num_table = r.num_table; p.step = r.step; p.y = d_out; p.n_out = n_out;
+    p.seg = seg; p.n_seg = n_seg;
     RY_LAUNCH(crepe_resample, dim3((unsigned)((n_out + 255) / 256)), 256, c->ctx->stream, p);
     RT_TRY(rt::last_error());
     return RY_OK;
@@ -260,12 +276,13 @@ int launch_resample(ry_crepe* c, const Resampler& r, const float* d_in, int n_in
 
 // the voicing of n frames whose confidence / f0 are in device memory, into device buffers (the handle's own, or a device caller's)
 int launch_voicing(ry_crepe* c, const float* conf, const float* f0, int n, double threshold, double step_ms,
-                   unsigned char* voiced, double* f0_64, double* t_64) {
+                   unsigned char* voiced, double* f0_64, double* t_64, const CrepeSeg* seg = nullptr, int n_seg = 1) {
     RY_TRY(c->v_bp.reserve(c->ctx, n));
     CrepeVoicingParams p;
     p.conf = conf; p.f0 = f0; p.n = n; p.threshold = (float)threshold; p.step_ms = step_ms; p.tab = c->vt;
     p.bp = c->v_bp.ptr(); p.voiced = voiced; p.f0_64 = f0_64; p.t_64 = t_64;
-    RY_LAUNCH(crepe_voicing, dim3(1), 256, c->ctx->stream, p);
+    p.seg = seg;
+    RY_LAUNCH(crepe_voicing, dim3((unsigned)n_seg), 256, c->ctx->stream, p);
     RT_TRY(rt::last_error());
     return RY_OK;
 }
@@ -274,6 +291,33 @@ int ensure_track(ry_crepe* c, int n) {
     RY_TRY(c->voiced.reserve(c->ctx, ((long long)n + 3) / 4 * 4));      // whole 32-bit words: ry_dev_download copies those
     RY_TRY(c->f0_64.reserve(c->ctx, n));
     RY_TRY(c->t_64.reserve(c->ctx, n));
+    return RY_OK;
+}
+
+// The segment table of n_waves tracks of n_frames[i] frames (in_len / n16: the samples of wave i at the caller's rate and at 16 kHz; null: tracks
+// alone) on the host and, one upload, on the card.  Refuses a list that is empty, a track with no frame and totals beyond what one call takes;
+// nothing is launched or written before it returns RY_OK.
+int plan_segments(int n_waves, const int* in_len, const int* n16, const int* n_frames, std::vector<CrepeSeg>* out) {
+    if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
+    out->resize((size_t)n_waves);
+    long long in_off = 0, off16 = 0, frame0 = 0;
+    for (int i = 0; i < n_waves; ++i) {
+        if (n_frames[i] < 1) return fail(RY_EINVAL, "track %d has %d frames", i, n_frames[i]);
+        CrepeSeg& g = (*out)[(size_t)i];
+        g.in_off = (int)in_off; g.in_len = in_len ? in_len[i] : 0; g.off16 = (int)off16; g.n16 = n16 ? n16[i] : 0;
+        g.frame0 = (int)frame0; g.n_frames = n_frames[i];
+        in_off += g.in_len; off16 += g.n16; frame0 += g.n_frames;
+        // the offsets are 32-bit on the card: a list whose samples or frames do not fit is refused, as the single calls refuse their sizes
+        if (in_off > 2147483647LL || off16 > 2147483647LL) return fail(RY_EINVAL, "the waves up to %d hold %lld samples (%lld at 16 kHz): too many for one call", i, in_off, off16);
+        if (frame0 > (1LL << 24)) return fail(RY_EINVAL, "%lld frames in one call", frame0);
+    }
+    return RY_OK;
+}
+
+int upload_segments(ry_crepe* c, const std::vector<CrepeSeg>& plan) {
+    RY_TRY(c->segs.reserve(c->ctx, (long long)plan.size()));
+    c->seg_host = plan;                                                 // the handle's copy: the host array of the upload outlives the call
+    RT_TRY(rt::h2d(c->segs.ptr(), c->seg_host.data(), c->seg_host.size() * sizeof(CrepeSeg), c->ctx->stream));
     return RY_OK;
 }
 
@@ -424,7 +468,7 @@ int ry_crepe_predict(ry_crepe* c, const float* audio, int n_samples, int hop, in
                      float* f0, float* confidence, float* activation, int on_device) {
     RY_TRY(check_handle(c, "crepe"));
     if (!audio || !f0 || !confidence || n_samples < 1 || hop < 1) return fail(RY_EINVAL, "bad argument");
-    c->trk_frames = 0;
+    forget_track(c);
     int nf = 0;
     RY_TRY(frame_count(n_samples, hop, center, &nf));
     ry_ctx* ctx = c->ctx;
@@ -469,7 +513,7 @@ int ry_crepe_set_resampler(ry_crepe* c, int sr, const double* win, int n_win, in
 int ry_crepe_resample(ry_crepe* c, const float* audio, int n_samples, int sr, float* out16k, int on_device) {
     RY_TRY(check_handle(c, "crepe"));
     if (!audio || !out16k) return fail(RY_EINVAL, "bad argument");
-    c->trk_frames = 0;
+    forget_track(c);
     const Resampler* r = nullptr;
     int n_out = 0;
     RY_TRY(resample_plan(c, n_samples, sr, &r, &n_out));
@@ -489,7 +533,7 @@ int ry_crepe_predict_sr(ry_crepe* c, const float* audio, int n_samples, int sr, 
     if (sr == 16000) return ry_crepe_predict(c, audio, n_samples, hop, center, viterbi, f0, confidence, activation, on_device);
     RY_TRY(check_handle(c, "crepe"));
     if (!audio || !f0 || !confidence || hop < 1) return fail(RY_EINVAL, "bad argument");
-    c->trk_frames = 0;
+    forget_track(c);
     const Resampler* r = nullptr;
     int n_out = 0, nf = 0;
     RY_TRY(resample_plan(c, n_samples, sr, &r, &n_out));
@@ -510,7 +554,7 @@ int ry_crepe_predict_sr(ry_crepe* c, const float* audio, int n_samples, int sr, 
 int ry_crepe_decode(ry_crepe* c, const float* activation, int n_frames, int viterbi, float* f0, float* confidence, int* path) {
     RY_TRY(check_handle(c, "crepe"));
     if (!activation || !f0 || !confidence || n_frames < 1 || n_frames > (1 << 24)) return fail(RY_EINVAL, "bad argument");
-    c->trk_frames = 0;
+    forget_track(c);
     const ry_stream_t s = c->ctx->stream;
     RY_TRY(ensure_call(c, n_frames, 0));
     RT_TRY(rt::h2d(c->act.ptr(), activation, (size_t)n_frames * CREPE_BINS * sizeof(float), s));
@@ -541,7 +585,7 @@ int ry_crepe_voicing(ry_crepe* c, const float* confidence, const float* f0, int 
     RY_TRY(check_handle(c, "crepe"));
     if (!confidence || !f0 || !voiced || !f0_64 || !t_64 || n < 1 || n > (1 << 24)) return fail(RY_EINVAL, "bad argument");
     RY_TRY(voicing_args(threshold, step_ms));
-    c->trk_frames = 0;
+    forget_track(c);
     if (on_device) return launch_voicing(c, confidence, f0, n, threshold, step_ms, voiced, f0_64, t_64);
     const ry_stream_t s = c->ctx->stream;
     RY_TRY(c->conf.reserve(c->ctx, n));
@@ -563,7 +607,7 @@ int ry_crepe_track(ry_crepe* c, const float* audio, int n_samples, int sr, int h
     if (!audio || !n_frames || n_samples < 1 || hop < 1) return fail(RY_EINVAL, "bad argument");
     if (!on_device_out && (!voiced || !f0_64 || !t_64)) return fail(RY_EINVAL, "null output");
     RY_TRY(voicing_args(threshold, step_ms));
-    c->trk_frames = 0;
+    forget_track(c);
     const ry_stream_t s = c->ctx->stream;
     const Resampler* r = nullptr;
     int n16 = n_samples, nf = 0;
@@ -601,6 +645,120 @@ int ry_crepe_track_buffers(ry_crepe* c, const float** wave_dev, int* n_samples, 
     if (voiced_dev) *voiced_dev = c->voiced.ptr();
     if (f0_dev) *f0_dev = c->f0_64.ptr();
     if (t_dev) *t_dev = c->t_64.ptr();
+    return RY_OK;
+}
+
+int ry_crepe_track_many(ry_crepe* c, const float* audio, const int* n_samples, int n_waves, int sr, int hop, double step_ms, double threshold,
+                        int* n_frames, unsigned char* voiced, double* f0_64, double* t_64, int on_device_out) {
+    RY_TRY(check_handle(c, "crepe"));
+    forget_track(c);                                                 // a refused call leaves no track either
+    if (!audio || !n_samples || !n_frames || hop < 1) return fail(RY_EINVAL, "bad argument");
+    if (!on_device_out && (!voiced || !f0_64 || !t_64)) return fail(RY_EINVAL, "null output");
+    if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
+    RY_TRY(voicing_args(threshold, step_ms));
+    // every refusal first: each wave is held to what ry_crepe_track asks of it, the list to the sizes one call takes
+    const Resampler* r = nullptr;
+    std::vector<int> n16((size_t)n_waves), nf((size_t)n_waves);
+    for (int i = 0; i < n_waves; ++i) {
+        if (n_samples[i] < 1) return fail(RY_EINVAL, "wave %d has %d samples", i, n_samples[i]);
+        n16[(size_t)i] = n_samples[i];
+        if (sr != 16000) RY_TRY(resample_plan(c, n_samples[i], sr, &r, &n16[(size_t)i]));
+        RY_TRY(frame_count(n16[(size_t)i], hop, 1, &nf[(size_t)i]));
+    }
+    std::vector<CrepeSeg> plan;
+    RY_TRY(plan_segments(n_waves, n_samples, n16.data(), nf.data(), &plan));
+    const CrepeSeg& last = plan.back();
+    const int total_in = last.in_off + last.in_len, total16 = last.off16 + last.n16, total_nf = last.frame0 + last.n_frames;
+    const ry_stream_t s = c->ctx->stream;
+    RY_TRY(ensure_chunk(c, std::min(total_nf, CHUNK)));
+    RY_TRY(ensure_call(c, total_nf, total16));
+    RY_TRY(ensure_track(c, total_nf));
+    float* wave = c->audio.ptr();                                    // the one upload: the waves at the caller's rate, back to back
+    if (r) {
+        RY_TRY(c->audio_sr.reserve(c->ctx, total_in));
+        wave = c->audio_sr.ptr();
+    }
+    RY_TRY(upload_segments(c, plan));
+    RT_TRY(rt::h2d(wave, audio, (size_t)total_in * sizeof(float), s));
+    const CrepeSeg* seg = c->segs.ptr();
+    if (r) RY_TRY(launch_resample(c, *r, wave, total_in, sr, c->audio.ptr(), total16, seg, n_waves));
+    RY_TRY(run_network(c, c->audio.ptr(), total16, hop, 1, 1, total_nf, nullptr, nullptr, nullptr, 1, seg, n_waves));
+    RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), total_nf, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr(), seg, n_waves));
+    c->trk_wave = wave;
+    c->trk_sample_off.assign((size_t)n_waves + 1, 0);
+    c->trk_frame_off.assign((size_t)n_waves + 1, 0);
+    for (int i = 0; i < n_waves; ++i) {
+        c->trk_sample_off[(size_t)i + 1] = (long long)plan[(size_t)i].in_off + plan[(size_t)i].in_len;
+        c->trk_frame_off[(size_t)i + 1] = plan[(size_t)i].frame0 + plan[(size_t)i].n_frames;
+        n_frames[i] = nf[(size_t)i];
+    }
+    c->trk_waves = n_waves;
+    if (on_device_out) return RY_OK;
+    RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)total_nf, s));
+    RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)total_nf * sizeof(double), s));
+    RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)total_nf * sizeof(double), s));
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+int ry_crepe_track_many_buffers(ry_crepe* c, const float** wave_dev, int* n_waves, const long long** sample_offsets, const int** frame_offsets,
+                                const unsigned char** voiced_dev, const double** f0_dev, const double** t_dev) {
+    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    if (c->trk_waves < 1) return fail(RY_ESTATE, "no tracks on the card: ry_crepe_track_many has not run, or a later call reused its buffers");
+    if (wave_dev) *wave_dev = c->trk_wave;
+    if (n_waves) *n_waves = c->trk_waves;
+    if (sample_offsets) *sample_offsets = c->trk_sample_off.data();
+    if (frame_offsets) *frame_offsets = c->trk_frame_off.data();
+    if (voiced_dev) *voiced_dev = c->voiced.ptr();
+    if (f0_dev) *f0_dev = c->f0_64.ptr();
+    if (t_dev) *t_dev = c->t_64.ptr();
+    return RY_OK;
+}
+
+int ry_crepe_decode_many(ry_crepe* c, const float* activation, const int* n_frames, int n_tracks, int viterbi, float* f0, float* confidence, int* path) {
+    RY_TRY(check_handle(c, "crepe"));
+    if (!activation || !n_frames || !f0 || !confidence) return fail(RY_EINVAL, "bad argument");
+    forget_track(c);
+    std::vector<CrepeSeg> plan;
+    RY_TRY(plan_segments(n_tracks, nullptr, nullptr, n_frames, &plan));
+    const int total = plan.back().frame0 + plan.back().n_frames;
+    const ry_stream_t s = c->ctx->stream;
+    RY_TRY(ensure_call(c, total, 0));
+    RY_TRY(upload_segments(c, plan));
+    RT_TRY(rt::h2d(c->act.ptr(), activation, (size_t)total * CREPE_BINS * sizeof(float), s));
+    RY_TRY(launch_decode(c, c->act.ptr(), total, viterbi, c->segs.ptr(), n_tracks));
+    RT_TRY(rt::d2h(f0, c->f0.ptr(), (size_t)total * sizeof(float), s));
+    RT_TRY(rt::d2h(confidence, c->conf.ptr(), (size_t)total * sizeof(float), s));
+    if (path) RT_TRY(rt::d2h(path, viterbi ? c->path.ptr() : c->obs.ptr(), (size_t)total * sizeof(int), s));
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+int ry_crepe_voicing_many(ry_crepe* c, const float* confidence, const float* f0, const int* n_frames, int n_tracks, double threshold, double step_ms,
+                          unsigned char* voiced, double* f0_64, double* t_64, int on_device) {
+    RY_TRY(check_handle(c, "crepe"));
+    if (!confidence || !f0 || !n_frames || !voiced || !f0_64 || !t_64) return fail(RY_EINVAL, "bad argument");
+    RY_TRY(voicing_args(threshold, step_ms));
+    forget_track(c);
+    std::vector<CrepeSeg> plan;
+    RY_TRY(plan_segments(n_tracks, nullptr, nullptr, n_frames, &plan));
+    const int n = plan.back().frame0 + plan.back().n_frames;
+    const ry_stream_t s = c->ctx->stream;
+    if (on_device) {
+        RY_TRY(upload_segments(c, plan));
+        return launch_voicing(c, confidence, f0, n, threshold, step_ms, voiced, f0_64, t_64, c->segs.ptr(), n_tracks);
+    }
+    RY_TRY(c->conf.reserve(c->ctx, n));
+    RY_TRY(c->f0.reserve(c->ctx, n));
+    RY_TRY(ensure_track(c, n));
+    RY_TRY(upload_segments(c, plan));
+    RT_TRY(rt::h2d(c->conf.ptr(), confidence, (size_t)n * sizeof(float), s));
+    RT_TRY(rt::h2d(c->f0.ptr(), f0, (size_t)n * sizeof(float), s));
+    RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), n, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr(), c->segs.ptr(), n_tracks));
+    RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)n, s));
+    RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)n * sizeof(double), s));
+    RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)n * sizeof(double), s));
+    RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }
 
@@ -647,7 +805,7 @@ int ry_crepe_debug_poison(ry_crepe* c) {
         RT_TRY(rt::dmemset(c->slabs, 0xff, c->slab_floats * sizeof(float), s));
     }
     for (DevBufBase* b : c->call) RY_TRY(b->poison(s));               // the voicing's back-pointers and the masked track are on this list too
-    c->trk_frames = 0;
+    forget_track(c);
     RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }

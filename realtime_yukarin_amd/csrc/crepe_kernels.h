@@ -32,18 +32,49 @@
 // subtracted and is divided by its population standard deviation, both taken in float64; the divisor is clamped at 1e-10 so that a
 // digitally silent frame gives zeros, not NaN (the one deliberate difference from the original).
 // ---------------------------------------------------------------------------------------------
-struct CrepeFrameParams { const float* audio; int n, hop, center, frame0, n_frames; float* out; };
+// Many waves in one call (ry_crepe_track_many): the waves lie back to back in one buffer and a table says where -- per wave its samples at
+// the caller's rate, its samples at 16 kHz and its frames, each as (first, count) in the concatenated buffers.  A kernel that is handed a
+// table (`seg`; null: one wave, the call's own sizes) finds the wave of a frame or an output sample by bisection -- every wave has at least
+// one sample and one frame, so the starts rise strictly -- and from there on works with indices local to that wave: the wave's own length,
+// its own centre padding, its own time register, its own first frame.  The arithmetic is the single call's.
+struct CrepeSeg { int in_off, in_len, off16, n16, frame0, n_frames; };
+
+RY_DEV int crepe_seg_of_frame(const CrepeSeg* seg, int n_seg, int f) {
+    int lo = 0, hi = n_seg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (seg[mid].frame0 <= f) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+RY_DEV int crepe_seg_of_sample16(const CrepeSeg* seg, int n_seg, int t) {
+    int lo = 0, hi = n_seg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (seg[mid].off16 <= t) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+struct CrepeFrameParams { const float* audio; int n, hop, center, frame0, n_frames; float* out; const CrepeSeg* seg; int n_seg; };
 
 RY_KERNEL(256) void crepe_frames(CrepeFrameParams p) {
     __shared__ double red[256];
     const int tid = (int)threadIdx.x;
-    const int f = p.frame0 + (int)blockIdx.x;
+    int f = p.frame0 + (int)blockIdx.x;
+    const float* audio = p.audio;
+    int n_audio = p.n;
+    if (p.seg) {                                                   // block-uniform: frame f of the call is frame f - frame0 of its wave
+        const CrepeSeg sg = p.seg[crepe_seg_of_frame(p.seg, p.n_seg, f)];
+        audio = p.audio + sg.off16; n_audio = sg.n16; f -= sg.frame0;
+    }
     const long long s0 = (long long)f * p.hop - (p.center ? CREPE_FRAME / 2 : 0) + 4 * tid;
     float v[4];
     double s = 0.0;
     for (int i = 0; i < 4; ++i) {
         const long long s_i = s0 + i;
-        v[i] = (s_i >= 0 && s_i < p.n) ? p.audio[s_i] : 0.f;
+        v[i] = (s_i >= 0 && s_i < n_audio) ? audio[s_i] : 0.f;
         s += (double)v[i];
     }
     red[tid] = s;
@@ -79,13 +110,20 @@ struct CrepeResampleParams {
     double scale;                      // min(1, ratio)
     int num_table, step;               // table entries per zero crossing; entries per input sample = int(scale * num_table)
     float* y; int n_out;
+    const CrepeSeg* seg; int n_seg;    // many waves: x and y are the concatenated buffers, n_out the outputs of all waves, n_in is not read
 };
 
 RY_KERNEL(256) void crepe_resample(CrepeResampleParams p) {
 #pragma clang fp contract(off)
     const int t = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (t >= p.n_out) return;
-    const double tr = p.tr[t];
+    const float* x = p.x;
+    int n_in = p.n_in, tl = t;
+    if (p.seg) {                                                   // output t of the call is output t - off16 of its wave: that wave's register entry, its samples only
+        const CrepeSeg sg = p.seg[crepe_seg_of_sample16(p.seg, p.n_seg, t)];
+        x = p.x + sg.in_off; n_in = sg.in_len; tl = t - sg.off16;
+    }
+    const double tr = p.tr[tl];
     const int n = (int)tr;                                         // 0 <= tr < 2^31 (ry_crepe_set_resampler)
     const double frac0 = p.scale * (tr - (double)n);
     double acc = 0.0;
@@ -95,9 +133,9 @@ RY_KERNEL(256) void crepe_resample(CrepeResampleParams p) {
         const int offset = (int)index_frac;                        // 0 .. num_table
         const double eta = index_frac - (double)offset;
         const int lim = (p.n_win - offset) / p.step;
-        const int room = side ? p.n_in - n - 1 : n + 1;
+        const int room = side ? n_in - n - 1 : n + 1;
         const int cap = room < lim ? room : lim;
-        const float* xs = p.x + (side ? n + 1 : n);
+        const float* xs = x + (side ? n + 1 : n);
         const double* w = p.win + offset;
         const int dir = side ? 1 : -1;
         for (int i = 0; i < cap; ++i) {
@@ -440,7 +478,7 @@ RY_KERNEL(256) void crepe_reduce_sig(CrepeReduceSigParams p) {
 
 // ---------------------------------------------------------------------------------------------
 // Decode.  crepe_argmax: one wave per frame, observation = argmax (lowest index on ties), confidence = max.
-// crepe_decode: ONE workgroup.  viterbi = 1: the 360-state Viterbi pass over all frames in float64 with the host's tables
+// crepe_decode: ONE workgroup per track (one track, or the tracks of a segment table side by side).  viterbi = 1: the 360-state Viterbi pass over all frames in float64 with the host's tables
 //   lat[0][j] = logS[j] + logE[j][obs 0];  lat[t][j] = max_i (lat[t - 1][i] + logT[i][j]) + logE[j][obs t]   (lowest i wins a tie)
 //   -- the additions of the numpy restatement in its order; only |i - j| <= 11 is visited (logT is -inf elsewhere and the lattice is
 //   finite, so the maximum and its index are the same) -- back-pointers in global memory, the backtrack by one lane.
@@ -473,13 +511,19 @@ struct CrepeDecodeParams {
     int* bp;                   // [n_frames][360] back-pointers
     int* path;                 // [n_frames]
     float* f0;
+    const CrepeSeg* seg;       // many tracks: one workgroup each (grid = tracks), every array above the concatenated one; n_frames is not read
 };
 
 RY_KERNEL(384) void crepe_decode(CrepeDecodeParams p) {
     __shared__ double lat[2][CREPE_BINS];
     __shared__ double tb[(2 * CREPE_BAND + 1) * CREPE_BINS];      // logT[j - 11 + d][j] at [d][j]: a wave reads consecutive doubles
     const int tid = (int)threadIdx.x;
-    const int n = p.n_frames;
+    int n = p.n_frames;
+    if (p.seg) {                                                   // this workgroup's track: its own rows of every array, its own start from logS
+        const CrepeSeg sg = p.seg[blockIdx.x];
+        n = sg.n_frames;
+        p.act += (size_t)sg.frame0 * CREPE_BINS; p.obs += sg.frame0; p.bp += (size_t)sg.frame0 * CREPE_BINS; p.path += sg.frame0; p.f0 += sg.frame0;
+    }
     if (p.viterbi) {
         const int j = tid;
         const bool live = j < CREPE_BINS;
@@ -549,7 +593,7 @@ RY_KERNEL(384) void crepe_decode(CrepeDecodeParams p) {
 // Voicing (`predict_voicing` of realtime_yukarin_amd/crepe.py and the mask the reference's wrapper makes of it): the Viterbi path of a
 // two-state Gaussian HMM over the confidence, voiced = (path == 1) | (confidence > threshold) -- the comparison in float32 against the threshold
 // rounded to float32, which is how numpy evaluates `confidence > 0.1` on a float32 array -- the masked f0 and the time axis in float64.
-// ONE workgroup; the frames run in chunks of CREPE_VOICING_CHUNK through the LDS, so a call may be of any length:
+// ONE workgroup per track; the frames run in chunks of CREPE_VOICING_CHUNK through the LDS, so a call may be of any length:
 //   forward, chunk by chunk: every lane computes logp[t][s] = -0.5 * (c[s] + (x - mu[s]) * (x - mu[s]) / var[s]) of its frames into the LDS; lane 0
 //     walks the chunk -- s[i][j] = lat[i] + logT[i][j], bp[j] = s[1][j] > s[0][j] (the lowest state wins a tie), lat[j] = s[bp[j]][j] + logp[t][j],
 //     the lattice in its registers from chunk to chunk -- and leaves the two back-pointer bits of every frame in the LDS; every lane copies them out
@@ -570,6 +614,7 @@ struct CrepeVoicingParams {
     CrepeVoicingTables tab;
     unsigned char* bp;                             // [n] scratch: bit j of entry t = the state before state j of frame t
     unsigned char* voiced; double* f0_64; double* t_64;
+    const CrepeSeg* seg;                           // many tracks: one workgroup each (grid = tracks), every array the concatenated one; n is not read
 };
 
 RY_KERNEL(256) void crepe_voicing(CrepeVoicingParams p) {
@@ -577,7 +622,12 @@ RY_KERNEL(256) void crepe_voicing(CrepeVoicingParams p) {
     __shared__ double lp[CREPE_VOICING_CHUNK][2];
     __shared__ unsigned char bits[CREPE_VOICING_CHUNK];            // forward: back-pointer bits; backward: the same, then the path
     const int tid = (int)threadIdx.x;
-    const int n = p.n;
+    int n = p.n;
+    if (p.seg) {                                                   // this workgroup's track: its own entries, its own back-pointers, k counted from its first frame
+        const CrepeSeg sg = p.seg[blockIdx.x];
+        n = sg.n_frames;
+        p.conf += sg.frame0; p.f0 += sg.frame0; p.bp += sg.frame0; p.voiced += sg.frame0; p.f0_64 += sg.frame0; p.t_64 += sg.frame0;
+    }
     const CrepeVoicingTables& T = p.tab;
     double lat0 = 0.0, lat1 = 0.0;                                 // lane 0 only
     for (int base = 0; base < n; base += CREPE_VOICING_CHUNK) {

@@ -19,7 +19,8 @@ from .world_synth import cheaptrick_fft_size
 crepe_classes = set()              # classes whose extract_f0 is the reference's CREPE body (`install` adds one)
 model_capacity = 'full'            # the capacity the wrapper asks `crepe.predict` for (tests set a smaller one)
 threshold = 0.1                    # its confidence threshold
-calls = {'fused': 0, 'unfused': 0}      # which path `extract` took, counted per call
+max_many_frames = 1 << 22         # frames one `Analyzer.run_device_many` takes (`ry_analysis_extract_many_dev`); a longer list is encoded wave by wave
+calls = {'fused': 0, 'unfused': 0, 'many': 0}      # which path `extract` took, counted per call; 'many': batched calls of `extract_many`
 
 
 def install(acoustic_feature, *crepe_wrappers) -> None:
@@ -71,3 +72,43 @@ def extract(cls, wave, frame_period, f0_floor, f0_ceil, fft_length, order, alpha
     feature = feature.astype_only_float(dtype)
     feature.validate()
     return feature
+
+
+def _frames(waves, frame_period) -> int:
+    """The frames `CrepeModel.track_many` makes of the waves (fusable, one rate): counted as the device counts them."""
+    fs, hop = int(waves[0].sampling_rate), _crepe.hop_length(frame_period)
+    n16 = [numpy.asarray(w.wave).size if fs == _crepe.MODEL_SRATE else _crepe.resampled_length(numpy.asarray(w.wave).size, fs) for w in waves]
+    return sum(_crepe.n_frames(n, hop, True) if n >= 1 else 0 for n in n16)
+
+
+def extract_many(cls, waves, frame_period, f0_floor, f0_ceil, fft_length, order, alpha, dtype):
+    """`extract` for a list of waves in one device call: -> a list of containers, one per wave, each equal to
+    `extract(cls, wave, ...)` bit for bit.  Batched (`calls['many']` counts the call) when every wave passes the conditions of the fused path and
+    all share one sampling rate and the list has at most `max_many_frames` frames in all (what one analysis call takes); otherwise
+    `[extract(cls, w, ...) for w in waves]`, each counted as `extract` counts it.  An empty list: []."""
+    waves = list(waves)
+    args = (frame_period, f0_floor, f0_ceil, fft_length, order, alpha, dtype)
+    if not waves or not all(_fusable(cls, w) for w in waves) or len({int(w.sampling_rate) for w in waves}) != 1 or _frames(waves, frame_period) > max_many_frames:
+        return [extract(cls, w, *args) for w in waves]
+    calls['many'] = calls.get('many', 0) + 1
+    from .compat import crepe as shim
+    fs = int(waves[0].sampling_rate)
+    xs = [numpy.ascontiguousarray(w.wave, dtype=numpy.float32) for w in waves]
+    model = shim._model(model_capacity)
+    fft_size = int(fft_length) if fft_length else cheaptrick_fft_size(fs)
+    analyzer = world_analysis._analyzer(fs, fft_size, order, float(alpha))
+    analyzer._get()
+    trk = model.track_many(xs, fs, _crepe.hop_length(frame_period), frame_period, threshold=threshold, device=True)
+    if trk.ctx is not analyzer._ctx:                                    # two contexts: two streams, nothing orders them but the host
+        trk.ctx.lib.check(trk.ctx.lib.dll.ry_sync(trk.ctx.handle))
+    sp, mc, ap, coded_ap = analyzer.run_device_many(trk.wave, trk.sample_offsets, trk.f0, trk.t, trk.frame_offsets, want=('sp', 'mc', 'ap', 'coded_ap'))
+    container = next(k for k in cls.__mro__ if 'astype_only_float' in vars(k))
+    out, o = [], trk.frame_offsets
+    for i, (_, f0) in enumerate(trk.download()):
+        a, b = int(o[i]), int(o[i + 1])
+        voiced = ~(f0 == 0)                                             # as the unfused body derives it: from the masked f0
+        feature = container(f0=f0[:, None], sp=sp[a:b], ap=ap[a:b], coded_ap=coded_ap[a:b], mc=mc[a:b], voiced=voiced[:, None])
+        feature = feature.astype_only_float(dtype)
+        feature.validate()
+        out.append(feature)
+    return out

@@ -129,6 +129,24 @@ class Analyzer(DeviceHandle):
         lib.check(lib.dll.ry_analysis_extract_dev(h, _lib._fptr(int(wave_dev)), n_samples, as_d(f0_dev), as_d(t_dev), n, float(threshold), *(out_sp + out_ap)))
         return tuple(got[k] for k in want)
 
+    def run_device_many(self, wave_dev: int, sample_offsets, f0_dev: int, t_dev: int, frame_offsets, want=('sp', 'mc', 'ap', 'coded_ap'),
+                        device_rows: bool = False, threshold: float = 0.85):
+        """`run_device` on the waves and tracks `CrepeModel.track_many(..., device=True)` left on the card (`ry_analysis_extract_many_dev`): the waves
+        back to back at `wave_dev`, the tracks back to back at `f0_dev` / `t_dev`, wave i at sample_offsets[i] / frame_offsets[i] (waves + 1 entries
+        each, starting at 0).  One check of the whole track and one wait for its verdict; the rows of all waves come back concatenated in wave order
+        -- the same `want` keys as `run`, rows of wave i with the bits of `run_device` on wave i alone."""
+        lib, h = self._get()
+        self._check_want(want)
+        so = numpy.ascontiguousarray(sample_offsets, dtype=numpy.int64).ravel()
+        fo = numpy.ascontiguousarray(frame_offsets, dtype=numpy.int32).ravel()
+        if so.size != fo.size or so.size < 2:
+            raise ValueError('run_device_many needs two offset arrays of waves + 1 >= 2 entries, got %d and %d' % (so.size, fo.size))
+        got, out_sp, out_ap = self._outputs(max(int(fo[-1]), 0), want, device_rows)
+        as_d = lambda a: ctypes.cast(ctypes.c_void_p(a), _DP)
+        lib.check(lib.dll.ry_analysis_extract_many_dev(h, _lib._fptr(int(wave_dev)), so.ctypes.data_as(_LLP), as_d(f0_dev), as_d(t_dev),
+                                                       fo.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), so.size - 1, float(threshold), *(out_sp + out_ap)))
+        return tuple(got[k] for k in want)
+
     def d4c(self, x, f0, t, threshold: float = 0.85) -> numpy.ndarray:
         """`pyworld.d4c` of this analyzer's rate: -> aperiodicity [frames][513] float64."""
         return self.run(x, f0, t, want=('ap',), threshold=threshold)[0]
