@@ -413,9 +413,20 @@ int ry_synth_push(ry_synth* synth, const double* f0, const float* sp, const floa
                   double* y, int y_capacity, int* n_out);
 int ry_synth_flush(ry_synth* synth, double* y, int y_capacity, int* n_out);
 int ry_synth_reset(ry_synth* synth);
+/* One shot, many waves: wave b has n_frames[b] frames; f0 (HOST), sp and ap (rows on the host, or with on_device on the card, read where
+ * they are) hold the waves back to back.  y receives the waves back to back, wave b at y[sample_offsets[b]] with
+ * sample_offsets[b + 1] - sample_offsets[b] = ry_synth_length(n_frames[b]) samples; sample_offsets has n_waves + 1 entries.  Every wave has the
+ * bits of ry_synth_run on it alone.  Drops a stream in progress and leaves the stream reset.  Refused before anything is launched or written
+ * (y and sample_offsets untouched): null pointers, n_waves < 1, a wave without a frame, bins != 513, f0 that ry_synth_run refuses (the message
+ * names wave and frame), y_capacity below the total, more than 2^22 frames or 2^30 - n_waves samples in all.  INTEGRATION.md section 10. */
+int ry_synth_run_many(ry_synth* synth, const double* f0, const float* sp, const float* ap, const int* n_frames, int n_waves, int bins,
+                      int on_device, double* y, long long y_capacity, long long* sample_offsets);
 /* tests: the pulses the last run / push / flush found: sample index, fractional shift in samples [0, 1), voiced flag.  All three arrays
- * null: the count alone. */
+ * null: the count alone.  After ry_synth_run_many: none (count 0) -- its pulse lists stay on the card, see ry_synth_debug_pulses_many. */
 int ry_synth_debug_pulses(ry_synth* synth, long long* index, double* shift, int* voiced, int capacity, int* n);
+/* tests: the same for wave `wave` of the last ry_synth_run_many, indices counted from the wave's first sample (read from the card here).
+ * RY_ESTATE when the last call was another one or ry_synth_debug_poison has run since. */
+int ry_synth_debug_pulses_many(ry_synth* synth, int wave, long long* index, double* shift, int* voiced, int capacity, int* n);
 /* tests: fills every scratch buffer and the unused part of the frame window with NaN bit patterns: a later call that reads anything it
  * did not write shows it in its output. */
 int ry_synth_debug_poison(ry_synth* synth);

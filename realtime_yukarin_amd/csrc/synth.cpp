@@ -4,6 +4,8 @@
 // two neighbouring frames are there, computes the response of every pulse that has a successor and emits the samples no later pulse can
 // reach.  Nothing but the wrapped phase, the pulse list and the frame window is carried from one push to the next: responses of pulses that
 // straddle a push boundary are computed again from the same inputs (the same bits), so any cut of a stream equals the one-shot call.
+// ry_synth_run_many is the one-shot call for a list of waves: the same three kernels over a segment table (SynthSeg), one scan workgroup per
+// wave, the pulses and the samples of all waves in one launch each.  It keeps no stream state and brings no pulse list to the host.
 #include "synth_kernels.h"
 #include "ry_host.h"
 
@@ -33,6 +35,14 @@ struct ry_synth {
     DevBuf<double> d_f0{scratch}, d_pshift{scratch}, d_resp{scratch}, d_y{scratch};
     DevBuf<long long> d_pidx{scratch};                // d_pidx / d_pshift / d_pvoiced: the pulse list, grown together
     DevBuf<int> d_pvoiced{scratch};
+    // many waves in one call: the packed f0, the zeroed scan states and the segment table in ONE buffer (one upload), the first response row of
+    // every wave, host rows brought over; what the last ry_synth_run_many left for ry_synth_debug_pulses_many (empty: no such call)
+    DevBuf<double> d_many{scratch};
+    DevBuf<int> d_rstart{scratch};
+    DevBuf<float> d_sp_many{scratch}, d_ap_many{scratch};
+    std::vector<double> many_host;
+    std::vector<int> rstart_host;
+    std::vector<int> many_pulse0;
 };
 
 namespace {
@@ -54,13 +64,56 @@ long long known_samples(const ry_synth* s, long long m) {
 
 long long frame_of(const ry_synth* s, long long sample) { return sample <= 0 ? 0 : (long long)std::floor((double)sample / s->spf); }
 
+enum { SYNTH_MAX_FRAMES = 1 << 22, SYNTH_MAX_PULSES = 1 << 30 };      // frames of one call; entries of the pulse arrays of one call
+
+// wave >= 0: the frames are those of that wave of a batched call (the message names it)
+int check_f0(const ry_synth* s, const double* f0, int n_frames, int wave = -1) {
+    for (int i = 0; i < n_frames; ++i)
+        if (!std::isfinite(f0[i]) || !(f0[i] < 0.5 * s->fs))
+            return wave < 0 ? fail(RY_EINVAL, "f0[%d] = %g: finite and below fs / 2", i, f0[i])
+                            : fail(RY_EINVAL, "wave %d: f0[%d] = %g: finite and below fs / 2", wave, i, f0[i]);
+    return RY_OK;
+}
+
 int check_frames(const ry_synth* s, const double* f0, const float* sp, const float* ap, int n_frames) {
     if (!f0 || !sp || !ap) return fail(RY_EINVAL, "null f0 / sp / ap");
     if (n_frames < 1) return fail(RY_EINVAL, "n_frames = %d: at least one frame", n_frames);
-    if (n_frames > (1 << 22)) return fail(RY_EINVAL, "%d frames in one call", n_frames);
-    for (int i = 0; i < n_frames; ++i)
-        if (!std::isfinite(f0[i]) || !(f0[i] < 0.5 * s->fs)) return fail(RY_EINVAL, "f0[%d] = %g: finite and below fs / 2", i, f0[i]);
+    if (n_frames > SYNTH_MAX_FRAMES) return fail(RY_EINVAL, "%d frames in one call", n_frames);
+    return check_f0(s, f0, n_frames);
+}
+
+double threshold_f0(const ry_synth* s, double f0) { return f0 < s->lowest_f0 ? 0.0 : f0; }
+
+// The pulse arrays, grown together, and the parameters of the three kernels that do not depend on the call: what `advance` and
+// ry_synth_run_many share.  The caller adds the frames, the sample range and, for many waves, the segment table.
+int grow_pulses(ry_synth* s, long long n_p) {
+    RY_TRY(s->d_pidx.grow(s->ctx, n_p));
+    RY_TRY(s->d_pshift.grow(s->ctx, n_p));
+    RY_TRY(s->d_pvoiced.grow(s->ctx, n_p));
     return RY_OK;
+}
+
+SynthScanParams scan_params(const ry_synth* s) {
+    SynthScanParams p;
+    memset(&p, 0, sizeof p);
+    p.spf = s->spf; p.fs = (double)s->fs; p.st = s->st;
+    p.pidx = s->d_pidx.ptr(); p.pshift = s->d_pshift.ptr(); p.pvoiced = s->d_pvoiced.ptr(); p.cap = (int)s->d_pidx.cap;
+    return p;
+}
+
+SynthPulseParams pulse_params(const ry_synth* s) {
+    SynthPulseParams p;
+    memset(&p, 0, sizeof p);
+    p.pidx = s->d_pidx.ptr(); p.pshift = s->d_pshift.ptr(); p.pvoiced = s->d_pvoiced.ptr();
+    p.spf = s->spf; p.seed_hash = s->seed_hash; p.tw = s->tw; p.dc = s->dc; p.resp = s->d_resp.ptr();
+    return p;
+}
+
+SynthOverlapParams overlap_params(const ry_synth* s) {
+    SynthOverlapParams p;
+    memset(&p, 0, sizeof p);
+    p.pidx = s->d_pidx.ptr(); p.resp = s->d_resp.ptr(); p.y = s->d_y.ptr();
+    return p;
 }
 
 // appends frames to the window; rows before `keep_from` (absolute) are dropped on the way
@@ -96,7 +149,7 @@ int append_frames(ry_synth* s, const double* f0, const float* sp, const float* a
         RT_TRY(rt::stream_sync(st));                               // the caller's arrays are free when the call returns
     }
     s->f0.erase(s->f0.begin(), s->f0.begin() + (keep_from - s->frame0));
-    for (int i = 0; i < n; ++i) s->f0.push_back(f0[i] < s->lowest_f0 ? 0.0 : f0[i]);
+    for (int i = 0; i < n; ++i) s->f0.push_back(threshold_f0(s, f0[i]));
     s->frame0 = keep_from;
     s->cur = to;
     s->n_frames += n;
@@ -120,12 +173,10 @@ int advance(ry_synth* s, bool final, double* y, long long y_capacity, long long*
         return fail(RY_EINVAL, "y holds %lld samples, this call may return up to %lld", y_capacity, k1 - s->done);
     const long long n_new = k1 - s->scanned;
     const long long n_old = (long long)s->live.size();
-    if (n_old + n_new + 1 > (1LL << 30)) return fail(RY_EINVAL, "%lld samples in one call", n_new);
+    if (n_old + n_new + 1 > SYNTH_MAX_PULSES) return fail(RY_EINVAL, "%lld samples in one call", n_new);
     // the pulse arrays: the live pulses, then what the scan appends (at most one pulse per sample)
     const long long n_p = n_old + n_new + 1;                       // (grow's n_p + n_p / 2 + 64 is the n_p * 3 / 2 + 64 these have always had)
-    RY_TRY(s->d_pidx.grow(s->ctx, n_p));
-    RY_TRY(s->d_pshift.grow(s->ctx, n_p));
-    RY_TRY(s->d_pvoiced.grow(s->ctx, n_p));
+    RY_TRY(grow_pulses(s, n_p));
     RY_TRY(s->d_f0.grow(s->ctx, (long long)s->f0.size()));
     std::vector<long long> hidx(n_old); std::vector<double> hshift(n_old); std::vector<int> hvo(n_old);
     for (long long i = 0; i < n_old; ++i) { hidx[i] = s->live[i].idx; hshift[i] = s->live[i].shift; hvo[i] = s->live[i].voiced; }
@@ -139,12 +190,12 @@ int advance(ry_synth* s, bool final, double* y, long long y_capacity, long long*
     SynthScanState hs;
     long long total = n_old;
     s->last_call.clear();
+    s->many_pulse0.clear();
     if (n_new > 0) {
         const int n_old_i = (int)n_old;
         RT_TRY(rt::h2d(&s->st->n_pulses, &n_old_i, sizeof(int), st));
-        SynthScanParams sp;
-        sp.f0 = s->d_f0.ptr(); sp.frame0 = s->frame0; sp.last_frame = m - 1; sp.n0 = s->scanned; sp.n1 = k1; sp.spf = s->spf; sp.fs = (double)s->fs;
-        sp.st = s->st; sp.pidx = s->d_pidx.ptr(); sp.pshift = s->d_pshift.ptr(); sp.pvoiced = s->d_pvoiced.ptr(); sp.cap = (int)s->d_pidx.cap;
+        SynthScanParams sp = scan_params(s);
+        sp.f0 = s->d_f0.ptr(); sp.frame0 = s->frame0; sp.last_frame = m - 1; sp.n0 = s->scanned; sp.n1 = k1;
         RY_LAUNCH(synth_scan, dim3(1), 256, st, sp);
         RT_TRY(rt::last_error());
         RT_TRY(rt::d2h(&hs, s->st, sizeof hs, st));
@@ -174,16 +225,15 @@ int advance(ry_synth* s, bool final, double* y, long long y_capacity, long long*
     if (n_emit > 0) {
         if (complete > 0) {
             RY_TRY(s->d_resp.grow(s->ctx, complete * SYNTH_FFT));
-            SynthPulseParams pp;
-            pp.pidx = s->d_pidx.ptr(); pp.pshift = s->d_pshift.ptr(); pp.pvoiced = s->d_pvoiced.ptr(); pp.n_pulses = (int)total; pp.n_complete = (int)complete;
-            pp.sp = s->sp[s->cur]; pp.ap = s->ap[s->cur]; pp.frame0 = s->frame0; pp.last_frame = m - 1; pp.spf = s->spf;
-            pp.seed_hash = s->seed_hash; pp.tw = s->tw; pp.dc = s->dc; pp.resp = s->d_resp.ptr();
+            SynthPulseParams pp = pulse_params(s);
+            pp.n_pulses = (int)total; pp.n_complete = (int)complete;
+            pp.sp = s->sp[s->cur]; pp.ap = s->ap[s->cur]; pp.frame0 = s->frame0; pp.last_frame = m - 1;
             RY_LAUNCH(synth_pulse, dim3((unsigned)complete), 256, st, pp);
             RT_TRY(rt::last_error());
         }
         RY_TRY(s->d_y.grow(s->ctx, n_emit));
-        SynthOverlapParams op;
-        op.pidx = s->d_pidx.ptr(); op.n_complete = (int)complete; op.resp = s->d_resp.ptr(); op.s0 = s->done; op.s1 = fin; op.y = s->d_y.ptr();
+        SynthOverlapParams op = overlap_params(s);
+        op.n_complete = (int)complete; op.s0 = s->done; op.s1 = fin;
         RY_LAUNCH(synth_overlap, dim3((unsigned)((n_emit + 255) / 256)), 256, st, op);
         RT_TRY(rt::last_error());
         RT_TRY(rt::d2h(y, s->d_y.ptr(), (size_t)n_emit * sizeof(double), st));
@@ -311,6 +361,108 @@ int ry_synth_run(ry_synth* s, const double* f0, const float* sp, const float* ap
     return rc != RY_OK ? rc : rc2;
 }
 
+int ry_synth_run_many(ry_synth* s, const double* f0, const float* sp, const float* ap, const int* n_frames, int n_waves, int bins, int on_device,
+                      double* y, long long y_capacity, long long* sample_offsets) {
+    RY_TRY(check_handle(s, "synthesizer"));
+    // every refusal comes before anything is launched or written
+    if (!f0 || !sp || !ap || !n_frames || !y || !sample_offsets) return fail(RY_EINVAL, "null f0 / sp / ap / n_frames / y / sample_offsets");
+    if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
+    if (bins != SYNTH_BINS) return fail(RY_EINVAL, "%d bins per frame, fft_size / 2 + 1 = %d expected", bins, SYNTH_BINS);
+    std::vector<SynthSeg> segs((size_t)n_waves);
+    long long rows = 0, samples = 0, pulses = 0;
+    for (int b = 0; b < n_waves; ++b) {
+        if (n_frames[b] < 1) return fail(RY_EINVAL, "wave %d has %d frames: at least one", b, n_frames[b]);
+        if (n_frames[b] > SYNTH_MAX_FRAMES - rows) return fail(RY_EINVAL, "more than %d frames in one call", (int)SYNTH_MAX_FRAMES);
+        const long long len = y_length(s, n_frames[b]);
+        if (pulses + len + 1 > SYNTH_MAX_PULSES) return fail(RY_EINVAL, "more than %d samples in one call", (int)SYNTH_MAX_PULSES);
+        SynthSeg& g = segs[(size_t)b];
+        g.row0 = (int)rows; g.n_frames = n_frames[b]; g.pulse0 = (int)pulses; g.pulse_cap = (int)len + 1; g.sample0 = (int)samples; g.n_samples = (int)len;
+        rows += n_frames[b]; samples += len; pulses += len + 1;
+    }
+    for (int b = 0; b < n_waves; ++b) RY_TRY(check_f0(s, f0 + segs[(size_t)b].row0, n_frames[b], b));
+    if (samples > y_capacity) return fail(RY_EINVAL, "y holds %lld samples, the %d waves give %lld", y_capacity, n_waves, samples);
+    const ry_stream_t st = s->ctx->stream;
+    // drops a stream in progress, as ry_synth_run does, and leaves the stream reset: nothing below touches its state.  The zeroed state goes up
+    // in stream order, without ry_synth_reset's wait.
+    static const SynthScanState zero_state = {0.0, 0, 0, 0, 0};
+    reset_stream(s);
+    RT_TRY(rt::h2d(s->st, &zero_state, sizeof zero_state, st));
+    s->last_call.clear();
+    s->many_pulse0.clear();
+    // one upload: [rows] thresholded f0 | [n_waves] zeroed scan states | [n_waves] segments, in units of a double
+    const size_t st_off = (size_t)rows, seg_off = st_off + (size_t)n_waves * (sizeof(SynthScanState) / sizeof(double));
+    const size_t n_many = seg_off + ((size_t)n_waves * sizeof(SynthSeg) + sizeof(double) - 1) / sizeof(double);
+    static_assert(sizeof(SynthScanState) % sizeof(double) == 0, "the scan states sit between two arrays of doubles");
+    s->many_host.assign(n_many, 0.0);                              // the handle's own: the host array of the upload outlives the call
+    for (long long i = 0; i < rows; ++i) s->many_host[(size_t)i] = threshold_f0(s, f0[i]);
+    memcpy(s->many_host.data() + seg_off, segs.data(), segs.size() * sizeof(SynthSeg));
+    RY_TRY(s->d_many.grow(s->ctx, (long long)n_many));
+    RY_TRY(s->d_rstart.grow(s->ctx, n_waves + 1));
+    RY_TRY(grow_pulses(s, pulses));
+    RY_TRY(s->d_y.grow(s->ctx, samples));
+    if (!on_device) {
+        RY_TRY(s->d_sp_many.grow(s->ctx, rows * SYNTH_BINS));
+        RY_TRY(s->d_ap_many.grow(s->ctx, rows * SYNTH_BINS));
+        RT_TRY(rt::h2d(s->d_sp_many.ptr(), sp, (size_t)rows * SYNTH_BINS * sizeof(float), st));
+        RT_TRY(rt::h2d(s->d_ap_many.ptr(), ap, (size_t)rows * SYNTH_BINS * sizeof(float), st));
+        sp = s->d_sp_many.ptr(); ap = s->d_ap_many.ptr();
+    }
+    RT_TRY(rt::h2d(s->d_many.ptr(), s->many_host.data(), n_many * sizeof(double), st));
+    const double* d_f0 = s->d_many.ptr();
+    SynthScanState* d_st = (SynthScanState*)(s->d_many.ptr() + st_off);
+    const SynthSeg* d_seg = (const SynthSeg*)(s->d_many.ptr() + seg_off);
+    SynthScanParams cp = scan_params(s);
+    cp.f0 = d_f0; cp.st = d_st; cp.seg = d_seg;
+    RY_LAUNCH(synth_scan, dim3((unsigned)n_waves), 256, st, cp);
+    RT_TRY(rt::last_error());
+    std::vector<SynthScanState> hs((size_t)n_waves);
+    RT_TRY(rt::d2h(hs.data(), d_st, hs.size() * sizeof(SynthScanState), st));
+    RT_TRY(rt::stream_sync(st));                                   // wait 1 of 2: the pulse counts and overflow words (the host rows are free from here on)
+    s->rstart_host.assign((size_t)n_waves + 1, 0);
+    for (int b = 0; b < n_waves; ++b) {
+        if (hs[(size_t)b].overflow) return fail(RY_ESTATE, "wave %d: pulse list overflow (%d)", b, hs[(size_t)b].overflow);
+        s->rstart_host[(size_t)b + 1] = s->rstart_host[(size_t)b] + hs[(size_t)b].n_pulses;      // at most `pulses` in all: fits
+    }
+    const int total = s->rstart_host[(size_t)n_waves];
+    RT_TRY(rt::h2d(s->d_rstart.ptr(), s->rstart_host.data(), s->rstart_host.size() * sizeof(int), st));
+    if (total > 0) {
+        RY_TRY(s->d_resp.grow(s->ctx, (long long)total * SYNTH_FFT));
+        SynthPulseParams pp = pulse_params(s);
+        pp.sp = sp; pp.ap = ap; pp.seg = d_seg; pp.rstart = s->d_rstart.ptr(); pp.n_seg = n_waves;
+        RY_LAUNCH(synth_pulse, dim3((unsigned)total), 256, st, pp);
+        RT_TRY(rt::last_error());
+    }
+    SynthOverlapParams op = overlap_params(s);
+    op.s0 = 0; op.s1 = samples; op.seg = d_seg; op.rstart = s->d_rstart.ptr(); op.n_seg = n_waves;
+    RY_LAUNCH(synth_overlap, dim3((unsigned)((samples + 255) / 256)), 256, st, op);
+    RT_TRY(rt::last_error());
+    RT_TRY(rt::d2h(y, s->d_y.ptr(), (size_t)samples * sizeof(double), st));
+    RT_TRY(rt::stream_sync(st));                                   // wait 2 of 2
+    for (int b = 0; b < n_waves; ++b) sample_offsets[b] = segs[(size_t)b].sample0;
+    sample_offsets[n_waves] = samples;
+    s->many_pulse0.resize((size_t)n_waves);
+    for (int b = 0; b < n_waves; ++b) s->many_pulse0[(size_t)b] = segs[(size_t)b].pulse0;
+    return RY_OK;
+}
+
+int ry_synth_debug_pulses_many(ry_synth* s, int wave, long long* index, double* shift, int* voiced, int capacity, int* n) {
+    RY_TRY(check_handle(s, "synthesizer"));
+    if (!n) return fail(RY_EINVAL, "bad argument");
+    *n = 0;
+    if (s->many_pulse0.empty()) return fail(RY_ESTATE, "the last call was not ry_synth_run_many");
+    if (wave < 0 || wave >= (int)s->many_pulse0.size()) return fail(RY_EINVAL, "wave %d of %d", wave, (int)s->many_pulse0.size());
+    const int count = s->rstart_host[(size_t)wave + 1] - s->rstart_host[(size_t)wave], p0 = s->many_pulse0[(size_t)wave];
+    *n = count;
+    if (!index && !shift && !voiced) return RY_OK;                 // the count alone
+    if (capacity < count) return fail(RY_EINVAL, "%d pulses, room for %d", count, capacity);
+    const ry_stream_t st = s->ctx->stream;
+    if (index) RT_TRY(rt::d2h(index, s->d_pidx.ptr() + p0, (size_t)count * sizeof(long long), st));
+    if (shift) RT_TRY(rt::d2h(shift, s->d_pshift.ptr() + p0, (size_t)count * sizeof(double), st));
+    if (voiced) RT_TRY(rt::d2h(voiced, s->d_pvoiced.ptr() + p0, (size_t)count * sizeof(int), st));
+    RT_TRY(rt::stream_sync(st));
+    return RY_OK;
+}
+
 int ry_synth_debug_pulses(ry_synth* s, long long* index, double* shift, int* voiced, int capacity, int* n) {
     if (!s || !n) return fail(RY_EINVAL, "bad argument");
     *n = (int)s->last_call.size();
@@ -328,6 +480,7 @@ int ry_synth_debug_poison(ry_synth* s) {
     RY_TRY(check_handle(s, "synthesizer"));
     const ry_stream_t st = s->ctx->stream;
     RT_TRY(rt::stream_sync(st));
+    s->many_pulse0.clear();                                        // the pulse slices of a batched call are gone
     // every scratch buffer and the set of the frame window that is not in use: all bits set (NaN as a float or a double, -1 as an index)
     for (DevBufBase* b : s->scratch) RY_TRY(b->poison(st));
     const int idle = 1 - s->cur;

@@ -9,6 +9,11 @@
 //                   the LDS (float64, radix-4 Stockham, five passes, one butterfly per thread and pass) -> response row [1024] (float64).
 //   synth_overlap   overlap-add as a gather: one thread per output sample finds its pulses by binary search and sums their contributions in
 //                   ascending pulse order.  No atomics: run-to-run and cut-to-cut bit identity depend on it.
+// Many waves in one call (ry_synth_run_many): the same three kernels over a segment table (`seg`; null: one wave, the call's own sizes).  A
+// workgroup or thread finds its wave -- the scan by its block index, a pulse by bisection over the compact response starts, an output sample by
+// bisection over the sample starts, which rise strictly because every wave has at least one sample -- and from there on works with that wave's
+// own rows, pulse slice, state and sample positions: frame 0 is the wave's first row, sample 0 its first sample.  The arithmetic is the single
+// call's, on the same numbers.
 #pragma once
 #include "lds_fft.h"               // the 1024-point transform (synth_fft) and the counter-based noise (synth_noise)
 
@@ -26,6 +31,30 @@ struct SynthScanState {
     int pad;
 };
 
+// Wave b of a batched call.  Everything is counted in elements of the packed arrays: rows of f0 / sp / ap, entries of the pulse arrays (the
+// slice holds n_samples + 1: a sample gives at most one pulse), samples of the output.
+struct SynthSeg { int row0, n_frames, pulse0, pulse_cap, sample0, n_samples; };
+
+// the wave whose first sample is the last one at or before s
+RY_DEV int synth_seg_of_sample(const SynthSeg* seg, int n_seg, long long s) {
+    int lo = 0, hi = n_seg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (seg[mid].sample0 <= s) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// the wave of compact pulse j: the LAST b with rstart[b] <= j (a wave without pulses shares its start with the next one and is passed over)
+RY_DEV int synth_seg_of_pulse(const int* rstart, int n_seg, int j) {
+    int lo = 0, hi = n_seg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (rstart[mid] <= j) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
 struct SynthScanParams {
     const double* f0;             // thresholded f0 of frames frame0 .. (0 = unvoiced)
     long long frame0, last_frame; // positions at or behind last_frame take that frame
@@ -33,6 +62,8 @@ struct SynthScanParams {
     double spf, fs;               // samples per frame, sampling rate
     SynthScanState* st;
     long long* pidx; double* pshift; int* pvoiced; int cap;
+    const SynthSeg* seg;          // many waves: one workgroup each (grid = waves); f0, st and the pulse arrays are the packed ones, the wave's
+                                  // st[b] zeroed by the host; frame0, last_frame, n0, n1 and cap are not read
 };
 
 RY_KERNEL(256) void synth_scan(SynthScanParams p) {
@@ -44,6 +75,12 @@ RY_KERNEL(256) void synth_scan(SynthScanParams p) {
     __shared__ int cnt[256];
     __shared__ int base;
     const int tid = (int)threadIdx.x;
+    if (p.seg) {                                                   // this workgroup's wave: its own rows, state and pulse slice, samples [0, n_samples)
+        const SynthSeg sg = p.seg[blockIdx.x];
+        p.f0 += sg.row0; p.frame0 = 0; p.last_frame = sg.n_frames - 1; p.n0 = 0; p.n1 = sg.n_samples;
+        p.st += blockIdx.x;
+        p.pidx += sg.pulse0; p.pshift += sg.pulse0; p.pvoiced += sg.pulse0; p.cap = sg.pulse_cap;
+    }
     if (tid == 0) { base = p.st->n_pulses; wr[0] = p.st->phase; vo[0] = (unsigned char)p.st->last_voiced; }
     __syncthreads();
     for (long long b0 = p.n0; b0 < p.n1; b0 += SYNTH_BLOCK) {
@@ -116,6 +153,9 @@ struct SynthPulseParams {
     const sy_c* tw;               // [1024]
     const double* dc;             // [1024] raised-cosine DC remover, normalised
     double* resp;                 // [n_complete][1024]
+    // many waves: grid = the pulses of all waves; rstart [n_seg + 1] = the first response row of every wave (the running sum of the waves' pulse
+    // counts), the pulse arrays and sp / ap are the packed ones; n_pulses, n_complete, frame0 and last_frame are not read
+    const SynthSeg* seg; const int* rstart; int n_seg;
 };
 
 // minimum phase of the log-amplitude in lg[0 .. 512] -> spectrum on bins 0 .. 512 in `out` (uses a, b)
@@ -161,8 +201,17 @@ RY_KERNEL(256) void synth_pulse(SynthPulseParams p) {
     __shared__ double per[SYNTH_FFT];                 // periodic response (fftshifted, DC removed)
     __shared__ double red[256];
     const int tid = (int)threadIdx.x;
-    const int j = (int)blockIdx.x;
+    int j = (int)blockIdx.x;
     double* out = p.resp + (size_t)j * SYNTH_FFT;
+    if (p.seg) {                                                   // block-uniform: response row j is pulse j - rstart[b] of wave b, whose last pulse has no successor
+        const int b = synth_seg_of_pulse(p.rstart, p.n_seg, j);
+        const SynthSeg sg = p.seg[b];
+        p.n_pulses = p.rstart[b + 1] - p.rstart[b];
+        j -= p.rstart[b];
+        p.pidx += sg.pulse0; p.pshift += sg.pulse0; p.pvoiced += sg.pulse0;
+        p.sp += (size_t)sg.row0 * SYNTH_BINS; p.ap += (size_t)sg.row0 * SYNTH_BINS;
+        p.frame0 = 0; p.last_frame = sg.n_frames - 1;
+    }
     const long long idx = p.pidx[j];
     const long long ns_true = j + 1 < p.n_pulses ? p.pidx[j + 1] - idx : 0;
     if (ns_true <= 0) {                                            // block-uniform
@@ -252,11 +301,21 @@ RY_KERNEL(256) void synth_pulse(SynthPulseParams p) {
 }
 
 // y[s - s0] = sum over the pulses with index in [s - 512, s + 511], ascending, of resp[pulse][s - index + 511]
-struct SynthOverlapParams { const long long* pidx; int n_complete; const double* resp; long long s0, s1; double* y; };
+// many waves: s0 = 0, s1 = the samples of all waves, y the packed output; a sample of wave b sees that wave's pulses and response rows only
+struct SynthOverlapParams {
+    const long long* pidx; int n_complete; const double* resp; long long s0, s1; double* y;
+    const SynthSeg* seg; const int* rstart; int n_seg;
+};
 
 RY_KERNEL(256) void synth_overlap(SynthOverlapParams p) {
-    const long long s = p.s0 + (long long)blockIdx.x * 256 + threadIdx.x;
+    long long s = p.s0 + (long long)blockIdx.x * 256 + threadIdx.x;
     if (s >= p.s1) return;
+    if (p.seg) {
+        const int b = synth_seg_of_sample(p.seg, p.n_seg, s);
+        const SynthSeg sg = p.seg[b];
+        p.pidx += sg.pulse0; p.n_complete = p.rstart[b + 1] - p.rstart[b]; p.resp += (size_t)p.rstart[b] * SYNTH_FFT;
+        p.y += sg.sample0; s -= sg.sample0;                        // p.s0 = 0: y[s] below is the wave's own sample s
+    }
     int lo = 0, hi = p.n_complete;                                 // first pulse with index >= s - 512
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;

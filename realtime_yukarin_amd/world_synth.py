@@ -25,6 +25,9 @@ from ._handle import _DP, DeviceHandle, EngineForTests
 
 FFT_SIZE = 1024
 BINS = FFT_SIZE // 2 + 1
+# which path `Synthesizer.synthesize_many` took, counted per call: 'in_place' (device rows read where they are), 'packed' (host rows, one
+# upload) -- both ONE `ry_synth_run_many` --, 'fallback' (one `synthesize` per item)
+calls = {'in_place': 0, 'packed': 0, 'fallback': 0}
 
 
 def cheaptrick_fft_size(fs, f0_floor: float = 71.0) -> int:
@@ -103,6 +106,61 @@ class Synthesizer(DeviceHandle):
         got = ctypes.c_int()
         lib.check(lib.dll.ry_synth_run(h, f0.ctypes.data_as(_DP), psp, pap, n, bins, dev, y.ctypes.data_as(_DP), y.size, ctypes.byref(got)))
         return y[:got.value]
+
+    def synthesize_many(self, items) -> list:
+        """`items`: a list of `(f0, sp, ap)` -> the list of their waves, each with the bits of `synthesize` on it alone, in ONE device call
+        (`ry_synth_run_many`): host rows are packed and uploaded once, `DeviceRows` that are consecutive slices of one buffer -- a batched
+        stage-2 output -- are read where they are.  Lists that mix host and device rows, or whose device rows do not follow one another, are
+        synthesized item by item (`calls` says which path ran)."""
+        items = [self._item(*it) for it in items]
+        if not items:
+            return []
+        lib, h = self._get()
+        kinds = set(dev for _, _, _, dev in items)
+        row = BINS * 4
+        in_place = kinds == {True} and all(b[k].address == a[k].address + a[k].frames * row for a, b in zip(items, items[1:]) for k in (1, 2))
+        if not (in_place or kinds == {False}):
+            calls['fallback'] += 1
+            return [self.synthesize(f0, sp, ap) for f0, sp, ap, _ in items]
+        for f0, sp, ap, dev in items:
+            if not dev and (sp.shape[1] != BINS or ap.shape[1] != BINS):
+                raise ValueError('%d bins per frame, %d expected' % (sp.shape[1], BINS))
+        f0 = numpy.ascontiguousarray(numpy.concatenate([it[0] for it in items]))
+        n = numpy.array([it[0].size for it in items], numpy.int32)
+        if in_place:
+            keep = items
+            psp, pap = _lib._fptr(items[0][1].address), _lib._fptr(items[0][2].address)
+        else:
+            keep = (numpy.concatenate([it[1] for it in items]), numpy.concatenate([it[2] for it in items]))
+            psp, pap = _lib._fptr(keep[0]), _lib._fptr(keep[1])
+        off = numpy.zeros(len(items) + 1, numpy.int64)
+        y = numpy.empty(max(sum(self.length(int(k)) for k in n if k > 0), 1), numpy.float64)
+        lib.check(lib.dll.ry_synth_run_many(h, f0.ctypes.data_as(_DP), psp, pap, n.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(items), BINS,
+                                            int(in_place), y.ctypes.data_as(_DP), y.size, off.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        calls['in_place' if in_place else 'packed'] += 1
+        del keep
+        return [y[off[i]:off[i + 1]].copy() for i in range(len(items))]
+
+    def _item(self, f0, sp, ap):
+        """-> (f0 float64 [n], sp, ap, on_device); sp / ap float32 `[n][bins]` arrays, or both `DeviceRows`; one of each: as they came."""
+        f0 = numpy.ascontiguousarray(numpy.asarray(f0, dtype=numpy.float64).reshape(-1))
+        from . import fusion
+        if isinstance(sp, fusion.LazySpectrogram):
+            sp = device_spectrogram(sp)
+        dsp, dap = isinstance(sp, DeviceRows), isinstance(ap, DeviceRows)
+        if dsp != dap:
+            return f0, sp, ap, None
+        return f0, self._rows(sp, f0.size, 'sp')[2], self._rows(ap, f0.size, 'ap')[2], dsp
+
+    def pulses_many(self, wave: int):
+        """`pulses()` for wave `wave` of the last `synthesize_many` that ran as one call (`ry_synth_debug_pulses_many`)."""
+        lib, h = self._get()
+        n = ctypes.c_int()
+        lib.check(lib.dll.ry_synth_debug_pulses_many(h, int(wave), None, None, None, 0, ctypes.byref(n)))
+        idx, sh, vo = numpy.empty(n.value, numpy.int64), numpy.empty(n.value, numpy.float64), numpy.empty(n.value, numpy.int32)
+        lib.check(lib.dll.ry_synth_debug_pulses_many(h, int(wave), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), sh.ctypes.data_as(_DP),
+                                                     vo.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n.value, ctypes.byref(n)))
+        return idx, sh, vo != 0
 
     def push(self, f0, sp, ap) -> numpy.ndarray:
         lib, h = self._get()
@@ -203,6 +261,17 @@ def decode(self, acoustic_feature):
     f = acoustic_feature
     out = _synth_of(self).synthesize(numpy.asarray(f.f0).ravel(), f.sp, f.ap)
     return Wave(out, sampling_rate=self.out_sampling_rate)
+
+
+def decode_many(self, features):
+    """The list form of `decode`: the waves of a list of features in one device call (`Synthesizer.synthesize_many`), each equal to `decode` of
+    its feature bit for bit.  An empty list gives `[]`."""
+    from yukarin import Wave
+    features = list(features)
+    if not features:
+        return []
+    outs = _synth_of(self).synthesize_many([(numpy.asarray(f.f0).ravel(), f.sp, f.ap) for f in features])
+    return [Wave(o, sampling_rate=self.out_sampling_rate) for o in outs]
 
 
 def create_synthesizer(self, buffer_size: int, number_of_pointers: int):
