@@ -431,6 +431,40 @@ int ry_synth_debug_pulses_many(ry_synth* synth, int wave, long long* index, doub
  * did not write shows it in its output. */
 int ry_synth_debug_poison(ry_synth* synth);
 
+/* ---- A bank of WORLD synthesis streams: B independent streams at one rate and one frame period, each with a seed of its own, advanced by ONE
+ * device call per buffer (the realtime decode of a process that serves B sessions).  Contract, without a tolerance: for every stream b and every
+ * call, the samples returned for b and the pulses found for b equal, bit for bit, those of a lone ry_synth handle with seed seeds[b] that
+ * received the same frames in the same cuts through ry_synth_push / ry_synth_flush -- whatever the other streams do in the same call (their
+ * frame counts, sitting out, ending, restarting, their values and seeds).  All carried state -- phase, pulse lists, frame windows -- lives on
+ * the card; the cost of a push (two stream waits, five kernel launches, a fixed number of copies) does not depend on B.  Frames, y and the
+ * domain: as ry_synth_*.  INTEGRATION.md section 10, DESIGN.md section 12.2. */
+typedef struct ry_synth_bank ry_synth_bank;
+/* seeds [n_streams]; the domain and the refusals of ry_synth_create, and n_streams >= 1 */
+int ry_synth_bank_create(ry_ctx* ctx, int fs, double frame_period_ms, int fft_size, int n_streams, const unsigned* seeds, ry_synth_bank** out);
+void ry_synth_bank_destroy(ry_synth_bank* bank);
+/* samples a push may return for `stream` (n_frames about to be pushed; final = 1: its signal ends with them), as ry_synth_bound */
+int ry_synth_bank_bound(ry_synth_bank* bank, int stream, int n_frames, int final);
+/* One call for all streams.  n_frames [n_streams] >= 0: 0 = the stream sits the call out.  final (may be null) [n_streams]: 1 = the stream's
+ * signal ends with these frames -- everything left is returned and the slot is a new stream from the next call on (ry_synth_flush; with no
+ * frames a plain flush; RY_ESTATE on a stream without a frame).  f0 (HOST), sp and ap (host rows, or with on_device rows on the card, read where
+ * they are) hold the streams' new frames back to back in stream order.  y receives stream b's samples at y[sample_offsets[b]], sample_offsets
+ * has n_streams + 1 entries; y must hold the sum of ry_synth_bank_bound over the streams that take part.  Refused before anything is launched,
+ * uploaded or changed (y and sample_offsets untouched, the bank continues as if the call had not been made): null pointers, a negative count,
+ * no stream with a frame or final, bins != 513, f0 that ry_synth_push refuses (the message names stream and frame), y_capacity below the sum of
+ * the bounds, more than 2^22 frames or 2^30 pulse entries in all. */
+int ry_synth_bank_push(ry_synth_bank* bank, const double* f0, const float* sp, const float* ap, const int* n_frames, const int* final, int bins,
+                       int on_device, double* y, long long y_capacity, long long* sample_offsets);
+/* forgets the signal of `stream` (-1: of every stream) */
+int ry_synth_bank_reset(ry_synth_bank* bank, int stream);
+/* tests: the pulses the last push found for `stream` (as ry_synth_debug_pulses; read from the card here; RY_ESTATE after a poison) */
+int ry_synth_bank_debug_pulses(ry_synth_bank* bank, int stream, long long* index, double* shift, int* voiced, int capacity, int* n);
+/* tests: NaN bit patterns in every scratch buffer and in the unused parts of the window buffers; carried state is not touched */
+int ry_synth_bank_debug_poison(ry_synth_bank* bank);
+/* tests: out[4] = stream waits, kernel launches, host-to-device copies, device-to-host copies of the last push */
+int ry_synth_bank_debug_counts(ry_synth_bank* bank, int* out);
+/* tests: window rows kept for `stream` */
+int ry_synth_bank_debug_rows(ry_synth_bank* bank, int stream);
+
 /* ---- WORLD analysis that feeds the networks (`pyworld.cheaptrick(x, f0, t, fs)` and `pysptk.sp2mc(sp, order, alpha)` in the reference's
  * AcousticFeature.extract, reached from Vocoder.encode).  Semantics: INTEGRATION.md section 11 and tests/world_analysis_ref.py (CheapTrick
  * and sp2mc restated; WORLD's two randn() terms are counter-based functions of (seed, centre sample, index), so a frame's rows depend on

@@ -66,6 +66,8 @@ ABI_SYMBOLS = (
     'ry_crepe_track_many', 'ry_crepe_track_many_buffers', 'ry_crepe_decode_many', 'ry_crepe_voicing_many', 'ry_analysis_extract_many_dev',
     'ry_synth_create', 'ry_synth_destroy', 'ry_synth_length', 'ry_synth_run', 'ry_synth_bound', 'ry_synth_push', 'ry_synth_flush', 'ry_synth_reset',
     'ry_synth_debug_pulses', 'ry_synth_debug_poison', 'ry_synth_run_many', 'ry_synth_debug_pulses_many',
+    'ry_synth_bank_create', 'ry_synth_bank_destroy', 'ry_synth_bank_bound', 'ry_synth_bank_push', 'ry_synth_bank_reset',
+    'ry_synth_bank_debug_pulses', 'ry_synth_bank_debug_poison', 'ry_synth_bank_debug_counts', 'ry_synth_bank_debug_rows',
     'ry_analysis_create', 'ry_analysis_destroy', 'ry_analysis_run', 'ry_analysis_sp2mc', 'ry_analysis_debug_record', 'ry_analysis_debug_ints', 'ry_analysis_debug_poison',
     'ry_analysis_d4c', 'ry_analysis_extract', 'ry_analysis_d4c_bands', 'ry_analysis_debug_d4c', 'ry_analysis_extract_dev',
 )
@@ -213,6 +215,16 @@ class Ry355Lib(object):
         d.ry_synth_debug_poison.argtypes = [_VP]
         d.ry_synth_run_many.argtypes = [_VP, _DP, _FP, _FP, _IP, _CI, _CI, _CI, _DP, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
         d.ry_synth_debug_pulses_many.argtypes = [_VP, _CI, ctypes.POINTER(ctypes.c_longlong), _DP, _IP, _CI, _IP]
+        d.ry_synth_bank_create.argtypes = [_VP, _CI, ctypes.c_double, _CI, _CI, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(_VP)]
+        d.ry_synth_bank_destroy.argtypes = [_VP]
+        d.ry_synth_bank_destroy.restype = None
+        d.ry_synth_bank_bound.argtypes = [_VP, _CI, _CI, _CI]
+        d.ry_synth_bank_push.argtypes = [_VP, _DP, _FP, _FP, _IP, _IP, _CI, _CI, _DP, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
+        d.ry_synth_bank_reset.argtypes = [_VP, _CI]
+        d.ry_synth_bank_debug_pulses.argtypes = [_VP, _CI, ctypes.POINTER(ctypes.c_longlong), _DP, _IP, _CI, _IP]
+        d.ry_synth_bank_debug_poison.argtypes = [_VP]
+        d.ry_synth_bank_debug_counts.argtypes = [_VP, _IP]
+        d.ry_synth_bank_debug_rows.argtypes = [_VP, _CI]
         _LL = ctypes.c_longlong
         d.ry_analysis_create.argtypes = [_VP, _CI, _CI, _CI, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_uint, ctypes.POINTER(_VP)]
         d.ry_analysis_destroy.argtypes = [_VP]

@@ -6,6 +6,9 @@
 // straddle a push boundary are computed again from the same inputs (the same bits), so any cut of a stream equals the one-shot call.
 // ry_synth_run_many is the one-shot call for a list of waves: the same three kernels over a segment table (SynthSeg), one scan workgroup per
 // wave, the pulses and the samples of all waves in one launch each.  It keeps no stream state and brings no pulse list to the host.
+// ry_synth_bank is the stream for many sessions: B streams advanced by one call per buffer, the same three kernels over a stream table
+// (SynthStream), the pulse lists and the frame windows carried on the card (synth_gather, synth_retire).  The rules -- what can be scanned, what
+// can be emitted, which pulses leave, which frames are still needed -- are the functions `advance` uses.
 #include "synth_kernels.h"
 #include "ry_host.h"
 
@@ -45,6 +48,45 @@ struct ry_synth {
     std::vector<int> many_pulse0;
 };
 
+// One stream of a bank on the host: what ry_synth keeps for its one stream, except the pulse list, which stays on the card -- the host knows
+// its length and the indices of its first and last entry, which is all the rules ask for.
+struct BankStream {
+    unsigned seed_hash = 0;
+    long long n_frames = 0, frame0 = 0, scanned = 0, done = 0;
+    std::vector<double> f0;                  // thresholded f0 of the window's frames
+    int n_live = 0;
+    long long first_idx = -1, last_idx = 0;
+    long long row0 = 0;                      // first row of its window in the window buffer in use
+    long long dbg_p0 = 0; int dbg_n = 0;     // ry_synth_bank_debug_pulses: where the pulses the last push found are
+};
+
+enum { SYNTH_CARRY = 1040 };                 // entries of a stream's carry slot: live pulses lie in [done - 512, done + 511] plus the last one
+
+struct ry_synth_bank {
+    ry_ctx* ctx = nullptr;
+    ry_synth* core = nullptr;                // rate, frame period, tables, the call buffers of the three kernels and their parameter builders
+    int n_streams = 0;
+    std::vector<BankStream> s;
+    // carried on the card: scan state and carry slot of every stream, the frame windows of all streams back to back (two sets, as ry_synth's)
+    Arena carried;
+    SynthScanState* st = nullptr;
+    long long* c_idx = nullptr; double* c_shift = nullptr; int* c_voiced = nullptr;
+    Arena win[2];
+    float *sp[2] = {}, *ap[2] = {};
+    long long win_cap[2] = {0, 0}, win_rows = 0;
+    int cur = 0;
+    // scratch of a call: [rows] f0 | [streams] table in ONE buffer, what synth_retire reports
+    DevBufList scratch;
+    DevBuf<double> d_tab{scratch};
+    DevBuf<SynthRetired> d_ret{scratch};
+    std::vector<double> tab_host;
+    std::vector<SynthStream> ent;
+    std::vector<SynthScanState> hs;
+    std::vector<SynthRetired> ret;
+    bool pulses_valid = false;
+    int counts[4] = {0, 0, 0, 0};            // stream waits, kernel launches, host-to-device and device-to-host copies of the last push
+};
+
 namespace {
 void reset_stream(ry_synth* s) {
     s->n_frames = 0; s->frame0 = 0; s->f0.clear();
@@ -66,12 +108,12 @@ long long frame_of(const ry_synth* s, long long sample) { return sample <= 0 ? 0
 
 enum { SYNTH_MAX_FRAMES = 1 << 22, SYNTH_MAX_PULSES = 1 << 30 };      // frames of one call; entries of the pulse arrays of one call
 
-// wave >= 0: the frames are those of that wave of a batched call (the message names it)
-int check_f0(const ry_synth* s, const double* f0, int n_frames, int wave = -1) {
+// wave >= 0: the frames are those of that wave of a batched call, or of that stream of a bank (the message names it)
+int check_f0(const ry_synth* s, const double* f0, int n_frames, int wave = -1, const char* what = "wave") {
     for (int i = 0; i < n_frames; ++i)
         if (!std::isfinite(f0[i]) || !(f0[i] < 0.5 * s->fs))
             return wave < 0 ? fail(RY_EINVAL, "f0[%d] = %g: finite and below fs / 2", i, f0[i])
-                            : fail(RY_EINVAL, "wave %d: f0[%d] = %g: finite and below fs / 2", wave, i, f0[i]);
+                            : fail(RY_EINVAL, "%s %d: f0[%d] = %g: finite and below fs / 2", what, wave, i, f0[i]);
     return RY_OK;
 }
 
@@ -156,18 +198,41 @@ int append_frames(ry_synth* s, const double* f0, const float* sp, const float* a
     return RY_OK;
 }
 
-// the first frame a later call can still read: the frames of the oldest live pulse and of the next sample to scan
-long long first_needed_frame(const ry_synth* s) {
-    long long f = frame_of(s, s->scanned);
-    if (!s->live.empty()) f = std::min(f, frame_of(s, s->live.front().idx));
+// The rules of a stream, shared by the single stream (`advance`, whose pulse list is on the host) and the bank (whose lists are on the card).
+// the first frame a later call can still read: the frames of the oldest live pulse (has_live) and of the next sample to scan
+long long needed_frame(const ry_synth* s, long long scanned, bool has_live, long long first_idx) {
+    long long f = frame_of(s, scanned);
+    if (has_live) f = std::min(f, frame_of(s, first_idx));
     return std::max(0LL, f - 1);
+}
+
+long long first_needed_frame(const ry_synth* s) { return needed_frame(s, s->scanned, !s->live.empty(), s->live.empty() ? 0 : s->live.front().idx); }
+
+// the sample a call scans up to: with m frames pushed, the whole signal (final) or what both neighbouring frames are there for
+long long scan_end(const ry_synth* s, long long m, bool final, long long scanned) {
+    return std::max(final ? y_length(s, m) : known_samples(s, m), scanned);
+}
+
+// what can be emitted after a scan up to k1 that left `total` pulses, the last at last_idx: everything (final), or the samples the last pulse
+// -- the one without a successor -- cannot reach; `complete` pulses have a response
+void emit_range(bool final, long long total, long long last_idx, long long done, long long k1, long long* complete, long long* fin) {
+    *complete = final ? total : std::max(0LL, total - 1);
+    const long long f = final ? k1 : (total > 0 ? std::max(done, last_idx - SYNTH_HALF + 1) : done);
+    *fin = std::min(f, k1);
+}
+
+// samples a call with n more frames may return
+long long may_return(const ry_synth* s, long long pushed, long long scanned, long long done, long long n, bool final) {
+    const long long m = pushed + n;
+    if (m < 1) return 0;
+    return std::max(0LL, scan_end(s, m, final, scanned) - done);
 }
 
 // scans what can be scanned, emits what can be emitted.  final: the signal ends with the frames pushed so far.
 int advance(ry_synth* s, bool final, double* y, long long y_capacity, long long* n_out) {
     const ry_stream_t st = s->ctx->stream;
     const long long m = s->n_frames;
-    const long long k1 = std::max(final ? y_length(s, m) : known_samples(s, m), s->scanned);
+    const long long k1 = scan_end(s, m, final, s->scanned);
     if (final && y_length(s, m) < s->scanned) return fail(RY_ESTATE, "stream state: %lld samples scanned, the signal has %lld", s->scanned, y_length(s, m));
     if (k1 - s->done > y_capacity)
         return fail(RY_EINVAL, "y holds %lld samples, this call may return up to %lld", y_capacity, k1 - s->done);
@@ -218,9 +283,8 @@ int advance(ry_synth* s, bool final, double* y, long long y_capacity, long long*
         s->scanned = k1;
     }
     // what can be emitted: everything (final), or the samples the last pulse found -- the one without a successor -- cannot reach
-    const long long complete = final ? total : std::max(0LL, total - 1);
-    long long fin = final ? k1 : (total > 0 ? std::max(s->done, s->live.back().idx - SYNTH_HALF + 1) : s->done);
-    fin = std::min(fin, k1);
+    long long complete = 0, fin = 0;
+    emit_range(final, total, total > 0 ? s->live.back().idx : 0, s->done, k1, &complete, &fin);
     const long long n_emit = fin - s->done;
     if (n_emit > 0) {
         if (complete > 0) {
@@ -310,10 +374,7 @@ int ry_synth_length(ry_synth* s, int n_frames) {
 
 int ry_synth_bound(ry_synth* s, int n_frames, int final) {
     if (!s || n_frames < 0) return fail(RY_EINVAL, "bad argument");
-    const long long m = s->n_frames + n_frames;
-    if (m < 1) return 0;
-    const long long k = final ? y_length(s, m) : known_samples(s, m);
-    return (int)std::max(0LL, std::max(k, s->scanned) - s->done);
+    return (int)may_return(s, s->n_frames, s->scanned, s->done, n_frames, final != 0);
 }
 
 int ry_synth_push(ry_synth* s, const double* f0, const float* sp, const float* ap, int n_frames, int bins, int on_device,
@@ -384,7 +445,7 @@ int ry_synth_run_many(ry_synth* s, const double* f0, const float* sp, const floa
     const ry_stream_t st = s->ctx->stream;
     // drops a stream in progress, as ry_synth_run does, and leaves the stream reset: nothing below touches its state.  The zeroed state goes up
     // in stream order, without ry_synth_reset's wait.
-    static const SynthScanState zero_state = {0.0, 0, 0, 0, 0};
+    static const SynthScanState zero_state = {0.0, 0, 0, 0, 0, 0};
     reset_stream(s);
     RT_TRY(rt::h2d(s->st, &zero_state, sizeof zero_state, st));
     s->last_call.clear();
@@ -495,6 +556,273 @@ int ry_synth_debug_poison(ry_synth* s) {
     }
     RT_TRY(rt::stream_sync(st));
     return RY_OK;
+}
+
+// ---- the bank of streams ---------------------------------------------------------------------------------------------------------------------
+static void bank_reset_stream(BankStream& t) {
+    t.n_frames = 0; t.frame0 = 0; t.scanned = 0; t.done = 0; t.f0.clear();
+    t.n_live = 0; t.first_idx = -1; t.last_idx = 0;
+}
+
+int ry_synth_bank_create(ry_ctx* ctx, int fs, double frame_period_ms, int fft_size, int n_streams, const unsigned* seeds, ry_synth_bank** out) {
+    if (!out) return fail(RY_EINVAL, "null out pointer");
+    *out = nullptr;
+    if (!seeds) return fail(RY_EINVAL, "null seeds");
+    if (n_streams < 1 || n_streams > (1 << 16)) return fail(RY_EINVAL, "%d streams: 1 .. 65536", n_streams);
+    ry_synth* core = nullptr;
+    RY_TRY(ry_synth_create(ctx, fs, frame_period_ms, fft_size, seeds[0], &core));       // the domain and the refusals of a single stream
+    std::unique_ptr<ry_synth_bank> k(new ry_synth_bank());
+    k->ctx = ctx; k->core = core; k->n_streams = n_streams;
+    k->s.resize((size_t)n_streams);
+    for (int b = 0; b < n_streams; ++b) k->s[(size_t)b].seed_hash = synth_hash32(seeds[b]);
+    const std::vector<SynthScanState> z((size_t)n_streams, SynthScanState{0.0, 0, 0, 0, 0, 0});
+    const size_t slots = (size_t)n_streams * SYNTH_CARRY;
+    int rc = upload_table(k->carried, ctx, z.data(), z.size(), &k->st);
+    if (rc == RY_OK) rc = k->carried.alloc((float**)&k->c_idx, slots * 2);
+    if (rc == RY_OK) rc = k->carried.alloc((float**)&k->c_shift, slots * 2);
+    if (rc == RY_OK) rc = k->carried.alloc((float**)&k->c_voiced, slots);
+    if (rc != RY_OK) { ry_synth_destroy(core); return rc; }
+    *out = k.release();
+    return RY_OK;
+}
+
+void ry_synth_bank_destroy(ry_synth_bank* k) {
+    if (!k) return;
+    rt::set_device(k->ctx->device);
+    rt::stream_sync(k->ctx->stream);
+    ry_synth_destroy(k->core);
+    delete k;
+}
+
+int ry_synth_bank_bound(ry_synth_bank* k, int stream, int n_frames, int final) {
+    if (!k || stream < 0 || stream >= k->n_streams || n_frames < 0) return fail(RY_EINVAL, "bad argument");
+    const BankStream& t = k->s[(size_t)stream];
+    return (int)may_return(k->core, t.n_frames, t.scanned, t.done, n_frames, final != 0);
+}
+
+int ry_synth_bank_reset(ry_synth_bank* k, int stream) {
+    RY_TRY(check_handle(k, "synthesizer bank"));
+    if (stream < -1 || stream >= k->n_streams) return fail(RY_EINVAL, "stream %d of %d", stream, k->n_streams);
+    const int b0 = stream < 0 ? 0 : stream, b1 = stream < 0 ? k->n_streams : stream + 1;
+    const std::vector<SynthScanState> z((size_t)(b1 - b0), SynthScanState{0.0, 0, 0, 0, 0, 0});
+    for (int b = b0; b < b1; ++b) bank_reset_stream(k->s[(size_t)b]);
+    RT_TRY(rt::h2d(k->st + b0, z.data(), z.size() * sizeof(SynthScanState), k->ctx->stream));
+    RT_TRY(rt::stream_sync(k->ctx->stream));
+    return RY_OK;
+}
+
+int ry_synth_bank_push(ry_synth_bank* k, const double* f0, const float* sp, const float* ap, const int* n_frames, const int* final, int bins,
+                       int on_device, double* y, long long y_capacity, long long* sample_offsets) {
+    RY_TRY(check_handle(k, "synthesizer bank"));
+    // every refusal comes before anything is launched, uploaded or changed in any stream's state
+    if (!f0 || !sp || !ap || !n_frames || !y || !sample_offsets) return fail(RY_EINVAL, "null f0 / sp / ap / n_frames / y / sample_offsets");
+    if (bins != SYNTH_BINS) return fail(RY_EINVAL, "%d bins per frame, fft_size / 2 + 1 = %d expected", bins, SYNTH_BINS);
+    ry_synth* const c = k->core;
+    const int B = k->n_streams;
+    std::vector<SynthStream>& ent = k->ent;
+    ent.assign((size_t)B, SynthStream());
+    std::vector<long long> keep_from((size_t)B), k1s((size_t)B);
+    long long rows = 0, new_rows = 0, pulses = 0, bound = 0;
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+        const BankStream& t = k->s[(size_t)b];
+        SynthStream& e = ent[(size_t)b];
+        memset(&e, 0, sizeof e);
+        const int n = n_frames[b];
+        const bool fin = final && final[b];
+        if (n < 0) return fail(RY_EINVAL, "stream %d has %d frames", b, n);
+        if (n > SYNTH_MAX_FRAMES - new_rows) return fail(RY_EINVAL, "more than %d frames in one call", (int)SYNTH_MAX_FRAMES);
+        const long long m = t.n_frames + n;
+        if (fin && m < 1) return fail(RY_ESTATE, "stream %d: final on an empty stream", b);
+        if (fin && y_length(c, m) < t.scanned) return fail(RY_ESTATE, "stream %d: %lld samples scanned, the signal has %lld", b, t.scanned, y_length(c, m));
+        e.active = n > 0 || fin; e.final = fin;
+        any = any || e.active;
+        const long long kf = std::max(needed_frame(c, t.scanned, t.n_live > 0, t.first_idx), t.frame0);
+        const long long kept = t.frame0 + (long long)t.f0.size() - kf;
+        const long long k1 = e.active ? scan_end(c, m, fin, t.scanned) : t.scanned;
+        const long long cap = e.active ? t.n_live + (k1 - t.scanned) + 1 : 0;
+        if (pulses + cap > SYNTH_MAX_PULSES) return fail(RY_EINVAL, "more than %d samples in one call", (int)SYNTH_MAX_PULSES);
+        keep_from[(size_t)b] = kf; k1s[(size_t)b] = k1;
+        e.frame0 = kf; e.last_frame = m - 1; e.n0 = t.scanned; e.n1 = k1;
+        e.row0 = (int)rows; e.rows = (int)(kept + n); e.kept = (int)kept; e.src_row0 = (int)(t.row0 + (kf - t.frame0)); e.new_row0 = (int)new_rows;
+        e.pulse0 = (int)pulses; e.pulse_cap = (int)cap; e.n_live = t.n_live; e.seed_hash = t.seed_hash;
+        e.done = e.fin = t.done;
+        rows += kept + n; new_rows += n; pulses += cap;
+        if (rows > 2LL * SYNTH_MAX_FRAMES) return fail(RY_EINVAL, "more than %d window rows in one call", 2 * (int)SYNTH_MAX_FRAMES);
+        if (e.active) bound += k1 - t.done;
+    }
+    if (!any) return fail(RY_EINVAL, "no stream has a frame or ends");
+    for (int b = 0; b < B; ++b) RY_TRY(check_f0(c, f0 + ent[(size_t)b].new_row0, n_frames[b], b, "stream"));
+    if (bound > y_capacity) return fail(RY_EINVAL, "y holds %lld samples, this push may return up to %lld (ry_synth_bank_bound)", y_capacity, bound);
+
+    const ry_stream_t st = k->ctx->stream;
+    int* const cnt = k->counts;
+    cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0;
+    // room first: a buffer that grows waits for the stream, and a failure here leaves every stream as it was
+    const int to = 1 - k->cur;
+    if (rows > k->win_cap[to]) {
+        RT_TRY(rt::stream_sync(st)); ++cnt[0];
+        k->win[to].release();
+        k->sp[to] = k->ap[to] = nullptr; k->win_cap[to] = 0;
+        const long long cap = rows + rows / 2 + 16;
+        RY_TRY(k->win[to].alloc(&k->sp[to], (size_t)cap * SYNTH_BINS));
+        RY_TRY(k->win[to].alloc(&k->ap[to], (size_t)cap * SYNTH_BINS));
+        k->win_cap[to] = cap;
+    }
+    static_assert(sizeof(SynthStream) % sizeof(double) == 0, "the stream table follows an array of doubles");
+    const size_t ent_off = (size_t)rows, n_tab = ent_off + (size_t)B * (sizeof(SynthStream) / sizeof(double));
+    auto grow = [&](DevBufBase& buf, long long need) { if (need > buf.cap) ++cnt[0]; return buf.grow(k->ctx, need); };
+    RY_TRY(grow(c->d_pidx, pulses));
+    RY_TRY(grow(c->d_pshift, pulses));
+    RY_TRY(grow(c->d_pvoiced, pulses));
+    RY_TRY(grow(k->d_tab, (long long)n_tab));
+    RY_TRY(grow(k->d_ret, B));
+    if (!on_device && new_rows > 0) {
+        RY_TRY(grow(c->d_sp_many, new_rows * SYNTH_BINS));
+        RY_TRY(grow(c->d_ap_many, new_rows * SYNTH_BINS));
+    }
+    // the windows' f0 on the host, then ONE upload: [rows] thresholded f0 | [streams] table
+    k->pulses_valid = false;
+    k->tab_host.assign(n_tab, 0.0);
+    for (int b = 0; b < B; ++b) {
+        BankStream& t = k->s[(size_t)b];
+        const SynthStream& e = ent[(size_t)b];
+        t.f0.erase(t.f0.begin(), t.f0.begin() + (keep_from[(size_t)b] - t.frame0));
+        for (int i = 0; i < n_frames[b]; ++i) t.f0.push_back(threshold_f0(c, f0[e.new_row0 + i]));
+        t.frame0 = keep_from[(size_t)b]; t.row0 = e.row0; t.n_frames += n_frames[b];
+        if (!t.f0.empty()) memcpy(k->tab_host.data() + e.row0, t.f0.data(), t.f0.size() * sizeof(double));
+        t.dbg_n = 0;
+    }
+    memcpy(k->tab_host.data() + ent_off, ent.data(), (size_t)B * sizeof(SynthStream));
+    RT_TRY(rt::h2d(k->d_tab.ptr(), k->tab_host.data(), n_tab * sizeof(double), st)); ++cnt[2];
+    const float *new_sp = sp, *new_ap = ap;
+    if (!on_device && new_rows > 0) {
+        RT_TRY(rt::h2d(c->d_sp_many.ptr(), sp, (size_t)new_rows * SYNTH_BINS * sizeof(float), st)); ++cnt[2];
+        RT_TRY(rt::h2d(c->d_ap_many.ptr(), ap, (size_t)new_rows * SYNTH_BINS * sizeof(float), st)); ++cnt[2];
+        new_sp = c->d_sp_many.ptr(); new_ap = c->d_ap_many.ptr();
+    }
+    const double* d_f0 = k->d_tab.ptr();
+    const SynthStream* d_ent = (const SynthStream*)(k->d_tab.ptr() + ent_off);
+    SynthGatherParams gp;
+    memset(&gp, 0, sizeof gp);
+    gp.bank = d_ent; gp.n_streams = B; gp.rows = (int)rows;
+    gp.old_sp = k->sp[k->cur]; gp.old_ap = k->ap[k->cur]; gp.new_sp = new_sp; gp.new_ap = new_ap; gp.sp = k->sp[to]; gp.ap = k->ap[to];
+    gp.c_idx = k->c_idx; gp.c_shift = k->c_shift; gp.c_voiced = k->c_voiced; gp.carry_cap = SYNTH_CARRY;
+    gp.pidx = c->d_pidx.ptr(); gp.pshift = c->d_pshift.ptr(); gp.pvoiced = c->d_pvoiced.ptr();
+    RY_LAUNCH(synth_gather, dim3((unsigned)std::max(rows, (long long)B), 3), 256, st, gp); ++cnt[1];
+    RT_TRY(rt::last_error());
+    k->cur = to; k->win_rows = rows;
+    SynthScanParams cp = scan_params(c);
+    cp.f0 = d_f0; cp.st = k->st; cp.bank = d_ent;
+    RY_LAUNCH(synth_scan, dim3((unsigned)B), 256, st, cp); ++cnt[1];
+    RT_TRY(rt::last_error());
+    k->hs.resize((size_t)B);
+    RT_TRY(rt::d2h(k->hs.data(), k->st, (size_t)B * sizeof(SynthScanState), st)); ++cnt[3];
+    RT_TRY(rt::stream_sync(st)); ++cnt[0];                          // wait 1 of 2: pulse counts, overflow words, last indices (the host rows are free from here on)
+    long long resp = 0, samples = 0;
+    for (int b = 0; b < B; ++b) {
+        BankStream& t = k->s[(size_t)b];
+        SynthStream& e = ent[(size_t)b];
+        e.out0 = samples; e.resp0 = (int)resp;
+        if (!e.active) continue;
+        const SynthScanState& h = k->hs[(size_t)b];
+        if (h.overflow) return fail(RY_ESTATE, "stream %d: pulse list overflow (%d)", b, h.overflow);
+        long long complete = 0, fin = 0;
+        emit_range(e.final != 0, h.n_pulses, h.last_idx, t.done, k1s[(size_t)b], &complete, &fin);
+        e.n_pulses = h.n_pulses; e.fin = fin;
+        e.n_complete = fin - t.done > 0 ? (int)complete : 0;       // as `advance`: no sample, no response
+        resp += e.n_complete; samples += fin - t.done;
+        t.dbg_p0 = e.pulse0 + e.n_live; t.dbg_n = h.n_pulses - e.n_live;
+    }
+    memcpy(k->tab_host.data() + ent_off, ent.data(), (size_t)B * sizeof(SynthStream));
+    RY_TRY(grow(c->d_resp, resp * SYNTH_FFT));
+    RY_TRY(grow(c->d_y, samples));
+    RT_TRY(rt::h2d(k->d_tab.ptr() + ent_off, k->tab_host.data() + ent_off, (size_t)B * sizeof(SynthStream), st)); ++cnt[2];
+    if (resp > 0) {
+        SynthPulseParams pp = pulse_params(c);
+        pp.sp = k->sp[to]; pp.ap = k->ap[to]; pp.bank = d_ent; pp.n_streams = B;
+        RY_LAUNCH(synth_pulse, dim3((unsigned)resp), 256, st, pp); ++cnt[1];
+        RT_TRY(rt::last_error());
+    }
+    if (samples > 0) {
+        SynthOverlapParams op = overlap_params(c);
+        op.s0 = 0; op.s1 = samples; op.bank = d_ent; op.n_streams = B;
+        RY_LAUNCH(synth_overlap, dim3((unsigned)((samples + 255) / 256)), 256, st, op); ++cnt[1];
+        RT_TRY(rt::last_error());
+    }
+    SynthRetireParams rp;
+    memset(&rp, 0, sizeof rp);
+    rp.bank = d_ent; rp.st = k->st; rp.pidx = c->d_pidx.ptr(); rp.pshift = c->d_pshift.ptr(); rp.pvoiced = c->d_pvoiced.ptr();
+    rp.c_idx = k->c_idx; rp.c_shift = k->c_shift; rp.c_voiced = k->c_voiced; rp.carry_cap = SYNTH_CARRY; rp.out = k->d_ret.ptr();
+    RY_LAUNCH(synth_retire, dim3((unsigned)B), 256, st, rp); ++cnt[1];
+    RT_TRY(rt::last_error());
+    if (samples > 0) { RT_TRY(rt::d2h(y, c->d_y.ptr(), (size_t)samples * sizeof(double), st)); ++cnt[3]; }
+    k->ret.resize((size_t)B);
+    RT_TRY(rt::d2h(k->ret.data(), k->d_ret.ptr(), (size_t)B * sizeof(SynthRetired), st)); ++cnt[3];
+    RT_TRY(rt::stream_sync(st)); ++cnt[0];                          // wait 2 of 2: the samples and what synth_retire carried
+    for (int b = 0; b < B; ++b) {
+        BankStream& t = k->s[(size_t)b];
+        const SynthStream& e = ent[(size_t)b];
+        sample_offsets[b] = e.out0;
+        if (!e.active) continue;
+        if (k->ret[(size_t)b].overflow) return fail(RY_ESTATE, "stream %d: %d live pulses beyond the carry slot", b, k->ret[(size_t)b].overflow);
+        if (e.final) { bank_reset_stream(t); continue; }
+        t.scanned = e.n1; t.done = e.fin;
+        t.n_live = k->ret[(size_t)b].n_live; t.first_idx = k->ret[(size_t)b].first_idx; t.last_idx = k->hs[(size_t)b].last_idx;
+    }
+    sample_offsets[B] = samples;
+    k->pulses_valid = true;
+    return RY_OK;
+}
+
+int ry_synth_bank_debug_pulses(ry_synth_bank* k, int stream, long long* index, double* shift, int* voiced, int capacity, int* n) {
+    RY_TRY(check_handle(k, "synthesizer bank"));
+    if (!n) return fail(RY_EINVAL, "bad argument");
+    *n = 0;
+    if (stream < 0 || stream >= k->n_streams) return fail(RY_EINVAL, "stream %d of %d", stream, k->n_streams);
+    if (!k->pulses_valid) return fail(RY_ESTATE, "no push since the bank was made or poisoned");
+    const BankStream& t = k->s[(size_t)stream];
+    *n = t.dbg_n;
+    if (!index && !shift && !voiced) return RY_OK;                 // the count alone
+    if (capacity < t.dbg_n) return fail(RY_EINVAL, "%d pulses, room for %d", t.dbg_n, capacity);
+    const ry_stream_t st = k->ctx->stream;
+    const ry_synth* c = k->core;
+    if (index) RT_TRY(rt::d2h(index, c->d_pidx.ptr() + t.dbg_p0, (size_t)t.dbg_n * sizeof(long long), st));
+    if (shift) RT_TRY(rt::d2h(shift, c->d_pshift.ptr() + t.dbg_p0, (size_t)t.dbg_n * sizeof(double), st));
+    if (voiced) RT_TRY(rt::d2h(voiced, c->d_pvoiced.ptr() + t.dbg_p0, (size_t)t.dbg_n * sizeof(int), st));
+    RT_TRY(rt::stream_sync(st));
+    return RY_OK;
+}
+
+int ry_synth_bank_debug_poison(ry_synth_bank* k) {
+    RY_TRY(check_handle(k, "synthesizer bank"));
+    const ry_stream_t st = k->ctx->stream;
+    k->pulses_valid = false;                                       // the pulse arrays are scratch: what the streams carry is in the carry slots
+    RY_TRY(ry_synth_debug_poison(k->core));
+    for (DevBufBase* b : k->scratch) RY_TRY(b->poison(st));
+    const int idle = 1 - k->cur;
+    if (k->sp[idle]) {
+        RT_TRY(rt::dmemset(k->sp[idle], 0xff, (size_t)k->win_cap[idle] * SYNTH_BINS * sizeof(float), st));
+        RT_TRY(rt::dmemset(k->ap[idle], 0xff, (size_t)k->win_cap[idle] * SYNTH_BINS * sizeof(float), st));
+    }
+    if (k->sp[k->cur]) {                                           // behind the windows of the set in use
+        const size_t used = (size_t)k->win_rows * SYNTH_BINS, cap = (size_t)k->win_cap[k->cur] * SYNTH_BINS;
+        RT_TRY(rt::dmemset(k->sp[k->cur] + used, 0xff, (cap - used) * sizeof(float), st));
+        RT_TRY(rt::dmemset(k->ap[k->cur] + used, 0xff, (cap - used) * sizeof(float), st));
+    }
+    RT_TRY(rt::stream_sync(st));
+    return RY_OK;
+}
+
+int ry_synth_bank_debug_counts(ry_synth_bank* k, int* out) {
+    if (!k || !out) return fail(RY_EINVAL, "bad argument");
+    for (int i = 0; i < 4; ++i) out[i] = k->counts[i];
+    return RY_OK;
+}
+
+int ry_synth_bank_debug_rows(ry_synth_bank* k, int stream) {
+    if (!k || stream < 0 || stream >= k->n_streams) return fail(RY_EINVAL, "bad argument");
+    return (int)k->s[(size_t)stream].f0.size();
 }
 
 }  // extern "C"

@@ -14,6 +14,12 @@
 // bisection over the sample starts, which rise strictly because every wave has at least one sample -- and from there on works with that wave's
 // own rows, pulse slice, state and sample positions: frame 0 is the wave's first row, sample 0 its first sample.  The arithmetic is the single
 // call's, on the same numbers.
+// Many streams in one call (ry_synth_bank_push): the same three kernels over a stream table (`bank`; null: the paths above).  Stream b is workgroup b
+// of the scan; a pulse finds its stream by bisection over the first response rows, an output sample by bisection over the first output samples.
+// An entry carries what `advance` passes per call -- window rows, frame0 / last_frame, the sample range to scan, the pulse slice, the emit range,
+// the seed hash -- with positions counted from the start of the STREAM's signal, which is what the noise is keyed by.  Two kernels do what the
+// host does for a single stream: synth_gather builds every stream's [kept rows | new rows] window in the other window buffer and puts its carried
+// pulses at the front of its slice, synth_retire drops the pulses that can reach no unemitted sample and carries the survivors to the next call.
 #pragma once
 #include "lds_fft.h"               // the 1024-point transform (synth_fft) and the counter-based noise (synth_noise)
 
@@ -29,7 +35,41 @@ struct SynthScanState {
     int n_pulses;                 // entries of the pulse arrays (old ones the host put there + the ones this launch appended)
     int overflow;                 // pulses that did not fit (the host sizes the arrays by the sample count: stays 0)
     int pad;
+    long long last_idx;           // index of entry n_pulses - 1 (n_pulses > 0): what the host of a bank sizes the emit range by
 };
+
+// Stream b of a bank call.  Positions (n0, n1, done, fin, pulse indices) count samples from the start of the stream's signal, frames likewise;
+// rows, pulse entries, response rows and output samples count elements of the call's packed arrays.  The host fills the first two groups
+// before the scan and the third after it, from the scan state.
+struct SynthStream {
+    long long frame0, last_frame; // absolute frame of the first row of its window, last frame pushed
+    long long n0, n1;             // samples [scanned, k1) to scan
+    int row0, rows;               // its window in the call's f0 / sp / ap rows
+    int kept, src_row0, new_row0; // gather: rows [0, kept) come from row src_row0 .. of the old window buffer, the rest from row new_row0 .. of the new rows
+    int pulse0, pulse_cap;        // its slice of the pulse arrays
+    int n_live;                   // carried pulses the gather puts at the front of the slice (= st[b].n_pulses)
+    unsigned seed_hash;
+    int active, final;            // takes part in this call (frames or final); its signal ends with this call
+    int n_pulses, n_complete;     // entries after the scan; pulses whose response is computed
+    int resp0;                    // first response row
+    long long done, fin;          // emits samples [done, fin)
+    long long out0;               // ... to y[out0 ..]
+};
+
+// what synth_retire leaves for the host: the carried pulses and the index of the first one (the oldest frame a later call reads)
+struct SynthRetired { long long first_idx; int n_live; int overflow; };
+
+// the stream of element j of a packed array whose stream b starts at start(b): the LAST b with start <= j (a stream without elements shares its
+// start with the next one and is passed over)
+#define SYNTH_STREAM_OF(bank, n, j, field, out)                    \
+    do {                                                           \
+        int lo__ = 0, hi__ = (n) - 1;                              \
+        while (lo__ < hi__) {                                      \
+            const int mid__ = (lo__ + hi__ + 1) >> 1;              \
+            if ((bank)[mid__].field <= (j)) lo__ = mid__; else hi__ = mid__ - 1; \
+        }                                                          \
+        (out) = lo__;                                              \
+    } while (0)
 
 // Wave b of a batched call.  Everything is counted in elements of the packed arrays: rows of f0 / sp / ap, entries of the pulse arrays (the
 // slice holds n_samples + 1: a sample gives at most one pulse), samples of the output.
@@ -64,6 +104,8 @@ struct SynthScanParams {
     long long* pidx; double* pshift; int* pvoiced; int cap;
     const SynthSeg* seg;          // many waves: one workgroup each (grid = waves); f0, st and the pulse arrays are the packed ones, the wave's
                                   // st[b] zeroed by the host; frame0, last_frame, n0, n1 and cap are not read
+    const SynthStream* bank;      // many streams: one workgroup each (grid = streams); f0 and the pulse arrays are the call's packed ones, st[b] the
+                                  // stream's carried state; frame0, last_frame, n0, n1 and cap are not read
 };
 
 RY_KERNEL(256) void synth_scan(SynthScanParams p) {
@@ -80,6 +122,13 @@ RY_KERNEL(256) void synth_scan(SynthScanParams p) {
         p.f0 += sg.row0; p.frame0 = 0; p.last_frame = sg.n_frames - 1; p.n0 = 0; p.n1 = sg.n_samples;
         p.st += blockIdx.x;
         p.pidx += sg.pulse0; p.pshift += sg.pulse0; p.pvoiced += sg.pulse0; p.cap = sg.pulse_cap;
+    }
+    if (p.bank) {                                                  // this workgroup's stream: its window, carried state and pulse slice, samples [n0, n1) of its signal
+        const SynthStream e = p.bank[blockIdx.x];
+        if (!e.active) return;                                     // block-uniform: a stream that sits the call out keeps its state as it is
+        p.f0 += e.row0; p.frame0 = e.frame0; p.last_frame = e.last_frame; p.n0 = e.n0; p.n1 = e.n1;
+        p.st += blockIdx.x;
+        p.pidx += e.pulse0; p.pshift += e.pulse0; p.pvoiced += e.pulse0; p.cap = e.pulse_cap;
     }
     if (tid == 0) { base = p.st->n_pulses; wr[0] = p.st->phase; vo[0] = (unsigned char)p.st->last_voiced; }
     __syncthreads();
@@ -137,7 +186,9 @@ RY_KERNEL(256) void synth_scan(SynthScanParams p) {
         p.st->phase = wr[0];
         p.st->last_voiced = vo[0];
         p.st->overflow = base > p.cap ? base - p.cap : 0;
-        p.st->n_pulses = base > p.cap ? p.cap : base;
+        const int n = base > p.cap ? p.cap : base;
+        p.st->n_pulses = n;
+        if (n > 0) p.st->last_idx = p.pidx[n - 1];                 // written by this workgroup before the loop's last barrier, or carried
     }
 }
 
@@ -156,6 +207,9 @@ struct SynthPulseParams {
     // many waves: grid = the pulses of all waves; rstart [n_seg + 1] = the first response row of every wave (the running sum of the waves' pulse
     // counts), the pulse arrays and sp / ap are the packed ones; n_pulses, n_complete, frame0 and last_frame are not read
     const SynthSeg* seg; const int* rstart; int n_seg;
+    // many streams: grid = the response rows of all streams; the pulse arrays and sp / ap are the call's packed ones; n_pulses, n_complete, frame0,
+    // last_frame and seed_hash are not read
+    const SynthStream* bank; int n_streams;
 };
 
 // minimum phase of the log-amplitude in lg[0 .. 512] -> spectrum on bins 0 .. 512 in `out` (uses a, b)
@@ -211,6 +265,16 @@ RY_KERNEL(256) void synth_pulse(SynthPulseParams p) {
         p.pidx += sg.pulse0; p.pshift += sg.pulse0; p.pvoiced += sg.pulse0;
         p.sp += (size_t)sg.row0 * SYNTH_BINS; p.ap += (size_t)sg.row0 * SYNTH_BINS;
         p.frame0 = 0; p.last_frame = sg.n_frames - 1;
+    }
+    if (p.bank) {                                                  // block-uniform: response row j is pulse j - resp0 of stream b
+        int b;
+        SYNTH_STREAM_OF(p.bank, p.n_streams, j, resp0, b);
+        const SynthStream e = p.bank[b];
+        p.n_pulses = e.n_pulses;
+        j -= e.resp0;
+        p.pidx += e.pulse0; p.pshift += e.pulse0; p.pvoiced += e.pulse0;
+        p.sp += (size_t)e.row0 * SYNTH_BINS; p.ap += (size_t)e.row0 * SYNTH_BINS;
+        p.frame0 = e.frame0; p.last_frame = e.last_frame; p.seed_hash = e.seed_hash;
     }
     const long long idx = p.pidx[j];
     const long long ns_true = j + 1 < p.n_pulses ? p.pidx[j + 1] - idx : 0;
@@ -305,6 +369,7 @@ RY_KERNEL(256) void synth_pulse(SynthPulseParams p) {
 struct SynthOverlapParams {
     const long long* pidx; int n_complete; const double* resp; long long s0, s1; double* y;
     const SynthSeg* seg; const int* rstart; int n_seg;
+    const SynthStream* bank; int n_streams;      // many streams: s0 = 0, s1 = the samples the call emits; sample out0 + i of y is sample done + i of stream b
 };
 
 RY_KERNEL(256) void synth_overlap(SynthOverlapParams p) {
@@ -315,6 +380,13 @@ RY_KERNEL(256) void synth_overlap(SynthOverlapParams p) {
         const SynthSeg sg = p.seg[b];
         p.pidx += sg.pulse0; p.n_complete = p.rstart[b + 1] - p.rstart[b]; p.resp += (size_t)p.rstart[b] * SYNTH_FFT;
         p.y += sg.sample0; s -= sg.sample0;                        // p.s0 = 0: y[s] below is the wave's own sample s
+    }
+    if (p.bank) {
+        int b;
+        SYNTH_STREAM_OF(p.bank, p.n_streams, s, out0, b);
+        const SynthStream e = p.bank[b];
+        p.pidx += e.pulse0; p.n_complete = e.n_complete; p.resp += (size_t)e.resp0 * SYNTH_FFT;
+        p.y += e.out0; s += e.done - e.out0; p.s0 = e.done;        // y[s - done] below: the stream's own position s
     }
     int lo = 0, hi = p.n_complete;                                 // first pulse with index >= s - 512
     while (lo < hi) {
@@ -328,4 +400,107 @@ RY_KERNEL(256) void synth_overlap(SynthOverlapParams p) {
         acc += p.resp[(size_t)j * SYNTH_FFT + d];
     }
     p.y[s - p.s0] = acc;
+}
+
+// ---- the two steps a bank does on the card (a single stream does them on the host: append_frames and the end of `advance`) ----------------------
+struct SynthGatherParams {
+    const SynthStream* bank; int n_streams;
+    int rows;                                     // rows of all windows
+    const float *old_sp, *old_ap;                 // the window buffer of the last call
+    const float *new_sp, *new_ap;                 // the call's new rows, streams back to back (the packed upload, or the caller's device rows)
+    float *sp, *ap;                               // the other window buffer: [stream][kept rows | new rows]
+    const long long* c_idx; const double* c_shift; const int* c_voiced; int carry_cap;     // carried pulses [stream][carry_cap]
+    long long* pidx; double* pshift; int* pvoiced;
+};
+
+// one row of 513 floats, 16 bytes per lane where source and destination sit alike in their 16-byte lines, 4 otherwise
+RY_DEV void synth_copy_row(float* d, const float* s) {
+    const int tid = (int)threadIdx.x;
+    if ((((size_t)d ^ (size_t)s) & 15) == 0) {
+        const int head = (int)(((16 - ((size_t)d & 15)) & 15) >> 2);
+        const int n4 = (SYNTH_BINS - head) >> 2;                   // <= 128
+        if (tid < n4) ry_st4(d + head + 4 * tid, ry_ld4(s + head + 4 * tid));
+        const int tail = head + 4 * n4;
+        if (tid >= 128 && tid - 128 < head) d[tid - 128] = s[tid - 128];
+        if (tid >= 192 && tail + tid - 192 < SYNTH_BINS) d[tail + tid - 192] = s[tail + tid - 192];
+    } else {
+        for (int i = tid; i < SYNTH_BINS; i += 256) d[i] = s[i];
+    }
+}
+
+// grid (max(rows, streams), 3): y = 0 / 1 the sp / ap row blockIdx.x of the new window buffer, y = 2 the carried pulses of stream blockIdx.x
+RY_KERNEL(256) void synth_gather(SynthGatherParams p) {
+    const int x = (int)blockIdx.x, tid = (int)threadIdx.x;
+    if (blockIdx.y == 2) {
+        if (x >= p.n_streams) return;
+        const SynthStream e = p.bank[x];
+        if (!e.active) return;
+        const size_t c0 = (size_t)x * p.carry_cap;
+        for (int i = tid; i < e.n_live; i += 256) {
+            p.pidx[e.pulse0 + i] = p.c_idx[c0 + i];
+            p.pshift[e.pulse0 + i] = p.c_shift[c0 + i];
+            p.pvoiced[e.pulse0 + i] = p.c_voiced[c0 + i];
+        }
+        return;
+    }
+    if (x >= p.rows) return;
+    int b;
+    SYNTH_STREAM_OF(p.bank, p.n_streams, x, row0, b);
+    const SynthStream e = p.bank[b];
+    const int r = x - e.row0;
+    const float* old = blockIdx.y == 0 ? p.old_sp : p.old_ap;
+    const float* nw = blockIdx.y == 0 ? p.new_sp : p.new_ap;
+    float* out = blockIdx.y == 0 ? p.sp : p.ap;
+    const float* src = r < e.kept ? old + (size_t)(e.src_row0 + r) * SYNTH_BINS : nw + (size_t)(e.new_row0 + r - e.kept) * SYNTH_BINS;
+    synth_copy_row(out + (size_t)x * SYNTH_BINS, src);
+}
+
+struct SynthRetireParams {
+    const SynthStream* bank;
+    SynthScanState* st;
+    const long long* pidx; const double* pshift; const int* pvoiced;
+    long long* c_idx; double* c_shift; int* c_voiced; int carry_cap;
+    SynthRetired* out;
+};
+
+// One workgroup per stream, after the overlap: pulses that cannot reach an unemitted sample -- index below fin - 512 -- leave the list, the last
+// one always stays (it has no successor yet); the survivors go to the front of the stream's carry slot.  The indices rise, so the pulses that
+// leave are a prefix and counting them is finding its length.  A stream whose signal ends is left as a new one.
+RY_KERNEL(256) void synth_retire(SynthRetireParams p) {
+    __shared__ int cnt[256];
+    const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const SynthStream e = p.bank[b];
+    if (!e.active) return;                                         // block-uniform
+    if (e.final) {
+        if (tid == 0) {
+            SynthScanState z;
+            z.phase = 0.0; z.last_voiced = 0; z.n_pulses = 0; z.overflow = 0; z.pad = 0; z.last_idx = 0;
+            p.st[b] = z;
+            SynthRetired r;
+            r.first_idx = -1; r.n_live = 0; r.overflow = 0;
+            p.out[b] = r;
+        }
+        return;
+    }
+    const long long* idx = p.pidx + e.pulse0;
+    int c = 0;
+    for (int j = tid; j + 1 < e.n_pulses; j += 256) c += idx[j] < e.fin - SYNTH_HALF ? 1 : 0;
+    cnt[tid] = c;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) { if (tid < s) cnt[tid] += cnt[tid + s]; __syncthreads(); }
+    const int drop = cnt[0];
+    const int keep = e.n_pulses - drop;
+    const int n = keep < p.carry_cap ? keep : p.carry_cap;
+    const size_t c0 = (size_t)b * p.carry_cap;
+    for (int i = tid; i < n; i += 256) {
+        p.c_idx[c0 + i] = idx[drop + i];
+        p.c_shift[c0 + i] = p.pshift[e.pulse0 + drop + i];
+        p.c_voiced[c0 + i] = p.pvoiced[e.pulse0 + drop + i];
+    }
+    if (tid == 0) {
+        p.st[b].n_pulses = n;
+        SynthRetired r;
+        r.first_idx = keep > 0 ? idx[drop] : -1; r.n_live = n; r.overflow = keep - n;
+        p.out[b] = r;
+    }
 }

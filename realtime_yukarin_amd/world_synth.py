@@ -27,7 +27,9 @@ FFT_SIZE = 1024
 BINS = FFT_SIZE // 2 + 1
 # which path `Synthesizer.synthesize_many` took, counted per call: 'in_place' (device rows read where they are), 'packed' (host rows, one
 # upload) -- both ONE `ry_synth_run_many` --, 'fallback' (one `synthesize` per item)
-calls = {'in_place': 0, 'packed': 0, 'fallback': 0}
+# ... and `StreamBank.push`: 'bank_in_place' / 'bank_packed' -- ONE `ry_synth_bank_push` --, 'bank_fallback' (one bank push per item, the other
+# streams sitting out)
+calls = {'in_place': 0, 'packed': 0, 'fallback': 0, 'bank_in_place': 0, 'bank_packed': 0, 'bank_fallback': 0}
 
 
 def cheaptrick_fft_size(fs, f0_floor: float = 71.0) -> int:
@@ -200,6 +202,180 @@ class Synthesizer(DeviceHandle):
         return self.fft_size // 2 + int(numpy.ceil(self.fs * self.frame_period / 1000)) + int(numpy.ceil(self.fs / f0))
 
 
+class StreamBank(DeviceHandle):
+    """B independent synthesis streams at one rate and one frame period, each with its own seed, advanced by ONE device call per buffer
+    (`ry_synth_bank_*`): what `Synthesizer.push` / `flush` are for one session, for the sessions of a process.  Stream b returns, call by call,
+    the bits a lone `Synthesizer(fs, frame_period, seed=seeds[b])` returns for the same frames in the same cuts, whatever the other streams do.
+    `seeds=None`: every stream has RY_SYNTH_SEED, as the synthesizers of the drop-in bodies."""
+
+    def __init__(self, fs: int, frame_period: float = 5.0, n_streams: int = 1, seeds=None, ctx=None, device: Optional[int] = None,
+                 fft_size: Optional[int] = None):
+        self.fs, self.frame_period, self.n_streams = int(fs), float(frame_period), int(n_streams)
+        if seeds is None:
+            seeds = [int(os.environ.get('RY_SYNTH_SEED', '0'))] * self.n_streams
+        self.seeds = [int(v) & 0xffffffff for v in seeds]
+        if len(self.seeds) != self.n_streams:
+            raise ValueError('%d seeds for %d streams' % (len(self.seeds), self.n_streams))
+        self.fft_size = int(fft_size) if fft_size else cheaptrick_fft_size(self.fs)
+        DeviceHandle.__init__(self, ctx, device)
+
+    _destroy = 'ry_synth_bank_destroy'
+    _rows = staticmethod(Synthesizer._rows)
+    _item = Synthesizer._item
+
+    def _create(self, lib, ctx):
+        h = ctypes.c_void_p()
+        seeds = (ctypes.c_uint * max(self.n_streams, 1))(*self.seeds)
+        lib.check(lib.dll.ry_synth_bank_create(ctx.handle, self.fs, self.frame_period, self.fft_size, self.n_streams, seeds, ctypes.byref(h)))
+        return h
+
+    def bound(self, stream: int, n: int, final: bool = False) -> int:
+        lib, h = self._get()
+        return int(lib.dll.ry_synth_bank_bound(h, int(stream), int(n), int(bool(final))))
+
+    def _call(self, entries, final, in_place):
+        """One `ry_synth_bank_push`: `entries` {stream: (f0, sp, ap)} with all rows on the host, or all on the card and consecutive."""
+        lib, h = self._get()
+        B = self.n_streams
+        order = sorted(entries)
+        n = numpy.zeros(B, numpy.int32)
+        fin = numpy.zeros(B, numpy.int32)
+        for b in order:
+            n[b] = entries[b][0].size
+        fin[list(final)] = 1
+        if order:
+            f0 = numpy.ascontiguousarray(numpy.concatenate([entries[b][0] for b in order]))
+        else:                                                      # a plain flush: nothing is read
+            f0 = numpy.zeros(1)
+        if in_place:
+            keep = entries
+            psp, pap = _lib._fptr(entries[order[0]][1].address), _lib._fptr(entries[order[0]][2].address)
+        elif order:
+            keep = (numpy.concatenate([entries[b][1] for b in order]), numpy.concatenate([entries[b][2] for b in order]))
+            psp, pap = _lib._fptr(keep[0]), _lib._fptr(keep[1])
+        else:
+            keep = (numpy.zeros((1, BINS), numpy.float32),) * 2
+            psp, pap = _lib._fptr(keep[0]), _lib._fptr(keep[1])
+        cap = sum(self.bound(b, int(n[b]), bool(fin[b])) for b in range(B) if n[b] > 0 or fin[b])
+        y = numpy.empty(max(cap, 1), numpy.float64)
+        off = numpy.zeros(B + 1, numpy.int64)
+        ip = ctypes.POINTER(ctypes.c_int)
+        lib.check(lib.dll.ry_synth_bank_push(h, f0.ctypes.data_as(_DP), psp, pap, n.ctypes.data_as(ip), fin.ctypes.data_as(ip), BINS, int(in_place),
+                                             y.ctypes.data_as(_DP), cap, off.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        del keep
+        return [y[off[b]:off[b + 1]].copy() for b in range(B)]
+
+    def push(self, items, final=()) -> list:
+        """`items`: a list of length B of `(f0, sp, ap)` or None (the stream sits the call out); `final`: the streams whose signal ends with this
+        call (everything left comes back and the slot starts a new signal with its next frames).  -> B float64 arrays, empty for a stream that
+        sat out.  Host rows go up in one packed upload, `DeviceRows` that are consecutive slices of one buffer are read where they are -- one
+        `ry_synth_bank_push` either way; any other list runs as one bank push per item with the other streams sitting out: the same bits."""
+        items = list(items)
+        if len(items) != self.n_streams:
+            raise ValueError('%d items for %d streams' % (len(items), self.n_streams))
+        final = sorted(set(int(b) for b in final))
+        if any(b < 0 or b >= self.n_streams for b in final):
+            raise ValueError('final names stream %s of %d' % (final, self.n_streams))
+        ent = {b: self._item(*it) for b, it in enumerate(items) if it is not None}
+        ent = {b: it for b, it in ent.items() if it[0].size > 0}
+        for f0, sp, ap, dev in ent.values():
+            if dev is False and (sp.shape[1] != BINS or ap.shape[1] != BINS):
+                raise ValueError('%d bins per frame, %d expected' % (sp.shape[1], BINS))
+        if not ent and not final:
+            raise ValueError('no stream has a frame or ends')
+        order = sorted(ent)
+        kinds = set(ent[b][3] for b in order)
+        row = BINS * 4
+        in_place = kinds == {True} and all(ent[b][k].address == ent[a][k].address + ent[a][k].frames * row for a, b in zip(order, order[1:]) for k in (1, 2))
+        self._kept_pulses = None
+        if in_place or kinds <= {False}:
+            out = self._call(ent, final, in_place)
+            calls['bank_in_place' if in_place else 'bank_packed'] += 1
+            return out
+        calls['bank_fallback'] += 1
+        out = [numpy.empty(0, numpy.float64) for _ in range(self.n_streams)]
+        kept = {}
+        for b in order:
+            f0, sp, ap, dev = ent[b]
+            if dev is None:                                        # one of each: bring the host side over
+                sp = sp if isinstance(sp, DeviceRows) else _upload(self._get_ctx(), self._rows(sp, f0.size, 'sp')[2])
+                ap = ap if isinstance(ap, DeviceRows) else _upload(self._get_ctx(), self._rows(ap, f0.size, 'ap')[2])
+                dev = True
+            out[b] = self._call({b: (f0, sp, ap)}, [b] if b in final else [], dev)[b]
+            kept[b] = self.pulses(b)                               # the next call reuses the pulse arrays
+        rest = [b for b in final if b not in ent]
+        if rest:
+            got = self._call({}, rest, False)
+            for b in rest:
+                out[b] = got[b]
+                kept[b] = self.pulses(b)
+        self._kept_pulses = kept
+        return out
+
+    def _get_ctx(self):
+        self._get()
+        return self._ctx
+
+    def flush(self, streams) -> list:
+        """Ends the signals of `streams`: what is left of each (a list of B arrays, empty for the others); their slots start anew."""
+        return self.push([None] * self.n_streams, final=streams)
+
+    def reset(self, stream=None) -> None:
+        lib, h = self._get()
+        lib.check(lib.dll.ry_synth_bank_reset(h, -1 if stream is None else int(stream)))
+
+    def pulses(self, stream: int):
+        """(index, shift, voiced) of the pulses the last push found for `stream`, as `Synthesizer.pulses` (`ry_synth_bank_debug_pulses`)."""
+        lib, h = self._get()
+        kept = getattr(self, '_kept_pulses', None)
+        if kept is not None:                                       # the last push ran item by item
+            return kept.get(int(stream), (numpy.empty(0, numpy.int64), numpy.empty(0, numpy.float64), numpy.empty(0, bool)))
+        n = ctypes.c_int()
+        lib.check(lib.dll.ry_synth_bank_debug_pulses(h, int(stream), None, None, None, 0, ctypes.byref(n)))
+        idx, sh, vo = numpy.empty(n.value, numpy.int64), numpy.empty(n.value, numpy.float64), numpy.empty(n.value, numpy.int32)
+        lib.check(lib.dll.ry_synth_bank_debug_pulses(h, int(stream), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), sh.ctypes.data_as(_DP),
+                                                     vo.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n.value, ctypes.byref(n)))
+        return idx, sh, vo != 0
+
+    def poison(self) -> None:
+        lib, h = self._get()
+        self._kept_pulses = None
+        lib.check(lib.dll.ry_synth_bank_debug_poison(h))
+
+    def counts(self) -> dict:
+        """Stream waits, kernel launches and host <-> device copies of the last push (`ry_synth_bank_debug_counts`)."""
+        lib, h = self._get()
+        c = (ctypes.c_int * 4)()
+        lib.check(lib.dll.ry_synth_bank_debug_counts(h, c))
+        return dict(zip(('waits', 'launches', 'h2d', 'd2h'), (int(v) for v in c)))
+
+    def rows(self, stream: int) -> int:
+        """Window rows kept for `stream` (`ry_synth_bank_debug_rows`)."""
+        lib, h = self._get()
+        return int(lib.dll.ry_synth_bank_debug_rows(h, int(stream)))
+
+
+class BankSlot(object):
+    """One stream of a `StreamBank`, with the `push` of a `Synthesizer`: what `create_synthesizer_many` gives a `RealtimeVocoder`."""
+
+    def __init__(self, bank: StreamBank, slot: int):
+        self.bank, self.slot = bank, int(slot)
+
+    def _alone(self, item):
+        items = [None] * self.bank.n_streams
+        items[self.slot] = item
+        return items
+
+    def push(self, f0, sp, ap) -> numpy.ndarray:
+        return self.bank.push(self._alone((f0, sp, ap)))[self.slot]
+
+    def flush(self) -> numpy.ndarray:
+        return self.bank.flush([self.slot])[self.slot]
+
+    def reset(self) -> None:
+        self.bank.reset(self.slot)
+
+
 class _DeviceBuffer(object):
     """A `ry_dev_alloc` buffer that frees itself."""
 
@@ -284,9 +460,48 @@ def create_synthesizer(self, buffer_size: int, number_of_pointers: int):
 
 
 def decode_realtime(self, acoustic_feature):
-    """Drop-in body of `RealtimeVocoder.decode` (vocoder.py:89-120): the frames go to the stream, the samples that are final come back."""
+    """Drop-in body of `RealtimeVocoder.decode` (vocoder.py:89-120): the frames go to the stream, the samples that are final come back.  A
+    vocoder that holds a slot of a bank (`create_synthesizer_many`) pushes that slot alone."""
     from yukarin import Wave
     assert self._synthesizer is not None
     f = acoustic_feature
     out = self._synthesizer.push(numpy.asarray(f.f0).ravel(), f.sp, f.ap)
     return Wave(wave=out, sampling_rate=self.out_sampling_rate)
+
+
+def create_synthesizer_many(vocoders, buffer_size: int, number_of_pointers: int) -> StreamBank:
+    """`create_synthesizer` for a list of `RealtimeVocoder` objects that one process serves: they get the slots of ONE `StreamBank`, so that
+    `decode_realtime_many` advances all of them in one device call.  They share the sampling rate and the frame period."""
+    vocoders = list(vocoders)
+    if not vocoders:
+        raise ValueError('no vocoder')
+    fs, fp = vocoders[0].out_sampling_rate, vocoders[0].acoustic_param.frame_period
+    if any(v.out_sampling_rate != fs or v.acoustic_param.frame_period != fp for v in vocoders):
+        raise ValueError('the vocoders of one bank share the sampling rate and the frame period')
+    assert all(v._synthesizer is None for v in vocoders)
+    bank = StreamBank(fs, fp, n_streams=len(vocoders), ctx=engine_for_tests.ctx)
+    bank.buffer_size, bank.number_of_pointers = int(buffer_size), int(number_of_pointers)
+    for i, v in enumerate(vocoders):
+        v._synthesizer = BankSlot(bank, i)
+    return bank
+
+
+def decode_realtime_many(vocoders, features):
+    """The list form of `decode_realtime` for vocoders that hold the slots of one bank (`create_synthesizer_many`): one feature per vocoder, None
+    for a vocoder that sits the call out (it gets an empty `Wave`) -> the `Wave`s, each equal to `decode_realtime` of its feature bit for bit."""
+    from yukarin import Wave
+    vocoders, features = list(vocoders), list(features)
+    if len(vocoders) != len(features):
+        raise ValueError('%d features for %d vocoders' % (len(features), len(vocoders)))
+    if not vocoders:
+        return []
+    slots = [v._synthesizer for v in vocoders]
+    if not all(isinstance(s, BankSlot) and s.bank is slots[0].bank for s in slots) or len(set(s.slot for s in slots)) != len(slots):
+        raise ValueError('the vocoders do not hold distinct slots of one bank (create_synthesizer_many)')
+    bank = slots[0].bank
+    items = [None] * bank.n_streams
+    for s, f in zip(slots, features):
+        if f is not None:
+            items[s.slot] = (numpy.asarray(f.f0).ravel(), f.sp, f.ap)
+    outs = bank.push(items)
+    return [Wave(wave=outs[s.slot], sampling_rate=v.out_sampling_rate) for s, v in zip(slots, vocoders)]
