@@ -191,6 +191,22 @@ int ry_vc_wait_wave(ry_vc* vc, int ticket, float* mc_out, float* sp_out, unsigne
  * frame indices row_of [n_eff] (null to skip). */
 int ry_vc_gate(ry_vc* vc, const float* wave, int n_samples, int hop, int fft_length, float p_effective, float p_all,
                const float* feat, int n_frames, unsigned char* effective_out, int* n_eff_out, float* x_eff_out, int* row_of_out);
+/* ry_vc_submit_wave for a wave and a feature block that are ALREADY ON THE CARD (what ry_crepe_track and ry_analysis_extract_resident left there),
+ * with the results left there too: wave_dev [n_samples] float32 and feat_dev [n_frames][in_ch] are read in place (no staging, no H2D copy);
+ * mc_out_dev [n_frames][M], sp_out_dev [n_frames][F] and mask_dev_out [n_frames] (bytes: 1 = effective) stay on the card (no mc / sp copy to the
+ * host).  The call waits once, for the count (it picks the stage-1 plan), and returns it in *n_eff_out with the mask in effective_out [n_frames]
+ * (host).  Ring slots, lanes and ry_vc_set_discard as ry_vc_enqueue_device (discarded rows of sp_out_dev are left untouched).  Order: the call
+ * makes its stage-1 stream wait for what the CONTEXT stream holds at the time of the call -- inputs produced there (ry_crepe_track, the analysis)
+ * need no wait by the caller, inputs produced on another stream must be complete (ry_sync) -- and makes the context stream wait for the end of
+ * the window, so work enqueued on the context stream afterwards (ry_mask_rows, ry_synth_run / ry_synth_push with on_device = 1, ry_dev_download)
+ * reads complete rows; a reader on another stream waits with ry_sync.  Refusals: those of ry_vc_submit_wave, and null outputs. */
+int ry_vc_enqueue_wave_device(ry_vc* vc, const float* wave_dev, int n_samples, int hop, int fft_length, float p_effective, float p_all,
+                              const float* feat_dev, int n_frames, float sp_floor, float* mc_out_dev, float* sp_out_dev,
+                              unsigned char* mask_dev_out, unsigned char* effective_out, int* n_eff_out);
+/* `combine_silent` for rows that stay where they are (the aperiodicity of a resident chain): rows k0 .. k1 - 1 of rows_dev [n][cols] (float32)
+ * whose byte in mask_dev [n] is 0 become +0.0f in place; every other row keeps its bits.  Enqueue only, on `stream` (a HIP stream; null: the
+ * context stream); nothing is waited for.  Refused: null pointers, n < 1, cols < 1, a range outside 0 <= k0 <= k1 <= n. */
+int ry_mask_rows(ry_ctx* ctx, float* rows_dev, const unsigned char* mask_dev, int n, int cols, int k0, int k1, void* stream);
 /* `AcousticConverter.decode_spectrogram` alone (host pointers): sp [n][bins] = exp(mc [n][m] @ mtx [m][bins]) + floor. */
 int ry_mc2sp(ry_ctx* ctx, const float* mc, const float* mtx, int n, int m, int bins, float floor, float* sp);
 
@@ -521,6 +537,12 @@ int ry_analysis_extract_dev(ry_analysis* analysis, const float* x32_dev, long lo
 int ry_analysis_extract_many_dev(ry_analysis* analysis, const float* x32_dev, const long long* sample_offsets, const double* f0_dev, const double* t_dev,
                                  const int* frame_offsets, int n_waves, double threshold,
                                  double* sp64_out, float* sp32_dev_out, double* mc_out, double* ap64_out, float* ap32_dev_out, double* coded_out);
+/* ry_analysis_extract_dev with DEVICE OUTPUTS ONLY, for a chain that keeps the rows on the card: mc32_dev_out [n][order + 1] float32 = (float)mc, the
+ * bits of the host's `mc.astype(float32)` (stored by the sp2mc step itself), sp32_dev_out [n][513] and ap32_dev_out [n][513] as the float32 rows of
+ * ry_analysis_extract_dev.  No host row is written and nothing but the verdict of the track check is copied to the host.  Refusals: those of
+ * ry_analysis_extract_dev, and a null output; a refused call writes nothing.  The call drains the context stream before it returns. */
+int ry_analysis_extract_resident(ry_analysis* analysis, const float* x32_dev, long long x_len, const double* f0_dev, const double* t_dev, int n,
+                                 double threshold, float* mc32_dev_out, float* sp32_dev_out, float* ap32_dev_out);
 /* the number of bands B (1 at 16 kHz, 3 at 24 kHz); negative (an error code) where D4C is not built for the handle's rate */
 int ry_analysis_d4c_bands(ry_analysis* analysis);
 /* tests: what the last recorded (ry_analysis_debug_record) D4C run decided.  ints_out [n][9]: half length of the Love-Train window, of the other

@@ -94,6 +94,7 @@ struct Outputs {
     double* sp64 = nullptr; float* sp32_dev = nullptr; double* mc = nullptr;
     bool d4c = false; double threshold = 0.85;
     double* ap64 = nullptr; float* ap32_dev = nullptr; double* coded = nullptr;
+    float* mc32_dev = nullptr;               // ry_analysis_extract_resident: the float32 mel-cepstrum rows, left on the card
 };
 
 // what every entry refuses before it looks at the wave or the track; *empty: nothing to analyse, nothing is written
@@ -166,6 +167,7 @@ int run_spans(ry_analysis* s, const double* d_x, const Span* spans, int n_spans,
         p.tw = s->tw; p.S = s->S; p.n_mc = s->order + 1;
         p.sp64 = o.sp64 ? s->d_sp.ptr() + k0 * SYNTH_BINS : nullptr; p.sp32 = o.sp32_dev ? o.sp32_dev + k0 * SYNTH_BINS : nullptr;
         p.mc = o.mc ? s->d_mc.ptr() + k0 * n_mc : nullptr; p.ints = s->record ? s->d_ints.ptr() + k0 : nullptr;
+        p.mc32 = o.mc32_dev ? o.mc32_dev + k0 * n_mc : nullptr;
         RY_LAUNCH(analysis_frame, dim3((unsigned)sp.n), 256, st, p);
         RT_TRY(rt::last_error());
     }
@@ -299,6 +301,21 @@ int ry_analysis_extract_dev(ry_analysis* s, const float* x32_dev, long long x_le
     if (!f0_dev || !t_dev) return fail(RY_EINVAL, "null f0 / t");
     const Span one = {0, x_len, 0, n};
     return extract_dev(s, x32_dev, x_len, f0_dev, t_dev, n, &one, 1, o);
+}
+
+int ry_analysis_extract_resident(ry_analysis* s, const float* x32_dev, long long x_len, const double* f0_dev, const double* t_dev, int n, double threshold,
+                                 float* mc32_dev_out, float* sp32_dev_out, float* ap32_dev_out) {
+    Outputs o;
+    o.mc32_dev = mc32_dev_out; o.sp32_dev = sp32_dev_out; o.ap32_dev = ap32_dev_out;
+    o.d4c = true; o.threshold = threshold;
+    bool empty = false;
+    RY_TRY(check_call(s, x_len, n, true, o, &empty));
+    if (!mc32_dev_out || !sp32_dev_out || !ap32_dev_out) return fail(RY_EINVAL, "null output rows");
+    if (empty) return RY_OK;
+    if (!x32_dev) return fail(RY_EINVAL, "null wave");
+    if (!f0_dev || !t_dev) return fail(RY_EINVAL, "null f0 / t");
+    const Span one = {0, x_len, 0, n};
+    return extract_dev(s, x32_dev, x_len, f0_dev, t_dev, n, &one, 1, o);       // no host row is named: the verdict is the only copy to the host
 }
 
 int ry_analysis_extract_many_dev(ry_analysis* s, const float* x32_dev, const long long* sample_offsets, const double* f0_dev, const double* t_dev,

@@ -29,6 +29,7 @@ struct AnalysisParams {
     const double* S;                              // [513][n_mc] freqt as a matrix
     int n_mc;                                     // order + 1
     double* sp64; float* sp32; double* mc;        // [n][513], [n][513], [n][n_mc]; any may be null
+    float* mc32;                                  // [n][n_mc]: (float)mc, the bits of the host's mc.astype(float32); may be null
     AnalysisFrameInts* ints;                      // [n]
 };
 
@@ -62,7 +63,8 @@ RY_DEV double analysis_block_sum(double* red, double v) {
 }
 
 // mc[m] = sum over i of c[i] S[i][m]: wave w takes m = w, w + 4, ...; its lanes sum i = lane, lane + 64, ... and meet in a tree
-RY_DEV void analysis_freqt(const double* c, const double* S, int n_mc, double* red, double* out) {
+// out32 (may be null): the same sums rounded to float32 once, from the register that holds the float64 sum -- no second pass over `out`
+RY_DEV void analysis_freqt(const double* c, const double* S, int n_mc, double* red, double* out, float* out32 = nullptr) {
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int m0 = 0; m0 < n_mc; m0 += 4) {
         const int m = m0 + wave;
@@ -72,7 +74,10 @@ RY_DEV void analysis_freqt(const double* c, const double* S, int n_mc, double* r
         red[tid] = acc;
         __syncthreads();
         for (int s = 32; s > 0; s >>= 1) { if (lane < s) red[tid] += red[tid + s]; __syncthreads(); }
-        if (lane == 0 && m < n_mc && out) out[m] = red[tid];
+        if (lane == 0 && m < n_mc) {
+            if (out) out[m] = red[tid];
+            if (out32) out32[m] = (float)red[tid];
+        }
         __syncthreads();
     }
 }
@@ -216,10 +221,10 @@ RY_KERNEL(256) void analysis_frame(AnalysisParams p) {
         if (p.sp32) p.sp32[(size_t)k * SYNTH_BINS + i] = (float)o;
     }
     // mc: c = irfft(log sp) is the liftered cepstrum; c[0] / 2, then freqt as a matrix
-    if (p.mc) {                                                    // block-uniform
+    if (p.mc || p.mc32) {                                          // block-uniform
         if (tid == 0) cp[0] = cp[0] / 2;
         __syncthreads();
-        analysis_freqt(cp, p.S, p.n_mc, red, p.mc + (size_t)k * p.n_mc);
+        analysis_freqt(cp, p.S, p.n_mc, red, p.mc ? p.mc + (size_t)k * p.n_mc : nullptr, p.mc32 ? p.mc32 + (size_t)k * p.n_mc : nullptr);
     }
 }
 

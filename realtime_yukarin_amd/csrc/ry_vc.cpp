@@ -2,7 +2,8 @@
 // (/root/reference/realtime_voice_conversion/yukarin_wrapper/voice_changer.py:24-42) on the device.  stage-1 on the effective frames ->
 // combine_silent (scatter into the silent block) -> decode_spectrogram (mc2sp = exp(mc @ M)) + floor -> stage-2, as one chain per window:
 // six ring slots with pinned staging (ry_vc_submit / ry_vc_wait), two window lanes over clones of the predictor pair (ry_vc_set_lanes),
-// the silence gate on the device (ry_vc_gate / ry_vc_submit_wave), several windows per call (ry_vc_enqueue_device_batch), and the same
+// the silence gate on the device (ry_vc_gate / ry_vc_submit_wave; ry_vc_enqueue_wave_device for a wave and features that are already on the
+// card, with ry_mask_rows as the combine_silent of rows that stay there), several windows per call (ry_vc_enqueue_device_batch), and the same
 // chain cut where the reference's own class cuts it (ry_vc_stage1 / ry_vc_stage2_from_mc / ry_vc_mid_sp).  The predictors themselves
 // are driven through the C ABI of ry_net.cpp (ry_ac_convert, ry_sr_convert_rows, ry_net_clone).
 #include "ry_vc_kernels.h"
@@ -20,7 +21,7 @@ struct VcSlot {
     float *h_wave = nullptr, *d_wave = nullptr, *h_feat = nullptr, *d_feat = nullptr, *d_pow = nullptr;
     unsigned char *h_mask = nullptr, *d_mask = nullptr;
     int *h_count = nullptr, *d_count = nullptr;
-    int cap_wave = 0;
+    int cap_wave = 0, cap_pow = 0;    // samples the wave staging holds; wave frames d_pow holds
     // every slot owns its buffers and grows on its own: a longer window never touches a slot that still holds a window in flight
     Arena bufs;
     std::vector<void*> pinned;
@@ -52,6 +53,7 @@ struct ry_vc {
     float* d_mtx = nullptr;
     VcSlot slot[RING];
     bool has_ev = false;
+    rt::Event ev_in;         // ry_vc_enqueue_wave_device: the context stream has produced the wave and the features the stage-1 stream is about to read
     int next_ticket = 0;
     int dev_count = 0;       // device-pointer calls (ry_vc_enqueue_device) take the slots round robin
     int split_eff = -1;      // ry_vc_stage1 left the converted rows of this many effective frames in slot 0's d_y1 (-1: nothing)
@@ -170,7 +172,7 @@ static int vc_reserve_slot(ry_vc* vc, VcSlot& sl, int n_eff, int n_frames) {
     RY_TRY(vc_halloc(sl, (void**)&sl.h_feat, (size_t)cf * cin * sizeof(float)));
     RY_TRY(vc_halloc(sl, (void**)&sl.h_mask, (size_t)cf + 16));
     RY_TRY(vc_halloc(sl, (void**)&sl.h_count, 16));
-    sl.h_wave = nullptr; sl.d_wave = nullptr; sl.d_pow = nullptr; sl.cap_wave = 0;
+    sl.h_wave = nullptr; sl.d_wave = nullptr; sl.d_pow = nullptr; sl.cap_wave = 0; sl.cap_pow = 0;
     sl.used = false;
     sl.cap_eff = ce; sl.cap_frames = cf;
     if (&sl == &vc->slot[0]) vc->split_eff = -1;
@@ -248,6 +250,7 @@ int ry_vc_create(ry_net* s1, ry_net* s2, const float* mtx, int M, int F, ry_vc**
     std::vector<float> h(mtx, mtx + (size_t)M * F);
     RY_TRY(upload(vc->arena, s1->ctx, h, &vc->d_mtx));
     for (VcSlot& sl : vc->slot) { RT_TRY(rt::event_create_fast(&sl.ev_mid)); RT_TRY(rt::event_create_fast(&sl.ev_done)); }
+    RT_TRY(rt::event_create_fast(&vc->ev_in));
     vc->has_ev = true;
     *out = vc.release();
     return RY_OK;
@@ -258,7 +261,7 @@ void ry_vc_destroy(ry_vc* vc) {
     rt::set_device(vc->s1->ctx->device);
     vc->sync_lanes();
     for (int k = 1; k < vc->lanes; ++k) { ry_net_destroy(vc->l1[k]); ry_net_destroy(vc->l2[k]); }
-    if (vc->has_ev) for (VcSlot& sl : vc->slot) { rt::event_destroy(sl.ev_mid); rt::event_destroy(sl.ev_done); }
+    if (vc->has_ev) { for (VcSlot& sl : vc->slot) { rt::event_destroy(sl.ev_mid); rt::event_destroy(sl.ev_done); } rt::event_destroy(vc->ev_in); }
     if (vc->b_ev) for (ry_vc::BatchSet& bs : vc->bset) { rt::event_destroy(bs.mid); rt::event_destroy(bs.done); }
     vc->free_pinned();
     delete vc;
@@ -381,22 +384,60 @@ int ry_vc_convert(ry_vc* vc, const float* x_eff, const int* row_of, int n_eff, i
 // back (4 bytes, pinned) before stage 1 is queued: one short wait per window in exchange for the host-side numpy gate.
 }  // extern "C"
 
-// wave + features up, frame powers, gate, compaction, count and mask back (waits for the count); leaves x_eff / row_of in the slot
+// The gate over a wave and a feature block in device memory: frame powers, gate, compaction, count and mask back (waits for the count); leaves
+// x_eff / row_of in the slot and the mask bytes in d_mask_out (the slot's, or a block of the caller).  Shared by the host-array calls
+// (vc_gate_into_slot stages the wave and the features first) and ry_vc_enqueue_wave_device (which reads them where they are).
+static int vc_gate_launch(ry_net* s1, VcSlot& sl, const float* d_wave, int n_samples, int hop, int fft_length, float p_effective, float p_all,
+                          const float* d_feat, int n_frames, unsigned char* d_mask_out, int* n_eff_out) {
+    const int cin = s1->desc.in_ch;
+    ry_stream_t st1 = s1->stream;
+    const int n_wave_frames = n_samples / hop + 1;              // librosa: 1 + (len + 2 * (fft / 2) - fft) / hop
+    if (n_wave_frames > sl.cap_pow) {                           // one power per WAVE frame (<= n_samples + 1 of them, whatever the hop)
+        RT_TRY(rt::stream_sync(st1));
+        if (sl.d_pow) sl.bufs.free_one(sl.d_pow);
+        sl.d_pow = nullptr; sl.cap_pow = 0;
+        const int cap = n_wave_frames + n_wave_frames / 4 + 1024;
+        RY_TRY(sl.bufs.alloc(&sl.d_pow, (size_t)cap));
+        sl.cap_pow = cap;
+    }
+    Launcher Lc{s1, s1->ctx, st1, nullptr, nullptr};
+    // The power of EVERY wave frame is taken: the host takes log_spec.max() (the top_db clamp) over all len(wave) // hop + 1 frames and
+    // truncates to the feature block afterwards, so a frame past the block can still decide the clamp (a live window has n * hop samples:
+    // always one frame more than features).  The mask and the compaction look at the first n_frames only (ry_gate_compact).
+    RyFramePowerParams fp;
+    fp.wave = d_wave; fp.n = n_samples; fp.hop = hop; fp.fft = fft_length; fp.n_wave_frames = n_wave_frames; fp.power = sl.d_pow;
+    dim3 fg((unsigned)((n_wave_frames + 3) / 4));
+    RY_TRY(Lc.begin("ry_frame_power", "separate_effective", 0, 0, fg));
+    RY_LAUNCH(ry_frame_power, fg, 256, st1, fp);
+    RY_TRY(Lc.end());
+    RyGateParams gp;
+    gp.power = sl.d_pow; gp.n_wave_frames = n_wave_frames; gp.n_frames = n_frames; gp.p_eff = p_effective; gp.p_all = p_all;
+    gp.feat = d_feat; gp.cin = cin; gp.x_eff = sl.d_x; gp.row_of = sl.d_row; gp.count = sl.d_count; gp.mask = d_mask_out;
+    RY_TRY(Lc.begin("ry_gate_compact", "separate_effective", 0, 0, dim3(1)));
+    RY_LAUNCH(ry_gate_compact, dim3(1), 1024, st1, gp);
+    RY_TRY(Lc.end());
+    RT_TRY(rt::d2h(sl.h_count, sl.d_count, sizeof(int), st1));
+    RT_TRY(rt::d2h(sl.h_mask, d_mask_out, (size_t)n_frames, st1));
+    RT_TRY(rt::stream_sync(st1));                               // the count picks the stage-1 plan
+    const int n_eff = sl.h_count[0];
+    if (n_eff < 0 || n_eff > n_frames) return fail(RY_EHIP, "the gate returned %d effective frames of %d", n_eff, n_frames);
+    *n_eff_out = n_eff;
+    return RY_OK;
+}
+
+// wave + features up, then the gate over them (vc_gate_launch)
 static int vc_gate_into_slot(ry_vc* vc, ry_net* s1, VcSlot& sl, const float* wave, int n_samples, int hop, int fft_length, float p_effective, float p_all,
                              const float* feat, int n_frames, int* n_eff_out) {
     const int cin = s1->desc.in_ch;
     ry_stream_t st1 = s1->stream;
     if (sl.used) RT_TRY(rt::stream_wait_event(st1, sl.ev_done));
-    const int n_wave_frames = n_samples / hop + 1;              // librosa: 1 + (len + 2 * (fft / 2) - fft) / hop
     if (n_samples > sl.cap_wave) {                              // wave staging of this slot, grown on demand: the previous buffers go
         RT_TRY(rt::stream_sync(st1));
         if (sl.d_wave) sl.bufs.free_one(sl.d_wave);
-        if (sl.d_pow) sl.bufs.free_one(sl.d_pow);
         if (sl.h_wave) sl.free_pinned_one(sl.h_wave);
-        sl.d_wave = sl.d_pow = sl.h_wave = nullptr; sl.cap_wave = 0;
+        sl.d_wave = sl.h_wave = nullptr; sl.cap_wave = 0;
         const int cap = n_samples + n_samples / 4 + 1024;
         RY_TRY(sl.bufs.alloc(&sl.d_wave, (size_t)cap));
-        RY_TRY(sl.bufs.alloc(&sl.d_pow, (size_t)cap + 8));       // one power per WAVE frame (<= n_samples + 1 of them, whatever the hop)
         RY_TRY(vc_halloc(sl, (void**)&sl.h_wave, (size_t)cap * sizeof(float)));
         sl.cap_wave = cap;
     }
@@ -404,29 +445,7 @@ static int vc_gate_into_slot(ry_vc* vc, ry_net* s1, VcSlot& sl, const float* wav
     memcpy(sl.h_feat, feat, (size_t)n_frames * cin * sizeof(float));
     RT_TRY(rt::h2d(sl.d_wave, sl.h_wave, (size_t)n_samples * sizeof(float), st1));
     RT_TRY(rt::h2d(sl.d_feat, sl.h_feat, (size_t)n_frames * cin * sizeof(float), st1));
-    Launcher Lc{s1, s1->ctx, st1, nullptr, nullptr};
-    // The power of EVERY wave frame is taken: the host takes log_spec.max() (the top_db clamp) over all len(wave) // hop + 1 frames and
-    // truncates to the feature block afterwards, so a frame past the block can still decide the clamp (a live window has n * hop samples:
-    // always one frame more than features).  The mask and the compaction look at the first n_frames only (ry_gate_compact).
-    RyFramePowerParams fp;
-    fp.wave = sl.d_wave; fp.n = n_samples; fp.hop = hop; fp.fft = fft_length; fp.n_wave_frames = n_wave_frames; fp.power = sl.d_pow;
-    dim3 fg((unsigned)((n_wave_frames + 3) / 4));
-    RY_TRY(Lc.begin("ry_frame_power", "separate_effective", 0, 0, fg));
-    RY_LAUNCH(ry_frame_power, fg, 256, st1, fp);
-    RY_TRY(Lc.end());
-    RyGateParams gp;
-    gp.power = sl.d_pow; gp.n_wave_frames = n_wave_frames; gp.n_frames = n_frames; gp.p_eff = p_effective; gp.p_all = p_all;
-    gp.feat = sl.d_feat; gp.cin = cin; gp.x_eff = sl.d_x; gp.row_of = sl.d_row; gp.count = sl.d_count; gp.mask = sl.d_mask;
-    RY_TRY(Lc.begin("ry_gate_compact", "separate_effective", 0, 0, dim3(1)));
-    RY_LAUNCH(ry_gate_compact, dim3(1), 1024, st1, gp);
-    RY_TRY(Lc.end());
-    RT_TRY(rt::d2h(sl.h_count, sl.d_count, sizeof(int), st1));
-    RT_TRY(rt::d2h(sl.h_mask, sl.d_mask, (size_t)n_frames, st1));
-    RT_TRY(rt::stream_sync(st1));                               // the count picks the stage-1 plan
-    const int n_eff = sl.h_count[0];
-    if (n_eff < 0 || n_eff > n_frames) return fail(RY_EHIP, "the gate returned %d effective frames of %d", n_eff, n_frames);
-    *n_eff_out = n_eff;
-    return RY_OK;
+    return vc_gate_launch(s1, sl, sl.d_wave, n_samples, hop, fft_length, p_effective, p_all, sl.d_feat, n_frames, sl.d_mask, n_eff_out);
 }
 
 static int vc_gate_args(const ry_vc* vc, const float* wave, int n_samples, int hop, int fft_length, const float* feat, int n_frames) {
@@ -527,6 +546,62 @@ int ry_vc_enqueue_device(ry_vc* vc, const float* x_eff_dev, const int* row_of_de
     RT_TRY(rt::event_record(sl.ev_done, st2));
     sl.used = true;
     vc->split_eff = -1;
+    return RY_OK;
+}
+
+// ry_vc_submit_wave for a wave (float32) and a feature block that are already on the card -- what ry_crepe_track and
+// ry_analysis_extract_resident left there -- with the results left on the card too: nothing is staged, no wave / feature / mc / sp copy crosses
+// the bus; the count (it picks the stage-1 plan) and the mask bytes are the only copies to the host, and the call waits for them once.  The
+// slots and the lanes are taken round robin as ry_vc_enqueue_device takes them; ry_vc_set_discard applies as it does there.
+// Order: the stage-1 stream waits (ev_in) for everything queued on the CONTEXT stream at the time of the call -- the stream ry_crepe_track and
+// the analysis enqueue on -- so inputs produced there need no wait by the caller; inputs produced on any other stream must be complete
+// (ry_sync).  Before it returns the call makes the context stream wait for the window's end (the slot's ev_done): what is enqueued on the
+// context stream afterwards (ry_mask_rows, ry_synth_run / ry_synth_push with on_device = 1, ry_dev_download) sees mc_out_dev and sp_out_dev
+// complete.  A caller that reads them from another stream waits with ry_sync.
+int ry_vc_enqueue_wave_device(ry_vc* vc, const float* wave_dev, int n_samples, int hop, int fft_length, float p_effective, float p_all,
+                              const float* feat_dev, int n_frames, float sp_floor, float* mc_out_dev, float* sp_out_dev,
+                              unsigned char* mask_dev_out, unsigned char* effective_out, int* n_eff_out) {
+    RY_TRY(vc_gate_args(vc, wave_dev, n_samples, hop, fft_length, feat_dev, n_frames));
+    if (!mc_out_dev || !sp_out_dev || !mask_dev_out || !effective_out || !n_eff_out) return fail(RY_EINVAL, "null argument");
+    RT_TRY(rt::set_device(vc->s1->ctx->device));
+    VcSlot& sl = vc->slot[vc->dev_count % vc->ring];
+    ry_net *s1 = vc->lane1(vc->dev_count % vc->ring), *s2 = vc->lane2(vc->dev_count % vc->ring);
+    Stage1On on_lane(vc, s1, s2);
+    if (sl.ticket >= 0) return fail(RY_ESTATE, "ring slot %d is held by ticket %d: ry_vc_wait it first", vc->dev_count % vc->ring, sl.ticket);
+    RY_TRY(vc_reserve_slot(vc, sl, n_frames, n_frames));
+    ++vc->dev_count;
+    ry_stream_t st1 = s1->stream, st2 = s2->stream, stc = s1->ctx->stream;
+    vc->note(st1, st2);
+    if (sl.used) RT_TRY(rt::stream_wait_event(st1, sl.ev_done));                        // the slot's previous window has left d_x / d_row / d_sp
+    if (stc != st1) { RT_TRY(rt::event_record(vc->ev_in, stc)); RT_TRY(rt::stream_wait_event(st1, vc->ev_in)); }
+    int n_eff = 0;
+    RY_TRY(vc_gate_launch(s1, sl, wave_dev, n_samples, hop, fft_length, p_effective, p_all, feat_dev, n_frames, mask_dev_out, &n_eff));
+    memcpy(effective_out, sl.h_mask, (size_t)n_frames);
+    *n_eff_out = n_eff;
+    if (n_eff > 0) RY_TRY(ry_ac_convert(s1, sl.d_x, sl.d_y1, 1, n_eff, 1));
+    RY_TRY(vc_enqueue_mid(vc, s1, sl.d_y1, sl.d_row, n_eff, n_frames, sp_floor, mc_out_dev, sl.d_sp));
+    RY_TRY(vc_join(sl.ev_mid, st1, st2));
+    RY_TRY(vc_run_stage2(vc, s2, sl.d_sp, sp_out_dev, n_frames));
+    RT_TRY(rt::event_record(sl.ev_done, st2));
+    if (stc != st2) RT_TRY(rt::stream_wait_event(stc, sl.ev_done));
+    sl.used = true;
+    vc->split_eff = -1;
+    return RY_OK;
+}
+
+// combine_silent of rows that are already in place (ry_vc_kernels.h): rows k0 .. k1 - 1 of rows_dev[n][cols] whose mask byte is 0 become
+// +0.0f.  Enqueue only, on `stream` (null: the context stream); nothing is waited for.
+int ry_mask_rows(ry_ctx* ctx, float* rows_dev, const unsigned char* mask_dev, int n, int cols, int k0, int k1, void* stream) {
+    if (!ctx || !rows_dev || !mask_dev) return fail(RY_EINVAL, "null argument");
+    if (n < 1 || cols < 1) return fail(RY_EINVAL, "bad sizes (%d rows of %d)", n, cols);
+    if (k0 < 0 || k0 > k1 || k1 > n) return fail(RY_EINVAL, "rows %d .. %d of %d", k0, k1, n);
+    if (k0 == k1) return RY_OK;
+    RT_TRY(rt::set_device(ctx->device));
+    const ry_stream_t st = stream ? (ry_stream_t)stream : ctx->stream;
+    RyMaskRowsParams p;
+    p.rows = rows_dev; p.mask = mask_dev; p.cols = cols; p.k0 = k0; p.k1 = k1;
+    RY_LAUNCH(ry_mask_rows, dim3((unsigned)((k1 - k0 + 3) / 4)), 256, st, p);
+    RT_TRY(rt::last_error());
     return RY_OK;
 }
 

@@ -1,5 +1,5 @@
-// ry_vc_kernels.h -- the small kernels of the window call (ry_vc.cpp): combine_silent (row scatter), the silence gate
-// (frame power in numpy's summation order, gate + ordered compaction) and decode_spectrogram (mc2sp = exp(mc @ M)).
+// ry_vc_kernels.h -- the small kernels of the window call (ry_vc.cpp): combine_silent (row scatter; ry_mask_rows for rows that are already
+// in place), the silence gate (frame power in numpy's summation order, gate + ordered compaction) and decode_spectrogram (mc2sp = exp(mc @ M)).
 // Reference: /root/reference/realtime_voice_conversion/yukarin_wrapper/voice_changer.py:27-39.
 #pragma once
 #include "ry_dev.h"
@@ -18,6 +18,26 @@ RY_KERNEL(256) void ry_scatter_rows(RyScatterParams p) {       // dst[row_of[i]]
     if (idx >= (long long)p.n_src * p.cols) return;
     const int c = (int)(idx % p.cols), i = (int)(idx / p.cols);
     p.dst[(size_t)p.row_of[i] * p.cols + c] = p.src[idx];
+}
+
+// `combine_silent` for rows that never left their block (the aperiodicity of a resident chain: AcousticConverter.convert passes ap through,
+// combine_silent leaves zeros on the frames the gate cut): rows k0 .. k1 - 1 of rows[n][cols] whose mask byte is 0 become +0.0f, the others
+// and everything outside the range keep their bits.  One wave per row, four rows per workgroup; a silent row is written as scalars up to the
+// first 16-byte boundary, 128-bit stores over the whole quads, scalars for what is left (cols = 513: rows start at every alignment).
+struct RyMaskRowsParams { float* rows; const unsigned char* mask; int cols, k0, k1; };
+
+RY_KERNEL(256) void ry_mask_rows(RyMaskRowsParams p) {
+    const int lane = (int)threadIdx.x & 63;
+    const long long r = (long long)p.k0 + (long long)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+    if (r >= p.k1 || p.mask[r] != 0) return;                    // wave-uniform
+    float* row = p.rows + (size_t)r * p.cols;
+    int head = (int)((4 - ((reinterpret_cast<unsigned long long>(row) >> 2) & 3)) & 3);     // floats in front of the first 16-byte boundary
+    if (head > p.cols) head = p.cols;
+    const int quads = (p.cols - head) >> 2, tail = head + 4 * quads;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    if (lane < head) row[lane] = 0.f;
+    for (int q = lane; q < quads; q += 64) ry_st4(row + head + 4 * q, zero);
+    if (tail + lane < p.cols) row[tail + lane] = 0.f;          // at most three
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -72,6 +72,12 @@ class Context(object):
         assert a.flags['C_CONTIGUOUS'] and a.dtype.itemsize == 4
         self.lib.check(self.lib.dll.ry_dev_download(self.handle, ctypes.cast(a.ctypes.data, ctypes.POINTER(ctypes.c_float)), _lib._fptr(int(ptr)), a.size))
 
+    def mask_rows(self, rows_ptr: int, mask_ptr: int, n: int, cols: int, k0: int = 0, k1: Optional[int] = None, stream: Optional[int] = None):
+        """`combine_silent` of float32 rows that stay on the card (`ry_mask_rows`): rows [k0, k1) of the (n, cols) block at `rows_ptr` whose byte in
+        the mask at `mask_ptr` is 0 become +0.0 in place.  Enqueued on `stream` (default: the context stream), nothing is waited for."""
+        self.lib.check(self.lib.dll.ry_mask_rows(self.handle, _lib._fptr(int(rows_ptr)), ctypes.cast(ctypes.c_void_p(int(mask_ptr)), ctypes.POINTER(ctypes.c_ubyte)),
+                                                 int(n), int(cols), int(k0), int(n if k1 is None else k1), ctypes.c_void_p(stream or 0)))
+
     def mc2sp(self, mc, mtx, floor: float = 0.0):
         """`decode_spectrogram` on the device: exp(mc (N, M) @ mtx (M, F)) + floor."""
         mc = numpy.ascontiguousarray(mc, dtype=numpy.float32)
@@ -294,6 +300,20 @@ class VcCore(object):
         self.lib.check(self.lib.dll.ry_vc_enqueue_device(
             self.handle, _lib._fptr(int(x_ptr)), ctypes.cast(ctypes.c_void_p(int(rows_ptr)), ctypes.POINTER(ctypes.c_int)),
             int(n_eff), int(n_frames), float(sp_floor), _lib._fptr(int(mc_ptr)), _lib._fptr(int(sp_ptr))))
+
+    def enqueue_wave_device(self, wave_ptr: int, n_samples: int, hop: int, fft_length: int, p_effective: float, p_all: float, feat_ptr: int,
+                            n_frames: int, mc_ptr: int, sp_ptr: int, mask_ptr: int, sp_floor: float = 1e-16):
+        """`ry_vc_enqueue_wave_device`: `submit_wave` on a float32 wave and a (n_frames, in_ch) feature block that are already on the card, mc / sp /
+        the mask bytes left on the card -> (effective (n_frames,) bool, n_eff).  Waits for the count only; the context stream is ordered behind the
+        window, so what is enqueued on it afterwards reads complete rows."""
+        mask = numpy.empty(int(n_frames), dtype=numpy.uint8)
+        n_eff = ctypes.c_int(0)
+        ub = ctypes.POINTER(ctypes.c_ubyte)
+        self.lib.check(self.lib.dll.ry_vc_enqueue_wave_device(
+            self.handle, _lib._fptr(int(wave_ptr)), int(n_samples), int(hop), int(fft_length), float(p_effective), float(p_all),
+            _lib._fptr(int(feat_ptr)), int(n_frames), float(sp_floor), _lib._fptr(int(mc_ptr)), _lib._fptr(int(sp_ptr)),
+            ctypes.cast(ctypes.c_void_p(int(mask_ptr)), ub), mask.ctypes.data_as(ub), ctypes.byref(n_eff)))
+        return mask.astype(bool), int(n_eff.value)
 
     def enqueue_device_batch(self, x_ptr: int, rows_ptr: int, n_eff, n_frames: int, mc_ptr: int, sp_ptr: int, sp_floor: float = 1e-16):
         """`ry_vc_enqueue_device_batch`: len(n_eff) windows of n_frames each, device pointers, nothing waited for."""

@@ -129,6 +129,19 @@ class Analyzer(DeviceHandle):
         lib.check(lib.dll.ry_analysis_extract_dev(h, _lib._fptr(int(wave_dev)), n_samples, as_d(f0_dev), as_d(t_dev), n, float(threshold), *(out_sp + out_ap)))
         return tuple(got[k] for k in want)
 
+    def extract_resident(self, wave_dev: int, n_samples: int, f0_dev: int, t_dev: int, n: int, mc32_dev: int, sp32_dev: int, ap32_dev: int,
+                         threshold: float = 0.85) -> None:
+        """`run_device` with device outputs only (`ry_analysis_extract_resident`): float32 `mc` (n, order + 1), `sp` and `ap` (n, 513) rows written to
+        the blocks at the three addresses -- the bits of `run_device(...)`'s float64 rows cast with `astype(float32)`.  Nothing but the verdict of the
+        track check comes back to the host; a refused track raises and leaves the blocks untouched."""
+        lib, h = self._get()
+        n, n_samples = int(n), int(n_samples)
+        if n > 0 and n_samples == 0:
+            raise ValueError('an empty wave cannot be analysed at %d frames' % n)
+        as_d = lambda a: ctypes.cast(ctypes.c_void_p(a), _DP)
+        lib.check(lib.dll.ry_analysis_extract_resident(h, _lib._fptr(int(wave_dev)), n_samples, as_d(f0_dev), as_d(t_dev), n, float(threshold),
+                                                       _lib._fptr(int(mc32_dev)), _lib._fptr(int(sp32_dev)), _lib._fptr(int(ap32_dev))))
+
     def run_device_many(self, wave_dev: int, sample_offsets, f0_dev: int, t_dev: int, frame_offsets, want=('sp', 'mc', 'ap', 'coded_ap'),
                         device_rows: bool = False, threshold: float = 0.85):
         """`run_device` on the waves and tracks `CrepeModel.track_many(..., device=True)` left on the card (`ry_analysis_extract_many_dev`): the waves
