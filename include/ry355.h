@@ -207,6 +207,40 @@ int ry_vc_enqueue_wave_device(ry_vc* vc, const float* wave_dev, int n_samples, i
  * whose byte in mask_dev [n] is 0 become +0.0f in place; every other row keeps its bits.  Enqueue only, on `stream` (a HIP stream; null: the
  * context stream); nothing is waited for.  Refused: null pointers, n < 1, cols < 1, a range outside 0 <= k0 <= k1 <= n. */
 int ry_mask_rows(ry_ctx* ctx, float* rows_dev, const unsigned char* mask_dev, int n, int cols, int k0, int k1, void* stream);
+/* Rows picked by an index table, packed back to back: dst_dev [n_out][cols] row j = rows_dev [n_rows][cols] row src_row_dev[j] (an int table on the
+ * card), or +0.0f where mask_dev [n_rows] (may be null: every row is kept) holds 0 for that source row -- `combine_silent` folded into the pick.
+ * One launch packs the rows [front, n_b - back) of every stream of a call in the order ry_synth_bank_push (on_device = 1) reads them.  Source
+ * and destination rows may start at any 4-byte alignment, independently; nothing outside a row is read or written; an index outside
+ * 0 .. n_rows - 1 reads nothing and gives a row of zeros.  Source and destination must not overlap.  Enqueue only, on `stream` (null: the
+ * context stream).  Refused: null pointers (the mask excepted), n_rows < 1, cols < 1, n_out < 0; n_out = 0 does nothing. */
+int ry_gather_rows(ry_ctx* ctx, const float* rows_dev, int n_rows, int cols, const int* src_row_dev, const unsigned char* mask_dev, float* dst_dev,
+                   int n_out, void* stream);
+/* `separate_effective` of n_waves >= 1 waves that are on the card with ONE launch pair and ONE wait: wave i has the samples
+ * [sample_offsets[i], sample_offsets[i + 1]) of wave_dev and the frames [frame_offsets[i], frame_offsets[i + 1]) of feat_dev [sum n][in_ch] (HOST
+ * arrays of n_waves + 1 entries, starting at 0, ascending: what ry_crepe_track_many_buffers reports).  Frame powers: one wave of lanes per frame
+ * over all waves, reflected at the ends of the frame's own wave; gate: one workgroup per wave, the maximum (the top_db clamp) over that wave's own
+ * powers.  mask_dev_out (device) / effective_out (host) [sum n]: the masks in wave order; n_eff_out [n_waves]; x_eff_dev_out [sum n][in_ch] /
+ * row_of_dev_out [sum n] (device; both null: blocks of the core): wave i's effective rows and their frame indices, counted from the wave's first
+ * frame, from row frame_offsets[i] on.  Everything of wave i has the bits of ry_vc_gate on wave i alone.  The stage-1 stream waits for the context
+ * stream first.  Refused, nothing launched: null pointers, n_waves < 1 or > 65536, offsets that do not start at 0 or do not ascend, hop < 1, an fft_length
+ * ry_vc_gate refuses, more than 2^31 - 1 samples or 2^22 frames in all (the message names the wave). */
+int ry_vc_gate_waves_device(ry_vc* vc, const float* wave_dev, const long long* sample_offsets, const int* frame_offsets, int n_waves, int hop,
+                            int fft_length, float p_effective, float p_all, const float* feat_dev, unsigned char* mask_dev_out,
+                            unsigned char* effective_out, int* n_eff_out, float* x_eff_dev_out, int* row_of_dev_out);
+/* ry_vc_enqueue_wave_device for n_waves waves in ONE call: the one gate of ry_vc_gate_waves_device (one wait for all counts and masks), then,
+ * wave by wave in order, the rest of the single call on that wave's rows: stage 1 under the plan its own count picks (none for a wave without an
+ * effective frame), scatter, mc2sp, stage 2.  Ring slots and lanes are taken round robin as a sequence of single calls takes them; a slot that
+ * comes round again within the call is ordered behind its previous window on the stream, so n_waves may exceed the ring.  feat_dev [sum n][in_ch],
+ * mc_out_dev [sum n][M], sp_out_dev [sum n][F], mask_dev_out / effective_out [sum n], n_eff_out [n_waves]; ry_vc_set_discard applies to every
+ * window (the discarded rows of each wave's part of sp_out_dev stay untouched).  mc, sp, mask and count of wave i have the bits of
+ * ry_vc_enqueue_wave_device on wave i alone, whatever the other waves hold and wherever wave i stands.  Stream order as in the single call: the
+ * gate waits for the context stream, the context stream waits for the end of every window before the call returns.  Refused, nothing launched:
+ * what ry_vc_gate_waves_device refuses, null outputs, a ring slot of the call held by a ticket (RY_ESTATE).  That covers the arguments only: a
+ * failure after the gate (a slot that cannot grow, a launch error) ends the call as it ends a sequence of single calls -- the windows queued so far
+ * stay queued, the slots they took stay taken and the outputs are partly written. */
+int ry_vc_enqueue_waves_device(ry_vc* vc, const float* wave_dev, const long long* sample_offsets, const int* frame_offsets, int n_waves, int hop,
+                               int fft_length, float p_effective, float p_all, const float* feat_dev, float sp_floor, float* mc_out_dev,
+                               float* sp_out_dev, unsigned char* mask_dev_out, unsigned char* effective_out, int* n_eff_out);
 /* `AcousticConverter.decode_spectrogram` alone (host pointers): sp [n][bins] = exp(mc [n][m] @ mtx [m][bins]) + floor. */
 int ry_mc2sp(ry_ctx* ctx, const float* mc, const float* mtx, int n, int m, int bins, float floor, float* sp);
 
@@ -543,6 +577,12 @@ int ry_analysis_extract_many_dev(ry_analysis* analysis, const float* x32_dev, co
  * ry_analysis_extract_dev, and a null output; a refused call writes nothing.  The call drains the context stream before it returns. */
 int ry_analysis_extract_resident(ry_analysis* analysis, const float* x32_dev, long long x_len, const double* f0_dev, const double* t_dev, int n,
                                  double threshold, float* mc32_dev_out, float* sp32_dev_out, float* ap32_dev_out);
+/* ry_analysis_extract_many_dev with the outputs of ry_analysis_extract_resident: mc32_dev_out [sum n][order + 1], sp32_dev_out [sum n][513] and
+ * ap32_dev_out [sum n][513] float32 on the DEVICE, rows in wave order; nothing but the ONE verdict of the track check goes to the host.  Rows of wave i
+ * have the bits ry_analysis_extract_resident writes for wave i alone.  Refusals: those of the two calls it combines; a refused call writes nothing. */
+int ry_analysis_extract_many_resident(ry_analysis* analysis, const float* x32_dev, const long long* sample_offsets, const double* f0_dev,
+                                      const double* t_dev, const int* frame_offsets, int n_waves, double threshold,
+                                      float* mc32_dev_out, float* sp32_dev_out, float* ap32_dev_out);
 /* the number of bands B (1 at 16 kHz, 3 at 24 kHz); negative (an error code) where D4C is not built for the handle's rate */
 int ry_analysis_d4c_bands(ry_analysis* analysis);
 /* tests: what the last recorded (ry_analysis_debug_record) D4C run decided.  ints_out [n][9]: half length of the Love-Train window, of the other

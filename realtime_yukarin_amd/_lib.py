@@ -71,6 +71,7 @@ ABI_SYMBOLS = (
     'ry_analysis_create', 'ry_analysis_destroy', 'ry_analysis_run', 'ry_analysis_sp2mc', 'ry_analysis_debug_record', 'ry_analysis_debug_ints', 'ry_analysis_debug_poison',
     'ry_analysis_d4c', 'ry_analysis_extract', 'ry_analysis_d4c_bands', 'ry_analysis_debug_d4c', 'ry_analysis_extract_dev',
     'ry_analysis_extract_resident', 'ry_vc_enqueue_wave_device', 'ry_mask_rows',
+    'ry_analysis_extract_many_resident', 'ry_vc_gate_waves_device', 'ry_vc_enqueue_waves_device', 'ry_gather_rows',
 )
 
 
@@ -242,6 +243,11 @@ class Ry355Lib(object):
         d.ry_analysis_extract_resident.argtypes = [_VP, _FP, _LL, _DP, _DP, _CI, ctypes.c_double, _FP, _FP, _FP]
         d.ry_vc_enqueue_wave_device.argtypes = [_VP, _FP, _CI, _CI, _CI, ctypes.c_float, ctypes.c_float, _FP, _CI, ctypes.c_float, _FP, _FP, _UB, _UB, _IP]
         d.ry_mask_rows.argtypes = [_VP, _FP, _UB, _CI, _CI, _CI, _CI, _VP]
+        d.ry_analysis_extract_many_resident.argtypes = [_VP, _FP, ctypes.POINTER(_LL), _DP, _DP, _IP, _CI, ctypes.c_double, _FP, _FP, _FP]
+        d.ry_gather_rows.argtypes = [_VP, _FP, _CI, _CI, _IP, _UB, _FP, _CI, _VP]
+        d.ry_vc_gate_waves_device.argtypes = [_VP, _FP, ctypes.POINTER(_LL), _IP, _CI, _CI, _CI, ctypes.c_float, ctypes.c_float, _FP, _UB, _UB, _IP, _FP, _IP]
+        d.ry_vc_enqueue_waves_device.argtypes = [_VP, _FP, ctypes.POINTER(_LL), _IP, _CI, _CI, _CI, ctypes.c_float, ctypes.c_float, _FP, ctypes.c_float,
+                                                 _FP, _FP, _UB, _UB, _IP]
         d.ry_analysis_d4c_bands.argtypes = [_VP]
         d.ry_analysis_debug_d4c.argtypes = [_VP, ctypes.POINTER(_LL), _DP, _CI, _IP]
         d.ry_net_profile_window.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RyKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]

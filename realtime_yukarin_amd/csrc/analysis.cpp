@@ -318,12 +318,12 @@ int ry_analysis_extract_resident(ry_analysis* s, const float* x32_dev, long long
     return extract_dev(s, x32_dev, x_len, f0_dev, t_dev, n, &one, 1, o);       // no host row is named: the verdict is the only copy to the host
 }
 
-int ry_analysis_extract_many_dev(ry_analysis* s, const float* x32_dev, const long long* sample_offsets, const double* f0_dev, const double* t_dev,
-                                 const int* frame_offsets, int n_waves, double threshold,
-                                 double* sp64_out, float* sp32_dev_out, double* mc_out, double* ap64_out, float* ap32_dev_out, double* coded_out) {
-    Outputs o;
-    o.sp64 = sp64_out; o.sp32_dev = sp32_dev_out; o.mc = mc_out;
-    o.d4c = true; o.threshold = threshold; o.ap64 = ap64_out; o.ap32_dev = ap32_dev_out; o.coded = coded_out;
+}  // extern "C"
+
+namespace {
+// the waves and tracks ry_crepe_track_many left on the card: the spans of the offsets, one check of the whole track, the frame kernels per wave
+int extract_many(ry_analysis* s, const float* x32_dev, const long long* sample_offsets, const double* f0_dev, const double* t_dev,
+                 const int* frame_offsets, int n_waves, const Outputs& o, bool device_rows_only) {
     RY_TRY(check_handle(s, "analysis"));
     if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
     if (!sample_offsets || !frame_offsets) return fail(RY_EINVAL, "null offsets");
@@ -341,9 +341,31 @@ int ry_analysis_extract_many_dev(ry_analysis* s, const float* x32_dev, const lon
     const int n = frame_offsets[n_waves];
     bool empty = false;
     RY_TRY(check_call(s, x_len, n, true, o, &empty));                   // never empty: every wave has a sample and a frame
+    if (device_rows_only && (!o.mc32_dev || !o.sp32_dev || !o.ap32_dev)) return fail(RY_EINVAL, "null output rows");
     if (!x32_dev) return fail(RY_EINVAL, "null wave");
     if (!f0_dev || !t_dev) return fail(RY_EINVAL, "null f0 / t");
     return extract_dev(s, x32_dev, x_len, f0_dev, t_dev, n, spans.data(), n_waves, o);
+}
+}  // namespace
+
+extern "C" {
+
+int ry_analysis_extract_many_dev(ry_analysis* s, const float* x32_dev, const long long* sample_offsets, const double* f0_dev, const double* t_dev,
+                                 const int* frame_offsets, int n_waves, double threshold,
+                                 double* sp64_out, float* sp32_dev_out, double* mc_out, double* ap64_out, float* ap32_dev_out, double* coded_out) {
+    Outputs o;
+    o.sp64 = sp64_out; o.sp32_dev = sp32_dev_out; o.mc = mc_out;
+    o.d4c = true; o.threshold = threshold; o.ap64 = ap64_out; o.ap32_dev = ap32_dev_out; o.coded = coded_out;
+    return extract_many(s, x32_dev, sample_offsets, f0_dev, t_dev, frame_offsets, n_waves, o, false);
+}
+
+int ry_analysis_extract_many_resident(ry_analysis* s, const float* x32_dev, const long long* sample_offsets, const double* f0_dev, const double* t_dev,
+                                      const int* frame_offsets, int n_waves, double threshold,
+                                      float* mc32_dev_out, float* sp32_dev_out, float* ap32_dev_out) {
+    Outputs o;
+    o.mc32_dev = mc32_dev_out; o.sp32_dev = sp32_dev_out; o.ap32_dev = ap32_dev_out;
+    o.d4c = true; o.threshold = threshold;
+    return extract_many(s, x32_dev, sample_offsets, f0_dev, t_dev, frame_offsets, n_waves, o, true);      // no host row is named: one verdict comes back
 }
 
 int ry_analysis_d4c_bands(ry_analysis* s) {

@@ -113,7 +113,21 @@ struct ry_vc {
     BatchSet bset[2];
     int b_turn = 0;
     bool b_ev = false;
-    void free_pinned() { for (VcSlot& sl : slot) sl.free_pinned(); }
+    // several waves per call (ry_vc_gate_waves_device / ry_vc_enqueue_waves_device): the blocks of the ONE gate -- the wave table, a power per wave
+    // frame, the compacted rows and their frame indices (wave i's region starts at its first frame), and the block the host reads with one
+    // copy (n_waves counts, then the mask bytes).  One set: a call reads them after the context stream has passed the end of every window of the
+    // call before it (ev_in), and the host has waited for the gate before the first window is queued.
+    struct WaveSet {
+        Arena bufs;
+        RyWaveSeg *d_seg = nullptr, *h_seg = nullptr;
+        float *d_pow = nullptr, *d_x = nullptr;
+        int *d_row = nullptr, *d_host = nullptr, *h_host = nullptr;
+        int cap_waves = 0, cap_pow = 0, cap_frames = 0;
+        std::vector<void*> pinned;
+        void release() { bufs.release(); for (void* q : pinned) rt::hfree(q); pinned.clear(); cap_waves = cap_pow = cap_frames = 0; }
+    };
+    WaveSet wset;
+    void free_pinned() { for (VcSlot& sl : slot) sl.free_pinned(); wset.release(); }
 };
 
 // COMPACT_A on the caller's own pair (lane 0; the batch and the split calls): its stage-1 handle enqueues on the stage-2 stream for the
@@ -602,6 +616,201 @@ int ry_mask_rows(ry_ctx* ctx, float* rows_dev, const unsigned char* mask_dev, in
     p.rows = rows_dev; p.mask = mask_dev; p.cols = cols; p.k0 = k0; p.k1 = k1;
     RY_LAUNCH(ry_mask_rows, dim3((unsigned)((k1 - k0 + 3) / 4)), 256, st, p);
     RT_TRY(rt::last_error());
+    return RY_OK;
+}
+
+// Rows picked by an index table on the card, packed back to back (ry_vc_kernels.h): dst_dev[j][:] = rows_dev[src_row_dev[j]][:] for j < n_out, or
+// +0.0f where mask_dev (may be null) holds 0 for the source row.  Enqueue only, on `stream` (null: the context stream); nothing is waited for.
+int ry_gather_rows(ry_ctx* ctx, const float* rows_dev, int n_rows, int cols, const int* src_row_dev, const unsigned char* mask_dev, float* dst_dev,
+                   int n_out, void* stream) {
+    if (!ctx || !rows_dev || !src_row_dev || !dst_dev) return fail(RY_EINVAL, "null argument");
+    if (n_rows < 1 || cols < 1) return fail(RY_EINVAL, "bad sizes (%d rows of %d)", n_rows, cols);
+    if (n_out < 0) return fail(RY_EINVAL, "%d output rows", n_out);
+    if (n_out == 0) return RY_OK;
+    RT_TRY(rt::set_device(ctx->device));
+    const ry_stream_t st = stream ? (ry_stream_t)stream : ctx->stream;
+    RyGatherRowsParams p;
+    p.rows = rows_dev; p.src_row = src_row_dev; p.mask = mask_dev; p.dst = dst_dev; p.n_rows = n_rows; p.n_out = n_out; p.cols = cols;
+    RY_LAUNCH(ry_gather_rows, dim3((unsigned)((n_out + 3) / 4)), 256, st, p);
+    RT_TRY(rt::last_error());
+    return RY_OK;
+}
+
+}  // extern "C"
+
+// ---- several waves per call: one gate over a table of waves, then every wave's window with that wave's own bits -------------------------------
+struct VcWaves { std::vector<RyWaveSeg> seg; int total_frames = 0, total_wave_frames = 0; };
+
+static int vc_waves_args(const ry_vc* vc, const float* wave_dev, const long long* sample_offsets, const int* frame_offsets, int n_waves, int hop,
+                         int fft_length, const float* feat_dev, VcWaves* out) {
+    if (!vc || !wave_dev || !feat_dev || !sample_offsets || !frame_offsets) return fail(RY_EINVAL, "null argument");
+    if (n_waves < 1 || n_waves > (1 << 16)) return fail(RY_EINVAL, "n_waves must be in 1..65536 (got %d)", n_waves);
+    if (hop < 1) return fail(RY_EINVAL, "bad sizes (hop %d)", hop);
+    if (fft_length < 128 || fft_length > 1024 || (fft_length & (fft_length - 1)))
+        return fail(RY_EINVAL, "the device gate takes fft_length 128 .. 1024, a power of two (got %d): use the host gate", fft_length);
+    if (sample_offsets[0] != 0 || frame_offsets[0] != 0)
+        return fail(RY_EINVAL, "the offsets start at %lld / %d, not at 0", sample_offsets[0], frame_offsets[0]);
+    out->seg.resize((size_t)n_waves);
+    long long slots = 0;
+    for (int i = 0; i < n_waves; ++i) {
+        const long long ns = sample_offsets[i + 1] - sample_offsets[i];
+        const long long nf = (long long)frame_offsets[i + 1] - frame_offsets[i];
+        if (ns < 1 || nf < 1) return fail(RY_EINVAL, "wave %d: bad sizes (%lld samples, %lld frames): the offsets must ascend", i, ns, nf);
+        if (sample_offsets[i + 1] > 0x7fffffffLL) return fail(RY_EINVAL, "wave %d ends at sample %lld: at most 2^31 - 1 in one call", i, sample_offsets[i + 1]);
+        if (frame_offsets[i + 1] > (1 << 22)) return fail(RY_EINVAL, "wave %d ends at frame %d: at most 2^22 in one call", i, frame_offsets[i + 1]);
+        RyWaveSeg& s = out->seg[(size_t)i];
+        s.s0 = (int)sample_offsets[i]; s.n_samples = (int)ns; s.f0 = frame_offsets[i]; s.n_frames = (int)nf;
+        s.p0 = (int)slots; s.n_wave_frames = (int)(ns / hop) + 1;         // librosa: 1 + (len + 2 * (fft / 2) - fft) / hop
+        s.r0 = s.f0; s.pad = 0;
+        slots += s.n_wave_frames;
+        if (slots > (1LL << 30)) return fail(RY_EINVAL, "wave %d: more than 2^30 wave frames in one call", i);
+    }
+    out->total_frames = frame_offsets[n_waves];
+    out->total_wave_frames = (int)slots;
+    return RY_OK;
+}
+
+// the call-level blocks, grown on demand (RY_POISON: NaN patterns over what the gate is about to write); on the context stream, before ev_in
+static int vc_waves_reserve(ry_vc* vc, const VcWaves& w) {
+    ry_vc::WaveSet& ws = vc->wset;
+    ry_ctx* ctx = vc->s1->ctx;
+    const int n_waves = (int)w.seg.size(), cin = vc->s1->desc.in_ch;
+    if (n_waves > ws.cap_waves || w.total_wave_frames > ws.cap_pow || w.total_frames > ws.cap_frames) {
+        vc->sync_lanes();                                           // queued windows may still read the old blocks
+        RT_TRY(rt::stream_sync(ctx->stream));
+        const int cw = std::max(n_waves + n_waves / 4 + 8, ws.cap_waves);
+        const int cp = std::max(w.total_wave_frames + w.total_wave_frames / 4 + 1024, ws.cap_pow);
+        const int cf = std::max(w.total_frames + w.total_frames / 4 + 64, ws.cap_frames);
+        ws.release();
+        float* q = nullptr;
+        RY_TRY(ws.bufs.alloc(&q, (size_t)cw * (sizeof(RyWaveSeg) / sizeof(float)))); ws.d_seg = (RyWaveSeg*)q;
+        RY_TRY(ws.bufs.alloc(&ws.d_pow, (size_t)cp));
+        RY_TRY(ws.bufs.alloc(&ws.d_x, (size_t)cf * cin));
+        RY_TRY(ws.bufs.alloc(&q, (size_t)cf)); ws.d_row = (int*)q;
+        RY_TRY(ws.bufs.alloc(&q, (size_t)cw + (size_t)cf / 4 + 4)); ws.d_host = (int*)q;
+        void* h = nullptr;
+        rt::err_t e = rt::hmalloc(&h, (size_t)cw * sizeof(RyWaveSeg));
+        if (e == 0) { ws.pinned.push_back(h); ws.h_seg = (RyWaveSeg*)h; e = rt::hmalloc(&h, ((size_t)cw + (size_t)cf / 4 + 4) * sizeof(int)); }
+        if (e != 0) return fail(RY_ENOMEM, "pinned host allocation failed: %s", rt::err_str(e));
+        ws.pinned.push_back(h); ws.h_host = (int*)h;
+        ws.cap_waves = cw; ws.cap_pow = cp; ws.cap_frames = cf;
+    }
+    RY_TRY(poison_fill(ctx, ws.d_pow, (size_t)ws.cap_pow));
+    RY_TRY(poison_fill(ctx, ws.d_x, (size_t)ws.cap_frames * cin));
+    RY_TRY(poison_fill(ctx, (float*)ws.d_row, (size_t)ws.cap_frames));
+    RY_TRY(poison_fill(ctx, (float*)ws.d_host, (size_t)ws.cap_waves + (size_t)ws.cap_frames / 4 + 4));
+    return RY_OK;
+}
+
+// table up, frame powers over all waves, one gate workgroup per wave, counts and masks back with one copy and one wait
+static int vc_gate_waves_launch(ry_vc* vc, ry_net* s1, const float* d_wave, const VcWaves& w, int hop, int fft_length, float p_effective, float p_all,
+                                const float* d_feat, float* d_x, int* d_row, unsigned char* d_mask, unsigned char* effective_out, int* n_eff_out) {
+    ry_vc::WaveSet& ws = vc->wset;
+    const int n_waves = (int)w.seg.size();
+    ry_stream_t st1 = s1->stream;
+    memcpy(ws.h_seg, w.seg.data(), (size_t)n_waves * sizeof(RyWaveSeg));
+    RT_TRY(rt::h2d(ws.d_seg, ws.h_seg, (size_t)n_waves * sizeof(RyWaveSeg), st1));
+    Launcher Lc{s1, s1->ctx, st1, nullptr, nullptr};
+    RyFramePowerManyParams fp;
+    fp.wave = d_wave; fp.seg = ws.d_seg; fp.n_waves = n_waves; fp.hop = hop; fp.fft = fft_length; fp.total_wave_frames = w.total_wave_frames;
+    fp.power = ws.d_pow;
+    dim3 fg((unsigned)((w.total_wave_frames + 3) / 4));
+    RY_TRY(Lc.begin("ry_frame_power_many", "separate_effective", 0, 0, fg));
+    RY_LAUNCH(ry_frame_power_many, fg, 256, st1, fp);
+    RY_TRY(Lc.end());
+    RyGateManyParams gp;
+    gp.power = ws.d_pow; gp.seg = ws.d_seg; gp.p_eff = p_effective; gp.p_all = p_all; gp.feat = d_feat; gp.cin = s1->desc.in_ch;
+    gp.x_eff = d_x; gp.row_of = d_row; gp.mask = d_mask; gp.host = ws.d_host; gp.n_waves = n_waves;
+    RY_TRY(Lc.begin("ry_gate_compact_many", "separate_effective", 0, 0, dim3((unsigned)n_waves)));
+    RY_LAUNCH(ry_gate_compact_many, dim3((unsigned)n_waves), 1024, st1, gp);
+    RY_TRY(Lc.end());
+    RT_TRY(rt::d2h(ws.h_host, ws.d_host, (size_t)n_waves * sizeof(int) + (size_t)w.total_frames, st1));
+    RT_TRY(rt::stream_sync(st1));                               // the counts pick the stage-1 plans
+    for (int i = 0; i < n_waves; ++i)
+        if (ws.h_host[i] < 0 || ws.h_host[i] > w.seg[(size_t)i].n_frames)
+            return fail(RY_EHIP, "the gate returned %d effective frames of %d for wave %d", ws.h_host[i], w.seg[(size_t)i].n_frames, i);
+    memcpy(n_eff_out, ws.h_host, (size_t)n_waves * sizeof(int));
+    memcpy(effective_out, ws.h_host + n_waves, (size_t)w.total_frames);
+    return RY_OK;
+}
+
+extern "C" {
+
+// `separate_effective` of n_waves waves that are on the card, in one launch pair and one wait: wave i has the samples
+// [sample_offsets[i], sample_offsets[i + 1]) of wave_dev and the frames [frame_offsets[i], frame_offsets[i + 1]) of feat_dev (HOST arrays of
+// n_waves + 1 entries, both starting at 0 and ascending).  mask_dev_out / effective_out [sum n]: the masks in wave order, on the card and on the host;
+// n_eff_out [n_waves]; x_eff_dev_out [sum n][in_ch] / row_of_dev_out [sum n] (device blocks; both null: blocks of the core): the effective rows of wave
+// i and their frame indices, counted from the wave's first frame, from row frame_offsets[i] on.  Everything of wave i has the bits of ry_vc_gate
+// on wave i alone.  The stage-1 stream waits for the context stream first, as in ry_vc_enqueue_wave_device.
+int ry_vc_gate_waves_device(ry_vc* vc, const float* wave_dev, const long long* sample_offsets, const int* frame_offsets, int n_waves, int hop,
+                            int fft_length, float p_effective, float p_all, const float* feat_dev, unsigned char* mask_dev_out,
+                            unsigned char* effective_out, int* n_eff_out, float* x_eff_dev_out, int* row_of_dev_out) {
+    VcWaves w;
+    RY_TRY(vc_waves_args(vc, wave_dev, sample_offsets, frame_offsets, n_waves, hop, fft_length, feat_dev, &w));
+    if (!mask_dev_out || !effective_out || !n_eff_out || (!x_eff_dev_out) != (!row_of_dev_out)) return fail(RY_EINVAL, "null argument");
+    RT_TRY(rt::set_device(vc->s1->ctx->device));
+    Stage1On on_lane(vc, vc->s1, vc->s2);
+    ry_stream_t st1 = vc->s1->stream, stc = vc->s1->ctx->stream;
+    vc->note(st1, st1);
+    RY_TRY(vc_waves_reserve(vc, w));
+    if (stc != st1) { RT_TRY(rt::event_record(vc->ev_in, stc)); RT_TRY(rt::stream_wait_event(st1, vc->ev_in)); }
+    return vc_gate_waves_launch(vc, vc->s1, wave_dev, w, hop, fft_length, p_effective, p_all, feat_dev, x_eff_dev_out ? x_eff_dev_out : vc->wset.d_x,
+                                row_of_dev_out ? row_of_dev_out : vc->wset.d_row, mask_dev_out, effective_out, n_eff_out);
+}
+
+// ry_vc_enqueue_wave_device for n_waves waves in one call: ONE gate over all of them (ry_vc_gate_waves_device: one launch pair, one wait for
+// all counts and masks), then, wave by wave in order, the rest of the single call on that wave's region -- stage 1 under the plan its own count picks
+// (none for a wave without an effective frame), scatter, mc2sp, stage 2 behind ev_mid -- with the ring slots and the lanes taken round robin as a
+// sequence of single calls takes them.  A slot that comes round again within the call is ordered behind its ev_done on the stream: any n_waves runs
+// on any ring.  feat_dev [sum n][in_ch], mc_out_dev [sum n][M], sp_out_dev [sum n][F], mask_dev_out / effective_out [sum n], n_eff_out [n_waves];
+// ry_vc_set_discard applies to every window.  mc, sp, mask and count of wave i have the bits of ry_vc_enqueue_wave_device on wave i alone, whatever
+// the other waves hold and wherever wave i stands.  Stream order as in the single call: the stage-1 stream waits for the context stream before
+// the gate, the context stream waits for the end of every window before the call returns.
+int ry_vc_enqueue_waves_device(ry_vc* vc, const float* wave_dev, const long long* sample_offsets, const int* frame_offsets, int n_waves, int hop,
+                               int fft_length, float p_effective, float p_all, const float* feat_dev, float sp_floor, float* mc_out_dev,
+                               float* sp_out_dev, unsigned char* mask_dev_out, unsigned char* effective_out, int* n_eff_out) {
+    VcWaves w;
+    RY_TRY(vc_waves_args(vc, wave_dev, sample_offsets, frame_offsets, n_waves, hop, fft_length, feat_dev, &w));
+    if (!mc_out_dev || !sp_out_dev || !mask_dev_out || !effective_out || !n_eff_out) return fail(RY_EINVAL, "null argument");
+    for (int i = 0; i < n_waves && i < vc->ring; ++i) {
+        const int k = (vc->dev_count + i) % vc->ring;
+        if (vc->slot[k].ticket >= 0) return fail(RY_ESTATE, "wave %d: ring slot %d is held by ticket %d: ry_vc_wait it first", i, k, vc->slot[k].ticket);
+    }
+    RT_TRY(rt::set_device(vc->s1->ctx->device));
+    const ry_stream_t stc = vc->s1->ctx->stream;
+    const size_t M = (size_t)vc->M, F = (size_t)vc->F, cin = (size_t)vc->s1->desc.in_ch;
+    RY_TRY(vc_waves_reserve(vc, w));
+    {   // the one gate, on the stage-1 stream of the first window's lane
+        const int k = vc->dev_count % vc->ring;
+        ry_net *s1 = vc->lane1(k), *s2 = vc->lane2(k);
+        Stage1On on_lane(vc, s1, s2);
+        ry_stream_t st1 = s1->stream;
+        vc->note(st1, st1);
+        if (stc != st1) { RT_TRY(rt::event_record(vc->ev_in, stc)); RT_TRY(rt::stream_wait_event(st1, vc->ev_in)); }
+        RY_TRY(vc_gate_waves_launch(vc, s1, wave_dev, w, hop, fft_length, p_effective, p_all, feat_dev, vc->wset.d_x, vc->wset.d_row, mask_dev_out,
+                                    effective_out, n_eff_out));
+    }
+    // the host has waited for the gate, and the gate for the context stream: what follows may run on any stream
+    for (int i = 0; i < n_waves; ++i) {
+        const RyWaveSeg& g = w.seg[(size_t)i];
+        const int k = vc->dev_count % vc->ring, n_eff = n_eff_out[i], n_frames = g.n_frames;
+        VcSlot& sl = vc->slot[k];
+        ry_net *s1 = vc->lane1(k), *s2 = vc->lane2(k);
+        Stage1On on_lane(vc, s1, s2);
+        RY_TRY(vc_reserve_slot(vc, sl, n_frames, n_frames));
+        ++vc->dev_count;
+        ry_stream_t st1 = s1->stream, st2 = s2->stream;
+        vc->note(st1, st2);
+        if (sl.used) RT_TRY(rt::stream_wait_event(st1, sl.ev_done));                    // the slot's previous window has left d_y1 / d_sp
+        if (n_eff > 0) RY_TRY(ry_ac_convert(s1, vc->wset.d_x + (size_t)g.r0 * cin, sl.d_y1, 1, n_eff, 1));
+        RY_TRY(vc_enqueue_mid(vc, s1, sl.d_y1, vc->wset.d_row + g.r0, n_eff, n_frames, sp_floor, mc_out_dev + (size_t)g.f0 * M, sl.d_sp));
+        RY_TRY(vc_join(sl.ev_mid, st1, st2));
+        RY_TRY(vc_run_stage2(vc, s2, sl.d_sp, sp_out_dev + (size_t)g.f0 * F, n_frames));
+        RT_TRY(rt::event_record(sl.ev_done, st2));
+        if (stc != st2) RT_TRY(rt::stream_wait_event(stc, sl.ev_done));
+        sl.used = true;
+    }
+    vc->split_eff = -1;
     return RY_OK;
 }
 

@@ -1,5 +1,6 @@
 // ry_vc_kernels.h -- the small kernels of the window call (ry_vc.cpp): combine_silent (row scatter; ry_mask_rows for rows that are already
-// in place), the silence gate (frame power in numpy's summation order, gate + ordered compaction) and decode_spectrogram (mc2sp = exp(mc @ M)).
+// in place; ry_gather_rows for rows that are packed elsewhere), the silence gate (frame power in numpy's summation order, gate + ordered compaction;
+// the same two over a table of waves) and decode_spectrogram (mc2sp = exp(mc @ M)).
 // Reference: /root/reference/realtime_voice_conversion/yukarin_wrapper/voice_changer.py:27-39.
 #pragma once
 #include "ry_dev.h"
@@ -40,6 +41,40 @@ RY_KERNEL(256) void ry_mask_rows(RyMaskRowsParams p) {
     if (tail + lane < p.cols) row[tail + lane] = 0.f;          // at most three
 }
 
+// Rows picked by an index table, packed back to back: dst[j][:] = (mask == null || mask[src_row[j]]) ? rows[src_row[j]][:] : +0.0f for j < n_out --
+// the rows [front, n_b - back) of every stream of a call in the order ry_synth_bank_push reads them, with combine_silent folded in for the
+// aperiodicity.  One wave per output row, four rows per workgroup.  Source and destination rows start at any 4-byte alignment, independently
+// (cols = 513): the destination is written as scalars up to its first 16-byte boundary, 128-bit stores over the whole quads, scalars for the rest;
+// a quad is read with one 128-bit load when the source row has the destination's residue, else as four scalars.  Nothing outside a row is
+// read or written; an index outside 0 .. n_rows - 1 reads nothing and gives a row of zeros.
+struct RyGatherRowsParams { const float* rows; const int* src_row; const unsigned char* mask; float* dst; int n_rows, n_out, cols; };
+
+RY_KERNEL(256) void ry_gather_rows(RyGatherRowsParams p) {
+    const int lane = (int)threadIdx.x & 63;
+    const long long j = (long long)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+    if (j >= p.n_out) return;                                   // wave-uniform
+    const int s = p.src_row[j];
+    const bool keep = s >= 0 && s < p.n_rows && (p.mask == nullptr || p.mask[s] != 0);      // wave-uniform
+    const float* src = p.rows + (size_t)(keep ? s : 0) * p.cols;
+    float* row = p.dst + (size_t)j * p.cols;
+    int head = (int)((4 - ((reinterpret_cast<unsigned long long>(row) >> 2) & 3)) & 3);     // floats in front of the first 16-byte boundary
+    if (head > p.cols) head = p.cols;
+    const int quads = (p.cols - head) >> 2, tail = head + 4 * quads;
+    const bool wide = (((reinterpret_cast<unsigned long long>(src) ^ reinterpret_cast<unsigned long long>(row)) >> 2) & 3) == 0;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    if (lane < head) row[lane] = keep ? src[lane] : 0.f;
+    for (int q = lane; q < quads; q += 64) {
+        const int c = head + 4 * q;
+        f32x4 v = zero;
+        if (keep) {
+            if (wide) v = ry_ld4(src + c);
+            else { v[0] = src[c]; v[1] = src[c + 1]; v[2] = src[c + 2]; v[3] = src[c + 3]; }
+        }
+        ry_st4(row + c, v);
+    }
+    if (tail + lane < p.cols) row[tail + lane] = keep ? src[tail + lane] : 0.f;             // at most three
+}
+
 // ---------------------------------------------------------------------------------------------
 // `AcousticConverter.separate_effective` on the device (voice_changer.py:27-31).
 // ry_frame_power: mse[t] = librosa.feature.rms(wave, frame_length, hop, center=True, pad_mode='reflect')[t] ** 2 in float32 with
@@ -63,26 +98,52 @@ RY_DEV int ry_reflect_index(int i, int n) {                     // numpy.pad(mod
     return j < n ? j : period - j;
 }
 
-RY_KERNEL(256) void ry_frame_power(RyFramePowerParams p) {
-    const int tid = (int)threadIdx.x, lane = tid & 63;
-    const int frame = (int)blockIdx.x * 4 + (tid >> 6);
-    if (frame >= p.n_wave_frames) return;                       // wave-uniform
-    const int L = p.fft >> 4;                                   // active lanes: 8 per 128-element leaf
+// the power of frame `frame` of a wave of n samples, by one wave of lanes: the return value is the frame's in every lane below fft / 16
+RY_DEV float ry_frame_power_of(const float* wave, int n, int hop, int fft, int frame, int lane) {
+    const int L = fft >> 4;                                     // active lanes: 8 per 128-element leaf
     float r = 0.f;
     if (lane < L) {
-        const int base = frame * p.hop - (p.fft >> 1) + 128 * (lane >> 3) + (lane & 7);
+        const int base = frame * hop - (fft >> 1) + 128 * (lane >> 3) + (lane & 7);
         float v[16];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) v[i] = p.wave[ry_reflect_index(base + 8 * i, p.n)];
+        for (int i = 0; i < 16; ++i) v[i] = wave[ry_reflect_index(base + 8 * i, n)];
         r = ry_mul_rn(v[0], v[0]);
 #pragma unroll
         for (int i = 1; i < 16; ++i) r = ry_add_rn(r, ry_mul_rn(v[i], v[i]));
     }
     for (int mask = 1; mask < L; mask <<= 1) r = ry_add_rn(r, ry_shfl_xor(r, mask));
-    if (lane == 0) {
-        const float rms = ry_sqrt_rn(r / (float)p.fft);        // a power of two: the division is exact scaling, as numpy's
-        p.power[frame] = ry_mul_rn(rms, rms);
+    const float rms = ry_sqrt_rn(r / (float)fft);              // a power of two: the division is exact scaling, as numpy's
+    return ry_mul_rn(rms, rms);
+}
+
+RY_KERNEL(256) void ry_frame_power(RyFramePowerParams p) {
+    const int tid = (int)threadIdx.x, lane = tid & 63;
+    const int frame = (int)blockIdx.x * 4 + (tid >> 6);
+    if (frame >= p.n_wave_frames) return;                       // wave-uniform
+    const float pw = ry_frame_power_of(p.wave, p.n, p.hop, p.fft, frame, lane);
+    if (lane == 0) p.power[frame] = pw;
+}
+
+// The same over a table of waves (ry_vc_enqueue_waves_device): per wave the first sample and the sample count in the call's wave block, the first
+// frame and the frame count in the call's feature / mask blocks, the number of wave frames (n_samples / hop + 1) and their first slot in the
+// call's power block, and the first row of the wave's region in the call's x_eff / row_of blocks.
+struct RyWaveSeg { int s0, n_samples, f0, n_frames, p0, n_wave_frames, r0, pad; };
+
+// One wave of lanes per wave frame over all waves: the frame finds its wave by bisection over p0 and reflects at the ends of that wave only.
+struct RyFramePowerManyParams { const float* wave; const RyWaveSeg* seg; int n_waves, hop, fft, total_wave_frames; float* power; };
+
+RY_KERNEL(256) void ry_frame_power_many(RyFramePowerManyParams p) {
+    const int tid = (int)threadIdx.x, lane = tid & 63;
+    const int g = (int)blockIdx.x * 4 + (tid >> 6);
+    if (g >= p.total_wave_frames) return;                       // wave-uniform
+    int lo = 0, hi = p.n_waves - 1;
+    while (lo < hi) {                                           // the last wave whose first slot is at or before g
+        const int mid = (lo + hi + 1) >> 1;
+        if (p.seg[mid].p0 <= g) lo = mid; else hi = mid - 1;
     }
+    const RyWaveSeg s = p.seg[lo];
+    const float pw = ry_frame_power_of(p.wave + s.s0, s.n_samples, p.hop, p.fft, g - s.p0, lane);
+    if (lane == 0) p.power[g] = pw;
 }
 
 struct RyGateParams {
@@ -91,7 +152,7 @@ struct RyGateParams {
     float* x_eff; int* row_of; int* count; unsigned char* mask;
 };
 
-RY_KERNEL(1024) void ry_gate_compact(RyGateParams p) {
+RY_DEV void ry_gate_compact_body(const RyGateParams& p) {
     __shared__ float fmx[1024];
     __shared__ int scan[1024];
     __shared__ int s_base;
@@ -127,6 +188,28 @@ RY_KERNEL(1024) void ry_gate_compact(RyGateParams p) {
         __syncthreads();
     }
     if (tid == 0) *p.count = s_base;
+}
+
+RY_KERNEL(1024) void ry_gate_compact(RyGateParams p) { ry_gate_compact_body(p); }
+
+// One workgroup per wave of the table: the maximum over the wave's own powers, the ordered compaction into the wave's own region of the call's
+// x_eff / row_of blocks (row_of counts from the wave's first frame), the mask bytes in wave order and one count per wave.  `host` is the block the
+// host reads with one copy: n_waves counts, then the mask bytes of all waves (each thread copies the bytes it wrote itself).
+struct RyGateManyParams {
+    const float* power; const RyWaveSeg* seg; float p_eff, p_all;
+    const float* feat; int cin;
+    float* x_eff; int* row_of; unsigned char* mask; int* host; int n_waves;
+};
+
+RY_KERNEL(1024) void ry_gate_compact_many(RyGateManyParams p) {
+    const RyWaveSeg s = p.seg[blockIdx.x];
+    RyGateParams g;
+    g.power = p.power + s.p0; g.n_wave_frames = s.n_wave_frames; g.n_frames = s.n_frames; g.p_eff = p.p_eff; g.p_all = p.p_all;
+    g.feat = p.feat + (size_t)s.f0 * p.cin; g.cin = p.cin;
+    g.x_eff = p.x_eff + (size_t)s.r0 * p.cin; g.row_of = p.row_of + s.r0; g.count = p.host + blockIdx.x; g.mask = p.mask + s.f0;
+    ry_gate_compact_body(g);
+    unsigned char* bytes = reinterpret_cast<unsigned char*>(p.host + p.n_waves) + s.f0;
+    for (int t = (int)threadIdx.x; t < s.n_frames; t += 1024) bytes[t] = g.mask[t];
 }
 
 struct RyMc2spParams { const float* mc; const float* mtx; float* sp; int n, m, f; float floor; };

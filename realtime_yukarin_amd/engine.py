@@ -78,6 +78,16 @@ class Context(object):
         self.lib.check(self.lib.dll.ry_mask_rows(self.handle, _lib._fptr(int(rows_ptr)), ctypes.cast(ctypes.c_void_p(int(mask_ptr)), ctypes.POINTER(ctypes.c_ubyte)),
                                                  int(n), int(cols), int(k0), int(n if k1 is None else k1), ctypes.c_void_p(stream or 0)))
 
+    def gather_rows(self, rows_ptr: int, n_rows: int, cols: int, src_row_ptr: int, dst_ptr: int, n_out: int, mask_ptr: Optional[int] = None,
+                    stream: Optional[int] = None):
+        """`ry_gather_rows`: row j < n_out of the block at `dst_ptr` = row src_row[j] of the (n_rows, cols) float32 block at `rows_ptr` (`src_row_ptr`: an
+        int32 table on the card), or +0.0 where the mask byte of that source row is 0 (`mask_ptr` None: every row is kept).  Enqueued on `stream`
+        (default: the context stream), nothing is waited for."""
+        self.lib.check(self.lib.dll.ry_gather_rows(self.handle, _lib._fptr(int(rows_ptr)), int(n_rows), int(cols),
+                                                   ctypes.cast(ctypes.c_void_p(int(src_row_ptr)), ctypes.POINTER(ctypes.c_int)),
+                                                   ctypes.cast(ctypes.c_void_p(int(mask_ptr or 0)), ctypes.POINTER(ctypes.c_ubyte)),
+                                                   _lib._fptr(int(dst_ptr)), int(n_out), ctypes.c_void_p(stream or 0)))
+
     def mc2sp(self, mc, mtx, floor: float = 0.0):
         """`decode_spectrogram` on the device: exp(mc (N, M) @ mtx (M, F)) + floor."""
         mc = numpy.ascontiguousarray(mc, dtype=numpy.float32)
@@ -314,6 +324,42 @@ class VcCore(object):
             _lib._fptr(int(feat_ptr)), int(n_frames), float(sp_floor), _lib._fptr(int(mc_ptr)), _lib._fptr(int(sp_ptr)),
             ctypes.cast(ctypes.c_void_p(int(mask_ptr)), ub), mask.ctypes.data_as(ub), ctypes.byref(n_eff)))
         return mask.astype(bool), int(n_eff.value)
+
+    @staticmethod
+    def _offsets(sample_offsets, frame_offsets):
+        so = numpy.ascontiguousarray(sample_offsets, dtype=numpy.int64).ravel()
+        fo = numpy.ascontiguousarray(frame_offsets, dtype=numpy.int32).ravel()
+        if so.size != fo.size or so.size < 2:
+            raise ValueError('two offset arrays of waves + 1 >= 2 entries are needed, got %d and %d' % (so.size, fo.size))
+        return so, fo, so.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), fo.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+
+    def gate_waves_device(self, wave_ptr: int, sample_offsets, frame_offsets, hop: int, fft_length: int, p_effective: float, p_all: float,
+                          feat_ptr: int, mask_ptr: int, x_eff_ptr: Optional[int] = None, row_of_ptr: Optional[int] = None):
+        """`ry_vc_gate_waves_device`: `separate_effective` of the waves back to back at `wave_ptr` (wave i at sample_offsets[i] / frame_offsets[i])
+        in one launch pair and one wait -> (effective (sum n,) bool, n_eff (waves,) int32); the mask bytes at `mask_ptr`, the effective rows and
+        their frame indices in the blocks at `x_eff_ptr` / `row_of_ptr` (wave i from row frame_offsets[i] on), all on the card."""
+        so, fo, pso, pfo = self._offsets(sample_offsets, frame_offsets)
+        mask, n_eff = numpy.empty(max(int(fo[-1]), 1), numpy.uint8), numpy.zeros(so.size - 1, numpy.int32)
+        ub, ip = ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_int)
+        self.lib.check(self.lib.dll.ry_vc_gate_waves_device(
+            self.handle, _lib._fptr(int(wave_ptr)), pso, pfo, so.size - 1, int(hop), int(fft_length), float(p_effective), float(p_all),
+            _lib._fptr(int(feat_ptr)), ctypes.cast(ctypes.c_void_p(int(mask_ptr)), ub), mask.ctypes.data_as(ub), n_eff.ctypes.data_as(ip),
+            _lib._fptr(None if x_eff_ptr is None else int(x_eff_ptr)), ctypes.cast(ctypes.c_void_p(int(row_of_ptr or 0)), ip)))
+        return mask[:int(fo[-1])].astype(bool), n_eff
+
+    def enqueue_waves_device(self, wave_ptr: int, sample_offsets, frame_offsets, hop: int, fft_length: int, p_effective: float, p_all: float,
+                             feat_ptr: int, mc_ptr: int, sp_ptr: int, mask_ptr: int, sp_floor: float = 1e-16):
+        """`ry_vc_enqueue_waves_device`: `enqueue_wave_device` for the waves back to back at `wave_ptr` in one call -- one gate and one wait for all
+        counts, then every wave's window on its own rows of the (sum n, ...) blocks -> (effective (sum n,) bool, n_eff (waves,) int32).  Wave i gets
+        the bits of the single call on it alone."""
+        so, fo, pso, pfo = self._offsets(sample_offsets, frame_offsets)
+        mask, n_eff = numpy.empty(max(int(fo[-1]), 1), numpy.uint8), numpy.zeros(so.size - 1, numpy.int32)
+        ub = ctypes.POINTER(ctypes.c_ubyte)
+        self.lib.check(self.lib.dll.ry_vc_enqueue_waves_device(
+            self.handle, _lib._fptr(int(wave_ptr)), pso, pfo, so.size - 1, int(hop), int(fft_length), float(p_effective), float(p_all),
+            _lib._fptr(int(feat_ptr)), float(sp_floor), _lib._fptr(int(mc_ptr)), _lib._fptr(int(sp_ptr)),
+            ctypes.cast(ctypes.c_void_p(int(mask_ptr)), ub), mask.ctypes.data_as(ub), n_eff.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return mask[:int(fo[-1])].astype(bool), n_eff
 
     def enqueue_device_batch(self, x_ptr: int, rows_ptr: int, n_eff, n_frames: int, mc_ptr: int, sp_ptr: int, sp_floor: float = 1e-16):
         """`ry_vc_enqueue_device_batch`: len(n_eff) windows of n_frames each, device pointers, nothing waited for."""

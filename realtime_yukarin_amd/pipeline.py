@@ -245,3 +245,222 @@ class Pipeline(object):
         """Ends the live stream: the samples `push` still held back; the next `push` starts a new signal."""
         from yukarin import Wave
         return Wave(wave=self.synth.flush(), sampling_rate=self.voice_changer.output_sampling_rate)
+
+
+calls_many = {'resident': 0, 'composed': 0}     # which way a `PipelineBank.convert_waves` / `push` went, counted per call
+
+
+class PipelineBank(object):
+    """`Pipeline` for the B streams one process serves, with ONE chain per buffer instead of B: `CrepeModel.track_many` (one upload of all waves) ->
+    `Analyzer.extract_many_resident` (one verdict) -> `VcCore.enqueue_waves_device` (one gate, one wait for all counts, then every wave's window) ->
+    `ry_mask_rows` / `ry_gather_rows` -> `ry_synth_run_many` (`convert_waves`) or one `ry_synth_bank_push` of a `StreamBank` with one seed per stream
+    (`push`).  What stream b returns, call by call, has the bits a lone `Pipeline(seed=seeds[b])` returns for the same waves, discards and flushes,
+    whatever the other streams do.  `seeds=None`: every stream has RY_SYNTH_SEED.  `convert_waves` is a one-shot call outside the streams: its
+    synthesizer has the seed of stream 0.  The resident chain runs when every wave of a call meets the conditions of `Pipeline`'s resident path and
+    all share one rate; otherwise every wave runs the chain of the separate calls, one after the other, over the same bank: the same bits
+    (`calls_many` counts which way a call went)."""
+
+    def __init__(self, voice_changer, acoustic_param, n_streams: int, seeds=None, crepe_capacity='full', feature_class=None):
+        self.n_streams = int(n_streams)
+        if self.n_streams < 1:
+            raise ValueError('a bank has at least one stream, got %d' % self.n_streams)
+        if seeds is None:
+            seeds = [int(os.environ.get('RY_SYNTH_SEED', '0'))] * self.n_streams
+        self.seeds = [int(s) for s in seeds]
+        if len(self.seeds) != self.n_streams:
+            raise ValueError('%d seeds for %d streams' % (len(self.seeds), self.n_streams))
+        self.voice_changer, self.acoustic_param = voice_changer, acoustic_param
+        self._one = Pipeline(voice_changer, acoustic_param, crepe_capacity=crepe_capacity, seed=self.seeds[0], feature_class=feature_class)
+        self.feature_class = self._one.feature_class
+        self.bank = world_synth.StreamBank(voice_changer.output_sampling_rate, acoustic_param.frame_period, n_streams=self.n_streams, seeds=self.seeds,
+                                           ctx=world_synth.engine_for_tests.ctx)
+        self.calls = calls_many
+        self._live = [False] * self.n_streams                              # the stream holds frames of a signal that has not ended
+        self._blocks, self._cap, self._ctx, self._pid, self._table = {}, 0, None, None, None
+
+    # ---- the blocks this object owns: grown, never shrunk, freed by `close` in the process that made them
+    def _reserve(self, ctx, n: int, m_in: int, m_out: int, f_out: int) -> dict:
+        if self._pid != os.getpid() or self._ctx is not ctx:
+            self._blocks, self._cap, self._ctx, self._pid, self._table = {}, 0, ctx, os.getpid(), None
+        widths = dict(mc32=m_in, sp32=BINS, ap32=BINS, mc_out=m_out, sp_out=f_out, sp_pack=BINS, ap_pack=BINS, rows=1)
+        if n > self._cap or any(self._blocks.get('w_' + k) != w for k, w in widths.items()):
+            self._free()
+            cap = max(n + n // 2, 64)
+            for k, w in widths.items():
+                self._blocks[k] = ctx.dev_alloc(cap * w)
+                self._blocks['w_' + k] = w
+            self._blocks['mask'] = ctx.dev_alloc(cap // 4 + 4)
+            self._cap = cap
+        return self._blocks
+
+    def _free(self) -> None:
+        if self._pid == os.getpid() and self._ctx is not None and self._ctx.handle is not None:
+            for k, p in self._blocks.items():
+                if not k.startswith('w_'):
+                    self._ctx.dev_free(p)
+        self._blocks, self._cap, self._table = {}, 0, None
+
+    def close(self) -> None:
+        """Frees the device blocks, the stream bank and the one-shot synthesizer in the process that created them; the voice changer and the shared
+        handles stay."""
+        self._free()
+        self.bank.close()
+        self._one.close()
+
+    # ---- which way a call goes
+    def _handles(self, waves):
+        """The handles of the resident chain when every wave meets `Pipeline._resident_handles`, all share one rate and the bank lives in their
+        context; else None."""
+        if len(set(int(w.sampling_rate) for w in waves)) != 1:
+            return None
+        handles = None
+        for w in waves:
+            handles = self._one._resident_handles(w)
+            if handles is None:
+                return None
+        self.bank._get()
+        return handles if self.bank._ctx is handles[2].stage1.ctx and self.bank.fft_size == FFT_SIZE else None
+
+    # ---- the resident chain up to the rows the synthesizers read
+    def _resident_rows(self, waves, handles, discard):
+        """-> (context, blocks, frame offsets int32 [waves + 1], [f0 float64 [frames_i]: the converted track of wave i, zeros on the silent frames])."""
+        model, analyzer, core, (p_eff, p_all), hop, gate_fft = handles
+        vc, p = self.voice_changer, self.acoustic_param
+        ac = vc.acoustic_converter
+        fs = int(waves[0].sampling_rate)
+        xs = [numpy.ascontiguousarray(w.wave, dtype=numpy.float32) for w in waves]
+        trk = model.track_many(xs, fs, _crepe.hop_length(p.frame_period), p.frame_period, threshold=encode.threshold, device=True)   # the one upload
+        n, ctx, fo = trk.frames, core.stage1.ctx, trk.frame_offsets
+        b = self._reserve(ctx, n, p.order + 1, core.M, core.F)
+        analyzer.extract_many_resident(trk.wave, trk.sample_offsets, trk.f0, trk.t, fo, b['mc32'], b['sp32'], b['ap32'])
+        tracks = trk.download()
+        discard = (int(discard[0]), int(discard[1])) if os.environ.get('RY_DISCARD_HINT', '1') != '0' else (0, 0)
+        if core.discard != discard:
+            core.set_discard(*discard)
+        effective, n_eff = core.enqueue_waves_device(trk.wave, trk.sample_offsets, fo, hop, gate_fft, p_eff, p_all, b['mc32'], b['mc_out'], b['sp_out'],
+                                                     b['mask'], SP_FLOOR)
+        # f0, wave by wave: the numpy operations of `Pipeline._resident_rows`
+        from yukarin.acoustic_feature import AcousticFeature
+        f0s = []
+        for i, (_, track) in enumerate(tracks):
+            eff = effective[fo[i]:fo[i + 1]]
+            f0_eff = track[:, None].astype(p.dtype)[eff]
+            if n_eff[i] and ac.f0_converter is not None:
+                f0_eff = ac.f0_converter.convert(AcousticFeature(f0=f0_eff)).f0
+            f0 = numpy.zeros((len(eff), 1), numpy.float32)
+            f0[eff] = f0_eff
+            f0s.append(numpy.ascontiguousarray(f0.ravel(), dtype=numpy.float64))
+        return ctx, b, fo, f0s
+
+    # ---- calls
+    def convert_waves(self, waves) -> list:
+        """A list of `yukarin.Wave` -> the list of their converted waves, each with the bits of `Pipeline(seed=seeds[0]).convert_wave` on it alone."""
+        from yukarin import Wave
+        waves = list(waves)
+        if not waves:
+            return []
+        rate = self.voice_changer.output_sampling_rate
+        handles = self._handles(waves)
+        if handles is None:
+            calls_many['composed'] += 1
+            return [world_synth.decode(self._one._vocoder, self._one._composed_feature(w, (0, 0))) for w in waves]
+        calls_many['resident'] += 1
+        ctx, b, fo, f0s = self._resident_rows(waves, handles, (0, 0))
+        n = int(fo[-1])
+        ctx.mask_rows(b['ap32'], b['mask'], n, BINS)
+        synth = self._one.synth
+        lib, h = synth._get()
+        counts = numpy.ascontiguousarray(numpy.diff(fo), dtype=numpy.int32)
+        f0 = numpy.ascontiguousarray(numpy.concatenate(f0s))
+        y = numpy.empty(max(sum(synth.length(int(k)) for k in counts), 1), numpy.float64)
+        off = numpy.zeros(len(waves) + 1, numpy.int64)
+        lib.check(lib.dll.ry_synth_run_many(h, f0.ctypes.data_as(world_synth._DP), Pipeline._at(b['sp_out'], 0), Pipeline._at(b['ap32'], 0),
+                                            counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(waves), BINS, 1, y.ctypes.data_as(world_synth._DP),
+                                            y.size, off.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return [Wave(y[off[i]:off[i + 1]].copy(), sampling_rate=rate) for i in range(len(waves))]
+
+    def _final(self, final):
+        final = sorted(set(int(s) for s in (final or ())))
+        if any(s < 0 or s >= self.n_streams for s in final):
+            raise ValueError('final names stream %s of %d' % (final, self.n_streams))
+        return final
+
+    def push(self, waves, discard=(0, 0), final=None) -> list:
+        """One buffer of every live stream: `waves` has one `yukarin.Wave` per stream, None for a stream that sits the call out; every wave is
+        encoded and converted on its own, the rows [front, frames - back) of each go to its synthesis stream, and the samples that are final come
+        back -> one `Wave` per stream (empty for a stream that sat out).  `final`: the streams whose signal ends with this call (what `Pipeline.push(
+        ..., final=True)` does for one); a stream named there without a wave is flushed."""
+        from yukarin import Wave
+        waves = list(waves)
+        if len(waves) != self.n_streams:
+            raise ValueError('%d waves for %d streams' % (len(waves), self.n_streams))
+        final = self._final(final)
+        front, back = int(discard[0]), int(discard[1])
+        rate = self.voice_changer.output_sampling_rate
+        part = [s for s, w in enumerate(waves) if w is not None]
+        outs = [numpy.empty(0, numpy.float64) for _ in range(self.n_streams)]
+        if not part:
+            if final:
+                outs = self.bank.flush(final)
+        else:
+            handles = self._handles([waves[s] for s in part])
+            if handles is None:
+                calls_many['composed'] += 1
+                for s in part:
+                    f = self._one._composed_feature(waves[s], (front, back))
+                    k0, k1 = front, len(f.f0) - back
+                    if k1 > k0:
+                        picked = f.pick(k0, k1, keys=('f0', 'sp', 'ap'))
+                        items = [None] * self.n_streams
+                        items[s] = (numpy.asarray(picked.f0).ravel(), picked.sp, picked.ap)
+                        outs[s] = self.bank.push(items, final=[s] if s in final else ())[s]
+                    elif s in final:
+                        outs[s] = self.bank.flush([s])[s]
+                rest = [s for s in final if s not in part]
+                if rest:
+                    got = self.bank.flush(rest)
+                    for s in rest:
+                        outs[s] = got[s]
+            else:
+                calls_many['resident'] += 1
+                ctx, b, fo, f0s = self._resident_rows([waves[s] for s in part], handles, (front, back))
+                picks = [(int(fo[i]) + front, int(fo[i + 1]) - back) for i in range(len(part))]
+                picks = [(k0, max(k1, k0)) for k0, k1 in picks]
+                total = sum(k1 - k0 for k0, k1 in picks)
+                items = [None] * self.n_streams
+                if total > 0:
+                    key = (tuple(picks), b['rows'])
+                    if self._table != key:                                 # live streams repeat their shapes: the table goes up once
+                        ctx.dev_upload(b['rows'], numpy.concatenate([numpy.arange(k0, k1, dtype=numpy.int32) for k0, k1 in picks]))
+                        self._table = key
+                    n = int(fo[-1])
+                    ctx.gather_rows(b['sp_out'], n, BINS, b['rows'], b['sp_pack'], total)
+                    ctx.gather_rows(b['ap32'], n, BINS, b['rows'], b['ap_pack'], total, mask_ptr=b['mask'])       # combine_silent folded in
+                    at = 0
+                    for i, s in enumerate(part):
+                        k0, k1 = picks[i]
+                        if k1 > k0:
+                            rows = [world_synth.DeviceRows(b[k] + at * BINS * 4, k1 - k0) for k in ('sp_pack', 'ap_pack')]
+                            items[s] = (numpy.ascontiguousarray(f0s[i][k0 - int(fo[i]):k1 - int(fo[i])]), rows[0], rows[1])
+                            at += k1 - k0
+                if total > 0 or final:
+                    outs = self.bank.push(items, final=final)              # one ry_synth_bank_push: the packed rows follow one another and are read in place
+        for s in part:
+            self._live[s] = True
+        for s in final:
+            self._live[s] = False
+        return [Wave(wave=o, sampling_rate=rate) for o in outs]
+
+    def flush(self, stream=None):
+        """Ends the signal of `stream` -> its `Wave`: the samples `push` still held back.  stream=None: ends every stream that holds frames -> one
+        `Wave` per stream (empty for the others).  The next `push` of an ended stream starts a new signal."""
+        from yukarin import Wave
+        rate = self.voice_changer.output_sampling_rate
+        if stream is not None:
+            out = self.bank.flush([int(stream)])[int(stream)]
+            self._live[int(stream)] = False
+            return Wave(wave=out, sampling_rate=rate)
+        live = [s for s in range(self.n_streams) if self._live[s]]
+        outs = self.bank.flush(live) if live else [numpy.empty(0, numpy.float64)] * self.n_streams
+        self._live = [False] * self.n_streams
+        return [Wave(wave=o, sampling_rate=rate) for o in outs]

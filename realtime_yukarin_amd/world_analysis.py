@@ -160,6 +160,21 @@ class Analyzer(DeviceHandle):
                                                        fo.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), so.size - 1, float(threshold), *(out_sp + out_ap)))
         return tuple(got[k] for k in want)
 
+    def extract_many_resident(self, wave_dev: int, sample_offsets, f0_dev: int, t_dev: int, frame_offsets, mc32_dev: int, sp32_dev: int, ap32_dev: int,
+                              threshold: float = 0.85) -> None:
+        """`run_device_many` with device outputs only (`ry_analysis_extract_many_resident`): float32 `mc` (sum n, order + 1), `sp` and `ap` (sum n, 513)
+        rows in wave order at the three addresses; rows of wave i have the bits `extract_resident` writes for wave i alone.  One verdict comes back
+        to the host; a refused call raises and leaves the blocks untouched."""
+        lib, h = self._get()
+        so = numpy.ascontiguousarray(sample_offsets, dtype=numpy.int64).ravel()
+        fo = numpy.ascontiguousarray(frame_offsets, dtype=numpy.int32).ravel()
+        if so.size != fo.size or so.size < 2:
+            raise ValueError('extract_many_resident needs two offset arrays of waves + 1 >= 2 entries, got %d and %d' % (so.size, fo.size))
+        as_d = lambda a: ctypes.cast(ctypes.c_void_p(a), _DP)
+        lib.check(lib.dll.ry_analysis_extract_many_resident(h, _lib._fptr(int(wave_dev)), so.ctypes.data_as(_LLP), as_d(f0_dev), as_d(t_dev),
+                                                            fo.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), so.size - 1, float(threshold),
+                                                            _lib._fptr(int(mc32_dev)), _lib._fptr(int(sp32_dev)), _lib._fptr(int(ap32_dev))))
+
     def d4c(self, x, f0, t, threshold: float = 0.85) -> numpy.ndarray:
         """`pyworld.d4c` of this analyzer's rate: -> aperiodicity [frames][513] float64."""
         return self.run(x, f0, t, want=('ap',), threshold=threshold)[0]
