@@ -425,6 +425,38 @@ int ry_crepe_debug_layer(ry_crepe* crepe, int layer, int n_frames, float* out);
 int ry_crepe_debug_poison(ry_crepe* crepe);
 /* diagnostics: the split-K count of conv1 .. conv6 and the dense layer (7 ints) in the mode in force (ry_crepe_set_dtype). */
 int ry_crepe_debug_splits(ry_crepe* crepe, int* splits);
+/* ---- A streaming tracker: ry_crepe_track window by window, with the activation rows of the frames two consecutive windows share taken from the
+ * previous call instead of being run through the network again (DESIGN.md section 18 states which rows).  A stream belongs to the model it was
+ * created from and is destroyed before it; a model serves any number of streams.  What a stream keeps (two activation blocks used in turn, the
+ * packed rows of the computed frames, two index tables) is its own: no call on the model, ry_crepe_debug_poison included, touches it. */
+typedef struct ry_crepe_stream ry_crepe_stream;
+int ry_crepe_stream_create(ry_crepe* crepe, ry_crepe_stream** out);
+void ry_crepe_stream_destroy(ry_crepe_stream* stream);
+/* forgets the kept rows: the next call computes every frame */
+int ry_crepe_stream_reset(ry_crepe_stream* stream);
+/* ry_crepe_track on a window of a live signal.  advance >= 0 and overlap_ok = 1: the caller declares that sample i of this window is sample
+ * i + advance of the previous window of this stream, and has verified it on the bit patterns of the overlap (the first
+ * min(n_samples, previous n_samples - advance) samples).  Rows are then kept when the advance is a whole number of 16 kHz samples and of hops,
+ * the rate's time register repeats exactly under it, and rate, hop, ry_crepe_set_dtype mode and filter table are those of the previous call: frame j
+ * takes the row of previous frame j + advance16 / hop when both are portable (their 1024 samples lie inside the signal, untouched by centre padding
+ * and by a resampler tap cut at an end of the signal).  Every other frame -- and with advance < 0 or overlap_ok = 0 every frame -- is computed;
+ * the rows are kept for the next call either way.  voiced / f0_64 / t_64, the masked track, the uploaded wave and what ry_crepe_track_buffers
+ * reports are bit for bit those of ry_crepe_track on the same window, whatever was kept.  *n_computed: the frames that went through the network.
+ * Refusals: those of ry_crepe_track and a null n_computed, made before anything is launched or written; a refused call leaves the kept rows as they
+ * were. */
+int ry_crepe_stream_track(ry_crepe_stream* stream, const float* audio, int n_samples, int sr, int hop, double step_ms, double threshold, int advance,
+                          int overlap_ok, int* n_frames, int* n_computed, unsigned char* voiced, double* f0_64, double* t_64, int on_device_out);
+/* the activation [n_frames][360] of the last ry_crepe_stream_track as it was assembled (host array, or on_device = 1 a device pointer);
+ * RY_ESTATE when the stream holds no window */
+int ry_crepe_stream_activation(ry_crepe_stream* stream, float* out, int on_device);
+/* tests: NaN bit patterns in the packed block, the tables on the card, the block the next call writes and every row of the kept block that is not
+ * portable -- everything but the rows the rule may hand to the next call.  *rows_left: the rows left alone. */
+int ry_crepe_stream_debug_poison(ry_crepe_stream* stream, int* rows_left);
+/* tests: the assembling kernel alone.  Row j of out_dev [n_rows][360] becomes row src[j] of keep_dev [n_keep][360] when src[j] >= 0, else row
+ * -1 - src[j] of fresh_dev [n_fresh][360]; a row whose source index lies outside its block is left as it is.  src is a host array; the blocks are
+ * device pointers, 16-byte aligned.  Waits for the stream. */
+int ry_crepe_stream_debug_assemble(ry_crepe_stream* stream, const float* keep_dev, int n_keep, const float* fresh_dev, int n_fresh, const int* src,
+                                   int n_rows, float* out_dev);
 /* tests (the predictors' counterpart of ry_crepe_debug_layer): one buffer of the launch plan that ran last on this handle (ry_net_forward, ry_ac_convert,
  * ry_sr_convert, ry_sr_convert_rows), copied to the host once its stream has drained.  layer -1, kind 0: the convert wrapper's padded input
  * [batch][T][cols] (stage 1: in_ch columns; stage 2: log of the spectrogram without its last bin, width columns).  layer 0 .. 15 (stage 2), kind 0:

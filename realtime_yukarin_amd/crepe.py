@@ -1,7 +1,8 @@
 """CREPE pitch tracker on the MI355X: network spec, weights (seeded synthetic, or a `.npz` / torch state-dict file), the host-side
 pieces (the resampler's tables and its host statement, the HMM tables, `predict_voicing`) and `CrepeModel`, the handle over `ry_crepe_*`
 (include/ry355.h), which resamples to 16 kHz, runs the network and decodes on the device; `CrepeModel.voicing` is `predict_voicing` and the
-wrapper's mask on the device, `CrepeModel.track` the whole chain in one call (`encode.extract` builds on it).
+wrapper's mask on the device, `CrepeModel.track` the whole chain in one call (`encode.extract` builds on it); `CrepeStream` is `track` window by
+window over a live signal, with the activation rows of the frames two windows share kept on the card (`ry_crepe_stream_*`).
 
 The reference turns CREPE on with `extract_f0_mode: crepe` (realtime-yukarin: realtime_voice_conversion/config.py:8-10); its
 CrepeAcousticFeatureWrapper.extract_f0 calls `crepe.predict(x, fs, viterbi=True, model_capacity='full', step_size=frame_period)` and
@@ -611,3 +612,94 @@ class CrepeModel(DeviceHandle):
         s = (ctypes.c_int * 7)()
         lib.check(lib.dll.ry_crepe_debug_splits(h, s))
         return list(s)
+
+
+class CrepeStream(DeviceHandle):
+    """`CrepeModel.track` window by window over a live signal (`ry_crepe_stream_*`): the activation rows of the frames a window shares with the
+    previous one are taken from that call instead of being run through the network again (DESIGN.md section 18 states which).  Call by call the
+    result has the bits of `model.track` on the same window.  `advance`: sample i of this window is sample i + advance of the previous window of
+    this stream; the object keeps the previous window and compares the overlap as 32-bit words before it says so to the device -- a window whose
+    overlap differs (zero padding that has become audio, say) is computed in full.  advance=None: computed in full, and kept for the next call.
+    `computed` / `frames`: the frames of the last call that went through the network / that it has.  A model serves any number of streams."""
+    _destroy = 'ry_crepe_stream_destroy'
+
+    def __init__(self, model: CrepeModel):
+        self.model = model
+        self.computed = self.frames = 0
+        self._prev = None
+        self._model_handle = None
+        DeviceHandle.__init__(self, model._given_ctx, model.device)
+
+    def __getstate__(self):
+        d = DeviceHandle.__getstate__(self)
+        d.update(_prev=None, _model_handle=None)
+        return d
+
+    def _get(self):
+        """-> (library, stream handle) of this process, over the model's handle as it is now."""
+        lib, mh = self.model._get()
+        if self._handle is None or self._pid != os.getpid() or self._model_handle is not mh:
+            h = ctypes.c_void_p()
+            lib.check(lib.dll.ry_crepe_stream_create(mh, ctypes.byref(h)))
+            self._ctx, self._handle, self._pid, self._model_handle, self._prev = self.model._ctx, h, os.getpid(), mh, None
+        return lib, self._handle
+
+    def close(self):
+        DeviceHandle.close(self)                                   # the handle frees its own blocks and reads nothing of the model
+        self._prev = self._model_handle = None
+
+    def reset(self) -> None:
+        """Forgets the kept rows and the previous window: the next call computes every frame."""
+        self._prev = None
+        if self._handle is not None and self._pid == os.getpid():
+            lib, h = self._get()
+            lib.check(lib.dll.ry_crepe_stream_reset(h))
+
+    def _overlap_ok(self, x, advance) -> bool:
+        old = self._prev
+        if advance is None or old is None or not 0 <= advance < old.size:
+            return False
+        m = min(x.size, old.size - advance)
+        return bool(numpy.array_equal(x[:m].view(numpy.uint32), old[advance:advance + m].view(numpy.uint32)))
+
+    def track(self, audio, sr, hop: int, step_size, threshold: float = 0.1, advance: Optional[int] = None, device: bool = False):
+        """What `CrepeModel.track` returns for the window (`ry_crepe_stream_track`)."""
+        sr = _rate(sr)
+        x = numpy.ascontiguousarray(audio, dtype=numpy.float32).ravel()
+        lib, h = self._get()
+        model = self.model
+        n = model._frames_at(x.size, sr, hop)
+        adv = -1 if advance is None else int(advance)
+        ok = self._overlap_ok(x, None if advance is None else adv)
+        nf, nc = ctypes.c_int(), ctypes.c_int()
+        head = (h, _lib._fptr(x), x.size, sr, int(hop), float(step_size), float(threshold), adv, int(ok), ctypes.byref(nf), ctypes.byref(nc))
+        if not device:
+            voiced, f64, t64 = numpy.empty(n, numpy.uint8), numpy.empty(n, numpy.float64), numpy.empty(n, numpy.float64)
+            lib.check(lib.dll.ry_crepe_stream_track(*head, voiced.ctypes.data_as(_UBP), _dptr(f64), _dptr(t64), 0))
+        else:
+            lib.check(lib.dll.ry_crepe_stream_track(*head, None, None, None, 1))
+        assert nf.value == n, (nf.value, n)
+        self._prev = x.copy()                                      # after the call: a refused window is not the previous one
+        self.frames, self.computed = nf.value, nc.value
+        if not device:
+            return voiced.astype(bool), f64, t64
+        mh = self._model_handle
+        p = [ctypes.c_void_p() for _ in range(4)]
+        ns, nfr = ctypes.c_int(), ctypes.c_int()
+        lib.check(lib.dll.ry_crepe_track_buffers(mh, ctypes.byref(p[0]), ctypes.byref(ns), ctypes.byref(nfr), *[ctypes.byref(q) for q in p[1:]]))
+        return DeviceTrack(model, model._ctx, p[0].value, ns.value, nfr.value, p[1].value, p[2].value, p[3].value)
+
+    def activation(self) -> numpy.ndarray:
+        """The assembled activation [frames][360] of the last call (`ry_crepe_stream_activation`)."""
+        lib, h = self._get()
+        out = numpy.empty((self.frames, BINS), numpy.float32)
+        lib.check(lib.dll.ry_crepe_stream_activation(h, _lib._fptr(out), 0))
+        return out
+
+    def poison(self) -> int:
+        """Tests: NaN bit patterns in everything of the stream but the rows the next call may keep -> how many those are
+        (`ry_crepe_stream_debug_poison`)."""
+        lib, h = self._get()
+        left = ctypes.c_int()
+        lib.check(lib.dll.ry_crepe_stream_debug_poison(h, ctypes.byref(left)))
+        return left.value

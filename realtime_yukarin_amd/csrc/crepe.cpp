@@ -9,6 +9,9 @@
 // ry_crepe_track_many is ry_crepe_track for a list of waves in one enqueue: the waves are uploaded back to back with a segment table (CrepeSeg), the
 // resampler runs over all of them, their frames share the passes of CHUNK, and the decode and the voicing run one workgroup per track.
 // ry_crepe_set_dtype(2) runs the seven GEMMs in split-bf16 form (crepe_igemm_x3) on filters split once into two bf16 planes; everything else is shared.
+// ry_crepe_stream_track is ry_crepe_track window by window over a live signal: the activation rows of the frames a window shares with the previous
+// one are kept on the card (two blocks used in turn), only the other frames run through the network (crepe_frames with a frame index list), and
+// crepe_act_assemble builds the window's block from both (DESIGN.md section 18 states which rows may be kept).
 #include "crepe_kernels.h"
 #include "ry_host.h"
 
@@ -91,6 +94,7 @@ struct ry_crepe {
     // resampling: tables per input rate
     Arena rs_tables;
     std::map<int, Resampler> rs;
+    int rs_epoch = 0;                               // counts the filter tables installed: rows a stream kept under another filter are not reused
     // ry_crepe_set_dtype: 0 = fp32 MFMA, 2 = split-bf16.  The filters of every layer as two bf16 planes (layer i at L[i].w_off), built at the
     // first switch to 2.  They are weights: a list of their own, which ry_crepe_debug_poison does not walk.
     int dtype = 0;
@@ -98,6 +102,28 @@ struct ry_crepe {
     DevBuf<unsigned short> w_hi{planes}, w_lo{planes};
     bool planes_built = false;
     int splits_of(int i) const { return dtype == 2 ? L[i].splits_x3 : L[i].splits; }
+};
+
+// A streaming tracker over a model (ry_crepe_stream_track): the activation rows of the last window, kept on the card for the next one.
+// Nothing here is on the model's buffer list: no call on the model, ry_crepe_debug_poison included, touches what a stream keeps.
+struct ry_crepe_stream {
+    ry_ctx* ctx = nullptr;
+    ry_crepe* model = nullptr;
+    DevBufList bufs;
+    DevBuf<float> act0{bufs}, act1{bufs}, fresh{bufs};      // the two activation blocks used in turn, the packed rows of the computed frames
+    DevBuf<int> tab{bufs};                                  // src [frames] | idx [computed] of the last upload
+    DevBuf<float>& act(int i) { return i ? act1 : act0; }
+    std::vector<int> tab_host[2];                           // the tables of the last two uploads (the host array of a copy outlives the call)
+    int tab_cur = -1;                                       // which of the two the card holds; -1: none
+    // the kept call: its block, frames, samples at the caller's rate and at 16 kHz, rate, hop, arithmetic, and which frames were portable
+    bool valid = false;
+    int kept = 0, nf = 0, n_in = 0, n16 = 0, sr = 0, hop = 0, dtype = 0, rs_epoch = 0;
+    std::vector<char> portable;
+    // what the rule needs of a window length / an advance, remembered: the portable frames of (rate, samples, hop), the verdict of the register
+    // check of (rate, advance, outputs checked).  Both follow from the rate's tables alone and are dropped when the filter changes.
+    std::map<std::tuple<int, int, int>, std::vector<char>> portable_of;
+    std::map<std::tuple<int, int, int>, bool> repeats_of;
+    int cache_epoch = 0;
 };
 
 namespace {
@@ -212,21 +238,30 @@ int frame_count(int n_samples, int hop, int center, int* nf) {
     return RY_OK;
 }
 
+// The network on n rows in passes of CHUNK: row b is frame b of the call, or frame idx[b] of it (`idx`: a device list of n frame indices, packed
+// back to back); the dense layer writes row b of `rows`.  ensure_chunk has run.
+int run_passes(ry_crepe* c, const float* d_audio, int n_samples, int hop, int center, int n, const int* idx, float* rows,
+               const CrepeSeg* seg = nullptr, int n_seg = 1) {
+    const ry_stream_t s = c->ctx->stream;
+    for (int f = 0; f < n; f += CHUNK) {
+        const int k = std::min(CHUNK, n - f);
+        CrepeFrameParams fp;
+        fp.audio = d_audio; fp.n = n_samples; fp.hop = hop; fp.center = center; fp.frame0 = f; fp.n_frames = k; fp.out = c->act_in[0];
+        fp.seg = seg; fp.n_seg = n_seg; fp.idx = idx;
+        RY_LAUNCH(crepe_frames, dim3((unsigned)k), 256, s, fp);
+        RT_TRY(rt::last_error());
+        for (int i = 0; i <= NCONV; ++i) RY_TRY(launch_layer(c, i, k, rows + (size_t)f * CREPE_BINS));
+        c->last_chunk = k;
+    }
+    return RY_OK;
+}
+
 // the network and the decode on n_samples at 16 kHz in device memory, results to the caller (ensure_chunk / ensure_call have run)
 int run_network(ry_crepe* c, const float* d_audio, int n_samples, int hop, int center, int viterbi, int nf,
                 float* f0, float* confidence, float* activation, int on_device, const CrepeSeg* seg = nullptr, int n_seg = 1) {
     const ry_stream_t s = c->ctx->stream;
     float* act_all = c->act.ptr();
-    for (int f = 0; f < nf; f += CHUNK) {
-        const int n = std::min(CHUNK, nf - f);
-        CrepeFrameParams fp;
-        fp.audio = d_audio; fp.n = n_samples; fp.hop = hop; fp.center = center; fp.frame0 = f; fp.n_frames = n; fp.out = c->act_in[0];
-        fp.seg = seg; fp.n_seg = n_seg;
-        RY_LAUNCH(crepe_frames, dim3((unsigned)n), 256, s, fp);
-        RT_TRY(rt::last_error());
-        for (int i = 0; i <= NCONV; ++i) RY_TRY(launch_layer(c, i, n, act_all + (size_t)f * CREPE_BINS));
-        c->last_chunk = n;
-    }
+    RY_TRY(run_passes(c, d_audio, n_samples, hop, center, nf, nullptr, act_all, seg, n_seg));
     RY_TRY(launch_decode(c, act_all, nf, viterbi, seg, n_seg));
     if (!f0 && !confidence && !activation) return RY_OK;                // ry_crepe_track: the results stay in the handle's buffers
     if (on_device) {
@@ -324,6 +359,115 @@ int upload_segments(ry_crepe* c, const std::vector<CrepeSeg>& plan) {
 int voicing_args(double threshold, double step_ms) {
     if (std::isnan(threshold)) return fail(RY_EINVAL, "threshold %g", threshold);
     if (!std::isfinite(step_ms) || !(step_ms > 0.0)) return fail(RY_EINVAL, "step %g ms", step_ms);
+    return RY_OK;
+}
+
+// ---- which rows of the previous window a streamed call may keep ----
+// The frames of a window of n_in samples at sr (r: the rate's tables, null at 16 kHz) that are portable: the whole support [f hop - 512,
+// f hop + 512) lies inside the 16 kHz signal and every output in it is clean -- neither tap loop of crepe_resample is cut by an end of the signal
+// (room >= lim on both sides, in the kernel's own arithmetic on the host copy of the register).
+std::vector<char> portable_frames(const Resampler* r, int sr, int n_in, int hop) {
+    std::vector<char> out;
+    if (n_in < 1) return out;
+    int n16 = n_in;
+    if (r) {
+        const double nd = (double)n_in * (16000.0 / sr);
+        n16 = nd < (double)r->n_times ? (int)nd : r->n_times;
+    }
+    if (n16 < 1) return out;
+    std::vector<int> cut((size_t)n16 + 1, 0);                       // cut[t]: outputs before t that are not clean
+    if (r) {
+        const double ratio = 16000.0 / sr, scale = ratio < 1.0 ? ratio : 1.0;
+        for (int t = 0; t < n16; ++t) {
+            const double tr = r->tr_host[(size_t)t];
+            const int n = (int)tr;
+            const double frac0 = scale * (tr - (double)n);
+            bool clean = true;
+            for (int side = 0; side < 2; ++side) {
+                const double frac = side ? scale - frac0 : frac0;
+                const int offset = (int)(frac * (double)r->num_table);
+                const int lim = (r->n_win - offset) / r->step;
+                const int room = side ? n_in - n - 1 : n + 1;
+                if (room < lim) clean = false;
+            }
+            cut[(size_t)t + 1] = cut[(size_t)t] + (clean ? 0 : 1);
+        }
+    }
+    const int nf = 1 + n16 / hop;
+    out.assign((size_t)nf, 0);
+    for (int f = 0; f < nf; ++f) {
+        const long long lo = (long long)f * hop - CREPE_FRAME / 2, hi = lo + CREPE_FRAME;
+        if (lo >= 0 && hi <= n16 && cut[(size_t)hi] == cut[(size_t)lo]) out[(size_t)f] = 1;
+    }
+    return out;
+}
+
+const std::vector<char>& portable_cached(ry_crepe_stream* s, const Resampler* r, int sr, int n_in, int hop) {
+    const auto key = std::make_tuple(sr, n_in, hop);
+    auto it = s->portable_of.find(key);
+    if (it != s->portable_of.end()) return it->second;
+    if (s->portable_of.size() >= 32) s->portable_of.clear();       // a live stream repeats a handful of lengths
+    return s->portable_of[key] = portable_frames(r, sr, n_in, hop);
+}
+
+// the rate's time register repeats exactly under the advance: tr[t + a16] == tr[t] + advance, as doubles, for the first n_check outputs
+bool register_repeats(ry_crepe_stream* s, const Resampler& r, int sr, int advance, long long a16, int n_check) {
+    const auto key = std::make_tuple(sr, advance, n_check);
+    const auto it = s->repeats_of.find(key);
+    if (it != s->repeats_of.end()) return it->second;
+    bool ok = true;
+    for (int t = 0; t < n_check && ok; ++t) {
+        if (t + a16 >= r.n_times) { ok = false; break; }
+        const double t_new = r.tr_host[(size_t)t], t_old = r.tr_host[(size_t)(t + a16)];
+        // ... and so do the two numbers the kernel takes from it, the first tap and the fraction (a sum that rounds could pass the first test alone)
+        ok = t_old == t_new + (double)advance && (int)t_old == (int)t_new + advance && t_old - (double)(int)t_old == t_new - (double)(int)t_new;
+    }
+    if (s->repeats_of.size() >= 32) s->repeats_of.clear();
+    return s->repeats_of[key] = ok;
+}
+
+// The tables of a streamed call of nf frames over n_samples at sr: src [nf] (>= 0: the kept row; else -1 - the row of the packed block) followed
+// by idx [computed] (the window frames the packed rows are computed from).  -> the number of computed frames.  Host work only.
+int plan_stream(ry_crepe_stream* s, const Resampler* r, int n_samples, int sr, int hop, int nf, int advance, int overlap_ok, std::vector<int>* tab) {
+    const ry_crepe* c = s->model;
+    if (s->cache_epoch != c->rs_epoch) { s->portable_of.clear(); s->repeats_of.clear(); s->cache_epoch = c->rs_epoch; }
+    bool reuse = s->valid && overlap_ok && advance >= 0 && advance < s->n_in && sr == s->sr && hop == s->hop && c->dtype == s->dtype &&
+                 c->rs_epoch == s->rs_epoch;
+    long long a16 = 0;
+    int d = 0, m = 0;
+    if (reuse) {
+        const long long num = (long long)advance * 16000;
+        a16 = num / sr;
+        reuse = num % sr == 0 && a16 % hop == 0;
+        d = (int)(a16 / hop);
+        m = std::min(n_samples, s->n_in - advance);
+    }
+    const std::vector<char>* pm = nullptr;                          // the new window read as m samples long
+    if (reuse) {
+        pm = &portable_cached(s, r, sr, m, hop);
+        if (r && !pm->empty()) {
+            const double nd = (double)m * (16000.0 / sr);
+            const long long left = (long long)s->n16 - a16;
+            reuse = register_repeats(s, *r, sr, advance, a16, (int)std::max(0LL, std::min((long long)nd, left)));
+        }
+    }
+    tab->assign((size_t)nf, 0);
+    int k = 0;
+    for (int j = 0; j < nf; ++j) {
+        const bool keep = reuse && j < (int)pm->size() && (*pm)[(size_t)j] && j + d < s->nf && s->portable[(size_t)(j + d)];
+        (*tab)[(size_t)j] = keep ? j + d : -1 - k++;
+    }
+    tab->resize((size_t)nf + (size_t)k);
+    for (int j = 0, q = 0; j < nf; ++j)
+        if ((*tab)[(size_t)j] < 0) (*tab)[(size_t)nf + (size_t)q++] = j;
+    return k;
+}
+
+int launch_assemble(ry_ctx* ctx, const float* keep, int n_keep, const float* fresh, int n_fresh, const int* src, float* out, int n_rows) {
+    CrepeAssembleParams p;
+    p.keep = keep; p.n_keep = n_keep; p.fresh = fresh; p.n_fresh = n_fresh; p.src = src; p.out = out; p.n_rows = n_rows;
+    RY_LAUNCH(crepe_act_assemble, dim3((unsigned)((n_rows + 3) / 4)), 256, ctx->stream, p);
+    RT_TRY(rt::last_error());
     return RY_OK;
 }
 }  // namespace
@@ -500,6 +644,7 @@ int ry_crepe_set_resampler(ry_crepe* c, int sr, const double* win, int n_win, in
         RY_TRY(upload_table(c->rs_tables, c->ctx, win, (size_t)n_win, &d));
         if (r.win) c->rs_tables.free_one(r.win);
         r.win = d; r.n_win = n_win; r.num_table = num_table; r.step = step;
+        ++c->rs_epoch;
     }
     double* d = nullptr;
     RY_TRY(upload_table(c->rs_tables, c->ctx, time_register, (size_t)n_times, &d));
@@ -813,6 +958,146 @@ int ry_crepe_debug_poison(ry_crepe* c) {
 int ry_crepe_debug_splits(ry_crepe* c, int* splits) {
     if (!c || !splits) return fail(RY_EINVAL, "bad argument");
     for (int i = 0; i <= NCONV; ++i) splits[i] = c->splits_of(i);
+    return RY_OK;
+}
+
+int ry_crepe_stream_create(ry_crepe* c, ry_crepe_stream** out) {
+    if (!out) return fail(RY_EINVAL, "null out pointer");
+    *out = nullptr;
+    RY_TRY(check_handle(c, "crepe"));
+    ry_crepe_stream* s = new ry_crepe_stream();
+    s->ctx = c->ctx;
+    s->model = c;
+    *out = s;
+    return RY_OK;
+}
+
+void ry_crepe_stream_destroy(ry_crepe_stream* s) {
+    if (!s) return;
+    rt::set_device(s->ctx->device);
+    rt::stream_sync(s->ctx->stream);
+    delete s;
+}
+
+int ry_crepe_stream_reset(ry_crepe_stream* s) {
+    if (!s) return fail(RY_ESTATE, "null crepe stream handle");
+    s->valid = false;
+    return RY_OK;
+}
+
+int ry_crepe_stream_track(ry_crepe_stream* st, const float* audio, int n_samples, int sr, int hop, double step_ms, double threshold, int advance,
+                          int overlap_ok, int* n_frames, int* n_computed, unsigned char* voiced, double* f0_64, double* t_64, int on_device_out) {
+    RY_TRY(check_handle(st, "crepe stream"));
+    ry_crepe* c = st->model;
+    // the refusals of ry_crepe_track, before anything is launched or written: the kept rows stay as they were
+    if (!audio || !n_frames || !n_computed || n_samples < 1 || hop < 1) return fail(RY_EINVAL, "bad argument");
+    if (!on_device_out && (!voiced || !f0_64 || !t_64)) return fail(RY_EINVAL, "null output");
+    RY_TRY(voicing_args(threshold, step_ms));
+    forget_track(c);
+    const ry_stream_t s = c->ctx->stream;
+    const Resampler* r = nullptr;
+    int n16 = n_samples, nf = 0;
+    if (sr != 16000) RY_TRY(resample_plan(c, n_samples, sr, &r, &n16));
+    RY_TRY(frame_count(n16, hop, 1, &nf));
+    std::vector<int>& tab = st->tab_host[st->tab_cur == 0 ? 1 : 0];
+    const int n_comp = plan_stream(st, r, n_samples, sr, hop, nf, advance, overlap_ok, &tab);
+    const bool all = n_comp == nf;                                    // nothing kept: the dense layer writes the window's block itself
+    const int w = st->valid ? 1 - st->kept : 0;
+    const float* keep = st->valid ? st->act(st->kept).ptr() : nullptr;
+    const int n_keep = st->valid ? st->nf : 0;
+    RY_TRY(ensure_chunk(c, std::min(n_comp, CHUNK)));
+    RY_TRY(ensure_call(c, nf, n16));
+    RY_TRY(ensure_track(c, nf));
+    RY_TRY(st->act(w).grow(c->ctx, (long long)nf * CREPE_BINS));      // the other block: the kept rows do not move
+    if (!all) {
+        RY_TRY(st->fresh.grow(c->ctx, (long long)n_comp * CREPE_BINS));
+        RY_TRY(st->tab.grow(c->ctx, (long long)tab.size()));
+        if (st->tab_cur < 0 || st->tab_host[st->tab_cur] != tab) {    // one copy for both tables, and only when they changed
+            RT_TRY(rt::h2d(st->tab.ptr(), tab.data(), tab.size() * sizeof(int), s));
+            st->tab_cur = st->tab_cur == 0 ? 1 : 0;
+        }
+    }
+    st->valid = false;                                                // from here on the block about to be written is in play
+    float* wave = c->audio.ptr();                                     // the one upload: the wave at the caller's rate
+    if (r) {
+        RY_TRY(c->audio_sr.reserve(c->ctx, n_samples));
+        wave = c->audio_sr.ptr();
+    }
+    RT_TRY(rt::h2d(wave, audio, (size_t)n_samples * sizeof(float), s));
+    if (r) RY_TRY(launch_resample(c, *r, wave, n_samples, sr, c->audio.ptr(), n16));
+    float* act = st->act(w).ptr();
+    if (all) {
+        RY_TRY(run_passes(c, c->audio.ptr(), n16, hop, 1, nf, nullptr, act));
+    } else {
+        RY_TRY(run_passes(c, c->audio.ptr(), n16, hop, 1, n_comp, st->tab.ptr() + nf, st->fresh.ptr()));
+        RY_TRY(launch_assemble(c->ctx, keep, n_keep, st->fresh.ptr(), n_comp, st->tab.ptr(), act, nf));
+    }
+    RY_TRY(launch_decode(c, act, nf, 1));
+    RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), nf, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr()));
+    c->trk_wave = wave; c->trk_samples = n_samples; c->trk_frames = nf;
+    st->kept = w; st->nf = nf; st->n_in = n_samples; st->n16 = n16; st->sr = sr; st->hop = hop; st->dtype = c->dtype; st->rs_epoch = c->rs_epoch;
+    st->portable = portable_cached(st, r, sr, n_samples, hop);
+    st->valid = true;
+    *n_frames = nf;
+    *n_computed = n_comp;
+    if (on_device_out) return RY_OK;
+    RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)nf, s));
+    RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)nf * sizeof(double), s));
+    RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)nf * sizeof(double), s));
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+int ry_crepe_stream_activation(ry_crepe_stream* st, float* out, int on_device) {
+    RY_TRY(check_handle(st, "crepe stream"));
+    if (!out) return fail(RY_EINVAL, "bad argument");
+    if (!st->valid) return fail(RY_ESTATE, "the stream holds no window: ry_crepe_stream_track has not run, or ry_crepe_stream_reset came after it");
+    const ry_stream_t s = st->ctx->stream;
+    const size_t bytes = (size_t)st->nf * CREPE_BINS * sizeof(float);
+    if (on_device) { RT_TRY(rt::d2d(out, st->act(st->kept).ptr(), bytes, s)); return RY_OK; }
+    RT_TRY(rt::d2h(out, st->act(st->kept).ptr(), bytes, s));
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+int ry_crepe_stream_debug_poison(ry_crepe_stream* st, int* rows_left) {
+    RY_TRY(check_handle(st, "crepe stream"));
+    if (!rows_left) return fail(RY_EINVAL, "bad argument");
+    const ry_stream_t s = st->ctx->stream;
+    RT_TRY(rt::stream_sync(s));
+    // all bits set in the packed block, the tables on the card, the block about to be written and every kept row that is not portable: the rows
+    // the rule may hand to the next call are the only ones left alone
+    RY_TRY(st->fresh.poison(s));
+    RY_TRY(st->tab.poison(s));
+    st->tab_cur = -1;
+    const int w = st->valid ? 1 - st->kept : 0;
+    RY_TRY(st->act(w).poison(s));
+    int left = 0;
+    if (st->valid) {
+        DevBuf<float>& k = st->act(st->kept);
+        for (long long f = 0; f * CREPE_BINS < k.cap; ++f) {
+            if (f < st->nf && st->portable[(size_t)f]) { ++left; continue; }
+            const long long n = std::min((long long)CREPE_BINS, k.cap - f * CREPE_BINS);
+            RT_TRY(rt::dmemset(k.ptr() + f * CREPE_BINS, 0xff, (size_t)n * sizeof(float), s));
+        }
+    } else {
+        RY_TRY(st->act(1 - w).poison(s));
+    }
+    RT_TRY(rt::stream_sync(s));
+    *rows_left = left;
+    return RY_OK;
+}
+
+int ry_crepe_stream_debug_assemble(ry_crepe_stream* st, const float* keep_dev, int n_keep, const float* fresh_dev, int n_fresh, const int* src,
+                                   int n_rows, float* out_dev) {
+    RY_TRY(check_handle(st, "crepe stream"));
+    if (!keep_dev || !fresh_dev || !src || !out_dev || n_keep < 0 || n_fresh < 0 || n_rows < 1 || n_rows > (1 << 24)) return fail(RY_EINVAL, "bad argument");
+    const ry_stream_t s = st->ctx->stream;
+    RY_TRY(st->tab.grow(st->ctx, n_rows));
+    st->tab_cur = -1;                                                 // the card's tables are no longer those of a call
+    RT_TRY(rt::h2d(st->tab.ptr(), src, (size_t)n_rows * sizeof(int), s));
+    RY_TRY(launch_assemble(st->ctx, keep_dev, n_keep, fresh_dev, n_fresh, st->tab.ptr(), out_dev, n_rows));
+    RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }
 

@@ -2,7 +2,7 @@
 // v_mfma_f32_32x32x2_f32 (conv1 .. conv6 and the dense classifier) and its split-bf16 form on v_mfma_f32_32x32x16_bf16, the split-K reduction with the
 // same epilogues, and the decode
 // (per-frame argmax / max, the 360-state Viterbi pass in float64, the local-average cents), and the voicing of the track (a two-state Viterbi
-// pass over the confidence, the masked float64 f0 and the time axis).
+// pass over the confidence, the masked float64 f0 and the time axis), and the assembly of a streamed window's activation block from kept and fresh rows.
 // Semantics restated from the public crepe package and its PyTorch fork ([MEM]; INTEGRATION.md section 9 lists what is unpinned).
 //
 // Activations are channels-last with every frame's 'same' padding stored as zero rows, so the kernels never test an edge:
@@ -57,12 +57,15 @@ RY_DEV int crepe_seg_of_sample16(const CrepeSeg* seg, int n_seg, int t) {
     return lo;
 }
 
-struct CrepeFrameParams { const float* audio; int n, hop, center, frame0, n_frames; float* out; const CrepeSeg* seg; int n_seg; };
+// A frame index list (`idx`; null: workgroup b frames frame frame0 + b) packs chosen frames of a window into the passes: workgroup b of a pass
+// frames window frame idx[frame0 + b] into row b (ry_crepe_stream_track: the frames whose rows the previous call cannot supply).
+struct CrepeFrameParams { const float* audio; int n, hop, center, frame0, n_frames; float* out; const CrepeSeg* seg; int n_seg; const int* idx; };
 
 RY_KERNEL(256) void crepe_frames(CrepeFrameParams p) {
     __shared__ double red[256];
     const int tid = (int)threadIdx.x;
     int f = p.frame0 + (int)blockIdx.x;
+    if (p.idx) f = p.idx[f];                                       // block-uniform: row blockIdx.x of the pass holds this frame of the window
     const float* audio = p.audio;
     int n_audio = p.n;
     if (p.seg) {                                                   // block-uniform: frame f of the call is frame f - frame0 of its wave
@@ -587,6 +590,26 @@ RY_KERNEL(384) void crepe_decode(CrepeDecodeParams p) {
         const double f = 10.0 * exp2((ps / ws) / 1200.0);
         p.f0[t] = CREPE_ISNAN(f) ? 0.f : (float)f;
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The activation block of a streamed window (ry_crepe_stream_track): row j is row src[j] of the block the previous call left (`keep`) when
+// src[j] >= 0, else row -1 - src[j] of the rows this call computed (`fresh`, packed back to back).  A row is 360 floats = 90 words of 16 bytes,
+// 16-byte aligned in every block; one wave per row, lane l moves words l and l + 64: consecutive lanes, consecutive 16 bytes.  A source index
+// outside its block reads nothing and writes nothing.  One launch instead of one copy per kept row.
+// ---------------------------------------------------------------------------------------------
+struct CrepeAssembleParams { const float* keep; int n_keep; const float* fresh; int n_fresh; const int* src; float* out; int n_rows; };
+
+RY_KERNEL(256) void crepe_act_assemble(CrepeAssembleParams p) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int j = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (j >= p.n_rows) return;                                     // wave-uniform, like everything up to the copy
+    const long long s = p.src[j];
+    const long long f = -1 - s;
+    if (s >= 0 ? s >= p.n_keep : f >= p.n_fresh) return;
+    const float* from = s >= 0 ? p.keep + (size_t)s * CREPE_BINS : p.fresh + (size_t)f * CREPE_BINS;
+    float* to = p.out + (size_t)j * CREPE_BINS;
+    for (int q = lane; q < CREPE_BINS / 4; q += 64) ry_st4(to + 4 * q, ry_ld4(from + 4 * q));
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -83,6 +83,7 @@ class Pipeline(object):
         self._vocoder = _Vocoder(acoustic_param, voice_changer.output_sampling_rate, self.synth)
         self.calls = calls
         self._blocks, self._cap, self._ctx, self._pid = {}, 0, None, None
+        self._crepe_stream = None                                          # `push(..., advance=a)`: the tracker that keeps rows between buffers
 
     # ---- the blocks this object owns: grown, never shrunk, freed by `close` in the process that made them
     def _reserve(self, ctx, n: int, m_in: int, m_out: int, f_out: int) -> dict:
@@ -109,7 +110,24 @@ class Pipeline(object):
     def close(self) -> None:
         """Frees the device blocks and the synthesizer in the process that created them; the voice changer and the shared handles stay."""
         self._free()
+        self._drop_stream()
         self.synth.close()
+
+    def _stream_of(self, model):
+        """The pipeline's `CrepeStream` over `model` (made on first use; a stream over another model is closed)."""
+        if self._crepe_stream is None or self._crepe_stream.model is not model:
+            self._drop_stream()
+            self._crepe_stream = _crepe.CrepeStream(model)
+        return self._crepe_stream
+
+    def _drop_stream(self) -> None:
+        if self._crepe_stream is not None:
+            self._crepe_stream.close()
+            self._crepe_stream = None
+
+    def _reset_stream(self) -> None:
+        if self._crepe_stream is not None:
+            self._crepe_stream.reset()
 
     # ---- which way a call goes
     def _encode_args(self):
@@ -149,14 +167,17 @@ class Pipeline(object):
         return model, analyzer, core, gate.thresholds(thr), hop, int(gp.fft_length)
 
     # ---- the resident chain up to the rows the synthesizer reads
-    def _resident_rows(self, wave, handles, discard):
-        """-> (context, blocks, frames, f0 float64 [frames]: the converted track, zeros on the silent frames)."""
+    def _resident_rows(self, wave, handles, discard, advance=None):
+        """-> (context, blocks, frames, f0 float64 [frames]: the converted track, zeros on the silent frames).  advance (an int): the track comes
+        from the pipeline's `CrepeStream` -- the same bits, with the rows of the frames shared with the previous buffer kept."""
         model, analyzer, core, (p_eff, p_all), hop, gate_fft = handles
         vc, p = self.voice_changer, self.acoustic_param
         ac = vc.acoustic_converter
         fs = int(wave.sampling_rate)
         x = numpy.ascontiguousarray(wave.wave, dtype=numpy.float32)
-        trk = model.track(x, fs, _crepe.hop_length(p.frame_period), p.frame_period, threshold=encode.threshold, device=True)     # the one upload
+        tracker = model if advance is None else self._stream_of(model)
+        extra = {} if advance is None else dict(advance=int(advance))
+        trk = tracker.track(x, fs, _crepe.hop_length(p.frame_period), p.frame_period, threshold=encode.threshold, device=True, **extra)     # the one upload
         n, ctx = trk.frames, core.stage1.ctx
         b = self._reserve(ctx, n, p.order + 1, core.M, core.F)
         analyzer.extract_resident(trk.wave, trk.samples, trk.f0, trk.t, n, b['mc32'], b['sp32'], b['ap32'])
@@ -208,15 +229,19 @@ class Pipeline(object):
                                        y.ctypes.data_as(world_synth._DP), y.size, ctypes.byref(got)))
         return Wave(y[:got.value], sampling_rate=self.voice_changer.output_sampling_rate)
 
-    def push(self, wave, discard=(0, 0), final: bool = False):
+    def push(self, wave, discard=(0, 0), final: bool = False, advance: Optional[int] = None):
         """One buffer of a live stream: the wave is encoded and converted on its own (as `EncodeStream` / `ConvertStream` do per buffer), the rows
         [front, frames - back) -- what `ConvertStream.process` picks -- go to the synthesis stream, and the samples that are final come back.
-        final=True: the stream ends with this buffer (`flush` follows)."""
+        final=True: the stream ends with this buffer (`flush` follows).  advance (an int): sample i of this buffer is sample i + advance of the previous
+        one -- consecutive windows of `time_length + 2 * extra_time` share `2 * extra_time` of audio -- and the resident path tracks through a
+        `CrepeStream`, which keeps the activation rows of the shared frames when the overlap really holds the same samples: the same bits, fewer frames
+        through the network.  The kept rows are dropped by `flush`, by final=True and by a buffer that takes the composed path."""
         from yukarin import Wave
         front, back = int(discard[0]), int(discard[1])
         handles = self._resident_handles(wave)
         if handles is None:
             calls['composed'] += 1
+            self._reset_stream()
             f = self._composed_feature(wave, (front, back))
             k0, k1 = front, len(f.f0) - back
             out = numpy.empty(0, numpy.float64)
@@ -225,7 +250,7 @@ class Pipeline(object):
                 out = world_synth.decode_realtime(self._vocoder, picked).wave
         else:
             calls['resident'] += 1
-            ctx, b, n, f0 = self._resident_rows(wave, handles, (front, back))
+            ctx, b, n, f0 = self._resident_rows(wave, handles, (front, back), advance)
             k0, k1 = front, n - back
             out = numpy.empty(0, numpy.float64)
             if k1 > k0:
@@ -239,11 +264,13 @@ class Pipeline(object):
                 out = y[:got.value].copy()
         if final:
             out = numpy.concatenate([out, self.synth.flush()])
+            self._reset_stream()
         return Wave(wave=out, sampling_rate=self.voice_changer.output_sampling_rate)
 
     def flush(self):
         """Ends the live stream: the samples `push` still held back; the next `push` starts a new signal."""
         from yukarin import Wave
+        self._reset_stream()
         return Wave(wave=self.synth.flush(), sampling_rate=self.voice_changer.output_sampling_rate)
 
 
