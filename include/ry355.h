@@ -457,6 +457,41 @@ int ry_crepe_stream_debug_poison(ry_crepe_stream* stream, int* rows_left);
  * device pointers, 16-byte aligned.  Waits for the stream. */
 int ry_crepe_stream_debug_assemble(ry_crepe_stream* stream, const float* keep_dev, int n_keep, const float* fresh_dev, int n_fresh, const int* src,
                                    int n_rows, float* out_dev);
+/* ---- A bank of streaming trackers: ry_crepe_track_many on the next windows of several live streams, each wave under the rule of
+ * ry_crepe_stream_track against the kept call of its own stream.  A bank belongs to the model it was created from and is
+ * destroyed before it.  Every stream has a pair of activation slots of its own, used in turn by the calls it takes part in, so a stream that sits
+ * calls out finds its rows intact; the packed rows of the computed frames and two sets of tables belong to the bank.  None of it is on the model's
+ * buffer list: no call on the model, ry_crepe_debug_poison included, touches it, and streams and banks of one model do not disturb each other. */
+typedef struct ry_crepe_bank ry_crepe_bank;
+int ry_crepe_bank_create(ry_crepe* crepe, int n_streams, ry_crepe_bank** out);
+void ry_crepe_bank_destroy(ry_crepe_bank* bank);
+/* forgets the kept rows of one stream, or with stream = -1 of every stream */
+int ry_crepe_bank_reset(ry_crepe_bank* bank, int stream);
+/* ry_crepe_track_many on n_waves waves (audio: the waves back to back, n_samples[i] each), wave i being the next window of stream stream_of[i]:
+ * advance[i] / overlap_ok[i] are what ry_crepe_stream_track takes for it, n_computed[i] the frames of wave i that went through the network.  One
+ * upload of the audio, one segment table, one resample launch, the computed frames of all waves packed into the passes of the network, one launch
+ * that assembles every wave's block, one Viterbi and one voicing workgroup per wave.  Everything written for wave i has the bits of ry_crepe_track on
+ * it alone, and the track is left on the card as ry_crepe_track_many leaves it (ry_crepe_track_many_buffers, ry_analysis_extract_many_resident).
+ * The tables go up in one copy, and only when the card holds them in neither of its two sets.
+ * Refusals, made before anything is launched or written (a refused call leaves every stream's kept rows as they were and no track reported): those
+ * of ry_crepe_track_many, a stream_of entry outside [0, n_streams), a stream named twice, a null stream_of, advance, overlap_ok or n_computed. */
+int ry_crepe_bank_track(ry_crepe_bank* bank, const float* audio, const int* n_samples, const int* stream_of, int n_waves, int sr, int hop, double step_ms,
+                        double threshold, const int* advance, const int* overlap_ok, int* n_frames, int* n_computed, unsigned char* voiced,
+                        double* f0_64, double* t_64, int on_device_out);
+/* the activation [n_frames][360] of the last window of `stream` as it was assembled (host array, or on_device = 1 a device pointer); RY_ESTATE when
+ * the stream holds none */
+int ry_crepe_bank_activation(ry_crepe_bank* bank, int stream, float* out, int on_device);
+/* tests: NaN bit patterns in the packed block, both sets of tables, the slot every stream writes next and every row of every kept slot that is not
+ * portable.  rows_left [n_streams]: the rows of each stream left alone. */
+int ry_crepe_bank_debug_poison(ry_crepe_bank* bank, int* rows_left);
+/* tests: how many times ry_crepe_bank_track has uploaded its tables so far */
+int ry_crepe_bank_debug_uploads(ry_crepe_bank* bank, long long* n_uploads);
+/* tests: the assembling kernel alone on n_waves waves of n_frames[i] rows.  Row j of wave i (row frame0_i + j of out_dev) becomes row src of
+ * keep_dev[i] [n_keep[i]][360] when src >= 0, else row -1 - src of fresh_dev [n_fresh][360], and is written to row j of write_dev[i] as well; a row
+ * whose source index lies outside its block is left as it is in both.  n_frames, keep_dev, n_keep, write_dev and src (one entry per row of the call)
+ * are host arrays; the blocks are device pointers, 16-byte aligned (keep_dev[i] may be null when n_keep[i] is 0).  Waits for the stream. */
+int ry_crepe_bank_debug_assemble(ry_crepe_bank* bank, const int* n_frames, int n_waves, const float* const* keep_dev, const int* n_keep,
+                                 float* const* write_dev, const float* fresh_dev, int n_fresh, const int* src, float* out_dev);
 /* tests (the predictors' counterpart of ry_crepe_debug_layer): one buffer of the launch plan that ran last on this handle (ry_net_forward, ry_ac_convert,
  * ry_sr_convert, ry_sr_convert_rows), copied to the host once its stream has drained.  layer -1, kind 0: the convert wrapper's padded input
  * [batch][T][cols] (stage 1: in_ch columns; stage 2: log of the spectrogram without its last bin, width columns).  layer 0 .. 15 (stage 2), kind 0:

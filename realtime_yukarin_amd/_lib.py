@@ -66,6 +66,8 @@ ABI_SYMBOLS = (
     'ry_crepe_track_many', 'ry_crepe_track_many_buffers', 'ry_crepe_decode_many', 'ry_crepe_voicing_many', 'ry_analysis_extract_many_dev',
     'ry_crepe_stream_create', 'ry_crepe_stream_destroy', 'ry_crepe_stream_reset', 'ry_crepe_stream_track', 'ry_crepe_stream_activation',
     'ry_crepe_stream_debug_poison', 'ry_crepe_stream_debug_assemble',
+    'ry_crepe_bank_create', 'ry_crepe_bank_destroy', 'ry_crepe_bank_reset', 'ry_crepe_bank_track', 'ry_crepe_bank_activation',
+    'ry_crepe_bank_debug_poison', 'ry_crepe_bank_debug_uploads', 'ry_crepe_bank_debug_assemble',
     'ry_synth_create', 'ry_synth_destroy', 'ry_synth_length', 'ry_synth_run', 'ry_synth_bound', 'ry_synth_push', 'ry_synth_flush', 'ry_synth_reset',
     'ry_synth_debug_pulses', 'ry_synth_debug_poison', 'ry_synth_run_many', 'ry_synth_debug_pulses_many',
     'ry_synth_bank_create', 'ry_synth_bank_destroy', 'ry_synth_bank_bound', 'ry_synth_bank_push', 'ry_synth_bank_reset',
@@ -214,6 +216,16 @@ class Ry355Lib(object):
         d.ry_crepe_stream_activation.argtypes = [_VP, _FP, ctypes.c_int]
         d.ry_crepe_stream_debug_poison.argtypes = [_VP, _IP]
         d.ry_crepe_stream_debug_assemble.argtypes = [_VP, _FP, ctypes.c_int, _FP, ctypes.c_int, _IP, ctypes.c_int, _FP]
+        d.ry_crepe_bank_create.argtypes = [_VP, ctypes.c_int, ctypes.POINTER(_VP)]
+        d.ry_crepe_bank_destroy.argtypes = [_VP]
+        d.ry_crepe_bank_destroy.restype = None
+        d.ry_crepe_bank_reset.argtypes = [_VP, ctypes.c_int]
+        d.ry_crepe_bank_track.argtypes = [_VP, _FP, _IP, _IP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _IP, _IP,
+                                          _IP, _IP, _UB, _DP, _DP, ctypes.c_int]
+        d.ry_crepe_bank_activation.argtypes = [_VP, ctypes.c_int, _FP, ctypes.c_int]
+        d.ry_crepe_bank_debug_poison.argtypes = [_VP, _IP]
+        d.ry_crepe_bank_debug_uploads.argtypes = [_VP, ctypes.POINTER(ctypes.c_longlong)]
+        d.ry_crepe_bank_debug_assemble.argtypes = [_VP, _IP, ctypes.c_int, ctypes.POINTER(_VP), _IP, ctypes.POINTER(_VP), _FP, ctypes.c_int, _IP, _FP]
         _CI = ctypes.c_int
         d.ry_synth_create.argtypes = [_VP, _CI, ctypes.c_double, _CI, ctypes.c_uint, ctypes.POINTER(_VP)]
         d.ry_synth_destroy.argtypes = [_VP]

@@ -703,3 +703,138 @@ class CrepeStream(DeviceHandle):
         left = ctypes.c_int()
         lib.check(lib.dll.ry_crepe_stream_debug_poison(h, ctypes.byref(left)))
         return left.value
+
+
+class CrepeStreamBank(DeviceHandle):
+    """`CrepeStream` for the B live streams one process serves, in ONE call per buffer (`ry_crepe_bank_*`): `CrepeModel.track_many` on the next
+    window of every stream that takes part, each wave under the rule of `CrepeStream` against the kept call of its own stream (DESIGN.md section
+    19).  Every stream has a pair of activation slots of its own on the card, so a stream that sits calls out finds its rows intact when it
+    returns; the object keeps the previous window of every stream and compares each overlap as 32-bit words before it declares it.  Wave by wave
+    the result has the bits of `model.track` on that window.  `computed` / `frames`: per stream, the frames of its last window that went through
+    the network / that it has."""
+    _destroy = 'ry_crepe_bank_destroy'
+
+    def __init__(self, model: CrepeModel, n_streams: int):
+        self.model = model
+        self.n_streams = int(n_streams)
+        if self.n_streams < 1:
+            raise ValueError('a bank has at least one stream, got %d' % self.n_streams)
+        self.computed, self.frames = [0] * self.n_streams, [0] * self.n_streams
+        self._prev = [None] * self.n_streams
+        self._model_handle = None
+        DeviceHandle.__init__(self, model._given_ctx, model.device)
+
+    def __getstate__(self):
+        d = DeviceHandle.__getstate__(self)
+        d.update(_prev=[None] * self.n_streams, _model_handle=None)
+        return d
+
+    def _get(self):
+        """-> (library, bank handle) of this process, over the model's handle as it is now."""
+        lib, mh = self.model._get()
+        if self._handle is None or self._pid != os.getpid() or self._model_handle is not mh:
+            h = ctypes.c_void_p()
+            lib.check(lib.dll.ry_crepe_bank_create(mh, self.n_streams, ctypes.byref(h)))
+            self._ctx, self._handle, self._pid, self._model_handle = self.model._ctx, h, os.getpid(), mh
+            self._prev = [None] * self.n_streams
+        return lib, self._handle
+
+    def close(self):
+        DeviceHandle.close(self)                                   # the handle frees its own blocks and reads nothing of the model
+        self._prev, self._model_handle = [None] * self.n_streams, None
+
+    def _streams(self, stream):
+        if stream is None:
+            return list(range(self.n_streams))
+        if not 0 <= int(stream) < self.n_streams:
+            raise ValueError('stream %s of %d' % (stream, self.n_streams))
+        return [int(stream)]
+
+    def reset(self, stream: Optional[int] = None) -> None:
+        """Forgets the kept rows and the previous window of `stream` (None: of every stream): its next window is computed in full."""
+        which = self._streams(stream)
+        for s in which:
+            self._prev[s] = None
+        if self._handle is not None and self._pid == os.getpid():
+            lib, h = self._get()
+            lib.check(lib.dll.ry_crepe_bank_reset(h, -1 if stream is None else which[0]))
+
+    def _overlap_ok(self, s: int, x, advance) -> bool:
+        old = self._prev[s]
+        if advance is None or old is None or not 0 <= advance < old.size:
+            return False
+        m = min(x.size, old.size - advance)
+        return bool(numpy.array_equal(x[:m].view(numpy.uint32), old[advance:advance + m].view(numpy.uint32)))
+
+    def track_many(self, windows, sr, hop: int, step_size, threshold: float = 0.1, advances=None, device: bool = True, order=None):
+        """windows: one array per stream, None for a stream that sits the call out; advances: None, one int for all, or one entry per stream (an
+        entry may be None: that window is computed in full and kept).  -> (what `CrepeModel.track_many` returns for the windows that are there, in
+        stream order -- `DeviceTracks`, or with device=False [(voiced, f0, t)] --, [computed frames] per such window).  order (tests): the
+        streams that take part, in the order their windows lie in the call, instead of stream order."""
+        windows = list(windows)
+        if len(windows) != self.n_streams:
+            raise ValueError('%d windows for %d streams' % (len(windows), self.n_streams))
+        if advances is None or isinstance(advances, (int, numpy.integer)):
+            advances = [advances] * self.n_streams
+        advances = list(advances)
+        if len(advances) != self.n_streams:
+            raise ValueError('%d advances for %d streams' % (len(advances), self.n_streams))
+        part = [s for s, w in enumerate(windows) if w is not None]
+        if not part:
+            raise ValueError('track_many needs at least one window')
+        if order is not None:
+            if sorted(int(s) for s in order) != part:
+                raise ValueError('order %s does not name the streams that take part, %s' % (list(order), part))
+            part = [int(s) for s in order]
+        sr = _rate(sr)
+        xs = [numpy.ascontiguousarray(windows[s], dtype=numpy.float32).ravel() for s in part]
+        lib, h = self._get()
+        model = self.model
+        want = [model._frames_at(x.size, sr, hop) for x in xs]
+        adv = [-1 if advances[s] is None else int(advances[s]) for s in part]
+        ok = [int(self._overlap_ok(s, x, None if advances[s] is None else a)) for s, x, a in zip(part, xs, adv)]
+        as_i = lambda v: numpy.ascontiguousarray(v, dtype=numpy.int32)
+        counts, stream_of, adv, ok = as_i([x.size for x in xs]), as_i(part), as_i(adv), as_i(ok)
+        audio = numpy.ascontiguousarray(numpy.concatenate(xs))
+        nf, nc = numpy.zeros(len(xs), numpy.int32), numpy.zeros(len(xs), numpy.int32)
+        _IP = ctypes.POINTER(ctypes.c_int)
+        ip = lambda a: a.ctypes.data_as(_IP)
+        head = (h, _lib._fptr(audio), ip(counts), ip(stream_of), len(xs), sr, int(hop), float(step_size), float(threshold), ip(adv), ip(ok), ip(nf), ip(nc))
+        if not device:
+            n = int(sum(want))
+            voiced, f64, t64 = numpy.empty(n, numpy.uint8), numpy.empty(n, numpy.float64), numpy.empty(n, numpy.float64)
+            lib.check(lib.dll.ry_crepe_bank_track(*head, voiced.ctypes.data_as(_UBP), _dptr(f64), _dptr(t64), 0))
+        else:
+            lib.check(lib.dll.ry_crepe_bank_track(*head, None, None, None, 1))
+        assert list(nf) == want, (list(nf), want)
+        for i, s in enumerate(part):                               # after the call: a refused window is not the previous one
+            self._prev[s] = xs[i].copy()
+            self.frames[s], self.computed[s] = int(nf[i]), int(nc[i])
+        computed = [int(c) for c in nc]
+        if device:
+            return model._tracks_on_card(), computed
+        o = numpy.concatenate([[0], numpy.cumsum(nf)])
+        return [(voiced[a:b].astype(bool), f64[a:b].copy(), t64[a:b].copy()) for a, b in zip(o[:-1], o[1:])], computed
+
+    def activation(self, stream: int) -> numpy.ndarray:
+        """The assembled activation [frames][360] of the last window of `stream` (`ry_crepe_bank_activation`)."""
+        lib, h = self._get()
+        s = self._streams(stream)[0]
+        out = numpy.empty((self.frames[s], BINS), numpy.float32)
+        lib.check(lib.dll.ry_crepe_bank_activation(h, s, _lib._fptr(out), 0))
+        return out
+
+    def poison(self) -> List[int]:
+        """Tests: NaN bit patterns in everything of the bank but the rows the next call may keep -> how many those are, per stream
+        (`ry_crepe_bank_debug_poison`)."""
+        lib, h = self._get()
+        left = (ctypes.c_int * self.n_streams)()
+        lib.check(lib.dll.ry_crepe_bank_debug_poison(h, left))
+        return list(left)
+
+    def uploads(self) -> int:
+        """Tests: how many calls have uploaded their tables so far (`ry_crepe_bank_debug_uploads`)."""
+        lib, h = self._get()
+        n = ctypes.c_longlong()
+        lib.check(lib.dll.ry_crepe_bank_debug_uploads(h, ctypes.byref(n)))
+        return n.value

@@ -12,6 +12,8 @@
 // ry_crepe_stream_track is ry_crepe_track window by window over a live signal: the activation rows of the frames a window shares with the previous
 // one are kept on the card (two blocks used in turn), only the other frames run through the network (crepe_frames with a frame index list), and
 // crepe_act_assemble builds the window's block from both (DESIGN.md section 18 states which rows may be kept).
+// ry_crepe_bank_track is ry_crepe_track_many over the next windows of several such streams: every stream has a pair of slots of its own, the
+// computed frames of all waves share the passes, and crepe_act_assemble_many builds every wave's block in one launch.
 #include "crepe_kernels.h"
 #include "ry_host.h"
 
@@ -104,6 +106,25 @@ struct ry_crepe {
     int splits_of(int i) const { return dtype == 2 ? L[i].splits_x3 : L[i].splits; }
 };
 
+namespace {
+// What the rule of DESIGN.md section 18 needs of the call a stream keeps rows of: which of its two blocks holds them, its frames, samples at the
+// caller's rate and at 16 kHz, rate, hop, arithmetic, filter table, and which frames were portable.  One per single stream, one per slot of a bank.
+struct KeptCall {
+    bool valid = false;
+    int kept = 0, nf = 0, n_in = 0, n16 = 0, sr = 0, hop = 0, dtype = 0, rs_epoch = 0;
+    std::vector<char> portable;
+};
+
+// What the rule needs of a window length / an advance, remembered: the portable frames of (rate, samples, hop), the verdict of the register
+// check of (rate, advance, outputs checked).  Both follow from the rate's tables alone and are dropped when the filter changes.  One per single
+// stream, one per bank (its streams share it: nothing in it depends on the stream).
+struct RuleCache {
+    std::map<std::tuple<int, int, int>, std::vector<char>> portable_of;
+    std::map<std::tuple<int, int, int>, bool> repeats_of;
+    int epoch = 0;
+};
+}  // namespace
+
 // A streaming tracker over a model (ry_crepe_stream_track): the activation rows of the last window, kept on the card for the next one.
 // Nothing here is on the model's buffer list: no call on the model, ry_crepe_debug_poison included, touches what a stream keeps.
 struct ry_crepe_stream {
@@ -115,15 +136,35 @@ struct ry_crepe_stream {
     DevBuf<float>& act(int i) { return i ? act1 : act0; }
     std::vector<int> tab_host[2];                           // the tables of the last two uploads (the host array of a copy outlives the call)
     int tab_cur = -1;                                       // which of the two the card holds; -1: none
-    // the kept call: its block, frames, samples at the caller's rate and at 16 kHz, rate, hop, arithmetic, and which frames were portable
-    bool valid = false;
-    int kept = 0, nf = 0, n_in = 0, n16 = 0, sr = 0, hop = 0, dtype = 0, rs_epoch = 0;
-    std::vector<char> portable;
-    // what the rule needs of a window length / an advance, remembered: the portable frames of (rate, samples, hop), the verdict of the register
-    // check of (rate, advance, outputs checked).  Both follow from the rate's tables alone and are dropped when the filter changes.
-    std::map<std::tuple<int, int, int>, std::vector<char>> portable_of;
-    std::map<std::tuple<int, int, int>, bool> repeats_of;
-    int cache_epoch = 0;
+    KeptCall k;                                             // the kept call
+    RuleCache cache;
+};
+
+// A bank of streaming trackers over a model (ry_crepe_bank_track): every stream has a pair of activation slots of its own, used in turn by the
+// calls that stream takes part in, so a stream that sits a call out finds its rows intact; the packed rows and the tables belong to the call.
+// As with a stream, nothing here is on the model's buffer list.
+struct ry_crepe_bank {
+    ry_ctx* ctx = nullptr;
+    ry_crepe* model = nullptr;
+    DevBufList bufs;
+    struct Slot {
+        DevBuf<float> act0, act1;
+        KeptCall k;
+        explicit Slot(DevBufList& l) : act0(l), act1(l) {}
+        DevBuf<float>& act(int i) { return i ? act1 : act0; }
+    };
+    std::vector<std::unique_ptr<Slot>> slots;
+    DevBuf<float> fresh{bufs};                              // the packed rows of the computed frames of all waves of a call
+    // The tables of a call: descriptors [waves] (CrepeBankWave) | src [frames] | idx [computed], one copy.  In steady state the descriptors
+    // alternate between two values (every stream swaps its slots from call to call), so the card holds the tables of two calls, each beside
+    // its host copy (which outlives the upload), and a call whose tables equal either uploads nothing.
+    DevBuf<int> tab0{bufs}, tab1{bufs};
+    DevBuf<int>& tab(int i) { return i ? tab1 : tab0; }
+    std::vector<int> tab_host[2];
+    bool tab_on_card[2] = {false, false};
+    int tab_last = 1;                                       // the one used last: the other is replaced by a call that matches neither
+    long long uploads = 0;                                  // table uploads so far (tests)
+    RuleCache cache;
 };
 
 namespace {
@@ -402,7 +443,7 @@ std::vector<char> portable_frames(const Resampler* r, int sr, int n_in, int hop)
     return out;
 }
 
-const std::vector<char>& portable_cached(ry_crepe_stream* s, const Resampler* r, int sr, int n_in, int hop) {
+const std::vector<char>& portable_cached(RuleCache* s, const Resampler* r, int sr, int n_in, int hop) {
     const auto key = std::make_tuple(sr, n_in, hop);
     auto it = s->portable_of.find(key);
     if (it != s->portable_of.end()) return it->second;
@@ -411,7 +452,7 @@ const std::vector<char>& portable_cached(ry_crepe_stream* s, const Resampler* r,
 }
 
 // the rate's time register repeats exactly under the advance: tr[t + a16] == tr[t] + advance, as doubles, for the first n_check outputs
-bool register_repeats(ry_crepe_stream* s, const Resampler& r, int sr, int advance, long long a16, int n_check) {
+bool register_repeats(RuleCache* s, const Resampler& r, int sr, int advance, long long a16, int n_check) {
     const auto key = std::make_tuple(sr, advance, n_check);
     const auto it = s->repeats_of.find(key);
     if (it != s->repeats_of.end()) return it->second;
@@ -428,9 +469,9 @@ bool register_repeats(ry_crepe_stream* s, const Resampler& r, int sr, int advanc
 
 // The tables of a streamed call of nf frames over n_samples at sr: src [nf] (>= 0: the kept row; else -1 - the row of the packed block) followed
 // by idx [computed] (the window frames the packed rows are computed from).  -> the number of computed frames.  Host work only.
-int plan_stream(ry_crepe_stream* s, const Resampler* r, int n_samples, int sr, int hop, int nf, int advance, int overlap_ok, std::vector<int>* tab) {
-    const ry_crepe* c = s->model;
-    if (s->cache_epoch != c->rs_epoch) { s->portable_of.clear(); s->repeats_of.clear(); s->cache_epoch = c->rs_epoch; }
+int plan_stream(const ry_crepe* c, RuleCache* cache, const KeptCall* s, const Resampler* r, int n_samples, int sr, int hop, int nf, int advance,
+                int overlap_ok, std::vector<int>* tab) {
+    if (cache->epoch != c->rs_epoch) { cache->portable_of.clear(); cache->repeats_of.clear(); cache->epoch = c->rs_epoch; }
     bool reuse = s->valid && overlap_ok && advance >= 0 && advance < s->n_in && sr == s->sr && hop == s->hop && c->dtype == s->dtype &&
                  c->rs_epoch == s->rs_epoch;
     long long a16 = 0;
@@ -444,11 +485,11 @@ int plan_stream(ry_crepe_stream* s, const Resampler* r, int n_samples, int sr, i
     }
     const std::vector<char>* pm = nullptr;                          // the new window read as m samples long
     if (reuse) {
-        pm = &portable_cached(s, r, sr, m, hop);
+        pm = &portable_cached(cache, r, sr, m, hop);
         if (r && !pm->empty()) {
             const double nd = (double)m * (16000.0 / sr);
             const long long left = (long long)s->n16 - a16;
-            reuse = register_repeats(s, *r, sr, advance, a16, (int)std::max(0LL, std::min((long long)nd, left)));
+            reuse = register_repeats(cache, *r, sr, advance, a16, (int)std::max(0LL, std::min((long long)nd, left)));
         }
     }
     tab->assign((size_t)nf, 0);
@@ -463,11 +504,39 @@ int plan_stream(ry_crepe_stream* s, const Resampler* r, int n_samples, int sr, i
     return k;
 }
 
+// the call just enqueued becomes the kept one: its rows are in block `block`
+void keep_call(const ry_crepe* c, RuleCache* cache, KeptCall* k, int block, const Resampler* r, int n_samples, int n16, int sr, int hop, int nf) {
+    k->kept = block; k->nf = nf; k->n_in = n_samples; k->n16 = n16; k->sr = sr; k->hop = hop; k->dtype = c->dtype; k->rs_epoch = c->rs_epoch;
+    k->portable = portable_cached(cache, r, sr, n_samples, hop);
+    k->valid = true;
+}
+
 int launch_assemble(ry_ctx* ctx, const float* keep, int n_keep, const float* fresh, int n_fresh, const int* src, float* out, int n_rows) {
     CrepeAssembleParams p;
     p.keep = keep; p.n_keep = n_keep; p.fresh = fresh; p.n_fresh = n_fresh; p.src = src; p.out = out; p.n_rows = n_rows;
     RY_LAUNCH(crepe_act_assemble, dim3((unsigned)((n_rows + 3) / 4)), 256, ctx->stream, p);
     RT_TRY(rt::last_error());
+    return RY_OK;
+}
+
+int launch_assemble_many(ry_ctx* ctx, const CrepeSeg* seg, int n_seg, const CrepeBankWave* wave, const int* src, const float* fresh, int n_fresh,
+                         float* out, int n_rows) {
+    CrepeAssembleManyParams p;
+    p.seg = seg; p.n_seg = n_seg; p.wave = wave; p.src = src; p.fresh = fresh; p.n_fresh = n_fresh; p.out = out; p.n_rows = n_rows;
+    RY_LAUNCH(crepe_act_assemble_many, dim3((unsigned)((n_rows + 3) / 4)), 256, ctx->stream, p);
+    RT_TRY(rt::last_error());
+    return RY_OK;
+}
+
+// all bits set in every row of a kept block that is not portable (every row when nothing is kept) -> the rows left alone
+int poison_kept(DevBuf<float>& b, const KeptCall& k, ry_stream_t s, int* left) {
+    *left = 0;
+    if (!k.valid) return b.poison(s);
+    for (long long f = 0; f * CREPE_BINS < b.cap; ++f) {
+        if (f < k.nf && k.portable[(size_t)f]) { ++*left; continue; }
+        const long long n = std::min((long long)CREPE_BINS, b.cap - f * CREPE_BINS);
+        RT_TRY(rt::dmemset(b.ptr() + f * CREPE_BINS, 0xff, (size_t)n * sizeof(float), s));
+    }
     return RY_OK;
 }
 }  // namespace
@@ -981,7 +1050,7 @@ void ry_crepe_stream_destroy(ry_crepe_stream* s) {
 
 int ry_crepe_stream_reset(ry_crepe_stream* s) {
     if (!s) return fail(RY_ESTATE, "null crepe stream handle");
-    s->valid = false;
+    s->k.valid = false;
     return RY_OK;
 }
 
@@ -1000,11 +1069,11 @@ int ry_crepe_stream_track(ry_crepe_stream* st, const float* audio, int n_samples
     if (sr != 16000) RY_TRY(resample_plan(c, n_samples, sr, &r, &n16));
     RY_TRY(frame_count(n16, hop, 1, &nf));
     std::vector<int>& tab = st->tab_host[st->tab_cur == 0 ? 1 : 0];
-    const int n_comp = plan_stream(st, r, n_samples, sr, hop, nf, advance, overlap_ok, &tab);
+    const int n_comp = plan_stream(c, &st->cache, &st->k, r, n_samples, sr, hop, nf, advance, overlap_ok, &tab);
     const bool all = n_comp == nf;                                    // nothing kept: the dense layer writes the window's block itself
-    const int w = st->valid ? 1 - st->kept : 0;
-    const float* keep = st->valid ? st->act(st->kept).ptr() : nullptr;
-    const int n_keep = st->valid ? st->nf : 0;
+    const int w = st->k.valid ? 1 - st->k.kept : 0;
+    const float* keep = st->k.valid ? st->act(st->k.kept).ptr() : nullptr;
+    const int n_keep = st->k.valid ? st->k.nf : 0;
     RY_TRY(ensure_chunk(c, std::min(n_comp, CHUNK)));
     RY_TRY(ensure_call(c, nf, n16));
     RY_TRY(ensure_track(c, nf));
@@ -1017,7 +1086,7 @@ int ry_crepe_stream_track(ry_crepe_stream* st, const float* audio, int n_samples
             st->tab_cur = st->tab_cur == 0 ? 1 : 0;
         }
     }
-    st->valid = false;                                                // from here on the block about to be written is in play
+    st->k.valid = false;                                              // from here on the block about to be written is in play
     float* wave = c->audio.ptr();                                     // the one upload: the wave at the caller's rate
     if (r) {
         RY_TRY(c->audio_sr.reserve(c->ctx, n_samples));
@@ -1035,9 +1104,7 @@ int ry_crepe_stream_track(ry_crepe_stream* st, const float* audio, int n_samples
     RY_TRY(launch_decode(c, act, nf, 1));
     RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), nf, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr()));
     c->trk_wave = wave; c->trk_samples = n_samples; c->trk_frames = nf;
-    st->kept = w; st->nf = nf; st->n_in = n_samples; st->n16 = n16; st->sr = sr; st->hop = hop; st->dtype = c->dtype; st->rs_epoch = c->rs_epoch;
-    st->portable = portable_cached(st, r, sr, n_samples, hop);
-    st->valid = true;
+    keep_call(c, &st->cache, &st->k, w, r, n_samples, n16, sr, hop, nf);
     *n_frames = nf;
     *n_computed = n_comp;
     if (on_device_out) return RY_OK;
@@ -1051,11 +1118,11 @@ int ry_crepe_stream_track(ry_crepe_stream* st, const float* audio, int n_samples
 int ry_crepe_stream_activation(ry_crepe_stream* st, float* out, int on_device) {
     RY_TRY(check_handle(st, "crepe stream"));
     if (!out) return fail(RY_EINVAL, "bad argument");
-    if (!st->valid) return fail(RY_ESTATE, "the stream holds no window: ry_crepe_stream_track has not run, or ry_crepe_stream_reset came after it");
+    if (!st->k.valid) return fail(RY_ESTATE, "the stream holds no window: ry_crepe_stream_track has not run, or ry_crepe_stream_reset came after it");
     const ry_stream_t s = st->ctx->stream;
-    const size_t bytes = (size_t)st->nf * CREPE_BINS * sizeof(float);
-    if (on_device) { RT_TRY(rt::d2d(out, st->act(st->kept).ptr(), bytes, s)); return RY_OK; }
-    RT_TRY(rt::d2h(out, st->act(st->kept).ptr(), bytes, s));
+    const size_t bytes = (size_t)st->k.nf * CREPE_BINS * sizeof(float);
+    if (on_device) { RT_TRY(rt::d2d(out, st->act(st->k.kept).ptr(), bytes, s)); return RY_OK; }
+    RT_TRY(rt::d2h(out, st->act(st->k.kept).ptr(), bytes, s));
     RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }
@@ -1070,19 +1137,10 @@ int ry_crepe_stream_debug_poison(ry_crepe_stream* st, int* rows_left) {
     RY_TRY(st->fresh.poison(s));
     RY_TRY(st->tab.poison(s));
     st->tab_cur = -1;
-    const int w = st->valid ? 1 - st->kept : 0;
+    const int w = st->k.valid ? 1 - st->k.kept : 0;
     RY_TRY(st->act(w).poison(s));
     int left = 0;
-    if (st->valid) {
-        DevBuf<float>& k = st->act(st->kept);
-        for (long long f = 0; f * CREPE_BINS < k.cap; ++f) {
-            if (f < st->nf && st->portable[(size_t)f]) { ++left; continue; }
-            const long long n = std::min((long long)CREPE_BINS, k.cap - f * CREPE_BINS);
-            RT_TRY(rt::dmemset(k.ptr() + f * CREPE_BINS, 0xff, (size_t)n * sizeof(float), s));
-        }
-    } else {
-        RY_TRY(st->act(1 - w).poison(s));
-    }
+    RY_TRY(poison_kept(st->act(1 - w), st->k, s, &left));
     RT_TRY(rt::stream_sync(s));
     *rows_left = left;
     return RY_OK;
@@ -1097,6 +1155,221 @@ int ry_crepe_stream_debug_assemble(ry_crepe_stream* st, const float* keep_dev, i
     st->tab_cur = -1;                                                 // the card's tables are no longer those of a call
     RT_TRY(rt::h2d(st->tab.ptr(), src, (size_t)n_rows * sizeof(int), s));
     RY_TRY(launch_assemble(st->ctx, keep_dev, n_keep, fresh_dev, n_fresh, st->tab.ptr(), out_dev, n_rows));
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+// ---- a bank of streams ----
+int ry_crepe_bank_create(ry_crepe* c, int n_streams, ry_crepe_bank** out) {
+    if (!out) return fail(RY_EINVAL, "null out pointer");
+    *out = nullptr;
+    RY_TRY(check_handle(c, "crepe"));
+    if (n_streams < 1 || n_streams > (1 << 16)) return fail(RY_EINVAL, "a bank of %d streams", n_streams);
+    std::unique_ptr<ry_crepe_bank> b(new ry_crepe_bank());
+    b->ctx = c->ctx;
+    b->model = c;
+    for (int i = 0; i < n_streams; ++i) b->slots.emplace_back(new ry_crepe_bank::Slot(b->bufs));
+    *out = b.release();
+    return RY_OK;
+}
+
+void ry_crepe_bank_destroy(ry_crepe_bank* b) {
+    if (!b) return;
+    rt::set_device(b->ctx->device);
+    rt::stream_sync(b->ctx->stream);
+    delete b;
+}
+
+int ry_crepe_bank_reset(ry_crepe_bank* b, int stream) {
+    if (!b) return fail(RY_ESTATE, "null crepe bank handle");
+    const int n = (int)b->slots.size();
+    if (stream < -1 || stream >= n) return fail(RY_EINVAL, "stream %d of %d", stream, n);
+    for (int i = 0; i < n; ++i)
+        if (stream < 0 || stream == i) b->slots[(size_t)i]->k.valid = false;
+    return RY_OK;
+}
+
+int ry_crepe_bank_track(ry_crepe_bank* b, const float* audio, const int* n_samples, const int* stream_of, int n_waves, int sr, int hop, double step_ms,
+                        double threshold, const int* advance, const int* overlap_ok, int* n_frames, int* n_computed, unsigned char* voiced,
+                        double* f0_64, double* t_64, int on_device_out) {
+    RY_TRY(check_handle(b, "crepe bank"));
+    ry_crepe* c = b->model;
+    forget_track(c);                                                 // a refused call leaves no track either
+    // every refusal first, before anything is launched or written: those of ry_crepe_track_many, then the bank's own
+    if (!audio || !n_samples || !stream_of || !advance || !overlap_ok || !n_frames || !n_computed || hop < 1) return fail(RY_EINVAL, "bad argument");
+    if (!on_device_out && (!voiced || !f0_64 || !t_64)) return fail(RY_EINVAL, "null output");
+    if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
+    RY_TRY(voicing_args(threshold, step_ms));
+    const int n_streams = (int)b->slots.size();
+    const Resampler* r = nullptr;
+    std::vector<int> n16((size_t)n_waves), nf((size_t)n_waves);
+    std::vector<char> named((size_t)n_streams, 0);
+    for (int i = 0; i < n_waves; ++i) {
+        if (n_samples[i] < 1) return fail(RY_EINVAL, "wave %d has %d samples", i, n_samples[i]);
+        n16[(size_t)i] = n_samples[i];
+        if (sr != 16000) RY_TRY(resample_plan(c, n_samples[i], sr, &r, &n16[(size_t)i]));
+        RY_TRY(frame_count(n16[(size_t)i], hop, 1, &nf[(size_t)i]));
+        const int st = stream_of[i];
+        if (st < 0 || st >= n_streams) return fail(RY_EINVAL, "wave %d names stream %d of %d", i, st, n_streams);
+        if (named[(size_t)st]) return fail(RY_EINVAL, "stream %d is named twice in one call", st);
+        named[(size_t)st] = 1;
+    }
+    std::vector<CrepeSeg> plan;
+    RY_TRY(plan_segments(n_waves, n_samples, n16.data(), nf.data(), &plan));
+    const CrepeSeg& last = plan.back();
+    const int total_in = last.in_off + last.in_len, total16 = last.off16 + last.n16, total_nf = last.frame0 + last.n_frames;
+    // the tables, host work only: per wave the rule against that stream's kept call, the packed rows numbered through the call, the frames call-global
+    static_assert(sizeof(CrepeBankWave) == 6 * sizeof(int), "the descriptors are copied as six ints each");
+    const size_t desc_ints = 6 * (size_t)n_waves;
+    std::vector<int> tab(desc_ints + (size_t)total_nf), idx, one;
+    std::vector<int> comp((size_t)n_waves);
+    for (int i = 0; i < n_waves; ++i) {
+        const CrepeSeg& g = plan[(size_t)i];
+        const KeptCall& k = b->slots[(size_t)stream_of[i]]->k;
+        const int n_comp = plan_stream(c, &b->cache, &k, r, n_samples[i], sr, hop, g.n_frames, advance[i], overlap_ok[i], &one);
+        const int base = (int)idx.size();
+        for (int j = 0; j < g.n_frames; ++j) tab[desc_ints + (size_t)(g.frame0 + j)] = one[(size_t)j] >= 0 ? one[(size_t)j] : one[(size_t)j] - base;
+        for (int q = 0; q < n_comp; ++q) idx.push_back(g.frame0 + one[(size_t)g.n_frames + (size_t)q]);
+        comp[(size_t)i] = n_comp;
+    }
+    const int total_comp = (int)idx.size();
+    tab.insert(tab.end(), idx.begin(), idx.end());
+    const ry_stream_t s = c->ctx->stream;
+    RY_TRY(ensure_chunk(c, std::min(total_comp, CHUNK)));
+    RY_TRY(ensure_call(c, total_nf, total16));
+    RY_TRY(ensure_track(c, total_nf));
+    RY_TRY(b->fresh.grow(c->ctx, (long long)total_comp * CREPE_BINS));
+    for (int i = 0; i < n_waves; ++i) {                                 // the slot each wave writes: the other one of its stream, whose kept rows do not move
+        ry_crepe_bank::Slot& sl = *b->slots[(size_t)stream_of[i]];
+        const int w = sl.k.valid ? 1 - sl.k.kept : 0;
+        RY_TRY(sl.act(w).grow(c->ctx, (long long)nf[(size_t)i] * CREPE_BINS));
+        CrepeBankWave d;
+        d.keep = sl.k.valid ? sl.act(sl.k.kept).ptr() : nullptr; d.n_keep = sl.k.valid ? sl.k.nf : 0; d.write = sl.act(w).ptr(); d.pad = 0;
+        memcpy(&tab[6 * (size_t)i], &d, sizeof d);
+    }
+    // one copy for the descriptors and both tables, and only when neither of the two sets the card holds is this one
+    int t = -1;
+    for (int i = 0; i < 2; ++i)
+        if (b->tab_on_card[i] && b->tab_host[i] == tab) t = i;
+    if (t < 0) {
+        t = 1 - b->tab_last;
+        b->tab_on_card[t] = false;
+        RY_TRY(b->tab(t).grow(c->ctx, (long long)tab.size()));
+        b->tab_host[t].swap(tab);
+        RT_TRY(rt::h2d(b->tab(t).ptr(), b->tab_host[t].data(), b->tab_host[t].size() * sizeof(int), s));
+        b->tab_on_card[t] = true;
+        ++b->uploads;
+    }
+    b->tab_last = t;
+    const CrepeBankWave* d_wave = (const CrepeBankWave*)b->tab(t).ptr();
+    const int* d_src = b->tab(t).ptr() + desc_ints;
+    const int* d_idx = d_src + total_nf;
+    std::vector<int> wrote((size_t)n_waves);
+    for (int i = 0; i < n_waves; ++i) {                                 // from here on the slots about to be written are in play
+        KeptCall& k = b->slots[(size_t)stream_of[i]]->k;
+        wrote[(size_t)i] = k.valid ? 1 - k.kept : 0;
+        k.valid = false;
+    }
+    float* wave = c->audio.ptr();                                    // the one upload: the waves at the caller's rate, back to back
+    if (r) {
+        RY_TRY(c->audio_sr.reserve(c->ctx, total_in));
+        wave = c->audio_sr.ptr();
+    }
+    RY_TRY(upload_segments(c, plan));
+    RT_TRY(rt::h2d(wave, audio, (size_t)total_in * sizeof(float), s));
+    const CrepeSeg* seg = c->segs.ptr();
+    if (r) RY_TRY(launch_resample(c, *r, wave, total_in, sr, c->audio.ptr(), total16, seg, n_waves));
+    RY_TRY(run_passes(c, c->audio.ptr(), total16, hop, 1, total_comp, d_idx, b->fresh.ptr(), seg, n_waves));
+    RY_TRY(launch_assemble_many(c->ctx, seg, n_waves, d_wave, d_src, b->fresh.ptr(), total_comp, c->act.ptr(), total_nf));
+    RY_TRY(launch_decode(c, c->act.ptr(), total_nf, 1, seg, n_waves));
+    RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), total_nf, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr(), seg, n_waves));
+    c->trk_wave = wave;
+    c->trk_sample_off.assign((size_t)n_waves + 1, 0);
+    c->trk_frame_off.assign((size_t)n_waves + 1, 0);
+    for (int i = 0; i < n_waves; ++i) {
+        c->trk_sample_off[(size_t)i + 1] = (long long)plan[(size_t)i].in_off + plan[(size_t)i].in_len;
+        c->trk_frame_off[(size_t)i + 1] = plan[(size_t)i].frame0 + plan[(size_t)i].n_frames;
+        keep_call(c, &b->cache, &b->slots[(size_t)stream_of[i]]->k, wrote[(size_t)i], r, n_samples[i], n16[(size_t)i], sr, hop, nf[(size_t)i]);
+        n_frames[i] = nf[(size_t)i];
+        n_computed[i] = comp[(size_t)i];
+    }
+    c->trk_waves = n_waves;
+    if (on_device_out) return RY_OK;
+    RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)total_nf, s));
+    RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)total_nf * sizeof(double), s));
+    RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)total_nf * sizeof(double), s));
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+int ry_crepe_bank_activation(ry_crepe_bank* b, int stream, float* out, int on_device) {
+    RY_TRY(check_handle(b, "crepe bank"));
+    if (!out || stream < 0 || stream >= (int)b->slots.size()) return fail(RY_EINVAL, "bad argument");
+    ry_crepe_bank::Slot& sl = *b->slots[(size_t)stream];
+    if (!sl.k.valid) return fail(RY_ESTATE, "stream %d holds no window: no ry_crepe_bank_track has named it, or ry_crepe_bank_reset came after it", stream);
+    const ry_stream_t s = b->ctx->stream;
+    const size_t bytes = (size_t)sl.k.nf * CREPE_BINS * sizeof(float);
+    if (on_device) { RT_TRY(rt::d2d(out, sl.act(sl.k.kept).ptr(), bytes, s)); return RY_OK; }
+    RT_TRY(rt::d2h(out, sl.act(sl.k.kept).ptr(), bytes, s));
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+int ry_crepe_bank_debug_poison(ry_crepe_bank* b, int* rows_left) {
+    RY_TRY(check_handle(b, "crepe bank"));
+    if (!rows_left) return fail(RY_EINVAL, "bad argument");
+    const ry_stream_t s = b->ctx->stream;
+    RT_TRY(rt::stream_sync(s));
+    // all bits set in the packed block, both sets of tables, every slot about to be written and every kept row that is not portable
+    RY_TRY(b->fresh.poison(s));
+    for (int i = 0; i < 2; ++i) {
+        RY_TRY(b->tab(i).poison(s));
+        b->tab_on_card[i] = false;
+    }
+    for (size_t i = 0; i < b->slots.size(); ++i) {
+        ry_crepe_bank::Slot& sl = *b->slots[i];
+        const int w = sl.k.valid ? 1 - sl.k.kept : 0;
+        RY_TRY(sl.act(w).poison(s));
+        RY_TRY(poison_kept(sl.act(1 - w), sl.k, s, &rows_left[i]));
+    }
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+int ry_crepe_bank_debug_uploads(ry_crepe_bank* b, long long* n_uploads) {
+    if (!b || !n_uploads) return fail(RY_EINVAL, "bad argument");
+    *n_uploads = b->uploads;
+    return RY_OK;
+}
+
+int ry_crepe_bank_debug_assemble(ry_crepe_bank* b, const int* n_frames, int n_waves, const float* const* keep_dev, const int* n_keep,
+                                 float* const* write_dev, const float* fresh_dev, int n_fresh, const int* src, float* out_dev) {
+    RY_TRY(check_handle(b, "crepe bank"));
+    if (!n_frames || !keep_dev || !n_keep || !write_dev || !fresh_dev || !src || !out_dev || n_fresh < 0) return fail(RY_EINVAL, "bad argument");
+    std::vector<CrepeSeg> plan;
+    RY_TRY(plan_segments(n_waves, nullptr, nullptr, n_frames, &plan));
+    for (int i = 0; i < n_waves; ++i)
+        if (n_keep[i] < 0 || !write_dev[i] || (n_keep[i] > 0 && !keep_dev[i])) return fail(RY_EINVAL, "wave %d: bad slot", i);
+    const int total = plan.back().frame0 + plan.back().n_frames;
+    // descriptors | segment table | src in the first table buffer; the card's tables are no longer those of a call
+    const size_t desc_ints = 6 * (size_t)n_waves;
+    static_assert(sizeof(CrepeSeg) == 6 * sizeof(int), "the segment table is copied as six ints per wave");
+    std::vector<int>& tab = b->tab_host[0];
+    b->tab_on_card[0] = false;
+    tab.assign(2 * desc_ints + (size_t)total, 0);
+    for (int i = 0; i < n_waves; ++i) {
+        CrepeBankWave d;
+        d.keep = keep_dev[i]; d.n_keep = n_keep[i]; d.write = write_dev[i]; d.pad = 0;
+        memcpy(&tab[6 * (size_t)i], &d, sizeof d);
+        memcpy(&tab[desc_ints + 6 * (size_t)i], &plan[(size_t)i], sizeof(CrepeSeg));
+    }
+    memcpy(&tab[2 * desc_ints], src, (size_t)total * sizeof(int));
+    const ry_stream_t s = b->ctx->stream;
+    RY_TRY(b->tab0.grow(b->ctx, (long long)tab.size()));
+    RT_TRY(rt::h2d(b->tab0.ptr(), tab.data(), tab.size() * sizeof(int), s));
+    const int* d = b->tab0.ptr();
+    RY_TRY(launch_assemble_many(b->ctx, (const CrepeSeg*)(d + desc_ints), n_waves, (const CrepeBankWave*)d, d + 2 * desc_ints, fresh_dev, n_fresh,
+                                out_dev, total));
     RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }

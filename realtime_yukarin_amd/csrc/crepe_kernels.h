@@ -2,7 +2,8 @@
 // v_mfma_f32_32x32x2_f32 (conv1 .. conv6 and the dense classifier) and its split-bf16 form on v_mfma_f32_32x32x16_bf16, the split-K reduction with the
 // same epilogues, and the decode
 // (per-frame argmax / max, the 360-state Viterbi pass in float64, the local-average cents), and the voicing of the track (a two-state Viterbi
-// pass over the confidence, the masked float64 f0 and the time axis), and the assembly of a streamed window's activation block from kept and fresh rows.
+// pass over the confidence, the masked float64 f0 and the time axis), and the assembly of a streamed window's activation block from kept and fresh rows
+// (one stream: crepe_act_assemble; the waves of a bank of streams in one launch: crepe_act_assemble_many).
 // Semantics restated from the public crepe package and its PyTorch fork ([MEM]; INTEGRATION.md section 9 lists what is unpinned).
 //
 // Activations are channels-last with every frame's 'same' padding stored as zero rows, so the kernels never test an edge:
@@ -610,6 +611,45 @@ RY_KERNEL(256) void crepe_act_assemble(CrepeAssembleParams p) {
     const float* from = s >= 0 ? p.keep + (size_t)s * CREPE_BINS : p.fresh + (size_t)f * CREPE_BINS;
     float* to = p.out + (size_t)j * CREPE_BINS;
     for (int q = lane; q < CREPE_BINS / 4; q += 64) ry_st4(to + 4 * q, ry_ld4(from + 4 * q));
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same for the waves of a bank call (ry_crepe_bank_track), all in one launch.  Every stream of a bank has a pair of slots of its own -- the
+// streams that take part change from call to call, and one that sits a call out finds its rows where it left them -- so a table says per wave
+// where the stream's kept slot is (`keep`, n_keep rows) and which slot this call writes (`write`, never the kept one: new row j reads old row
+// j + d while another wave of lanes writes row j + d).  Row j of the call finds its wave by bisection over the segment table; src[j] >= 0 names
+// a row of that wave's kept slot, else -1 - src[j] a row of `fresh`, the packed rows all waves of the call share.  The row is written twice: to
+// row j of the call's contiguous block (`out`, which the decode reads with the same segment table) and to row j - frame0 of the wave's write slot,
+// the kept slot of that stream's next call.  A source index outside its block reads nothing and writes nothing.
+// ---------------------------------------------------------------------------------------------
+struct CrepeBankWave { const float* keep; float* write; int n_keep; int pad; };
+
+struct CrepeAssembleManyParams {
+    const CrepeSeg* seg; int n_seg;            // the call's waves: frame0 / n_frames are read
+    const CrepeBankWave* wave;                 // [n_seg]
+    const int* src;                            // [n_rows]
+    const float* fresh; int n_fresh;
+    float* out; int n_rows;
+};
+
+RY_KERNEL(256) void crepe_act_assemble_many(CrepeAssembleManyParams p) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int j = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (j >= p.n_rows) return;                                     // wave-uniform, like everything up to the copy
+    const int w = crepe_seg_of_frame(p.seg, p.n_seg, j);
+    const CrepeBankWave d = p.wave[w];
+    const int local = j - p.seg[w].frame0;
+    const long long s = p.src[j];
+    const long long f = -1 - s;
+    if (s >= 0 ? s >= d.n_keep : f >= p.n_fresh) return;
+    const float* from = s >= 0 ? d.keep + (size_t)s * CREPE_BINS : p.fresh + (size_t)f * CREPE_BINS;
+    float* to = p.out + (size_t)j * CREPE_BINS;
+    float* slot = d.write + (size_t)local * CREPE_BINS;
+    for (int q = lane; q < CREPE_BINS / 4; q += 64) {
+        const f32x4 v = ry_ld4(from + 4 * q);
+        ry_st4(to + 4 * q, v);
+        ry_st4(slot + 4 * q, v);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

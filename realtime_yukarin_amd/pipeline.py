@@ -304,6 +304,7 @@ class PipelineBank(object):
         self.calls = calls_many
         self._live = [False] * self.n_streams                              # the stream holds frames of a signal that has not ended
         self._blocks, self._cap, self._ctx, self._pid, self._table = {}, 0, None, None, None
+        self._crepe_bank = None                                            # `push(..., advance=a)`: the trackers that keep rows between buffers
 
     # ---- the blocks this object owns: grown, never shrunk, freed by `close` in the process that made them
     def _reserve(self, ctx, n: int, m_in: int, m_out: int, f_out: int) -> dict:
@@ -331,8 +332,26 @@ class PipelineBank(object):
         """Frees the device blocks, the stream bank and the one-shot synthesizer in the process that created them; the voice changer and the shared
         handles stay."""
         self._free()
+        self._drop_trackers()
         self.bank.close()
         self._one.close()
+
+    def _trackers_of(self, model):
+        """The bank's `CrepeStreamBank` over `model` (made on first use; one over another model is closed)."""
+        if self._crepe_bank is None or self._crepe_bank.model is not model:
+            self._drop_trackers()
+            self._crepe_bank = _crepe.CrepeStreamBank(model, self.n_streams)
+        return self._crepe_bank
+
+    def _drop_trackers(self) -> None:
+        if self._crepe_bank is not None:
+            self._crepe_bank.close()
+            self._crepe_bank = None
+
+    def _reset_trackers(self, streams) -> None:
+        if self._crepe_bank is not None:
+            for s in streams:
+                self._crepe_bank.reset(s)
 
     # ---- which way a call goes
     def _handles(self, waves):
@@ -349,14 +368,23 @@ class PipelineBank(object):
         return handles if self.bank._ctx is handles[2].stage1.ctx and self.bank.fft_size == FFT_SIZE else None
 
     # ---- the resident chain up to the rows the synthesizers read
-    def _resident_rows(self, waves, handles, discard):
-        """-> (context, blocks, frame offsets int32 [waves + 1], [f0 float64 [frames_i]: the converted track of wave i, zeros on the silent frames])."""
+    def _resident_rows(self, waves, handles, discard, part=None, advance=None):
+        """-> (context, blocks, frame offsets int32 [waves + 1], [f0 float64 [frames_i]: the converted track of wave i, zeros on the silent frames]).
+        part, advance (`push(..., advance=a)`): wave i is the next buffer of stream part[i], and the tracks come from the bank's `CrepeStreamBank`
+        -- the same bits, with the rows of the frames shared with that stream's previous buffer kept."""
         model, analyzer, core, (p_eff, p_all), hop, gate_fft = handles
         vc, p = self.voice_changer, self.acoustic_param
         ac = vc.acoustic_converter
         fs = int(waves[0].sampling_rate)
         xs = [numpy.ascontiguousarray(w.wave, dtype=numpy.float32) for w in waves]
-        trk = model.track_many(xs, fs, _crepe.hop_length(p.frame_period), p.frame_period, threshold=encode.threshold, device=True)   # the one upload
+        if advance is None:
+            trk = model.track_many(xs, fs, _crepe.hop_length(p.frame_period), p.frame_period, threshold=encode.threshold, device=True)   # the one upload
+        else:
+            windows = [None] * self.n_streams
+            for s, x in zip(part, xs):
+                windows[s] = x
+            trk, _ = self._trackers_of(model).track_many(windows, fs, _crepe.hop_length(p.frame_period), p.frame_period, threshold=encode.threshold,
+                                                         advances=advance, device=True)
         n, ctx, fo = trk.frames, core.stage1.ctx, trk.frame_offsets
         b = self._reserve(ctx, n, p.order + 1, core.M, core.F)
         analyzer.extract_many_resident(trk.wave, trk.sample_offsets, trk.f0, trk.t, fo, b['mc32'], b['sp32'], b['ap32'])
@@ -412,15 +440,24 @@ class PipelineBank(object):
             raise ValueError('final names stream %s of %d' % (final, self.n_streams))
         return final
 
-    def push(self, waves, discard=(0, 0), final=None) -> list:
+    def push(self, waves, discard=(0, 0), final=None, advance=None) -> list:
         """One buffer of every live stream: `waves` has one `yukarin.Wave` per stream, None for a stream that sits the call out; every wave is
         encoded and converted on its own, the rows [front, frames - back) of each go to its synthesis stream, and the samples that are final come
         back -> one `Wave` per stream (empty for a stream that sat out).  `final`: the streams whose signal ends with this call (what `Pipeline.push(
-        ..., final=True)` does for one); a stream named there without a wave is flushed."""
+        ..., final=True)` does for one); a stream named there without a wave is flushed.  `advance` (one int, or one entry per stream, None where
+        nothing is declared): sample i of a stream's buffer is sample i + advance of that stream's previous buffer, and the resident chain tracks
+        through a `CrepeStreamBank`, which keeps per stream the activation rows of the shared frames when the overlap really holds the same samples:
+        the same bits, fewer frames through the network.  A stream that sits calls out keeps its rows (its advance then spans the buffers it
+        missed).  A stream's kept rows are dropped by `final` naming it, by `flush` of it and by a call it takes part in that takes the composed
+        path.  advance=None: the call as it was, through `CrepeModel.track_many`."""
         from yukarin import Wave
         waves = list(waves)
         if len(waves) != self.n_streams:
             raise ValueError('%d waves for %d streams' % (len(waves), self.n_streams))
+        if advance is not None and not isinstance(advance, (int, numpy.integer)):
+            advance = list(advance)
+            if len(advance) != self.n_streams:
+                raise ValueError('%d advances for %d streams' % (len(advance), self.n_streams))
         final = self._final(final)
         front, back = int(discard[0]), int(discard[1])
         rate = self.voice_changer.output_sampling_rate
@@ -433,6 +470,7 @@ class PipelineBank(object):
             handles = self._handles([waves[s] for s in part])
             if handles is None:
                 calls_many['composed'] += 1
+                self._reset_trackers(part)
                 for s in part:
                     f = self._one._composed_feature(waves[s], (front, back))
                     k0, k1 = front, len(f.f0) - back
@@ -450,7 +488,7 @@ class PipelineBank(object):
                         outs[s] = got[s]
             else:
                 calls_many['resident'] += 1
-                ctx, b, fo, f0s = self._resident_rows([waves[s] for s in part], handles, (front, back))
+                ctx, b, fo, f0s = self._resident_rows([waves[s] for s in part], handles, (front, back), part, advance)
                 picks = [(int(fo[i]) + front, int(fo[i + 1]) - back) for i in range(len(part))]
                 picks = [(k0, max(k1, k0)) for k0, k1 in picks]
                 total = sum(k1 - k0 for k0, k1 in picks)
@@ -476,6 +514,7 @@ class PipelineBank(object):
             self._live[s] = True
         for s in final:
             self._live[s] = False
+        self._reset_trackers(final)
         return [Wave(wave=o, sampling_rate=rate) for o in outs]
 
     def flush(self, stream=None):
@@ -486,8 +525,10 @@ class PipelineBank(object):
         if stream is not None:
             out = self.bank.flush([int(stream)])[int(stream)]
             self._live[int(stream)] = False
+            self._reset_trackers([int(stream)])
             return Wave(wave=out, sampling_rate=rate)
         live = [s for s in range(self.n_streams) if self._live[s]]
         outs = self.bank.flush(live) if live else [numpy.empty(0, numpy.float64)] * self.n_streams
         self._live = [False] * self.n_streams
+        self._reset_trackers(range(self.n_streams))
         return [Wave(wave=o, sampling_rate=rate) for o in outs]
