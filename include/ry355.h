@@ -658,6 +658,53 @@ int ry_analysis_d4c_bands(ry_analysis* analysis);
  * null: the count alone. */
 int ry_analysis_debug_d4c(ry_analysis* analysis, long long* ints_out, double* values_out, int capacity, int* n);
 
+/* ---- The output gate: the tail of the reference's decode worker (worker/decode_worker.py:53-59, run.py:194-198, stream/decode_stream.py:38).
+ * Samples (float64, NaN replaced by 0.0) are appended to a carried fragment; once it holds `chunk` samples ONE chunk is cut per call and the
+ * rest stays carried.  The chunk is silent iff mean_db < -threshold_db, where, in float64,
+ *     mean_db = mean(max(db, max(db) - 80)),  db = 10 log10(max(1e-10, |rfft(frame * hann)|^2))
+ * over the 1 + chunk / 512 frames of 2048 samples at hop 512 of the chunk padded by 1024 reflected samples on each side (periodic Hann window,
+ * 1025 bins): librosa's power_to_db(abs(stft(wave)) ** 2).mean().  An audible chunk is returned as sample * scale, float64 or (out_f32) rounded
+ * once to float32: the bits of numpy's (wave * scale).astype(float32).  A chunk that holds +-inf is audible, mean_db NaN, returned as it is.
+ * Semantics: tests/output_gate_ref.py, INTEGRATION.md section 18, DESIGN.md section 20.
+ * Refused by ry_outgate_create: a null pointer, chunk < 1025 (the reflection would wrap twice) or > 2^24, a NaN threshold or scale. */
+typedef struct ry_outgate ry_outgate;
+int ry_outgate_create(ry_ctx* ctx, int chunk, double threshold_db, double scale, int out_f32, ry_outgate** out);
+void ry_outgate_destroy(ry_outgate* gate);
+/* forgets the carried samples */
+int ry_outgate_reset(ry_outgate* gate);
+/* samples [n] float64, n >= 0, on the host or (on_device = 1) a device pointer read in the order of the context stream.  At most one chunk comes
+ * out: *n_out = chunk when one was completed (0 otherwise), *silent = 1 when it is silent -- `out` is then untouched --, *mean_db its mean.  out:
+ * HOST, room for out_capacity >= chunk elements of float64 (float32 with out_f32) whenever the call completes a chunk.  A call that completes no
+ * chunk does not wait for the stream; one that does waits once for the record and, for an audible chunk, once more for the samples.  Refused
+ * before anything is launched or changed: null pointers, n < 0, an `out` too small for the chunk this call completes. */
+int ry_outgate_push(ry_outgate* gate, const double* samples, int n, int on_device, void* out, int out_capacity, int* n_out, int* silent, double* mean_db);
+/* the samples carried at the moment (negative: error) */
+int ry_outgate_held(ry_outgate* gate);
+/* tests: out[5] = stream waits, kernel launches, host-to-device copies, device-to-host copies, sample bytes brought to the host by the last push */
+int ry_outgate_debug_counts(ry_outgate* gate, long long* out);
+/* tests: NaN bit patterns in every scratch buffer and in every part of the two fragment buffers that holds no carried sample */
+int ry_outgate_debug_poison(ry_outgate* gate);
+
+/* ---- A bank of output gates: B streams with one chunk size, threshold, scale and output type, served by ONE call per buffer -- one og_append,
+ * one og_frame_db, one og_finish and one og_emit launch, one upload, one download of all records and one wait for the audible chunks, whatever B
+ * is.  Contract, without a tolerance: stream b returns, call by call, the records and the chunks a lone ry_outgate returns for the same samples,
+ * whatever the other streams do. */
+typedef struct ry_outgate_bank ry_outgate_bank;
+int ry_outgate_bank_create(ry_ctx* ctx, int n_streams, int chunk, double threshold_db, double scale, int out_f32, ry_outgate_bank** out);
+void ry_outgate_bank_destroy(ry_outgate_bank* bank);
+/* forgets the carried samples of `stream` (-1: of every stream) */
+int ry_outgate_bank_reset(ry_outgate_bank* bank, int stream);
+/* samples: the streams' new samples back to back, stream b at samples[sample_offsets[b] .. sample_offsets[b + 1]) (n_streams + 1 entries on the
+ * HOST, starting at 0).  A stream without a new sample sits the call out: nothing of it changes and no chunk is cut.  out_offsets [n_streams + 1]:
+ * stream b's chunk is at out[out_offsets[b]], out_offsets[b + 1] - out_offsets[b] = chunk when it completed one (silent or not), 0 otherwise.
+ * silent [n_streams]: -1 no chunk, 0 audible, 1 silent (its part of `out` untouched); mean_db [n_streams].  Refused before anything is launched or
+ * any stream changes: null pointers, offsets that do not start at 0 or fall, out_capacity below chunk times the chunks this call completes. */
+int ry_outgate_bank_push(ry_outgate_bank* bank, const double* samples, const long long* sample_offsets, int on_device, void* out, long long out_capacity,
+                         long long* out_offsets, int* silent, double* mean_db);
+int ry_outgate_bank_held(ry_outgate_bank* bank, int stream);
+int ry_outgate_bank_debug_counts(ry_outgate_bank* bank, long long* out);
+int ry_outgate_bank_debug_poison(ry_outgate_bank* bank);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,9 @@ ABI_SYMBOLS = (
     'ry_analysis_d4c', 'ry_analysis_extract', 'ry_analysis_d4c_bands', 'ry_analysis_debug_d4c', 'ry_analysis_extract_dev',
     'ry_analysis_extract_resident', 'ry_vc_enqueue_wave_device', 'ry_mask_rows',
     'ry_analysis_extract_many_resident', 'ry_vc_gate_waves_device', 'ry_vc_enqueue_waves_device', 'ry_gather_rows',
+    'ry_outgate_create', 'ry_outgate_destroy', 'ry_outgate_reset', 'ry_outgate_push', 'ry_outgate_held', 'ry_outgate_debug_counts', 'ry_outgate_debug_poison',
+    'ry_outgate_bank_create', 'ry_outgate_bank_destroy', 'ry_outgate_bank_reset', 'ry_outgate_bank_push', 'ry_outgate_bank_held',
+    'ry_outgate_bank_debug_counts', 'ry_outgate_bank_debug_poison',
 )
 
 
@@ -272,6 +275,23 @@ class Ry355Lib(object):
         d.ry_vc_enqueue_waves_device.argtypes = [_VP, _FP, ctypes.POINTER(_LL), _IP, _CI, _CI, _CI, ctypes.c_float, ctypes.c_float, _FP, ctypes.c_float,
                                                  _FP, _FP, _UB, _UB, _IP]
         d.ry_analysis_d4c_bands.argtypes = [_VP]
+        _LLP = ctypes.POINTER(_LL)
+        d.ry_outgate_create.argtypes = [_VP, _CI, ctypes.c_double, ctypes.c_double, _CI, ctypes.POINTER(_VP)]
+        d.ry_outgate_destroy.argtypes = [_VP]
+        d.ry_outgate_destroy.restype = None
+        d.ry_outgate_reset.argtypes = [_VP]
+        d.ry_outgate_push.argtypes = [_VP, _DP, _CI, _CI, _VP, _CI, _IP, _IP, _DP]
+        d.ry_outgate_held.argtypes = [_VP]
+        d.ry_outgate_debug_counts.argtypes = [_VP, _LLP]
+        d.ry_outgate_debug_poison.argtypes = [_VP]
+        d.ry_outgate_bank_create.argtypes = [_VP, _CI, _CI, ctypes.c_double, ctypes.c_double, _CI, ctypes.POINTER(_VP)]
+        d.ry_outgate_bank_destroy.argtypes = [_VP]
+        d.ry_outgate_bank_destroy.restype = None
+        d.ry_outgate_bank_reset.argtypes = [_VP, _CI]
+        d.ry_outgate_bank_push.argtypes = [_VP, _DP, _LLP, _CI, _VP, _LL, _LLP, _IP, _DP]
+        d.ry_outgate_bank_held.argtypes = [_VP, _CI]
+        d.ry_outgate_bank_debug_counts.argtypes = [_VP, _LLP]
+        d.ry_outgate_bank_debug_poison.argtypes = [_VP]
         d.ry_analysis_debug_d4c.argtypes = [_VP, ctypes.POINTER(_LL), _DP, _CI, _IP]
         d.ry_net_profile_window.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RyKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         d.ry_net_debug_activation.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]

@@ -229,13 +229,16 @@ class Pipeline(object):
                                        y.ctypes.data_as(world_synth._DP), y.size, ctypes.byref(got)))
         return Wave(y[:got.value], sampling_rate=self.voice_changer.output_sampling_rate)
 
-    def push(self, wave, discard=(0, 0), final: bool = False, advance: Optional[int] = None):
+    def push(self, wave, discard=(0, 0), final: bool = False, advance: Optional[int] = None, out_gate=None):
         """One buffer of a live stream: the wave is encoded and converted on its own (as `EncodeStream` / `ConvertStream` do per buffer), the rows
         [front, frames - back) -- what `ConvertStream.process` picks -- go to the synthesis stream, and the samples that are final come back.
         final=True: the stream ends with this buffer (`flush` follows).  advance (an int): sample i of this buffer is sample i + advance of the previous
         one -- consecutive windows of `time_length + 2 * extra_time` share `2 * extra_time` of audio -- and the resident path tracks through a
         `CrepeStream`, which keeps the activation rows of the shared frames when the overlap really holds the same samples: the same bits, fewer frames
-        through the network.  The kept rows are dropped by `flush`, by final=True and by a buffer that takes the composed path."""
+        through the network.  The kept rows are dropped by `flush`, by final=True and by a buffer that takes the composed path.
+        out_gate (an `output_gate.OutputGate`): the samples go through it -- the tail of the reference's decode worker -- and the returned `Wave` is
+        the chunk it emits (scaled, in the gate's dtype), empty when no chunk was completed or the chunk is silent.  The samples take the host route
+        into the gate."""
         from yukarin import Wave
         front, back = int(discard[0]), int(discard[1])
         handles = self._resident_handles(wave)
@@ -265,6 +268,10 @@ class Pipeline(object):
         if final:
             out = numpy.concatenate([out, self.synth.flush()])
             self._reset_stream()
+        if out_gate is not None:
+            out = out_gate.push(out)
+            if out is None:
+                out = numpy.empty(0, out_gate.dtype)
         return Wave(wave=out, sampling_rate=self.voice_changer.output_sampling_rate)
 
     def flush(self):
@@ -440,7 +447,7 @@ class PipelineBank(object):
             raise ValueError('final names stream %s of %d' % (final, self.n_streams))
         return final
 
-    def push(self, waves, discard=(0, 0), final=None, advance=None) -> list:
+    def push(self, waves, discard=(0, 0), final=None, advance=None, out_gate=None) -> list:
         """One buffer of every live stream: `waves` has one `yukarin.Wave` per stream, None for a stream that sits the call out; every wave is
         encoded and converted on its own, the rows [front, frames - back) of each go to its synthesis stream, and the samples that are final come
         back -> one `Wave` per stream (empty for a stream that sat out).  `final`: the streams whose signal ends with this call (what `Pipeline.push(
@@ -449,7 +456,10 @@ class PipelineBank(object):
         through a `CrepeStreamBank`, which keeps per stream the activation rows of the shared frames when the overlap really holds the same samples:
         the same bits, fewer frames through the network.  A stream that sits calls out keeps its rows (its advance then spans the buffers it
         missed).  A stream's kept rows are dropped by `final` naming it, by `flush` of it and by a call it takes part in that takes the composed
-        path.  advance=None: the call as it was, through `CrepeModel.track_many`."""
+        path.  advance=None: the call as it was, through `CrepeModel.track_many`.
+        out_gate (an `output_gate.OutputGateBank` of n_streams streams): the samples of all streams go through it in ONE call and every returned
+        `Wave` is the chunk its stream's gate emits, empty when no chunk was completed or the chunk is silent; a stream without a sample in this call
+        sits the gate's call out.  The samples take the host route into the gate."""
         from yukarin import Wave
         waves = list(waves)
         if len(waves) != self.n_streams:
@@ -515,6 +525,8 @@ class PipelineBank(object):
         for s in final:
             self._live[s] = False
         self._reset_trackers(final)
+        if out_gate is not None:
+            outs = [o if o is not None else numpy.empty(0, out_gate.dtype) for o in out_gate.push(outs)]
         return [Wave(wave=o, sampling_rate=rate) for o in outs]
 
     def flush(self, stream=None):

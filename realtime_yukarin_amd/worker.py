@@ -69,3 +69,36 @@ def convert_worker(acoustic_converter, super_resolution, time_length: float, ext
         stream_wrapper._current_time += time_length
         pending.append((item, vc.begin(in_feature, discard=(pad, pad)), start))     # the rows `pick` drops below are not computed by stage 2
         stream.remove(end_time=retire_time(stream_wrapper._current_time, time_length, extra_time))
+
+
+def decode_worker(realtime_vocoder, time_length: float, extra_time: float, vocoder_buffer_size: int, out_audio_chunk: int,
+                  output_silent_threshold: float, queue_input, queue_output, acquired_lock) -> None:
+    """Mirror of the decode worker loop (worker/decode_worker.py:16-66): the reference's arguments, `Item` protocol and stream arithmetic on its
+    own `DecodeStream` / `StreamWrapper`, with the tail of the loop -- fragment, one chunk per item, the librosa silence verdict (lines 53-61) -- in
+    an `output_gate.OutputGate` (scale 1.0, float64: run.py applies its own scale and cast).  `item.item` is the chunk, or None when no chunk was
+    completed or the chunk is silent.  As `convert_worker`: an item of `None` ends the loop, and segments no later window can fetch are dropped."""
+    from realtime_voice_conversion.stream import DecodeStream, StreamWrapper
+    from .output_gate import OutputGate
+    logger = logging.getLogger('decode')
+    realtime_vocoder.create_synthesizer(buffer_size=vocoder_buffer_size, number_of_pointers=16)
+    stream = DecodeStream(vocoder=realtime_vocoder)
+    stream_wrapper = StreamWrapper(stream=stream, extra_time=extra_time)
+    gate = OutputGate(out_audio_chunk, output_silent_threshold, 1.0, 'float64')
+
+    acquired_lock.release()
+    start_time = extra_time
+    try:
+        while True:
+            item = queue_input.get()
+            if item is None:
+                return
+            start = time.time()
+            stream.add(start_time=start_time, data=item.item)
+            start_time += time_length
+            wave = stream_wrapper.process_next(time_length=time_length)
+            item.item = gate.push(wave)
+            queue_output.put(item)
+            stream.remove(end_time=retire_time(stream_wrapper._current_time, time_length, extra_time))
+            logger.debug('%s: %s', item.index, time.time() - start)
+    finally:
+        gate.close()
