@@ -241,6 +241,32 @@ int ry_vc_gate_waves_device(ry_vc* vc, const float* wave_dev, const long long* s
 int ry_vc_enqueue_waves_device(ry_vc* vc, const float* wave_dev, const long long* sample_offsets, const int* frame_offsets, int n_waves, int hop,
                                int fft_length, float p_effective, float p_all, const float* feat_dev, float sp_floor, float* mc_out_dev,
                                float* sp_out_dev, unsigned char* mask_dev_out, unsigned char* effective_out, int* n_eff_out);
+/* ---- gate before encode: the verdict first, the tracker and the analysis for the audible waves only, then the window call on that verdict.
+ * The verdict of ry_vc_gate_waves_device alone, for waves whose feature rows do not exist yet: the same frame-power and gate launches and the same ONE
+ * wait, with no feature row read and no feature row written (the gate kernel still writes the frame indices of the effective frames into the core's
+ * own row_of block, which the compaction of the window call that follows overwrites in stream order).  mask_dev_out (device) / effective_out (host)
+ * [sum n] and n_eff_out [n_waves] have the bits of ry_vc_gate_waves_device.  Refused, nothing launched: what that call refuses of the arguments this one has. */
+int ry_vc_gate_verdict_waves_device(ry_vc* vc, const float* wave_dev, const long long* sample_offsets, const int* frame_offsets, int n_waves, int hop,
+                                    int fft_length, float p_effective, float p_all, unsigned char* mask_dev_out, unsigned char* effective_out,
+                                    int* n_eff_out);
+/* The ordered compaction of the gate alone, from a verdict that exists: mask_dev [sum n] (device, the gate's mask), effective [sum n] and n_eff
+ * [n_waves] (host, its copies), feat_dev [sum n][in_ch] -> x_eff_dev_out [sum n][in_ch] / row_of_dev_out [sum n] (device; both null: blocks of the
+ * core): from row frame_offsets[i] on, the effective rows of wave i and their frame indices counted from the wave's first frame, with the bits and
+ * the order ry_vc_gate_waves_device writes.  One workgroup per wave, a fixed order, no atomics.  The feature row of a frame whose mask byte is 0 is
+ * not read and the rows behind n_eff[i] of a wave are not written: a wave with n_eff = 0 leaves its region as it was and its feature rows need not
+ * exist.  The call waits for the kernel.  Refused (RY_EINVAL), nothing launched or written: null pointers (one output without the other),
+ * n_waves < 1 or > 65536, offsets that do not start at 0 or do not ascend, more than 2^22 frames, n_eff[i] outside 0 .. frames of wave i, a host
+ * mask whose ones in wave i are not n_eff[i] of them. */
+int ry_vc_compact_waves_device(ry_vc* vc, const int* frame_offsets, int n_waves, const unsigned char* mask_dev, const unsigned char* effective,
+                               const int* n_eff, const float* feat_dev, float* x_eff_dev_out, int* row_of_dev_out);
+/* ry_vc_enqueue_waves_device with the verdict as an INPUT: the frame-power and gate kernels do not run and the call waits for nothing.  One
+ * compaction launch (that of ry_vc_compact_waves_device, into the core's blocks; none when no wave has an effective frame), then, wave by wave in
+ * order, the rest of ry_vc_enqueue_waves_device -- stage 1 only where n_eff[i] > 0, scatter, mc2sp, stage 2 -- with the same ring slots and
+ * lanes.  mc and sp of wave i have the bits of ry_vc_enqueue_wave_device on wave i alone.  No feature row of a wave with n_eff = 0 is read.  Stream
+ * order as there: the stage-1 streams wait for the context stream, the context stream waits for the end of every window.  Refused, nothing
+ * launched or written: what ry_vc_compact_waves_device refuses, null outputs, a ring slot of the call held by a ticket (RY_ESTATE). */
+int ry_vc_enqueue_waves_masked_device(ry_vc* vc, const int* frame_offsets, int n_waves, const float* feat_dev, float sp_floor, float* mc_out_dev,
+                                      float* sp_out_dev, const unsigned char* mask_dev, const unsigned char* effective, const int* n_eff);
 /* `AcousticConverter.decode_spectrogram` alone (host pointers): sp [n][bins] = exp(mc [n][m] @ mtx [m][bins]) + floor. */
 int ry_mc2sp(ry_ctx* ctx, const float* mc, const float* mtx, int n, int m, int bins, float floor, float* sp);
 
@@ -408,6 +434,27 @@ int ry_crepe_track_many(ry_crepe* crepe, const float* audio, const int* n_sample
  * ry_crepe_track_many, a null argument included, no track is reported. */
 int ry_crepe_track_many_buffers(ry_crepe* crepe, const float** wave_dev, int* n_waves, const long long** sample_offsets, const int** frame_offsets,
                                 const unsigned char** voiced_dev, const double** f0_dev, const double** t_dev);
+/* ry_crepe_track_many in two steps, for a caller that decides between them which waves are worth tracking (the silence gate of the window call).
+ * ry_crepe_upload_waves: the ONE upload -- n_waves >= 1 float32 waves back to back at sr, n_samples[i] each -> *wave_dev, their device address;
+ * wave i starts at the sum of the counts in front of it.  The table holds until the next call on this handle that is not one of the two tracking
+ * calls below; those may follow each other on one table.  Refused, nothing written: null pointers, n_waves < 1, a wave with no sample, a wave
+ * ry_crepe_track refuses at this rate, a rate without resampler tables (RY_ESTATE), more than 2^31 - 1 samples in all.
+ * ry_crepe_track_uploaded: ry_crepe_track_many on n_waves >= 1 waves OF THAT TABLE, read where they lie: first_sample[i] / n_samples[i] name wave
+ * i's first sample in the table and its length.  The same segment table, passes of 256 frames and decode / voicing workgroup per wave: the tracked
+ * waves get the bits of ry_crepe_track_many on them alone.  The masked tracks stay in the handle, back to back in the order of the call
+ * (ry_crepe_uploaded_buffers; ry_crepe_track_many_buffers reports no track).  Refused before anything is launched or written: what
+ * ry_crepe_track_many refuses, no table on the card (RY_ESTATE), another rate than the upload's, an entry that is not a wave of the table (first
+ * sample and length), entries that do not ascend.
+ * ry_crepe_uploaded_buffers (any pointer may be null): the table's address and samples, the waves the last tracking call tracked (0: none since
+ * the upload), a HOST array of n_tracked + 1 frame offsets that belongs to the handle, and the addresses of voiced / f0_64 / t_64.  RY_ESTATE
+ * without a table. */
+int ry_crepe_upload_waves(ry_crepe* crepe, const float* audio, const int* n_samples, int n_waves, int sr, const float** wave_dev);
+int ry_crepe_track_uploaded(ry_crepe* crepe, const int* first_sample, const int* n_samples, int n_waves, int sr, int hop, double step_ms,
+                            double threshold, int* n_frames, unsigned char* voiced, double* f0_64, double* t_64, int on_device_out);
+int ry_crepe_uploaded_buffers(ry_crepe* crepe, const float** wave_dev, long long* n_samples, int* n_tracked, const int** frame_offsets,
+                              const unsigned char** voiced_dev, const double** f0_dev, const double** t_dev);
+/* tests: how many frames have gone through the network on this handle so far (every pass of every call, streams and banks over it included) */
+int ry_crepe_debug_frames(ry_crepe* crepe, long long* n_frames);
 /* ry_crepe_decode / ry_crepe_voicing on n_tracks >= 1 tracks side by side, one workgroup each: the arrays hold the tracks back to back, track i of
  * n_frames[i] >= 1 frames (at most 2^24 in all); every track gets the bits of the single call on it alone.  Pointers and on_device as in the single
  * calls. */
@@ -478,6 +525,12 @@ int ry_crepe_bank_reset(ry_crepe_bank* bank, int stream);
 int ry_crepe_bank_track(ry_crepe_bank* bank, const float* audio, const int* n_samples, const int* stream_of, int n_waves, int sr, int hop, double step_ms,
                         double threshold, const int* advance, const int* overlap_ok, int* n_frames, int* n_computed, unsigned char* voiced,
                         double* f0_64, double* t_64, int on_device_out);
+/* ry_crepe_bank_track on waves of the table ry_crepe_upload_waves left on the bank's model (first_sample[i] / n_samples[i] as in
+ * ry_crepe_track_uploaded): nothing is uploaded but the tables; a stream whose wave of the table is not named sits the call out and keeps its rows.
+ * The same bits, the track reported by ry_crepe_uploaded_buffers.  Refusals: those of ry_crepe_bank_track and of ry_crepe_track_uploaded. */
+int ry_crepe_bank_track_uploaded(ry_crepe_bank* bank, const int* first_sample, const int* n_samples, const int* stream_of, int n_waves, int sr, int hop,
+                                 double step_ms, double threshold, const int* advance, const int* overlap_ok, int* n_frames, int* n_computed,
+                                 unsigned char* voiced, double* f0_64, double* t_64, int on_device_out);
 /* the activation [n_frames][360] of the last window of `stream` as it was assembled (host array, or on_device = 1 a device pointer); RY_ESTATE when
  * the stream holds none */
 int ry_crepe_bank_activation(ry_crepe_bank* bank, int stream, float* out, int on_device);
@@ -650,6 +703,16 @@ int ry_analysis_extract_resident(ry_analysis* analysis, const float* x32_dev, lo
 int ry_analysis_extract_many_resident(ry_analysis* analysis, const float* x32_dev, const long long* sample_offsets, const double* f0_dev,
                                       const double* t_dev, const int* frame_offsets, int n_waves, double threshold,
                                       float* mc32_dev_out, float* sp32_dev_out, float* ap32_dev_out);
+/* ry_analysis_extract_many_resident for waves that lie anywhere in an uploaded block and rows that go anywhere in the caller's blocks (what
+ * ry_crepe_track_uploaded left, into the frame layout of a call that holds more waves than were tracked): wave i has the samples
+ * [first_sample[i], first_sample[i] + n_samples[i]) of x32_dev (x_len samples in all), the frames [frame_offsets[i], frame_offsets[i + 1]) of
+ * f0_dev / t_dev (n_waves + 1 entries from 0) and writes rows [row_offsets[i], row_offsets[i] + its frames) of the three blocks; no other row is
+ * written.  All tables are HOST arrays.  The same launches and the same one verdict; every row has the bits of ry_analysis_extract_resident on its
+ * wave alone.  Refused: what ry_analysis_extract_many_resident refuses, null tables, waves that overlap, do not ascend or leave the block, row
+ * ranges that overlap or do not ascend. */
+int ry_analysis_extract_spans_resident(ry_analysis* analysis, const float* x32_dev, long long x_len, const long long* first_sample, const int* n_samples,
+                                       const double* f0_dev, const double* t_dev, const int* frame_offsets, const int* row_offsets, int n_waves,
+                                       double threshold, float* mc32_dev_out, float* sp32_dev_out, float* ap32_dev_out);
 /* the number of bands B (1 at 16 kHz, 3 at 24 kHz); negative (an error code) where D4C is not built for the handle's rate */
 int ry_analysis_d4c_bands(ry_analysis* analysis);
 /* tests: what the last recorded (ry_analysis_debug_record) D4C run decided.  ints_out [n][9]: half length of the Love-Train window, of the other

@@ -76,6 +76,8 @@ ABI_SYMBOLS = (
     'ry_analysis_d4c', 'ry_analysis_extract', 'ry_analysis_d4c_bands', 'ry_analysis_debug_d4c', 'ry_analysis_extract_dev',
     'ry_analysis_extract_resident', 'ry_vc_enqueue_wave_device', 'ry_mask_rows',
     'ry_analysis_extract_many_resident', 'ry_vc_gate_waves_device', 'ry_vc_enqueue_waves_device', 'ry_gather_rows',
+    'ry_vc_gate_verdict_waves_device', 'ry_vc_compact_waves_device', 'ry_vc_enqueue_waves_masked_device', 'ry_analysis_extract_spans_resident',
+    'ry_crepe_upload_waves', 'ry_crepe_track_uploaded', 'ry_crepe_uploaded_buffers', 'ry_crepe_bank_track_uploaded', 'ry_crepe_debug_frames',
     'ry_outgate_create', 'ry_outgate_destroy', 'ry_outgate_reset', 'ry_outgate_push', 'ry_outgate_held', 'ry_outgate_debug_counts', 'ry_outgate_debug_poison',
     'ry_outgate_bank_create', 'ry_outgate_bank_destroy', 'ry_outgate_bank_reset', 'ry_outgate_bank_push', 'ry_outgate_bank_held',
     'ry_outgate_bank_debug_counts', 'ry_outgate_bank_debug_poison',
@@ -274,6 +276,17 @@ class Ry355Lib(object):
         d.ry_vc_gate_waves_device.argtypes = [_VP, _FP, ctypes.POINTER(_LL), _IP, _CI, _CI, _CI, ctypes.c_float, ctypes.c_float, _FP, _UB, _UB, _IP, _FP, _IP]
         d.ry_vc_enqueue_waves_device.argtypes = [_VP, _FP, ctypes.POINTER(_LL), _IP, _CI, _CI, _CI, ctypes.c_float, ctypes.c_float, _FP, ctypes.c_float,
                                                  _FP, _FP, _UB, _UB, _IP]
+        d.ry_vc_gate_verdict_waves_device.argtypes = [_VP, _FP, ctypes.POINTER(_LL), _IP, _CI, _CI, _CI, ctypes.c_float, ctypes.c_float, _UB, _UB, _IP]
+        d.ry_vc_compact_waves_device.argtypes = [_VP, _IP, _CI, _UB, _UB, _IP, _FP, _FP, _IP]
+        d.ry_vc_enqueue_waves_masked_device.argtypes = [_VP, _IP, _CI, _FP, ctypes.c_float, _FP, _FP, _UB, _UB, _IP]
+        d.ry_analysis_extract_spans_resident.argtypes = [_VP, _FP, _LL, ctypes.POINTER(_LL), _IP, _DP, _DP, _IP, _IP, _CI, ctypes.c_double, _FP, _FP, _FP]
+        d.ry_crepe_upload_waves.argtypes = [_VP, _FP, _IP, _CI, _CI, ctypes.POINTER(_VP)]
+        d.ry_crepe_track_uploaded.argtypes = [_VP, _IP, _IP, _CI, _CI, _CI, ctypes.c_double, ctypes.c_double, _IP, _UB, _DP, _DP, _CI]
+        d.ry_crepe_uploaded_buffers.argtypes = [_VP, ctypes.POINTER(_VP), ctypes.POINTER(_LL), _IP, _IPP, ctypes.POINTER(_VP), ctypes.POINTER(_VP),
+                                                ctypes.POINTER(_VP)]
+        d.ry_crepe_bank_track_uploaded.argtypes = [_VP, _IP, _IP, _IP, _CI, _CI, _CI, ctypes.c_double, ctypes.c_double, _IP, _IP, _IP, _IP, _UB, _DP, _DP,
+                                                   _CI]
+        d.ry_crepe_debug_frames.argtypes = [_VP, ctypes.POINTER(_LL)]
         d.ry_analysis_d4c_bands.argtypes = [_VP]
         _LLP = ctypes.POINTER(_LL)
         d.ry_outgate_create.argtypes = [_VP, _CI, ctypes.c_double, ctypes.c_double, _CI, ctypes.POINTER(_VP)]

@@ -157,6 +157,13 @@ def n_frames(n_samples: int, hop: int, center: bool = True) -> int:
     return 1 + (int(n_samples) + (FRAME if center else 0) - FRAME) // int(hop)
 
 
+def track_frames(n_samples: int, sr, hop: int) -> int:
+    """The frames `CrepeModel.track` returns for n_samples at sr -- centred frames of the signal at 16 kHz, `n_frames(resampled_length(n), hop)`,
+    the rule `ry_crepe_track` applies on its side -- computed without a model: what a caller that skips the tracker for a wave needs to know of it."""
+    n16 = int(n_samples) if int(sr) == MODEL_SRATE else resampled_length(n_samples, sr)
+    return n_frames(n16, hop, True) if n16 >= 1 else 0
+
+
 def hop_length(step_size) -> int:
     """`int(16000 * step_size / 1000)`: 80 samples for the reference's 5 ms."""
     return int(MODEL_SRATE * step_size / 1000)
@@ -307,6 +314,35 @@ class DeviceTracks(object):
 
     def download(self):
         """[(voiced [frames] bool, f0 [frames] float64)] per wave (waits for the stream)."""
+        voiced, f0 = self.model._download_track(self)
+        o = self.frame_offsets
+        return [(voiced[o[i]:o[i + 1]], f0[o[i]:o[i + 1]]) for i in range(self.waves)]
+
+
+class UploadedWaves(object):
+    """What `CrepeModel.upload_waves` left on the card: the address of the float32 waves (back to back, at `sr`) and `offsets` (int64, waves + 1
+    entries): where wave i starts.  Holds until the next call on the model that is not `track_uploaded` (of the model or of a bank over it)."""
+
+    def __init__(self, model, ctx, wave, sr, offsets):
+        self.model, self.ctx, self.wave, self.sr, self.offsets = model, ctx, wave, sr, offsets
+        self.waves, self.samples = offsets.size - 1, int(offsets[-1])
+
+
+class UploadedTracks(object):
+    """What `track_uploaded` left on the card for the waves `which` of an `UploadedWaves`: the addresses of the concatenated `voiced` (bytes), `f0` and
+    `t` (float64) of the tracked waves, `frame_offsets` (int32, tracked + 1 entries) into them, `first_sample` / `n_samples` of every tracked wave in
+    the uploaded block `wave` of `samples` samples."""
+
+    def __init__(self, model, ctx, uploaded, which, voiced, f0, t, frame_offsets):
+        self.model, self.ctx, self.which = model, ctx, list(which)
+        self.wave, self.samples = uploaded.wave, uploaded.samples
+        self.first_sample = numpy.asarray([uploaded.offsets[i] for i in which], numpy.int64)
+        self.n_samples = numpy.asarray([uploaded.offsets[i + 1] - uploaded.offsets[i] for i in which], numpy.int32)
+        self.voiced, self.f0, self.t, self.frame_offsets = voiced, f0, t, frame_offsets
+        self.waves, self.frames = len(self.which), int(frame_offsets[-1])
+
+    def download(self):
+        """[(voiced [frames] bool, f0 [frames] float64)] per tracked wave (waits for the stream)."""
         voiced, f0 = self.model._download_track(self)
         o = self.frame_offsets
         return [(voiced[o[i]:o[i + 1]], f0[o[i]:o[i + 1]]) for i in range(self.waves)]
@@ -536,6 +572,60 @@ class CrepeModel(DeviceHandle):
         sample_offsets = numpy.asarray(so[:nw.value + 1], numpy.int64)          # copies: the handle's arrays change with its next call
         frame_offsets = numpy.asarray(fo[:nw.value + 1], numpy.int32)
         return DeviceTracks(self, self._ctx, p[0].value, p[1].value, p[2].value, p[3].value, sample_offsets, frame_offsets)
+
+    def upload_waves(self, waves, sr) -> UploadedWaves:
+        """The one upload of `track_many`, alone (`ry_crepe_upload_waves`): the waves back to back on the card, for a caller that decides before the
+        tracker runs which of them are worth tracking (`pipeline`'s gate-first form)."""
+        sr = _rate(sr)
+        xs = [numpy.ascontiguousarray(w, dtype=numpy.float32).ravel() for w in waves]
+        if not xs:
+            raise ValueError('upload_waves needs at least one wave')
+        lib, h = self._get()
+        for x in xs:
+            self._frames_at(x.size, sr, MODEL_SRATE)                 # installs the rate's tables; refuses a wave without a sample at 16 kHz
+        counts = numpy.asarray([x.size for x in xs], numpy.int32)
+        audio = numpy.ascontiguousarray(numpy.concatenate(xs))
+        p = ctypes.c_void_p()
+        lib.check(lib.dll.ry_crepe_upload_waves(h, _lib._fptr(audio), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(xs), sr, ctypes.byref(p)))
+        return UploadedWaves(self, self._ctx, p.value, sr, numpy.concatenate([[0], numpy.cumsum(counts, dtype=numpy.int64)]).astype(numpy.int64))
+
+    def _uploaded_tracks(self, uploaded, which) -> UploadedTracks:
+        lib, h = self._get()
+        p = [ctypes.c_void_p() for _ in range(4)]
+        ns, nt = ctypes.c_longlong(), ctypes.c_int()
+        fo = ctypes.POINTER(ctypes.c_int)()
+        lib.check(lib.dll.ry_crepe_uploaded_buffers(h, ctypes.byref(p[0]), ctypes.byref(ns), ctypes.byref(nt), ctypes.byref(fo),
+                                                    *[ctypes.byref(q) for q in p[1:]]))
+        assert nt.value == len(which) and p[0].value == uploaded.wave, (nt.value, len(which))
+        frame_offsets = numpy.asarray(fo[:nt.value + 1], numpy.int32)           # a copy: the handle's array changes with its next call
+        return UploadedTracks(self, self._ctx, uploaded, which, p[1].value, p[2].value, p[3].value, frame_offsets)
+
+    def _which(self, uploaded, which):
+        which = [int(i) for i in which]
+        if uploaded.model is not self or not which or any(i < 0 or i >= uploaded.waves for i in which) or any(b <= a for a, b in zip(which, which[1:])):
+            raise ValueError('the waves to track must be ascending indices into an upload of this model, got %s of %d' % (which, uploaded.waves))
+        as_i = lambda v: numpy.ascontiguousarray(v, dtype=numpy.int32)
+        return which, as_i([uploaded.offsets[i] for i in which]), as_i([uploaded.offsets[i + 1] - uploaded.offsets[i] for i in which])
+
+    def track_uploaded(self, uploaded: UploadedWaves, which, hop: int, step_size, threshold: float = 0.1) -> UploadedTracks:
+        """`track_many(..., device=True)` on the waves `which` (ascending indices) of `uploaded`, read where they lie (`ry_crepe_track_uploaded`):
+        nothing is uploaded but the segment table; every tracked wave gets the bits of `track` on it alone."""
+        lib, h = self._get()
+        which, first, counts = self._which(uploaded, which)
+        want = [self._frames_at(int(n), uploaded.sr, hop) for n in counts]
+        nf = numpy.zeros(len(which), numpy.int32)
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        lib.check(lib.dll.ry_crepe_track_uploaded(h, ip(first), ip(counts), len(which), uploaded.sr, int(hop), float(step_size), float(threshold), ip(nf),
+                                                  None, None, None, 1))
+        assert list(nf) == want, (list(nf), want)
+        return self._uploaded_tracks(uploaded, which)
+
+    def frames_through_network(self) -> int:
+        """Tests: the frames that have gone through the network on this model's handle so far (`ry_crepe_debug_frames`)."""
+        lib, h = self._get()
+        n = ctypes.c_longlong()
+        lib.check(lib.dll.ry_crepe_debug_frames(h, ctypes.byref(n)))
+        return n.value
 
     def decode_many(self, activations, viterbi: bool = True):
         """`decode` of several activations side by side, one workgroup each (`ry_crepe_decode_many`) -> [(f0, confidence, centre bins)]."""
@@ -815,6 +905,36 @@ class CrepeStreamBank(DeviceHandle):
             return model._tracks_on_card(), computed
         o = numpy.concatenate([[0], numpy.cumsum(nf)])
         return [(voiced[a:b].astype(bool), f64[a:b].copy(), t64[a:b].copy()) for a, b in zip(o[:-1], o[1:])], computed
+
+    def track_uploaded(self, uploaded: UploadedWaves, which, streams, windows, hop: int, step_size, threshold: float = 0.1, advances=None):
+        """`track_many(..., device=True)` on the waves `which` (ascending indices) of `uploaded` (`ry_crepe_bank_track_uploaded`): wave which[i] is
+        the next window of stream streams[i] and windows[i] the host array that was uploaded for it (the overlap is compared on the host);
+        advances: one entry per named wave (None: computed in full).  -> (`UploadedTracks`, [computed frames] per named wave).  A stream that is
+        not named keeps its rows."""
+        lib, h = self._get()
+        model = self.model
+        which, first, counts = model._which(uploaded, which)
+        part = [int(s) for s in streams]
+        xs = [numpy.ascontiguousarray(w, dtype=numpy.float32).ravel() for w in windows]
+        advances = [None] * len(which) if advances is None else list(advances)
+        if not (len(part) == len(xs) == len(advances) == len(which)) or any(x.size != n for x, n in zip(xs, counts)):
+            raise ValueError('one stream, one window of the uploaded length and one advance per tracked wave are needed')
+        if any(not 0 <= s < self.n_streams for s in part):
+            raise ValueError('streams %s of %d' % (part, self.n_streams))
+        want = [model._frames_at(x.size, uploaded.sr, hop) for x in xs]
+        adv = [-1 if a is None else int(a) for a in advances]
+        ok = [int(self._overlap_ok(s, x, None if a0 is None else a)) for s, x, a0, a in zip(part, xs, advances, adv)]
+        as_i = lambda v: numpy.ascontiguousarray(v, dtype=numpy.int32)
+        stream_of, adv, ok = as_i(part), as_i(adv), as_i(ok)
+        nf, nc = numpy.zeros(len(xs), numpy.int32), numpy.zeros(len(xs), numpy.int32)
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        lib.check(lib.dll.ry_crepe_bank_track_uploaded(h, ip(first), ip(counts), ip(stream_of), len(xs), uploaded.sr, int(hop), float(step_size),
+                                                       float(threshold), ip(adv), ip(ok), ip(nf), ip(nc), None, None, None, 1))
+        assert list(nf) == want, (list(nf), want)
+        for i, s in enumerate(part):                               # after the call: a refused window is not the previous one
+            self._prev[s] = xs[i].copy()
+            self.frames[s], self.computed[s] = int(nf[i]), int(nc[i])
+        return model._uploaded_tracks(uploaded, which), [int(c) for c in nc]
 
     def activation(self, stream: int) -> numpy.ndarray:
         """The assembled activation [frames][360] of the last window of `stream` (`ry_crepe_bank_activation`)."""

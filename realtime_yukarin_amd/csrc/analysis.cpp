@@ -113,13 +113,14 @@ int check_call(ry_analysis* s, long long x_len, int n, bool cheaptrick, const Ou
     return RY_OK;
 }
 
-// frames [k0, k0 + n) of a call analyse the wave of x_len samples at x0 of the call's wave buffer
-struct Span { long long x0, x_len; int k0, n; };
+// frames [k0, k0 + n) of a call analyse the wave of x_len samples at x0 of the call's wave buffer; their float32 device rows (sp32 / mc32 / ap32) are
+// rows [r0, r0 + n) of the caller's blocks (r0 = k0 unless the caller says where the rows of a wave go: ry_analysis_extract_spans_resident)
+struct Span { long long x0, x_len; int k0, n, r0; };
 
 int run_spans(ry_analysis* s, const double* d_x, const Span* spans, int n_spans, const double* d_f0, const double* d_t, int n, bool cheaptrick, const Outputs& o);
 
 int run_kernels(ry_analysis* s, const double* d_x, long long x_len, const double* d_f0, const double* d_t, int n, bool cheaptrick, const Outputs& o) {
-    const Span one = {0, x_len, 0, n};
+    const Span one = {0, x_len, 0, n, 0};
     return run_spans(s, d_x, &one, 1, d_f0, d_t, n, cheaptrick, o);
 }
 
@@ -160,20 +161,20 @@ int run_spans(ry_analysis* s, const double* d_x, const Span* spans, int n_spans,
     const size_t n_mc = (size_t)s->order + 1;
     for (int i = 0; i < n_spans && cheaptrick; ++i) {
         const Span& sp = spans[i];
-        const size_t k0 = (size_t)sp.k0;
+        const size_t k0 = (size_t)sp.k0, r0 = (size_t)sp.r0;
         AnalysisParams p;
         p.x = d_x + sp.x0; p.x_len = sp.x_len; p.f0 = d_f0 + k0; p.t = d_t + k0;
         p.fs = (double)s->fs; p.floor_f0 = s->floor_f0; p.q1 = s->q1; p.seed_hash = s->seed_hash;
         p.tw = s->tw; p.S = s->S; p.n_mc = s->order + 1;
-        p.sp64 = o.sp64 ? s->d_sp.ptr() + k0 * SYNTH_BINS : nullptr; p.sp32 = o.sp32_dev ? o.sp32_dev + k0 * SYNTH_BINS : nullptr;
+        p.sp64 = o.sp64 ? s->d_sp.ptr() + k0 * SYNTH_BINS : nullptr; p.sp32 = o.sp32_dev ? o.sp32_dev + r0 * SYNTH_BINS : nullptr;
         p.mc = o.mc ? s->d_mc.ptr() + k0 * n_mc : nullptr; p.ints = s->record ? s->d_ints.ptr() + k0 : nullptr;
-        p.mc32 = o.mc32_dev ? o.mc32_dev + k0 * n_mc : nullptr;
+        p.mc32 = o.mc32_dev ? o.mc32_dev + r0 * n_mc : nullptr;
         RY_LAUNCH(analysis_frame, dim3((unsigned)sp.n), 256, st, p);
         RT_TRY(rt::last_error());
     }
     for (int i = 0; i < n_spans && o.d4c; ++i) {
         const Span& sp = spans[i];
-        const size_t k0 = (size_t)sp.k0;
+        const size_t k0 = (size_t)sp.k0, r0 = (size_t)sp.r0;
         D4cParams p;
         p.x = d_x + sp.x0; p.x_len = sp.x_len; p.f0 = d_f0 + k0; p.t = d_t + k0;
         p.fs = (double)s->fs; p.threshold = o.threshold; p.seed_hash = s->seed_hash;
@@ -181,7 +182,7 @@ int run_spans(ry_analysis* s, const double* d_x, const Span* spans, int n_spans,
         p.n_bands = s->n_bands; p.band_half = s->band_half;
         for (int i = 0; i < D4C_MAX_BANDS; ++i) p.band_centre[i] = s->band_centre[i];
         p.lt0 = s->lt[0]; p.lt1 = s->lt[1]; p.lt2 = s->lt[2];
-        p.ap64 = o.ap64 ? s->d_ap.ptr() + k0 * SYNTH_BINS : nullptr; p.ap32 = o.ap32_dev ? o.ap32_dev + k0 * SYNTH_BINS : nullptr;
+        p.ap64 = o.ap64 ? s->d_ap.ptr() + k0 * SYNTH_BINS : nullptr; p.ap32 = o.ap32_dev ? o.ap32_dev + r0 * SYNTH_BINS : nullptr;
         p.coded = o.coded ? s->d_coded.ptr() + k0 * (size_t)s->n_bands : nullptr; p.rec = s->record ? s->d_rec.ptr() + k0 : nullptr;
         RY_LAUNCH(d4c_frame, dim3((unsigned)sp.n), 256, st, p);
         RT_TRY(rt::last_error());
@@ -299,7 +300,7 @@ int ry_analysis_extract_dev(ry_analysis* s, const float* x32_dev, long long x_le
     if (empty) return RY_OK;
     if (!x32_dev) return fail(RY_EINVAL, "null wave");
     if (!f0_dev || !t_dev) return fail(RY_EINVAL, "null f0 / t");
-    const Span one = {0, x_len, 0, n};
+    const Span one = {0, x_len, 0, n, 0};
     return extract_dev(s, x32_dev, x_len, f0_dev, t_dev, n, &one, 1, o);
 }
 
@@ -314,7 +315,7 @@ int ry_analysis_extract_resident(ry_analysis* s, const float* x32_dev, long long
     if (empty) return RY_OK;
     if (!x32_dev) return fail(RY_EINVAL, "null wave");
     if (!f0_dev || !t_dev) return fail(RY_EINVAL, "null f0 / t");
-    const Span one = {0, x_len, 0, n};
+    const Span one = {0, x_len, 0, n, 0};
     return extract_dev(s, x32_dev, x_len, f0_dev, t_dev, n, &one, 1, o);       // no host row is named: the verdict is the only copy to the host
 }
 
@@ -332,7 +333,7 @@ int extract_many(ry_analysis* s, const float* x32_dev, const long long* sample_o
     for (int i = 0; i < n_waves; ++i) {
         Span& sp = spans[(size_t)i];
         sp.x0 = sample_offsets[i]; sp.x_len = sample_offsets[i + 1] - sample_offsets[i];
-        sp.k0 = frame_offsets[i]; sp.n = frame_offsets[i + 1] - frame_offsets[i];
+        sp.k0 = frame_offsets[i]; sp.n = frame_offsets[i + 1] - frame_offsets[i]; sp.r0 = sp.k0;
         if (sp.x_len < 1) return fail(RY_EINVAL, "wave %d has %lld samples", i, sp.x_len);
         if (sp.n < 1) return fail(RY_EINVAL, "wave %d has %d frames", i, sp.n);
         if (frame_offsets[i + 1] > (1 << 22)) return fail(RY_EINVAL, "%d frames in one call", frame_offsets[i + 1]);
@@ -366,6 +367,42 @@ int ry_analysis_extract_many_resident(ry_analysis* s, const float* x32_dev, cons
     o.mc32_dev = mc32_dev_out; o.sp32_dev = sp32_dev_out; o.ap32_dev = ap32_dev_out;
     o.d4c = true; o.threshold = threshold;
     return extract_many(s, x32_dev, sample_offsets, f0_dev, t_dev, frame_offsets, n_waves, o, true);      // no host row is named: one verdict comes back
+}
+
+// ry_analysis_extract_many_resident for waves that lie anywhere in an uploaded block and rows that go anywhere in the caller's blocks: wave i has the
+// samples [first_sample[i], first_sample[i] + n_samples[i]) of x32_dev (x_len samples in all), the frames [frame_offsets[i], frame_offsets[i + 1]) of
+// f0_dev / t_dev (the tracks back to back, as a tracker left them) and writes the rows [row_offsets[i], row_offsets[i] + its frames) of the three
+// blocks.  The waves ascend without overlap, and so do the row ranges: nothing outside them is written.
+int ry_analysis_extract_spans_resident(ry_analysis* s, const float* x32_dev, long long x_len, const long long* first_sample, const int* n_samples,
+                                       const double* f0_dev, const double* t_dev, const int* frame_offsets, const int* row_offsets, int n_waves,
+                                       double threshold, float* mc32_dev_out, float* sp32_dev_out, float* ap32_dev_out) {
+    Outputs o;
+    o.mc32_dev = mc32_dev_out; o.sp32_dev = sp32_dev_out; o.ap32_dev = ap32_dev_out;
+    o.d4c = true; o.threshold = threshold;
+    RY_TRY(check_handle(s, "analysis"));
+    if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
+    if (!first_sample || !n_samples || !frame_offsets || !row_offsets) return fail(RY_EINVAL, "null tables");
+    if (frame_offsets[0] != 0) return fail(RY_EINVAL, "the frame offsets start at %d, not at 0", frame_offsets[0]);
+    std::vector<Span> spans((size_t)n_waves);
+    long long x_end = 0, r_end = 0;
+    for (int i = 0; i < n_waves; ++i) {
+        Span& sp = spans[(size_t)i];
+        sp.x0 = first_sample[i]; sp.x_len = n_samples[i];
+        sp.k0 = frame_offsets[i]; sp.n = frame_offsets[i + 1] - frame_offsets[i]; sp.r0 = row_offsets[i];
+        if (sp.x_len < 1) return fail(RY_EINVAL, "wave %d has %lld samples", i, sp.x_len);
+        if (sp.n < 1) return fail(RY_EINVAL, "wave %d has %d frames", i, sp.n);
+        if (sp.x0 < x_end || sp.x0 + sp.x_len > x_len) return fail(RY_EINVAL, "wave %d: samples %lld .. %lld of %lld: the table must ascend inside the block", i, sp.x0, sp.x0 + sp.x_len, x_len);
+        if (sp.r0 < r_end || (long long)sp.r0 + sp.n > (1 << 22)) return fail(RY_EINVAL, "wave %d: rows %d .. %lld: the table must ascend, at most 2^22 rows", i, sp.r0, (long long)sp.r0 + sp.n);
+        if (frame_offsets[i + 1] > (1 << 22)) return fail(RY_EINVAL, "%d frames in one call", frame_offsets[i + 1]);
+        x_end = sp.x0 + sp.x_len; r_end = (long long)sp.r0 + sp.n;
+    }
+    const int n = frame_offsets[n_waves];
+    bool empty = false;
+    RY_TRY(check_call(s, x_len, n, true, o, &empty));                   // never empty: every wave has a sample and a frame
+    if (!mc32_dev_out || !sp32_dev_out || !ap32_dev_out) return fail(RY_EINVAL, "null output rows");
+    if (!x32_dev) return fail(RY_EINVAL, "null wave");
+    if (!f0_dev || !t_dev) return fail(RY_EINVAL, "null f0 / t");
+    return extract_dev(s, x32_dev, x_len, f0_dev, t_dev, n, spans.data(), n_waves, o);
 }
 
 int ry_analysis_d4c_bands(ry_analysis* s) {

@@ -93,6 +93,15 @@ struct ry_crepe {
     std::vector<long long> trk_sample_off;
     std::vector<int> trk_frame_off;
     int trk_waves = 0;
+    // ry_crepe_upload_waves: the waves it left on the card at the caller's rate (in `audio` at 16 kHz, else in `audio_sr`), where each starts (waves + 1
+    // entries; empty: no such table) and their rate; what the last ry_crepe_track_uploaded / ry_crepe_bank_track_uploaded tracked of them
+    // (ry_crepe_uploaded_buffers).  Every other call that writes a call buffer forgets the table with the tracks.
+    const float* up_wave = nullptr;
+    std::vector<long long> up_off;
+    int up_sr = 0;
+    std::vector<int> sub_frame_off;
+    int sub_waves = 0;
+    long long net_frames = 0;                       // frames that went through the network so far (ry_crepe_debug_frames)
     // resampling: tables per input rate
     Arena rs_tables;
     std::map<int, Resampler> rs;
@@ -168,8 +177,11 @@ struct ry_crepe_bank {
 };
 
 namespace {
-// every call that writes a buffer of the track on the card forgets it
-void forget_track(ry_crepe* c) { c->trk_frames = 0; c->trk_waves = 0; }
+// every call that writes a buffer of the track on the card forgets it, and with it the uploaded table -- unless the call tracks waves of that table
+void forget_track(ry_crepe* c, bool keep_upload = false) {
+    c->trk_frames = 0; c->trk_waves = 0; c->sub_waves = 0;
+    if (!keep_upload) c->up_off.clear();
+}
 
 int ensure_chunk(ry_crepe* c, int nf) {
     if (nf <= c->cap_chunk) return RY_OK;
@@ -293,6 +305,7 @@ int run_passes(ry_crepe* c, const float* d_audio, int n_samples, int hop, int ce
         RT_TRY(rt::last_error());
         for (int i = 0; i <= NCONV; ++i) RY_TRY(launch_layer(c, i, k, rows + (size_t)f * CREPE_BINS));
         c->last_chunk = k;
+        c->net_frames += k;
     }
     return RY_OK;
 }
@@ -394,6 +407,37 @@ int upload_segments(ry_crepe* c, const std::vector<CrepeSeg>& plan) {
     RY_TRY(c->segs.reserve(c->ctx, (long long)plan.size()));
     c->seg_host = plan;                                                 // the handle's copy: the host array of the upload outlives the call
     RT_TRY(rt::h2d(c->segs.ptr(), c->seg_host.data(), c->seg_host.size() * sizeof(CrepeSeg), c->ctx->stream));
+    return RY_OK;
+}
+
+// The one upload of a call: total_in samples at the caller's rate into `audio` (16 kHz: the network reads them there) or `audio_sr` (r: the
+// resampler reads them there) -> where they lie.
+int upload_audio(ry_crepe* c, const Resampler* r, const float* audio, int total_in, float** wave) {
+    if (r) RY_TRY(c->audio_sr.reserve(c->ctx, total_in));
+    else RY_TRY(c->audio.reserve(c->ctx, total_in));
+    *wave = r ? c->audio_sr.ptr() : c->audio.ptr();
+    RT_TRY(rt::h2d(*wave, audio, (size_t)total_in * sizeof(float), c->ctx->stream));
+    return RY_OK;
+}
+
+// The segments of a call over waves ry_crepe_upload_waves left on the card: entry i of the table (first sample, samples) must BE one of the uploaded
+// waves, the entries ascend, the rate is the upload's.  The samples are read where they lie (in_off; at 16 kHz off16 too: the network reads the
+// upload itself), the 16 kHz samples and the frames of the tracked waves are packed as those of a call on these waves alone.
+int place_uploaded(const ry_crepe* c, const int* first_sample, const int* n_samples, int n_waves, int sr, std::vector<CrepeSeg>* plan) {
+    if (c->up_off.empty()) return fail(RY_ESTATE, "no waves on the card: ry_crepe_upload_waves has not run, or a later call reused its buffers");
+    if (sr != c->up_sr) return fail(RY_EINVAL, "the waves were uploaded at %d Hz, the call says %d", c->up_sr, sr);
+    long long end = 0;
+    for (int i = 0; i < n_waves; ++i) {
+        const long long a = first_sample[i];
+        if (a < end) return fail(RY_EINVAL, "wave %d starts at sample %lld, before the end of the one in front of it: the table must ascend", i, a);
+        const auto it = std::lower_bound(c->up_off.begin(), c->up_off.end() - 1, a);
+        if (it == c->up_off.end() - 1 || *it != a || *(it + 1) - a != (long long)n_samples[i])
+            return fail(RY_EINVAL, "wave %d (%d samples from %lld) is not a wave of the uploaded table", i, n_samples[i], a);
+        CrepeSeg& g = (*plan)[(size_t)i];
+        g.in_off = (int)a;
+        if (sr == 16000) g.off16 = (int)a;
+        end = a + n_samples[i];
+    }
     return RY_OK;
 }
 
@@ -862,11 +906,14 @@ int ry_crepe_track_buffers(ry_crepe* c, const float** wave_dev, int* n_samples, 
     return RY_OK;
 }
 
-int ry_crepe_track_many(ry_crepe* c, const float* audio, const int* n_samples, int n_waves, int sr, int hop, double step_ms, double threshold,
-                        int* n_frames, unsigned char* voiced, double* f0_64, double* t_64, int on_device_out) {
+// ry_crepe_track_many (audio: the waves of the call, uploaded by it) and ry_crepe_track_uploaded (audio null: first_sample names waves of the table
+// ry_crepe_upload_waves left): one body, so the segment table, the passes and the decode / voicing workgroup per wave are the same
+static int track_many_impl(ry_crepe* c, const float* audio, const int* first_sample, const int* n_samples, int n_waves, int sr, int hop, double step_ms,
+                           double threshold, int* n_frames, unsigned char* voiced, double* f0_64, double* t_64, int on_device_out) {
     RY_TRY(check_handle(c, "crepe"));
-    forget_track(c);                                                 // a refused call leaves no track either
-    if (!audio || !n_samples || !n_frames || hop < 1) return fail(RY_EINVAL, "bad argument");
+    const bool uploaded = audio == nullptr && first_sample != nullptr;
+    forget_track(c, uploaded);                                       // a refused call leaves no track either
+    if ((!audio && !first_sample) || !n_samples || !n_frames || hop < 1) return fail(RY_EINVAL, "bad argument");
     if (!on_device_out && (!voiced || !f0_64 || !t_64)) return fail(RY_EINVAL, "null output");
     if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
     RY_TRY(voicing_args(threshold, step_ms));
@@ -881,19 +928,16 @@ int ry_crepe_track_many(ry_crepe* c, const float* audio, const int* n_samples, i
     }
     std::vector<CrepeSeg> plan;
     RY_TRY(plan_segments(n_waves, n_samples, n16.data(), nf.data(), &plan));
+    if (uploaded) RY_TRY(place_uploaded(c, first_sample, n_samples, n_waves, sr, &plan));
     const CrepeSeg& last = plan.back();
     const int total_in = last.in_off + last.in_len, total16 = last.off16 + last.n16, total_nf = last.frame0 + last.n_frames;
     const ry_stream_t s = c->ctx->stream;
     RY_TRY(ensure_chunk(c, std::min(total_nf, CHUNK)));
-    RY_TRY(ensure_call(c, total_nf, total16));
+    RY_TRY(ensure_call(c, total_nf, total16));                         // an upload at 16 kHz lies in `audio`: it is longer than total16 and stays
     RY_TRY(ensure_track(c, total_nf));
-    float* wave = c->audio.ptr();                                    // the one upload: the waves at the caller's rate, back to back
-    if (r) {
-        RY_TRY(c->audio_sr.reserve(c->ctx, total_in));
-        wave = c->audio_sr.ptr();
-    }
+    float* wave = const_cast<float*>(c->up_wave);
+    if (!uploaded) RY_TRY(upload_audio(c, r, audio, total_in, &wave));     // the one upload: the waves at the caller's rate, back to back
     RY_TRY(upload_segments(c, plan));
-    RT_TRY(rt::h2d(wave, audio, (size_t)total_in * sizeof(float), s));
     const CrepeSeg* seg = c->segs.ptr();
     if (r) RY_TRY(launch_resample(c, *r, wave, total_in, sr, c->audio.ptr(), total16, seg, n_waves));
     RY_TRY(run_network(c, c->audio.ptr(), total16, hop, 1, 1, total_nf, nullptr, nullptr, nullptr, 1, seg, n_waves));
@@ -906,12 +950,64 @@ int ry_crepe_track_many(ry_crepe* c, const float* audio, const int* n_samples, i
         c->trk_frame_off[(size_t)i + 1] = plan[(size_t)i].frame0 + plan[(size_t)i].n_frames;
         n_frames[i] = nf[(size_t)i];
     }
-    c->trk_waves = n_waves;
+    if (uploaded) { c->sub_frame_off = c->trk_frame_off; c->sub_waves = n_waves; }    // the waves are not back to back: ry_crepe_uploaded_buffers reports them
+    else c->trk_waves = n_waves;
     if (on_device_out) return RY_OK;
     RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)total_nf, s));
     RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)total_nf * sizeof(double), s));
     RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)total_nf * sizeof(double), s));
     RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+int ry_crepe_track_many(ry_crepe* c, const float* audio, const int* n_samples, int n_waves, int sr, int hop, double step_ms, double threshold,
+                        int* n_frames, unsigned char* voiced, double* f0_64, double* t_64, int on_device_out) {
+    return track_many_impl(c, audio, nullptr, n_samples, n_waves, sr, hop, step_ms, threshold, n_frames, voiced, f0_64, t_64, on_device_out);
+}
+
+int ry_crepe_upload_waves(ry_crepe* c, const float* audio, const int* n_samples, int n_waves, int sr, const float** wave_dev) {
+    RY_TRY(check_handle(c, "crepe"));
+    forget_track(c);                                                 // a refused call leaves no table either
+    if (!audio || !n_samples || !wave_dev) return fail(RY_EINVAL, "bad argument");
+    if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
+    const Resampler* r = nullptr;
+    std::vector<long long> off((size_t)n_waves + 1, 0);
+    for (int i = 0; i < n_waves; ++i) {
+        if (n_samples[i] < 1) return fail(RY_EINVAL, "wave %d has %d samples", i, n_samples[i]);
+        int n16 = 0;
+        if (sr != 16000) RY_TRY(resample_plan(c, n_samples[i], sr, &r, &n16));
+        off[(size_t)i + 1] = off[(size_t)i] + n_samples[i];
+        if (off[(size_t)i + 1] > 2147483647LL) return fail(RY_EINVAL, "the waves up to %d hold %lld samples: too many for one call", i, off[(size_t)i + 1]);
+    }
+    float* wave = nullptr;
+    RY_TRY(upload_audio(c, r, audio, (int)off.back(), &wave));
+    c->up_wave = wave; c->up_off.swap(off); c->up_sr = sr;
+    *wave_dev = wave;
+    return RY_OK;
+}
+
+int ry_crepe_track_uploaded(ry_crepe* c, const int* first_sample, const int* n_samples, int n_waves, int sr, int hop, double step_ms, double threshold,
+                            int* n_frames, unsigned char* voiced, double* f0_64, double* t_64, int on_device_out) {
+    return track_many_impl(c, nullptr, first_sample, n_samples, n_waves, sr, hop, step_ms, threshold, n_frames, voiced, f0_64, t_64, on_device_out);
+}
+
+int ry_crepe_uploaded_buffers(ry_crepe* c, const float** wave_dev, long long* n_samples, int* n_tracked, const int** frame_offsets,
+                              const unsigned char** voiced_dev, const double** f0_dev, const double** t_dev) {
+    if (!c) return fail(RY_ESTATE, "null crepe handle");
+    if (c->up_off.empty()) return fail(RY_ESTATE, "no waves on the card: ry_crepe_upload_waves has not run, or a later call reused its buffers");
+    if (wave_dev) *wave_dev = c->up_wave;
+    if (n_samples) *n_samples = c->up_off.back();
+    if (n_tracked) *n_tracked = c->sub_waves;
+    if (frame_offsets) *frame_offsets = c->sub_waves > 0 ? c->sub_frame_off.data() : nullptr;
+    if (voiced_dev) *voiced_dev = c->voiced.ptr();
+    if (f0_dev) *f0_dev = c->f0_64.ptr();
+    if (t_dev) *t_dev = c->t_64.ptr();
+    return RY_OK;
+}
+
+int ry_crepe_debug_frames(ry_crepe* c, long long* n_frames) {
+    if (!c || !n_frames) return fail(RY_EINVAL, "bad argument");
+    *n_frames = c->net_frames;
     return RY_OK;
 }
 
@@ -1189,14 +1285,17 @@ int ry_crepe_bank_reset(ry_crepe_bank* b, int stream) {
     return RY_OK;
 }
 
-int ry_crepe_bank_track(ry_crepe_bank* b, const float* audio, const int* n_samples, const int* stream_of, int n_waves, int sr, int hop, double step_ms,
-                        double threshold, const int* advance, const int* overlap_ok, int* n_frames, int* n_computed, unsigned char* voiced,
-                        double* f0_64, double* t_64, int on_device_out) {
+// ry_crepe_bank_track (audio: the waves of the call, uploaded by it) and ry_crepe_bank_track_uploaded (audio null: first_sample names waves of the
+// table ry_crepe_upload_waves left on the model): one body
+static int bank_track_impl(ry_crepe_bank* b, const float* audio, const int* first_sample, const int* n_samples, const int* stream_of, int n_waves, int sr,
+                           int hop, double step_ms, double threshold, const int* advance, const int* overlap_ok, int* n_frames, int* n_computed,
+                           unsigned char* voiced, double* f0_64, double* t_64, int on_device_out) {
     RY_TRY(check_handle(b, "crepe bank"));
     ry_crepe* c = b->model;
-    forget_track(c);                                                 // a refused call leaves no track either
+    const bool uploaded = audio == nullptr && first_sample != nullptr;
+    forget_track(c, uploaded);                                       // a refused call leaves no track either
     // every refusal first, before anything is launched or written: those of ry_crepe_track_many, then the bank's own
-    if (!audio || !n_samples || !stream_of || !advance || !overlap_ok || !n_frames || !n_computed || hop < 1) return fail(RY_EINVAL, "bad argument");
+    if ((!audio && !first_sample) || !n_samples || !stream_of || !advance || !overlap_ok || !n_frames || !n_computed || hop < 1) return fail(RY_EINVAL, "bad argument");
     if (!on_device_out && (!voiced || !f0_64 || !t_64)) return fail(RY_EINVAL, "null output");
     if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
     RY_TRY(voicing_args(threshold, step_ms));
@@ -1216,6 +1315,7 @@ int ry_crepe_bank_track(ry_crepe_bank* b, const float* audio, const int* n_sampl
     }
     std::vector<CrepeSeg> plan;
     RY_TRY(plan_segments(n_waves, n_samples, n16.data(), nf.data(), &plan));
+    if (uploaded) RY_TRY(place_uploaded(c, first_sample, n_samples, n_waves, sr, &plan));
     const CrepeSeg& last = plan.back();
     const int total_in = last.in_off + last.in_len, total16 = last.off16 + last.n16, total_nf = last.frame0 + last.n_frames;
     // the tables, host work only: per wave the rule against that stream's kept call, the packed rows numbered through the call, the frames call-global
@@ -1270,13 +1370,9 @@ int ry_crepe_bank_track(ry_crepe_bank* b, const float* audio, const int* n_sampl
         wrote[(size_t)i] = k.valid ? 1 - k.kept : 0;
         k.valid = false;
     }
-    float* wave = c->audio.ptr();                                    // the one upload: the waves at the caller's rate, back to back
-    if (r) {
-        RY_TRY(c->audio_sr.reserve(c->ctx, total_in));
-        wave = c->audio_sr.ptr();
-    }
+    float* wave = const_cast<float*>(c->up_wave);
+    if (!uploaded) RY_TRY(upload_audio(c, r, audio, total_in, &wave));     // the one upload: the waves at the caller's rate, back to back
     RY_TRY(upload_segments(c, plan));
-    RT_TRY(rt::h2d(wave, audio, (size_t)total_in * sizeof(float), s));
     const CrepeSeg* seg = c->segs.ptr();
     if (r) RY_TRY(launch_resample(c, *r, wave, total_in, sr, c->audio.ptr(), total16, seg, n_waves));
     RY_TRY(run_passes(c, c->audio.ptr(), total16, hop, 1, total_comp, d_idx, b->fresh.ptr(), seg, n_waves));
@@ -1293,13 +1389,28 @@ int ry_crepe_bank_track(ry_crepe_bank* b, const float* audio, const int* n_sampl
         n_frames[i] = nf[(size_t)i];
         n_computed[i] = comp[(size_t)i];
     }
-    c->trk_waves = n_waves;
+    if (uploaded) { c->sub_frame_off = c->trk_frame_off; c->sub_waves = n_waves; }
+    else c->trk_waves = n_waves;
     if (on_device_out) return RY_OK;
     RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)total_nf, s));
     RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)total_nf * sizeof(double), s));
     RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)total_nf * sizeof(double), s));
     RT_TRY(rt::stream_sync(s));
     return RY_OK;
+}
+
+int ry_crepe_bank_track(ry_crepe_bank* b, const float* audio, const int* n_samples, const int* stream_of, int n_waves, int sr, int hop, double step_ms,
+                        double threshold, const int* advance, const int* overlap_ok, int* n_frames, int* n_computed, unsigned char* voiced,
+                        double* f0_64, double* t_64, int on_device_out) {
+    return bank_track_impl(b, audio, nullptr, n_samples, stream_of, n_waves, sr, hop, step_ms, threshold, advance, overlap_ok, n_frames, n_computed, voiced,
+                           f0_64, t_64, on_device_out);
+}
+
+int ry_crepe_bank_track_uploaded(ry_crepe_bank* b, const int* first_sample, const int* n_samples, const int* stream_of, int n_waves, int sr, int hop,
+                                 double step_ms, double threshold, const int* advance, const int* overlap_ok, int* n_frames, int* n_computed,
+                                 unsigned char* voiced, double* f0_64, double* t_64, int on_device_out) {
+    return bank_track_impl(b, nullptr, first_sample, n_samples, stream_of, n_waves, sr, hop, step_ms, threshold, advance, overlap_ok, n_frames, n_computed,
+                           voiced, f0_64, t_64, on_device_out);
 }
 
 int ry_crepe_bank_activation(ry_crepe_bank* b, int stream, float* out, int on_device) {

@@ -127,6 +127,10 @@ struct ry_vc {
         void release() { bufs.release(); for (void* q : pinned) rt::hfree(q); pinned.clear(); cap_waves = cap_pow = cap_frames = 0; }
     };
     WaveSet wset;
+    // ry_vc_enqueue_waves_masked_device does not wait for its compaction: ev_seg (recorded behind it) orders the windows of the other lanes behind
+    // it, and the next call that rewrites the pinned wave table waits for it on the host (seg_busy)
+    rt::Event ev_seg;
+    bool seg_busy = false;
     void free_pinned() { for (VcSlot& sl : slot) sl.free_pinned(); wset.release(); }
 };
 
@@ -265,6 +269,7 @@ int ry_vc_create(ry_net* s1, ry_net* s2, const float* mtx, int M, int F, ry_vc**
     RY_TRY(upload(vc->arena, s1->ctx, h, &vc->d_mtx));
     for (VcSlot& sl : vc->slot) { RT_TRY(rt::event_create_fast(&sl.ev_mid)); RT_TRY(rt::event_create_fast(&sl.ev_done)); }
     RT_TRY(rt::event_create_fast(&vc->ev_in));
+    RT_TRY(rt::event_create_fast(&vc->ev_seg));
     vc->has_ev = true;
     *out = vc.release();
     return RY_OK;
@@ -275,7 +280,7 @@ void ry_vc_destroy(ry_vc* vc) {
     rt::set_device(vc->s1->ctx->device);
     vc->sync_lanes();
     for (int k = 1; k < vc->lanes; ++k) { ry_net_destroy(vc->l1[k]); ry_net_destroy(vc->l2[k]); }
-    if (vc->has_ev) { for (VcSlot& sl : vc->slot) { rt::event_destroy(sl.ev_mid); rt::event_destroy(sl.ev_done); } rt::event_destroy(vc->ev_in); }
+    if (vc->has_ev) { for (VcSlot& sl : vc->slot) { rt::event_destroy(sl.ev_mid); rt::event_destroy(sl.ev_done); } rt::event_destroy(vc->ev_in); rt::event_destroy(vc->ev_seg); }
     if (vc->b_ev) for (ry_vc::BatchSet& bs : vc->bset) { rt::event_destroy(bs.mid); rt::event_destroy(bs.done); }
     vc->free_pinned();
     delete vc;
@@ -642,8 +647,8 @@ int ry_gather_rows(ry_ctx* ctx, const float* rows_dev, int n_rows, int cols, con
 struct VcWaves { std::vector<RyWaveSeg> seg; int total_frames = 0, total_wave_frames = 0; };
 
 static int vc_waves_args(const ry_vc* vc, const float* wave_dev, const long long* sample_offsets, const int* frame_offsets, int n_waves, int hop,
-                         int fft_length, const float* feat_dev, VcWaves* out) {
-    if (!vc || !wave_dev || !feat_dev || !sample_offsets || !frame_offsets) return fail(RY_EINVAL, "null argument");
+                         int fft_length, const float* feat_dev, VcWaves* out, bool need_feat = true) {
+    if (!vc || !wave_dev || (need_feat && !feat_dev) || !sample_offsets || !frame_offsets) return fail(RY_EINVAL, "null argument");
     if (n_waves < 1 || n_waves > (1 << 16)) return fail(RY_EINVAL, "n_waves must be in 1..65536 (got %d)", n_waves);
     if (hop < 1) return fail(RY_EINVAL, "bad sizes (hop %d)", hop);
     if (fft_length < 128 || fft_length > 1024 || (fft_length & (fft_length - 1)))
@@ -708,6 +713,7 @@ static int vc_gate_waves_launch(ry_vc* vc, ry_net* s1, const float* d_wave, cons
     ry_vc::WaveSet& ws = vc->wset;
     const int n_waves = (int)w.seg.size();
     ry_stream_t st1 = s1->stream;
+    if (vc->seg_busy) { RT_TRY(rt::event_sync(vc->ev_seg)); vc->seg_busy = false; }      // a masked call's copy of the table may still be queued
     memcpy(ws.h_seg, w.seg.data(), (size_t)n_waves * sizeof(RyWaveSeg));
     RT_TRY(rt::h2d(ws.d_seg, ws.h_seg, (size_t)n_waves * sizeof(RyWaveSeg), st1));
     Launcher Lc{s1, s1->ctx, st1, nullptr, nullptr};
@@ -719,7 +725,7 @@ static int vc_gate_waves_launch(ry_vc* vc, ry_net* s1, const float* d_wave, cons
     RY_LAUNCH(ry_frame_power_many, fg, 256, st1, fp);
     RY_TRY(Lc.end());
     RyGateManyParams gp;
-    gp.power = ws.d_pow; gp.seg = ws.d_seg; gp.p_eff = p_effective; gp.p_all = p_all; gp.feat = d_feat; gp.cin = s1->desc.in_ch;
+    gp.power = ws.d_pow; gp.seg = ws.d_seg; gp.p_eff = p_effective; gp.p_all = p_all; gp.feat = d_feat; gp.cin = d_feat ? s1->desc.in_ch : 0;
     gp.x_eff = d_x; gp.row_of = d_row; gp.mask = d_mask; gp.host = ws.d_host; gp.n_waves = n_waves;
     RY_TRY(Lc.begin("ry_gate_compact_many", "separate_effective", 0, 0, dim3((unsigned)n_waves)));
     RY_LAUNCH(ry_gate_compact_many, dim3((unsigned)n_waves), 1024, st1, gp);
@@ -804,6 +810,155 @@ int ry_vc_enqueue_waves_device(ry_vc* vc, const float* wave_dev, const long long
         if (sl.used) RT_TRY(rt::stream_wait_event(st1, sl.ev_done));                    // the slot's previous window has left d_y1 / d_sp
         if (n_eff > 0) RY_TRY(ry_ac_convert(s1, vc->wset.d_x + (size_t)g.r0 * cin, sl.d_y1, 1, n_eff, 1));
         RY_TRY(vc_enqueue_mid(vc, s1, sl.d_y1, vc->wset.d_row + g.r0, n_eff, n_frames, sp_floor, mc_out_dev + (size_t)g.f0 * M, sl.d_sp));
+        RY_TRY(vc_join(sl.ev_mid, st1, st2));
+        RY_TRY(vc_run_stage2(vc, s2, sl.d_sp, sp_out_dev + (size_t)g.f0 * F, n_frames));
+        RT_TRY(rt::event_record(sl.ev_done, st2));
+        if (stc != st2) RT_TRY(rt::stream_wait_event(stc, sl.ev_done));
+        sl.used = true;
+    }
+    vc->split_eff = -1;
+    return RY_OK;
+}
+
+// The verdict of ry_vc_gate_waves_device alone, for waves whose feature rows do not exist yet: the same two launches and the same one wait, with no
+// feature row read or written (the gate's copy loop runs over zero columns; its row_of entries land in the core's own block and are overwritten by
+// the compaction of the window call that follows) -- mask_dev_out / effective_out [sum n] and
+// n_eff_out [n_waves] have the bits of ry_vc_gate_waves_device.  What it refuses: what that call refuses, but for the feature block it does not take.
+int ry_vc_gate_verdict_waves_device(ry_vc* vc, const float* wave_dev, const long long* sample_offsets, const int* frame_offsets, int n_waves, int hop,
+                                    int fft_length, float p_effective, float p_all, unsigned char* mask_dev_out, unsigned char* effective_out,
+                                    int* n_eff_out) {
+    VcWaves w;
+    RY_TRY(vc_waves_args(vc, wave_dev, sample_offsets, frame_offsets, n_waves, hop, fft_length, nullptr, &w, false));
+    if (!mask_dev_out || !effective_out || !n_eff_out) return fail(RY_EINVAL, "null argument");
+    RT_TRY(rt::set_device(vc->s1->ctx->device));
+    Stage1On on_lane(vc, vc->s1, vc->s2);
+    ry_stream_t st1 = vc->s1->stream, stc = vc->s1->ctx->stream;
+    vc->note(st1, st1);
+    RY_TRY(vc_waves_reserve(vc, w));
+    if (stc != st1) { RT_TRY(rt::event_record(vc->ev_in, stc)); RT_TRY(rt::stream_wait_event(st1, vc->ev_in)); }
+    return vc_gate_waves_launch(vc, vc->s1, wave_dev, w, hop, fft_length, p_effective, p_all, nullptr, vc->wset.d_x, vc->wset.d_row, mask_dev_out,
+                                effective_out, n_eff_out);
+}
+
+}  // extern "C"
+
+// what the calls that take a verdict refuse, before anything is launched or written: null pointers, offsets that do not start at 0 or do not ascend,
+// a count outside its wave, a host mask whose ones are not n_eff[i] of them
+static int vc_masked_args(const ry_vc* vc, const int* frame_offsets, int n_waves, const unsigned char* mask_dev, const unsigned char* effective,
+                          const int* n_eff, const float* feat_dev, VcWaves* out, int* total_eff) {
+    if (!vc || !frame_offsets || !mask_dev || !effective || !n_eff || !feat_dev) return fail(RY_EINVAL, "null argument");
+    if (n_waves < 1 || n_waves > (1 << 16)) return fail(RY_EINVAL, "n_waves must be in 1..65536 (got %d)", n_waves);
+    if (frame_offsets[0] != 0) return fail(RY_EINVAL, "the offsets start at %d, not at 0", frame_offsets[0]);
+    out->seg.resize((size_t)n_waves);
+    *total_eff = 0;
+    for (int i = 0; i < n_waves; ++i) {
+        const long long nf = (long long)frame_offsets[i + 1] - frame_offsets[i];
+        if (nf < 1) return fail(RY_EINVAL, "wave %d: %lld frames: the offsets must ascend", i, nf);
+        if (frame_offsets[i + 1] > (1 << 22)) return fail(RY_EINVAL, "wave %d ends at frame %d: at most 2^22 in one call", i, frame_offsets[i + 1]);
+        if (n_eff[i] < 0 || n_eff[i] > nf) return fail(RY_EINVAL, "wave %d: %d effective frames of %lld", i, n_eff[i], nf);
+        int ones = 0;
+        for (int t = frame_offsets[i]; t < frame_offsets[i + 1]; ++t) ones += effective[t] != 0;
+        if (ones != n_eff[i]) return fail(RY_EINVAL, "wave %d: the mask holds %d effective frames, n_eff says %d", i, ones, n_eff[i]);
+        RyWaveSeg& s = out->seg[(size_t)i];
+        s.s0 = 0; s.n_samples = 0; s.f0 = frame_offsets[i]; s.n_frames = (int)nf; s.p0 = 0; s.n_wave_frames = 0; s.r0 = s.f0; s.pad = 0;
+        *total_eff += n_eff[i];
+    }
+    out->total_frames = frame_offsets[n_waves];
+    out->total_wave_frames = 0;
+    return RY_OK;
+}
+
+// table up, one compaction workgroup per wave; nothing is waited for (ev_seg is recorded behind it)
+static int vc_compact_launch(ry_vc* vc, ry_net* s1, const VcWaves& w, const unsigned char* d_mask, const float* d_feat, float* d_x, int* d_row) {
+    ry_vc::WaveSet& ws = vc->wset;
+    const int n_waves = (int)w.seg.size();
+    ry_stream_t st1 = s1->stream;
+    if (vc->seg_busy) { RT_TRY(rt::event_sync(vc->ev_seg)); vc->seg_busy = false; }
+    memcpy(ws.h_seg, w.seg.data(), (size_t)n_waves * sizeof(RyWaveSeg));
+    RT_TRY(rt::h2d(ws.d_seg, ws.h_seg, (size_t)n_waves * sizeof(RyWaveSeg), st1));
+    Launcher Lc{s1, s1->ctx, st1, nullptr, nullptr};
+    RyCompactManyParams cp;
+    cp.mask = d_mask; cp.seg = ws.d_seg; cp.feat = d_feat; cp.cin = s1->desc.in_ch; cp.x_eff = d_x; cp.row_of = d_row;
+    RY_TRY(Lc.begin("ry_compact_rows_many", "separate_effective", 0, 0, dim3((unsigned)n_waves)));
+    RY_LAUNCH(ry_compact_rows_many, dim3((unsigned)n_waves), 1024, st1, cp);
+    RY_TRY(Lc.end());
+    RT_TRY(rt::event_record(vc->ev_seg, st1));
+    vc->seg_busy = true;
+    return RY_OK;
+}
+
+extern "C" {
+
+// The compaction alone (tests): x_eff_dev_out [sum n][in_ch] / row_of_dev_out [sum n] (both null: blocks of the core) get, from row frame_offsets[i] on,
+// the effective rows of wave i and their frame indices as ry_vc_gate_waves_device writes them, from mask_dev [sum n] (the gate's mask on the card),
+// effective [sum n] (its host copy) and n_eff [n_waves].  Rows behind the n_eff[i] of a wave are not written.  The call waits for the kernel.
+int ry_vc_compact_waves_device(ry_vc* vc, const int* frame_offsets, int n_waves, const unsigned char* mask_dev, const unsigned char* effective,
+                               const int* n_eff, const float* feat_dev, float* x_eff_dev_out, int* row_of_dev_out) {
+    VcWaves w;
+    int total_eff = 0;
+    RY_TRY(vc_masked_args(vc, frame_offsets, n_waves, mask_dev, effective, n_eff, feat_dev, &w, &total_eff));
+    if ((!x_eff_dev_out) != (!row_of_dev_out)) return fail(RY_EINVAL, "null argument");
+    RT_TRY(rt::set_device(vc->s1->ctx->device));
+    Stage1On on_lane(vc, vc->s1, vc->s2);
+    ry_stream_t st1 = vc->s1->stream, stc = vc->s1->ctx->stream;
+    vc->note(st1, st1);
+    RY_TRY(vc_waves_reserve(vc, w));
+    if (stc != st1) { RT_TRY(rt::event_record(vc->ev_in, stc)); RT_TRY(rt::stream_wait_event(st1, vc->ev_in)); }
+    RY_TRY(vc_compact_launch(vc, vc->s1, w, mask_dev, feat_dev, x_eff_dev_out ? x_eff_dev_out : vc->wset.d_x,
+                             row_of_dev_out ? row_of_dev_out : vc->wset.d_row));
+    RT_TRY(rt::stream_sync(st1));
+    return RY_OK;
+}
+
+// ry_vc_enqueue_waves_device with the verdict as an INPUT (ry_vc_gate_verdict_waves_device made it before the feature rows existed): mask_dev [sum n] on
+// the card, effective [sum n] and n_eff [n_waves] on the host.  The frame-power and verdict kernels do not run and nothing is waited for: one
+// compaction launch (ry_compact_rows_many; none when no wave has an effective frame) gathers the effective rows of every wave from feat_dev -- no
+// feature row of a frame whose mask byte is 0 is read, so the rows of a wave with n_eff = 0 need not exist -- then, wave by wave in order, the rest
+// of ry_vc_enqueue_waves_device: stage 1 where n_eff > 0, scatter, mc2sp, stage 2, with the same ring slots and lanes.  mc and sp of wave i have the
+// bits of ry_vc_enqueue_wave_device on wave i alone.  Stream order as there.  What it refuses (RY_EINVAL), before anything is launched or written:
+// null pointers, offsets that do not start at 0 or do not ascend, a count outside its wave, a host mask whose ones are not n_eff[i] of them; a ring
+// slot of the call held by a ticket (RY_ESTATE).
+int ry_vc_enqueue_waves_masked_device(ry_vc* vc, const int* frame_offsets, int n_waves, const float* feat_dev, float sp_floor, float* mc_out_dev,
+                                      float* sp_out_dev, const unsigned char* mask_dev, const unsigned char* effective, const int* n_eff) {
+    VcWaves w;
+    int total_eff = 0;
+    RY_TRY(vc_masked_args(vc, frame_offsets, n_waves, mask_dev, effective, n_eff, feat_dev, &w, &total_eff));
+    if (!mc_out_dev || !sp_out_dev) return fail(RY_EINVAL, "null argument");
+    for (int i = 0; i < n_waves && i < vc->ring; ++i) {
+        const int k = (vc->dev_count + i) % vc->ring;
+        if (vc->slot[k].ticket >= 0) return fail(RY_ESTATE, "wave %d: ring slot %d is held by ticket %d: ry_vc_wait it first", i, k, vc->slot[k].ticket);
+    }
+    RT_TRY(rt::set_device(vc->s1->ctx->device));
+    const ry_stream_t stc = vc->s1->ctx->stream;
+    const size_t M = (size_t)vc->M, F = (size_t)vc->F, cin = (size_t)vc->s1->desc.in_ch;
+    RY_TRY(vc_waves_reserve(vc, w));
+    ry_stream_t st_first = nullptr;
+    {   // the one compaction, on the stage-1 stream of the first window's lane, behind everything queued on the context stream
+        const int k = vc->dev_count % vc->ring;
+        ry_net *s1 = vc->lane1(k), *s2 = vc->lane2(k);
+        Stage1On on_lane(vc, s1, s2);
+        st_first = s1->stream;
+        vc->note(st_first, st_first);
+        if (stc != st_first) { RT_TRY(rt::event_record(vc->ev_in, stc)); RT_TRY(rt::stream_wait_event(st_first, vc->ev_in)); }
+        if (total_eff > 0) RY_TRY(vc_compact_launch(vc, s1, w, mask_dev, feat_dev, vc->wset.d_x, vc->wset.d_row));
+    }
+    for (int i = 0; i < n_waves; ++i) {
+        const RyWaveSeg& g = w.seg[(size_t)i];
+        const int k = vc->dev_count % vc->ring, ne = n_eff[i], n_frames = g.n_frames;
+        VcSlot& sl = vc->slot[k];
+        ry_net *s1 = vc->lane1(k), *s2 = vc->lane2(k);
+        Stage1On on_lane(vc, s1, s2);
+        RY_TRY(vc_reserve_slot(vc, sl, n_frames, n_frames));
+        ++vc->dev_count;
+        ry_stream_t st1 = s1->stream, st2 = s2->stream;
+        vc->note(st1, st2);
+        if (sl.used) RT_TRY(rt::stream_wait_event(st1, sl.ev_done));                    // the slot's previous window has left d_y1 / d_sp
+        if (st1 != st_first) {                                                         // nobody has waited for the context stream or the compaction here
+            if (stc != st1) RT_TRY(rt::stream_wait_event(st1, vc->ev_in));
+            if (total_eff > 0) RT_TRY(rt::stream_wait_event(st1, vc->ev_seg));
+        }
+        if (ne > 0) RY_TRY(ry_ac_convert(s1, vc->wset.d_x + (size_t)g.r0 * cin, sl.d_y1, 1, ne, 1));
+        RY_TRY(vc_enqueue_mid(vc, s1, sl.d_y1, vc->wset.d_row + g.r0, ne, n_frames, sp_floor, mc_out_dev + (size_t)g.f0 * M, sl.d_sp));
         RY_TRY(vc_join(sl.ev_mid, st1, st2));
         RY_TRY(vc_run_stage2(vc, s2, sl.d_sp, sp_out_dev + (size_t)g.f0 * F, n_frames));
         RT_TRY(rt::event_record(sl.ev_done, st2));

@@ -212,6 +212,50 @@ RY_KERNEL(1024) void ry_gate_compact_many(RyGateManyParams p) {
     for (int t = (int)threadIdx.x; t < s.n_frames; t += 1024) bytes[t] = g.mask[t];
 }
 
+// The compaction of ry_gate_compact_many alone, from a verdict that already exists (ry_vc_enqueue_waves_masked_device: the gate ran before the
+// feature rows were made): one workgroup per wave of the table reads the wave's mask bytes, 1024 frames a round, and writes row_of and the
+// effective rows into the wave's own region of the call's blocks -- ascending frames, so order and bits are the gate's.  The positions come from
+// the same inclusive scan over the round in the LDS, no atomics; the rows of a round are then copied by all threads, element by element
+// in destination order, so the stores of a wave of lanes are contiguous.  A frame whose mask byte is 0 has no feature row read: a wave without an
+// effective frame reads and writes nothing but its mask bytes.
+struct RyCompactManyParams { const unsigned char* mask; const RyWaveSeg* seg; const float* feat; int cin; float* x_eff; int* row_of; };
+
+RY_KERNEL(1024) void ry_compact_rows_many(RyCompactManyParams p) {
+    __shared__ int scan[1024];
+    __shared__ int rows[1024];
+    __shared__ int s_base;
+    const RyWaveSeg s = p.seg[blockIdx.x];
+    const int tid = (int)threadIdx.x, cin = p.cin;
+    const unsigned char* mask = p.mask + s.f0;
+    const float* feat = p.feat + (size_t)s.f0 * cin;
+    float* x_eff = p.x_eff + (size_t)s.r0 * cin;
+    int* row_of = p.row_of + s.r0;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int t0 = 0; t0 < s.n_frames; t0 += 1024) {
+        const int t = t0 + tid;
+        const bool eff = t < s.n_frames && mask[t] != 0;
+        scan[tid] = eff ? 1 : 0;
+        __syncthreads();
+        for (int d = 1; d < 1024; d <<= 1) {                    // inclusive Hillis-Steele scan
+            const int add = tid >= d ? scan[tid - d] : 0;
+            __syncthreads();
+            scan[tid] += add;
+            __syncthreads();
+        }
+        const int base = s_base, count = scan[1023];
+        if (eff) { rows[scan[tid] - 1] = t; row_of[base + scan[tid] - 1] = t; }
+        __syncthreads();
+        for (int i = tid; i < count * cin; i += 1024) {         // count <= 1024: the product fits
+            const int r = i / cin;
+            x_eff[(size_t)base * cin + i] = feat[(size_t)rows[r] * cin + (i - r * cin)];
+        }
+        __syncthreads();
+        if (tid == 1023) s_base = base + count;
+        __syncthreads();
+    }
+}
+
 struct RyMc2spParams { const float* mc; const float* mtx; float* sp; int n, m, f; float floor; };
 
 RY_KERNEL(256) void ry_mc2sp(RyMc2spParams p) {                 // sp[n][f] = exp(sum_m mc[n][m] * mtx[m][f]) + floor

@@ -361,6 +361,50 @@ class VcCore(object):
             ctypes.cast(ctypes.c_void_p(int(mask_ptr)), ub), mask.ctypes.data_as(ub), n_eff.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return mask[:int(fo[-1])].astype(bool), n_eff
 
+    def gate_verdict_waves_device(self, wave_ptr: int, sample_offsets, frame_offsets, hop: int, fft_length: int, p_effective: float, p_all: float,
+                                  mask_ptr: int):
+        """`ry_vc_gate_verdict_waves_device`: the verdict of `gate_waves_device` before any feature row exists -- the same launches, the same one
+        wait, no row read or written -> (effective (sum n,) bool, n_eff (waves,) int32), the mask bytes at `mask_ptr`."""
+        so, fo, pso, pfo = self._offsets(sample_offsets, frame_offsets)
+        mask, n_eff = numpy.empty(max(int(fo[-1]), 1), numpy.uint8), numpy.zeros(so.size - 1, numpy.int32)
+        ub = ctypes.POINTER(ctypes.c_ubyte)
+        self.lib.check(self.lib.dll.ry_vc_gate_verdict_waves_device(
+            self.handle, _lib._fptr(int(wave_ptr)), pso, pfo, so.size - 1, int(hop), int(fft_length), float(p_effective), float(p_all),
+            ctypes.cast(ctypes.c_void_p(int(mask_ptr)), ub), mask.ctypes.data_as(ub), n_eff.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return mask[:int(fo[-1])].astype(bool), n_eff
+
+    @staticmethod
+    def _verdict(frame_offsets, effective, n_eff):
+        fo = numpy.ascontiguousarray(frame_offsets, dtype=numpy.int32).ravel()
+        if fo.size < 2:
+            raise ValueError('frame offsets of waves + 1 >= 2 entries are needed, got %d' % fo.size)
+        eff = numpy.ascontiguousarray(numpy.asarray(effective).astype(numpy.uint8)).ravel()
+        ne = numpy.ascontiguousarray(n_eff, dtype=numpy.int32).ravel()
+        if eff.size != int(fo[-1]) or ne.size != fo.size - 1:
+            raise ValueError('%d mask bytes and %d counts for %d frames of %d waves' % (eff.size, ne.size, int(fo[-1]), fo.size - 1))
+        ub, ip = ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_int)
+        return fo, eff, ne, fo.ctypes.data_as(ip), eff.ctypes.data_as(ub), ne.ctypes.data_as(ip)
+
+    def compact_waves_device(self, frame_offsets, mask_ptr: int, effective, n_eff, feat_ptr: int, x_eff_ptr: Optional[int] = None,
+                             row_of_ptr: Optional[int] = None) -> None:
+        """`ry_vc_compact_waves_device`: the ordered compaction of `gate_waves_device` alone, from its verdict (the mask bytes at `mask_ptr`, their
+        host copy and the counts): the effective rows and their frame indices at `x_eff_ptr` / `row_of_ptr`, wave i from row frame_offsets[i] on."""
+        fo, eff, ne, pfo, peff, pne = self._verdict(frame_offsets, effective, n_eff)
+        ub, ip = ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_int)
+        self.lib.check(self.lib.dll.ry_vc_compact_waves_device(
+            self.handle, pfo, fo.size - 1, ctypes.cast(ctypes.c_void_p(int(mask_ptr)), ub), peff, pne, _lib._fptr(int(feat_ptr)),
+            _lib._fptr(None if x_eff_ptr is None else int(x_eff_ptr)), ctypes.cast(ctypes.c_void_p(int(row_of_ptr or 0)), ip)))
+
+    def enqueue_waves_masked_device(self, frame_offsets, feat_ptr: int, mc_ptr: int, sp_ptr: int, mask_ptr: int, effective, n_eff,
+                                    sp_floor: float = 1e-16) -> None:
+        """`ry_vc_enqueue_waves_masked_device`: `enqueue_waves_device` on a verdict `gate_verdict_waves_device` made earlier -- no gate kernel, no
+        wait; the feature rows of a wave without an effective frame are not read."""
+        fo, eff, ne, pfo, peff, pne = self._verdict(frame_offsets, effective, n_eff)
+        ub = ctypes.POINTER(ctypes.c_ubyte)
+        self.lib.check(self.lib.dll.ry_vc_enqueue_waves_masked_device(
+            self.handle, pfo, fo.size - 1, _lib._fptr(int(feat_ptr)), float(sp_floor), _lib._fptr(int(mc_ptr)), _lib._fptr(int(sp_ptr)),
+            ctypes.cast(ctypes.c_void_p(int(mask_ptr)), ub), peff, pne))
+
     def enqueue_device_batch(self, x_ptr: int, rows_ptr: int, n_eff, n_frames: int, mc_ptr: int, sp_ptr: int, sp_floor: float = 1e-16):
         """`ry_vc_enqueue_device_batch`: len(n_eff) windows of n_frames each, device pointers, nothing waited for."""
         ne = numpy.ascontiguousarray(n_eff, dtype=numpy.int32)

@@ -13,7 +13,14 @@ converted spectrogram stay on the card) -> `ry_mask_rows` (combine_silent of ap)
 exchanges the wave (up, once), the track, the mask and the count (down), the converted f0 (up) and the samples (down); f0 goes through the
 F0Converter on the host with exactly the numpy operations of the separate calls.  Every result has the bits of the chain of the separate calls:
 `encode.extract` -> `VoiceChanger.convert_from_acoustic_feature` -> `world_synth.decode` (or `decode_realtime`), which is also what runs -- unchanged
--- whenever the resident path does not apply (`calls` counts which way a call went)."""
+-- whenever the resident path does not apply (`calls` counts which way a call went).
+
+`gate_first=True` (at construction, or per call) is the resident path with the silence gate in front of the encode stage: the waves go up once
+(`CrepeModel.upload_waves`), `VcCore.gate_verdict_waves_device` gives every wave's mask and count with one wait, and only the waves with an
+effective frame go through the tracker (`track_uploaded`) and the analysis (`Analyzer.extract_spans_resident`, rows at the wave's place in the
+layout of the whole call); `VcCore.enqueue_waves_masked_device` then runs every wave's window on that verdict.  A wave without an effective frame
+costs no tracker, CheapTrick, sp2mc or D4C kernel, none of its feature rows is read, and every sample of every stream keeps its bits (DESIGN.md
+section 21).  `calls['gated']` counts the waves skipped; `last_gate` is the record of the last such call."""
 import ctypes
 import os
 from typing import Optional
@@ -26,7 +33,68 @@ from . import encode, gate, world_analysis, world_synth
 from .voice_changer import SP_FLOOR
 from .world_synth import BINS, FFT_SIZE, cheaptrick_fft_size
 
-calls = {'resident': 0, 'composed': 0}          # which path `convert_wave` / `push` took, counted per call
+calls = {'resident': 0, 'composed': 0}          # which path `convert_wave` / `push` took, counted per call; 'gated' (from the first gate_first
+                                                # call on): the waves whose encode stage the gate skipped
+
+
+def _gated(counter: dict, n: int) -> None:
+    counter['gated'] = counter.get('gated', 0) + int(n)
+
+
+def _spanned(advance, pending):
+    """The advance of a buffer against the window its stream's tracker keeps: the caller's, plus those of the buffers the gate skipped since
+    (None: one of them declared nothing, so neither does this one)."""
+    return None if advance is None or pending is None else int(advance) + int(pending)
+
+
+def _gate_first_rows(handles, acoustic_param, voice_changer, waves, discard, reserve, tracker=None, streams=None, advances=None):
+    """The resident chain with the gate in front, for the waves of one call -> (context, blocks, frame offsets int32 [waves + 1], [f0 float64
+    [frames_i]], record).  tracker / streams / advances (`push(..., advance=a)`): a `CrepeStreamBank`, the stream of every wave and its advance
+    against the window that stream's tracker keeps; None: `CrepeModel.track_uploaded`.  record: n_eff per wave, which waves were tracked, and the
+    frames of each that went through the network where a stream bank ran (None for a wave that was skipped)."""
+    model, analyzer, core, (p_eff, p_all), hop, gate_fft = handles
+    p, ac = acoustic_param, voice_changer.acoustic_converter
+    fs = int(waves[0].sampling_rate)
+    xs = [numpy.ascontiguousarray(w.wave, dtype=numpy.float32).ravel() for w in waves]
+    hop16 = _crepe.hop_length(p.frame_period)
+    up = model.upload_waves(xs, fs)                                        # the one upload
+    fo = numpy.concatenate([[0], numpy.cumsum([_crepe.track_frames(x.size, fs, hop16) for x in xs])]).astype(numpy.int32)
+    n, ctx = int(fo[-1]), core.stage1.ctx
+    b = reserve(ctx, n, p.order + 1, core.M, core.F)
+    effective, n_eff = core.gate_verdict_waves_device(up.wave, up.offsets, fo, hop, gate_fft, p_eff, p_all, b['mask'])      # the one wait of the gate
+    which = [i for i in range(len(xs)) if n_eff[i] > 0]
+    tracks, computed = {}, [None] * len(xs)
+    if which:
+        if tracker is None:
+            trk = model.track_uploaded(up, which, hop16, p.frame_period, threshold=encode.threshold)
+        else:
+            trk, comp = tracker.track_uploaded(up, which, [streams[i] for i in which], [xs[i] for i in which], hop16, p.frame_period,
+                                               threshold=encode.threshold, advances=[advances[i] for i in which])
+            for i, c in zip(which, comp):
+                computed[i] = c
+        if list(numpy.diff(trk.frame_offsets)) != [int(fo[i + 1] - fo[i]) for i in which]:
+            raise RuntimeError('the tracker returned %s frames, the frame-count rule says %s' % (list(numpy.diff(trk.frame_offsets)), list(numpy.diff(fo))))
+        analyzer.extract_spans_resident(trk.wave, trk.samples, trk.first_sample, trk.n_samples, trk.f0, trk.t, trk.frame_offsets,
+                                        [int(fo[i]) for i in which], b['mc32'], b['sp32'], b['ap32'])
+        tracks = dict(zip(which, trk.download()))
+    discard = (int(discard[0]), int(discard[1])) if os.environ.get('RY_DISCARD_HINT', '1') != '0' else (0, 0)
+    if core.discard != discard:
+        core.set_discard(*discard)
+    core.enqueue_waves_masked_device(fo, b['mc32'], b['mc_out'], b['sp_out'], b['mask'], effective, n_eff, SP_FLOOR)
+    # f0, wave by wave: the numpy operations of `Pipeline._resident_rows`; a skipped wave has combine_silent's float32 zeros
+    from yukarin.acoustic_feature import AcousticFeature
+    f0s = []
+    for i in range(len(xs)):
+        eff = effective[fo[i]:fo[i + 1]]
+        f0 = numpy.zeros((len(eff), 1), numpy.float32)
+        if i in tracks:
+            f0_eff = tracks[i][1][:, None].astype(p.dtype)[eff]
+            if ac.f0_converter is not None:
+                f0_eff = ac.f0_converter.convert(AcousticFeature(f0=f0_eff)).f0
+            f0[eff] = f0_eff
+        f0s.append(numpy.ascontiguousarray(f0.ravel(), dtype=numpy.float64))
+    record = dict(n_eff=[int(k) for k in n_eff], tracked=[i in tracks for i in range(len(xs))], n_computed=computed)
+    return ctx, b, fo, f0s, record
 
 
 _feature_class = None
@@ -73,8 +141,11 @@ class Pipeline(object):
     its own, the rows the caller keeps go to one synthesis stream.  `voice_changer`: the mirror `voice_changer.VoiceChanger` over the two converter
     shims; `acoustic_param`: the vocoder's (`Vocoder.acoustic_param`); `feature_class`: the class `Vocoder.encode` would call `extract` on."""
 
-    def __init__(self, voice_changer, acoustic_param, crepe_capacity='full', seed: Optional[int] = None, feature_class=None):
+    def __init__(self, voice_changer, acoustic_param, crepe_capacity='full', seed: Optional[int] = None, feature_class=None, gate_first: bool = False):
         self.voice_changer, self.acoustic_param = voice_changer, acoustic_param
+        self.gate_first = bool(gate_first)                                 # the silence gate in front of the encode stage (resident path only)
+        self.last_gate = None                                              # the record of the last gate_first call
+        self._gate_bank, self._pending = None, 0                           # gate_first with `advance`: a one-stream tracker bank; the advance of the skipped buffers
         self.crepe_capacity = crepe_capacity
         self.feature_class = crepe_feature_class() if feature_class is None else feature_class
         self.seed = int(os.environ.get('RY_SYNTH_SEED', '0')) if seed is None else int(seed)
@@ -124,10 +195,43 @@ class Pipeline(object):
         if self._crepe_stream is not None:
             self._crepe_stream.close()
             self._crepe_stream = None
+        if self._gate_bank is not None:
+            self._gate_bank.close()
+            self._gate_bank = None
 
-    def _reset_stream(self) -> None:
-        if self._crepe_stream is not None:
+    def _reset_stream(self, which=(True, True)) -> None:
+        """Forgets the kept rows: of the plain form's `CrepeStream` (which[0]) and of the gate_first form's tracker with its accumulated advance
+        (which[1]).  A call in one form resets the other: they keep different windows."""
+        if which[0] and self._crepe_stream is not None:
             self._crepe_stream.reset()
+        if which[1]:
+            self._pending = 0
+            if self._gate_bank is not None:
+                self._gate_bank.reset()
+
+    def _gate_tracker(self, model):
+        if self._gate_bank is None or self._gate_bank.model is not model:
+            if self._gate_bank is not None:
+                self._gate_bank.close()
+            self._gate_bank, self._pending = _crepe.CrepeStreamBank(model, 1), 0
+        return self._gate_bank
+
+    def _gate_first_row(self, wave, handles, discard, advance=None, live: bool = False):
+        """`_resident_rows` with the gate in front (`_gate_first_rows` on one wave)."""
+        calls.setdefault('gated', 0)
+        if live:
+            self._reset_stream((True, False))
+        if advance is None:
+            out = _gate_first_rows(handles, self.acoustic_param, self.voice_changer, [wave], discard, self._reserve)
+        else:
+            adv = _spanned(advance, self._pending)
+            out = _gate_first_rows(handles, self.acoustic_param, self.voice_changer, [wave], discard, self._reserve, self._gate_tracker(handles[0]), [0],
+                                   [adv])
+            self._pending = 0 if out[4]['tracked'][0] else _spanned(advance, self._pending)
+        ctx, b, fo, f0s, record = out
+        _gated(calls, 1 - sum(record['tracked']))
+        self.last_gate = record
+        return ctx, b, int(fo[-1]), f0s[0]
 
     # ---- which way a call goes
     def _encode_args(self):
@@ -212,15 +316,19 @@ class Pipeline(object):
         return self.voice_changer.convert_from_acoustic_feature(f, discard)
 
     # ---- calls
-    def convert_wave(self, wave):
-        """`yukarin.Wave` in (mono float32 at the input rate for the resident path) -> `yukarin.Wave` (float64) at the output rate."""
+    def convert_wave(self, wave, gate_first: Optional[bool] = None):
+        """`yukarin.Wave` in (mono float32 at the input rate for the resident path) -> `yukarin.Wave` (float64) at the output rate.  gate_first
+        (None: the constructor's): the gate before the encode stage; the composed path ignores it."""
         from yukarin import Wave
         handles = self._resident_handles(wave)
         if handles is None:
             calls['composed'] += 1
             return world_synth.decode(self._vocoder, self._composed_feature(wave, (0, 0)))
         calls['resident'] += 1
-        ctx, b, n, f0 = self._resident_rows(wave, handles, (0, 0))
+        if self.gate_first if gate_first is None else gate_first:
+            ctx, b, n, f0 = self._gate_first_row(wave, handles, (0, 0))
+        else:
+            ctx, b, n, f0 = self._resident_rows(wave, handles, (0, 0))
         ctx.mask_rows(b['ap32'], b['mask'], n, BINS)
         lib, h = self.synth._get()
         y = numpy.empty(max(self.synth.length(n), 1), numpy.float64)
@@ -229,7 +337,7 @@ class Pipeline(object):
                                        y.ctypes.data_as(world_synth._DP), y.size, ctypes.byref(got)))
         return Wave(y[:got.value], sampling_rate=self.voice_changer.output_sampling_rate)
 
-    def push(self, wave, discard=(0, 0), final: bool = False, advance: Optional[int] = None, out_gate=None):
+    def push(self, wave, discard=(0, 0), final: bool = False, advance: Optional[int] = None, out_gate=None, gate_first: Optional[bool] = None):
         """One buffer of a live stream: the wave is encoded and converted on its own (as `EncodeStream` / `ConvertStream` do per buffer), the rows
         [front, frames - back) -- what `ConvertStream.process` picks -- go to the synthesis stream, and the samples that are final come back.
         final=True: the stream ends with this buffer (`flush` follows).  advance (an int): sample i of this buffer is sample i + advance of the previous
@@ -238,7 +346,10 @@ class Pipeline(object):
         through the network.  The kept rows are dropped by `flush`, by final=True and by a buffer that takes the composed path.
         out_gate (an `output_gate.OutputGate`): the samples go through it -- the tail of the reference's decode worker -- and the returned `Wave` is
         the chunk it emits (scaled, in the gate's dtype), empty when no chunk was completed or the chunk is silent.  The samples take the host route
-        into the gate."""
+        into the gate.
+        gate_first (None: the constructor's): the silence gate runs before the encode stage and a buffer without an effective frame skips the
+        tracker and the analysis: the same samples.  Its tracker's kept rows stay, and its `advance` is added to that of the next buffer that is
+        tracked, which so spans the buffers skipped.  The composed path ignores the flag."""
         from yukarin import Wave
         front, back = int(discard[0]), int(discard[1])
         handles = self._resident_handles(wave)
@@ -253,7 +364,11 @@ class Pipeline(object):
                 out = world_synth.decode_realtime(self._vocoder, picked).wave
         else:
             calls['resident'] += 1
-            ctx, b, n, f0 = self._resident_rows(wave, handles, (front, back), advance)
+            if self.gate_first if gate_first is None else gate_first:
+                ctx, b, n, f0 = self._gate_first_row(wave, handles, (front, back), advance, live=True)
+            else:
+                self._reset_stream((False, True))
+                ctx, b, n, f0 = self._resident_rows(wave, handles, (front, back), advance)
             k0, k1 = front, n - back
             out = numpy.empty(0, numpy.float64)
             if k1 > k0:
@@ -294,7 +409,9 @@ class PipelineBank(object):
     all share one rate; otherwise every wave runs the chain of the separate calls, one after the other, over the same bank: the same bits
     (`calls_many` counts which way a call went)."""
 
-    def __init__(self, voice_changer, acoustic_param, n_streams: int, seeds=None, crepe_capacity='full', feature_class=None):
+    def __init__(self, voice_changer, acoustic_param, n_streams: int, seeds=None, crepe_capacity='full', feature_class=None, gate_first: bool = False):
+        self.gate_first = bool(gate_first)                                 # the silence gate in front of the encode stage (resident chain only)
+        self.last_gate = None                                              # the record of the last gate_first call
         self.n_streams = int(n_streams)
         if self.n_streams < 1:
             raise ValueError('a bank has at least one stream, got %d' % self.n_streams)
@@ -312,6 +429,7 @@ class PipelineBank(object):
         self._live = [False] * self.n_streams                              # the stream holds frames of a signal that has not ended
         self._blocks, self._cap, self._ctx, self._pid, self._table = {}, 0, None, None, None
         self._crepe_bank = None                                            # `push(..., advance=a)`: the trackers that keep rows between buffers
+        self._pending = [0] * self.n_streams                               # gate_first: the advance of the buffers of a stream skipped since its last tracked one
 
     # ---- the blocks this object owns: grown, never shrunk, freed by `close` in the process that made them
     def _reserve(self, ctx, n: int, m_in: int, m_out: int, f_out: int) -> dict:
@@ -356,9 +474,27 @@ class PipelineBank(object):
             self._crepe_bank = None
 
     def _reset_trackers(self, streams) -> None:
+        streams = list(streams)
+        for s in streams:
+            self._pending[s] = 0
         if self._crepe_bank is not None:
             for s in streams:
                 self._crepe_bank.reset(s)
+
+    def _gate_first_rows(self, waves, handles, discard, part=None, advance=None):
+        """`_resident_rows` with the gate in front of the encode stage (`_gate_first_rows` of the module)."""
+        calls_many.setdefault('gated', 0)
+        args = (handles, self.acoustic_param, self.voice_changer, waves, discard, self._reserve)
+        if advance is None:
+            ctx, b, fo, f0s, record = _gate_first_rows(*args)
+        else:
+            adv = [_spanned(a, self._pending[s]) for s, a in zip(part, advance)]
+            ctx, b, fo, f0s, record = _gate_first_rows(*args, self._trackers_of(handles[0]), part, adv)
+            for i, s in enumerate(part):
+                self._pending[s] = 0 if record['tracked'][i] else adv[i]
+        _gated(calls_many, len(waves) - sum(record['tracked']))
+        self.last_gate = dict(record, streams=list(part) if part is not None else None)
+        return ctx, b, fo, f0s
 
     # ---- which way a call goes
     def _handles(self, waves):
@@ -415,8 +551,9 @@ class PipelineBank(object):
         return ctx, b, fo, f0s
 
     # ---- calls
-    def convert_waves(self, waves) -> list:
-        """A list of `yukarin.Wave` -> the list of their converted waves, each with the bits of `Pipeline(seed=seeds[0]).convert_wave` on it alone."""
+    def convert_waves(self, waves, gate_first: Optional[bool] = None) -> list:
+        """A list of `yukarin.Wave` -> the list of their converted waves, each with the bits of `Pipeline(seed=seeds[0]).convert_wave` on it alone.
+        gate_first (None: the constructor's): the gate before the encode stage; the composed path ignores it."""
         from yukarin import Wave
         waves = list(waves)
         if not waves:
@@ -427,7 +564,8 @@ class PipelineBank(object):
             calls_many['composed'] += 1
             return [world_synth.decode(self._one._vocoder, self._one._composed_feature(w, (0, 0))) for w in waves]
         calls_many['resident'] += 1
-        ctx, b, fo, f0s = self._resident_rows(waves, handles, (0, 0))
+        rows = self._gate_first_rows if (self.gate_first if gate_first is None else gate_first) else self._resident_rows
+        ctx, b, fo, f0s = rows(waves, handles, (0, 0))
         n = int(fo[-1])
         ctx.mask_rows(b['ap32'], b['mask'], n, BINS)
         synth = self._one.synth
@@ -447,7 +585,7 @@ class PipelineBank(object):
             raise ValueError('final names stream %s of %d' % (final, self.n_streams))
         return final
 
-    def push(self, waves, discard=(0, 0), final=None, advance=None, out_gate=None) -> list:
+    def push(self, waves, discard=(0, 0), final=None, advance=None, out_gate=None, gate_first: Optional[bool] = None) -> list:
         """One buffer of every live stream: `waves` has one `yukarin.Wave` per stream, None for a stream that sits the call out; every wave is
         encoded and converted on its own, the rows [front, frames - back) of each go to its synthesis stream, and the samples that are final come
         back -> one `Wave` per stream (empty for a stream that sat out).  `final`: the streams whose signal ends with this call (what `Pipeline.push(
@@ -459,7 +597,11 @@ class PipelineBank(object):
         path.  advance=None: the call as it was, through `CrepeModel.track_many`.
         out_gate (an `output_gate.OutputGateBank` of n_streams streams): the samples of all streams go through it in ONE call and every returned
         `Wave` is the chunk its stream's gate emits, empty when no chunk was completed or the chunk is silent; a stream without a sample in this call
-        sits the gate's call out.  The samples take the host route into the gate."""
+        sits the gate's call out.  The samples take the host route into the gate.
+        gate_first (None: the constructor's): the silence gate runs before the encode stage, and the streams whose buffer has no effective frame
+        skip the tracker and the analysis -- no kernel of either runs when every buffer is silent -- while their synthesis streams, their gates
+        and every sample they return go on as before.  A skipped stream keeps its tracker's rows, and the `advance` of every buffer skipped is
+        added to that of its next tracked buffer.  The composed path ignores the flag."""
         from yukarin import Wave
         waves = list(waves)
         if len(waves) != self.n_streams:
@@ -498,7 +640,19 @@ class PipelineBank(object):
                         outs[s] = got[s]
             else:
                 calls_many['resident'] += 1
-                ctx, b, fo, f0s = self._resident_rows([waves[s] for s in part], handles, (front, back), part, advance)
+                per = advance
+                if advance is not None:                                    # per wave of the call: against the window the stream's tracker keeps
+                    per = [advance if isinstance(advance, (int, numpy.integer)) else advance[s] for s in part]
+                if self.gate_first if gate_first is None else gate_first:
+                    ctx, b, fo, f0s = self._gate_first_rows([waves[s] for s in part], handles, (front, back), part, per)
+                else:
+                    if advance is not None and any(self._pending[s] != 0 for s in part):      # buffers a gate_first call skipped lie in between
+                        advance = [None] * self.n_streams
+                        for s, a in zip(part, per):
+                            advance[s] = _spanned(a, self._pending[s])
+                    for s in part:
+                        self._pending[s] = 0
+                    ctx, b, fo, f0s = self._resident_rows([waves[s] for s in part], handles, (front, back), part, advance)
                 picks = [(int(fo[i]) + front, int(fo[i + 1]) - back) for i in range(len(part))]
                 picks = [(k0, max(k1, k0)) for k0, k1 in picks]
                 total = sum(k1 - k0 for k0, k1 in picks)

@@ -175,6 +175,26 @@ class Analyzer(DeviceHandle):
                                                             fo.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), so.size - 1, float(threshold),
                                                             _lib._fptr(int(mc32_dev)), _lib._fptr(int(sp32_dev)), _lib._fptr(int(ap32_dev))))
 
+    def extract_spans_resident(self, wave_dev: int, samples: int, first_sample, n_samples, f0_dev: int, t_dev: int, frame_offsets, row_offsets,
+                               mc32_dev: int, sp32_dev: int, ap32_dev: int, threshold: float = 0.85) -> None:
+        """`extract_many_resident` for waves that lie anywhere in an uploaded block of `samples` samples (`first_sample` / `n_samples` per wave) and
+        rows that go anywhere in the blocks (`row_offsets`: the first row of every wave; `frame_offsets`: waves + 1 entries, where its track starts)
+        -- what `CrepeModel.track_uploaded` left, into the frame layout of a call with more waves than were tracked
+        (`ry_analysis_extract_spans_resident`).  No other row of the blocks is written."""
+        lib, h = self._get()
+        fs = numpy.ascontiguousarray(first_sample, dtype=numpy.int64).ravel()
+        ns = numpy.ascontiguousarray(n_samples, dtype=numpy.int32).ravel()
+        fo = numpy.ascontiguousarray(frame_offsets, dtype=numpy.int32).ravel()
+        ro = numpy.ascontiguousarray(row_offsets, dtype=numpy.int32).ravel()
+        if not (fs.size == ns.size == ro.size == fo.size - 1 and fs.size >= 1):
+            raise ValueError('extract_spans_resident needs one first sample, count and row offset per wave and waves + 1 frame offsets')
+        as_d = lambda a: ctypes.cast(ctypes.c_void_p(a), _DP)
+        ip = ctypes.POINTER(ctypes.c_int)
+        lib.check(lib.dll.ry_analysis_extract_spans_resident(h, _lib._fptr(int(wave_dev)), int(samples), fs.ctypes.data_as(_LLP), ns.ctypes.data_as(ip),
+                                                             as_d(f0_dev), as_d(t_dev), fo.ctypes.data_as(ip), ro.ctypes.data_as(ip), fs.size,
+                                                             float(threshold), _lib._fptr(int(mc32_dev)), _lib._fptr(int(sp32_dev)),
+                                                             _lib._fptr(int(ap32_dev))))
+
     def d4c(self, x, f0, t, threshold: float = 0.85) -> numpy.ndarray:
         """`pyworld.d4c` of this analyzer's rate: -> aperiodicity [frames][513] float64."""
         return self.run(x, f0, t, want=('ap',), threshold=threshold)[0]
