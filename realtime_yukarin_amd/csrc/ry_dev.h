@@ -94,10 +94,19 @@ RY_DEV float ry_shfl_xor_c(float v) {
 }
 RY_DEV float ry_shfl(float v, int src) { return __shfl(v, src, 64); }
 // separately rounded float32 product / sum (never contracted into an fma) and the correctly rounded square root: the silence gate
-// has to reproduce numpy's float32 arithmetic bit for bit
-RY_DEV float ry_mul_rn(float a, float b) { return __fmul_rn(a, b); }
-RY_DEV float ry_add_rn(float a, float b) { return __fadd_rn(a, b); }
-RY_DEV float ry_sqrt_rn(float a) { return __fsqrt_rn(a); }
+// has to reproduce numpy's float32 arithmetic bit for bit.  Without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define __fmul_rn / __fadd_rn
+// as plain `*` / `+`, which the default -ffp-contract=fast-honor-pragmas fuses into v_fmac after inlining, and __fsqrt_rn as the NATIVE
+// square root (v_sqrt_f32 alone, 1 ulp): the threshold sweep of tests/gate_power_cases.py found both on the card.  So: contraction switched
+// off by pragma where the operation is written, and sqrtf, which hipcc expands to the correctly rounded, denormal-safe sequence.
+RY_DEV float ry_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+RY_DEV float ry_add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+RY_DEV float ry_sqrt_rn(float a) { return sqrtf(a); }
 RY_DEV int ry_lane() { return (int)(threadIdx.x & 63u); }
 
 typedef hipStream_t ry_stream_t;

@@ -83,10 +83,15 @@ RY_KERNEL(256) void ry_gather_rows(RyGatherRowsParams p) {
 //   ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), leaves combined in a binary tree.  One wave per frame: lane (leaf, j) walks its
 //   16 elements in order, then a butterfly over the lanes IS that tree (fp addition is commutative, the tree shape is what matters).
 //   fft_length = 128 .. 1024, a power of two.  Products and sums are rounded separately (no fma contraction), sqrt is correctly rounded.
+//   hop = 1 is the one exception to the order: both axes of the frame view then have the same stride, numpy lays `abs(x) ** 2` out row-major
+//   and `mean(axis=0)` adds the fft rows one after the other -- one running sum per frame, which is what the kernel does there
+//   (tests/gate_power_cases.py holds both orders to numpy).
 // ry_gate_compact: one workgroup: the gate in the POWER domain -- effective = mse >= p_eff, or every frame when max(mse) >= p_all
 //   (librosa.power_to_db's top_db clamp) -- with both thresholds derived on the host, once per threshold_db, by bisection over the
 //   float32 values through the host's own log10 (realtime_yukarin_amd/gate.py), then an ordered compaction: row_of, the feature rows
-//   of the effective frames, the mask and the count.
+//   of the effective frames, the mask and the count.  A NaN power in any of the wave's frames (a NaN sample) leaves NO frame effective:
+//   on the host the NaN is log_spec.max(), the clamp makes every entry NaN and every comparison false.  An infinite power is an
+//   ordinary maximum (every frame effective).
 // ---------------------------------------------------------------------------------------------
 struct RyFramePowerParams { const float* wave; int n, hop, fft, n_wave_frames; float* power; };
 
@@ -102,6 +107,15 @@ RY_DEV int ry_reflect_index(int i, int n) {                     // numpy.pad(mod
 RY_DEV float ry_frame_power_of(const float* wave, int n, int hop, int fft, int frame, int lane) {
     const int L = fft >> 4;                                     // active lanes: 8 per 128-element leaf
     float r = 0.f;
+    if (hop == 1) {                                             // wave-uniform: one running sum, the same in every lane (see above)
+        const int base = frame - (fft >> 1);
+        for (int k = 0; k < fft; ++k) {
+            const float v = wave[ry_reflect_index(base + k, n)];
+            r = k == 0 ? ry_mul_rn(v, v) : ry_add_rn(r, ry_mul_rn(v, v));
+        }
+        const float rms1 = ry_sqrt_rn(r / (float)fft);
+        return ry_mul_rn(rms1, rms1);
+    }
     if (lane < L) {
         const int base = frame * hop - (fft >> 1) + 128 * (lane >> 3) + (lane & 7);
         float v[16];
@@ -152,22 +166,26 @@ struct RyGateParams {
     float* x_eff; int* row_of; int* count; unsigned char* mask;
 };
 
+// the maximum that keeps a NaN (fmaxf drops it): the NaN of any power reaches slot 0 through the same reduction as the maximum
+RY_DEV float ry_max_nan(float a, float b) { return a != a ? a : (b != b ? b : fmaxf(a, b)); }
+
 RY_DEV void ry_gate_compact_body(const RyGateParams& p) {
     __shared__ float fmx[1024];
     __shared__ int scan[1024];
     __shared__ int s_base;
     const int tid = (int)threadIdx.x;
     float m = 0.f;
-    for (int t = tid; t < p.n_wave_frames; t += 1024) m = fmaxf(m, p.power[t]);
+    for (int t = tid; t < p.n_wave_frames; t += 1024) m = ry_max_nan(m, p.power[t]);
     fmx[tid] = m;
     __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) { if (tid < s) fmx[tid] = fmaxf(fmx[tid], fmx[tid + s]); __syncthreads(); }
-    const bool all = fmx[0] >= p.p_all;
+    for (int s = 512; s > 0; s >>= 1) { if (tid < s) fmx[tid] = ry_max_nan(fmx[tid], fmx[tid + s]); __syncthreads(); }
+    const bool none = fmx[0] != fmx[0];                        // a NaN power anywhere in the wave: the host's clamp makes every entry NaN
+    const bool all = !none && fmx[0] >= p.p_all;
     if (tid == 0) s_base = 0;
     __syncthreads();
     for (int t0 = 0; t0 < p.n_frames; t0 += 1024) {
         const int t = t0 + tid;
-        const bool eff = t < p.n_frames && t < p.n_wave_frames && (all || p.power[t] >= p.p_eff);
+        const bool eff = t < p.n_frames && t < p.n_wave_frames && !none && (all || p.power[t] >= p.p_eff);
         scan[tid] = eff ? 1 : 0;
         __syncthreads();
         for (int d = 1; d < 1024; d <<= 1) {                    // inclusive Hillis-Steele scan

@@ -19,10 +19,14 @@ def waves():
     w[200 * HOP:230 * HOP] = 0.0
     ramp = (numpy.geomspace(1e-6, 0.5, 120 * HOP) * rng.normal(size=120 * HOP)).astype(numpy.float32)
     w60 = w[:60 * HOP].copy(); w60[10 * HOP:25 * HOP] *= 1e-4; w60[40 * HOP:50 * HOP] = 0.0
+    w_nan, w_inf = w60.copy(), w60.copy()
+    w_nan[30 * HOP + 7] = numpy.nan                     # the NaN is log_spec.max() on the host: the clamp makes every entry NaN, no frame is effective
+    w_inf[30 * HOP + 7] = numpy.inf                     # an infinite maximum: the clamp lifts every frame
     return {'speechlike': w, 'ramp': ramp, 'speech60': w60, 'ramp40': ramp[::3].copy(), 'short': w[:300].copy(), 'tiny': w[:37].copy(), 'one_hop': w[:55].copy(),
             'ragged': w[:1234].copy(), 'all_silent': numpy.zeros(50 * HOP, numpy.float32),
             'all_loud': (0.5 * numpy.sign(rng.normal(size=50 * HOP))).astype(numpy.float32),
-            'loud_clamp': (30.0 * rng.normal(size=40 * HOP)).astype(numpy.float32)}          # max power > 20 dB: top_db clamp territory
+            'loud_clamp': (30.0 * rng.normal(size=40 * HOP)).astype(numpy.float32),          # max power > 20 dB: top_db clamp territory
+            'nan_sample': w_nan, 'inf_sample': w_inf}
 
 
 def make_core(ctx, name, sp_fftlen=256):
@@ -47,7 +51,10 @@ def run_all(ctx, name, fft_lengths=(1024, 256), thrs=(60, 80, 100, 20), deltas=(
                     if n < 1:
                         continue
                     feat = (rng.normal(size=(n, 9)) * synth.MC_SCALE).astype(numpy.float32)
-                    want = oef.separate_effective_mask(w, FS, n, thr, fft, FP, 'abs')
+                    with numpy.errstate(invalid='ignore'):
+                        want = oef.separate_effective_mask(w, FS, n, thr, fft, FP, 'abs')
+                    assert wname != 'nan_sample' or not want.any()
+                    assert wname != 'inf_sample' or want[:len(w) // HOP + 1].all()
                     p_eff, p_all = gate.thresholds(thr)
                     eff, x_eff, rows = core.gate(w, HOP, fft, p_eff, p_all, feat)            # the gate alone: mask, gathered rows, their indices
                     assert numpy.array_equal(eff, want), (wname, fft, thr, delta, numpy.nonzero(eff != want)[0][:8])
@@ -75,7 +82,7 @@ def test_thresholds_reproduce_the_host_gate_at_the_boundary():
 
 def test_device_gate_masks_are_bit_equal_emu(emu_ctx):
     # (the emulator runs a 1024-fiber workgroup per window: a subset here, the full cross product on the GPU)
-    assert run_all(emu_ctx, 'SYN-8', only=('speech60', 'short', 'one_hop', 'ragged', 'all_silent', 'loud_clamp'),
+    assert run_all(emu_ctx, 'SYN-8', only=('speech60', 'short', 'one_hop', 'ragged', 'all_silent', 'loud_clamp', 'nan_sample', 'inf_sample'),
                    chain=False) >= 130
     assert run_all(emu_ctx, 'SYN-8', fft_lengths=(1024,), thrs=(60,), deltas=(0,), only=('speech60', 'tiny', 'all_silent')) == 3
 
