@@ -556,6 +556,33 @@ int ry_crepe_bank_debug_assemble(ry_crepe_bank* bank, const int* n_frames, int n
  * first layer pads for itself.  Adds nothing to the forward / convert path: the handle only remembers which plan ran. */
 int ry_net_debug_activation(ry_net* net, int layer, int kind, void* out, size_t out_bytes, int* dims);
 
+/* tests: what the stage-2 planner decided for one layer of a (batch, frames) launch plan, and the rows one enqueue of it computes.  Zeros where a
+ * field does not apply to the layer's path. */
+typedef struct ry_plan_record {
+    int layer;                  /* 0 .. 15 */
+    int path;                   /* 1 implicit GEMM, 2 direct, 3 first layer, 4 fused end layer, 5 16-bit implicit GEMM, 7 output-stationary, 8 Winograd */
+    int tile;                   /* implicit GEMM: 1 128x128, 3 64x128, 4 32x128, 5 128x64, 6 96x128 */
+    int splits, kgroups;        /* external split-K, K groups per workgroup */
+    int wino_cfg, wino_mbw;     /* Winograd: workgroup shape (1: 2 x 2 waves, 2: 4 x 2), M-blocks per tile row */
+    int os2[4];                 /* output-stationary: mt4, nt4, waves, depth */
+    int reads16;                /* sources: 0 fp32, 1 the producers' bf16 copies, 2 their split-bf16 copies */
+    int writes32, writes16;     /* copies of the output: fp32 (0 / 1); 16-bit (0 none, 1 bf16, 2 split-bf16) */
+    int patch;                  /* implicit GEMM: input-patch variant of the kernel (0 none, 1 deconvolution, 2 k4 s2 p1 convolution) */
+    int reduce;                 /* node behind an external split: 0 none, 1 ry_splitk_reduce, 2 ry_splitk_reduce_wide */
+    int last_exp;               /* fused end layer: exp / edge bin / crop of the convert wrapper */
+    int rows_out;               /* output rows of the layer (per window) */
+    int grid_rows, grid_cols;   /* rows and columns of the whole pixel grid the launch tiles (a deconvolution: its input pixels) */
+    int tile_rows, tile_cols;   /* 2-D pixel tile of the launch; 0: raster tiles or no GEMM grid */
+    int out_lo, out_n;          /* output rows [out_lo, out_lo + out_n) the launch computes (the dead-row crop; the end layer: the kept frames) */
+    int crop_lo, crop_n;        /* the same as grid rows; crop_n = 0: the launch runs whole */
+    int hole_lo, hole_n;        /* output rows the launch leaves out and ry_rep_rows copies from row hole_lo - 1; hole_n = 0: none */
+} ry_plan_record;
+/* tests (the planner's counterpart of ry_net_debug_activation): the launch plan of (batch, frames) of a stage-2 predictor, built if it does not
+ * exist yet, one record per layer; nothing is enqueued and nothing is added to the forward / convert path.  window = 1: the convert wrapper on
+ * `frames` real frames per window, for a caller that throws away discard_front / discard_back of them (ry_sr_convert_rows); window = 0: the raw
+ * forward at `frames` padded rows (the discards must be 0).  *n = records written (16); RY_EINVAL when max is smaller. */
+int ry_net_debug_plan(ry_net* net, int batch, int frames, int window, int discard_front, int discard_back, ry_plan_record* records, int max, int* n);
+
 /* ---- WORLD synthesizer (`pyworld.synthesize(f0, sp, ap, fs, frame_period)` in the reference's Vocoder.decode and world4py's realtime
  * synthesizer in RealtimeVocoder.decode, yukarin_wrapper/vocoder.py:50-120).  Semantics: INTEGRATION.md section 10 and
  * tests/world_synth_ref.py (WORLD's Synthesis restated; counter-based noise of `seed`, phase wrapped at every step).

@@ -53,7 +53,7 @@ ABI_SYMBOLS = (
     'ry_init', 'ry_shutdown', 'ry_sync', 'ry_stream', 'ry_device_count', 'ry_last_error',
     'ry_net_param_count', 'ry_net_create', 'ry_net_destroy', 'ry_net_clone', 'ry_net_set_dtype', 'ry_net_forward',
     'ry_ac_convert', 'ry_sr_convert', 'ry_sr_convert_rows', 'ry_conv1d', 'ry_conv1d_os', 'ry_conv2d', 'ry_conv2d_dilated',
-    'ry_timer_start', 'ry_timer_stop', 'ry_net_profile', 'ry_net_profile_window', 'ry_net_debug_activation', 'ry_debug_plan_igemm', 'ry_debug_reload_env', 'ry_debug_stream_overlap', 'ry_debug_plan_igemm_bf16', 'ry_debug_plan_os2', 'ry_debug_plan_wino',
+    'ry_timer_start', 'ry_timer_stop', 'ry_net_profile', 'ry_net_profile_window', 'ry_net_debug_activation', 'ry_net_debug_plan', 'ry_debug_plan_igemm', 'ry_debug_reload_env', 'ry_debug_stream_overlap', 'ry_debug_plan_igemm_bf16', 'ry_debug_plan_os2', 'ry_debug_plan_wino',
     'ry_vc_create', 'ry_vc_destroy', 'ry_vc_convert', 'ry_mc2sp',
     'ry_vc_submit', 'ry_vc_set_lanes', 'ry_vc_set_discard', 'ry_vc_wait', 'ry_vc_enqueue_device', 'ry_vc_enqueue_device_batch', 'ry_vc_stage1', 'ry_vc_stage2_from_mc', 'ry_vc_mid_sp', 'ry_vc_reserve_frames',
     'ry_vc_submit_wave', 'ry_vc_wait_wave', 'ry_vc_gate', 'ry_vc_debug_streams',
@@ -93,6 +93,13 @@ class RyNetDesc(ctypes.Structure):
 class RyKernelStat(ctypes.Structure):
     _fields_ = [('name', ctypes.c_char * 48), ('layer', ctypes.c_char * 24), ('ms', ctypes.c_float),
                 ('flops', ctypes.c_double), ('bytes', ctypes.c_double), ('grid', ctypes.c_int * 3), ('flops_exec', ctypes.c_double)]
+
+
+class RyPlanRecord(ctypes.Structure):
+    """ry_plan_record (include/ry355.h): all ints, in the header's order"""
+    FIELDS = ('layer', 'path', 'tile', 'splits', 'kgroups', 'wino_cfg', 'wino_mbw', 'os2', 'reads16', 'writes32', 'writes16', 'patch', 'reduce', 'last_exp',
+              'rows_out', 'grid_rows', 'grid_cols', 'tile_rows', 'tile_cols', 'out_lo', 'out_n', 'crop_lo', 'crop_n', 'hole_lo', 'hole_n')
+    _fields_ = [(f, ctypes.c_int * 4 if f == 'os2' else ctypes.c_int) for f in FIELDS]
 
 
 class Ry355Error(RuntimeError):
@@ -308,6 +315,7 @@ class Ry355Lib(object):
         d.ry_analysis_debug_d4c.argtypes = [_VP, ctypes.POINTER(_LL), _DP, _CI, _IP]
         d.ry_net_profile_window.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RyKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         d.ry_net_debug_activation.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+        d.ry_net_debug_plan.argtypes = [_VP] + [ctypes.c_int] * 5 + [ctypes.POINTER(RyPlanRecord), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
 
     def check(self, rc):
         if rc != 0:

@@ -107,7 +107,7 @@ static int launch_reduce(Launcher& Lc, const Layer& l, const LayerPlan& lp, int 
     // one window: only the rows this launch wrote (a prefix when cropped)
     r.total = B == 1 ? (long long)Ho_run * lp.Wo * l.cout : slab_stride; r.N = l.cout;
     r.act = l.act; r.slope = slope;
-    if (lp.splits >= 16 && r.total <= (1 << 20)) {      // many slabs, few outputs
+    if (plan_reduce_wide(lp.splits, r.total)) {         // many slabs, few outputs
         dim3 rg((unsigned)((r.total / 4 + 63) / 64));
         RY_TRY(Lc.begin("ry_splitk_reduce_wide", l.name, 0, (double)r.total * 4 * (lp.splits + 1), rg));
         RY_LAUNCH(ry_splitk_reduce_wide, rg, 256, Lc.stream, r);
@@ -227,14 +227,7 @@ static int launch_igemm(Launcher& Lc, const Layer& l, const LayerPlan& lp, int B
     if (!plan_tile_rows(lp, g.Mh, g.Mw, &th, &tw)) tw = 0;
     const int M = B * g.Mh * g.Mw;
     const int ck = bf16 ? 64 : 32, cpt = (C1 + C2) / ck, nkc = g.ntaps * cpt;
-    // patch variants of the kernel on 16-pixel-wide 2-D tiles (K units = whole channel chunks): 1: sub-pixel deconvolution, one patch per channel
-    // chunk; 2: k4 s2 p1 convolution, one patch per (chunk, input parity).  Small layers: the longer set-up costs more than the reuse saves
-    // (measured at M = 192).
-    int patch = 0;
-    if (tw == 16 && (M >= 512 || lp.any_m_patch)) {
-        if (g.ostride == 2 && lp.splits * lp.kg <= cpt) patch = 1;
-        else if (!l.deconv && l.k == 4 && l.stride == 2 && l.pad == 1 && l.dil == 1 && lp.splits * lp.kg <= 4 * cpt) patch = 2;
-    }
+    const int patch = plan_igemm_patch(l, lp, M, tw, cpt);     // input-patch variant of the kernel (ry_plan.h)
     const int units = patch == 1 ? cpt : patch == 2 ? 4 * cpt : nkc;
     RY_TRY(fill_sched(p.s, l, lp, g, B, bm, tw, l.cout / bn, units, (double)g.nphases * l.cout * g.ntaps * (C1 + C2)));
     // prologue helpers of the kernel (ry_fdiv reciprocals)

@@ -296,6 +296,64 @@ int ry_net_debug_activation(ry_net* net, int layer, int kind, void* out, size_t 
     return RY_OK;
 }
 
+// tests: the records of a (batch, frames) plan -- LayerPlan as build_plan left it, with the rows plan_window_rows gives one enqueue and what the
+// launchers derive from both (tile shape, patch variant, reduce kernel: the same functions they call).  Reads; enqueues nothing.
+int ry_net_debug_plan(ry_net* net, int batch, int frames, int window, int discard_front, int discard_back, ry_plan_record* records, int max, int* n) {
+    if (!net || !records || !n) return fail(RY_EINVAL, "null argument");
+    *n = 0;
+    if (net->desc.ndim != 2) return fail(RY_EINVAL, "plan records are handed back for the stage-2 predictor only");
+    if (window != 0 && window != 1) return fail(RY_EINVAL, "window must be 0 (raw forward) or 1 (convert wrapper); got %d", window);
+    if (frames < 1 || batch < 1) return fail(RY_EINVAL, "batch and frames must be positive (got %d, %d)", batch, frames);
+    if (discard_front < 0 || discard_back < 0 || (!window && (discard_front || discard_back)))
+        return fail(RY_EINVAL, "discarded frame counts must not be negative, and the raw forward has none (got %d, %d)", discard_front, discard_back);
+    if (max < 16) return fail(RY_EINVAL, "room for %d records, a plan has 16", max);
+    RT_TRY(rt::set_device(net->ctx->device));
+    Plan* P = nullptr;
+    if (window) RY_TRY(get_plan(net, batch, frames + (128 - frames % 128), 1, frames, &P));
+    else RY_TRY(get_plan(net, batch, frames, 0, 0, &P));
+    const int df = P->disc_front, db = P->disc_back;
+    P->disc_front = discard_front; P->disc_back = discard_back;
+    const WindowRows rows = plan_window_rows(net, *P);
+    P->disc_front = df; P->disc_back = db;
+    for (int i = 0; i < 16; ++i) {
+        const Layer& l = net->layers[i];
+        LayerPlan lq = P->lp[i];                                  // as enqueue_forward hands it to the launcher
+        if (rows.hole_n[i] > 0) { lq.hole_lo = rows.hole_lo[i]; lq.hole_n = rows.hole_n[i]; }
+        if (rows.crop_hi[i] > 0) { lq.crop_hi = rows.crop_hi[i]; lq.crop_lo = rows.crop_lo[i]; }
+        ry_plan_record& r = records[i];
+        memset(&r, 0, sizeof r);
+        r.layer = i; r.path = lq.path; r.splits = lq.splits;
+        const bool igemm = lq.path == PATH_IGEMM || lq.path == PATH_IGEMM_BF16, gemm = igemm || lq.path == PATH_WINO;
+        if (igemm) { r.tile = lq.tile; r.kgroups = lq.kg; }
+        if (lq.path == PATH_WINO) { r.wino_cfg = lq.wino_cfg; r.wino_mbw = lq.wino_mbw; }
+        if (lq.path == PATH_OS2D) { r.os2[0] = lq.os2_mt4; r.os2[1] = lq.os2_nt4; r.os2[2] = lq.os2_waves; r.os2[3] = lq.os2_depth; }
+        r.reads16 = lq.path == PATH_IGEMM_BF16 ? (lq.x3 ? 2 : 1) : 0;
+        r.writes32 = lq.w32 ? 1 : 0; r.writes16 = lq.w16 ? (lq.o16x3 ? 2 : 1) : 0;
+        r.rows_out = lq.Ho;
+        r.out_n = lq.Ho;
+        if (lq.path == PATH_LAST) {
+            r.last_exp = lq.last_exp;
+            if (P->mode == 1) { r.out_lo = rows.k0; r.out_n = rows.k1 - rows.k0; }
+        }
+        if (gemm || lq.path == PATH_OS2D || lq.path == PATH_DIRECT) { r.grid_rows = l.deconv ? lq.Hi : lq.Ho; r.grid_cols = l.deconv ? lq.Wi : lq.Wo; }
+        if (gemm) {
+            const int up = l.deconv ? 2 : 1;
+            int Mh = r.grid_rows;
+            if (lq.crop_hi > 0) { Mh = lq.crop_hi; r.crop_lo = lq.crop_lo; r.crop_n = lq.crop_hi; r.out_lo = up * lq.crop_lo; r.out_n = up * lq.crop_hi; }
+            r.hole_lo = lq.hole_lo; r.hole_n = lq.hole_n;
+            int th = 0, tw = 0;
+            if (plan_tile_rows(lq, Mh, r.grid_cols, &th, &tw)) { r.tile_rows = th; r.tile_cols = tw; } else tw = 0;
+            if (igemm) r.patch = plan_igemm_patch(l, lq, batch * Mh * r.grid_cols, tw, l.cin() / (lq.path == PATH_IGEMM_BF16 ? 64 : 32) * (lq.x3 ? 3 : 1));
+            if (lq.splits > 1) {
+                const long long total = batch == 1 ? (long long)up * Mh * lq.Wo * l.cout : (long long)batch * lq.Ho * lq.Wo * l.cout;
+                r.reduce = plan_reduce_wide(lq.splits, total) ? 2 : 1;
+            }
+        }
+    }
+    *n = 16;
+    return RY_OK;
+}
+
 // diagnostics / tests: read the process-wide RY_* switches again (they are otherwise read when a context is created; launch plans built before keep
 // their choices until ry_net_set_dtype drops them)
 int ry_debug_reload_env(void) { return read_env_switches(); }

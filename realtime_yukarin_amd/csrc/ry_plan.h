@@ -88,6 +88,18 @@ bool plan_tile_rows(const LayerPlan& lp, int Mh, int Mw, int* th, int* tw_out = 
 bool plan_hole_ok(const Layer& l, const LayerPlan& lp, int lo, int n);
 int plan_s2_layer(ry_ctx* ctx, Arena& arena, const Layer& l, LayerPlan& lp, int B, int dtype, const LayerForce& f, bool src16, bool out_layer, int mode);
 WindowRows plan_window_rows(const ry_net* net, const Plan& P);
+// What the launchers derive from a layer's plan at enqueue time, in one place for them and for ry_net_debug_plan:
+// the reduce kernel behind an external split of `total` output floats (many slabs, few outputs: ry_splitk_reduce_wide) ...
+inline bool plan_reduce_wide(int splits, long long total) { return splits >= 16 && total <= (1 << 20); }
+// ... and the input-patch variant of the implicit GEMM on 16-pixel-wide 2-D tiles (K units = whole channel chunks): 1: sub-pixel deconvolution, one patch
+// per channel chunk; 2: k4 s2 p1 convolution, one patch per (chunk, input parity); 0: none.  Small layers: the longer set-up costs more than the reuse
+// saves (measured at M = 192).  M: GEMM rows of the launch, tw: tile width (0: raster tiles), cpt: channel chunks per tap.
+inline int plan_igemm_patch(const Layer& l, const LayerPlan& lp, int M, int tw, int cpt) {
+    if (tw != 16 || !(M >= 512 || lp.any_m_patch)) return 0;
+    if (l.deconv && lp.splits * lp.kg <= cpt) return 1;
+    if (!l.deconv && l.k == 4 && l.stride == 2 && l.pad == 1 && l.dil == 1 && lp.splits * lp.kg <= 4 * cpt) return 2;
+    return 0;
+}
 // Does the first stage-1 layer of this enqueue pad the caller's block itself (no ry_pad_min_rows node, Plan::x_in stays unwritten)?  The fused pad
 // takes the column minimum inside the workgroups that reach the padding: one chain of n_frames / 8 load rounds, worth it while the window is
 // short (measured: 300 frames -3 us, 1000 frames +14 us against the separate node; the cooperative minimum: one round of loads per 1024 frames)

@@ -595,6 +595,16 @@ class Net(object):
             return out[..., 0]
         return out.reshape(B, H, W, 2, C // 2) if fmt == 2 else out
 
+    def debug_plan(self, batch: int, frames: int, window: bool = False, discard=(0, 0)) -> List[dict]:
+        """Tests: the stage-2 launch plan of (batch, frames), one dict per layer with the fields of `ry_plan_record` (`ry_net_debug_plan`): built if it
+        does not exist yet, nothing is enqueued.  window=True: the convert wrapper on `frames` real frames (discard as in `convert`); False: the raw
+        forward at `frames` padded rows."""
+        recs = (_lib.RyPlanRecord * 16)()
+        n = ctypes.c_int()
+        self.ctx.lib.check(self.ctx.lib.dll.ry_net_debug_plan(self.handle, int(batch), int(frames), int(bool(window)), int(discard[0]), int(discard[1]),
+                                                             recs, 16, ctypes.byref(n)))
+        return [{f: (tuple(getattr(recs[i], f)) if f == 'os2' else int(getattr(recs[i], f))) for f in _lib.RyPlanRecord.FIELDS} for i in range(n.value)]
+
     def profile(self, batch: int, frames: int, reps: int = 5, window: bool = False) -> List[dict]:
         """Per-launch timings of the raw forward at `frames` padded rows, or (window=True) of the convert wrapper on one window
         of `frames` real frames -- what the window call runs."""

@@ -825,17 +825,41 @@ def s2_reads_16bit(prof):
     return {q['layer'] for q in prof if q['name'].startswith('ry_igemm_ldsdma<') and q['name'][:-1].split(',')[5] == 'true'}
 
 
-def s2_walk(net, desc, P, n_frames, y, discard=(0, 0), prof=(), refs=True, cache=None, out=None, what=''):
+def s2_band_reference(spec, srcs_rows, W, bb, bn, a, b, Hi):
+    """The float64 reference of output rows [a, b) of one layer alone, from the source rows their stencil reads and nothing else.
+    srcs_rows(lo, hi) -> the float64 sources' rows [lo, hi) (B, hi - lo, W, C each); Hi = the sources' rows.  The row axis is laid out by hand (rows outside
+    the image are zeros, as the operator's padding has them) and the operator runs with no row padding of its own.  -> (r, bound), (B, b - a, Wo, Cout)"""
+    if spec['tr']:          # k4 s2 p1 transposed: input row i feeds output rows 2 i - 1 + k'; with no row padding the slice's local row j is output row j + 2 ia - 1
+        ia, ib = s2_rows_read(spec, a, b, Hi)
+        xs = numpy.concatenate(srcs_rows(ia, ib), axis=3)
+        r, bound = ref_conv2d_f64(xs, W, bb, bn, spec['s'], (0, spec['p']), True, spec['act'])
+        off = 2 * ia - 1
+        return r[:, a - off:b - off], bound[:, a - off:b - off]
+    lo, hi = a * spec['s'] - spec['p'], (b - 1) * spec['s'] - spec['p'] + spec['k']          # unclamped: output row a starts at source row lo
+    ia, ib = max(lo, 0), min(hi, Hi)
+    xs = numpy.concatenate(srcs_rows(ia, ib), axis=3)
+    xs = numpy.pad(xs, [(0, 0), (ia - lo, hi - ib), (0, 0), (0, 0)])
+    r, bound = ref_conv2d_f64(xs, W, bb, bn, spec['s'], (0, spec['p']), False, spec['act'])
+    assert r.shape[1] == b - a, (spec['name'], r.shape, a, b)
+    return r, bound
+
+
+def s2_walk(net, desc, P, n_frames, y, discard=(0, 0), prof=(), refs=True, cache=None, out=None, what='', layers=None, bands=None, x_in=None):
     """After y = net.convert(sp, discard) on a fresh, poisoned plan: every layer of the graph against float64 on the device's own sources.
     refs: True = every layer; False = finiteness of the needed rows only (the caller checks the last layer).  cache: {layer: (sources, r, bound)} of an
     earlier run of the same window and mode -- its reference is taken over for a layer whose sources are bit-equal on every row the needed rows read.
+    layers: the layer indices held to float64 (None: all of them); every other layer gets what refs=False gives every layer.
+    bands: {layer: [(a, b), ...]} -- that layer is held to float64 on these output row ranges only (clipped to its needed rows), each against a reference
+    of the band alone (s2_band_reference); the finiteness / NaN-row rule still covers every row.
+    x_in: the padded block of a raw forward (net.forward(x_in) ran, n_frames = its rows): the plan has no padded input of its own.
     -> dict(layers=[per-layer report], need, bufs={layer: value array}, fused)"""
     specs = s2_layers(desc)
     B = y.shape[0]
     k0 = discard[0] if discard[0] < n_frames else 0
     k1 = n_frames - discard[1] if n_frames - discard[1] > k0 else n_frames
     reads16 = s2_reads_16bit(prof)
-    x_in = s2_fetch(net, -1, 0)
+    if x_in is None:
+        x_in = s2_fetch(net, -1, 0)
     assert x_in is not None
     T = x_in.shape[1]
     raw = {}
@@ -854,23 +878,24 @@ def s2_walk(net, desc, P, n_frames, y, discard=(0, 0), prof=(), refs=True, cache
         o32, o16 = raw[i]
         a, b = need[i]
         is16 = spec['name'] in reads16
-        srcs, fmts = [], []
+        held, fmts = [], []                                       # the sources as the device holds them: (block, is it a 16-bit copy)
         for sidx in spec['src']:
             if sidx is None:
                 continue
             if sidx < 0:
-                srcs.append(x_in[..., None].astype(numpy.float64)); fmts.append('f32'); continue
+                held.append((x_in[..., None], False)); fmts.append('f32'); continue
             s32, s16 = raw[sidx]
             if is16:
                 assert s16 is not None, (what, spec['name'], 'reads a 16-bit copy that layer %d does not write' % sidx)
-                srcs.append(s2_value16(s16)); fmts.append('x3' if s16.ndim == 5 else 'bf16')
+                held.append((s16, True)); fmts.append('x3' if s16.ndim == 5 else 'bf16')
             else:
                 assert s32 is not None, (what, spec['name'], 'reads an fp32 copy that layer %d does not write' % sidx)
-                srcs.append(s32.astype(numpy.float64)); fmts.append('f32')
+                held.append((s32, False)); fmts.append('f32')
         assert len(set(fmts)) == 1, (what, spec['name'], fmts)
+        srcs_rows = lambda lo, hi, held=held: [s2_value16(u[:, lo:hi]) if h16 else u[:, lo:hi].astype(numpy.float64) for u, h16 in held]
         fmt = fmts[0]
         tol = dict(f32=F32_TOL, bf16=BF16_TOL, x3=X3_TOL)[fmt]
-        q = dict(layer=spec['name'], fmt=fmt, need=(a, b), worst=None, worst16=None, nan32=None, nan16=None, reused=False)
+        q = dict(layer=spec['name'], fmt=fmt, need=(a, b), worst=None, worst16=None, nan32=None, nan16=None, reused=False, held=False, banded=None)
         if i == 15 and fused:
             rep.append(q)
             continue
@@ -891,35 +916,54 @@ def s2_walk(net, desc, P, n_frames, y, discard=(0, 0), prof=(), refs=True, cache
             bad = (want != o16) & okk
             assert not bad.any(), (what, spec['name'], '%d elements of the 16-bit copy are not the rounding of the fp32 copy' % int(bad.sum()))
             assert numpy.isnan(s2_value16(o16))[~ok].all(), (what, spec['name'], 'the 16-bit copy holds values where the fp32 copy is NaN')
-        if not refs:
+        if not refs or (layers is not None and i not in layers):
             rep.append(q)
             continue
-        Hi = srcs[0].shape[1]
+        q['held'] = True
+        Hi = held[0][0].shape[1]
+
+        def compare(a_, b_, rr, bd):
+            """rows [a_, b_) of this layer's output against their reference -> (worst, worst16)"""
+            assert numpy.isfinite(rr).all(), (what, spec['name'], 'the reference of a needed row read a NaN source row')
+            if o32 is not None:
+                return assert_close_elementwise(o32[:, a_:b_], rr, bd, tol, '%s %s fp32 rows %d..%d' % (what, spec['name'], a_, b_ - 1)), None
+            v = s2_value16(o16[:, a_:b_])
+            if o16.ndim == 5:      # hi + lo rebuilds the fp32 value to 2^-17 of it (lo = bf16(v - hi), |v - hi| <= 2^-9 |v|, rounded to 8 bits again)
+                return None, assert_close_elementwise(v, rr, bd + (2.0 ** -17 / tol) * numpy.abs(rr), tol, '%s %s split copy' % (what, spec['name']))
+            # rounding is monotone: the stored bf16 lies between the roundings of the two ends of the fp32 value's interval
+            lo_, hi_ = bf16_round((rr - tol * bd).astype(numpy.float32)), bf16_round((rr + tol * bd).astype(numpy.float32))
+            lo_ = numpy.minimum(lo_, bf16_round(numpy.nextafter((rr - tol * bd).astype(numpy.float32), numpy.float32(-numpy.inf))))   # (float64 -> float32 may round inwards)
+            hi_ = numpy.maximum(hi_, bf16_round(numpy.nextafter((rr + tol * bd).astype(numpy.float32), numpy.float32(numpy.inf))))
+            bad = ~((v >= lo_) & (v <= hi_))
+            assert not bad.any(), ('%s %s bf16 copy: %d elements outside bf16([r - tol bound, r + tol bound])' % (what, spec['name'], int(bad.sum())))
+            return None, float((numpy.abs(v - rr) / numpy.maximum(bd, 1e-300)).max())
+
+        W, bb, bn = s2_layer_params(P, spec, fmt == 'bf16')
+        if bands is not None and i in bands:
+            q['banded'] = []
+            for a_, b_ in bands[i]:
+                a_, b_ = max(a_, a), min(b_, b)
+                if b_ <= a_:
+                    continue
+                rr, bd = s2_band_reference(spec, srcs_rows, W, bb, bn, a_, b_, Hi)
+                w32, w16 = compare(a_, b_, rr, bd)
+                q['worst'] = w32 if q['worst'] is None else max(q['worst'], w32) if w32 is not None else q['worst']
+                q['worst16'] = w16 if q['worst16'] is None else max(q['worst16'], w16) if w16 is not None else q['worst16']
+                q['banded'].append((a_, b_))
+            assert q['banded'], (what, spec['name'], 'no band inside the needed rows %d .. %d' % (a, b - 1))
+            rep.append(q)
+            continue
         ra, rb = s2_rows_read(spec, a, b, Hi)
+        srcs = srcs_rows(0, Hi)
         hit = cache.get(i) if cache is not None else None
         if hit is not None and len(hit[0]) == len(srcs) and all(numpy.array_equal(u[:, ra:rb], v[:, ra:rb]) for u, v in zip(hit[0], srcs)):
             r, bound = hit[1], hit[2]; q['reused'] = True
         else:
-            W, bb, bn = s2_layer_params(P, spec, fmt == 'bf16')
             xs = numpy.concatenate(srcs, axis=3) if len(srcs) > 1 else srcs[0]
             r, bound = ref_conv2d_f64(xs, W, bb, bn, spec['s'], spec['p'], spec['tr'], spec['act'])
             if cache is not None:
                 cache[i] = (srcs, r, bound)
-        rr, bd = r[:, a:b], bound[:, a:b]
-        assert numpy.isfinite(rr).all(), (what, spec['name'], 'the reference of a needed row read a NaN source row')
-        if o32 is not None:
-            q['worst'] = assert_close_elementwise(o32[:, a:b], rr, bd, tol, '%s %s fp32' % (what, spec['name']))
-        else:
-            v = s2_value16(o16)[:, a:b]
-            if o16.ndim == 5:      # hi + lo rebuilds the fp32 value to 2^-17 of it (lo = bf16(v - hi), |v - hi| <= 2^-9 |v|, rounded to 8 bits again)
-                q['worst16'] = assert_close_elementwise(v, rr, bd + (2.0 ** -17 / tol) * numpy.abs(rr), tol, '%s %s split copy' % (what, spec['name']))
-            else:                  # rounding is monotone: the stored bf16 lies between the roundings of the two ends of the fp32 value's interval
-                lo_, hi_ = bf16_round((rr - tol * bd).astype(numpy.float32)), bf16_round((rr + tol * bd).astype(numpy.float32))
-                lo_ = numpy.minimum(lo_, bf16_round(numpy.nextafter((rr - tol * bd).astype(numpy.float32), numpy.float32(-numpy.inf))))   # (float64 -> float32 may round inwards)
-                hi_ = numpy.maximum(hi_, bf16_round(numpy.nextafter((rr + tol * bd).astype(numpy.float32), numpy.float32(numpy.inf))))
-                bad = ~((v >= lo_) & (v <= hi_))
-                assert not bad.any(), ('%s %s bf16 copy: %d elements outside bf16([r - tol bound, r + tol bound])' % (what, spec['name'], int(bad.sum())))
-                q['worst16'] = float((numpy.abs(v - rr) / numpy.maximum(bd, 1e-300)).max())
+        q['worst'], q['worst16'] = compare(a, b, r[:, a:b], bound[:, a:b])
         rep.append(q)
     return dict(layers=rep, need=need, raw=raw, x_in=x_in, fused=fused, k=(k0, k1), specs=specs)
 
