@@ -740,6 +740,26 @@ int ry_analysis_extract_many_resident(ry_analysis* analysis, const float* x32_de
 int ry_analysis_extract_spans_resident(ry_analysis* analysis, const float* x32_dev, long long x_len, const long long* first_sample, const int* n_samples,
                                        const double* f0_dev, const double* t_dev, const int* frame_offsets, const int* row_offsets, int n_waves,
                                        double threshold, float* mc32_dev_out, float* sp32_dev_out, float* ap32_dev_out);
+/* ---- A track of the caller's own (WORLD mode: f0 from a host tracker such as Harvest) for the device entries above; no ry_crepe handle is needed.
+ * ry_analysis_upload_waves: ONE upload -- n_waves >= 1 float32 waves back to back, n_samples[i] each, into a growable block of the handle ->
+ * *wave_dev, its device address (the x32_dev of the extract calls, the wave of the ry_vc gate entries).  The call returns once the caller's array is
+ * free.  Refused before anything is uploaded: null pointers, n_waves < 1, a wave without a sample, more than 2^31 - 1 samples in all.
+ * ry_analysis_ingest_tracks: ONE upload (f0 [sum n_frames] float64 on the HOST, the tracks back to back, and the segment table) and ONE launch of
+ * analysis_ingest_tracks, one thread per frame.  For frame k of every track, counted from that track's first frame: t = (k * frame_period_ms) / 1000
+ * in two separately rounded float64 operations (numpy's arange(n) * frame_period / 1000.0), voiced = (f0 != 0), f0 as it came -- so a track has the
+ * bits of the call on it alone, wherever it stands.  The tracks need not be those of all uploaded waves (a caller that gates first ingests the
+ * audible ones and names their waves to ry_analysis_extract_spans_resident).  NOTHING about the f0 values is checked here: the extract calls refuse
+ * a non-finite f0 or one at or above fs / 2 by their kernel's verdict, with nothing written.  Refused before anything is uploaded: null pointers,
+ * n_waves < 1, a track without a frame, more than 2^22 frames in all, a frame period that is not finite and positive.
+ * A refused call of either leaves the waves and the track of the last good call in place and reported.
+ * ry_analysis_track_buffers (any pointer may be null): the uploaded block, its waves and sample_offsets (HOST, n_waves + 1 entries from 0; null and
+ * 0 when no waves are on the card), the tracks of the last ingest and frame_offsets (HOST, n_tracks + 1 entries from 0), and the device addresses
+ * of voiced (bytes), f0 and t (float64).  The host tables hold until the next upload / ingest on the handle.  RY_ESTATE when no track is there:
+ * before the first ingest, and after ry_analysis_debug_poison (which covers these buffers and forgets waves and track). */
+int ry_analysis_upload_waves(ry_analysis* analysis, const float* audio, const int* n_samples, int n_waves, const float** wave_dev);
+int ry_analysis_ingest_tracks(ry_analysis* analysis, const double* f0, const int* n_frames, int n_waves, double frame_period_ms);
+int ry_analysis_track_buffers(ry_analysis* analysis, const float** wave_dev, int* n_waves, const long long** sample_offsets, int* n_tracks,
+                              const int** frame_offsets, const unsigned char** voiced_dev, const double** f0_dev, const double** t_dev);
 /* the number of bands B (1 at 16 kHz, 3 at 24 kHz); negative (an error code) where D4C is not built for the handle's rate */
 int ry_analysis_d4c_bands(ry_analysis* analysis);
 /* tests: what the last recorded (ry_analysis_debug_record) D4C run decided.  ints_out [n][9]: half length of the Love-Train window, of the other

@@ -81,6 +81,7 @@ ABI_SYMBOLS = (
     'ry_outgate_create', 'ry_outgate_destroy', 'ry_outgate_reset', 'ry_outgate_push', 'ry_outgate_held', 'ry_outgate_debug_counts', 'ry_outgate_debug_poison',
     'ry_outgate_bank_create', 'ry_outgate_bank_destroy', 'ry_outgate_bank_reset', 'ry_outgate_bank_push', 'ry_outgate_bank_held',
     'ry_outgate_bank_debug_counts', 'ry_outgate_bank_debug_poison',
+    'ry_analysis_upload_waves', 'ry_analysis_ingest_tracks', 'ry_analysis_track_buffers',
 )
 
 
@@ -294,6 +295,9 @@ class Ry355Lib(object):
         d.ry_crepe_bank_track_uploaded.argtypes = [_VP, _IP, _IP, _IP, _CI, _CI, _CI, ctypes.c_double, ctypes.c_double, _IP, _IP, _IP, _IP, _UB, _DP, _DP,
                                                    _CI]
         d.ry_crepe_debug_frames.argtypes = [_VP, ctypes.POINTER(_LL)]
+        d.ry_analysis_upload_waves.argtypes = [_VP, _FP, _IP, _CI, ctypes.POINTER(_VP)]
+        d.ry_analysis_ingest_tracks.argtypes = [_VP, _DP, _IP, _CI, ctypes.c_double]
+        d.ry_analysis_track_buffers.argtypes = [_VP, ctypes.POINTER(_VP), _IP, _LLPP, _IP, _IPP, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP)]
         d.ry_analysis_d4c_bands.argtypes = [_VP]
         _LLP = ctypes.POINTER(_LL)
         d.ry_outgate_create.argtypes = [_VP, _CI, ctypes.c_double, ctypes.c_double, _CI, ctypes.POINTER(_VP)]

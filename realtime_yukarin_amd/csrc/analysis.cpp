@@ -7,6 +7,8 @@
 // on the card, the track is checked by a kernel whose verdict the host reads before it launches the same frame kernels.
 // ry_analysis_extract_many_dev does that for the waves and tracks of ry_crepe_track_many: one widening, one check and one verdict for the call, then
 // the frame kernels once per wave on that wave's samples and rows (a frame kernel takes one wave: its clamp at both ends is that wave's).
+// ry_analysis_upload_waves / ry_analysis_ingest_tracks put the waves and an f0 track of the caller's own (WORLD mode: a host tracker) into buffers
+// of this handle, in the layout those device entries read; no CREPE handle is involved.
 #include "analysis_kernels.h"
 #include "d4c_kernels.h"
 #include "ry_host.h"
@@ -36,6 +38,16 @@ struct ry_analysis {
     DevBuf<D4cFrameRecord> d_rec{scratch};
     DevBuf<int> d_verdict{scratch};                   // ry_analysis_extract_dev: (first refused frame or -1, kind) of the track check
     std::vector<D4cFrameRecord> last_rec;             // ry_analysis_debug_d4c: a0, on / off, integers and coarse values of the last recorded run
+    // a caller's own track (WORLD mode: f0 from a host tracker).  ry_analysis_upload_waves: the float32 waves back to back and where each starts
+    // (waves + 1 entries; empty: none).  ry_analysis_ingest_tracks: its one upload (f0, then the segment table) lands in d_ingest, the kernel leaves
+    // f0 / t / voiced of the tracks back to back; trk_off: where each starts (tracks + 1 entries; empty: no track).  ry_analysis_track_buffers reports
+    // both; the extract calls read them in place.  No other call writes these buffers; ry_analysis_debug_poison forgets waves and track.
+    DevBuf<float> d_wave32{scratch};
+    DevBuf<double> d_ingest{scratch}, d_trk_f0{scratch}, d_trk_t{scratch};
+    DevBuf<unsigned char> d_trk_voiced{scratch};
+    std::vector<double> ingest_host;                  // the handle's copy of the upload: it outlives the call
+    std::vector<long long> up_off;
+    std::vector<int> trk_off;
 };
 
 namespace {
@@ -405,6 +417,83 @@ int ry_analysis_extract_spans_resident(ry_analysis* s, const float* x32_dev, lon
     return extract_dev(s, x32_dev, x_len, f0_dev, t_dev, n, spans.data(), n_waves, o);
 }
 
+// ---- a caller's own track: the waves and the f0 of a host tracker put on the card for the extract calls above.  Every refusal comes before anything
+// is uploaded or changed, so a refused call leaves the waves and the track of the last good call in place.
+int ry_analysis_upload_waves(ry_analysis* s, const float* audio, const int* n_samples, int n_waves, const float** wave_dev) {
+    RY_TRY(check_handle(s, "analysis"));
+    if (!audio || !n_samples || !wave_dev) return fail(RY_EINVAL, "null audio / n_samples / wave_dev");
+    if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
+    std::vector<long long> off((size_t)n_waves + 1, 0);
+    for (int i = 0; i < n_waves; ++i) {
+        if (n_samples[i] < 1) return fail(RY_EINVAL, "wave %d has %d samples", i, n_samples[i]);
+        off[(size_t)i + 1] = off[(size_t)i] + n_samples[i];
+        if (off[(size_t)i + 1] > 2147483647LL) return fail(RY_EINVAL, "the waves up to %d hold %lld samples: too many for one call", i, off[(size_t)i + 1]);
+    }
+    const ry_stream_t st = s->ctx->stream;
+    s->up_off.clear();                                                  // from here on the old block may be gone
+    RY_TRY(s->d_wave32.grow(s->ctx, off.back()));
+    RT_TRY(rt::h2d(s->d_wave32.ptr(), audio, (size_t)off.back() * sizeof(float), st));      // the one upload
+    RT_TRY(rt::stream_sync(st));                                        // the caller's array is free
+    s->up_off.swap(off);
+    *wave_dev = s->d_wave32.ptr();
+    return RY_OK;
+}
+
+int ry_analysis_ingest_tracks(ry_analysis* s, const double* f0, const int* n_frames, int n_waves, double frame_period_ms) {
+    RY_TRY(check_handle(s, "analysis"));
+    if (!f0 || !n_frames) return fail(RY_EINVAL, "null f0 / n_frames");
+    if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
+    if (!std::isfinite(frame_period_ms) || !(frame_period_ms > 0.0)) return fail(RY_EINVAL, "frame period %g ms: finite and positive", frame_period_ms);
+    std::vector<int> off((size_t)n_waves + 1, 0);
+    for (int i = 0; i < n_waves; ++i) {
+        if (n_frames[i] < 1) return fail(RY_EINVAL, "wave %d has %d frames", i, n_frames[i]);
+        const long long end = (long long)off[(size_t)i] + n_frames[i];
+        if (end > (1 << 22)) return fail(RY_EINVAL, "%lld frames in one call", end);
+        off[(size_t)i + 1] = (int)end;
+    }
+    const int n = off.back();
+    const ry_stream_t st = s->ctx->stream;
+    s->trk_off.clear();                                                 // from here on the old track may be gone
+    static_assert(sizeof(AnalysisIngestSeg) == sizeof(double), "a segment takes one slot of the upload");
+    const size_t slots = (size_t)n + (size_t)n_waves;                   // f0 [n], then the segment table [n_waves]
+    RY_TRY(s->d_ingest.grow(s->ctx, (long long)slots));
+    RY_TRY(s->d_trk_f0.grow(s->ctx, (long long)n));
+    RY_TRY(s->d_trk_t.grow(s->ctx, (long long)n));
+    RY_TRY(s->d_trk_voiced.grow(s->ctx, ((long long)n + 3) / 4 * 4));   // whole 32-bit words: ry_dev_download copies those
+    s->ingest_host.resize(slots);
+    std::memcpy(s->ingest_host.data(), f0, (size_t)n * sizeof(double));
+    for (int i = 0; i < n_waves; ++i) {
+        const AnalysisIngestSeg seg = {off[(size_t)i], n_frames[i]};
+        std::memcpy(s->ingest_host.data() + n + i, &seg, sizeof seg);
+    }
+    RT_TRY(rt::h2d(s->d_ingest.ptr(), s->ingest_host.data(), slots * sizeof(double), st));          // the one upload
+    AnalysisIngestParams p;
+    p.f0_in = s->d_ingest.ptr(); p.segs = reinterpret_cast<const AnalysisIngestSeg*>(s->d_ingest.ptr() + n); p.n_segs = n_waves; p.n = n;
+    p.frame_period = frame_period_ms;
+    p.f0_64 = s->d_trk_f0.ptr(); p.t_64 = s->d_trk_t.ptr(); p.voiced = s->d_trk_voiced.ptr();
+    RY_LAUNCH(analysis_ingest_tracks, dim3((unsigned)((n + 255) / 256)), 256, st, p);
+    RT_TRY(rt::last_error());
+    RT_TRY(rt::stream_sync(st));                                        // the handle's copy of the upload is free for the next call
+    s->trk_off.swap(off);
+    return RY_OK;
+}
+
+int ry_analysis_track_buffers(ry_analysis* s, const float** wave_dev, int* n_waves, const long long** sample_offsets, int* n_tracks,
+                              const int** frame_offsets, const unsigned char** voiced_dev, const double** f0_dev, const double** t_dev) {
+    if (!s) return fail(RY_ESTATE, "null analysis handle");
+    if (s->trk_off.empty()) return fail(RY_ESTATE, "no track on the card: ry_analysis_ingest_tracks has not run, or the buffers were poisoned");
+    const bool up = !s->up_off.empty();
+    if (wave_dev) *wave_dev = up ? s->d_wave32.ptr() : nullptr;
+    if (n_waves) *n_waves = up ? (int)s->up_off.size() - 1 : 0;
+    if (sample_offsets) *sample_offsets = up ? s->up_off.data() : nullptr;
+    if (n_tracks) *n_tracks = (int)s->trk_off.size() - 1;
+    if (frame_offsets) *frame_offsets = s->trk_off.data();
+    if (voiced_dev) *voiced_dev = s->d_trk_voiced.ptr();
+    if (f0_dev) *f0_dev = s->d_trk_f0.ptr();
+    if (t_dev) *t_dev = s->d_trk_t.ptr();
+    return RY_OK;
+}
+
 int ry_analysis_d4c_bands(ry_analysis* s) {
     if (!s) return fail(RY_ESTATE, "null analysis handle");
     if (!s->d4c_ok) return fail(RY_EINVAL, "%s", s->d4c_why.c_str());
@@ -479,6 +568,7 @@ int ry_analysis_debug_poison(ry_analysis* s) {
     RT_TRY(rt::stream_sync(st));
     for (DevBufBase* b : s->scratch) RY_TRY(b->poison(st));            // all bits set: NaN as a double, -1 as an integer
     RT_TRY(rt::stream_sync(st));
+    s->up_off.clear(); s->trk_off.clear();                              // the uploaded waves and the ingested track are gone with their buffers
     return RY_OK;
 }
 

@@ -7,6 +7,7 @@
 //                    smoothing boundary) are decided without floating-point contraction: they have to equal the restatement's exactly.
 //   analysis_sp2mc   one workgroup per frame of a spectrogram that comes from elsewhere: log, transform, times S.
 // Both are pure functions of their frame: no atomics, nothing shared between workgroups, so a row does not depend on what else is in the call.
+// At the end of the file: analysis_widen / analysis_check_track (inputs already on the card) and analysis_ingest_tracks (a caller's own f0 track).
 #pragma once
 #include "lds_fft.h"
 
@@ -289,4 +290,44 @@ RY_KERNEL(256) void analysis_check_track(AnalysisCheckParams p) {
         p.verdict[0] = k < p.n ? k : -1;
         p.verdict[1] = kind;
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// A track that comes from the caller (ry_analysis_ingest_tracks): the f0 of a host tracker -- WORLD mode's Harvest -- for several waves, back to back.
+//   analysis_ingest_tracks  one thread per frame of the call.  A thread finds its wave in the segment table (first frame and frames per wave,
+//                           ascending: a binary search) and writes, for frame k of that wave, t_64 = (k * frame_period) / 1000 -- two separately
+//                           rounded float64 operations, numpy's `arange(n) * frame_period / 1000.0` --, voiced = (f0 != 0) and f0_64 = f0 as it came.
+// k counts from the wave's own first frame, so a wave's rows do not depend on where it stands in the call.  Nothing is validated here: the extract
+// calls refuse a track by the verdict of analysis_check_track, the one place that does.
+// ---------------------------------------------------------------------------------------------
+struct AnalysisIngestSeg { int frame0, n_frames; };
+
+struct AnalysisIngestParams {
+    const double* f0_in;                          // [n] as uploaded
+    const AnalysisIngestSeg* segs; int n_segs;    // segs[i].frame0 ascending from 0, segs[i].frame0 + segs[i].n_frames = segs[i + 1].frame0
+    int n;                                        // frames in all
+    double frame_period;                          // ms
+    double* f0_64; double* t_64; unsigned char* voiced;       // [n]
+};
+
+RY_DEV double analysis_frame_time(int k, double frame_period) {
+#pragma clang fp contract(off)
+    const double ms = (double)k * frame_period;
+    return ms / 1000.0;
+}
+
+RY_KERNEL(256) void analysis_ingest_tracks(AnalysisIngestParams p) {
+    const long long g = (long long)blockIdx.x * 256 + (long long)threadIdx.x;
+    if (g >= (long long)p.n) return;
+    const int i = (int)g;
+    int lo = 0, hi = p.n_segs - 1;                                 // the last segment that starts at or before frame i
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (p.segs[mid].frame0 <= i) lo = mid; else hi = mid - 1;
+    }
+    const int k = i - p.segs[lo].frame0;
+    const double f = p.f0_in[i];
+    p.t_64[i] = analysis_frame_time(k, p.frame_period);
+    p.voiced[i] = f != 0.0 ? 1 : 0;                                // NaN != 0: voiced, as numpy has it
+    p.f0_64[i] = f;
 }

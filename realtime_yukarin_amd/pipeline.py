@@ -20,7 +20,13 @@ F0Converter on the host with exactly the numpy operations of the separate calls.
 effective frame go through the tracker (`track_uploaded`) and the analysis (`Analyzer.extract_spans_resident`, rows at the wave's place in the
 layout of the whole call); `VcCore.enqueue_waves_masked_device` then runs every wave's window on that verdict.  A wave without an effective frame
 costs no tracker, CheapTrick, sp2mc or D4C kernel, none of its feature rows is read, and every sample of every stream keeps its bits (DESIGN.md
-section 21).  `calls['gated']` counts the waves skipped; `last_gate` is the record of the last such call."""
+section 21).  `calls['gated']` counts the waves skipped; `last_gate` is the record of the last such call.
+
+`f0_mode='world'` (the reference's default `extract_f0_mode`): f0 comes from a host callable -- `pyworld.harvest` through the feature class's
+`extract_f0` unless `f0_fn` is given -- and the resident path starts at `Analyzer.upload_waves` / `Analyzer.ingest_tracks` instead of the CREPE
+tracker; no CREPE model is built.  The bits are those of the composed chain with the same callable (`world_analysis.extract` ->
+`convert_from_acoustic_feature` -> `world_synth.decode`), which also runs whenever the callable's track is not the one the frame-count rule
+expects; with `gate_first` a silent wave costs no host f0 call."""
 import ctypes
 import os
 from typing import Optional
@@ -97,6 +103,75 @@ def _gate_first_rows(handles, acoustic_param, voice_changer, waves, discard, res
     return ctx, b, fo, f0s, record
 
 
+def _track_fits(f0, t, n: int, frame_period) -> bool:
+    """WORLD mode: what the f0 callable returned is a track the ingest kernel restates -- n frames, t = k * frame_period / 1000 to the bit."""
+    return f0.ndim == 1 and t.ndim == 1 and f0.size == n and t.size == n and bool(numpy.array_equal(t, world_analysis.frame_times(n, frame_period)))
+
+
+def _world_f0(f0_fn, wave, acoustic_param):
+    """The host f0 call of WORLD mode on `wave.wave.astype(float64)`, what `AcousticFeature.extract` hands `extract_f0` -> (f0, t) float64."""
+    p = acoustic_param
+    f0, t = f0_fn(wave.wave.astype(numpy.float64), wave.sampling_rate, p.frame_period, p.f0_floor, p.f0_ceil)
+    return numpy.asarray(f0, numpy.float64), numpy.asarray(t, numpy.float64)
+
+
+def _converted_f0(ac, dtype, track, eff):
+    """f0 of one wave as the synthesizer reads it: the numpy operations of the separate calls -- astype_only_float(dtype), indexing(effective), the
+    F0Converter, combine_silent's float32 zeros, the synthesizer's float64 cast.  track None: a wave the gate skipped."""
+    from yukarin.acoustic_feature import AcousticFeature
+    f0 = numpy.zeros((len(eff), 1), numpy.float32)
+    if track is not None:
+        f0_eff = track[:, None].astype(dtype)[eff]
+        if eff.any() and ac.f0_converter is not None:
+            f0_eff = ac.f0_converter.convert(AcousticFeature(f0=f0_eff)).f0
+        f0[eff] = f0_eff
+    return numpy.ascontiguousarray(f0.ravel(), dtype=numpy.float64)
+
+
+def _world_rows(handles, acoustic_param, voice_changer, waves, discard, reserve, f0_fn, gate_first: bool):
+    """The resident chain of WORLD mode for the waves of one call: one upload (`Analyzer.upload_waves`), the host f0 call per wave, one ingest
+    (`Analyzer.ingest_tracks`), then the chain of CREPE mode unchanged -> (rows, tracks).  rows: (context, blocks, frame offsets int32 [waves + 1],
+    [f0 float64 [frames_i]], record), or None when a track does not fit (another frame count than Harvest's rule, another t): the call then takes
+    the composed path.  tracks: {wave index: (f0, t)} of every host f0 call made, so that the composed path does not make them again.
+    gate_first: the verdict of the gate first (`VcCore.gate_verdict_waves_device`), the host f0 call and the analysis only for the waves with an
+    effective frame; record as `_gate_first_rows` has it (None without the flag)."""
+    _, analyzer, core, (p_eff, p_all), hop, gate_fft = handles
+    p, ac = acoustic_param, voice_changer.acoustic_converter
+    fs = int(waves[0].sampling_rate)
+    xs = [numpy.ascontiguousarray(w.wave, dtype=numpy.float32).ravel() for w in waves]
+    up = analyzer.upload_waves(xs)                                         # the one upload
+    fo = numpy.concatenate([[0], numpy.cumsum([world_analysis.harvest_frames(x.size, fs, p.frame_period) for x in xs])]).astype(numpy.int32)
+    n, ctx = int(fo[-1]), core.stage1.ctx
+    b = reserve(ctx, n, p.order + 1, core.M, core.F)
+    which = list(range(len(xs)))
+    if gate_first:
+        effective, n_eff = core.gate_verdict_waves_device(up.wave, up.offsets, fo, hop, gate_fft, p_eff, p_all, b['mask'])      # the one wait of the gate
+        which = [i for i in which if n_eff[i] > 0]
+    tracks = {}
+    for i in which:                                                        # a wave the gate skipped costs no host f0 call
+        tracks[i] = _world_f0(f0_fn, waves[i], p)
+        if not _track_fits(tracks[i][0], tracks[i][1], int(fo[i + 1] - fo[i]), p.frame_period):
+            return None, tracks
+    discard = (int(discard[0]), int(discard[1])) if os.environ.get('RY_DISCARD_HINT', '1') != '0' else (0, 0)
+    if which:
+        trk = analyzer.ingest_tracks([tracks[i][0] for i in which], p.frame_period, up, which)
+        if gate_first:
+            analyzer.extract_spans_resident(trk.wave, trk.samples, trk.first_sample, trk.n_samples, trk.f0, trk.t, trk.frame_offsets,
+                                            [int(fo[i]) for i in which], b['mc32'], b['sp32'], b['ap32'])
+        else:
+            analyzer.extract_many_resident(trk.wave, trk.sample_offsets, trk.f0, trk.t, fo, b['mc32'], b['sp32'], b['ap32'])
+    if core.discard != discard:
+        core.set_discard(*discard)
+    if gate_first:
+        core.enqueue_waves_masked_device(fo, b['mc32'], b['mc_out'], b['sp_out'], b['mask'], effective, n_eff, SP_FLOOR)
+    else:
+        effective, n_eff = core.enqueue_waves_device(up.wave, up.offsets, fo, hop, gate_fft, p_eff, p_all, b['mc32'], b['mc_out'], b['sp_out'],
+                                                     b['mask'], SP_FLOOR)
+    f0s = [_converted_f0(ac, p.dtype, tracks[i][0] if i in tracks else None, effective[fo[i]:fo[i + 1]]) for i in range(len(xs))]
+    record = dict(n_eff=[int(k) for k in n_eff], tracked=[i in tracks for i in range(len(xs))], n_computed=[None] * len(xs)) if gate_first else None
+    return (ctx, b, fo, f0s, record), tracks
+
+
 _feature_class = None
 
 
@@ -141,13 +216,32 @@ class Pipeline(object):
     its own, the rows the caller keeps go to one synthesis stream.  `voice_changer`: the mirror `voice_changer.VoiceChanger` over the two converter
     shims; `acoustic_param`: the vocoder's (`Vocoder.acoustic_param`); `feature_class`: the class `Vocoder.encode` would call `extract` on."""
 
-    def __init__(self, voice_changer, acoustic_param, crepe_capacity='full', seed: Optional[int] = None, feature_class=None, gate_first: bool = False):
+    def __init__(self, voice_changer, acoustic_param, crepe_capacity='full', seed: Optional[int] = None, feature_class=None, gate_first: bool = False,
+                 f0_mode: str = 'crepe', f0_fn=None):
+        """f0_mode='world' (the reference's default `extract_f0_mode`): f0 comes from the host -- `f0_fn(x float64, fs, frame_period, f0_floor,
+        f0_ceil) -> (f0, t)`, by default the feature class's `extract_f0` (`pyworld.harvest`) -- and enters the resident path through
+        `Analyzer.upload_waves` / `ingest_tracks`; no CREPE model is built or asked for, `crepe_capacity` and `advance=` are ignored
+        (INTEGRATION.md section 20)."""
+        if f0_mode not in ('crepe', 'world'):
+            raise ValueError("f0_mode is 'crepe' or 'world', got %r" % (f0_mode,))
         self.voice_changer, self.acoustic_param = voice_changer, acoustic_param
+        self.f0_mode = f0_mode
         self.gate_first = bool(gate_first)                                 # the silence gate in front of the encode stage (resident path only)
         self.last_gate = None                                              # the record of the last gate_first call
         self._gate_bank, self._pending = None, 0                           # gate_first with `advance`: a one-stream tracker bank; the advance of the skipped buffers
         self.crepe_capacity = crepe_capacity
-        self.feature_class = crepe_feature_class() if feature_class is None else feature_class
+        if f0_mode == 'world':
+            if feature_class is None:
+                from yukarin.acoustic_feature import AcousticFeature as feature_class
+            self.feature_class = feature_class
+            self.f0_fn = f0_fn if f0_fn is not None else (
+                lambda x, fs, frame_period, f0_floor, f0_ceil: feature_class.extract_f0(x=x, fs=fs, frame_period=frame_period, f0_floor=f0_floor,
+                                                                                         f0_ceil=f0_ceil))
+        else:
+            if f0_fn is not None:
+                raise ValueError("f0_fn belongs to f0_mode='world': CREPE mode tracks on the card")
+            self.feature_class = crepe_feature_class() if feature_class is None else feature_class
+            self.f0_fn = None
         self.seed = int(os.environ.get('RY_SYNTH_SEED', '0')) if seed is None else int(seed)
         self.synth = world_synth.Synthesizer(voice_changer.output_sampling_rate, acoustic_param.frame_period, seed=self.seed,
                                              ctx=world_synth.engine_for_tests.ctx)
@@ -239,10 +333,35 @@ class Pipeline(object):
         return dict(frame_period=p.frame_period, f0_floor=p.f0_floor, f0_ceil=p.f0_ceil, fft_length=p.fft_length, order=p.order, alpha=p.alpha,
                     dtype=p.dtype)
 
+    @staticmethod
+    def _world_fusable(wave) -> bool:
+        """WORLD mode's part of `encode._fusable`: D4C from the device, a mono wave that is not empty and holds float32 values, a whole rate."""
+        if world_analysis.aperiodicity is not world_analysis.device_aperiodicity:
+            return False
+        w, fs = numpy.asarray(wave.wave), wave.sampling_rate
+        if w.ndim != 1 or w.size == 0 or not numpy.issubdtype(w.dtype, numpy.floating) or int(fs) != fs:
+            return False
+        # the chain analyses wave.astype(float64): the one float32 upload serves it only when both hold the same values
+        return w.dtype == numpy.float32 or bool(numpy.array_equal(w.astype(numpy.float32).astype(w.dtype), w))
+
+    def _world_row(self, wave, handles, discard, gate_first: bool):
+        """WORLD mode's `_resident_rows` / `_gate_first_row` (`_world_rows` on one wave) -> ((context, blocks, frames, f0), track); the first is
+        None when the track of the f0 callable does not fit and the call takes the composed path with that track."""
+        rows, tracks = _world_rows(handles, self.acoustic_param, self.voice_changer, [wave], discard, self._reserve, self.f0_fn, gate_first)
+        if rows is None:
+            return None, tracks.get(0)
+        ctx, b, fo, f0s, record = rows
+        if gate_first:
+            calls.setdefault('gated', 0)
+            _gated(calls, 1 - sum(record['tracked']))
+            self.last_gate = record
+        return (ctx, b, int(fo[-1]), f0s[0]), tracks.get(0)
+
     def _resident_handles(self, wave):
         """-> (model, analyzer, core, gate thresholds, hop, fft_length of the gate) when every condition of the resident path holds, else None."""
         vc, p = self.voice_changer, self.acoustic_param
-        if not encode._fusable(self.feature_class, wave):
+        world = self.f0_mode == 'world'
+        if not (self._world_fusable(wave) if world else encode._fusable(self.feature_class, wave)):
             return None
         ac = vc.acoustic_converter
         if not (hasattr(ac, 'fusable') and ac.fusable()):
@@ -260,12 +379,15 @@ class Pipeline(object):
         core = vc._fused_core()
         if core is None or core.F != BINS or ac.desc.in_ch != p.order + 1:
             return None
-        from .compat import crepe as shim
-        model = shim._model(self.crepe_capacity)
+        model = None                                                       # WORLD mode: no CREPE model is built or asked for
+        if not world:
+            from .compat import crepe as shim
+            model = shim._model(self.crepe_capacity)
+            model._get()
         analyzer = world_analysis._analyzer(fs, fft_size, p.order, float(p.alpha))
-        model._get(), analyzer._get(), self.synth._get()
+        analyzer._get(), self.synth._get()
         ctx = core.stage1.ctx
-        if not (model._ctx is ctx and analyzer._ctx is ctx and self.synth._ctx is ctx):
+        if not ((model is None or model._ctx is ctx) and analyzer._ctx is ctx and self.synth._ctx is ctx):
             return None                                                    # the rows of one context are not addresses of another
         hop, _ = wave.get_hop_and_length(gp.frame_period)
         return model, analyzer, core, gate.thresholds(thr), hop, int(gp.fft_length)
@@ -305,7 +427,16 @@ class Pipeline(object):
     def _at(block: int, row: int):
         return _lib._fptr(int(block) + int(row) * BINS * 4)
 
-    def _composed_feature(self, wave, discard):
+    def _composed_feature(self, wave, discard, track=None):
+        """The chain of the separate calls up to the converted feature.  WORLD mode: `world_analysis.extract` over a class whose `extract_f0` is
+        the f0 callable -- or hands out `track`, the (f0, t) that callable already returned for this wave."""
+        if self.f0_mode == 'world':
+            fn = self.f0_fn if track is None else (lambda x, fs, frame_period, f0_floor, f0_ceil: track)
+            cls = type('WorldFeature', (self.feature_class,), {'extract_f0': classmethod(
+                lambda cls, x, fs, frame_period, f0_floor, f0_ceil: fn(x, fs, frame_period, f0_floor, f0_ceil))})
+            f = world_analysis.extract(cls, wave, **self._encode_args())
+            f.wave = wave
+            return self.voice_changer.convert_from_acoustic_feature(f, discard)
         saved = encode.model_capacity
         encode.model_capacity = self.crepe_capacity                        # `encode.extract` and the default class's `extract_f0` read it
         try:
@@ -321,11 +452,18 @@ class Pipeline(object):
         (None: the constructor's): the gate before the encode stage; the composed path ignores it."""
         from yukarin import Wave
         handles = self._resident_handles(wave)
+        rows = track = None
+        if handles is not None and self.f0_mode == 'world':
+            rows, track = self._world_row(wave, handles, (0, 0), self.gate_first if gate_first is None else gate_first)
+            if rows is None:
+                handles = None                                             # the callable's track does not fit: the composed path, with that track
         if handles is None:
             calls['composed'] += 1
-            return world_synth.decode(self._vocoder, self._composed_feature(wave, (0, 0)))
+            return world_synth.decode(self._vocoder, self._composed_feature(wave, (0, 0), track))
         calls['resident'] += 1
-        if self.gate_first if gate_first is None else gate_first:
+        if rows is not None:
+            ctx, b, n, f0 = rows
+        elif self.gate_first if gate_first is None else gate_first:
             ctx, b, n, f0 = self._gate_first_row(wave, handles, (0, 0))
         else:
             ctx, b, n, f0 = self._resident_rows(wave, handles, (0, 0))
@@ -353,10 +491,15 @@ class Pipeline(object):
         from yukarin import Wave
         front, back = int(discard[0]), int(discard[1])
         handles = self._resident_handles(wave)
+        rows = track = None
+        if handles is not None and self.f0_mode == 'world':               # `advance` is ignored: there are no kept activation rows
+            rows, track = self._world_row(wave, handles, (front, back), self.gate_first if gate_first is None else gate_first)
+            if rows is None:
+                handles = None                                             # the callable's track does not fit: the composed path, with that track
         if handles is None:
             calls['composed'] += 1
             self._reset_stream()
-            f = self._composed_feature(wave, (front, back))
+            f = self._composed_feature(wave, (front, back), track)
             k0, k1 = front, len(f.f0) - back
             out = numpy.empty(0, numpy.float64)
             if k1 > k0:
@@ -364,7 +507,9 @@ class Pipeline(object):
                 out = world_synth.decode_realtime(self._vocoder, picked).wave
         else:
             calls['resident'] += 1
-            if self.gate_first if gate_first is None else gate_first:
+            if rows is not None:
+                ctx, b, n, f0 = rows
+            elif self.gate_first if gate_first is None else gate_first:
                 ctx, b, n, f0 = self._gate_first_row(wave, handles, (front, back), advance, live=True)
             else:
                 self._reset_stream((False, True))
@@ -409,8 +554,10 @@ class PipelineBank(object):
     all share one rate; otherwise every wave runs the chain of the separate calls, one after the other, over the same bank: the same bits
     (`calls_many` counts which way a call went)."""
 
-    def __init__(self, voice_changer, acoustic_param, n_streams: int, seeds=None, crepe_capacity='full', feature_class=None, gate_first: bool = False):
-        self.gate_first = bool(gate_first)                                 # the silence gate in front of the encode stage (resident chain only)
+    def __init__(self, voice_changer, acoustic_param, n_streams: int, seeds=None, crepe_capacity='full', feature_class=None, gate_first: bool = False,
+                 f0_mode: str = 'crepe', f0_fn=None):
+        """f0_mode / f0_fn: as `Pipeline` has them -- WORLD mode runs ONE upload, the host f0 call per wave, ONE ingest and one chain per call."""
+        self.gate_first = bool(gate_first)                                # the silence gate in front of the encode stage (resident chain only)
         self.last_gate = None                                              # the record of the last gate_first call
         self.n_streams = int(n_streams)
         if self.n_streams < 1:
@@ -421,8 +568,9 @@ class PipelineBank(object):
         if len(self.seeds) != self.n_streams:
             raise ValueError('%d seeds for %d streams' % (len(self.seeds), self.n_streams))
         self.voice_changer, self.acoustic_param = voice_changer, acoustic_param
-        self._one = Pipeline(voice_changer, acoustic_param, crepe_capacity=crepe_capacity, seed=self.seeds[0], feature_class=feature_class)
-        self.feature_class = self._one.feature_class
+        self._one = Pipeline(voice_changer, acoustic_param, crepe_capacity=crepe_capacity, seed=self.seeds[0], feature_class=feature_class,
+                             f0_mode=f0_mode, f0_fn=f0_fn)
+        self.feature_class, self.f0_mode, self.f0_fn = self._one.feature_class, self._one.f0_mode, self._one.f0_fn
         self.bank = world_synth.StreamBank(voice_changer.output_sampling_rate, acoustic_param.frame_period, n_streams=self.n_streams, seeds=self.seeds,
                                            ctx=world_synth.engine_for_tests.ctx)
         self.calls = calls_many
@@ -496,6 +644,19 @@ class PipelineBank(object):
         self.last_gate = dict(record, streams=list(part) if part is not None else None)
         return ctx, b, fo, f0s
 
+    def _world_rows(self, waves, handles, discard, part, gate_first: bool):
+        """WORLD mode's `_resident_rows` / `_gate_first_rows` (`_world_rows` of the module) -> ((context, blocks, frame offsets, f0s), tracks); the
+        first is None when a track does not fit and the call takes the composed path with the tracks the callable already returned."""
+        rows, tracks = _world_rows(handles, self.acoustic_param, self.voice_changer, waves, discard, self._reserve, self.f0_fn, gate_first)
+        if rows is None:
+            return None, tracks
+        ctx, b, fo, f0s, record = rows
+        if gate_first:
+            calls_many.setdefault('gated', 0)
+            _gated(calls_many, len(waves) - sum(record['tracked']))
+            self.last_gate = dict(record, streams=list(part) if part is not None else None)
+        return (ctx, b, fo, f0s), tracks
+
     # ---- which way a call goes
     def _handles(self, waves):
         """The handles of the resident chain when every wave meets `Pipeline._resident_handles`, all share one rate and the bank lives in their
@@ -560,12 +721,18 @@ class PipelineBank(object):
             return []
         rate = self.voice_changer.output_sampling_rate
         handles = self._handles(waves)
+        gated = self.gate_first if gate_first is None else gate_first
+        done, tracks = None, {}
+        if handles is not None and self.f0_mode == 'world':
+            done, tracks = self._world_rows(waves, handles, (0, 0), None, gated)
+            if done is None:
+                handles = None                                             # a track does not fit: the composed path, with the tracks made so far
         if handles is None:
             calls_many['composed'] += 1
-            return [world_synth.decode(self._one._vocoder, self._one._composed_feature(w, (0, 0))) for w in waves]
+            return [world_synth.decode(self._one._vocoder, self._one._composed_feature(w, (0, 0), tracks.get(i))) for i, w in enumerate(waves)]
         calls_many['resident'] += 1
-        rows = self._gate_first_rows if (self.gate_first if gate_first is None else gate_first) else self._resident_rows
-        ctx, b, fo, f0s = rows(waves, handles, (0, 0))
+        rows = self._gate_first_rows if gated else self._resident_rows
+        ctx, b, fo, f0s = done if done is not None else rows(waves, handles, (0, 0))
         n = int(fo[-1])
         ctx.mask_rows(b['ap32'], b['mask'], n, BINS)
         synth = self._one.synth
@@ -620,11 +787,17 @@ class PipelineBank(object):
                 outs = self.bank.flush(final)
         else:
             handles = self._handles([waves[s] for s in part])
+            done, tracks = None, {}
+            if handles is not None and self.f0_mode == 'world':           # `advance` is ignored: there are no kept activation rows
+                done, tracks = self._world_rows([waves[s] for s in part], handles, (front, back), part,
+                                                self.gate_first if gate_first is None else gate_first)
+                if done is None:
+                    handles = None                                         # a track does not fit: the composed path, with the tracks made so far
             if handles is None:
                 calls_many['composed'] += 1
                 self._reset_trackers(part)
-                for s in part:
-                    f = self._one._composed_feature(waves[s], (front, back))
+                for i, s in enumerate(part):
+                    f = self._one._composed_feature(waves[s], (front, back), tracks.get(i))
                     k0, k1 = front, len(f.f0) - back
                     if k1 > k0:
                         picked = f.pick(k0, k1, keys=('f0', 'sp', 'ap'))
@@ -643,7 +816,9 @@ class PipelineBank(object):
                 per = advance
                 if advance is not None:                                    # per wave of the call: against the window the stream's tracker keeps
                     per = [advance if isinstance(advance, (int, numpy.integer)) else advance[s] for s in part]
-                if self.gate_first if gate_first is None else gate_first:
+                if done is not None:
+                    ctx, b, fo, f0s = done
+                elif self.gate_first if gate_first is None else gate_first:
                     ctx, b, fo, f0s = self._gate_first_rows([waves[s] for s in part], handles, (front, back), part, per)
                 else:
                     if advance is not None and any(self._pending[s] != 0 for s in part):      # buffers a gate_first call skipped lie in between

@@ -33,6 +33,55 @@ from .world_synth import BINS, FFT_SIZE, DeviceRows, _DeviceBuffer, cheaptrick_f
 _LLP = ctypes.POINTER(ctypes.c_longlong)
 
 
+def harvest_frames(n_samples: int, fs, frame_period) -> int:
+    """The frames `pyworld.harvest` returns for n_samples at fs: `int(1000 * n / fs / frame_period) + 1`.  Restated from memory of WORLD's
+    GetSamplesForHarvest and unpinned like the rest of the `pyworld` boundary: the pipeline only ever compares it with what
+    the f0 callable really returned and takes the composed path when they differ."""
+    return int(1000.0 * int(n_samples) / fs / frame_period) + 1
+
+
+def frame_times(n: int, frame_period) -> numpy.ndarray:
+    """`t` of a WORLD f0 tracker for n frames: k * frame_period / 1000, two rounded float64 operations -- what `ry_analysis_ingest_tracks` writes."""
+    return numpy.arange(int(n), dtype=numpy.float64) * float(frame_period) / 1000.0
+
+
+class UploadedWaves(object):
+    """What `Analyzer.upload_waves` left on the card: the address of the float32 waves (back to back) and `offsets` (int64, waves + 1 entries): where
+    wave i starts.  Holds until the next `upload_waves` / `poison` of the analyzer."""
+
+    def __init__(self, analyzer, ctx, wave, offsets):
+        self.analyzer, self.ctx, self.wave, self.offsets = analyzer, ctx, wave, offsets
+        self.waves, self.samples = offsets.size - 1, int(offsets[-1])
+
+
+class WorldTracks(object):
+    """What `Analyzer.ingest_tracks` left on the card for the waves `which` of an `UploadedWaves`, with the fields `pipeline` reads of a CREPE track:
+    the addresses of the uploaded block `wave` (`samples` of it) and of the concatenated `voiced` (bytes), `f0` and `t` (float64) of the tracked
+    waves; `frame_offsets` (int32, tracked + 1 entries) into them; `first_sample` / `n_samples` of every tracked wave in the block, and -- when every
+    uploaded wave was tracked, so that waves and tracks correspond -- `sample_offsets` (int64, waves + 1 entries; else None).  They belong to the
+    analyzer's handle and hold until its next `upload_waves` / `ingest_tracks` / `poison`."""
+
+    def __init__(self, analyzer, ctx, uploaded, which, voiced, f0, t, frame_offsets):
+        self.analyzer, self.ctx, self.which = analyzer, ctx, list(which)
+        self.wave, self.samples = uploaded.wave, uploaded.samples
+        self.first_sample = numpy.asarray([uploaded.offsets[i] for i in which], numpy.int64)
+        self.n_samples = numpy.asarray([uploaded.offsets[i + 1] - uploaded.offsets[i] for i in which], numpy.int32)
+        self.sample_offsets = uploaded.offsets if self.which == list(range(uploaded.waves)) else None
+        self.voiced, self.f0, self.t, self.frame_offsets = voiced, f0, t, frame_offsets
+        self.waves, self.frames = len(self.which), int(frame_offsets[-1])
+
+    def download(self, t: bool = False):
+        """[(voiced [frames] bool, f0 [frames] float64)] per tracked wave, read back from the card; t=True: [(voiced, f0, t)]."""
+        n, ctx = self.frames, self.ctx
+        words, f64, t64 = numpy.empty((n + 3) // 4, numpy.float32), numpy.empty(n, numpy.float64), numpy.empty(n, numpy.float64)
+        ctx.dev_download(self.voiced, words)
+        ctx.dev_download(self.f0, f64.view(numpy.float32))
+        if t:
+            ctx.dev_download(self.t, t64.view(numpy.float32))
+        voiced, o = words.view(numpy.uint8)[:n].astype(bool), self.frame_offsets
+        return [(voiced[o[i]:o[i + 1]], f64[o[i]:o[i + 1]]) + ((t64[o[i]:o[i + 1]],) if t else ()) for i in range(self.waves)]
+
+
 class Analyzer(DeviceHandle):
     """CheapTrick + sp2mc on the device (`ry_analysis_*`): one workgroup per frame, stateless.  `ctx` (tests): a context over another build of
     the library."""
@@ -194,6 +243,47 @@ class Analyzer(DeviceHandle):
                                                              as_d(f0_dev), as_d(t_dev), fo.ctypes.data_as(ip), ro.ctypes.data_as(ip), fs.size,
                                                              float(threshold), _lib._fptr(int(mc32_dev)), _lib._fptr(int(sp32_dev)),
                                                              _lib._fptr(int(ap32_dev))))
+
+    def upload_waves(self, waves) -> UploadedWaves:
+        """The one upload of a call whose f0 comes from the caller (`ry_analysis_upload_waves`): float32 waves back to back in a block of this
+        analyzer's handle -- no CREPE model is involved.  What `extract_*_resident` and the gate entries of `VcCore` read."""
+        xs = [numpy.ascontiguousarray(w, dtype=numpy.float32).ravel() for w in waves]
+        if not xs:
+            raise ValueError('upload_waves needs at least one wave')
+        lib, h = self._get()
+        counts = numpy.asarray([x.size for x in xs], numpy.int32)
+        audio = numpy.ascontiguousarray(numpy.concatenate(xs))
+        p = ctypes.c_void_p()
+        lib.check(lib.dll.ry_analysis_upload_waves(h, _lib._fptr(audio), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(xs), ctypes.byref(p)))
+        return UploadedWaves(self, self._ctx, p.value, numpy.concatenate([[0], numpy.cumsum(counts, dtype=numpy.int64)]).astype(numpy.int64))
+
+    def ingest_tracks(self, f0s, frame_period, uploaded: UploadedWaves, which=None) -> WorldTracks:
+        """The f0 tracks of a host tracker (one float64 array per wave of `which`, ascending indices into `uploaded`; None: every wave) onto the card
+        in one upload and one launch (`ry_analysis_ingest_tracks`): `t = k * frame_period / 1000`, `voiced = f0 != 0` and f0 itself, per wave from its
+        own first frame -- the bits of the call on that wave alone.  Nothing about the values is checked here; `extract_*_resident` refuses a track
+        `run` would refuse."""
+        which = list(range(uploaded.waves)) if which is None else [int(i) for i in which]
+        tracks = [numpy.ascontiguousarray(numpy.asarray(f, dtype=numpy.float64).reshape(-1)) for f in f0s]
+        if uploaded.analyzer is not self or not which or len(tracks) != len(which) or any(i < 0 or i >= uploaded.waves for i in which) \
+                or any(b <= a for a, b in zip(which, which[1:])):
+            raise ValueError('ingest_tracks needs one track per wave of ascending indices into an upload of this analyzer, got %d tracks for %s of %d'
+                             % (len(tracks), which, uploaded.waves))
+        lib, h = self._get()
+        counts = numpy.asarray([f.size for f in tracks], numpy.int32)
+        f0 = numpy.ascontiguousarray(numpy.concatenate(tracks))
+        lib.check(lib.dll.ry_analysis_ingest_tracks(h, _dptr(f0), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(tracks), float(frame_period)))
+        return self._tracks_on_card(uploaded, which)
+
+    def _tracks_on_card(self, uploaded, which) -> WorldTracks:
+        lib, h = self._get()
+        p = [ctypes.c_void_p() for _ in range(4)]
+        nw, nt = ctypes.c_int(), ctypes.c_int()
+        so, fo = _LLP(), ctypes.POINTER(ctypes.c_int)()
+        lib.check(lib.dll.ry_analysis_track_buffers(h, ctypes.byref(p[0]), ctypes.byref(nw), ctypes.byref(so), ctypes.byref(nt), ctypes.byref(fo),
+                                                    *[ctypes.byref(q) for q in p[1:]]))
+        assert nt.value == len(which) and p[0].value == uploaded.wave and nw.value == uploaded.waves, (nt.value, len(which), nw.value)
+        frame_offsets = numpy.asarray(fo[:nt.value + 1], numpy.int32)           # a copy: the handle's array changes with its next call
+        return WorldTracks(self, self._ctx, uploaded, which, p[1].value, p[2].value, p[3].value, frame_offsets)
 
     def d4c(self, x, f0, t, threshold: float = 0.85) -> numpy.ndarray:
         """`pyworld.d4c` of this analyzer's rate: -> aperiodicity [frames][513] float64."""
