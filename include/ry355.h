@@ -583,6 +583,35 @@ typedef struct ry_plan_record {
  * forward at `frames` padded rows (the discards must be 0).  *n = records written (16); RY_EINVAL when max is smaller. */
 int ry_net_debug_plan(ry_net* net, int batch, int frames, int window, int discard_front, int discard_back, ry_plan_record* records, int max, int* n);
 
+/* ---- where the filter layouts of a predictor are built.  Process-wide.  0 = host, the default:
+ * ry_net_create lays every filter out in host loops and uploads each layout; the Winograd filters of a layer are read back from the card,
+ * transformed on the host and uploaded when the first launch plan takes the layer onto that path.  1 = device: the raw filter of a layer is uploaded
+ * once and kernels write every layout (same allocations, same bits); the Winograd transform is one launch, without a download.  Also set by the
+ * environment variable RY_FILTER_BUILD=host|device, read by ry_init and ry_debug_reload_env; an absent variable leaves the mode as it is.  Any other
+ * mode number / value: RY_EINVAL, the mode stays as it was.  Predictors that exist keep their filters; the mode applies to what is built next (the
+ * filters ry_net_create builds, a lazy Winograd build, the single operators). */
+int ry_set_filter_build(int mode);
+typedef struct ry_build_stats {
+    unsigned long long bytes_uploaded;        /* host -> card copies into the predictor's filter arena (raw filters or layouts, scale / shift, 16-bit copies) */
+    unsigned long long bytes_downloaded;      /* card -> host copies the build made (host mode: the direct layout for the Winograd transform; ry_net_set_dtype) */
+    unsigned long long layout_launches;       /* layout kernels launched (device mode: one per layout built) */
+    unsigned long long host_relayout_floats;  /* floats of the layouts that host loops wrote (host mode) */
+    unsigned long long arena_bytes;           /* bytes allocated in the filter arena so far */
+} ry_build_stats;
+/* What building the filters of this predictor has taken so far.  The counters belong to the filter arena, which the clones of a predictor share
+ * (ry_net_clone): every handle reports the same totals, and they go on counting across lazy builds. */
+int ry_net_build_stats(ry_net* net, ry_build_stats* out);
+/* tests: one filter layout of predictor layer 0 .. 15, copied to the host.  kind: 0 w1d, 1 w1os (stage 1), 2 wig (implicit GEMM), 3 wdir (direct),
+ * 4 w2os (output-stationary), 5 wwin (Winograd; built on demand in the mode in force, as a launch plan would).  *n_floats = the layout's size.
+ * RY_ESTATE: the layer has no such layout.  RY_EINVAL: bad layer / kind, or out_floats < the size (*n_floats is set: out = NULL, out_floats = 0 asks
+ * for the size).  A refused call writes nothing to out and builds nothing. */
+int ry_net_debug_filters(ry_net* net, int layer, int kind, float* out, size_t out_floats, size_t* n_floats);
+/* tests: the same for one layer of any shape outside a predictor: the layer's filters are built from the raw Chainer filter W (HOST; conv (Cout, Cin, k[, k]),
+ * transposed (Cin, Cout, 4[, 4]), Cin = cin_a + cin_b for two skip sources) in the mode in force, into memory of the call, and layout `kind` comes back.
+ * ndim 1 / 2; k <= 4; transposed: k4 s2 p1 only; want_os2: build the output-stationary layout whatever the filter's size.  Refusals as above. */
+int ry_debug_layer_filters(ry_ctx* ctx, int ndim, int cin_a, int cin_b, int cout, int k, int stride, int pad, int transposed, int want_os2,
+                           const float* W, int kind, float* out, size_t out_floats, size_t* n_floats);
+
 /* ---- WORLD synthesizer (`pyworld.synthesize(f0, sp, ap, fs, frame_period)` in the reference's Vocoder.decode and world4py's realtime
  * synthesizer in RealtimeVocoder.decode, yukarin_wrapper/vocoder.py:50-120).  Semantics: INTEGRATION.md section 10 and
  * tests/world_synth_ref.py (WORLD's Synthesis restated; counter-based noise of `seed`, phase wrapped at every step).

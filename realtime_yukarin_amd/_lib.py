@@ -82,6 +82,7 @@ ABI_SYMBOLS = (
     'ry_outgate_bank_create', 'ry_outgate_bank_destroy', 'ry_outgate_bank_reset', 'ry_outgate_bank_push', 'ry_outgate_bank_held',
     'ry_outgate_bank_debug_counts', 'ry_outgate_bank_debug_poison',
     'ry_analysis_upload_waves', 'ry_analysis_ingest_tracks', 'ry_analysis_track_buffers',
+    'ry_set_filter_build', 'ry_net_build_stats', 'ry_net_debug_filters', 'ry_debug_layer_filters',
 )
 
 
@@ -101,6 +102,16 @@ class RyPlanRecord(ctypes.Structure):
     FIELDS = ('layer', 'path', 'tile', 'splits', 'kgroups', 'wino_cfg', 'wino_mbw', 'os2', 'reads16', 'writes32', 'writes16', 'patch', 'reduce', 'last_exp',
               'rows_out', 'grid_rows', 'grid_cols', 'tile_rows', 'tile_cols', 'out_lo', 'out_n', 'crop_lo', 'crop_n', 'hole_lo', 'hole_n')
     _fields_ = [(f, ctypes.c_int * 4 if f == 'os2' else ctypes.c_int) for f in FIELDS]
+
+
+class RyBuildStats(ctypes.Structure):
+    """ry_build_stats (include/ry355.h): unsigned 64-bit counters, in the header's order"""
+    FIELDS = ('bytes_uploaded', 'bytes_downloaded', 'layout_launches', 'host_relayout_floats', 'arena_bytes')
+    _fields_ = [(f, ctypes.c_ulonglong) for f in FIELDS]
+
+
+FILTER_BUILD = {'host': 0, 'device': 1}
+FILTER_KINDS = {'w1d': 0, 'w1os': 1, 'wig': 2, 'wdir': 3, 'w2os': 4, 'wwin': 5}
 
 
 class Ry355Error(RuntimeError):
@@ -320,6 +331,10 @@ class Ry355Lib(object):
         d.ry_net_profile_window.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RyKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         d.ry_net_debug_activation.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
         d.ry_net_debug_plan.argtypes = [_VP] + [ctypes.c_int] * 5 + [ctypes.POINTER(RyPlanRecord), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        d.ry_set_filter_build.argtypes = [ctypes.c_int]
+        d.ry_net_build_stats.argtypes = [_VP, ctypes.POINTER(RyBuildStats)]
+        d.ry_net_debug_filters.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _FP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+        d.ry_debug_layer_filters.argtypes = [_VP] + [ctypes.c_int] * 9 + [_FP, ctypes.c_int, _FP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
 
     def check(self, rc):
         if rc != 0:

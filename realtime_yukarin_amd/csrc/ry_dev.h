@@ -128,3 +128,5 @@ RY_DEV void ry_st8h(unsigned short* p, u16x8 v) { *reinterpret_cast<u16x8*>(p) =
 // constants the host planner (ry_plan.cpp) and the kernels share: epilogue activations, forms of a stage-1 layer
 enum { RY_ACT_NONE = 0, RY_ACT_LRELU = 1, RY_ACT_RELU = 2, RY_ACT_GLU = 3 };
 enum { RY_C1D_S2 = 0, RY_C1D_S1 = 1, RY_C1D_DECONV = 2, RY_C1D_GEN = 3 };
+// ... the filter layouts of a layer (relayout_kernels.h; `kind` of ry_net_debug_filters)
+enum { RY_LAYOUT_W1D = 0, RY_LAYOUT_W1OS = 1, RY_LAYOUT_WIG = 2, RY_LAYOUT_WDIR = 3, RY_LAYOUT_W2OS = 4, RY_LAYOUT_WWIN = 5 };

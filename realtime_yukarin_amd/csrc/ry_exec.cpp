@@ -2,6 +2,7 @@
 // forward of a plan enqueued on the predictor's stream (captured once into a hipGraph, replayed per window), plan autotuning, per-launch profiling, and the
 // single operators of the C ABI (ry_conv1d / ry_conv2d: the kernels behind one call, what the operator-level parity tests drive).
 #include "ry_kernels.h"
+#include "relayout_kernels.h"
 #include "ry_plan.h"
 
 static void fill_geom(RyConvGeom& g, const Layer& l, const LayerPlan& lp, int B, const float* s1, int C1, const float* s2, int C2) {
@@ -744,6 +745,44 @@ extern "C" int ry_debug_stream_overlap(ry_ctx* ctx, int n, int us, float* ratio)
 #endif
 }
 
+// ---- filter layouts built on the card (filter build mode `device`, relayout_kernels.h) ----------
+int launch_relayout(ry_ctx* ctx, const Layer& l, int kind, const float* W, float* out) {
+    const TapTable t = make_taps(l);
+    RyRelayoutParams p;
+    memset(&p, 0, sizeof p);
+    p.W = W; p.out = out; p.total = (long long)filter_layout_floats(l, kind);
+    p.C = l.cin(); p.N = l.cout; p.K = l.k; p.deconv = l.deconv ? 1 : 0; p.nphases = t.nphases; p.ntaps = t.ntaps;
+    for (int ph = 0; ph < t.nphases; ++ph)
+        for (int tt = 0; tt < t.ntaps; ++tt) { p.ky[ph][tt] = (unsigned char)t.ky[ph][tt]; p.kx[ph][tt] = (unsigned char)t.kx[ph][tt]; }
+    if (p.total < 1) return fail(RY_EINVAL, "%s: empty filter layout", l.name);
+    const dim3 grid((unsigned)(((p.total + 3) / 4 + 255) / 256));
+    switch (kind) {
+        case RY_LAYOUT_W1D: RY_LAUNCH(ry_relayout<RY_LAYOUT_W1D>, grid, 256, ctx->stream, p); break;
+        case RY_LAYOUT_W1OS: RY_LAUNCH(ry_relayout<RY_LAYOUT_W1OS>, grid, 256, ctx->stream, p); break;
+        case RY_LAYOUT_WIG: RY_LAUNCH(ry_relayout<RY_LAYOUT_WIG>, grid, 256, ctx->stream, p); break;
+        case RY_LAYOUT_WDIR: RY_LAUNCH(ry_relayout<RY_LAYOUT_WDIR>, grid, 256, ctx->stream, p); break;
+        case RY_LAYOUT_W2OS: RY_LAUNCH(ry_relayout<RY_LAYOUT_W2OS>, grid, 256, ctx->stream, p); break;
+        default: return fail(RY_EINVAL, "%s: no layout kernel of kind %d", l.name, kind);
+    }
+    RT_TRY(rt::last_error());
+    return RY_OK;
+}
+
+int launch_relayout_wino(ry_ctx* ctx, const Layer& l, const float* wdir, float* out) {
+    const TapTable t = make_taps(l);
+    RyRelayoutWinoParams p;
+    memset(&p, 0, sizeof p);
+    p.wd = wdir; p.out = out; p.C = l.cin(); p.N = l.cout; p.deconv = l.deconv ? 1 : 0;
+    p.nsl = l.deconv ? p.C / 8 : (p.C / 16) * 8;
+    for (int ph = 0; ph < t.nphases; ++ph)
+        for (int tt = 0; tt < t.ntaps; ++tt) p.where[t.ky[ph][tt]][t.kx[ph][tt]] = (unsigned char)(ph * t.ntaps + tt);
+    p.threads = (long long)(l.deconv ? 4 : 1) * p.N * p.nsl * 8;
+    const dim3 grid((unsigned)((p.threads + 255) / 256));
+    RY_LAUNCH(ry_relayout_wino, grid, 256, ctx->stream, p);
+    RT_TRY(rt::last_error());
+    return RY_OK;
+}
+
 // ---- single operators -------------------------------------------------------------------------
 extern "C" {
 int ry_conv1d(ry_ctx* ctx, const float* x, int B, int L, int Cin, const float* W, const float* bias, const float* bn,
@@ -794,7 +833,7 @@ int ry_conv1d(ry_ctx* ctx, const float* x, int B, int L, int Cin, const float* W
     RY_TRY(Lc.end());
     RT_TRY(rt::d2h(y, dy, (size_t)B * lp.Wo * Cy * sizeof(float), ctx->stream));
     RT_TRY(rt::stream_sync(ctx->stream));
-    return RY_OK;
+    return finish_filter_build(ctx);            // (filter build mode `device`: the staging buffer goes back)
 }
 
 int ry_conv1d_os(ry_ctx* ctx, const float* xa, const float* xb, int B, int Lin, int Ca, int Cb, const float* W, const float* bias, const float* bn,
@@ -840,7 +879,7 @@ int ry_conv1d_os(ry_ctx* ctx, const float* xa, const float* xb, int B, int Lin, 
     RY_TRY(launch_c1d_os(Lc, l, lp, B, da, Ca, db, Cb, dy, keep, 0.2f, n_real));
     RT_TRY(rt::d2h(y, dy, ny * sizeof(float), ctx->stream));
     RT_TRY(rt::stream_sync(ctx->stream));
-    return RY_OK;
+    return finish_filter_build(ctx);            // (filter build mode `device`: the staging buffer goes back)
 }
 
 int ry_conv2d(ry_ctx* ctx, const float* x, int B, int H, int Wd, int Cin, const float* Wt, const float* bias, const float* bn,
@@ -945,7 +984,7 @@ int ry_conv2d_dilated(ry_ctx* ctx, const float* x, int B, int H, int Wd, int Cin
     }
     RT_TRY(rt::d2h(y, lp.out, out_elems * sizeof(float), ctx->stream));
     RT_TRY(rt::stream_sync(ctx->stream));
-    return RY_OK;
+    return finish_filter_build(ctx);            // (filter build mode `device`: the staging buffer goes back)
 }
 
 }  // extern "C"

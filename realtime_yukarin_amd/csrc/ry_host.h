@@ -111,8 +111,12 @@ static int fail(int code, const char* fmt, ...) {
 
 // ------------------------------------------------------------------------------------------------
 struct ry_net;
+struct FilterStage;
 struct ry_ctx {
     std::vector<ry_net*> nets;
+    // filter build mode `device`: the raw filter of the layer being prepared (grown and reused across the layers of a predictor, dropped when
+    // ry_net_create returns); defined below DevBuf
+    std::unique_ptr<FilterStage> stage;
     int device = 0;
     ry_stream_t stream = nullptr;
     rt::Event t0, t1;
@@ -131,11 +135,15 @@ struct ry_ctx {
 // arena of device buffers freed together
 struct Arena {
     std::vector<void*> bufs;
+    // what building the filters in this arena took (ry_net_build_stats; arena_bytes: every allocation made here, never lowered)
+    ry_build_stats stats = {0, 0, 0, 0, 0};
+    bool lazy_pending = false;           // a layout in `lazy` was launched on the context stream and nothing has waited for it yet (build_plan does)
     int alloc(float** p, size_t nfloats) {
         void* q = nullptr;
         rt::err_t e = rt::dmalloc(&q, nfloats * sizeof(float));
         if (e != 0) return fail(RY_ENOMEM, "device allocation of %zu bytes failed: %s", nfloats * sizeof(float), rt::err_str(e));
         bufs.push_back(q);
+        stats.arena_bytes += (unsigned long long)(nfloats * sizeof(float));
         *p = (float*)q;
         return RY_OK;
     }
@@ -182,11 +190,19 @@ struct DevBufBase {
         if (raw) RT_TRY(rt::dmemset(raw, 0xff, (size_t)cap * elem, st));
         return RY_OK;
     }
+    void drop() {                                                   // give the memory back (the caller has waited for the work that used it)
+        if (raw) rt::dfree(raw);
+        raw = nullptr; cap = 0;
+    }
 };
 template <typename T>
 struct DevBuf : DevBufBase {
     explicit DevBuf(DevBufList& owner) : DevBufBase(owner, sizeof(T)) {}
     T* ptr() const { return (T*)raw; }
+};
+struct FilterStage {
+    DevBufList list;
+    DevBuf<float> buf{list};
 };
 
 // ------------------------------------------------------------------------------------------------

@@ -141,15 +141,22 @@ int ry_net_create(ry_ctx* ctx, const ry_net_desc* desc, const float* weights, si
     RT_TRY(rt::stream_create(&net->stream));
     RT_TRY(rt::event_create_fast(&net->done));
     net->has_done = true;
+    if (on_device) net->weights->stats.bytes_downloaded += (unsigned long long)(n_floats * sizeof(float));
     size_t off = 0;
+    int rc = RY_OK;
     for (Layer& l : net->layers) {
         const size_t nw = (size_t)l.cin() * l.cout * ipow((size_t)l.k, desc->ndim);
         const float* W = blob + off; off += nw;
         const float* b = blob + off; off += l.cout;
         const float* bn = nullptr;
         if (l.bn) { bn = blob + off; off += 4 * (size_t)l.cout; }
-        RY_TRY(prepare_layer(ctx, *net->weights, l, desc->ndim, net->desc.bn_eps, W, b, bn));
+        rc = prepare_layer(ctx, *net->weights, l, desc->ndim, net->desc.bn_eps, W, b, bn);
+        if (rc != RY_OK) break;
     }
+    // filter build mode `device`: the layout kernels and the copies of the raw filters are queued on the context stream -- one wait for all of them
+    // (the blob is the caller's, or `host` above), then the staging buffer goes back; after a refusal too
+    if (rc != RY_OK) { const std::string why = g_ry_err; finish_filter_build(ctx); g_ry_err = why; return rc; }
+    RY_TRY(finish_filter_build(ctx));
     ctx->nets.push_back(net.get());
     *out = net.release();
     return RY_OK;
@@ -351,6 +358,63 @@ int ry_net_debug_plan(ry_net* net, int batch, int frames, int window, int discar
         }
     }
     *n = 16;
+    return RY_OK;
+}
+
+int ry_set_filter_build(int mode) { return set_filter_build(mode); }
+
+int ry_net_build_stats(ry_net* net, ry_build_stats* out) {
+    if (!net || !out) return fail(RY_EINVAL, "null argument");
+    *out = net->weights->stats;
+    return RY_OK;
+}
+
+// tests: one filter layout of a layer as it lies on the card.  Every refusal comes before anything is built or written.
+int ry_net_debug_filters(ry_net* net, int layer, int kind, float* out, size_t out_floats, size_t* n_floats) {
+    if (!net || !n_floats) return fail(RY_EINVAL, "null argument");
+    if (layer < 0 || layer >= (int)net->layers.size()) return fail(RY_EINVAL, "layer must be 0 .. 15 (got %d)", layer);
+    if (kind < RY_LAYOUT_W1D || kind > RY_LAYOUT_WWIN) return fail(RY_EINVAL, "kind must be 0 (w1d), 1 (w1os), 2 (wig), 3 (wdir), 4 (w2os) or 5 (wwin); got %d", kind);
+    const Layer& l = net->layers[layer];
+    const float* src = kind == RY_LAYOUT_W1D ? l.w1d : kind == RY_LAYOUT_W1OS ? l.w1os : kind == RY_LAYOUT_WIG ? l.wig : kind == RY_LAYOUT_WDIR ? l.wdir
+                     : kind == RY_LAYOUT_W2OS ? l.w2os : nullptr;
+    if (kind == RY_LAYOUT_WWIN ? !(l.wdir && wino_eligible(l, net->desc.ndim)) : !src) return fail(RY_ESTATE, "%s has no layout of kind %d", l.name, kind);
+    const size_t n = filter_layout_floats(l, kind);
+    *n_floats = n;
+    if (!out || out_floats < n) return fail(RY_EINVAL, "%s: the layout has %zu floats, the buffer holds %zu", l.name, n, out ? out_floats : (size_t)0);
+    RT_TRY(rt::set_device(net->ctx->device));
+    if (kind == RY_LAYOUT_WWIN) RY_TRY(net_wwin(net, layer, &src));
+    RT_TRY(rt::stream_sync(net->stream));
+    RT_TRY(rt::d2h(out, src, n * sizeof(float), net->ctx->stream));
+    RT_TRY(rt::stream_sync(net->ctx->stream));
+    return RY_OK;
+}
+
+// tests: the same for ONE layer of any shape prepare_layer takes, without a predictor around it -- the layer's filters are built in an arena of the
+// call, in the mode in force, from the raw filter W (host), and one layout comes back.  cin_b > 0: two skip sources.  want_os2: the output-stationary
+// layout whatever the filter's size (as ry_conv2d's path 7).
+int ry_debug_layer_filters(ry_ctx* ctx, int ndim, int cin_a, int cin_b, int cout, int k, int stride, int pad, int transposed, int want_os2,
+                           const float* W, int kind, float* out, size_t out_floats, size_t* n_floats) {
+    if (!ctx || !W || !n_floats) return fail(RY_EINVAL, "null argument");
+    if ((ndim != 1 && ndim != 2) || cin_a < 1 || cin_b < 0 || cout < 1 || k < 1 || k > 4 || stride < 1 || pad < 0) return fail(RY_EINVAL, "bad layer shape");
+    if (transposed && !(k == 4 && stride == 2 && pad == 1)) return fail(RY_EINVAL, "transposed layers are k4 s2 p1 only");
+    if (kind < RY_LAYOUT_W1D || kind > RY_LAYOUT_WWIN) return fail(RY_EINVAL, "kind must be 0 .. 5 (got %d)", kind);
+    RT_TRY(rt::set_device(ctx->device));
+    Layer l;
+    snprintf(l.name, sizeof l.name, "layer");
+    l.deconv = transposed != 0; l.k = k; l.stride = stride; l.pad = pad; l.cin_a = cin_a; l.cin_b = cin_b; l.cout = cout;
+    Arena arena;
+    int rc = prepare_layer(ctx, arena, l, ndim, 2e-5f, W, nullptr, nullptr, want_os2 != 0);
+    if (rc != RY_OK) { const std::string why = g_ry_err; finish_filter_build(ctx); g_ry_err = why; return rc; }
+    RY_TRY(finish_filter_build(ctx));
+    const float* src = kind == RY_LAYOUT_W1D ? l.w1d : kind == RY_LAYOUT_W1OS ? l.w1os : kind == RY_LAYOUT_WIG ? l.wig : kind == RY_LAYOUT_WDIR ? l.wdir
+                     : kind == RY_LAYOUT_W2OS ? l.w2os : nullptr;
+    if (kind == RY_LAYOUT_WWIN ? !(l.wdir && wino_eligible(l, ndim)) : !src) return fail(RY_ESTATE, "this layer has no layout of kind %d", kind);
+    const size_t n = filter_layout_floats(l, kind);
+    *n_floats = n;
+    if (!out || out_floats < n) return fail(RY_EINVAL, "the layout has %zu floats, the buffer holds %zu", n, out ? out_floats : (size_t)0);
+    if (kind == RY_LAYOUT_WWIN) { float* w = nullptr; RY_TRY(upload_wwin(ctx, arena, l, &w)); src = w; }
+    RT_TRY(rt::d2h(out, src, n * sizeof(float), ctx->stream));
+    RT_TRY(rt::stream_sync(ctx->stream));
     return RY_OK;
 }
 

@@ -256,14 +256,78 @@ static void relayout_wino(const Layer& l, const std::vector<float>& wd, std::vec
 
 // The Winograd filters of a layer, uploaded into `arena` (2.25 x the floats of its filters): read the direct layout back, transform.  Never called under
 // stream capture (plans are built before their first run).
+// Filter build mode `device`: one launch on the context stream from the direct layout where it lies -- no download, no host vector, no wait here (a
+// predictor's plan waits once for what its layers launched, build_plan; the single operator runs on the same stream).
+static int g_filter_build = 0;                         // ry_set_filter_build / RY_FILTER_BUILD: 0 host, 1 device
+static int g_poison = 0;                               // RY_POISON (below)
+int filter_build_mode() { return g_filter_build; }
+int set_filter_build(int mode) {
+    if (mode != 0 && mode != 1) return fail(RY_EINVAL, "filter build mode must be 0 (host) or 1 (device), got %d", mode);
+    g_filter_build = mode;
+    return RY_OK;
+}
+
+// floats of one layout of a layer (the sizes the host functions above give their vectors)
+size_t filter_layout_floats(const Layer& l, int kind) {
+    const TapTable t = make_taps(l);
+    const size_t C = (size_t)l.cin(), N = (size_t)l.cout;
+    if (kind == RY_LAYOUT_W1D || kind == RY_LAYOUT_W1OS) return C * N * 4;
+    if (kind == RY_LAYOUT_WWIN) return (size_t)(l.deconv ? 4 : 1) * N * (l.deconv ? C / 8 : (C / 16) * 8) * 72;
+    return (size_t)t.nphases * t.ntaps * C * N;
+}
+
+// an upload into the arena, counted (ry_net_build_stats)
+static int upload_counted(Arena& arena, ry_ctx* ctx, const std::vector<float>& h, float** d) {
+    arena.stats.bytes_uploaded += (unsigned long long)(h.size() * sizeof(float));
+    return upload(arena, ctx, h, d);
+}
+// ... of a layout that a host loop wrote
+static int upload_layout(Arena& arena, ry_ctx* ctx, const std::vector<float>& h, float** d) {
+    arena.stats.host_relayout_floats += (unsigned long long)h.size();
+    return upload_counted(arena, ctx, h, d);
+}
+
+// device mode: an allocation of the layout's size in the arena (RY_POISON: NaN patterns first, so a float the kernel leaves out shows), one launch
+static int build_layout(ry_ctx* ctx, Arena& arena, const Layer& l, int kind, const float* src, float** out) {
+    const size_t n = filter_layout_floats(l, kind);
+    RY_TRY(arena.alloc(out, n));
+    if (g_poison) RT_TRY(rt::dmemset(*out, 0xFF, n * sizeof(float), ctx->stream));
+    RY_TRY(kind == RY_LAYOUT_WWIN ? launch_relayout_wino(ctx, l, src, *out) : launch_relayout(ctx, l, kind, src, *out));
+    arena.stats.layout_launches += 1;
+    return RY_OK;
+}
+
 int upload_wwin(ry_ctx* ctx, Arena& arena, const Layer& l, float** out) {
     if (!l.wdir || !wino_eligible(l, 2)) return fail(RY_ESTATE, "%s: no Winograd form of this layer", l.name);
+    if (g_filter_build == 1) return build_layout(ctx, arena, l, RY_LAYOUT_WWIN, l.wdir, out);
     const TapTable t = make_taps(l);
     std::vector<float> wd((size_t)t.nphases * t.ntaps * l.cin() * l.cout), w;
     RT_TRY(rt::d2h(wd.data(), l.wdir, wd.size() * sizeof(float), ctx->stream));
     RT_TRY(rt::stream_sync(ctx->stream));
+    arena.stats.bytes_downloaded += (unsigned long long)(wd.size() * sizeof(float));
     relayout_wino(l, wd, w);
-    return upload(arena, ctx, w, out);
+    return upload_layout(arena, ctx, w, out);
+}
+
+// device mode: the raw filter of a layer in the context's staging buffer (grown when a layer needs more, reused otherwise; the copy is queued behind the
+// kernels that read the previous layer's filter).  The caller's array must stay until finish_filter_build has waited.
+static int stage_filter(ry_ctx* ctx, Arena& arena, const float* W, size_t n, const float** dev) {
+    if (!ctx->stage) ctx->stage.reset(new FilterStage());
+    DevBuf<float>& st = ctx->stage->buf;
+    RY_TRY(st.reserve(ctx, (long long)n));
+    if (g_poison) RY_TRY(st.poison(ctx->stream));
+    RT_TRY(rt::h2d(st.ptr(), W, n * sizeof(float), ctx->stream));
+    arena.stats.bytes_uploaded += (unsigned long long)(n * sizeof(float));
+    *dev = st.ptr();
+    return RY_OK;
+}
+
+int finish_filter_build(ry_ctx* ctx) {
+    if (!ctx->stage) return RY_OK;
+    const rt::err_t e = rt::stream_sync(ctx->stream);
+    ctx->stage->buf.drop();
+    if (e != 0) return fail(RY_EHIP, "waiting for the filter layout kernels failed: %s", rt::err_str(e));
+    return RY_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -279,30 +343,42 @@ int prepare_layer(ry_ctx* ctx, Arena& arena, Layer& l, int ndim, float eps, cons
     fold_scale_shift(l, b, bn, eps, sc, sh);
     // scale/shift padded to a multiple of 4 floats (16-byte epilogue loads)
     sc.resize((sc.size() + 3) / 4 * 4, 1.f); sh.resize((sh.size() + 3) / 4 * 4, 0.f);
-    RY_TRY(upload(arena, ctx, sc, &l.scale));
-    RY_TRY(upload(arena, ctx, sh, &l.shift));
-    if (ndim == 1) {
-        if (l.k > 4) return fail(RY_EINVAL, "%s: 1-D kernels wider than 4 taps are not supported", l.name);
-        relayout_1d(l, W, w);
-        RY_TRY(upload(arena, ctx, w, &l.w1d));
-        relayout_1d_os(l, W, w);
-        RY_TRY(upload(arena, ctx, w, &l.w1os));
-    } else {
-        if (l.k * l.k > 16) return fail(RY_EINVAL, "%s: 2-D kernels larger than 4x4 are not supported", l.name);
-        if (igemm_eligible(l)) { relayout_igemm(l, W, w); RY_TRY(upload(arena, ctx, w, &l.wig)); }
-        if (c2d_os_eligible(l) && (want_os2 || (l.wig && (size_t)l.cin() * l.cout * l.k * l.k >= g_os2_min_filter))) {
-            relayout_c2d_os(l, W, w); RY_TRY(upload(arena, ctx, w, &l.w2os));
+    RY_TRY(upload_counted(arena, ctx, sc, &l.scale));
+    RY_TRY(upload_counted(arena, ctx, sh, &l.shift));
+    if (ndim == 1 && l.k > 4) return fail(RY_EINVAL, "%s: 1-D kernels wider than 4 taps are not supported", l.name);
+    if (ndim != 1 && l.k * l.k > 16) return fail(RY_EINVAL, "%s: 2-D kernels larger than 4x4 are not supported", l.name);
+    const bool os2 = ndim != 1 && c2d_os_eligible(l) && (want_os2 || (igemm_eligible(l) && (size_t)l.cin() * l.cout * l.k * l.k >= g_os2_min_filter));
+    if (g_filter_build == 1) {
+        // one upload of the raw filter, then a kernel per layout (relayout_kernels.h): the same allocations in the same order, the same bits
+        const float* dW = nullptr;
+        RY_TRY(stage_filter(ctx, arena, W, (size_t)l.cin() * l.cout * ipow((size_t)l.k, ndim), &dW));
+        if (ndim == 1) {
+            RY_TRY(build_layout(ctx, arena, l, RY_LAYOUT_W1D, dW, &l.w1d));
+            RY_TRY(build_layout(ctx, arena, l, RY_LAYOUT_W1OS, dW, &l.w1os));
+        } else {
+            if (igemm_eligible(l)) RY_TRY(build_layout(ctx, arena, l, RY_LAYOUT_WIG, dW, &l.wig));
+            if (os2) RY_TRY(build_layout(ctx, arena, l, RY_LAYOUT_W2OS, dW, &l.w2os));
+            RY_TRY(build_layout(ctx, arena, l, RY_LAYOUT_WDIR, dW, &l.wdir));
         }
+        return RY_OK;
+    }
+    if (ndim == 1) {
+        relayout_1d(l, W, w);
+        RY_TRY(upload_layout(arena, ctx, w, &l.w1d));
+        relayout_1d_os(l, W, w);
+        RY_TRY(upload_layout(arena, ctx, w, &l.w1os));
+    } else {
+        if (igemm_eligible(l)) { relayout_igemm(l, W, w); RY_TRY(upload_layout(arena, ctx, w, &l.wig)); }
+        if (os2) { relayout_c2d_os(l, W, w); RY_TRY(upload_layout(arena, ctx, w, &l.w2os)); }
         relayout_direct(l, W, w);
-        RY_TRY(upload(arena, ctx, w, &l.wdir));
+        RY_TRY(upload_layout(arena, ctx, w, &l.wdir));
     }
     return RY_OK;
 }
 
 // RY_POISON=1 (diagnostics): fresh activation buffers, split-K slabs and the outputs of the single operators are filled with NaN patterns, so
 // that a kernel that reads a row / pixel its producer never wrote, or a launch that leaves an output element unwritten, shows up as NaN in the
-// result instead of depending on what the allocator handed out
-static int g_poison = 0;
+// result instead of depending on what the allocator handed out (g_poison: above, the filter layouts built on the card start the same way)
 int poison_fill(ry_ctx* ctx, float* p, size_t nfloats) {
     if (!g_poison || !p || !nfloats) return RY_OK;
     RT_TRY(rt::dmemset(p, 0xFF, nfloats * sizeof(float), ctx->stream));
@@ -667,9 +743,24 @@ static int ensure_wwin(ry_net* net, int i, const float** out) {
         float* d = nullptr;
         RY_TRY(upload_wwin(net->ctx, *net->weights, net->layers[i], &d));
         it = lazy.emplace(i, d).first;
+        if (g_filter_build == 1) net->weights->lazy_pending = true;       // launched on the context stream, not waited for
     }
     *out = it->second;
     return RY_OK;
+}
+
+// Layouts in `lazy` that were launched and not waited for: the predictor streams (this handle's and its clones') do not follow the context stream, so
+// whoever is about to hand such a layout to them waits once -- a launch plan after its layer loop, however many layers it built
+static int wait_lazy(ry_net* net) {
+    if (!net->weights->lazy_pending) return RY_OK;
+    RT_TRY(rt::stream_sync(net->ctx->stream));
+    net->weights->lazy_pending = false;
+    return RY_OK;
+}
+
+int net_wwin(ry_net* net, int layer, const float** out) {
+    RY_TRY(ensure_wwin(net, layer, out));
+    return wait_lazy(net);
 }
 
 // The 2-D pixel tiles a stage-2 GEMM layer's launch walks over its Mh x Mw grid: th rows x tw columns (the launchers take them from here; the
@@ -910,6 +1001,7 @@ int build_plan(ry_net* net, Plan& P) {
             if (lp.path == PATH_WINO) RY_TRY(ensure_wwin(net, i, &lp.wwin));
         }
     }
+    RY_TRY(wait_lazy(net));
     // bf16 mode: which copies of each activation are needed (fp32 for fp32 consumers and the caller, bf16 for bf16 consumers)
     if (nd == 2 && net->dtype != 0) {
         const bool x3 = net->dtype == 2;
@@ -989,6 +1081,13 @@ int read_plan_env() {
 }
 
 int read_env_switches() {
+    // RY_FILTER_BUILD=host|device: the filter build mode.  Unlike the switches below it also has a setter (ry_set_filter_build), so an absent variable
+    // leaves the mode alone; a value that is neither is refused before anything else is touched
+    if (const char* e = getenv("RY_FILTER_BUILD")) {
+        if (!strcmp(e, "host")) g_filter_build = 0;
+        else if (!strcmp(e, "device")) g_filter_build = 1;
+        else return fail(RY_EINVAL, "RY_FILTER_BUILD: expected host or device, got '%s'", e);
+    }
     // (re-read by ry_debug_reload_env: an absent variable means the defaults)
     g_autotune = 0; g_autotune_reps = 3; g_autotune_max = 0; g_autotune_pick = -1;
     if (const char* e = getenv("RY_AUTOTUNE")) {                                        // "1[:reps[:max[:pick]]]"
@@ -1055,10 +1154,12 @@ int prepare_bf16(ry_ctx* ctx, Arena& arena, Layer& l, int dtype) {
     std::vector<float> w32((size_t)t.nphases * l.cout * t.ntaps * l.cin());
     RT_TRY(rt::d2h(w32.data(), l.wig, w32.size() * sizeof(float), ctx->stream));
     RT_TRY(rt::stream_sync(ctx->stream));
+    arena.stats.bytes_downloaded += (unsigned long long)(w32.size() * sizeof(float));
     std::vector<unsigned short> w16;
     (dtype == 2 ? build_wigx3 : build_wig16)(l, w32, w16);
     float* d = nullptr;
     RY_TRY(arena.alloc(&d, (w16.size() + 1) / 2));
+    arena.stats.bytes_uploaded += (unsigned long long)(w16.size() * sizeof(unsigned short));
     RT_TRY(rt::h2d(d, w16.data(), w16.size() * sizeof(unsigned short), ctx->stream));
     RT_TRY(rt::stream_sync(ctx->stream));
     dst = d;

@@ -62,6 +62,15 @@ bool wino_eligible(const Layer& l, int ndim);
 int prepare_layer(ry_ctx* ctx, Arena& arena, Layer& l, int ndim, float eps, const float* W, const float* b, const float* bn, bool want_os2 = false);
 int prepare_bf16(ry_ctx* ctx, Arena& arena, Layer& l, int dtype);
 int upload_wwin(ry_ctx* ctx, Arena& arena, const Layer& l, float** out);
+// filter build mode (ry_set_filter_build / RY_FILTER_BUILD): 0 host loops + one upload per layout, 1 one upload of the raw filter + layout kernels
+int filter_build_mode();
+int set_filter_build(int mode);
+int finish_filter_build(ry_ctx* ctx);                         // device mode: wait for the layout kernels, give the staging buffer back
+size_t filter_layout_floats(const Layer& l, int kind);        // floats of layout `kind` (RY_LAYOUT_*) of a layer that has it
+int net_wwin(ry_net* net, int layer, const float** out);      // the Winograd filters of a predictor layer, built if need be and waited for
+// the layout kernels of relayout_kernels.h on ctx->stream (ry_exec.cpp): the raw filter `W` on the card -> layout `kind` in `out`; wdir -> wwin
+int launch_relayout(ry_ctx* ctx, const Layer& l, int kind, const float* W, float* out);
+int launch_relayout_wino(ry_ctx* ctx, const Layer& l, const float* wdir, float* out);
 int alloc_ztail(ry_ctx* ctx, Arena& arena, float** p, size_t nfloats);
 int poison_fill(ry_ctx* ctx, float* p, size_t nfloats);       // RY_POISON: NaN patterns over a buffer a launch is about to write (else nothing)
 void tile_dims(int tile, int* bm, int* bn);

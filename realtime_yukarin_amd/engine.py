@@ -88,6 +88,24 @@ class Context(object):
                                                    ctypes.cast(ctypes.c_void_p(int(mask_ptr or 0)), ctypes.POINTER(ctypes.c_ubyte)),
                                                    _lib._fptr(int(dst_ptr)), int(n_out), ctypes.c_void_p(stream or 0)))
 
+    def debug_layer_filters(self, W: numpy.ndarray, kind: str, cin_b: int = 0, stride: int = 1, pad: int = 0, transposed: bool = False,
+                            want_os2: bool = False) -> numpy.ndarray:
+        """Tests: layout `kind` ('w1d', 'w1os', 'wig', 'wdir', 'w2os', 'wwin') of ONE layer with the raw Chainer filter W -- (Cout, Cin, k[, k]), transposed
+        (Cin, Cout, 4[, 4]); the last cin_b input channels are the second skip source -- built in the filter build mode in force
+        (`ry_debug_layer_filters`), flat float32.  Raises `Ry355Error` when the layer has no such layout."""
+        W = numpy.ascontiguousarray(W, dtype=numpy.float32)
+        ndim = W.ndim - 2
+        cin, cout = (W.shape[0], W.shape[1]) if transposed else (W.shape[1], W.shape[0])
+        args = [self.handle, ndim, cin - int(cin_b), int(cin_b), cout, W.shape[2], int(stride), int(pad), int(bool(transposed)), int(bool(want_os2)),
+                _lib._fptr(W), _lib.FILTER_KINDS[kind]]
+        n = ctypes.c_size_t(0)
+        rc = self.lib.dll.ry_debug_layer_filters(*(args + [None, 0, ctypes.byref(n)]))
+        if n.value == 0:
+            self.lib.check(rc)
+        out = numpy.empty(n.value, dtype=numpy.float32)
+        self.lib.check(self.lib.dll.ry_debug_layer_filters(*(args + [_lib._fptr(out), out.size, ctypes.byref(n)])))
+        return out
+
     def mc2sp(self, mc, mtx, floor: float = 0.0):
         """`decode_spectrogram` on the device: exp(mc (N, M) @ mtx (M, F)) + floor."""
         mc = numpy.ascontiguousarray(mc, dtype=numpy.float32)
@@ -497,6 +515,17 @@ def get_context(device: int = 0, lib: Optional[_lib.Ry355Lib] = None) -> Context
     return ctx
 
 
+def set_filter_build(mode: str, lib: Optional[_lib.Ry355Lib] = None):
+    """Where the filter layouts of the predictors created from now on are built (`ry_set_filter_build`, process-wide): 'host' (the default: host
+    loops, one upload per layout, the Winograd filters by way of a download) or 'device' (one upload of each raw filter, layout kernels on the
+    card; the same bits).  The environment variable RY_FILTER_BUILD=host|device sets the same switch when a context is created
+    or `Context.reload_env` runs; the compat shims follow the variable only.  lib: another build of the library (tests: the emulator)."""
+    if mode not in _lib.FILTER_BUILD:
+        raise ValueError("filter build mode must be 'host' or 'device', got %r" % (mode,))
+    lib = lib if lib is not None else _lib.default_lib()
+    lib.check(lib.dll.ry_set_filter_build(_lib.FILTER_BUILD[mode]))
+
+
 class Net(object):
     """A predictor resident on one GPU.  `blob` = flat float32 weights (netspec K-list order), either a
     host ndarray or (ptr, n) of a device buffer (e.g. the tensor an RCCL broadcast filled)."""
@@ -604,6 +633,26 @@ class Net(object):
         self.ctx.lib.check(self.ctx.lib.dll.ry_net_debug_plan(self.handle, int(batch), int(frames), int(bool(window)), int(discard[0]), int(discard[1]),
                                                              recs, 16, ctypes.byref(n)))
         return [{f: (tuple(getattr(recs[i], f)) if f == 'os2' else int(getattr(recs[i], f))) for f in _lib.RyPlanRecord.FIELDS} for i in range(n.value)]
+
+    def build_stats(self) -> dict:
+        """What building this predictor's filters has taken so far (`ry_net_build_stats`): bytes_uploaded, bytes_downloaded, layout_launches,
+        host_relayout_floats, arena_bytes.  The clones of a predictor share the counters; lazy Winograd builds go on counting."""
+        st = _lib.RyBuildStats()
+        self.ctx.lib.check(self.ctx.lib.dll.ry_net_build_stats(self.handle, ctypes.byref(st)))
+        return {f: int(getattr(st, f)) for f in _lib.RyBuildStats.FIELDS}
+
+    def debug_filters(self, layer: int, kind: str) -> numpy.ndarray:
+        """Tests: one filter layout of layer 0 .. 15 as it lies on the card (`ry_net_debug_filters`), flat float32.  kind: 'w1d', 'w1os' (stage 1),
+        'wig', 'wdir', 'w2os', 'wwin' (stage 2; 'wwin' is built on demand in the filter build mode in force).  Raises `Ry355Error` when the layer has
+        no such layout."""
+        lib = self.ctx.lib
+        n = ctypes.c_size_t(0)
+        rc = lib.dll.ry_net_debug_filters(self.handle, int(layer), _lib.FILTER_KINDS[kind], None, 0, ctypes.byref(n))
+        if n.value == 0:                                     # (the size query itself is refused with the size set: anything else is an error)
+            lib.check(rc)
+        out = numpy.empty(n.value, dtype=numpy.float32)
+        lib.check(lib.dll.ry_net_debug_filters(self.handle, int(layer), _lib.FILTER_KINDS[kind], _lib._fptr(out), out.size, ctypes.byref(n)))
+        return out
 
     def profile(self, batch: int, frames: int, reps: int = 5, window: bool = False) -> List[dict]:
         """Per-launch timings of the raw forward at `frames` padded rows, or (window=True) of the convert wrapper on one window
