@@ -638,6 +638,17 @@ int ry_synth_bound(ry_synth* synth, int n_frames, int final);
 int ry_synth_push(ry_synth* synth, const double* f0, const float* sp, const float* ap, int n_frames, int bins, int on_device,
                   double* y, int y_capacity, int* n_out);
 int ry_synth_flush(ry_synth* synth, double* y, int y_capacity, int* n_out);
+/* The same two calls with the samples left on the card: y_dev is a DEVICE pointer of the caller's with room for y_capacity samples (the rule of
+ * ry_synth_bound), and the overlap-add kernel writes the *n_out emitted samples straight to y_dev[0 .. *n_out) -- one 8-byte store per sample,
+ * so any double-aligned address will do, e.g. y_dev + k behind the k samples of the push before, and no byte outside that range is written.
+ * Nothing is staged, copied or brought down, and the call does not wait for that launch: it is enqueued on the context stream, where a reader
+ * (ry_outgate_push with on_device = 1) finds the samples in order.  *n_out is known on the host when the call returns.  The bits are those of
+ * ry_synth_push / ry_synth_flush; so are the refusals, in the same order (a null y_dev among the bad output arguments), each before anything is
+ * launched or any carried state changes.  ry_synth_flush_dev resets the stream in stream order, without the wait of ry_synth_reset.
+ * DESIGN.md section 24, INTEGRATION.md section 22. */
+int ry_synth_push_dev(ry_synth* synth, const double* f0, const float* sp, const float* ap, int n_frames, int bins, int on_device,
+                      double* y_dev, long long y_capacity, long long* n_out);
+int ry_synth_flush_dev(ry_synth* synth, double* y_dev, long long y_capacity, long long* n_out);
 int ry_synth_reset(ry_synth* synth);
 /* One shot, many waves: wave b has n_frames[b] frames; f0 (HOST), sp and ap (rows on the host, or with on_device on the card, read where
  * they are) hold the waves back to back.  y receives the waves back to back, wave b at y[sample_offsets[b]] with
@@ -680,6 +691,12 @@ int ry_synth_bank_bound(ry_synth_bank* bank, int stream, int n_frames, int final
  * the bounds, more than 2^22 frames or 2^30 pulse entries in all. */
 int ry_synth_bank_push(ry_synth_bank* bank, const double* f0, const float* sp, const float* ap, const int* n_frames, const int* final, int bins,
                        int on_device, double* y, long long y_capacity, long long* sample_offsets);
+/* The same call with the samples left on the card: y_dev is a DEVICE pointer of the caller's, stream b's samples are written at
+ * y_dev[sample_offsets[b]], back to back -- the layout ry_outgate_bank_push (on_device = 1) reads.  sample_offsets is on the HOST and valid when
+ * the call returns.  The records of the retired pulses still come down and the call still ends with its second wait (the next push needs them):
+ * against ry_synth_bank_push one device-to-host copy fewer, the same launches.  The bits, the refusals and their order: ry_synth_bank_push. */
+int ry_synth_bank_push_dev(ry_synth_bank* bank, const double* f0, const float* sp, const float* ap, const int* n_frames, const int* final, int bins,
+                           int on_device, double* y_dev, long long y_capacity, long long* sample_offsets);
 /* forgets the signal of `stream` (-1: of every stream) */
 int ry_synth_bank_reset(ry_synth_bank* bank, int stream);
 /* tests: the pulses the last push found for `stream` (as ry_synth_debug_pulses; read from the card here; RY_ESTATE after a poison) */
@@ -821,6 +838,9 @@ int ry_outgate_push(ry_outgate* gate, const double* samples, int n, int on_devic
 int ry_outgate_held(ry_outgate* gate);
 /* tests: out[5] = stream waits, kernel launches, host-to-device copies, device-to-host copies, sample bytes brought to the host by the last push */
 int ry_outgate_debug_counts(ry_outgate* gate, long long* out);
+/* tests: the bytes of the last push's one upload: the stream table and the chunk map, and the new samples when they came from the host
+ * (on_device = 0) -- with on_device = 1 it does not depend on n (negative: error) */
+long long ry_outgate_debug_upload_bytes(ry_outgate* gate);
 /* tests: NaN bit patterns in every scratch buffer and in every part of the two fragment buffers that holds no carried sample */
 int ry_outgate_debug_poison(ry_outgate* gate);
 
@@ -842,6 +862,7 @@ int ry_outgate_bank_push(ry_outgate_bank* bank, const double* samples, const lon
                          long long* out_offsets, int* silent, double* mean_db);
 int ry_outgate_bank_held(ry_outgate_bank* bank, int stream);
 int ry_outgate_bank_debug_counts(ry_outgate_bank* bank, long long* out);
+long long ry_outgate_bank_debug_upload_bytes(ry_outgate_bank* bank);
 int ry_outgate_bank_debug_poison(ry_outgate_bank* bank);
 
 #ifdef __cplusplus

@@ -81,6 +81,7 @@ ABI_SYMBOLS = (
     'ry_outgate_create', 'ry_outgate_destroy', 'ry_outgate_reset', 'ry_outgate_push', 'ry_outgate_held', 'ry_outgate_debug_counts', 'ry_outgate_debug_poison',
     'ry_outgate_bank_create', 'ry_outgate_bank_destroy', 'ry_outgate_bank_reset', 'ry_outgate_bank_push', 'ry_outgate_bank_held',
     'ry_outgate_bank_debug_counts', 'ry_outgate_bank_debug_poison',
+    'ry_synth_push_dev', 'ry_synth_flush_dev', 'ry_synth_bank_push_dev', 'ry_outgate_debug_upload_bytes', 'ry_outgate_bank_debug_upload_bytes',
     'ry_analysis_upload_waves', 'ry_analysis_ingest_tracks', 'ry_analysis_track_buffers',
     'ry_set_filter_build', 'ry_net_build_stats', 'ry_net_debug_filters', 'ry_debug_layer_filters',
 )
@@ -260,6 +261,8 @@ class Ry355Lib(object):
         d.ry_synth_push.argtypes = [_VP, _DP, _FP, _FP, _CI, _CI, _CI, _DP, _CI, _IP]
         d.ry_synth_flush.argtypes = [_VP, _DP, _CI, _IP]
         d.ry_synth_reset.argtypes = [_VP]
+        d.ry_synth_push_dev.argtypes = [_VP, _DP, _FP, _FP, _CI, _CI, _CI, _DP, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
+        d.ry_synth_flush_dev.argtypes = [_VP, _DP, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
         d.ry_synth_debug_pulses.argtypes = [_VP, ctypes.POINTER(ctypes.c_longlong), _DP, _IP, _CI, _IP]
         d.ry_synth_debug_poison.argtypes = [_VP]
         d.ry_synth_run_many.argtypes = [_VP, _DP, _FP, _FP, _IP, _CI, _CI, _CI, _DP, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
@@ -269,6 +272,7 @@ class Ry355Lib(object):
         d.ry_synth_bank_destroy.restype = None
         d.ry_synth_bank_bound.argtypes = [_VP, _CI, _CI, _CI]
         d.ry_synth_bank_push.argtypes = [_VP, _DP, _FP, _FP, _IP, _IP, _CI, _CI, _DP, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
+        d.ry_synth_bank_push_dev.argtypes = [_VP, _DP, _FP, _FP, _IP, _IP, _CI, _CI, _DP, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
         d.ry_synth_bank_reset.argtypes = [_VP, _CI]
         d.ry_synth_bank_debug_pulses.argtypes = [_VP, _CI, ctypes.POINTER(ctypes.c_longlong), _DP, _IP, _CI, _IP]
         d.ry_synth_bank_debug_poison.argtypes = [_VP]
@@ -327,6 +331,10 @@ class Ry355Lib(object):
         d.ry_outgate_bank_held.argtypes = [_VP, _CI]
         d.ry_outgate_bank_debug_counts.argtypes = [_VP, _LLP]
         d.ry_outgate_bank_debug_poison.argtypes = [_VP]
+        d.ry_outgate_debug_upload_bytes.argtypes = [_VP]
+        d.ry_outgate_debug_upload_bytes.restype = ctypes.c_longlong
+        d.ry_outgate_bank_debug_upload_bytes.argtypes = [_VP]
+        d.ry_outgate_bank_debug_upload_bytes.restype = ctypes.c_longlong
         d.ry_analysis_debug_d4c.argtypes = [_VP, ctypes.POINTER(_LL), _DP, _CI, _IP]
         d.ry_net_profile_window.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RyKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         d.ry_net_debug_activation.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]

@@ -39,6 +39,7 @@ struct ry_outgate_bank {
     std::vector<int> stream_of;
     std::vector<OgRecord> rec;
     long long counts[5] = {0, 0, 0, 0, 0};           // of the last push: stream waits, launches, uploads, downloads, sample bytes brought down
+    long long up_bytes = 0;                          // of the last push: bytes of its one upload (the tables, and the samples when they came from the host)
     DevBuf<double>& frag(int i) { return i ? frag1 : frag0; }
 };
 
@@ -89,6 +90,7 @@ int og_push(ry_outgate_bank* k, const double* samples, const long long* first, c
     const ry_stream_t st = k->ctx->stream;
     long long* const cnt = k->counts;
     cnt[0] = cnt[1] = cnt[2] = cnt[3] = cnt[4] = 0;
+    k->up_bytes = 0;
     out_offsets[0] = 0;
     for (int b = 0; b < B; ++b) {
         out_offsets[b + 1] = out_offsets[b] + (tab[(size_t)b].emit >= 0 ? chunk : 0);
@@ -131,6 +133,7 @@ int og_push(ry_outgate_bank* k, const double* samples, const long long* first, c
     memcpy(stage, tab.data(), (size_t)B * sizeof(OgStream));
     memcpy(stage + tab_d, k->stream_of.data(), (size_t)B * sizeof(int));
     RT_TRY(rt::h2d(k->d_stage.ptr(), stage, up_d * sizeof(double), st)); ++cnt[2];
+    k->up_bytes = (long long)(up_d * sizeof(double));
     if (k->has_event) { RT_TRY(rt::event_record(k->up_done, st)); k->up_pending = true; }
     const OgStream* d_tab = (const OgStream*)k->d_stage.ptr();
     const int* d_map = (const int*)(k->d_stage.ptr() + tab_d);
@@ -283,6 +286,11 @@ int ry_outgate_bank_debug_counts(ry_outgate_bank* k, long long* out) {
     return RY_OK;
 }
 
+long long ry_outgate_bank_debug_upload_bytes(ry_outgate_bank* k) {
+    if (!k) return fail(RY_EINVAL, "bad argument");
+    return k->up_bytes;
+}
+
 int ry_outgate_bank_debug_poison(ry_outgate_bank* k) {
     RY_TRY(check_handle(k, "output gate bank"));
     return poison(k);
@@ -338,6 +346,11 @@ int ry_outgate_push(ry_outgate* h, const double* samples, int n, int on_device, 
 int ry_outgate_debug_counts(ry_outgate* h, long long* out) {
     if (!h) return fail(RY_EINVAL, "bad argument");
     return ry_outgate_bank_debug_counts(h->k, out);
+}
+
+long long ry_outgate_debug_upload_bytes(ry_outgate* h) {
+    if (!h) return fail(RY_EINVAL, "bad argument");
+    return ry_outgate_bank_debug_upload_bytes(h->k);
 }
 
 int ry_outgate_debug_poison(ry_outgate* h) {

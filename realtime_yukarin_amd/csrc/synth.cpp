@@ -228,8 +228,9 @@ long long may_return(const ry_synth* s, long long pushed, long long scanned, lon
     return std::max(0LL, scan_end(s, m, final, scanned) - done);
 }
 
-// scans what can be scanned, emits what can be emitted.  final: the signal ends with the frames pushed so far.
-int advance(ry_synth* s, bool final, double* y, long long y_capacity, long long* n_out) {
+// scans what can be scanned, emits what can be emitted.  final: the signal ends with the frames pushed so far.  y_on_device: y is a block of
+// the caller's on the card -- synth_overlap writes the samples there and the call returns behind that launch, without download or wait.
+int advance(ry_synth* s, bool final, double* y, long long y_capacity, long long* n_out, bool y_on_device = false) {
     const ry_stream_t st = s->ctx->stream;
     const long long m = s->n_frames;
     const long long k1 = scan_end(s, m, final, s->scanned);
@@ -295,13 +296,16 @@ int advance(ry_synth* s, bool final, double* y, long long y_capacity, long long*
             RY_LAUNCH(synth_pulse, dim3((unsigned)complete), 256, st, pp);
             RT_TRY(rt::last_error());
         }
-        RY_TRY(s->d_y.grow(s->ctx, n_emit));
+        if (!y_on_device) RY_TRY(s->d_y.grow(s->ctx, n_emit));
         SynthOverlapParams op = overlap_params(s);
         op.n_complete = (int)complete; op.s0 = s->done; op.s1 = fin;
+        if (y_on_device) op.y = y;                                 // one 8-byte store per sample: any double-aligned destination, nothing outside [y, y + n_emit)
         RY_LAUNCH(synth_overlap, dim3((unsigned)((n_emit + 255) / 256)), 256, st, op);
         RT_TRY(rt::last_error());
-        RT_TRY(rt::d2h(y, s->d_y.ptr(), (size_t)n_emit * sizeof(double), st));
-        RT_TRY(rt::stream_sync(st));
+        if (!y_on_device) {
+            RT_TRY(rt::d2h(y, s->d_y.ptr(), (size_t)n_emit * sizeof(double), st));
+            RT_TRY(rt::stream_sync(st));
+        }
         s->done = fin;
     }
     *n_out = n_emit;
@@ -317,6 +321,35 @@ int reset_device_state(ry_synth* s) {
     memset(&z, 0, sizeof z);
     RT_TRY(rt::h2d(s->st, &z, sizeof z, s->ctx->stream));
     RT_TRY(rt::stream_sync(s->ctx->stream));
+    return RY_OK;
+}
+
+// ry_synth_push and ry_synth_push_dev: the refusals, the frames, the advance.  y_on_device: see `advance`.
+int push_frames(ry_synth* s, const double* f0, const float* sp, const float* ap, int n_frames, int bins, int on_device,
+                double* y, long long y_capacity, long long* n_out, bool y_on_device) {
+    RY_TRY(check_handle(s, "synthesizer"));
+    if (n_out) *n_out = 0;
+    if (!y || !n_out || y_capacity < 0) return fail(RY_EINVAL, "bad output arguments");
+    if (bins != SYNTH_BINS) return fail(RY_EINVAL, "%d bins per frame, fft_size / 2 + 1 = %d expected", bins, SYNTH_BINS);
+    RY_TRY(check_frames(s, f0, sp, ap, n_frames));
+    const long long m = s->n_frames + n_frames;
+    const long long may = std::max(known_samples(s, m), s->scanned) - s->done;
+    if (may > y_capacity) return fail(RY_EINVAL, "y holds %lld samples, this push may return up to %lld (ry_synth_bound)", y_capacity, may);
+    RY_TRY(append_frames(s, f0, sp, ap, n_frames, on_device, first_needed_frame(s)));
+    return advance(s, false, y, y_capacity, n_out, y_on_device);
+}
+
+// ry_synth_flush and ry_synth_flush_dev.  The device form resets the stream in stream order, as ry_synth_run_many does: it waits for nothing.
+int flush_frames(ry_synth* s, double* y, long long y_capacity, long long* n_out, bool y_on_device) {
+    RY_TRY(check_handle(s, "synthesizer"));
+    if (n_out) *n_out = 0;
+    if (!y || !n_out || y_capacity < 0) return fail(RY_EINVAL, "bad output arguments");
+    if (s->n_frames < 1) return fail(RY_ESTATE, "flush of an empty stream");
+    RY_TRY(advance(s, true, y, y_capacity, n_out, y_on_device));
+    if (!y_on_device) return ry_synth_reset(s);
+    static const SynthScanState zero_state = {0.0, 0, 0, 0, 0, 0};
+    reset_stream(s);
+    RT_TRY(rt::h2d(s->st, &zero_state, sizeof zero_state, s->ctx->stream));
     return RY_OK;
 }
 }  // namespace
@@ -379,30 +412,28 @@ int ry_synth_bound(ry_synth* s, int n_frames, int final) {
 
 int ry_synth_push(ry_synth* s, const double* f0, const float* sp, const float* ap, int n_frames, int bins, int on_device,
                   double* y, int y_capacity, int* n_out) {
-    RY_TRY(check_handle(s, "synthesizer"));
     if (n_out) *n_out = 0;
-    if (!y || !n_out || y_capacity < 0) return fail(RY_EINVAL, "bad output arguments");
-    if (bins != SYNTH_BINS) return fail(RY_EINVAL, "%d bins per frame, fft_size / 2 + 1 = %d expected", bins, SYNTH_BINS);
-    RY_TRY(check_frames(s, f0, sp, ap, n_frames));
-    const long long m = s->n_frames + n_frames;
-    const long long may = std::max(known_samples(s, m), s->scanned) - s->done;
-    if (may > y_capacity) return fail(RY_EINVAL, "y holds %d samples, this push may return up to %lld (ry_synth_bound)", y_capacity, may);
-    RY_TRY(append_frames(s, f0, sp, ap, n_frames, on_device, first_needed_frame(s)));
     long long n = 0;
-    RY_TRY(advance(s, false, y, y_capacity, &n));
-    *n_out = (int)n;
-    return RY_OK;
+    const int rc = push_frames(s, f0, sp, ap, n_frames, bins, on_device, y, n_out ? (long long)y_capacity : -1, &n, false);
+    if (n_out) *n_out = (int)n;
+    return rc;
+}
+
+int ry_synth_push_dev(ry_synth* s, const double* f0, const float* sp, const float* ap, int n_frames, int bins, int on_device,
+                      double* y_dev, long long y_capacity, long long* n_out) {
+    return push_frames(s, f0, sp, ap, n_frames, bins, on_device, y_dev, y_capacity, n_out, true);
 }
 
 int ry_synth_flush(ry_synth* s, double* y, int y_capacity, int* n_out) {
-    RY_TRY(check_handle(s, "synthesizer"));
     if (n_out) *n_out = 0;
-    if (!y || !n_out || y_capacity < 0) return fail(RY_EINVAL, "bad output arguments");
-    if (s->n_frames < 1) return fail(RY_ESTATE, "flush of an empty stream");
     long long n = 0;
-    RY_TRY(advance(s, true, y, y_capacity, &n));
-    *n_out = (int)n;
-    return ry_synth_reset(s);
+    const int rc = flush_frames(s, y, n_out ? (long long)y_capacity : -1, &n, false);
+    if (n_out) *n_out = (int)n;
+    return rc;
+}
+
+int ry_synth_flush_dev(ry_synth* s, double* y_dev, long long y_capacity, long long* n_out) {
+    return flush_frames(s, y_dev, y_capacity, n_out, true);
 }
 
 int ry_synth_run(ry_synth* s, const double* f0, const float* sp, const float* ap, int n_frames, int bins, int on_device,
@@ -611,8 +642,10 @@ int ry_synth_bank_reset(ry_synth_bank* k, int stream) {
     return RY_OK;
 }
 
-int ry_synth_bank_push(ry_synth_bank* k, const double* f0, const float* sp, const float* ap, const int* n_frames, const int* final, int bins,
-                       int on_device, double* y, long long y_capacity, long long* sample_offsets) {
+// ry_synth_bank_push and ry_synth_bank_push_dev.  y_on_device: y is a block of the caller's on the card -- synth_overlap writes stream b's
+// samples at y[out0 of b] and no sample comes down; the records of synth_retire and the second wait stay, the next push needs them.
+static int bank_push_frames(ry_synth_bank* k, const double* f0, const float* sp, const float* ap, const int* n_frames, const int* final, int bins,
+                            int on_device, double* y, long long y_capacity, long long* sample_offsets, bool y_on_device) {
     RY_TRY(check_handle(k, "synthesizer bank"));
     // every refusal comes before anything is launched, uploaded or changed in any stream's state
     if (!f0 || !sp || !ap || !n_frames || !y || !sample_offsets) return fail(RY_EINVAL, "null f0 / sp / ap / n_frames / y / sample_offsets");
@@ -736,7 +769,7 @@ int ry_synth_bank_push(ry_synth_bank* k, const double* f0, const float* sp, cons
     }
     memcpy(k->tab_host.data() + ent_off, ent.data(), (size_t)B * sizeof(SynthStream));
     RY_TRY(grow(c->d_resp, resp * SYNTH_FFT));
-    RY_TRY(grow(c->d_y, samples));
+    if (!y_on_device) RY_TRY(grow(c->d_y, samples));
     RT_TRY(rt::h2d(k->d_tab.ptr() + ent_off, k->tab_host.data() + ent_off, (size_t)B * sizeof(SynthStream), st)); ++cnt[2];
     if (resp > 0) {
         SynthPulseParams pp = pulse_params(c);
@@ -747,6 +780,7 @@ int ry_synth_bank_push(ry_synth_bank* k, const double* f0, const float* sp, cons
     if (samples > 0) {
         SynthOverlapParams op = overlap_params(c);
         op.s0 = 0; op.s1 = samples; op.bank = d_ent; op.n_streams = B;
+        if (y_on_device) op.y = y;
         RY_LAUNCH(synth_overlap, dim3((unsigned)((samples + 255) / 256)), 256, st, op); ++cnt[1];
         RT_TRY(rt::last_error());
     }
@@ -756,7 +790,7 @@ int ry_synth_bank_push(ry_synth_bank* k, const double* f0, const float* sp, cons
     rp.c_idx = k->c_idx; rp.c_shift = k->c_shift; rp.c_voiced = k->c_voiced; rp.carry_cap = SYNTH_CARRY; rp.out = k->d_ret.ptr();
     RY_LAUNCH(synth_retire, dim3((unsigned)B), 256, st, rp); ++cnt[1];
     RT_TRY(rt::last_error());
-    if (samples > 0) { RT_TRY(rt::d2h(y, c->d_y.ptr(), (size_t)samples * sizeof(double), st)); ++cnt[3]; }
+    if (samples > 0 && !y_on_device) { RT_TRY(rt::d2h(y, c->d_y.ptr(), (size_t)samples * sizeof(double), st)); ++cnt[3]; }
     k->ret.resize((size_t)B);
     RT_TRY(rt::d2h(k->ret.data(), k->d_ret.ptr(), (size_t)B * sizeof(SynthRetired), st)); ++cnt[3];
     RT_TRY(rt::stream_sync(st)); ++cnt[0];                          // wait 2 of 2: the samples and what synth_retire carried
@@ -773,6 +807,16 @@ int ry_synth_bank_push(ry_synth_bank* k, const double* f0, const float* sp, cons
     sample_offsets[B] = samples;
     k->pulses_valid = true;
     return RY_OK;
+}
+
+int ry_synth_bank_push(ry_synth_bank* k, const double* f0, const float* sp, const float* ap, const int* n_frames, const int* final, int bins,
+                       int on_device, double* y, long long y_capacity, long long* sample_offsets) {
+    return bank_push_frames(k, f0, sp, ap, n_frames, final, bins, on_device, y, y_capacity, sample_offsets, false);
+}
+
+int ry_synth_bank_push_dev(ry_synth_bank* k, const double* f0, const float* sp, const float* ap, const int* n_frames, const int* final, int bins,
+                           int on_device, double* y_dev, long long y_capacity, long long* sample_offsets) {
+    return bank_push_frames(k, f0, sp, ap, n_frames, final, bins, on_device, y_dev, y_capacity, sample_offsets, true);
 }
 
 int ry_synth_bank_debug_pulses(ry_synth_bank* k, int stream, long long* index, double* shift, int* voiced, int capacity, int* n) {

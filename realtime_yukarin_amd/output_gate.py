@@ -106,14 +106,36 @@ class OutputGate(DeviceHandle):
         if self._host is not None:
             out, self.last = self._host.push(wave)
             return out
-        lib, h = self._get()
         x = _samples(wave)
+        return self._push(_dptr(x), x.size, 0)
+
+    def _push(self, samples, n, on_device):
+        lib, h = self._get()
         out = numpy.empty(self.chunk, self.dtype)
         n_out, silent, mean = ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
-        lib.check(lib.dll.ry_outgate_push(h, _dptr(x), x.size, 0, out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(n_out), ctypes.byref(silent),
+        lib.check(lib.dll.ry_outgate_push(h, samples, n, on_device, out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(n_out), ctypes.byref(silent),
                                           ctypes.byref(mean)))
         self.last = (n_out.value > 0, bool(silent.value), float(mean.value))
         return out if n_out.value > 0 and not silent.value else None
+
+    def on_device(self, ctx=None) -> bool:
+        """Whether `push_device` exists for this gate: it judges on the card (chunk >= MIN_DEVICE_CHUNK) -- and, with `ctx`, on that context,
+        whose device pointers it can then read."""
+        if self._host is not None:
+            return False
+        self._get()
+        return ctx is None or self._ctx is ctx
+
+    def push_device(self, ptr: int, n: int) -> Optional[numpy.ndarray]:
+        """`push` of `n` float64 samples that are on the card at address `ptr` (e.g. where `Synthesizer.push_device` left them), read in the
+        order of the context stream: nothing goes up but the gate's table, and only an audible chunk comes down.  Returns what `push` returns
+        and sets `last` the same way.  A gate on the host fallback (`chunk < MIN_DEVICE_CHUNK`) has no device form."""
+        if self._host is not None:
+            raise ValueError('a chunk of %d samples is judged on the host: no device form below %d' % (self.chunk, MIN_DEVICE_CHUNK))
+        n = int(n)
+        if n < 0 or (n > 0 and not ptr):
+            raise ValueError('%d samples at address %r' % (n, ptr))
+        return self._push(ctypes.cast(ctypes.c_void_p(int(ptr or 0)), _DP), n, 1)
 
     def held(self) -> int:
         if self._host is not None:
@@ -136,7 +158,9 @@ class OutputGate(DeviceHandle):
         lib, h = self._get()
         c = (ctypes.c_longlong * 5)()
         lib.check(lib.dll.ry_outgate_debug_counts(h, c))
-        return dict(zip(('waits', 'launches', 'uploads', 'downloads', 'sample_bytes_down'), (int(v) for v in c)))
+        d = dict(zip(('waits', 'launches', 'uploads', 'downloads', 'sample_bytes_down'), (int(v) for v in c)))
+        d['upload_bytes'] = int(lib.dll.ry_outgate_debug_upload_bytes(h))
+        return d
 
     def poison(self) -> None:
         lib, h = self._get()
@@ -184,16 +208,40 @@ class OutputGateBank(DeviceHandle):
         B = self.n_streams
         off = numpy.zeros(B + 1, numpy.int64)
         numpy.cumsum([x.size for x in xs], out=off[1:])
+        x = numpy.ascontiguousarray(numpy.concatenate(xs))
+        return self._push(x.ctypes.data_as(_DP), off, 0)
+
+    def on_device(self, ctx=None) -> bool:
+        """As `OutputGate.on_device`."""
+        if self._host is not None:
+            return False
+        self._get()
+        return ctx is None or self._ctx is ctx
+
+    def push_device(self, ptr: int, offsets) -> list:
+        """`push` of samples that are on the card: stream b's are the float64 samples [offsets[b], offsets[b + 1]) behind address `ptr`
+        (`n_streams + 1` offsets on the host, starting at 0) -- where `StreamBank.push_device` left them.  Returns what `push` returns and sets
+        `last` the same way; a stream without a sample sits the call out.  No device form on the host fallback."""
+        if self._host is not None:
+            raise ValueError('a chunk of %d samples is judged on the host: no device form below %d' % (self.chunk, MIN_DEVICE_CHUNK))
+        off = numpy.ascontiguousarray(offsets, dtype=numpy.int64).reshape(-1)
+        if off.size != self.n_streams + 1 or off[0] != 0 or (numpy.diff(off) < 0).any():
+            raise ValueError('offsets %s for %d streams' % (off.tolist(), self.n_streams))
+        if off[-1] > 0 and not ptr:
+            raise ValueError('%d samples at address %r' % (int(off[-1]), ptr))
+        return self._push(ctypes.cast(ctypes.c_void_p(int(ptr or 0)), _DP), off, 1)
+
+    def _push(self, samples, off, on_device):
+        B = self.n_streams
         self.last = [(False, False, 0.0)] * B
         if off[B] == 0:
             return [None] * B
         lib, h = self._get()
-        x = numpy.ascontiguousarray(numpy.concatenate(xs))
         out = numpy.empty(B * self.chunk, self.dtype)
         out_off = numpy.zeros(B + 1, numpy.int64)
         silent, mean = numpy.zeros(B, numpy.int32), numpy.zeros(B, numpy.float64)
         LLP = ctypes.POINTER(ctypes.c_longlong)
-        lib.check(lib.dll.ry_outgate_bank_push(h, x.ctypes.data_as(_DP), off.ctypes.data_as(LLP), 0, out.ctypes.data_as(ctypes.c_void_p), out.size,
+        lib.check(lib.dll.ry_outgate_bank_push(h, samples, off.ctypes.data_as(LLP), on_device, out.ctypes.data_as(ctypes.c_void_p), out.size,
                                                out_off.ctypes.data_as(LLP), silent.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), mean.ctypes.data_as(_DP)))
         self.last = [(int(s) >= 0, int(s) == 1, float(m)) for s, m in zip(silent, mean)]
         return [out[out_off[b]:out_off[b + 1]].copy() if silent[b] == 0 else None for b in range(B)]
@@ -219,7 +267,9 @@ class OutputGateBank(DeviceHandle):
         lib, h = self._get()
         c = (ctypes.c_longlong * 5)()
         lib.check(lib.dll.ry_outgate_bank_debug_counts(h, c))
-        return dict(zip(('waits', 'launches', 'uploads', 'downloads', 'sample_bytes_down'), (int(v) for v in c)))
+        d = dict(zip(('waits', 'launches', 'uploads', 'downloads', 'sample_bytes_down'), (int(v) for v in c)))
+        d['upload_bytes'] = int(lib.dll.ry_outgate_bank_debug_upload_bytes(h))
+        return d
 
     def poison(self) -> None:
         lib, h = self._get()

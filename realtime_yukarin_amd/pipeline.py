@@ -41,10 +41,29 @@ from .world_synth import BINS, FFT_SIZE, cheaptrick_fft_size
 
 calls = {'resident': 0, 'composed': 0}          # which path `convert_wave` / `push` took, counted per call; 'gated' (from the first gate_first
                                                 # call on): the waves whose encode stage the gate skipped
+routes = {'gate_device': 0, 'gate_host': 0}     # how the samples of a `push(..., out_gate=g)` reached the gate, counted per call: read where the
+                                                # synthesizer wrote them on the card, or brought down and handed over through the host
 
 
 def _gated(counter: dict, n: int) -> None:
     counter['gated'] = counter.get('gated', 0) + int(n)
+
+
+def _gate_on_card(out_gate, ctx) -> bool:
+    """The samples can stay on the card: the gate judges there and lives in the context whose stream the synthesizer writes on."""
+    return out_gate is not None and hasattr(out_gate, 'on_device') and out_gate.on_device(ctx)
+
+
+def _sample_block(owner, need: int):
+    """The block the synthesizer of `owner` (a `Pipeline` / `PipelineBank`) leaves its samples in: one of the blocks `_reserve` has made --
+    grown when a call may return more than it holds (`need`: the sum of `ry_synth_bound` / `ry_synth_bank_bound`), freed with them in `_free`."""
+    b = owner._blocks
+    if 'y' not in b or need > b['w_y']:
+        if 'y' in b:
+            owner._ctx.dev_free(b.pop('y'))                                # waits for the context stream: the gate's last read has ended
+        cap = max(need + need // 2, 4096)
+        b['y'], b['w_y'] = owner._ctx.dev_alloc(2 * cap), cap             # float64 samples in units of a float
+    return world_synth.SampleBlock(b['y'], b['w_y'])
 
 
 def _spanned(advance, pending):
@@ -483,8 +502,11 @@ class Pipeline(object):
         `CrepeStream`, which keeps the activation rows of the shared frames when the overlap really holds the same samples: the same bits, fewer frames
         through the network.  The kept rows are dropped by `flush`, by final=True and by a buffer that takes the composed path.
         out_gate (an `output_gate.OutputGate`): the samples go through it -- the tail of the reference's decode worker -- and the returned `Wave` is
-        the chunk it emits (scaled, in the gate's dtype), empty when no chunk was completed or the chunk is silent.  The samples take the host route
-        into the gate.
+        the chunk it emits (scaled, in the gate's dtype), empty when no chunk was completed or the chunk is silent.  On the resident path, with a
+        gate that judges on the card in the pipeline's context, the samples never leave the card: the synthesizer writes them into a block of the
+        pipeline's (`push_device`, `flush_device` behind it when final), the gate reads them there (ONE `push_device`), and only an audible chunk comes
+        down, in the gate's dtype.  Otherwise -- the composed path, a host-fallback gate (chunk below 1025), a gate of another context -- they take
+        the host route: the same bits (`routes` counts which).
         gate_first (None: the constructor's): the silence gate runs before the encode stage and a buffer without an effective frame skips the
         tracker and the analysis: the same samples.  Its tracker's kept rows stay, and its `advance` is added to that of the next buffer that is
         tracked, which so spans the buffers skipped.  The composed path ignores the flag."""
@@ -515,6 +537,19 @@ class Pipeline(object):
                 self._reset_stream((False, True))
                 ctx, b, n, f0 = self._resident_rows(wave, handles, (front, back), advance)
             k0, k1 = front, n - back
+            if _gate_on_card(out_gate, ctx):
+                block = _sample_block(self, self.synth.bound(k1 - k0, final))
+                got = 0
+                if k1 > k0:
+                    ctx.mask_rows(b['ap32'], b['mask'], n, BINS, k0, k1)
+                    rows = [world_synth.DeviceRows(b[k] + k0 * BINS * 4, k1 - k0) for k in ('sp_out', 'ap32')]
+                    got = self.synth.push_device(f0[k0:k1], rows[0], rows[1], block, 0)
+                if final:
+                    got += self.synth.flush_device(block, got)             # behind the push, in the same block
+                    self._reset_stream()
+                routes['gate_device'] += 1
+                out = out_gate.push_device(block.address, got)             # the one wait for the samples, and only when a chunk is complete
+                return Wave(wave=out if out is not None else numpy.empty(0, out_gate.dtype), sampling_rate=self.voice_changer.output_sampling_rate)
             out = numpy.empty(0, numpy.float64)
             if k1 > k0:
                 ctx.mask_rows(b['ap32'], b['mask'], n, BINS, k0, k1)
@@ -529,6 +564,7 @@ class Pipeline(object):
             out = numpy.concatenate([out, self.synth.flush()])
             self._reset_stream()
         if out_gate is not None:
+            routes['gate_host'] += 1
             out = out_gate.push(out)
             if out is None:
                 out = numpy.empty(0, out_gate.dtype)
@@ -764,7 +800,9 @@ class PipelineBank(object):
         path.  advance=None: the call as it was, through `CrepeModel.track_many`.
         out_gate (an `output_gate.OutputGateBank` of n_streams streams): the samples of all streams go through it in ONE call and every returned
         `Wave` is the chunk its stream's gate emits, empty when no chunk was completed or the chunk is silent; a stream without a sample in this call
-        sits the gate's call out.  The samples take the host route into the gate.
+        sits the gate's call out.  On the resident chain, with a bank of gates that judges on the card in the pipeline's context, the samples stay
+        on the card: ONE `StreamBank.push_device` leaves them back to back in a block of this object's and ONE `OutputGateBank.push_device` reads
+        them there.  Otherwise they take the host route, as `Pipeline.push` says: the same bits (`routes` counts which).
         gate_first (None: the constructor's): the silence gate runs before the encode stage, and the streams whose buffer has no effective frame
         skip the tracker and the analysis -- no kernel of either runs when every buffer is silent -- while their synthesis streams, their gates
         and every sample they return go on as before.  A skipped stream keeps its tracker's rows, and the `advance` of every buffer skipped is
@@ -782,6 +820,7 @@ class PipelineBank(object):
         rate = self.voice_changer.output_sampling_rate
         part = [s for s, w in enumerate(waves) if w is not None]
         outs = [numpy.empty(0, numpy.float64) for _ in range(self.n_streams)]
+        on_card = None                                                     # the device route: (block, sample offsets)
         if not part:
             if final:
                 outs = self.bank.flush(final)
@@ -847,14 +886,22 @@ class PipelineBank(object):
                             rows = [world_synth.DeviceRows(b[k] + at * BINS * 4, k1 - k0) for k in ('sp_pack', 'ap_pack')]
                             items[s] = (numpy.ascontiguousarray(f0s[i][k0 - int(fo[i]):k1 - int(fo[i])]), rows[0], rows[1])
                             at += k1 - k0
-                if total > 0 or final:
+                if _gate_on_card(out_gate, ctx):
+                    took = [s for s in range(self.n_streams) if items[s] is not None or s in final]
+                    block = _sample_block(self, sum(self.bank.bound(s, 0 if items[s] is None else items[s][0].size, s in final) for s in took))
+                    on_card = (block, self.bank.push_device(items, final, block) if took else numpy.zeros(self.n_streams + 1, numpy.int64))
+                elif total > 0 or final:
                     outs = self.bank.push(items, final=final)              # one ry_synth_bank_push: the packed rows follow one another and are read in place
         for s in part:
             self._live[s] = True
         for s in final:
             self._live[s] = False
         self._reset_trackers(final)
-        if out_gate is not None:
+        if on_card is not None:
+            routes['gate_device'] += 1
+            outs = [o if o is not None else numpy.empty(0, out_gate.dtype) for o in out_gate.push_device(on_card[0].address, on_card[1])]
+        elif out_gate is not None:
+            routes['gate_host'] += 1
             outs = [o if o is not None else numpy.empty(0, out_gate.dtype) for o in out_gate.push(outs)]
         return [Wave(wave=o, sampling_rate=rate) for o in outs]
 

@@ -13,7 +13,8 @@ parity at the `pyworld` boundary is unpinned: the package cannot be installed wh
 
 Spectrogram and aperiodicity travel as float32 `[frames][513]` rows (what stage 2 writes); `DeviceRows` -- rows already on the card,
 e.g. a stage-2 output left there -- are read where they are, without a host round trip (a `fusion.LazySpectrogram` stands for the INPUT
-of stage 2 and is materialised).  f0 goes in and the float64 wave comes out through the host."""
+of stage 2 and is materialised).  f0 goes in through the host; the float64 wave comes out through the host, or -- `push_device` /
+`flush_device` / `StreamBank.push_device` -- stays on the card in a `SampleBlock` of the caller's, where `output_gate` reads it."""
 import ctypes
 import os
 from typing import Optional
@@ -42,6 +43,25 @@ class DeviceRows(object):
     def __init__(self, address: int, frames: int, keep=None):
         self.address, self.frames, self.keep = int(address), int(frames), keep
         self.shape = (self.frames, BINS)
+
+
+class SampleBlock(object):
+    """Room for `samples` float64 samples on the GPU of the synthesizer's context, at `address`: where `Synthesizer.push_device` /
+    `flush_device` / `StreamBank.push_device` leave their samples and `OutputGate.push_device` reads them."""
+
+    def __init__(self, address: int, samples: int, keep=None):
+        self.address, self.samples, self.keep = int(address), int(samples), keep
+
+    def at(self, k: int) -> int:
+        """The address of sample k."""
+        return self.address + 8 * int(k)
+
+
+def _block_room(block: SampleBlock, at: int):
+    at = int(at)
+    if at < 0 or at > block.samples:
+        raise ValueError('sample %d of a block of %d' % (at, block.samples))
+    return ctypes.cast(ctypes.c_void_p(block.at(at)), _DP), block.samples - at
 
 
 class Synthesizer(DeviceHandle):
@@ -179,6 +199,31 @@ class Synthesizer(DeviceHandle):
         lib.check(lib.dll.ry_synth_flush(h, y.ctypes.data_as(_DP), y.size, ctypes.byref(got)))
         return y[:got.value].copy()
 
+    def push_device(self, f0, sp, ap, block: SampleBlock, at: int = 0) -> int:
+        """`push` with the samples left on the card: they are written at sample `at` of `block` (room for `bound` samples behind it) by the
+        overlap-add kernel itself -> how many (`ry_synth_push_dev`).  Nothing comes down and nothing is waited for beyond the scan's own
+        waits; a reader on the context stream (`OutputGate.push_device`) finds them in order."""
+        lib, h = self._get()
+        f0, n, psp, pap, bins, dev, keep = self._frames(f0, sp, ap)
+        y, room = _block_room(block, at)
+        got = ctypes.c_longlong()
+        lib.check(lib.dll.ry_synth_push_dev(h, f0.ctypes.data_as(_DP), psp, pap, n, bins, dev, y, room, ctypes.byref(got)))
+        return int(got.value)
+
+    def flush_device(self, block: SampleBlock, at: int = 0) -> int:
+        """`flush` with the samples left on the card at sample `at` of `block` -> how many (`ry_synth_flush_dev`); `at` = what the push before
+        returned puts push and flush back to back."""
+        lib, h = self._get()
+        y, room = _block_room(block, at)
+        got = ctypes.c_longlong()
+        lib.check(lib.dll.ry_synth_flush_dev(h, y, room, ctypes.byref(got)))
+        return int(got.value)
+
+    def bound(self, n: int, final: bool = False) -> int:
+        """Samples a push of `n` frames (final: with the flush behind it) may return (`ry_synth_bound`)."""
+        lib, h = self._get()
+        return int(lib.dll.ry_synth_bound(h, max(int(n), 0), int(bool(final))))
+
     def reset(self) -> None:
         lib, h = self._get()
         lib.check(lib.dll.ry_synth_reset(h))
@@ -233,8 +278,9 @@ class StreamBank(DeviceHandle):
         lib, h = self._get()
         return int(lib.dll.ry_synth_bank_bound(h, int(stream), int(n), int(bool(final))))
 
-    def _call(self, entries, final, in_place):
-        """One `ry_synth_bank_push`: `entries` {stream: (f0, sp, ap)} with all rows on the host, or all on the card and consecutive."""
+    def _call(self, entries, final, in_place, block=None, at=0):
+        """One `ry_synth_bank_push`: `entries` {stream: (f0, sp, ap)} with all rows on the host, or all on the card and consecutive.  block (a
+        `SampleBlock`): one `ry_synth_bank_push_dev` that leaves the samples at sample `at` of it -> the offsets int64 [B + 1] from there."""
         lib, h = self._get()
         B = self.n_streams
         order = sorted(entries)
@@ -257,19 +303,23 @@ class StreamBank(DeviceHandle):
             keep = (numpy.zeros((1, BINS), numpy.float32),) * 2
             psp, pap = _lib._fptr(keep[0]), _lib._fptr(keep[1])
         cap = sum(self.bound(b, int(n[b]), bool(fin[b])) for b in range(B) if n[b] > 0 or fin[b])
-        y = numpy.empty(max(cap, 1), numpy.float64)
         off = numpy.zeros(B + 1, numpy.int64)
         ip = ctypes.POINTER(ctypes.c_int)
+        if block is not None:
+            y, room = _block_room(block, at)
+            lib.check(lib.dll.ry_synth_bank_push_dev(h, f0.ctypes.data_as(_DP), psp, pap, n.ctypes.data_as(ip), fin.ctypes.data_as(ip), BINS,
+                                                     int(in_place), y, room, off.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+            del keep
+            return off
+        y = numpy.empty(max(cap, 1), numpy.float64)
         lib.check(lib.dll.ry_synth_bank_push(h, f0.ctypes.data_as(_DP), psp, pap, n.ctypes.data_as(ip), fin.ctypes.data_as(ip), BINS, int(in_place),
                                              y.ctypes.data_as(_DP), cap, off.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
         del keep
         return [y[off[b]:off[b + 1]].copy() for b in range(B)]
 
-    def push(self, items, final=()) -> list:
-        """`items`: a list of length B of `(f0, sp, ap)` or None (the stream sits the call out); `final`: the streams whose signal ends with this
-        call (everything left comes back and the slot starts a new signal with its next frames).  -> B float64 arrays, empty for a stream that
-        sat out.  Host rows go up in one packed upload, `DeviceRows` that are consecutive slices of one buffer are read where they are -- one
-        `ry_synth_bank_push` either way; any other list runs as one bank push per item with the other streams sitting out: the same bits."""
+    def _entries(self, items, final):
+        """The arguments of `push` / `push_device` -> ({stream: (f0, sp, ap, on_device)} of the streams with frames, `final` sorted, whether the
+        rows are read in place, whether the list runs as ONE call)."""
         items = list(items)
         if len(items) != self.n_streams:
             raise ValueError('%d items for %d streams' % (len(items), self.n_streams))
@@ -287,8 +337,46 @@ class StreamBank(DeviceHandle):
         kinds = set(ent[b][3] for b in order)
         row = BINS * 4
         in_place = kinds == {True} and all(ent[b][k].address == ent[a][k].address + ent[a][k].frames * row for a, b in zip(order, order[1:]) for k in (1, 2))
+        return ent, final, in_place, in_place or kinds <= {False}
+
+    def push_device(self, items, final, block: SampleBlock) -> numpy.ndarray:
+        """`push` with the samples left on the card: stream b's lie at samples [offsets[b], offsets[b + 1]) of `block`, back to back -- what
+        `OutputGateBank.push_device` reads -> offsets int64 [B + 1].  `block` holds the sum of `bound` over the streams that take part.  A list
+        that `push` runs item by item runs here as one `ry_synth_bank_push_dev` per stream, in stream order, each behind the one before."""
+        ent, final, in_place, one_call = self._entries(items, final)
         self._kept_pulses = None
-        if in_place or kinds <= {False}:
+        if one_call:
+            off = self._call(ent, final, in_place, block)
+            calls['bank_in_place' if in_place else 'bank_packed'] += 1
+            return off
+        calls['bank_fallback'] += 1
+        off, kept = numpy.zeros(self.n_streams + 1, numpy.int64), {}
+        for b in range(self.n_streams):
+            off[b + 1] = off[b]
+            if b not in ent and b not in final:
+                continue
+            one, dev = {}, False
+            if b in ent:
+                f0, sp, ap, dev = ent[b]
+                if dev is None:                                    # one of each: bring the host side over
+                    sp = sp if isinstance(sp, DeviceRows) else _upload(self._get_ctx(), self._rows(sp, f0.size, 'sp')[2])
+                    ap = ap if isinstance(ap, DeviceRows) else _upload(self._get_ctx(), self._rows(ap, f0.size, 'ap')[2])
+                    dev = True
+                one = {b: (f0, sp, ap)}
+            off[b + 1] += self._call(one, [b] if b in final else [], dev, block, int(off[b]))[self.n_streams]
+            kept[b] = self.pulses(b)                               # the next call reuses the pulse arrays
+        self._kept_pulses = kept
+        return off
+
+    def push(self, items, final=()) -> list:
+        """`items`: a list of length B of `(f0, sp, ap)` or None (the stream sits the call out); `final`: the streams whose signal ends with this
+        call (everything left comes back and the slot starts a new signal with its next frames).  -> B float64 arrays, empty for a stream that
+        sat out.  Host rows go up in one packed upload, `DeviceRows` that are consecutive slices of one buffer are read where they are -- one
+        `ry_synth_bank_push` either way; any other list runs as one bank push per item with the other streams sitting out: the same bits."""
+        ent, final, in_place, one_call = self._entries(items, final)
+        order = sorted(ent)
+        self._kept_pulses = None
+        if one_call:
             out = self._call(ent, final, in_place)
             calls['bank_in_place' if in_place else 'bank_packed'] += 1
             return out
