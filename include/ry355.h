@@ -865,6 +865,43 @@ int ry_outgate_bank_debug_counts(ry_outgate_bank* bank, long long* out);
 long long ry_outgate_bank_debug_upload_bytes(ry_outgate_bank* bank);
 int ry_outgate_bank_debug_poison(ry_outgate_bank* bank);
 
+/* ---- The row store: the feature segments of a live stream (the reference's stream.stream list, stream/base_stream.py) kept as device rows.
+ * Three float32 rings on the card: mc [cap_rows][mc_cols], ap [cap_rows][ap_cols], wave [cap_samples].  Segments are appended in arrival order
+ * from blocks that are already on the card and read back as the spans BaseStream.fetch would concatenate; which spans those are, and when a
+ * segment may go, is decided on the host (realtime_yukarin_amd/streams.py: fetch_plan, wave_spans, retire).  Every call is enqueued on the
+ * context stream; every refusal is made before anything is enqueued or changed.  Semantics: INTEGRATION.md section 23, DESIGN.md section 25.
+ * Refused by ry_rowstore_create: null pointers, widths outside 1 .. 65536, cap_rows outside 1 .. 2^22 or more than 2^30 floats in a ring,
+ * cap_samples outside 1 .. 2^30. */
+typedef struct ry_rowstore ry_rowstore;
+int ry_rowstore_create(ry_ctx* ctx, int mc_cols, int ap_cols, int cap_rows, int cap_samples, ry_rowstore** out);
+void ry_rowstore_destroy(ry_rowstore* store);
+/* rows [row0, row0 + n_rows) of the device blocks mc_dev [.][mc_cols] and ap_dev [.][ap_cols] and samples [sample0, sample0 + n_samples) of
+ * wave_dev go behind what the rings hold, in ONE launch that wraps at the ring ends; nothing is waited for.  *row_pos / *sample_pos: the ring
+ * positions the segment starts at.  Refused: null pointers, counts or offsets below 0, more rows or samples than the rings have free -- what is
+ * live is never overwritten; ry_rowstore_retire makes room. */
+int ry_rowstore_append(ry_rowstore* store, const float* mc_dev, const float* ap_dev, int row0, int n_rows, const float* wave_dev, int sample0,
+                       int n_samples, int* row_pos, int* sample_pos);
+/* the oldest n_rows rows and n_samples samples may be overwritten from now on (host bookkeeping only) */
+int ry_rowstore_retire(ry_rowstore* store, int n_rows, int n_samples);
+/* the live rows and samples */
+int ry_rowstore_held(ry_rowstore* store, int* rows, int* samples);
+/* row_spans [n_row_spans][3], sample_spans [n_sample_spans][3] (HOST, int): ring position or -1 for a pad, destination offset, count -- in rows
+ * of mc_dst_dev [dst_rows][mc_cols] / ap_dst_dev [dst_rows][ap_cols] and in samples of wave_dst_dev [dst_samples].  ONE upload carries both
+ * tables and ONE launch writes all three destinations; a pad writes +0.0f; a span may cross the ring end; rows and samples may start at any
+ * 4-byte alignment; nothing outside the destination spans is written; count 0 is accepted.  The call waits for the upload of the table (the
+ * host tables are free when it returns), not for the launch.  Refused: null pointers, counts below 0, spans outside the ring or the
+ * destination, a position that is retired or was never written. */
+int ry_rowstore_fetch(ry_rowstore* store, const int* row_spans, int n_row_spans, const int* sample_spans, int n_sample_spans, float* mc_dst_dev,
+                      float* ap_dst_dev, float* wave_dst_dev, int dst_rows, int dst_samples);
+/* forgets every segment (host bookkeeping only) */
+int ry_rowstore_reset(ry_rowstore* store);
+/* tests: the device addresses of the three rings (any pointer may be null) */
+int ry_rowstore_debug_buffers(ry_rowstore* store, const float** mc_dev, const float** ap_dev, const float** wave_dev);
+/* tests: out[4] = kernel launches, uploads, waits, bytes uploaded by the last append / fetch */
+int ry_rowstore_debug_counts(ry_rowstore* store, long long* out);
+/* tests: NaN bit patterns in the table buffer and in every part of the rings that holds nothing live */
+int ry_rowstore_debug_poison(ry_rowstore* store);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,8 @@ ABI_SYMBOLS = (
     'ry_synth_push_dev', 'ry_synth_flush_dev', 'ry_synth_bank_push_dev', 'ry_outgate_debug_upload_bytes', 'ry_outgate_bank_debug_upload_bytes',
     'ry_analysis_upload_waves', 'ry_analysis_ingest_tracks', 'ry_analysis_track_buffers',
     'ry_set_filter_build', 'ry_net_build_stats', 'ry_net_debug_filters', 'ry_debug_layer_filters',
+    'ry_rowstore_create', 'ry_rowstore_destroy', 'ry_rowstore_append', 'ry_rowstore_retire', 'ry_rowstore_held', 'ry_rowstore_fetch', 'ry_rowstore_reset',
+    'ry_rowstore_debug_buffers', 'ry_rowstore_debug_counts', 'ry_rowstore_debug_poison',
 )
 
 
@@ -335,6 +337,17 @@ class Ry355Lib(object):
         d.ry_outgate_debug_upload_bytes.restype = ctypes.c_longlong
         d.ry_outgate_bank_debug_upload_bytes.argtypes = [_VP]
         d.ry_outgate_bank_debug_upload_bytes.restype = ctypes.c_longlong
+        d.ry_rowstore_create.argtypes = [_VP, _CI, _CI, _CI, _CI, ctypes.POINTER(_VP)]
+        d.ry_rowstore_destroy.argtypes = [_VP]
+        d.ry_rowstore_destroy.restype = None
+        d.ry_rowstore_append.argtypes = [_VP, _FP, _FP, _CI, _CI, _FP, _CI, _CI, _IP, _IP]
+        d.ry_rowstore_retire.argtypes = [_VP, _CI, _CI]
+        d.ry_rowstore_held.argtypes = [_VP, _IP, _IP]
+        d.ry_rowstore_fetch.argtypes = [_VP, _IP, _CI, _IP, _CI, _FP, _FP, _FP, _CI, _CI]
+        d.ry_rowstore_reset.argtypes = [_VP]
+        d.ry_rowstore_debug_buffers.argtypes = [_VP, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP)]
+        d.ry_rowstore_debug_counts.argtypes = [_VP, _LLP]
+        d.ry_rowstore_debug_poison.argtypes = [_VP]
         d.ry_analysis_debug_d4c.argtypes = [_VP, ctypes.POINTER(_LL), _DP, _CI, _IP]
         d.ry_net_profile_window.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RyKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         d.ry_net_debug_activation.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]

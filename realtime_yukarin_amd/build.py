@@ -10,8 +10,8 @@ CSRC = PKG / 'csrc'
 LIB = PKG / 'libry355.so'
 EMU_DIR = ROOT / 'tests' / 'emu'
 EMU_LIB = EMU_DIR / 'libry355_emu.so'
-UNITS = [CSRC / 'ry_exec.cpp', CSRC / 'ry_plan.cpp', CSRC / 'ry_net.cpp', CSRC / 'ry_vc.cpp', CSRC / 'ry_comm.cpp', CSRC / 'crepe.cpp', CSRC / 'synth.cpp', CSRC / 'analysis.cpp', CSRC / 'outgate.cpp']          # translation units of libry355.so (ry_exec.cpp carries the kernels)
-SOURCES = UNITS + [CSRC / 'ry_kernels.h', CSRC / 'relayout_kernels.h', CSRC / 'ry_vc_kernels.h', CSRC / 'crepe_kernels.h', CSRC / 'synth_kernels.h', CSRC / 'analysis_kernels.h', CSRC / 'd4c_kernels.h', CSRC / 'outgate_kernels.h', CSRC / 'lds_fft.h', CSRC / 'ry_plan.h', CSRC / 'ry_host.h', CSRC / 'ry_dev.h', ROOT / 'include' / 'ry355.h']
+UNITS = [CSRC / 'ry_exec.cpp', CSRC / 'ry_plan.cpp', CSRC / 'ry_net.cpp', CSRC / 'ry_vc.cpp', CSRC / 'ry_comm.cpp', CSRC / 'crepe.cpp', CSRC / 'synth.cpp', CSRC / 'analysis.cpp', CSRC / 'outgate.cpp', CSRC / 'rowstore.cpp']          # translation units of libry355.so (ry_exec.cpp carries the kernels)
+SOURCES = UNITS + [CSRC / 'ry_kernels.h', CSRC / 'relayout_kernels.h', CSRC / 'ry_vc_kernels.h', CSRC / 'crepe_kernels.h', CSRC / 'synth_kernels.h', CSRC / 'analysis_kernels.h', CSRC / 'd4c_kernels.h', CSRC / 'outgate_kernels.h', CSRC / 'rowstore_kernels.h', CSRC / 'lds_fft.h', CSRC / 'ry_plan.h', CSRC / 'ry_host.h', CSRC / 'ry_dev.h', ROOT / 'include' / 'ry355.h']
 
 
 def _stale(target: Path, deps) -> bool:

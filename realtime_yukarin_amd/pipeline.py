@@ -446,16 +446,16 @@ class Pipeline(object):
     def _at(block: int, row: int):
         return _lib._fptr(int(block) + int(row) * BINS * 4)
 
-    def _composed_feature(self, wave, discard, track=None):
-        """The chain of the separate calls up to the converted feature.  WORLD mode: `world_analysis.extract` over a class whose `extract_f0` is
-        the f0 callable -- or hands out `track`, the (f0, t) that callable already returned for this wave."""
+    def _composed_extract(self, wave, track=None):
+        """The encode stage of the separate calls -> the feature with its wave.  WORLD mode: `world_analysis.extract` over a class whose
+        `extract_f0` is the f0 callable -- or hands out `track`, the (f0, t) that callable already returned for this wave."""
         if self.f0_mode == 'world':
             fn = self.f0_fn if track is None else (lambda x, fs, frame_period, f0_floor, f0_ceil: track)
             cls = type('WorldFeature', (self.feature_class,), {'extract_f0': classmethod(
                 lambda cls, x, fs, frame_period, f0_floor, f0_ceil: fn(x, fs, frame_period, f0_floor, f0_ceil))})
             f = world_analysis.extract(cls, wave, **self._encode_args())
             f.wave = wave
-            return self.voice_changer.convert_from_acoustic_feature(f, discard)
+            return f
         saved = encode.model_capacity
         encode.model_capacity = self.crepe_capacity                        # `encode.extract` and the default class's `extract_f0` read it
         try:
@@ -463,7 +463,11 @@ class Pipeline(object):
         finally:
             encode.model_capacity = saved
         f.wave = wave
-        return self.voice_changer.convert_from_acoustic_feature(f, discard)
+        return f
+
+    def _composed_feature(self, wave, discard, track=None):
+        """The chain of the separate calls up to the converted feature (`_composed_extract`, then the voice changer)."""
+        return self.voice_changer.convert_from_acoustic_feature(self._composed_extract(wave, track), discard)
 
     # ---- calls
     def convert_wave(self, wave, gate_first: Optional[bool] = None):
@@ -920,3 +924,308 @@ class PipelineBank(object):
         self._live = [False] * self.n_streams
         self._reset_trackers(range(self.n_streams))
         return [Wave(wave=o, sampling_rate=rate) for o in outs]
+
+
+class LivePipeline(object):
+    """The reference's three-stream live loop (run.py: `EncodeStream` -> `ConvertStream` -> `DecodeStream`, each with its own margin) as one
+    object: `push(buffer)` does for item k what the three workers do -- every `add` at `extra_time + k * time_length`, every window from
+    `k * time_length`, the clocks accumulated as theirs are -- and returns the samples that are final.  Each buffer goes through the encode
+    stage ONCE; its rows [pad, n - pad) and their wave slice are kept as a segment, and a convert window is FETCHED from the kept segments by
+    the plan `BaseStream.fetch` follows (`streams.fetch_plan`), silent pads included, instead of being re-encoded from audio.
+
+    Resident path: the encode window (assembled on the host from the kept input buffers: it arrives from the host anyway) goes up once
+    (`CrepeModel.track(..., device=True)`, or `Analyzer.upload_waves` + `ingest_tracks` in WORLD mode), `Analyzer.extract_resident` leaves its
+    rows on the card, `RowStore.append` takes the segment from there, `RowStore.fetch` writes the convert window's mc / ap rows and wave into
+    blocks of this object's, `VcCore.enqueue_wave_device` reads them with the discard hint (pad, pad), `ry_mask_rows` is the combine_silent of
+    ap, and the rows [pad, n - pad) go to the synthesis stream as in `Pipeline.push`.  f0 stays on the host per segment, is concatenated by the
+    same plan and goes through the F0Converter with the numpy operations of the separate calls.  No mc / sp / ap row crosses the bus
+    (`transfers` lists what did, call by call).  The resident path asks that the decode plan hands on exactly the rows just converted -- with
+    `decode_extra_time = 0` it does -- and that `Pipeline`'s conditions hold (`_resident_handles`).
+
+    Composed path, otherwise: the same plans applied to host arrays over the separate calls -- `encode.extract` / `world_analysis.extract`,
+    `convert_from_acoustic_feature`, `decode_realtime` -- with the bits of the resident path where both apply.  A signal that has taken it once
+    stays on it until `flush` (its segments are then on the host; those of earlier resident buffers are brought down once).  `calls` counts
+    which way a call went.  Retired segments (`streams.retire`) are dropped after every push on both paths.
+
+    One stream; `gate_first`, `advance` and banks are `Pipeline` / `PipelineBank` matters: with `encode_extra_time = 0` no audio is encoded
+    twice, so there is no overlap for them to save.  INTEGRATION.md section 23, DESIGN.md section 25."""
+
+    def __init__(self, voice_changer, acoustic_param, time_length: float, encode_extra_time: float, convert_extra_time: float, decode_extra_time: float,
+                 f0_mode: str = 'crepe', f0_fn=None, crepe_capacity='full', seed: Optional[int] = None, feature_class=None,
+                 ring_rows: Optional[int] = None, ring_samples: Optional[int] = None, resident: bool = True):
+        """ring_rows / ring_samples: the capacity of the store's rings (None: what the retire rule keeps live, with a segment to spare).
+        resident=False: every call takes the composed path -- the yardstick of the tests and of scripts/live_pipeline_bench.py."""
+        from . import streams
+        self._streams = streams
+        self._pipe = Pipeline(voice_changer, acoustic_param, crepe_capacity=crepe_capacity, seed=seed, feature_class=feature_class, f0_mode=f0_mode, f0_fn=f0_fn)
+        self.voice_changer, self.acoustic_param, self.f0_mode, self.synth = voice_changer, acoustic_param, f0_mode, self._pipe.synth
+        self.time_length = time_length
+        self.extra = (encode_extra_time, convert_extra_time, decode_extra_time)
+        self.calls, self.routes = calls, routes
+        self.transfers = []                                                # of the last call: (direction, what, elements)
+        self.ring_rows, self.ring_samples, self.resident = ring_rows, ring_samples, bool(resident)
+        self._store, self._win, self._win_cap = None, {}, (0, 0)
+        self._start()
+
+    def _start(self) -> None:
+        """A new signal: the workers' clocks at their first values, no segment anywhere."""
+        self._add = list(self.extra)                                       # `start_time = extra_time` of the three workers
+        self._now = [0., 0., 0.]                                           # `StreamWrapper._current_time` of the three streams
+        self._inputs, self._features, self._outputs = [], [], []           # EncodeStream / ConvertStream / DecodeStream .stream
+        self._mode = None                                                  # None until the first push, then 'resident' or 'composed'
+        if self._store is not None:
+            self._store.reset()
+
+    # ---- rates and pads of the three streams, as their constructors take them
+    def _rates(self):
+        vc, p = self.voice_changer, self.acoustic_param
+        gp = vc.acoustic_converter.config.dataset.acoustic_param
+        sp = vc.super_resolution.config.dataset.param.acoustic_feature_param
+        return 1000 // p.frame_period, 1000 // gp.frame_period, 1000 // sp.frame_period
+
+    @staticmethod
+    def _inner(pad: int, n: int):
+        """`pick(data, pad, -pad)` of n elements as numpy slices it (the whole when pad is 0: the streams then do not pick)."""
+        return (0, n) if pad <= 0 else LivePipeline._clip(pad, -pad, n)
+
+    @staticmethod
+    def _clip(first, last, n):
+        a, b, _ = slice(first, last).indices(n)
+        return a, max(a, b)
+
+    def _frames(self, n_samples: int, fs) -> int:
+        p = self.acoustic_param
+        if n_samples < 1:
+            return 0
+        if self.f0_mode == 'world':
+            return world_analysis.harvest_frames(n_samples, fs, p.frame_period)
+        return _crepe.track_frames(n_samples, fs, _crepe.hop_length(p.frame_period))
+
+    def _window_blocks(self, ctx, rows: int, samples: int, m_in: int):
+        """The blocks a fetched window lies in: mc (rows, m_in), ap (rows, 513), wave (samples,) -- grown, never shrunk."""
+        if self._win.get('ctx') is not ctx or self._win.get('pid') != os.getpid():
+            self._win, self._win_cap = {'ctx': ctx, 'pid': os.getpid()}, (0, 0)
+        if rows > self._win_cap[0] or samples > self._win_cap[1] or self._win.get('m_in') != m_in:
+            self._free_window()
+            cap = (max(rows + rows // 2, 64), max(samples + samples // 2, 4096))
+            self._win.update(ctx=ctx, pid=os.getpid(), m_in=m_in, mc=ctx.dev_alloc(cap[0] * m_in), ap=ctx.dev_alloc(cap[0] * BINS), wave=ctx.dev_alloc(cap[1]))
+            self._win_cap = cap
+        return self._win
+
+    def _free_window(self) -> None:
+        w = self._win
+        if w.get('pid') == os.getpid() and w.get('ctx') is not None and w['ctx'].handle is not None:
+            for k in ('mc', 'ap', 'wave'):
+                if k in w:
+                    w['ctx'].dev_free(w.pop(k))
+        self._win_cap = (0, 0)
+
+    def _store_of(self, ctx, m_in: int, seg_rows: int, seg_samples: int):
+        if self._store is None or self._store._given_ctx is not ctx or self._store.mc_cols != m_in:
+            if self._store is not None:
+                self._store.close()
+            live = int((2 * self.extra[1] + 2 * self.time_length) / self.time_length) + 3        # segments the retire rule keeps, and one to spare
+            rows = self.ring_rows if self.ring_rows is not None else live * (seg_rows + 2)
+            samples = self.ring_samples if self.ring_samples is not None else live * (seg_samples + 2)
+            self._store = self._streams.RowStore(m_in, BINS, rows, samples, ctx=ctx)
+        return self._store
+
+    def close(self) -> None:
+        """Frees the store, the window blocks and the synthesizer in the process that created them; the voice changer and the shared handles stay."""
+        if self._store is not None:
+            self._store.close()
+            self._store = None
+        self._free_window()
+        self._pipe.close()
+
+    # ---- host arrays by plan: what `concat` of the picked segments and the pads holds
+    @staticmethod
+    def _concat(spans, arrays, width, dtype):
+        parts = [numpy.zeros((b - a,) + width, dtype) if i < 0 else arrays[i][a:b] for i, a, b in spans]
+        return numpy.concatenate(parts)
+
+    def _demote(self) -> None:
+        """The signal leaves the resident path: its live segments come down once, and every later buffer is composed."""
+        if self._mode == 'resident' and self._store is not None:
+            for f, seg in zip(self._features, self._store.segments):
+                f['mc'], f['ap'], f['wave'] = self._store.download(seg)
+                f['voiced'] = f['f0'] != 0
+                self.transfers += [('down', 'mc', f['mc'].size), ('down', 'ap', f['ap'].size), ('down', 'wave', f['wave'].size)]
+            self._store.reset()
+        self._mode = 'composed'
+
+    def _plans(self, n_enc: int, n_window: int, fs):
+        """Everything the stream arithmetic decides for this buffer, from the clocks and the lengths alone: the rows / samples `EncodeStream` picks
+        of an encode window of n_enc frames, the convert window's plan with its clipped row and sample spans and their totals, the convert pad
+        and the rows `ConvertStream` picks, and the decode window's clocks and spans."""
+        S, p, T = self._streams, self.acoustic_param, self.time_length
+        rate_e, rate_c, rate_d = self._rates()
+        gp = self.voice_changer.acoustic_converter.config.dataset.acoustic_param
+        pad_e = round(self.extra[0] * rate_e)
+        ra, rb = self._inner(pad_e, n_enc)
+        wa, wb = (0, n_window) if pad_e <= 0 else self._clip(round(pad_e * p.frame_period / 1000 * fs), round(-pad_e * p.frame_period / 1000 * fs), n_window)
+        clocks = [(f['start'], f['rows']) for f in self._features] + [(self._add[1], rb - ra)]
+        sizes = [f['samples'] for f in self._features] + [wb - wa]
+        c_plan = S.fetch_plan(clocks, self._now[1], T, self.extra[1], rate_c)
+        c_rows = S.row_spans(c_plan, [n for _, n in clocks])
+        c_samples = S.wave_spans(c_plan, gp.frame_period, fs, sizes)
+        n_c, n_w = S.span_count(c_rows), S.span_count(c_samples)
+        pad_c = round(self.extra[1] * rate_c)
+        k0, k1 = self._inner(pad_c, n_c)
+        d_clocks = [(o['start'], o['rows']) for o in self._outputs] + [(self._add[2], k1 - k0)]
+        d_rows = S.row_spans(S.fetch_plan(d_clocks, self._now[2], T, self.extra[2], rate_d), [n for _, n in d_clocks])
+        return (ra, rb), (wa, wb), c_plan, c_rows, c_samples, n_c, n_w, pad_c, (k0, k1), d_clocks, d_rows
+
+    def push(self, buffer, out_gate=None):
+        """One buffer of `time_length` seconds at the input rate (a float32 array, or a `yukarin.Wave`) -> the `Wave` of the samples that are
+        final; with `out_gate` the chunk the gate emits, as `Pipeline.push` returns it."""
+        from yukarin import Wave
+        from yukarin.acoustic_feature import AcousticFeature
+        S, p, vc = self._streams, self.acoustic_param, self.voice_changer
+        T = self.time_length
+        fs = int(buffer.sampling_rate) if hasattr(buffer, 'sampling_rate') else int(p.sampling_rate)
+        x = numpy.asarray(buffer.wave if hasattr(buffer, 'wave') else buffer)
+        rate_e, rate_c, rate_d = self._rates()
+        gp = vc.acoustic_converter.config.dataset.acoustic_param
+        self.transfers = []
+        # ---- the three plans, from clocks and lengths alone: which way the call goes is known before anything runs
+        self._inputs.append((self._add[0], x))
+        self._add[0] += T
+        in_plan = S.row_spans(S.fetch_plan([(s, len(a)) for s, a in self._inputs], self._now[0], T, self.extra[0], fs), [len(a) for _, a in self._inputs])
+        window = self._concat(in_plan, [a for _, a in self._inputs], (), numpy.float32)          # WaveSegmentMethod.pad: float32 zeros
+        self._now[0] += T
+        del self._inputs[:S.retire([(s, len(a)) for s, a in self._inputs], self._now[0], T, self.extra[0], fs)]
+        wave = Wave(window, fs)
+        n_enc = self._frames(window.size, fs)
+        (ra, rb), (wa, wb), c_plan, c_rows, c_samples, n_c, n_w, pad_c, (k0, k1), d_clocks, d_rows = self._plans(n_enc, window.size, fs)
+        handles = None
+        if self.resident and self._mode != 'composed' and rb > ra and k1 > k0 and n_w > 0 and S.is_identity(d_rows, len(d_clocks) - 1, k1 - k0):
+            handles = self._pipe._resident_handles(wave)
+        track = None
+        if handles is not None and self.f0_mode == 'world':
+            track = _world_f0(self._pipe.f0_fn, wave, p)
+            if not _track_fits(track[0], track[1], n_enc, p.frame_period):
+                handles = None                                             # the callable's track does not fit: the composed path, with that track
+        if handles is None:
+            self._demote()
+            out = self._push_composed(wave, track)
+        else:
+            self._mode = 'resident'
+            out = self._push_resident(handles, wave, track, n_enc, (ra, rb), (wa, wb), c_plan, c_rows, n_c, n_w, pad_c, (k0, k1), out_gate)
+        # ---- the clocks move on and what no later window can fetch goes, on both paths
+        self._add[1] += T
+        self._add[2] += T
+        self._now[1] += T
+        self._now[2] += T
+        gone = S.retire([(f['start'], f['rows']) for f in self._features], self._now[1], T, self.extra[1], rate_c)
+        if self._mode == 'resident':
+            self._store.retire(gone)
+        del self._features[:gone]
+        del self._outputs[:S.retire([(o['start'], o['rows']) for o in self._outputs], self._now[2], T, self.extra[2], rate_d)]
+        if isinstance(out, Wave):
+            return out                                                     # the gate read the samples on the card
+        if out_gate is not None:
+            routes['gate_host'] += 1
+            out = out_gate.push(out)
+            if out is None:
+                out = numpy.empty(0, out_gate.dtype)
+        return Wave(wave=out, sampling_rate=vc.output_sampling_rate)
+
+    def _push_resident(self, handles, wave, track, n_enc, rows, samples, c_plan, c_rows, n_c, n_w, pad_c, keep, out_gate):
+        from yukarin import Wave
+        from yukarin.acoustic_feature import AcousticFeature
+        model, analyzer, core, (p_eff, p_all), hop, gate_fft = handles
+        p, ac = self.acoustic_param, self.voice_changer.acoustic_converter
+        fs, (ra, rb), (wa, wb), (k0, k1) = int(wave.sampling_rate), rows, samples, keep
+        calls['resident'] += 1
+        x = numpy.ascontiguousarray(wave.wave, dtype=numpy.float32)
+        # encode: the window goes up once; its rows stay on the card
+        if self.f0_mode == 'world':
+            trk = analyzer.ingest_tracks([track[0]], p.frame_period, analyzer.upload_waves([x]))
+            self.transfers += [('up', 'wave', x.size), ('up', 'f0', track[0].size)]
+            f0_track = track[0]
+        else:
+            trk = model.track(x, fs, _crepe.hop_length(p.frame_period), p.frame_period, threshold=encode.threshold, device=True)
+            self.transfers.append(('up', 'wave', x.size))
+        if trk.frames != n_enc:
+            raise RuntimeError('the tracker returned %d frames, the frame-count rule says %d' % (trk.frames, n_enc))
+        ctx = core.stage1.ctx
+        b = self._pipe._reserve(ctx, max(n_enc, n_c), p.order + 1, core.M, core.F)
+        analyzer.extract_resident(trk.wave, trk.samples, trk.f0, trk.t, n_enc, b['mc32'], b['sp32'], b['ap32'])
+        if self.f0_mode != 'world':
+            f0_track = trk.download()[1]
+            self.transfers.append(('down', 'track', n_enc))
+        store = self._store_of(ctx, p.order + 1, rb - ra, wb - wa)
+        store.append(self._add[1], b['mc32'], b['ap32'], ra, rb - ra, trk.wave, wa, wb - wa)
+        self._features.append(dict(start=self._add[1], rows=rb - ra, samples=wb - wa, f0=f0_track[:, None].astype(p.dtype)[ra:rb]))
+        # convert: the window is fetched from the rows on the card
+        w = self._window_blocks(ctx, n_c, n_w, p.order + 1)
+        store.fetch(c_plan, ac.config.dataset.acoustic_param.frame_period, fs, w['mc'], w['ap'], w['wave'], n_c, n_w)
+        self.transfers.append(('up', 'table', store.counts()['upload_bytes'] // 4))
+        discard = (pad_c, pad_c) if os.environ.get('RY_DISCARD_HINT', '1') != '0' else (0, 0)
+        if core.discard != discard:
+            core.set_discard(*discard)
+        effective, n_eff = core.enqueue_wave_device(w['wave'], n_w, hop, gate_fft, p_eff, p_all, w['mc'], n_c, b['mc_out'], b['sp_out'], b['mask'], SP_FLOOR)
+        self.transfers.append(('down', 'mask', n_c))
+        f0_in = self._concat(c_rows, [f['f0'] for f in self._features], (1,), numpy.float32)
+        f0_eff = f0_in[effective]
+        if n_eff and ac.f0_converter is not None:
+            f0_eff = ac.f0_converter.convert(AcousticFeature(f0=f0_eff)).f0
+        f0 = numpy.zeros((n_c, 1), numpy.float32)
+        f0[effective] = f0_eff
+        f0 = numpy.ascontiguousarray(f0.ravel(), dtype=numpy.float64)[k0:k1]
+        # decode: the plan hands on exactly the rows just converted
+        self._outputs.append(dict(start=self._add[2], rows=k1 - k0))
+        ctx.mask_rows(w['ap'], b['mask'], n_c, BINS, k0, k1)
+        dev_rows = [world_synth.DeviceRows(base + k0 * BINS * 4, k1 - k0) for base in (b['sp_out'], w['ap'])]
+        self.transfers.append(('up', 'f0', k1 - k0))
+        if _gate_on_card(out_gate, ctx):
+            block = _sample_block(self._pipe, self.synth.bound(k1 - k0, False))
+            got = self.synth.push_device(f0, dev_rows[0], dev_rows[1], block, 0)
+            routes['gate_device'] += 1
+            out = out_gate.push_device(block.address, got)
+            if out is not None:
+                self.transfers.append(('down', 'samples', out.size))
+            return Wave(wave=out if out is not None else numpy.empty(0, out_gate.dtype), sampling_rate=self.voice_changer.output_sampling_rate)
+        out = self.synth.push(f0, dev_rows[0], dev_rows[1])
+        self.transfers.append(('down', 'samples', out.size))
+        return out
+
+    def _push_composed(self, wave, track):
+        from yukarin import Wave
+        from yukarin.acoustic_feature import AcousticFeature
+        calls['composed'] += 1
+        self._pipe._reset_stream()
+        # encode: the separate call on the window, then `pick(pad, -pad)`; the plans follow the frames it really returned
+        f = self._pipe._composed_extract(wave, track)
+        (ra, rb), (wa, wb), _, c_rows, c_samples, _, _, pad_c, (k0, k1), _, d_rows = self._plans(len(f.f0), len(wave.wave), int(wave.sampling_rate))
+        self._features.append(dict(start=self._add[1], rows=rb - ra, samples=wb - wa, f0=numpy.asarray(f.f0)[ra:rb], mc=numpy.asarray(f.mc)[ra:rb],
+                                   ap=numpy.asarray(f.ap)[ra:rb], voiced=numpy.asarray(f.voiced)[ra:rb], wave=numpy.asarray(wave.wave)[wa:wb]))
+        # convert: the window by the plan (`FeatureWrapperSegmentMethod`: float32 pads, keys f0 / ap / mc / voiced and the wave)
+        fs_ = self._features
+        g = AcousticFeature(f0=self._concat(c_rows, [s['f0'] for s in fs_], (1,), numpy.float32),
+                            ap=self._concat(c_rows, [s['ap'] for s in fs_], (fs_[-1]['ap'].shape[1],), numpy.float32),
+                            mc=self._concat(c_rows, [s['mc'] for s in fs_], (fs_[-1]['mc'].shape[1],), numpy.float32),
+                            voiced=self._concat(c_rows, [s['voiced'] for s in fs_], (1,), bool))
+        g.wave = Wave(self._concat(c_samples, [s['wave'] for s in fs_], (), numpy.float32), wave.sampling_rate)
+        out = self.voice_changer.convert_from_acoustic_feature(g, (pad_c, pad_c))
+        self._outputs.append(dict(start=self._add[2], rows=k1 - k0, f0=numpy.asarray(out.f0)[k0:k1], sp=numpy.asarray(out.sp)[k0:k1],
+                                  ap=numpy.asarray(out.ap)[k0:k1]))
+        # decode: the window by the plan (`FeatureSegmentMethod`: `AcousticFeature.silent` pads), to the synthesis stream
+        held = [o for o in self._outputs]
+        if any(i >= 0 and b > a and 'sp' not in held[i] for i, a, b in d_rows):
+            raise RuntimeError('the decode window reaches rows that were synthesized on the card and not kept')
+        if self._streams.span_count(d_rows) == 0:
+            return numpy.empty(0, numpy.float64)
+        last = held[-1]
+        h = AcousticFeature(f0=self._concat(d_rows, [o.get('f0') for o in held], (1,), numpy.float32),
+                            sp=self._concat(d_rows, [o.get('sp') for o in held], (last['sp'].shape[1],), numpy.float32),
+                            ap=self._concat(d_rows, [o.get('ap') for o in held], (last['ap'].shape[1],), numpy.float32))
+        return world_synth.decode_realtime(self._pipe._vocoder, h).wave
+
+    def flush(self):
+        """Ends the signal: the samples `push` still held back; the next `push` starts a new signal with the clocks at their first values."""
+        from yukarin import Wave
+        self._pipe._reset_stream()
+        self._start()
+        return Wave(wave=self.synth.flush(), sampling_rate=self.voice_changer.output_sampling_rate)
