@@ -9,7 +9,7 @@ stages already have:
 
 The resident path is `CrepeModel.track(..., device=True)` (the one upload of the wave) -> `Analyzer.extract_resident` (float32 mc / sp / ap rows in
 blocks this object owns) -> `VcCore.enqueue_wave_device` (the gate reads the wave the tracker uploaded, stage 1 reads the mc rows, mc and the
-converted spectrogram stay on the card) -> `ry_mask_rows` (combine_silent of ap) -> `ry_synth_run` / `ry_synth_push` with device rows.  The host
+converted spectrogram stay on the card) -> `ry_mask_rows` (combine_silent of ap) -> `Synthesizer.synthesize` / `push` on device rows.  The host
 exchanges the wave (up, once), the track, the mask and the count (down), the converted f0 (up) and the samples (down); f0 goes through the
 F0Converter on the host with exactly the numpy operations of the separate calls.  Every result has the bits of the chain of the separate calls:
 `encode.extract` -> `VoiceChanger.convert_from_acoustic_feature` -> `world_synth.decode` (or `decode_realtime`), which is also what runs -- unchanged
@@ -27,13 +27,11 @@ section 21).  `calls['gated']` counts the waves skipped; `last_gate` is the reco
 tracker; no CREPE model is built.  The bits are those of the composed chain with the same callable (`world_analysis.extract` ->
 `convert_from_acoustic_feature` -> `world_synth.decode`), which also runs whenever the callable's track is not the one the frame-count rule
 expects; with `gate_first` a silent wave costs no host f0 call."""
-import ctypes
 import os
 from typing import Optional
 
 import numpy
 
-from . import _lib
 from . import crepe as _crepe
 from . import encode, gate, world_analysis, world_synth
 from .voice_changer import SP_FLOOR
@@ -45,8 +43,10 @@ routes = {'gate_device': 0, 'gate_host': 0}     # how the samples of a `push(...
                                                 # synthesizer wrote them on the card, or brought down and handed over through the host
 
 
-def _gated(counter: dict, n: int) -> None:
-    counter['gated'] = counter.get('gated', 0) + int(n)
+def _note_gate(owner, counter: dict, record: dict) -> None:
+    """What a gate_first call leaves behind: the waves whose encode stage it skipped, counted, and its record."""
+    counter['gated'] = counter.get('gated', 0) + len(record['tracked']) - sum(record['tracked'])
+    owner.last_gate = record
 
 
 def _gate_on_card(out_gate, ctx) -> bool:
@@ -54,16 +54,27 @@ def _gate_on_card(out_gate, ctx) -> bool:
     return out_gate is not None and hasattr(out_gate, 'on_device') and out_gate.on_device(ctx)
 
 
-def _sample_block(owner, need: int):
-    """The block the synthesizer of `owner` (a `Pipeline` / `PipelineBank`) leaves its samples in: one of the blocks `_reserve` has made --
-    grown when a call may return more than it holds (`need`: the sum of `ry_synth_bound` / `ry_synth_bank_bound`), freed with them in `_free`."""
-    b = owner._blocks
-    if 'y' not in b or need > b['w_y']:
-        if 'y' in b:
-            owner._ctx.dev_free(b.pop('y'))                                # waits for the context stream: the gate's last read has ended
-        cap = max(need + need // 2, 4096)
-        b['y'], b['w_y'] = owner._ctx.dev_alloc(2 * cap), cap             # float64 samples in units of a float
-    return world_synth.SampleBlock(b['y'], b['w_y'])
+def _through_host_gate(out_gate, out):
+    """The host route through an output gate: the samples that came down -- one array, or the list a bank of gates takes -- are handed over, and
+    what the gate does not emit comes back empty, in the gate's dtype."""
+    routes['gate_host'] += 1
+    emitted = lambda o: o if o is not None else numpy.empty(0, out_gate.dtype)
+    got = out_gate.push(out)
+    return [emitted(o) for o in got] if isinstance(out, list) else emitted(got)
+
+
+def _apply_discard(core, discard) -> None:
+    """The discard hint of the window calls that follow (none when the environment switches it off), set only when the core has another."""
+    discard = (int(discard[0]), int(discard[1])) if os.environ.get('RY_DISCARD_HINT', '1') != '0' else (0, 0)
+    if core.discard != discard:
+        core.set_discard(*discard)
+
+
+def _device_rows(b, first: int, counts):
+    """The rows the synthesizer reads where the chain left them -- sp in `sp_out`, ap in `ap32` -- from row `first` on: one (sp, ap) pair of
+    `DeviceRows` per count, each behind the other."""
+    starts = first + numpy.concatenate([[0], numpy.cumsum(counts)])
+    return [tuple(world_synth.DeviceRows(b[k] + int(at) * BINS * 4, int(n)) for k in ('sp_out', 'ap32')) for at, n in zip(starts, counts)]
 
 
 def _spanned(advance, pending):
@@ -102,22 +113,9 @@ def _gate_first_rows(handles, acoustic_param, voice_changer, waves, discard, res
         analyzer.extract_spans_resident(trk.wave, trk.samples, trk.first_sample, trk.n_samples, trk.f0, trk.t, trk.frame_offsets,
                                         [int(fo[i]) for i in which], b['mc32'], b['sp32'], b['ap32'])
         tracks = dict(zip(which, trk.download()))
-    discard = (int(discard[0]), int(discard[1])) if os.environ.get('RY_DISCARD_HINT', '1') != '0' else (0, 0)
-    if core.discard != discard:
-        core.set_discard(*discard)
+    _apply_discard(core, discard)
     core.enqueue_waves_masked_device(fo, b['mc32'], b['mc_out'], b['sp_out'], b['mask'], effective, n_eff, SP_FLOOR)
-    # f0, wave by wave: the numpy operations of `Pipeline._resident_rows`; a skipped wave has combine_silent's float32 zeros
-    from yukarin.acoustic_feature import AcousticFeature
-    f0s = []
-    for i in range(len(xs)):
-        eff = effective[fo[i]:fo[i + 1]]
-        f0 = numpy.zeros((len(eff), 1), numpy.float32)
-        if i in tracks:
-            f0_eff = tracks[i][1][:, None].astype(p.dtype)[eff]
-            if ac.f0_converter is not None:
-                f0_eff = ac.f0_converter.convert(AcousticFeature(f0=f0_eff)).f0
-            f0[eff] = f0_eff
-        f0s.append(numpy.ascontiguousarray(f0.ravel(), dtype=numpy.float64))
+    f0s = [_converted_f0(ac, p.dtype, tracks[i][1] if i in tracks else None, effective[fo[i]:fo[i + 1]]) for i in range(len(xs))]
     record = dict(n_eff=[int(k) for k in n_eff], tracked=[i in tracks for i in range(len(xs))], n_computed=computed)
     return ctx, b, fo, f0s, record
 
@@ -134,17 +132,23 @@ def _world_f0(f0_fn, wave, acoustic_param):
     return numpy.asarray(f0, numpy.float64), numpy.asarray(t, numpy.float64)
 
 
-def _converted_f0(ac, dtype, track, eff):
-    """f0 of one wave as the synthesizer reads it: the numpy operations of the separate calls -- astype_only_float(dtype), indexing(effective), the
-    F0Converter, combine_silent's float32 zeros, the synthesizer's float64 cast.  track None: a wave the gate skipped."""
+def _converted_column(ac, column, eff):
+    """f0 as the synthesizer reads it, from the float32 column [frames, 1] the encode stage hands on: the numpy operations of the separate calls
+    -- indexing(effective), the F0Converter, combine_silent's float32 zeros, the synthesizer's float64 cast.  column None: a wave the gate skipped."""
     from yukarin.acoustic_feature import AcousticFeature
     f0 = numpy.zeros((len(eff), 1), numpy.float32)
-    if track is not None:
-        f0_eff = track[:, None].astype(dtype)[eff]
+    if column is not None:
+        f0_eff = column[eff]
+        # the converter sees no empty column; one guard for every caller: a wave `_gate_first_rows` tracked has n_eff > 0, so eff.any() holds there
         if eff.any() and ac.f0_converter is not None:
             f0_eff = ac.f0_converter.convert(AcousticFeature(f0=f0_eff)).f0
         f0[eff] = f0_eff
     return numpy.ascontiguousarray(f0.ravel(), dtype=numpy.float64)
+
+
+def _converted_f0(ac, dtype, track, eff):
+    """`_converted_column` of one wave's track (float64 [frames]; None: a wave the gate skipped), after astype_only_float(dtype)."""
+    return _converted_column(ac, None if track is None else track[:, None].astype(dtype), eff)
 
 
 def _world_rows(handles, acoustic_param, voice_changer, waves, discard, reserve, f0_fn, gate_first: bool):
@@ -171,7 +175,6 @@ def _world_rows(handles, acoustic_param, voice_changer, waves, discard, reserve,
         tracks[i] = _world_f0(f0_fn, waves[i], p)
         if not _track_fits(tracks[i][0], tracks[i][1], int(fo[i + 1] - fo[i]), p.frame_period):
             return None, tracks
-    discard = (int(discard[0]), int(discard[1])) if os.environ.get('RY_DISCARD_HINT', '1') != '0' else (0, 0)
     if which:
         trk = analyzer.ingest_tracks([tracks[i][0] for i in which], p.frame_period, up, which)
         if gate_first:
@@ -179,8 +182,7 @@ def _world_rows(handles, acoustic_param, voice_changer, waves, discard, reserve,
                                             [int(fo[i]) for i in which], b['mc32'], b['sp32'], b['ap32'])
         else:
             analyzer.extract_many_resident(trk.wave, trk.sample_offsets, trk.f0, trk.t, fo, b['mc32'], b['sp32'], b['ap32'])
-    if core.discard != discard:
-        core.set_discard(*discard)
+    _apply_discard(core, discard)
     if gate_first:
         core.enqueue_waves_masked_device(fo, b['mc32'], b['mc_out'], b['sp_out'], b['mask'], effective, n_eff, SP_FLOOR)
     else:
@@ -230,7 +232,50 @@ class _Vocoder(object):
         self._ry_synth = self._synthesizer = synthesizer
 
 
-class Pipeline(object):
+class _BlockOwner(object):
+    """The device blocks of a `Pipeline` / `PipelineBank`: grown, never shrunk, freed by `close` in the process that made them.  `_blocks` holds
+    the feature blocks by name with their widths ('w_' + name), the gate's mask and, once a gate has read samples on the card, the sample block
+    'y' of 'w_y' samples."""
+    _more_widths = {}                                                      # what a subclass keeps beside the rows of the chain: {name: floats per frame}
+
+    def __init__(self):
+        self._blocks, self._cap, self._ctx, self._pid = {}, 0, None, None
+        self._table = None                                                 # `PipelineBank.push`: what the index table in 'rows' holds
+
+    def _reserve(self, ctx, n: int, m_in: int, m_out: int, f_out: int) -> dict:
+        if self._pid != os.getpid() or self._ctx is not ctx:
+            self._blocks, self._cap, self._ctx, self._pid, self._table = {}, 0, ctx, os.getpid(), None     # another process / context: its blocks are not ours to free
+        widths = dict(mc32=m_in, sp32=BINS, ap32=BINS, mc_out=m_out, sp_out=f_out, **self._more_widths)
+        if n > self._cap or any(self._blocks.get('w_' + k) != w for k, w in widths.items()):
+            self._free()
+            cap = max(n + n // 2, 64)
+            for k, w in widths.items():
+                self._blocks[k] = ctx.dev_alloc(cap * w)
+                self._blocks['w_' + k] = w
+            self._blocks['mask'] = ctx.dev_alloc(cap // 4 + 4)
+            self._cap = cap
+        return self._blocks
+
+    def _free(self) -> None:
+        if self._pid == os.getpid() and self._ctx is not None and self._ctx.handle is not None:
+            for k, p in self._blocks.items():
+                if not k.startswith('w_'):
+                    self._ctx.dev_free(p)
+        self._blocks, self._cap, self._table = {}, 0, None
+
+    def _sample_block(self, need: int):
+        """The block the synthesizer leaves its samples in: one of the blocks `_reserve` has made -- grown when a call may return more than it
+        holds (`need`: the sum of `Synthesizer.bound` / `StreamBank.bound`), freed with them in `_free`."""
+        b = self._blocks
+        if 'y' not in b or need > b['w_y']:
+            if 'y' in b:
+                self._ctx.dev_free(b.pop('y'))                             # waits for the context stream: the gate's last read has ended
+            cap = max(need + need // 2, 4096)
+            b['y'], b['w_y'] = self._ctx.dev_alloc(2 * cap), cap           # float64 samples in units of a float
+        return world_synth.SampleBlock(b['y'], b['w_y'])
+
+
+class Pipeline(_BlockOwner):
     """`convert_wave(wave)`: one buffer, start to end.  `push(wave, discard)` / `flush()`: the live form -- every buffer is encoded and converted on
     its own, the rows the caller keeps go to one synthesis stream.  `voice_changer`: the mirror `voice_changer.VoiceChanger` over the two converter
     shims; `acoustic_param`: the vocoder's (`Vocoder.acoustic_param`); `feature_class`: the class `Vocoder.encode` would call `extract` on."""
@@ -266,30 +311,8 @@ class Pipeline(object):
                                              ctx=world_synth.engine_for_tests.ctx)
         self._vocoder = _Vocoder(acoustic_param, voice_changer.output_sampling_rate, self.synth)
         self.calls = calls
-        self._blocks, self._cap, self._ctx, self._pid = {}, 0, None, None
+        _BlockOwner.__init__(self)
         self._crepe_stream = None                                          # `push(..., advance=a)`: the tracker that keeps rows between buffers
-
-    # ---- the blocks this object owns: grown, never shrunk, freed by `close` in the process that made them
-    def _reserve(self, ctx, n: int, m_in: int, m_out: int, f_out: int) -> dict:
-        if self._pid != os.getpid() or self._ctx is not ctx:
-            self._blocks, self._cap, self._ctx, self._pid = {}, 0, ctx, os.getpid()          # another process / context: its blocks are not ours to free
-        widths = dict(mc32=m_in, sp32=BINS, ap32=BINS, mc_out=m_out, sp_out=f_out)
-        if n > self._cap or any(self._blocks.get('w_' + k) != w for k, w in widths.items()):
-            self._free()
-            cap = max(n + n // 2, 64)
-            for k, w in widths.items():
-                self._blocks[k] = ctx.dev_alloc(cap * w)
-                self._blocks['w_' + k] = w
-            self._blocks['mask'] = ctx.dev_alloc(cap // 4 + 4)
-            self._cap = cap
-        return self._blocks
-
-    def _free(self) -> None:
-        if self._pid == os.getpid() and self._ctx is not None and self._ctx.handle is not None:
-            for k, p in self._blocks.items():
-                if not k.startswith('w_'):
-                    self._ctx.dev_free(p)
-        self._blocks, self._cap = {}, 0
 
     def close(self) -> None:
         """Frees the device blocks and the synthesizer in the process that created them; the voice changer and the shared handles stay."""
@@ -329,23 +352,6 @@ class Pipeline(object):
             self._gate_bank, self._pending = _crepe.CrepeStreamBank(model, 1), 0
         return self._gate_bank
 
-    def _gate_first_row(self, wave, handles, discard, advance=None, live: bool = False):
-        """`_resident_rows` with the gate in front (`_gate_first_rows` on one wave)."""
-        calls.setdefault('gated', 0)
-        if live:
-            self._reset_stream((True, False))
-        if advance is None:
-            out = _gate_first_rows(handles, self.acoustic_param, self.voice_changer, [wave], discard, self._reserve)
-        else:
-            adv = _spanned(advance, self._pending)
-            out = _gate_first_rows(handles, self.acoustic_param, self.voice_changer, [wave], discard, self._reserve, self._gate_tracker(handles[0]), [0],
-                                   [adv])
-            self._pending = 0 if out[4]['tracked'][0] else _spanned(advance, self._pending)
-        ctx, b, fo, f0s, record = out
-        _gated(calls, 1 - sum(record['tracked']))
-        self.last_gate = record
-        return ctx, b, int(fo[-1]), f0s[0]
-
     # ---- which way a call goes
     def _encode_args(self):
         p = self.acoustic_param
@@ -362,19 +368,6 @@ class Pipeline(object):
             return False
         # the chain analyses wave.astype(float64): the one float32 upload serves it only when both hold the same values
         return w.dtype == numpy.float32 or bool(numpy.array_equal(w.astype(numpy.float32).astype(w.dtype), w))
-
-    def _world_row(self, wave, handles, discard, gate_first: bool):
-        """WORLD mode's `_resident_rows` / `_gate_first_row` (`_world_rows` on one wave) -> ((context, blocks, frames, f0), track); the first is
-        None when the track of the f0 callable does not fit and the call takes the composed path with that track."""
-        rows, tracks = _world_rows(handles, self.acoustic_param, self.voice_changer, [wave], discard, self._reserve, self.f0_fn, gate_first)
-        if rows is None:
-            return None, tracks.get(0)
-        ctx, b, fo, f0s, record = rows
-        if gate_first:
-            calls.setdefault('gated', 0)
-            _gated(calls, 1 - sum(record['tracked']))
-            self.last_gate = record
-        return (ctx, b, int(fo[-1]), f0s[0]), tracks.get(0)
 
     def _resident_handles(self, wave):
         """-> (model, analyzer, core, gate thresholds, hop, fft_length of the gate) when every condition of the resident path holds, else None."""
@@ -416,8 +409,7 @@ class Pipeline(object):
         """-> (context, blocks, frames, f0 float64 [frames]: the converted track, zeros on the silent frames).  advance (an int): the track comes
         from the pipeline's `CrepeStream` -- the same bits, with the rows of the frames shared with the previous buffer kept."""
         model, analyzer, core, (p_eff, p_all), hop, gate_fft = handles
-        vc, p = self.voice_changer, self.acoustic_param
-        ac = vc.acoustic_converter
+        p = self.acoustic_param
         fs = int(wave.sampling_rate)
         x = numpy.ascontiguousarray(wave.wave, dtype=numpy.float32)
         tracker = model if advance is None else self._stream_of(model)
@@ -427,24 +419,41 @@ class Pipeline(object):
         b = self._reserve(ctx, n, p.order + 1, core.M, core.F)
         analyzer.extract_resident(trk.wave, trk.samples, trk.f0, trk.t, n, b['mc32'], b['sp32'], b['ap32'])
         track = trk.download()[1]
-        discard = (int(discard[0]), int(discard[1])) if os.environ.get('RY_DISCARD_HINT', '1') != '0' else (0, 0)
-        if core.discard != discard:
-            core.set_discard(*discard)
-        effective, n_eff = core.enqueue_wave_device(trk.wave, trk.samples, hop, gate_fft, p_eff, p_all, b['mc32'], n, b['mc_out'], b['sp_out'],
-                                                    b['mask'], SP_FLOOR)
-        # f0: the numpy operations of the separate calls -- astype_only_float(dtype), indexing(effective), the F0Converter, combine_silent's
-        # float32 zeros, the synthesizer's float64 cast
-        from yukarin.acoustic_feature import AcousticFeature
-        f0_eff = track[:, None].astype(p.dtype)[effective]
-        if n_eff and ac.f0_converter is not None:
-            f0_eff = ac.f0_converter.convert(AcousticFeature(f0=f0_eff)).f0
-        f0 = numpy.zeros((n, 1), numpy.float32)
-        f0[effective] = f0_eff
-        return ctx, b, n, numpy.ascontiguousarray(f0.ravel(), dtype=numpy.float64)
+        _apply_discard(core, discard)
+        effective, _ = core.enqueue_wave_device(trk.wave, trk.samples, hop, gate_fft, p_eff, p_all, b['mc32'], n, b['mc_out'], b['sp_out'],
+                                                b['mask'], SP_FLOOR)
+        return ctx, b, n, _converted_f0(self.voice_changer.acoustic_converter, p.dtype, track, effective)
 
-    @staticmethod
-    def _at(block: int, row: int):
-        return _lib._fptr(int(block) + int(row) * BINS * 4)
+    def _rows(self, wave, discard, gate_first: Optional[bool], advance=None, live: bool = False):
+        """Which way a call goes, and the resident chain when it goes that way -> ((context, blocks, frames, f0) or None: the composed path, the
+        (f0, t) the f0 callable of WORLD mode already returned for this wave or None).  gate_first None: the constructor's.  live (`push`): the
+        call belongs to a stream, and a buffer in one form of CREPE mode drops the rows the other form's tracker keeps."""
+        handles = self._resident_handles(wave)
+        if handles is None:
+            return None, None
+        gate_first = self.gate_first if gate_first is None else gate_first
+        args = (handles, self.acoustic_param, self.voice_changer, [wave], discard, self._reserve)
+        if self.f0_mode == 'world':                                        # `advance` is ignored: there are no kept activation rows
+            rows, tracks = _world_rows(*args, self.f0_fn, gate_first)
+            if rows is None:
+                return None, tracks.get(0)                                 # the callable's track does not fit: the composed path, with that track
+        elif not gate_first:
+            if live:
+                self._reset_stream((False, True))
+            return self._resident_rows(wave, handles, discard, advance), None
+        else:
+            if live:
+                self._reset_stream((True, False))
+            if advance is None:
+                rows = _gate_first_rows(*args)
+            else:                                                          # against the window the tracker keeps: the buffers skipped since are spanned
+                adv = _spanned(advance, self._pending)
+                rows = _gate_first_rows(*args, self._gate_tracker(handles[0]), [0], [adv])
+                self._pending = 0 if rows[4]['tracked'][0] else adv
+        ctx, b, fo, f0s, record = rows
+        if record is not None:
+            _note_gate(self, calls, record)
+        return (ctx, b, int(fo[-1]), f0s[0]), None
 
     def _composed_extract(self, wave, track=None):
         """The encode stage of the separate calls -> the feature with its wave.  WORLD mode: `world_analysis.extract` over a class whose
@@ -474,29 +483,14 @@ class Pipeline(object):
         """`yukarin.Wave` in (mono float32 at the input rate for the resident path) -> `yukarin.Wave` (float64) at the output rate.  gate_first
         (None: the constructor's): the gate before the encode stage; the composed path ignores it."""
         from yukarin import Wave
-        handles = self._resident_handles(wave)
-        rows = track = None
-        if handles is not None and self.f0_mode == 'world':
-            rows, track = self._world_row(wave, handles, (0, 0), self.gate_first if gate_first is None else gate_first)
-            if rows is None:
-                handles = None                                             # the callable's track does not fit: the composed path, with that track
-        if handles is None:
+        rows, track = self._rows(wave, (0, 0), gate_first)
+        if rows is None:
             calls['composed'] += 1
             return world_synth.decode(self._vocoder, self._composed_feature(wave, (0, 0), track))
         calls['resident'] += 1
-        if rows is not None:
-            ctx, b, n, f0 = rows
-        elif self.gate_first if gate_first is None else gate_first:
-            ctx, b, n, f0 = self._gate_first_row(wave, handles, (0, 0))
-        else:
-            ctx, b, n, f0 = self._resident_rows(wave, handles, (0, 0))
+        ctx, b, n, f0 = rows
         ctx.mask_rows(b['ap32'], b['mask'], n, BINS)
-        lib, h = self.synth._get()
-        y = numpy.empty(max(self.synth.length(n), 1), numpy.float64)
-        got = ctypes.c_int()
-        lib.check(lib.dll.ry_synth_run(h, f0.ctypes.data_as(world_synth._DP), self._at(b['sp_out'], 0), self._at(b['ap32'], 0), n, BINS, 1,
-                                       y.ctypes.data_as(world_synth._DP), y.size, ctypes.byref(got)))
-        return Wave(y[:got.value], sampling_rate=self.voice_changer.output_sampling_rate)
+        return Wave(self.synth.synthesize(f0, *_device_rows(b, 0, [n])[0]), sampling_rate=self.voice_changer.output_sampling_rate)
 
     def push(self, wave, discard=(0, 0), final: bool = False, advance: Optional[int] = None, out_gate=None, gate_first: Optional[bool] = None):
         """One buffer of a live stream: the wave is encoded and converted on its own (as `EncodeStream` / `ConvertStream` do per buffer), the rows
@@ -516,63 +510,42 @@ class Pipeline(object):
         tracked, which so spans the buffers skipped.  The composed path ignores the flag."""
         from yukarin import Wave
         front, back = int(discard[0]), int(discard[1])
-        handles = self._resident_handles(wave)
-        rows = track = None
-        if handles is not None and self.f0_mode == 'world':               # `advance` is ignored: there are no kept activation rows
-            rows, track = self._world_row(wave, handles, (front, back), self.gate_first if gate_first is None else gate_first)
-            if rows is None:
-                handles = None                                             # the callable's track does not fit: the composed path, with that track
-        if handles is None:
+        rate = self.voice_changer.output_sampling_rate
+        rows, track = self._rows(wave, (front, back), gate_first, advance, live=True)
+        out = numpy.empty(0, numpy.float64)
+        if rows is None:
             calls['composed'] += 1
             self._reset_stream()
             f = self._composed_feature(wave, (front, back), track)
             k0, k1 = front, len(f.f0) - back
-            out = numpy.empty(0, numpy.float64)
             if k1 > k0:
                 picked = f.pick(k0, k1, keys=('f0', 'sp', 'ap'))
                 out = world_synth.decode_realtime(self._vocoder, picked).wave
         else:
             calls['resident'] += 1
-            if rows is not None:
-                ctx, b, n, f0 = rows
-            elif self.gate_first if gate_first is None else gate_first:
-                ctx, b, n, f0 = self._gate_first_row(wave, handles, (front, back), advance, live=True)
-            else:
-                self._reset_stream((False, True))
-                ctx, b, n, f0 = self._resident_rows(wave, handles, (front, back), advance)
+            ctx, b, n, f0 = rows
             k0, k1 = front, n - back
             if _gate_on_card(out_gate, ctx):
-                block = _sample_block(self, self.synth.bound(k1 - k0, final))
+                block = self._sample_block(self.synth.bound(k1 - k0, final))
                 got = 0
                 if k1 > k0:
                     ctx.mask_rows(b['ap32'], b['mask'], n, BINS, k0, k1)
-                    rows = [world_synth.DeviceRows(b[k] + k0 * BINS * 4, k1 - k0) for k in ('sp_out', 'ap32')]
-                    got = self.synth.push_device(f0[k0:k1], rows[0], rows[1], block, 0)
+                    got = self.synth.push_device(f0[k0:k1], *_device_rows(b, k0, [k1 - k0])[0], block, 0)
                 if final:
                     got += self.synth.flush_device(block, got)             # behind the push, in the same block
                     self._reset_stream()
                 routes['gate_device'] += 1
                 out = out_gate.push_device(block.address, got)             # the one wait for the samples, and only when a chunk is complete
-                return Wave(wave=out if out is not None else numpy.empty(0, out_gate.dtype), sampling_rate=self.voice_changer.output_sampling_rate)
-            out = numpy.empty(0, numpy.float64)
+                return Wave(wave=out if out is not None else numpy.empty(0, out_gate.dtype), sampling_rate=rate)
             if k1 > k0:
                 ctx.mask_rows(b['ap32'], b['mask'], n, BINS, k0, k1)
-                lib, h = self.synth._get()
-                f0 = numpy.ascontiguousarray(f0[k0:k1])
-                y = numpy.empty(max(int(lib.dll.ry_synth_bound(h, k1 - k0, 0)), 1), numpy.float64)
-                got = ctypes.c_int()
-                lib.check(lib.dll.ry_synth_push(h, f0.ctypes.data_as(world_synth._DP), self._at(b['sp_out'], k0), self._at(b['ap32'], k0), k1 - k0, BINS, 1,
-                                                y.ctypes.data_as(world_synth._DP), y.size, ctypes.byref(got)))
-                out = y[:got.value].copy()
+                out = self.synth.push(f0[k0:k1], *_device_rows(b, k0, [k1 - k0])[0])
         if final:
             out = numpy.concatenate([out, self.synth.flush()])
             self._reset_stream()
         if out_gate is not None:
-            routes['gate_host'] += 1
-            out = out_gate.push(out)
-            if out is None:
-                out = numpy.empty(0, out_gate.dtype)
-        return Wave(wave=out, sampling_rate=self.voice_changer.output_sampling_rate)
+            out = _through_host_gate(out_gate, out)
+        return Wave(wave=out, sampling_rate=rate)
 
     def flush(self):
         """Ends the live stream: the samples `push` still held back; the next `push` starts a new signal."""
@@ -584,10 +557,10 @@ class Pipeline(object):
 calls_many = {'resident': 0, 'composed': 0}     # which way a `PipelineBank.convert_waves` / `push` went, counted per call
 
 
-class PipelineBank(object):
+class PipelineBank(_BlockOwner):
     """`Pipeline` for the B streams one process serves, with ONE chain per buffer instead of B: `CrepeModel.track_many` (one upload of all waves) ->
     `Analyzer.extract_many_resident` (one verdict) -> `VcCore.enqueue_waves_device` (one gate, one wait for all counts, then every wave's window) ->
-    `ry_mask_rows` / `ry_gather_rows` -> `ry_synth_run_many` (`convert_waves`) or one `ry_synth_bank_push` of a `StreamBank` with one seed per stream
+    `ry_mask_rows` / `ry_gather_rows` -> `Synthesizer.synthesize_many` (`convert_waves`) or one `push` of a `StreamBank` with one seed per stream
     (`push`).  What stream b returns, call by call, has the bits a lone `Pipeline(seed=seeds[b])` returns for the same waves, discards and flushes,
     whatever the other streams do.  `seeds=None`: every stream has RY_SYNTH_SEED.  `convert_waves` is a one-shot call outside the streams: its
     synthesizer has the seed of stream 0.  The resident chain runs when every wave of a call meets the conditions of `Pipeline`'s resident path and
@@ -615,31 +588,11 @@ class PipelineBank(object):
                                            ctx=world_synth.engine_for_tests.ctx)
         self.calls = calls_many
         self._live = [False] * self.n_streams                              # the stream holds frames of a signal that has not ended
-        self._blocks, self._cap, self._ctx, self._pid, self._table = {}, 0, None, None, None
+        _BlockOwner.__init__(self)
         self._crepe_bank = None                                            # `push(..., advance=a)`: the trackers that keep rows between buffers
         self._pending = [0] * self.n_streams                               # gate_first: the advance of the buffers of a stream skipped since its last tracked one
 
-    # ---- the blocks this object owns: grown, never shrunk, freed by `close` in the process that made them
-    def _reserve(self, ctx, n: int, m_in: int, m_out: int, f_out: int) -> dict:
-        if self._pid != os.getpid() or self._ctx is not ctx:
-            self._blocks, self._cap, self._ctx, self._pid, self._table = {}, 0, ctx, os.getpid(), None
-        widths = dict(mc32=m_in, sp32=BINS, ap32=BINS, mc_out=m_out, sp_out=f_out, sp_pack=BINS, ap_pack=BINS, rows=1)
-        if n > self._cap or any(self._blocks.get('w_' + k) != w for k, w in widths.items()):
-            self._free()
-            cap = max(n + n // 2, 64)
-            for k, w in widths.items():
-                self._blocks[k] = ctx.dev_alloc(cap * w)
-                self._blocks['w_' + k] = w
-            self._blocks['mask'] = ctx.dev_alloc(cap // 4 + 4)
-            self._cap = cap
-        return self._blocks
-
-    def _free(self) -> None:
-        if self._pid == os.getpid() and self._ctx is not None and self._ctx.handle is not None:
-            for k, p in self._blocks.items():
-                if not k.startswith('w_'):
-                    self._ctx.dev_free(p)
-        self._blocks, self._cap, self._table = {}, 0, None
+    _more_widths = dict(sp_pack=BINS, ap_pack=BINS, rows=1)             # the picked rows of a `push`, packed stream by stream, and their index table
 
     def close(self) -> None:
         """Frees the device blocks, the stream bank and the one-shot synthesizer in the process that created them; the voice changer and the shared
@@ -669,34 +622,6 @@ class PipelineBank(object):
             for s in streams:
                 self._crepe_bank.reset(s)
 
-    def _gate_first_rows(self, waves, handles, discard, part=None, advance=None):
-        """`_resident_rows` with the gate in front of the encode stage (`_gate_first_rows` of the module)."""
-        calls_many.setdefault('gated', 0)
-        args = (handles, self.acoustic_param, self.voice_changer, waves, discard, self._reserve)
-        if advance is None:
-            ctx, b, fo, f0s, record = _gate_first_rows(*args)
-        else:
-            adv = [_spanned(a, self._pending[s]) for s, a in zip(part, advance)]
-            ctx, b, fo, f0s, record = _gate_first_rows(*args, self._trackers_of(handles[0]), part, adv)
-            for i, s in enumerate(part):
-                self._pending[s] = 0 if record['tracked'][i] else adv[i]
-        _gated(calls_many, len(waves) - sum(record['tracked']))
-        self.last_gate = dict(record, streams=list(part) if part is not None else None)
-        return ctx, b, fo, f0s
-
-    def _world_rows(self, waves, handles, discard, part, gate_first: bool):
-        """WORLD mode's `_resident_rows` / `_gate_first_rows` (`_world_rows` of the module) -> ((context, blocks, frame offsets, f0s), tracks); the
-        first is None when a track does not fit and the call takes the composed path with the tracks the callable already returned."""
-        rows, tracks = _world_rows(handles, self.acoustic_param, self.voice_changer, waves, discard, self._reserve, self.f0_fn, gate_first)
-        if rows is None:
-            return None, tracks
-        ctx, b, fo, f0s, record = rows
-        if gate_first:
-            calls_many.setdefault('gated', 0)
-            _gated(calls_many, len(waves) - sum(record['tracked']))
-            self.last_gate = dict(record, streams=list(part) if part is not None else None)
-        return (ctx, b, fo, f0s), tracks
-
     # ---- which way a call goes
     def _handles(self, waves):
         """The handles of the resident chain when every wave meets `Pipeline._resident_handles`, all share one rate and the bank lives in their
@@ -714,42 +639,57 @@ class PipelineBank(object):
     # ---- the resident chain up to the rows the synthesizers read
     def _resident_rows(self, waves, handles, discard, part=None, advance=None):
         """-> (context, blocks, frame offsets int32 [waves + 1], [f0 float64 [frames_i]: the converted track of wave i, zeros on the silent frames]).
-        part, advance (`push(..., advance=a)`): wave i is the next buffer of stream part[i], and the tracks come from the bank's `CrepeStreamBank`
-        -- the same bits, with the rows of the frames shared with that stream's previous buffer kept."""
+        part, advance (`push(..., advance=a)`): wave i is the next buffer of stream part[i], advance[i] samples on from the window that stream's
+        tracker keeps, and the tracks come from the bank's `CrepeStreamBank` -- the same bits, with the rows of the shared frames kept."""
         model, analyzer, core, (p_eff, p_all), hop, gate_fft = handles
-        vc, p = self.voice_changer, self.acoustic_param
-        ac = vc.acoustic_converter
+        p, ac = self.acoustic_param, self.voice_changer.acoustic_converter
         fs = int(waves[0].sampling_rate)
         xs = [numpy.ascontiguousarray(w.wave, dtype=numpy.float32) for w in waves]
         if advance is None:
             trk = model.track_many(xs, fs, _crepe.hop_length(p.frame_period), p.frame_period, threshold=encode.threshold, device=True)   # the one upload
         else:
-            windows = [None] * self.n_streams
-            for s, x in zip(part, xs):
-                windows[s] = x
+            windows, advances = [None] * self.n_streams, [None] * self.n_streams
+            for s, x, a in zip(part, xs, advance):
+                windows[s], advances[s] = x, a
             trk, _ = self._trackers_of(model).track_many(windows, fs, _crepe.hop_length(p.frame_period), p.frame_period, threshold=encode.threshold,
-                                                         advances=advance, device=True)
+                                                         advances=advances, device=True)
         n, ctx, fo = trk.frames, core.stage1.ctx, trk.frame_offsets
         b = self._reserve(ctx, n, p.order + 1, core.M, core.F)
         analyzer.extract_many_resident(trk.wave, trk.sample_offsets, trk.f0, trk.t, fo, b['mc32'], b['sp32'], b['ap32'])
         tracks = trk.download()
-        discard = (int(discard[0]), int(discard[1])) if os.environ.get('RY_DISCARD_HINT', '1') != '0' else (0, 0)
-        if core.discard != discard:
-            core.set_discard(*discard)
-        effective, n_eff = core.enqueue_waves_device(trk.wave, trk.sample_offsets, fo, hop, gate_fft, p_eff, p_all, b['mc32'], b['mc_out'], b['sp_out'],
-                                                     b['mask'], SP_FLOOR)
-        # f0, wave by wave: the numpy operations of `Pipeline._resident_rows`
-        from yukarin.acoustic_feature import AcousticFeature
-        f0s = []
-        for i, (_, track) in enumerate(tracks):
-            eff = effective[fo[i]:fo[i + 1]]
-            f0_eff = track[:, None].astype(p.dtype)[eff]
-            if n_eff[i] and ac.f0_converter is not None:
-                f0_eff = ac.f0_converter.convert(AcousticFeature(f0=f0_eff)).f0
-            f0 = numpy.zeros((len(eff), 1), numpy.float32)
-            f0[eff] = f0_eff
-            f0s.append(numpy.ascontiguousarray(f0.ravel(), dtype=numpy.float64))
-        return ctx, b, fo, f0s
+        _apply_discard(core, discard)
+        effective, _ = core.enqueue_waves_device(trk.wave, trk.sample_offsets, fo, hop, gate_fft, p_eff, p_all, b['mc32'], b['mc_out'], b['sp_out'],
+                                                 b['mask'], SP_FLOOR)
+        return ctx, b, fo, [_converted_f0(ac, p.dtype, track, effective[fo[i]:fo[i + 1]]) for i, (_, track) in enumerate(tracks)]
+
+    def _rows(self, waves, discard, gate_first: Optional[bool], part=None, advance=None):
+        """Which way a call goes, and the resident chain when it goes that way -> ((context, blocks, frame offsets, f0s) or None: the composed
+        path, {wave index: the (f0, t) the f0 callable of WORLD mode already returned}).  gate_first None: the constructor's.  part, advance
+        (`push`): wave i is the next buffer of stream part[i], with its advance (or advance None); a stream's advance spans the buffers of it that
+        gate_first calls skipped since it was last tracked (`_pending`), whichever form tracks it."""
+        handles = self._handles(waves)
+        if handles is None:
+            return None, {}
+        gate_first = self.gate_first if gate_first is None else gate_first
+        args = (handles, self.acoustic_param, self.voice_changer, waves, discard, self._reserve)
+        if self.f0_mode == 'world':                                        # `advance` is ignored: there are no kept activation rows
+            rows, tracks = _world_rows(*args, self.f0_fn, gate_first)
+            if rows is None:
+                return None, tracks                                        # a track does not fit: the composed path, with the tracks made so far
+        else:
+            adv = None if advance is None else [_spanned(a, self._pending[s]) for s, a in zip(part, advance)]
+            if gate_first:
+                rows = _gate_first_rows(*args, None if adv is None else self._trackers_of(handles[0]), part, adv)
+                if adv is not None:
+                    for i, s in enumerate(part):
+                        self._pending[s] = 0 if rows[4]['tracked'][i] else adv[i]
+            else:
+                for s in part or ():
+                    self._pending[s] = 0
+                rows = self._resident_rows(waves, handles, discard, part, adv) + (None,)
+        if rows[4] is not None:
+            _note_gate(self, calls_many, dict(rows[4], streams=list(part) if part is not None else None))
+        return rows[:4], {}
 
     # ---- calls
     def convert_waves(self, waves, gate_first: Optional[bool] = None) -> list:
@@ -760,31 +700,16 @@ class PipelineBank(object):
         if not waves:
             return []
         rate = self.voice_changer.output_sampling_rate
-        handles = self._handles(waves)
-        gated = self.gate_first if gate_first is None else gate_first
-        done, tracks = None, {}
-        if handles is not None and self.f0_mode == 'world':
-            done, tracks = self._world_rows(waves, handles, (0, 0), None, gated)
-            if done is None:
-                handles = None                                             # a track does not fit: the composed path, with the tracks made so far
-        if handles is None:
+        rows, tracks = self._rows(waves, (0, 0), gate_first)
+        if rows is None:
             calls_many['composed'] += 1
             return [world_synth.decode(self._one._vocoder, self._one._composed_feature(w, (0, 0), tracks.get(i))) for i, w in enumerate(waves)]
         calls_many['resident'] += 1
-        rows = self._gate_first_rows if gated else self._resident_rows
-        ctx, b, fo, f0s = done if done is not None else rows(waves, handles, (0, 0))
-        n = int(fo[-1])
-        ctx.mask_rows(b['ap32'], b['mask'], n, BINS)
-        synth = self._one.synth
-        lib, h = synth._get()
-        counts = numpy.ascontiguousarray(numpy.diff(fo), dtype=numpy.int32)
-        f0 = numpy.ascontiguousarray(numpy.concatenate(f0s))
-        y = numpy.empty(max(sum(synth.length(int(k)) for k in counts), 1), numpy.float64)
-        off = numpy.zeros(len(waves) + 1, numpy.int64)
-        lib.check(lib.dll.ry_synth_run_many(h, f0.ctypes.data_as(world_synth._DP), Pipeline._at(b['sp_out'], 0), Pipeline._at(b['ap32'], 0),
-                                            counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(waves), BINS, 1, y.ctypes.data_as(world_synth._DP),
-                                            y.size, off.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
-        return [Wave(y[off[i]:off[i + 1]].copy(), sampling_rate=rate) for i in range(len(waves))]
+        ctx, b, fo, f0s = rows
+        ctx.mask_rows(b['ap32'], b['mask'], int(fo[-1]), BINS)
+        # consecutive rows of one block: `synthesize_many` reads them in place, in one device call
+        items = [(f0, sp, ap) for f0, (sp, ap) in zip(f0s, _device_rows(b, 0, numpy.diff(fo)))]
+        return [Wave(y, sampling_rate=rate) for y in self._one.synth.synthesize_many(items)]
 
     def _final(self, final):
         final = sorted(set(int(s) for s in (final or ())))
@@ -829,14 +754,10 @@ class PipelineBank(object):
             if final:
                 outs = self.bank.flush(final)
         else:
-            handles = self._handles([waves[s] for s in part])
-            done, tracks = None, {}
-            if handles is not None and self.f0_mode == 'world':           # `advance` is ignored: there are no kept activation rows
-                done, tracks = self._world_rows([waves[s] for s in part], handles, (front, back), part,
-                                                self.gate_first if gate_first is None else gate_first)
-                if done is None:
-                    handles = None                                         # a track does not fit: the composed path, with the tracks made so far
-            if handles is None:
+            if advance is not None:                                        # per wave of the call
+                advance = [advance if isinstance(advance, (int, numpy.integer)) else advance[s] for s in part]
+            rows, tracks = self._rows([waves[s] for s in part], (front, back), gate_first, part, advance)
+            if rows is None:
                 calls_many['composed'] += 1
                 self._reset_trackers(part)
                 for i, s in enumerate(part):
@@ -856,21 +777,7 @@ class PipelineBank(object):
                         outs[s] = got[s]
             else:
                 calls_many['resident'] += 1
-                per = advance
-                if advance is not None:                                    # per wave of the call: against the window the stream's tracker keeps
-                    per = [advance if isinstance(advance, (int, numpy.integer)) else advance[s] for s in part]
-                if done is not None:
-                    ctx, b, fo, f0s = done
-                elif self.gate_first if gate_first is None else gate_first:
-                    ctx, b, fo, f0s = self._gate_first_rows([waves[s] for s in part], handles, (front, back), part, per)
-                else:
-                    if advance is not None and any(self._pending[s] != 0 for s in part):      # buffers a gate_first call skipped lie in between
-                        advance = [None] * self.n_streams
-                        for s, a in zip(part, per):
-                            advance[s] = _spanned(a, self._pending[s])
-                    for s in part:
-                        self._pending[s] = 0
-                    ctx, b, fo, f0s = self._resident_rows([waves[s] for s in part], handles, (front, back), part, advance)
+                ctx, b, fo, f0s = rows
                 picks = [(int(fo[i]) + front, int(fo[i + 1]) - back) for i in range(len(part))]
                 picks = [(k0, max(k1, k0)) for k0, k1 in picks]
                 total = sum(k1 - k0 for k0, k1 in picks)
@@ -892,10 +799,10 @@ class PipelineBank(object):
                             at += k1 - k0
                 if _gate_on_card(out_gate, ctx):
                     took = [s for s in range(self.n_streams) if items[s] is not None or s in final]
-                    block = _sample_block(self, sum(self.bank.bound(s, 0 if items[s] is None else items[s][0].size, s in final) for s in took))
+                    block = self._sample_block(sum(self.bank.bound(s, 0 if items[s] is None else items[s][0].size, s in final) for s in took))
                     on_card = (block, self.bank.push_device(items, final, block) if took else numpy.zeros(self.n_streams + 1, numpy.int64))
                 elif total > 0 or final:
-                    outs = self.bank.push(items, final=final)              # one ry_synth_bank_push: the packed rows follow one another and are read in place
+                    outs = self.bank.push(items, final=final)              # one device call: the packed rows follow one another and are read in place
         for s in part:
             self._live[s] = True
         for s in final:
@@ -905,8 +812,7 @@ class PipelineBank(object):
             routes['gate_device'] += 1
             outs = [o if o is not None else numpy.empty(0, out_gate.dtype) for o in out_gate.push_device(on_card[0].address, on_card[1])]
         elif out_gate is not None:
-            routes['gate_host'] += 1
-            outs = [o if o is not None else numpy.empty(0, out_gate.dtype) for o in out_gate.push(outs)]
+            outs = _through_host_gate(out_gate, outs)
         return [Wave(wave=o, sampling_rate=rate) for o in outs]
 
     def flush(self, stream=None):
@@ -1125,15 +1031,11 @@ class LivePipeline(object):
         if isinstance(out, Wave):
             return out                                                     # the gate read the samples on the card
         if out_gate is not None:
-            routes['gate_host'] += 1
-            out = out_gate.push(out)
-            if out is None:
-                out = numpy.empty(0, out_gate.dtype)
+            out = _through_host_gate(out_gate, out)
         return Wave(wave=out, sampling_rate=vc.output_sampling_rate)
 
     def _push_resident(self, handles, wave, track, n_enc, rows, samples, c_plan, c_rows, n_c, n_w, pad_c, keep, out_gate):
         from yukarin import Wave
-        from yukarin.acoustic_feature import AcousticFeature
         model, analyzer, core, (p_eff, p_all), hop, gate_fft = handles
         p, ac = self.acoustic_param, self.voice_changer.acoustic_converter
         fs, (ra, rb), (wa, wb), (k0, k1) = int(wave.sampling_rate), rows, samples, keep
@@ -1162,25 +1064,17 @@ class LivePipeline(object):
         w = self._window_blocks(ctx, n_c, n_w, p.order + 1)
         store.fetch(c_plan, ac.config.dataset.acoustic_param.frame_period, fs, w['mc'], w['ap'], w['wave'], n_c, n_w)
         self.transfers.append(('up', 'table', store.counts()['upload_bytes'] // 4))
-        discard = (pad_c, pad_c) if os.environ.get('RY_DISCARD_HINT', '1') != '0' else (0, 0)
-        if core.discard != discard:
-            core.set_discard(*discard)
-        effective, n_eff = core.enqueue_wave_device(w['wave'], n_w, hop, gate_fft, p_eff, p_all, w['mc'], n_c, b['mc_out'], b['sp_out'], b['mask'], SP_FLOOR)
+        _apply_discard(core, (pad_c, pad_c))
+        effective, _ = core.enqueue_wave_device(w['wave'], n_w, hop, gate_fft, p_eff, p_all, w['mc'], n_c, b['mc_out'], b['sp_out'], b['mask'], SP_FLOOR)
         self.transfers.append(('down', 'mask', n_c))
-        f0_in = self._concat(c_rows, [f['f0'] for f in self._features], (1,), numpy.float32)
-        f0_eff = f0_in[effective]
-        if n_eff and ac.f0_converter is not None:
-            f0_eff = ac.f0_converter.convert(AcousticFeature(f0=f0_eff)).f0
-        f0 = numpy.zeros((n_c, 1), numpy.float32)
-        f0[effective] = f0_eff
-        f0 = numpy.ascontiguousarray(f0.ravel(), dtype=numpy.float64)[k0:k1]
+        f0 = _converted_column(ac, self._concat(c_rows, [f['f0'] for f in self._features], (1,), numpy.float32), effective)[k0:k1]
         # decode: the plan hands on exactly the rows just converted
         self._outputs.append(dict(start=self._add[2], rows=k1 - k0))
         ctx.mask_rows(w['ap'], b['mask'], n_c, BINS, k0, k1)
         dev_rows = [world_synth.DeviceRows(base + k0 * BINS * 4, k1 - k0) for base in (b['sp_out'], w['ap'])]
         self.transfers.append(('up', 'f0', k1 - k0))
         if _gate_on_card(out_gate, ctx):
-            block = _sample_block(self._pipe, self.synth.bound(k1 - k0, False))
+            block = self._pipe._sample_block(self.synth.bound(k1 - k0, False))
             got = self.synth.push_device(f0, dev_rows[0], dev_rows[1], block, 0)
             routes['gate_device'] += 1
             out = out_gate.push_device(block.address, got)
