@@ -902,6 +902,46 @@ int ry_rowstore_debug_counts(ry_rowstore* store, long long* out);
 /* tests: NaN bit patterns in the table buffer and in every part of the rings that holds nothing live */
 int ry_rowstore_debug_poison(ry_rowstore* store);
 
+/* ---- The row bank: the row store for the B live streams of one process.  B independent sets of the three rings, all of one shape, each with
+ * its own live range; every call names the streams it serves (stream_of [n], HOST, strictly ascending) and runs ONE launch for all of them.
+ * Semantics: INTEGRATION.md section 24, DESIGN.md section 26.  Refused by the create call: what the row store's refuses per stream, n_streams
+ * outside 1 .. 65536, more than 2^40 floats in one of the three arrays.  Every refusal of every call is made before anything is enqueued or
+ * changed for any stream; a repeated or descending stream index is one. */
+typedef struct ry_rowbank ry_rowbank;
+int ry_rowbank_create(ry_ctx* ctx, int n_streams, int mc_cols, int ap_cols, int cap_rows, int cap_samples, ry_rowbank** out);
+void ry_rowbank_destroy(ry_rowbank* bank);
+/* For entry i: rows [row0[i], row0[i] + n_rows[i]) of the SHARED device blocks mc_dev / ap_dev and samples [sample0[i], sample0[i] + n_samples[i])
+ * of the shared wave_dev (the blocks a many-wave encode leaves on the card) go behind what the rings of stream stream_of[i] hold, wrapping at the
+ * ring ends.  ONE launch whatever n is; up to six pieces travel in the kernel arguments, a longer table goes up in ONE upload that is waited
+ * for.  row_pos [n] / sample_pos [n]: where each segment starts in its stream's rings.  Refused per entry as the row store's append refuses. */
+int ry_rowbank_append(ry_rowbank* bank, int n, const int* stream_of, const float* mc_dev, const float* ap_dev, const int* row0, const int* n_rows,
+                      const float* wave_dev, const long long* sample0, const int* n_samples, int* row_pos, int* sample_pos);
+/* The convert windows of n streams, back to back in the layout ry_vc_enqueue_waves_device reads: entry i's mc rows from row frame_offsets[i] of
+ * mc_dst_dev, its samples from sample sample_offsets[i] of wave_dst_dev (n + 1 entries each, HOST, from 0, ascending).  Its spans are
+ * row_spans [row_span_offsets[i] .. row_span_offsets[i + 1]) and the like for the samples: (position in that stream's ring or -1 for a pad,
+ * destination offset relative to the entry's first row / sample, count); a pad writes +0.0f.  ONE upload, ONE launch, the upload alone is waited
+ * for.  Refused per entry as the row store's fetch refuses, with the entry's slice as the destination, and: offset tables that do not start at 0
+ * or fall.  ap is not fetched: the pick call below reads it. */
+int ry_rowbank_fetch(ry_rowbank* bank, int n, const int* stream_of, const int* row_spans, const int* row_span_offsets, const int* sample_spans,
+                     const int* sample_span_offsets, float* mc_dst_dev, float* wave_dst_dev, const int* frame_offsets, const long long* sample_offsets);
+/* The ap rows the synthesizers read, with the silence mask applied: for entry i the rows [keep[2 i], keep[2 i + 1]) of its convert window (the row
+ * spans of the fetch call) go to ap_pack_dev [pack_rows][ap_cols], entry after entry -- the order ry_synth_bank_push reads with on_device = 1.  A
+ * row is +0.0f where it lies in a pad span or where mask_dev[frame_offsets[i] + row] is 0 (the mask the window call wrote: this call goes behind
+ * it on the context stream), else the ring's row, word for word: what ry_rowstore_fetch, ry_mask_rows and the slice give, without the full ap
+ * window being written anywhere.  A kept row that no span covers is left as it was.  ONE launch; ONE upload, waited for, when a row is kept.
+ * Refused: what the fetch call refuses of the row tables, keep outside the window, pack_rows other than the sum of the kept rows. */
+int ry_rowbank_pick_ap(ry_rowbank* bank, int n, const int* stream_of, const int* row_spans, const int* row_span_offsets, const int* frame_offsets,
+                       const int* keep, const unsigned char* mask_dev, float* ap_pack_dev, int pack_rows);
+/* host bookkeeping only, per stream: the oldest rows / samples may be overwritten; forget every segment (stream -1: of all); the live counts */
+int ry_rowbank_retire(ry_rowbank* bank, int stream, int n_rows, int n_samples);
+int ry_rowbank_reset(ry_rowbank* bank, int stream);
+int ry_rowbank_held(ry_rowbank* bank, int stream, int* rows, int* samples);
+/* tests, as the row store's: the three arrays (stream b's rings start b * cap_rows * cols / b * cap_samples floats in); out[4] of the last
+ * append / fetch / pick; NaN bit patterns in the table buffers and in every part of every stream's rings that holds nothing live */
+int ry_rowbank_debug_buffers(ry_rowbank* bank, const float** mc_dev, const float** ap_dev, const float** wave_dev);
+int ry_rowbank_debug_counts(ry_rowbank* bank, long long* out);
+int ry_rowbank_debug_poison(ry_rowbank* bank);
+
 #ifdef __cplusplus
 }
 #endif

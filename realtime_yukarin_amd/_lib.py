@@ -86,6 +86,8 @@ ABI_SYMBOLS = (
     'ry_set_filter_build', 'ry_net_build_stats', 'ry_net_debug_filters', 'ry_debug_layer_filters',
     'ry_rowstore_create', 'ry_rowstore_destroy', 'ry_rowstore_append', 'ry_rowstore_retire', 'ry_rowstore_held', 'ry_rowstore_fetch', 'ry_rowstore_reset',
     'ry_rowstore_debug_buffers', 'ry_rowstore_debug_counts', 'ry_rowstore_debug_poison',
+    'ry_rowbank_create', 'ry_rowbank_destroy', 'ry_rowbank_append', 'ry_rowbank_fetch', 'ry_rowbank_pick_ap', 'ry_rowbank_retire', 'ry_rowbank_reset',
+    'ry_rowbank_held', 'ry_rowbank_debug_buffers', 'ry_rowbank_debug_counts', 'ry_rowbank_debug_poison',
 )
 
 
@@ -348,6 +350,18 @@ class Ry355Lib(object):
         d.ry_rowstore_debug_buffers.argtypes = [_VP, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP)]
         d.ry_rowstore_debug_counts.argtypes = [_VP, _LLP]
         d.ry_rowstore_debug_poison.argtypes = [_VP]
+        d.ry_rowbank_create.argtypes = [_VP, _CI, _CI, _CI, _CI, _CI, ctypes.POINTER(_VP)]
+        d.ry_rowbank_destroy.argtypes = [_VP]
+        d.ry_rowbank_destroy.restype = None
+        d.ry_rowbank_append.argtypes = [_VP, _CI, _IP, _FP, _FP, _IP, _IP, _FP, _LLP, _IP, _IP, _IP]
+        d.ry_rowbank_fetch.argtypes = [_VP, _CI, _IP, _IP, _IP, _IP, _IP, _FP, _FP, _IP, _LLP]
+        d.ry_rowbank_pick_ap.argtypes = [_VP, _CI, _IP, _IP, _IP, _IP, _IP, _UB, _FP, _CI]
+        d.ry_rowbank_retire.argtypes = [_VP, _CI, _CI, _CI]
+        d.ry_rowbank_reset.argtypes = [_VP, _CI]
+        d.ry_rowbank_held.argtypes = [_VP, _CI, _IP, _IP]
+        d.ry_rowbank_debug_buffers.argtypes = [_VP, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP)]
+        d.ry_rowbank_debug_counts.argtypes = [_VP, _LLP]
+        d.ry_rowbank_debug_poison.argtypes = [_VP]
         d.ry_analysis_debug_d4c.argtypes = [_VP, ctypes.POINTER(_LL), _DP, _CI, _IP]
         d.ry_net_profile_window.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RyKernelStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         d.ry_net_debug_activation.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]

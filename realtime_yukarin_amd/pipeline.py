@@ -832,7 +832,208 @@ class PipelineBank(_BlockOwner):
         return [Wave(wave=o, sampling_rate=rate) for o in outs]
 
 
-class LivePipeline(object):
+class _LiveState(object):
+    """The host state of ONE stream of the three-stream live loop and every rule that reads it, stated once for `LivePipeline` and
+    `LivePipelineBank`: the clocks of the three workers, the lists `EncodeStream` / `ConvertStream` / `DecodeStream` keep, the plans
+    (`streams.fetch_plan` over them) and the composed path, which is all host arrays.  Nothing here touches the card."""
+
+    def __init__(self, voice_changer, acoustic_param, f0_mode: str, time_length: float, extra):
+        from . import streams
+        self.streams = streams
+        self.voice_changer, self.acoustic_param, self.f0_mode = voice_changer, acoustic_param, f0_mode
+        self.time_length, self.extra = time_length, tuple(extra)
+        self.start()
+
+    def start(self) -> None:
+        """A new signal: the workers' clocks at their first values, no segment anywhere."""
+        self.add = list(self.extra)                                        # `start_time = extra_time` of the three workers
+        self.now = [0., 0., 0.]                                            # `StreamWrapper._current_time` of the three streams
+        self.inputs, self.features, self.outputs = [], [], []              # EncodeStream / ConvertStream / DecodeStream .stream
+        self.mode = None                                                   # None until the first push, then 'resident' or 'composed'
+
+    # ---- rates and pads of the three streams, as their constructors take them
+    def rates(self):
+        vc, p = self.voice_changer, self.acoustic_param
+        gp = vc.acoustic_converter.config.dataset.acoustic_param
+        sp = vc.super_resolution.config.dataset.param.acoustic_feature_param
+        return 1000 // p.frame_period, 1000 // gp.frame_period, 1000 // sp.frame_period
+
+    @staticmethod
+    def inner(pad: int, n: int):
+        """`pick(data, pad, -pad)` of n elements as numpy slices it (the whole when pad is 0: the streams then do not pick)."""
+        return (0, n) if pad <= 0 else _LiveState.clip(pad, -pad, n)
+
+    @staticmethod
+    def clip(first, last, n):
+        a, b, _ = slice(first, last).indices(n)
+        return a, max(a, b)
+
+    def frames(self, n_samples: int, fs) -> int:
+        p = self.acoustic_param
+        if n_samples < 1:
+            return 0
+        if self.f0_mode == 'world':
+            return world_analysis.harvest_frames(n_samples, fs, p.frame_period)
+        return _crepe.track_frames(n_samples, fs, _crepe.hop_length(p.frame_period))
+
+    # ---- host arrays by plan: what `concat` of the picked segments and the pads holds
+    @staticmethod
+    def concat(spans, arrays, width, dtype):
+        parts = [numpy.zeros((b - a,) + width, dtype) if i < 0 else arrays[i][a:b] for i, a, b in spans]
+        return numpy.concatenate(parts)
+
+    def take(self, buffer):
+        """The encode worker's input stage for one buffer of `time_length` seconds (a float32 array at the vocoder's rate, or a `yukarin.Wave`):
+        it joins the kept inputs, the encode window is assembled by the plan and what no later window reaches goes -> the window as a `Wave`."""
+        from yukarin import Wave
+        S, T = self.streams, self.time_length
+        fs = int(buffer.sampling_rate) if hasattr(buffer, 'sampling_rate') else int(self.acoustic_param.sampling_rate)
+        x = numpy.asarray(buffer.wave if hasattr(buffer, 'wave') else buffer)
+        self.inputs.append((self.add[0], x))
+        self.add[0] += T
+        in_plan = S.row_spans(S.fetch_plan([(s, len(a)) for s, a in self.inputs], self.now[0], T, self.extra[0], fs), [len(a) for _, a in self.inputs])
+        window = self.concat(in_plan, [a for _, a in self.inputs], (), numpy.float32)            # WaveSegmentMethod.pad: float32 zeros
+        self.now[0] += T
+        del self.inputs[:S.retire([(s, len(a)) for s, a in self.inputs], self.now[0], T, self.extra[0], fs)]
+        return Wave(window, fs)
+
+    def plans(self, n_enc: int, n_window: int, fs):
+        """Everything the stream arithmetic decides for this buffer, from the clocks and the lengths alone: the rows / samples `EncodeStream` picks
+        of an encode window of n_enc frames, the convert window's plan with its clipped row and sample spans and their totals, the convert pad
+        and the rows `ConvertStream` picks, and the decode window's clocks and spans."""
+        S, p, T = self.streams, self.acoustic_param, self.time_length
+        rate_e, rate_c, rate_d = self.rates()
+        gp = self.voice_changer.acoustic_converter.config.dataset.acoustic_param
+        pad_e = round(self.extra[0] * rate_e)
+        ra, rb = self.inner(pad_e, n_enc)
+        wa, wb = (0, n_window) if pad_e <= 0 else self.clip(round(pad_e * p.frame_period / 1000 * fs), round(-pad_e * p.frame_period / 1000 * fs), n_window)
+        clocks = [(f['start'], f['rows']) for f in self.features] + [(self.add[1], rb - ra)]
+        sizes = [f['samples'] for f in self.features] + [wb - wa]
+        c_plan = S.fetch_plan(clocks, self.now[1], T, self.extra[1], rate_c)
+        c_rows = S.row_spans(c_plan, [n for _, n in clocks])
+        c_samples = S.wave_spans(c_plan, gp.frame_period, fs, sizes)
+        n_c, n_w = S.span_count(c_rows), S.span_count(c_samples)
+        pad_c = round(self.extra[1] * rate_c)
+        k0, k1 = self.inner(pad_c, n_c)
+        d_clocks = [(o['start'], o['rows']) for o in self.outputs] + [(self.add[2], k1 - k0)]
+        d_rows = S.row_spans(S.fetch_plan(d_clocks, self.now[2], T, self.extra[2], rate_d), [n for _, n in d_clocks])
+        return (ra, rb), (wa, wb), c_plan, c_rows, c_samples, n_c, n_w, pad_c, (k0, k1), d_clocks, d_rows
+
+    def fits_resident(self, plans) -> bool:
+        """The stream's part of the resident path's conditions: the signal has not been composed, the buffer leaves rows and samples to convert,
+        and the decode plan hands on exactly the rows just converted."""
+        (ra, rb), _, _, _, _, _, n_w, _, (k0, k1), d_clocks, d_rows = plans
+        return self.mode != 'composed' and rb > ra and k1 > k0 and n_w > 0 and self.streams.is_identity(d_rows, len(d_clocks) - 1, k1 - k0)
+
+    def add_resident(self, f0_track, plans) -> None:
+        """The segment a resident buffer leaves on the host: its clock, its sizes and its f0 column (the rows and the wave are in the store)."""
+        (ra, rb), (wa, wb) = plans[0], plans[1]
+        self.features.append(dict(start=self.add[1], rows=rb - ra, samples=wb - wa, f0=f0_track[:, None].astype(self.acoustic_param.dtype)[ra:rb]))
+
+    def resident_f0(self, plans, effective):
+        """The converted f0 of the rows `ConvertStream` picks, by the convert plan over the kept columns; the decode segment joins its list."""
+        c_rows, (k0, k1) = plans[3], plans[8]
+        ac = self.voice_changer.acoustic_converter
+        f0 = _converted_column(ac, self.concat(c_rows, [f['f0'] for f in self.features], (1,), numpy.float32), effective)[k0:k1]
+        self.outputs.append(dict(start=self.add[2], rows=k1 - k0))
+        return f0
+
+    def demote(self, download) -> list:
+        """The signal leaves the resident path: its live segments come down once (`download(k)` -> (mc, ap, wave) of segment k), and every later
+        buffer is composed -> what came down, as `transfers` entries."""
+        moved = []
+        if self.mode == 'resident':
+            for k, f in enumerate(self.features):
+                f['mc'], f['ap'], f['wave'] = download(k)
+                f['voiced'] = f['f0'] != 0
+                moved += [('down', 'mc', f['mc'].size), ('down', 'ap', f['ap'].size), ('down', 'wave', f['wave'].size)]
+        self.mode = 'composed'
+        return moved
+
+    def push_composed(self, pipe, vocoder, wave, track):
+        """One buffer over the separate calls, the plans applied to host arrays: `pipe` encodes (`Pipeline._composed_extract`), `vocoder` holds
+        the stream's synthesizer -> the samples that are final."""
+        from yukarin import Wave
+        from yukarin.acoustic_feature import AcousticFeature
+        calls['composed'] += 1
+        pipe._reset_stream()
+        # encode: the separate call on the window, then `pick(pad, -pad)`; the plans follow the frames it really returned
+        f = pipe._composed_extract(wave, track)
+        (ra, rb), (wa, wb), _, c_rows, c_samples, _, _, pad_c, (k0, k1), _, d_rows = self.plans(len(f.f0), len(wave.wave), int(wave.sampling_rate))
+        self.features.append(dict(start=self.add[1], rows=rb - ra, samples=wb - wa, f0=numpy.asarray(f.f0)[ra:rb], mc=numpy.asarray(f.mc)[ra:rb],
+                                  ap=numpy.asarray(f.ap)[ra:rb], voiced=numpy.asarray(f.voiced)[ra:rb], wave=numpy.asarray(wave.wave)[wa:wb]))
+        # convert: the window by the plan (`FeatureWrapperSegmentMethod`: float32 pads, keys f0 / ap / mc / voiced and the wave)
+        fs_ = self.features
+        g = AcousticFeature(f0=self.concat(c_rows, [s['f0'] for s in fs_], (1,), numpy.float32),
+                            ap=self.concat(c_rows, [s['ap'] for s in fs_], (fs_[-1]['ap'].shape[1],), numpy.float32),
+                            mc=self.concat(c_rows, [s['mc'] for s in fs_], (fs_[-1]['mc'].shape[1],), numpy.float32),
+                            voiced=self.concat(c_rows, [s['voiced'] for s in fs_], (1,), bool))
+        g.wave = Wave(self.concat(c_samples, [s['wave'] for s in fs_], (), numpy.float32), wave.sampling_rate)
+        out = self.voice_changer.convert_from_acoustic_feature(g, (pad_c, pad_c))
+        self.outputs.append(dict(start=self.add[2], rows=k1 - k0, f0=numpy.asarray(out.f0)[k0:k1], sp=numpy.asarray(out.sp)[k0:k1],
+                                 ap=numpy.asarray(out.ap)[k0:k1]))
+        # decode: the window by the plan (`FeatureSegmentMethod`: `AcousticFeature.silent` pads), to the synthesis stream
+        held = [o for o in self.outputs]
+        if any(i >= 0 and b > a and 'sp' not in held[i] for i, a, b in d_rows):
+            raise RuntimeError('the decode window reaches rows that were synthesized on the card and not kept')
+        if self.streams.span_count(d_rows) == 0:
+            return numpy.empty(0, numpy.float64)
+        last = held[-1]
+        h = AcousticFeature(f0=self.concat(d_rows, [o.get('f0') for o in held], (1,), numpy.float32),
+                            sp=self.concat(d_rows, [o.get('sp') for o in held], (last['sp'].shape[1],), numpy.float32),
+                            ap=self.concat(d_rows, [o.get('ap') for o in held], (last['ap'].shape[1],), numpy.float32))
+        return world_synth.decode_realtime(vocoder, h).wave
+
+    def move_on(self) -> int:
+        """The clocks move on and what no later window can fetch goes, on both paths -> how many of the oldest feature segments went (the
+        store gives their room back)."""
+        S, T = self.streams, self.time_length
+        _, rate_c, rate_d = self.rates()
+        self.add[1] += T
+        self.add[2] += T
+        self.now[1] += T
+        self.now[2] += T
+        gone = S.retire([(f['start'], f['rows']) for f in self.features], self.now[1], T, self.extra[1], rate_c)
+        del self.features[:gone]
+        del self.outputs[:S.retire([(o['start'], o['rows']) for o in self.outputs], self.now[2], T, self.extra[2], rate_d)]
+        return gone
+
+
+class _WindowOwner(object):
+    """The device blocks a fetched convert window lies in -- mc (rows, m_in), ap (rows, 513), wave (samples,), those of `_window_arrays` --
+    grown, never shrunk, freed in the process that made them."""
+    _window_arrays = ('mc', 'ap', 'wave')
+
+    def __init__(self):
+        self._win, self._win_cap = {}, (0, 0)
+
+    def _window_blocks(self, ctx, rows: int, samples: int, m_in: int):
+        if self._win.get('ctx') is not ctx or self._win.get('pid') != os.getpid():
+            self._win, self._win_cap = {'ctx': ctx, 'pid': os.getpid()}, (0, 0)
+        if rows > self._win_cap[0] or samples > self._win_cap[1] or self._win.get('m_in') != m_in:
+            self._free_window()
+            cap = (max(rows + rows // 2, 64), max(samples + samples // 2, 4096))
+            sizes = dict(mc=cap[0] * m_in, ap=cap[0] * BINS, wave=cap[1])
+            self._win.update(ctx=ctx, pid=os.getpid(), m_in=m_in, **{k: ctx.dev_alloc(sizes[k]) for k in self._window_arrays})
+            self._win_cap = cap
+        return self._win
+
+    def _free_window(self) -> None:
+        w = self._win
+        if w.get('pid') == os.getpid() and w.get('ctx') is not None and w['ctx'].handle is not None:
+            for k in self._window_arrays:
+                if k in w:
+                    w['ctx'].dev_free(w.pop(k))
+        self._win_cap = (0, 0)
+
+
+def _ring_sizes(time_length, convert_extra_time, ring_rows, ring_samples, seg_rows: int, seg_samples: int):
+    """The capacity of a stream's rings: the caller's, or what the retire rule keeps live, with a segment to spare."""
+    live = int((2 * convert_extra_time + 2 * time_length) / time_length) + 3
+    return (ring_rows if ring_rows is not None else live * (seg_rows + 2)), (ring_samples if ring_samples is not None else live * (seg_samples + 2))
+
+
+class LivePipeline(_WindowOwner):
     """The reference's three-stream live loop (run.py: `EncodeStream` -> `ConvertStream` -> `DecodeStream`, each with its own margin) as one
     object: `push(buffer)` does for item k what the three workers do -- every `add` at `extra_time + k * time_length`, every window from
     `k * time_length`, the clocks accumulated as theirs are -- and returns the samples that are final.  Each buffer goes through the encode
@@ -853,8 +1054,8 @@ class LivePipeline(object):
     stays on it until `flush` (its segments are then on the host; those of earlier resident buffers are brought down once).  `calls` counts
     which way a call went.  Retired segments (`streams.retire`) are dropped after every push on both paths.
 
-    One stream; `gate_first`, `advance` and banks are `Pipeline` / `PipelineBank` matters: with `encode_extra_time = 0` no audio is encoded
-    twice, so there is no overlap for them to save.  INTEGRATION.md section 23, DESIGN.md section 25."""
+    One stream (B streams in one chain: `LivePipelineBank`); `gate_first` and `advance` are `Pipeline` / `PipelineBank` matters: with
+    `encode_extra_time = 0` no audio is encoded twice, so there is no overlap for them to save.  INTEGRATION.md section 23, DESIGN.md section 25."""
 
     def __init__(self, voice_changer, acoustic_param, time_length: float, encode_extra_time: float, convert_extra_time: float, decode_extra_time: float,
                  f0_mode: str = 'crepe', f0_fn=None, crepe_capacity='full', seed: Optional[int] = None, feature_class=None,
@@ -870,69 +1071,20 @@ class LivePipeline(object):
         self.calls, self.routes = calls, routes
         self.transfers = []                                                # of the last call: (direction, what, elements)
         self.ring_rows, self.ring_samples, self.resident = ring_rows, ring_samples, bool(resident)
-        self._store, self._win, self._win_cap = None, {}, (0, 0)
-        self._start()
+        self._store = None
+        self._state = _LiveState(voice_changer, acoustic_param, f0_mode, time_length, self.extra)
+        _WindowOwner.__init__(self)
 
     def _start(self) -> None:
-        """A new signal: the workers' clocks at their first values, no segment anywhere."""
-        self._add = list(self.extra)                                       # `start_time = extra_time` of the three workers
-        self._now = [0., 0., 0.]                                           # `StreamWrapper._current_time` of the three streams
-        self._inputs, self._features, self._outputs = [], [], []           # EncodeStream / ConvertStream / DecodeStream .stream
-        self._mode = None                                                  # None until the first push, then 'resident' or 'composed'
+        self._state.start()
         if self._store is not None:
             self._store.reset()
-
-    # ---- rates and pads of the three streams, as their constructors take them
-    def _rates(self):
-        vc, p = self.voice_changer, self.acoustic_param
-        gp = vc.acoustic_converter.config.dataset.acoustic_param
-        sp = vc.super_resolution.config.dataset.param.acoustic_feature_param
-        return 1000 // p.frame_period, 1000 // gp.frame_period, 1000 // sp.frame_period
-
-    @staticmethod
-    def _inner(pad: int, n: int):
-        """`pick(data, pad, -pad)` of n elements as numpy slices it (the whole when pad is 0: the streams then do not pick)."""
-        return (0, n) if pad <= 0 else LivePipeline._clip(pad, -pad, n)
-
-    @staticmethod
-    def _clip(first, last, n):
-        a, b, _ = slice(first, last).indices(n)
-        return a, max(a, b)
-
-    def _frames(self, n_samples: int, fs) -> int:
-        p = self.acoustic_param
-        if n_samples < 1:
-            return 0
-        if self.f0_mode == 'world':
-            return world_analysis.harvest_frames(n_samples, fs, p.frame_period)
-        return _crepe.track_frames(n_samples, fs, _crepe.hop_length(p.frame_period))
-
-    def _window_blocks(self, ctx, rows: int, samples: int, m_in: int):
-        """The blocks a fetched window lies in: mc (rows, m_in), ap (rows, 513), wave (samples,) -- grown, never shrunk."""
-        if self._win.get('ctx') is not ctx or self._win.get('pid') != os.getpid():
-            self._win, self._win_cap = {'ctx': ctx, 'pid': os.getpid()}, (0, 0)
-        if rows > self._win_cap[0] or samples > self._win_cap[1] or self._win.get('m_in') != m_in:
-            self._free_window()
-            cap = (max(rows + rows // 2, 64), max(samples + samples // 2, 4096))
-            self._win.update(ctx=ctx, pid=os.getpid(), m_in=m_in, mc=ctx.dev_alloc(cap[0] * m_in), ap=ctx.dev_alloc(cap[0] * BINS), wave=ctx.dev_alloc(cap[1]))
-            self._win_cap = cap
-        return self._win
-
-    def _free_window(self) -> None:
-        w = self._win
-        if w.get('pid') == os.getpid() and w.get('ctx') is not None and w['ctx'].handle is not None:
-            for k in ('mc', 'ap', 'wave'):
-                if k in w:
-                    w['ctx'].dev_free(w.pop(k))
-        self._win_cap = (0, 0)
 
     def _store_of(self, ctx, m_in: int, seg_rows: int, seg_samples: int):
         if self._store is None or self._store._given_ctx is not ctx or self._store.mc_cols != m_in:
             if self._store is not None:
                 self._store.close()
-            live = int((2 * self.extra[1] + 2 * self.time_length) / self.time_length) + 3        # segments the retire rule keeps, and one to spare
-            rows = self.ring_rows if self.ring_rows is not None else live * (seg_rows + 2)
-            samples = self.ring_samples if self.ring_samples is not None else live * (seg_samples + 2)
+            rows, samples = _ring_sizes(self.time_length, self.extra[1], self.ring_rows, self.ring_samples, seg_rows, seg_samples)
             self._store = self._streams.RowStore(m_in, BINS, rows, samples, ctx=ctx)
         return self._store
 
@@ -944,68 +1096,26 @@ class LivePipeline(object):
         self._free_window()
         self._pipe.close()
 
-    # ---- host arrays by plan: what `concat` of the picked segments and the pads holds
-    @staticmethod
-    def _concat(spans, arrays, width, dtype):
-        parts = [numpy.zeros((b - a,) + width, dtype) if i < 0 else arrays[i][a:b] for i, a, b in spans]
-        return numpy.concatenate(parts)
-
     def _demote(self) -> None:
         """The signal leaves the resident path: its live segments come down once, and every later buffer is composed."""
-        if self._mode == 'resident' and self._store is not None:
-            for f, seg in zip(self._features, self._store.segments):
-                f['mc'], f['ap'], f['wave'] = self._store.download(seg)
-                f['voiced'] = f['f0'] != 0
-                self.transfers += [('down', 'mc', f['mc'].size), ('down', 'ap', f['ap'].size), ('down', 'wave', f['wave'].size)]
-            self._store.reset()
-        self._mode = 'composed'
-
-    def _plans(self, n_enc: int, n_window: int, fs):
-        """Everything the stream arithmetic decides for this buffer, from the clocks and the lengths alone: the rows / samples `EncodeStream` picks
-        of an encode window of n_enc frames, the convert window's plan with its clipped row and sample spans and their totals, the convert pad
-        and the rows `ConvertStream` picks, and the decode window's clocks and spans."""
-        S, p, T = self._streams, self.acoustic_param, self.time_length
-        rate_e, rate_c, rate_d = self._rates()
-        gp = self.voice_changer.acoustic_converter.config.dataset.acoustic_param
-        pad_e = round(self.extra[0] * rate_e)
-        ra, rb = self._inner(pad_e, n_enc)
-        wa, wb = (0, n_window) if pad_e <= 0 else self._clip(round(pad_e * p.frame_period / 1000 * fs), round(-pad_e * p.frame_period / 1000 * fs), n_window)
-        clocks = [(f['start'], f['rows']) for f in self._features] + [(self._add[1], rb - ra)]
-        sizes = [f['samples'] for f in self._features] + [wb - wa]
-        c_plan = S.fetch_plan(clocks, self._now[1], T, self.extra[1], rate_c)
-        c_rows = S.row_spans(c_plan, [n for _, n in clocks])
-        c_samples = S.wave_spans(c_plan, gp.frame_period, fs, sizes)
-        n_c, n_w = S.span_count(c_rows), S.span_count(c_samples)
-        pad_c = round(self.extra[1] * rate_c)
-        k0, k1 = self._inner(pad_c, n_c)
-        d_clocks = [(o['start'], o['rows']) for o in self._outputs] + [(self._add[2], k1 - k0)]
-        d_rows = S.row_spans(S.fetch_plan(d_clocks, self._now[2], T, self.extra[2], rate_d), [n for _, n in d_clocks])
-        return (ra, rb), (wa, wb), c_plan, c_rows, c_samples, n_c, n_w, pad_c, (k0, k1), d_clocks, d_rows
+        store = self._store
+        self.transfers += self._state.demote(lambda k: store.download(store.segments[k]))
+        if store is not None:
+            store.reset()
 
     def push(self, buffer, out_gate=None):
         """One buffer of `time_length` seconds at the input rate (a float32 array, or a `yukarin.Wave`) -> the `Wave` of the samples that are
         final; with `out_gate` the chunk the gate emits, as `Pipeline.push` returns it."""
         from yukarin import Wave
-        from yukarin.acoustic_feature import AcousticFeature
-        S, p, vc = self._streams, self.acoustic_param, self.voice_changer
-        T = self.time_length
-        fs = int(buffer.sampling_rate) if hasattr(buffer, 'sampling_rate') else int(p.sampling_rate)
-        x = numpy.asarray(buffer.wave if hasattr(buffer, 'wave') else buffer)
-        rate_e, rate_c, rate_d = self._rates()
-        gp = vc.acoustic_converter.config.dataset.acoustic_param
+        s, p, vc = self._state, self.acoustic_param, self.voice_changer
         self.transfers = []
         # ---- the three plans, from clocks and lengths alone: which way the call goes is known before anything runs
-        self._inputs.append((self._add[0], x))
-        self._add[0] += T
-        in_plan = S.row_spans(S.fetch_plan([(s, len(a)) for s, a in self._inputs], self._now[0], T, self.extra[0], fs), [len(a) for _, a in self._inputs])
-        window = self._concat(in_plan, [a for _, a in self._inputs], (), numpy.float32)          # WaveSegmentMethod.pad: float32 zeros
-        self._now[0] += T
-        del self._inputs[:S.retire([(s, len(a)) for s, a in self._inputs], self._now[0], T, self.extra[0], fs)]
-        wave = Wave(window, fs)
-        n_enc = self._frames(window.size, fs)
-        (ra, rb), (wa, wb), c_plan, c_rows, c_samples, n_c, n_w, pad_c, (k0, k1), d_clocks, d_rows = self._plans(n_enc, window.size, fs)
+        wave = s.take(buffer)
+        fs = int(wave.sampling_rate)
+        n_enc = s.frames(wave.wave.size, fs)
+        plans = s.plans(n_enc, wave.wave.size, fs)
         handles = None
-        if self.resident and self._mode != 'composed' and rb > ra and k1 > k0 and n_w > 0 and S.is_identity(d_rows, len(d_clocks) - 1, k1 - k0):
+        if self.resident and s.fits_resident(plans):
             handles = self._pipe._resident_handles(wave)
         track = None
         if handles is not None and self.f0_mode == 'world':
@@ -1014,31 +1124,25 @@ class LivePipeline(object):
                 handles = None                                             # the callable's track does not fit: the composed path, with that track
         if handles is None:
             self._demote()
-            out = self._push_composed(wave, track)
+            out = s.push_composed(self._pipe, self._pipe._vocoder, wave, track)
         else:
-            self._mode = 'resident'
-            out = self._push_resident(handles, wave, track, n_enc, (ra, rb), (wa, wb), c_plan, c_rows, n_c, n_w, pad_c, (k0, k1), out_gate)
-        # ---- the clocks move on and what no later window can fetch goes, on both paths
-        self._add[1] += T
-        self._add[2] += T
-        self._now[1] += T
-        self._now[2] += T
-        gone = S.retire([(f['start'], f['rows']) for f in self._features], self._now[1], T, self.extra[1], rate_c)
-        if self._mode == 'resident':
+            s.mode = 'resident'
+            out = self._push_resident(handles, wave, track, n_enc, plans, out_gate)
+        gone = s.move_on()
+        if s.mode == 'resident':
             self._store.retire(gone)
-        del self._features[:gone]
-        del self._outputs[:S.retire([(o['start'], o['rows']) for o in self._outputs], self._now[2], T, self.extra[2], rate_d)]
         if isinstance(out, Wave):
             return out                                                     # the gate read the samples on the card
         if out_gate is not None:
             out = _through_host_gate(out_gate, out)
         return Wave(wave=out, sampling_rate=vc.output_sampling_rate)
 
-    def _push_resident(self, handles, wave, track, n_enc, rows, samples, c_plan, c_rows, n_c, n_w, pad_c, keep, out_gate):
+    def _push_resident(self, handles, wave, track, n_enc, plans, out_gate):
         from yukarin import Wave
         model, analyzer, core, (p_eff, p_all), hop, gate_fft = handles
-        p, ac = self.acoustic_param, self.voice_changer.acoustic_converter
-        fs, (ra, rb), (wa, wb), (k0, k1) = int(wave.sampling_rate), rows, samples, keep
+        p, ac, s = self.acoustic_param, self.voice_changer.acoustic_converter, self._state
+        (ra, rb), (wa, wb), c_plan, _, _, n_c, n_w, pad_c, (k0, k1), _, _ = plans
+        fs = int(wave.sampling_rate)
         calls['resident'] += 1
         x = numpy.ascontiguousarray(wave.wave, dtype=numpy.float32)
         # encode: the window goes up once; its rows stay on the card
@@ -1058,8 +1162,8 @@ class LivePipeline(object):
             f0_track = trk.download()[1]
             self.transfers.append(('down', 'track', n_enc))
         store = self._store_of(ctx, p.order + 1, rb - ra, wb - wa)
-        store.append(self._add[1], b['mc32'], b['ap32'], ra, rb - ra, trk.wave, wa, wb - wa)
-        self._features.append(dict(start=self._add[1], rows=rb - ra, samples=wb - wa, f0=f0_track[:, None].astype(p.dtype)[ra:rb]))
+        store.append(s.add[1], b['mc32'], b['ap32'], ra, rb - ra, trk.wave, wa, wb - wa)
+        s.add_resident(f0_track, plans)
         # convert: the window is fetched from the rows on the card
         w = self._window_blocks(ctx, n_c, n_w, p.order + 1)
         store.fetch(c_plan, ac.config.dataset.acoustic_param.frame_period, fs, w['mc'], w['ap'], w['wave'], n_c, n_w)
@@ -1067,9 +1171,8 @@ class LivePipeline(object):
         _apply_discard(core, (pad_c, pad_c))
         effective, _ = core.enqueue_wave_device(w['wave'], n_w, hop, gate_fft, p_eff, p_all, w['mc'], n_c, b['mc_out'], b['sp_out'], b['mask'], SP_FLOOR)
         self.transfers.append(('down', 'mask', n_c))
-        f0 = _converted_column(ac, self._concat(c_rows, [f['f0'] for f in self._features], (1,), numpy.float32), effective)[k0:k1]
         # decode: the plan hands on exactly the rows just converted
-        self._outputs.append(dict(start=self._add[2], rows=k1 - k0))
+        f0 = s.resident_f0(plans, effective)
         ctx.mask_rows(w['ap'], b['mask'], n_c, BINS, k0, k1)
         dev_rows = [world_synth.DeviceRows(base + k0 * BINS * 4, k1 - k0) for base in (b['sp_out'], w['ap'])]
         self.transfers.append(('up', 'f0', k1 - k0))
@@ -1085,41 +1188,254 @@ class LivePipeline(object):
         self.transfers.append(('down', 'samples', out.size))
         return out
 
-    def _push_composed(self, wave, track):
-        from yukarin import Wave
-        from yukarin.acoustic_feature import AcousticFeature
-        calls['composed'] += 1
-        self._pipe._reset_stream()
-        # encode: the separate call on the window, then `pick(pad, -pad)`; the plans follow the frames it really returned
-        f = self._pipe._composed_extract(wave, track)
-        (ra, rb), (wa, wb), _, c_rows, c_samples, _, _, pad_c, (k0, k1), _, d_rows = self._plans(len(f.f0), len(wave.wave), int(wave.sampling_rate))
-        self._features.append(dict(start=self._add[1], rows=rb - ra, samples=wb - wa, f0=numpy.asarray(f.f0)[ra:rb], mc=numpy.asarray(f.mc)[ra:rb],
-                                   ap=numpy.asarray(f.ap)[ra:rb], voiced=numpy.asarray(f.voiced)[ra:rb], wave=numpy.asarray(wave.wave)[wa:wb]))
-        # convert: the window by the plan (`FeatureWrapperSegmentMethod`: float32 pads, keys f0 / ap / mc / voiced and the wave)
-        fs_ = self._features
-        g = AcousticFeature(f0=self._concat(c_rows, [s['f0'] for s in fs_], (1,), numpy.float32),
-                            ap=self._concat(c_rows, [s['ap'] for s in fs_], (fs_[-1]['ap'].shape[1],), numpy.float32),
-                            mc=self._concat(c_rows, [s['mc'] for s in fs_], (fs_[-1]['mc'].shape[1],), numpy.float32),
-                            voiced=self._concat(c_rows, [s['voiced'] for s in fs_], (1,), bool))
-        g.wave = Wave(self._concat(c_samples, [s['wave'] for s in fs_], (), numpy.float32), wave.sampling_rate)
-        out = self.voice_changer.convert_from_acoustic_feature(g, (pad_c, pad_c))
-        self._outputs.append(dict(start=self._add[2], rows=k1 - k0, f0=numpy.asarray(out.f0)[k0:k1], sp=numpy.asarray(out.sp)[k0:k1],
-                                  ap=numpy.asarray(out.ap)[k0:k1]))
-        # decode: the window by the plan (`FeatureSegmentMethod`: `AcousticFeature.silent` pads), to the synthesis stream
-        held = [o for o in self._outputs]
-        if any(i >= 0 and b > a and 'sp' not in held[i] for i, a, b in d_rows):
-            raise RuntimeError('the decode window reaches rows that were synthesized on the card and not kept')
-        if self._streams.span_count(d_rows) == 0:
-            return numpy.empty(0, numpy.float64)
-        last = held[-1]
-        h = AcousticFeature(f0=self._concat(d_rows, [o.get('f0') for o in held], (1,), numpy.float32),
-                            sp=self._concat(d_rows, [o.get('sp') for o in held], (last['sp'].shape[1],), numpy.float32),
-                            ap=self._concat(d_rows, [o.get('ap') for o in held], (last['ap'].shape[1],), numpy.float32))
-        return world_synth.decode_realtime(self._pipe._vocoder, h).wave
-
     def flush(self):
         """Ends the signal: the samples `push` still held back; the next `push` starts a new signal with the clocks at their first values."""
         from yukarin import Wave
         self._pipe._reset_stream()
         self._start()
         return Wave(wave=self.synth.flush(), sampling_rate=self.voice_changer.output_sampling_rate)
+
+
+class LivePipelineBank(_BlockOwner, _WindowOwner):
+    """`LivePipeline` for the B live streams one process serves, with ONE resident chain per call instead of B: the encode windows are assembled
+    on the host per stream, then `CrepeModel.track_many` (one upload of all windows; WORLD mode: `Analyzer.upload_waves` + one `ingest_tracks`) ->
+    `Analyzer.extract_many_resident` (one verdict) -> `RowBank.append_many` (one launch) -> `RowBank.fetch_many` (every stream's convert window, one
+    upload and one launch) -> `VcCore.enqueue_waves_device` with the discard hint (pad, pad) (one gate, one wait) -> `ry_gather_rows` of sp ->
+    `RowBank.pick_ap` with the gate's mask (the full ap window is written nowhere) -> ONE `StreamBank.push`, or `push_device` and ONE
+    `OutputGateBank.push_device`.  f0 stays on the host per segment, as in `LivePipeline`.
+
+    Every stream has its own `_LiveState` -- clocks, input, feature and output lists: a stream that sits a call out or is flushed does not
+    move the others' clocks.  Which path a stream takes is decided per stream by `LivePipeline`'s rule (the decode plan is an identity,
+    `Pipeline`'s resident conditions hold, in WORLD mode the track fits), and the resident streams of a call share one rate.  A stream that
+    is not eligible is demoted alone: its live segments come down once and it runs the composed path through its slot of the same
+    `StreamBank` until its `flush`; the others stay in the chain.  `calls` counts per stream and call.
+
+    What stream b returns, call by call, has the bits a lone `LivePipeline(seed=seeds[b])` returns for the same buffers and flushes, whatever
+    the other streams do.  `gate_first` and `advance` stay out, for `LivePipeline`'s reason.  INTEGRATION.md section 24, DESIGN.md section 26."""
+    _more_widths = PipelineBank._more_widths
+    _window_arrays = ('mc', 'wave')                                        # ap is read from the rings by `pick_ap`
+
+    def __init__(self, voice_changer, acoustic_param, n_streams: int, time_length: float, encode_extra_time: float, convert_extra_time: float,
+                 decode_extra_time: float, seeds=None, f0_mode: str = 'crepe', f0_fn=None, crepe_capacity='full', feature_class=None,
+                 ring_rows: Optional[int] = None, ring_samples: Optional[int] = None, resident: bool = True):
+        """seeds: one per stream (None: every stream has RY_SYNTH_SEED); ring_rows / ring_samples: the capacity of EACH stream's rings;
+        resident=False: every stream is composed."""
+        from . import streams
+        self._streams = streams
+        self.n_streams = int(n_streams)
+        if self.n_streams < 1:
+            raise ValueError('a bank has at least one stream, got %d' % self.n_streams)
+        if seeds is None:
+            seeds = [int(os.environ.get('RY_SYNTH_SEED', '0'))] * self.n_streams
+        self.seeds = [int(s) for s in seeds]
+        if len(self.seeds) != self.n_streams:
+            raise ValueError('%d seeds for %d streams' % (len(self.seeds), self.n_streams))
+        if f0_mode not in ('crepe', 'world'):
+            raise ValueError("f0_mode is 'crepe' or 'world', got %r" % (f0_mode,))
+        self._pipe = Pipeline(voice_changer, acoustic_param, crepe_capacity=crepe_capacity, seed=self.seeds[0], feature_class=feature_class, f0_mode=f0_mode,
+                              f0_fn=f0_fn)                                 # the conditions and handles of the resident path, the composed encode
+        self.voice_changer, self.acoustic_param, self.f0_mode = voice_changer, acoustic_param, f0_mode
+        self.time_length = time_length
+        self.extra = (encode_extra_time, convert_extra_time, decode_extra_time)
+        rate = voice_changer.output_sampling_rate
+        self.bank = world_synth.StreamBank(rate, acoustic_param.frame_period, n_streams=self.n_streams, seeds=self.seeds, ctx=world_synth.engine_for_tests.ctx)
+        self._vocoders = [_Vocoder(acoustic_param, rate, world_synth.BankSlot(self.bank, b)) for b in range(self.n_streams)]
+        self._states = [_LiveState(voice_changer, acoustic_param, f0_mode, time_length, self.extra) for _ in range(self.n_streams)]
+        self.calls, self.routes = calls, routes
+        self.transfers = []                                                # of the last call: (direction, what, elements)
+        self.ring_rows, self.ring_samples, self.resident = ring_rows, ring_samples, bool(resident)
+        self._store = None
+        _BlockOwner.__init__(self)
+        _WindowOwner.__init__(self)
+
+    def close(self) -> None:
+        """Frees the row bank, the device blocks, the stream bank and the one-shot pipeline in the process that created them; the voice changer
+        and the shared handles stay."""
+        if self._store is not None:
+            self._store.close()
+            self._store = None
+        self._free_window()
+        self._free()
+        self.bank.close()
+        self._pipe.close()
+
+    def _store_of(self, ctx, m_in: int, seg_rows: int, seg_samples: int):
+        if self._store is None or self._store._given_ctx is not ctx or self._store.mc_cols != m_in:
+            if any(s.mode == 'resident' for s in self._states):
+                raise RuntimeError('the context of the resident chain changed under live streams')
+            if self._store is not None:
+                self._store.close()
+            rows, samples = _ring_sizes(self.time_length, self.extra[1], self.ring_rows, self.ring_samples, seg_rows, seg_samples)
+            self._store = self._streams.RowBank(self.n_streams, m_in, BINS, rows, samples, ctx=ctx)
+        return self._store
+
+    def _demote(self, b: int) -> None:
+        """Stream b leaves the resident chain: its live segments come down once, and it is composed until its flush."""
+        store = self._store
+        self.transfers += self._states[b].demote(lambda k: store.download(b, store.segments[b][k]))
+        if store is not None:
+            store.reset(b)
+
+    def _final(self, final):
+        final = sorted(set(int(s) for s in (final or ())))
+        if any(s < 0 or s >= self.n_streams for s in final):
+            raise ValueError('final names stream %s of %d' % (final, self.n_streams))
+        return final
+
+    def _end(self, streams) -> None:
+        """New signals for `streams`: their clocks at the first values, their rings empty."""
+        for b in streams:
+            self._states[b].start()
+            if self._store is not None:
+                self._store.reset(b)
+
+    def push(self, buffers, out_gate=None, final=None) -> list:
+        """One buffer of `time_length` seconds for every live stream: `buffers` has one entry per stream (a float32 array or a `yukarin.Wave`),
+        None for a stream that sits the call out -> one `Wave` per stream: the samples that are final (empty for a stream that sat out).
+        out_gate (an `output_gate.OutputGateBank` of n_streams streams): the samples of all streams go through it in ONE call, on the card when
+        every stream of the call is resident and the gates judge there in the pipeline's context, else through the host: the same bits (`routes`
+        counts which, once per call).  final: the streams whose signal ends with this call, as `PipelineBank.push` has it; the next buffer of
+        such a stream starts a new signal."""
+        from yukarin import Wave
+        buffers = list(buffers)
+        B = self.n_streams
+        if len(buffers) != B:
+            raise ValueError('%d buffers for %d streams' % (len(buffers), B))
+        final = self._final(final)
+        p, rate = self.acoustic_param, self.voice_changer.output_sampling_rate
+        self.transfers = []
+        part = [b for b in range(B) if buffers[b] is not None]
+        # ---- per stream: the window, the plans and which way it goes, before anything runs
+        waves, plans, n_encs, handles, tracks = {}, {}, {}, {}, {}
+        for b in part:
+            s = self._states[b]
+            waves[b] = s.take(buffers[b])
+            n, fs = waves[b].wave.size, int(waves[b].sampling_rate)
+            n_encs[b] = s.frames(n, fs)
+            plans[b] = s.plans(n_encs[b], n, fs)
+            handles[b] = self._pipe._resident_handles(waves[b]) if self.resident and s.fits_resident(plans[b]) else None
+            tracks[b] = None
+            if handles[b] is not None and self.f0_mode == 'world':
+                tracks[b] = _world_f0(self._pipe.f0_fn, waves[b], p)
+                if not _track_fits(tracks[b][0], tracks[b][1], n_encs[b], p.frame_period):
+                    handles[b] = None                                      # this stream's track does not fit: it alone is composed, with that track
+        res = [b for b in part if handles[b] is not None]
+        if res:
+            self.bank._get()
+            ctx = handles[res[0]][2].stage1.ctx
+            if len(set(int(waves[b].sampling_rate) for b in res)) != 1 or self.bank._ctx is not ctx or self.bank.fft_size != FFT_SIZE:
+                res = []                                                   # the chain reads one rate in one context
+        outs = [numpy.empty(0, numpy.float64) for _ in range(B)]
+        for b in part:
+            if b not in res:
+                self._demote(b)
+                outs[b] = self._states[b].push_composed(self._pipe, self._vocoders[b], waves[b], tracks[b])
+                self.transfers.append(('down', 'samples', outs[b].size))
+        on_card = None
+        rest = [b for b in final if b not in res]                          # composed or absent streams that end: what their slots still hold
+        if res:                                                            # the gate reads on the card when every sample of the call is there
+            on_card = self._push_resident(res, handles[res[0]], waves, tracks, n_encs, plans, out_gate if len(res) == len(part) and not rest else None,
+                                          final, outs)
+        if rest:
+            got = self.bank.flush(rest)
+            for b in rest:
+                outs[b] = numpy.concatenate([outs[b], got[b]])
+        for b in part:
+            gone = self._states[b].move_on()
+            if self._states[b].mode == 'resident':
+                self._store.retire(b, gone)
+        self._end(final)
+        if on_card is not None:
+            routes['gate_device'] += 1
+            outs = [o if o is not None else numpy.empty(0, out_gate.dtype) for o in out_gate.push_device(on_card[0].address, on_card[1])]
+        elif out_gate is not None:
+            outs = _through_host_gate(out_gate, outs)
+        return [Wave(wave=o, sampling_rate=rate) for o in outs]
+
+    def _push_resident(self, res, handles, waves, tracks, n_encs, plans, out_gate, final, outs):
+        """The one chain of the streams `res` (ascending).  The samples go into `outs`, or stay on the card for `out_gate` -> (block, offsets)."""
+        model, analyzer, core, (p_eff, p_all), hop, gate_fft = handles
+        p, ac, S = self.acoustic_param, self.voice_changer.acoustic_converter, self._streams
+        fs = int(waves[res[0]].sampling_rate)
+        calls['resident'] += len(res)
+        xs = [numpy.ascontiguousarray(waves[b].wave, dtype=numpy.float32) for b in res]
+        fo_e = S._offsets([n_encs[b] for b in res])
+        # encode: the windows go up once; their rows stay on the card
+        if self.f0_mode == 'world':
+            trk = analyzer.ingest_tracks([tracks[b][0] for b in res], p.frame_period, analyzer.upload_waves(xs))
+            self.transfers += [('up', 'wave', sum(x.size for x in xs)), ('up', 'f0', int(fo_e[-1]))]
+            f0_tracks = [tracks[b][0] for b in res]
+        else:
+            trk = model.track_many(xs, fs, _crepe.hop_length(p.frame_period), p.frame_period, threshold=encode.threshold, device=True)
+            self.transfers.append(('up', 'wave', sum(x.size for x in xs)))
+        if list(trk.frame_offsets) != list(fo_e):
+            raise RuntimeError('the tracker returned %s frames, the frame-count rule says %s' % (list(numpy.diff(trk.frame_offsets)), list(numpy.diff(fo_e))))
+        ctx = core.stage1.ctx
+        sizes = [(plans[b][5], plans[b][6]) for b in res]                  # rows and samples of every convert window
+        fo_c, so_c = S._offsets([r for r, _ in sizes]), S._offsets([n for _, n in sizes], numpy.int64)
+        blk = self._reserve(ctx, max(int(fo_e[-1]), int(fo_c[-1])), p.order + 1, core.M, core.F)
+        analyzer.extract_many_resident(trk.wave, trk.sample_offsets, trk.f0, trk.t, fo_e, blk['mc32'], blk['sp32'], blk['ap32'])
+        if self.f0_mode != 'world':
+            f0_tracks = [track for _, track in trk.download()]
+            self.transfers.append(('down', 'track', int(fo_e[-1])))
+        (ra, rb), (wa, wb) = plans[res[0]][0], plans[res[0]][1]
+        store = self._store_of(ctx, p.order + 1, rb - ra, wb - wa)
+        store.append_many(res, [self._states[b].add[1] for b in res], (blk['mc32'], blk['ap32'], trk.wave),
+                          [(int(fo_e[i]) + plans[b][0][0], plans[b][0][1] - plans[b][0][0]) for i, b in enumerate(res)],
+                          [(int(trk.sample_offsets[i]) + plans[b][1][0], plans[b][1][1] - plans[b][1][0]) for i, b in enumerate(res)])
+        self.transfers.append(('up', 'table', store.counts()['upload_bytes'] // 4))
+        for b, f0_track in zip(res, f0_tracks):
+            self._states[b].mode = 'resident'
+            self._states[b].add_resident(f0_track, plans[b])
+        # convert: every window is fetched from its stream's rows on the card, back to back
+        w = self._window_blocks(ctx, int(fo_c[-1]), int(so_c[-1]), p.order + 1)
+        c_plans = [plans[b][2] for b in res]
+        if store.fetch_many(res, c_plans, ac.config.dataset.acoustic_param.frame_period, fs, w['mc'], w['wave']) != sizes:
+            raise RuntimeError('the row bank fetched other windows than the plans say')
+        self.transfers.append(('up', 'table', store.counts()['upload_bytes'] // 4))
+        pad_c = plans[res[0]][7]
+        _apply_discard(core, (pad_c, pad_c))
+        effective, _ = core.enqueue_waves_device(w['wave'], so_c, fo_c, hop, gate_fft, p_eff, p_all, w['mc'], blk['mc_out'], blk['sp_out'], blk['mask'], SP_FLOOR)
+        self.transfers.append(('down', 'mask', int(fo_c[-1])))
+        # decode: every plan hands on exactly the rows just converted; sp is gathered and ap picked into packed rows, stream after stream
+        keep = [plans[b][8] for b in res]
+        picks = [(int(fo_c[i]) + k0, int(fo_c[i]) + k1) for i, (k0, k1) in enumerate(keep)]
+        total = sum(k1 - k0 for k0, k1 in keep)
+        key = (tuple(picks), blk['rows'])
+        if self._table != key:                                             # live streams repeat their shapes: the table goes up once
+            ctx.dev_upload(blk['rows'], numpy.concatenate([numpy.arange(k0, k1, dtype=numpy.int32) for k0, k1 in picks]))
+            self._table = key
+            self.transfers.append(('up', 'table', total))
+        ctx.gather_rows(blk['sp_out'], int(fo_c[-1]), BINS, blk['rows'], blk['sp_pack'], total)
+        store.pick_ap(res, c_plans, keep, blk['mask'], blk['ap_pack'])
+        self.transfers.append(('up', 'table', store.counts()['upload_bytes'] // 4))
+        items, at = [None] * self.n_streams, 0
+        for i, b in enumerate(res):
+            k0, k1 = keep[i]
+            f0 = self._states[b].resident_f0(plans[b], effective[fo_c[i]:fo_c[i + 1]])
+            items[b] = (numpy.ascontiguousarray(f0), world_synth.DeviceRows(blk['sp_pack'] + at * BINS * 4, k1 - k0),
+                        world_synth.DeviceRows(blk['ap_pack'] + at * BINS * 4, k1 - k0))
+            at += k1 - k0
+        self.transfers.append(('up', 'f0', total))
+        ends = [b for b in final if b in res]
+        if _gate_on_card(out_gate, ctx):
+            block = self._sample_block(sum(self.bank.bound(b, items[b][0].size, b in ends) for b in res))
+            return block, self.bank.push_device(items, ends, block)
+        got = self.bank.push(items, final=ends)
+        for b in res:
+            outs[b] = got[b]
+        self.transfers.append(('down', 'samples', sum(got[b].size for b in res)))
+        return None
+
+    def flush(self, stream=None):
+        """Ends the signal of `stream` -> its `Wave`: the samples `push` still held back; its next `push` starts a new signal with the clocks at
+        their first values, and no other stream's clocks move.  stream=None: ends every stream -> one `Wave` per stream."""
+        from yukarin import Wave
+        rate = self.voice_changer.output_sampling_rate
+        which = list(range(self.n_streams)) if stream is None else [int(stream)]
+        self._pipe._reset_stream()
+        outs = self.bank.flush(which)
+        self._end(which)
+        if stream is not None:
+            return Wave(wave=outs[int(stream)], sampling_rate=rate)
+        return [Wave(wave=o, sampling_rate=rate) for o in outs]

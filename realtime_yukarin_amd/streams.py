@@ -219,3 +219,152 @@ class RowStore(DeviceHandle):
     def poison(self) -> None:
         lib, h = self._get()
         lib.check(lib.dll.ry_rowstore_debug_poison(h))
+
+
+def _ints(a, dtype=numpy.int32):
+    a = numpy.ascontiguousarray(a, dtype=dtype).ravel()
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong if dtype == numpy.int64 else ctypes.c_int))
+
+
+def _offsets(counts, dtype=numpy.int32) -> numpy.ndarray:
+    return numpy.concatenate([[0], numpy.cumsum(counts, dtype=numpy.int64)]).astype(dtype)
+
+
+class RowBank(DeviceHandle):
+    """`RowStore` for the B live streams of one process (`ry_rowbank_*`): B sets of the three rings, one shape, each stream with its own
+    `segments` list and live range.  Every device call names the streams it serves (`part`, ascending) and is ONE launch for all of them:
+    `append_many` takes each stream's segment from the shared blocks a many-wave encode left on the card, `fetch_many` writes every stream's
+    convert window back to back in the layout `VcCore.enqueue_waves_device` reads, `pick_ap` packs the ap rows the synthesizers read with the
+    silence mask applied.  The plans are `fetch_plan`'s, per stream over `clocks(stream)`."""
+    _destroy = 'ry_rowbank_destroy'
+
+    def __init__(self, n_streams: int, mc_cols: int, ap_cols: int, cap_rows: int, cap_samples: int, ctx=None, device: Optional[int] = None):
+        self.n_streams = int(n_streams)
+        self.mc_cols, self.ap_cols, self.cap_rows, self.cap_samples = int(mc_cols), int(ap_cols), int(cap_rows), int(cap_samples)
+        self.segments: List[List[Segment]] = [[] for _ in range(max(self.n_streams, 0))]
+        DeviceHandle.__init__(self, ctx, device)
+
+    def __getstate__(self):
+        d = DeviceHandle.__getstate__(self)
+        d['segments'] = [[] for _ in range(max(self.n_streams, 0))]
+        return d
+
+    def _create(self, lib, ctx):
+        h = ctypes.c_void_p()
+        lib.check(lib.dll.ry_rowbank_create(ctx.handle, self.n_streams, self.mc_cols, self.ap_cols, self.cap_rows, self.cap_samples, ctypes.byref(h)))
+        return h
+
+    def append_many(self, part, start_times, blocks, rows, samples) -> List[Segment]:
+        """For every stream of `part` (ascending) its newest segment: rows [row0, row0 + n) of the device blocks `blocks = (mc, ap, wave)` --
+        `rows[i] = (row0, n)` -- and samples `samples[i] = (sample0, n)` of the wave block -> the segments.  One launch; nothing is waited for up
+        to two streams, a longer piece table goes up once."""
+        lib, h = self._get()
+        n = len(part)
+        _, sp = _ints(part)
+        r0, r0p = _ints([r[0] for r in rows])
+        rn, rnp = _ints([r[1] for r in rows])
+        s0, s0p = _ints([s[0] for s in samples], numpy.int64)
+        sn, snp = _ints([s[1] for s in samples])
+        rp, sq = numpy.zeros(max(n, 1), numpy.int32), numpy.zeros(max(n, 1), numpy.int32)
+        lib.check(lib.dll.ry_rowbank_append(h, n, sp, _lib._fptr(int(blocks[0] or 0)), _lib._fptr(int(blocks[1] or 0)), r0p, rnp, _lib._fptr(int(blocks[2] or 0)),
+                                            s0p, snp, rp.ctypes.data_as(_IP), sq.ctypes.data_as(_IP)))
+        out = []
+        for i, b in enumerate(part):
+            out.append(Segment(start_times[i], rn[i], sn[i], rp[i], sq[i]))
+            self.segments[b].append(out[-1])
+        return out
+
+    def clocks(self, stream: int) -> List[Tuple[float, int]]:
+        return [(s.start_time, s.rows) for s in self.segments[stream]]
+
+    def _row_tables(self, part, plans):
+        """The clipped row spans of every stream's plan -> (spans per stream, the int32 table of all, its offsets per stream)."""
+        spans = [row_spans(plan, [s.rows for s in self.segments[b]]) for b, plan in zip(part, plans)]
+        tabs = [_table(sp, [s.row_pos for s in self.segments[b]], self.cap_rows) for b, sp in zip(part, spans)]
+        return spans, numpy.concatenate(tabs + [numpy.empty((0, 3), numpy.int32)]), _offsets([len(t) for t in tabs])
+
+    def fetch_many(self, part, plans, frame_period, fs, mc_ptr: int, wave_ptr: int) -> List[Tuple[int, int]]:
+        """Applies one `fetch_plan` per stream of `part`: every window's mc rows back to back from row 0 of the block at `mc_ptr` and its samples
+        back to back from sample 0 of the block at `wave_ptr` -> [(rows, samples)] per stream; the windows' offsets are the running sums of those.
+        One upload, one launch; the upload is waited for."""
+        lib, h = self._get()
+        rows, rt, ro = self._row_tables(part, plans)
+        samples = [wave_spans(plan, frame_period, fs, [s.samples for s in self.segments[b]]) for b, plan in zip(part, plans)]
+        sts = [_table(sp, [s.sample_pos for s in self.segments[b]], self.cap_samples) for b, sp in zip(part, samples)]
+        st, so = numpy.concatenate(sts + [numpy.empty((0, 3), numpy.int32)]), _offsets([len(t) for t in sts])
+        sizes = [(span_count(r), span_count(s)) for r, s in zip(rows, samples)]
+        fo, fop = _ints(_offsets([r for r, _ in sizes]))
+        wo, wop = _ints(_offsets([s for _, s in sizes], numpy.int64), numpy.int64)
+        lib.check(lib.dll.ry_rowbank_fetch(h, len(part), _ints(part)[1], rt.ctypes.data_as(_IP), ro.ctypes.data_as(_IP), st.ctypes.data_as(_IP),
+                                           so.ctypes.data_as(_IP), _lib._fptr(int(mc_ptr or 0)), _lib._fptr(int(wave_ptr or 0)), fop, wop))
+        return sizes
+
+    def pick_ap(self, part, plans, keep, mask_ptr: int, ap_pack_ptr: int) -> int:
+        """Behind the window call that wrote the mask at `mask_ptr` (one byte per window row, the windows in `fetch_many`'s layout): rows
+        `keep[i] = (k0, k1)` of every stream's window ap go to the block at `ap_pack_ptr`, stream after stream, zeros where the mask cut the
+        frame or the plan pads -> the rows packed.  One launch; the full ap window is written nowhere."""
+        lib, h = self._get()
+        rows, rt, ro = self._row_tables(part, plans)
+        fo, fop = _ints(_offsets([span_count(r) for r in rows]))
+        kp, kpp = _ints([int(k) for pair in keep for k in pair])
+        total = int(sum(k1 - k0 for k0, k1 in keep))
+        lib.check(lib.dll.ry_rowbank_pick_ap(h, len(part), _ints(part)[1], rt.ctypes.data_as(_IP), ro.ctypes.data_as(_IP), fop, kpp,
+                                             ctypes.cast(ctypes.c_void_p(int(mask_ptr or 0)), ctypes.POINTER(ctypes.c_ubyte)), _lib._fptr(int(ap_pack_ptr or 0)),
+                                             total))
+        return total
+
+    def download(self, stream: int, seg: Segment):
+        """The rows and samples of a live segment of `stream`, brought to the host -> (mc, ap, wave) float32; waits for the context stream."""
+        mc_ring, ap_ring, wave_ring = self.buffers()
+
+        def part(ring, pos, n, cols, cap):
+            ring += 4 * stream * cap * cols
+            out = numpy.empty((n, cols), numpy.float32)
+            head = min(n, cap - pos)
+            if head > 0:
+                self._ctx.dev_download(ring + 4 * pos * cols, out[:head])
+            if n > head:
+                self._ctx.dev_download(ring, out[head:])
+            return out
+        return (part(mc_ring, seg.row_pos, seg.rows, self.mc_cols, self.cap_rows), part(ap_ring, seg.row_pos, seg.rows, self.ap_cols, self.cap_rows),
+                part(wave_ring, seg.sample_pos, seg.samples, 1, self.cap_samples).ravel())
+
+    def retire(self, stream: int, n_segments: int) -> None:
+        """The `n_segments` oldest segments of `stream` may be overwritten from now on."""
+        gone = self.segments[stream][:int(n_segments)]
+        if gone:
+            lib, h = self._get()
+            lib.check(lib.dll.ry_rowbank_retire(h, int(stream), sum(s.rows for s in gone), sum(s.samples for s in gone)))
+            del self.segments[stream][:len(gone)]
+
+    def reset(self, stream: Optional[int] = None) -> None:
+        if self._handle is not None:
+            lib, h = self._get()
+            lib.check(lib.dll.ry_rowbank_reset(h, -1 if stream is None else int(stream)))
+        for b in range(self.n_streams):
+            if stream is None or b == int(stream):
+                self.segments[b] = []
+
+    def held(self, stream: int) -> Tuple[int, int]:
+        lib, h = self._get()
+        r, s = ctypes.c_int(), ctypes.c_int()
+        lib.check(lib.dll.ry_rowbank_held(h, int(stream), ctypes.byref(r), ctypes.byref(s)))
+        return r.value, s.value
+
+    def counts(self) -> dict:
+        """tests: launches, uploads, waits and bytes uploaded by the last append / fetch / pick."""
+        lib, h = self._get()
+        out = (ctypes.c_longlong * 4)()
+        lib.check(lib.dll.ry_rowbank_debug_counts(h, out))
+        return dict(zip(('launches', 'uploads', 'waits', 'upload_bytes'), (int(v) for v in out)))
+
+    def buffers(self) -> Tuple[int, int, int]:
+        """tests: the device addresses of the mc, ap and wave arrays (stream b's rings lie b rings in)."""
+        lib, h = self._get()
+        p = [ctypes.c_void_p() for _ in range(3)]
+        lib.check(lib.dll.ry_rowbank_debug_buffers(h, *[ctypes.byref(q) for q in p]))
+        return tuple(int(q.value) for q in p)
+
+    def poison(self) -> None:
+        lib, h = self._get()
+        lib.check(lib.dll.ry_rowbank_debug_poison(h))
