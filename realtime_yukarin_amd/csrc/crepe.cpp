@@ -14,6 +14,8 @@
 // crepe_act_assemble builds the window's block from both (DESIGN.md section 18 states which rows may be kept).
 // ry_crepe_bank_track is ry_crepe_track_many over the next windows of several such streams: every stream has a pair of slots of its own, the
 // computed frames of all waves share the passes, and crepe_act_assemble_many builds every wave's block in one launch.
+// The four tracking bodies are the same steps over one TrackCall -- size_call, reserve_call, bring_up, finish_track -- plus what is theirs alone; a
+// stream and every stream of a bank keep their rows in a Slot.
 #include "crepe_kernels.h"
 #include "ry_host.h"
 
@@ -132,6 +134,18 @@ struct RuleCache {
     std::map<std::tuple<int, int, int>, bool> repeats_of;
     int epoch = 0;
 };
+
+// The kept rows of one stream, single or of a bank: two activation blocks used in turn by the calls the stream takes part in, and the call
+// whose rows one of them holds.
+struct Slot {
+    DevBuf<float> act0, act1;
+    KeptCall k;
+    explicit Slot(DevBufList& l) : act0(l), act1(l) {}
+    DevBuf<float>& act(int i) { return i ? act1 : act0; }
+    int next() const { return k.valid ? 1 - k.kept : 0; }   // the block the next call writes: the other one, so the kept rows do not move
+    const float* keep() { return k.valid ? act(k.kept).ptr() : nullptr; }
+    int n_keep() const { return k.valid ? k.nf : 0; }
+};
 }  // namespace
 
 // A streaming tracker over a model (ry_crepe_stream_track): the activation rows of the last window, kept on the card for the next one.
@@ -140,12 +154,11 @@ struct ry_crepe_stream {
     ry_ctx* ctx = nullptr;
     ry_crepe* model = nullptr;
     DevBufList bufs;
-    DevBuf<float> act0{bufs}, act1{bufs}, fresh{bufs};      // the two activation blocks used in turn, the packed rows of the computed frames
+    Slot rows{bufs};
+    DevBuf<float> fresh{bufs};                              // the packed rows of the computed frames
     DevBuf<int> tab{bufs};                                  // src [frames] | idx [computed] of the last upload
-    DevBuf<float>& act(int i) { return i ? act1 : act0; }
     std::vector<int> tab_host[2];                           // the tables of the last two uploads (the host array of a copy outlives the call)
     int tab_cur = -1;                                       // which of the two the card holds; -1: none
-    KeptCall k;                                             // the kept call
     RuleCache cache;
 };
 
@@ -156,12 +169,6 @@ struct ry_crepe_bank {
     ry_ctx* ctx = nullptr;
     ry_crepe* model = nullptr;
     DevBufList bufs;
-    struct Slot {
-        DevBuf<float> act0, act1;
-        KeptCall k;
-        explicit Slot(DevBufList& l) : act0(l), act1(l) {}
-        DevBuf<float>& act(int i) { return i ? act1 : act0; }
-    };
     std::vector<std::unique_ptr<Slot>> slots;
     DevBuf<float> fresh{bufs};                              // the packed rows of the computed frames of all waves of a call
     // The tables of a call: descriptors [waves] (CrepeBankWave) | src [frames] | idx [computed], one copy.  In steady state the descriptors
@@ -447,6 +454,101 @@ int voicing_args(double threshold, double step_ms) {
     return RY_OK;
 }
 
+// ---- the steps of a tracking call (ry_crepe_track, _track_many / _track_uploaded, _stream_track, _bank_track / _bank_track_uploaded) ----
+// The sizes of a call and, once bring_up has run, where its samples and its segment table lie on the card (one wave: no table, plan is empty).
+struct TrackCall {
+    int sr = 0, hop = 0, total_in = 0, total16 = 0, total_nf = 0;
+    const Resampler* r = nullptr;                   // null at 16 kHz
+    std::vector<int> n16, nf;                       // samples at 16 kHz / frames of every wave
+    std::vector<CrepeSeg> plan;
+    bool uploaded = false;                          // the waves are those ry_crepe_upload_waves left on the card
+    float* wave = nullptr;
+    const CrepeSeg* seg = nullptr;
+    int n_seg() const { return plan.empty() ? 1 : (int)plan.size(); }
+};
+
+// Every refusal of a list of waves: each wave is held to what ry_crepe_track asks of it (and to wave_ok(i), the caller's own, before the next
+// wave is looked at), the list to the sizes one call takes; first_sample: the waves are entries of the uploaded table, else null.  Host work only.
+int any_wave(int) { return RY_OK; }
+template <typename WaveOk>
+int size_call(ry_crepe* c, const int* first_sample, const int* n_samples, int n_waves, int sr, int hop, TrackCall* z, WaveOk wave_ok) {
+    z->sr = sr; z->hop = hop; z->uploaded = first_sample != nullptr;
+    z->n16.assign(n_samples, n_samples + n_waves); z->nf.resize((size_t)n_waves);
+    for (int i = 0; i < n_waves; ++i) {
+        if (n_samples[i] < 1) return fail(RY_EINVAL, "wave %d has %d samples", i, n_samples[i]);
+        if (sr != 16000) RY_TRY(resample_plan(c, n_samples[i], sr, &z->r, &z->n16[(size_t)i]));
+        RY_TRY(frame_count(z->n16[(size_t)i], hop, 1, &z->nf[(size_t)i]));
+        RY_TRY(wave_ok(i));
+    }
+    RY_TRY(plan_segments(n_waves, n_samples, z->n16.data(), z->nf.data(), &z->plan));
+    if (z->uploaded) RY_TRY(place_uploaded(c, first_sample, n_samples, n_waves, sr, &z->plan));
+    const CrepeSeg& last = z->plan.back();
+    z->total_in = last.in_off + last.in_len; z->total16 = last.off16 + last.n16; z->total_nf = last.frame0 + last.n_frames;
+    return RY_OK;
+}
+
+// one wave, tracked without a table (n_samples < 1 is refused by the caller, in its own words)
+int size_call(ry_crepe* c, int n_samples, int sr, int hop, TrackCall* z) {
+    RY_TRY(size_call(c, nullptr, &n_samples, 1, sr, hop, z, any_wave));
+    z->plan.clear();
+    return RY_OK;
+}
+
+// every buffer of the model the call needs, before its first enqueue; computed: the frames that go through the network
+int reserve_call(ry_crepe* c, const TrackCall& z, int computed) {
+    RY_TRY(ensure_chunk(c, std::min(computed, CHUNK)));
+    RY_TRY(ensure_call(c, z.total_nf, z.total16));                     // an upload at 16 kHz lies in `audio`: it is longer than total16 and stays
+    RY_TRY(ensure_track(c, z.total_nf));
+    return RY_OK;
+}
+
+// The one upload of the call (the waves at the caller's rate, back to back; none when they are on the card already), the segment table of a
+// list, and the resampler over all of it -> the samples at 16 kHz in `audio`.  At 16 kHz the reserve inside upload_audio finds the room
+// ensure_call made: total_in == total16 there.
+int bring_up(ry_crepe* c, TrackCall* z, const float* audio) {
+    z->wave = const_cast<float*>(c->up_wave);
+    if (!z->uploaded) RY_TRY(upload_audio(c, z->r, audio, z->total_in, &z->wave));
+    if (!z->plan.empty()) {
+        RY_TRY(upload_segments(c, z->plan));
+        z->seg = c->segs.ptr();
+    }
+    if (z->r) RY_TRY(launch_resample(c, *z->r, z->wave, z->total_in, z->sr, c->audio.ptr(), z->total16, z->seg, z->n_seg()));
+    return RY_OK;
+}
+
+// the masked track of n frames from the handle's buffers to the caller's, and the wait for it
+int download_track(ry_crepe* c, int n, unsigned char* voiced, double* f0_64, double* t_64) {
+    const ry_stream_t s = c->ctx->stream;
+    RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)n, s));
+    RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)n * sizeof(double), s));
+    RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)n * sizeof(double), s));
+    RT_TRY(rt::stream_sync(s));
+    return RY_OK;
+}
+
+// The end of a call whose decode is enqueued: the voicing, what the call leaves on the card (ry_crepe_track_buffers for one wave,
+// ry_crepe_uploaded_buffers for waves of the uploaded table -- they are not back to back --, else ry_crepe_track_many_buffers), the frames of
+// every wave to the caller, and the track too unless it stays on the card.
+int finish_track(ry_crepe* c, const TrackCall& z, double threshold, double step_ms, int* n_frames, unsigned char* voiced, double* f0_64, double* t_64,
+                 int on_device_out) {
+    RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), z.total_nf, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr(), z.seg, z.n_seg()));
+    c->trk_wave = z.wave;
+    const size_t n = z.plan.size();
+    if (n == 0) { c->trk_samples = z.total_in; c->trk_frames = z.total_nf; }
+    else {
+        c->trk_sample_off.assign(n + 1, 0);
+        c->trk_frame_off.assign(n + 1, 0);
+        for (size_t i = 0; i < n; ++i) {
+            c->trk_sample_off[i + 1] = (long long)z.plan[i].in_off + z.plan[i].in_len;
+            c->trk_frame_off[i + 1] = z.plan[i].frame0 + z.plan[i].n_frames;
+        }
+        if (z.uploaded) { c->sub_frame_off = c->trk_frame_off; c->sub_waves = (int)n; }
+        else c->trk_waves = (int)n;
+    }
+    std::copy(z.nf.begin(), z.nf.end(), n_frames);
+    return on_device_out ? RY_OK : download_track(c, z.total_nf, voiced, f0_64, t_64);
+}
+
 // ---- which rows of the previous window a streamed call may keep ----
 // The frames of a window of n_in samples at sr (r: the rate's tables, null at 16 kHz) that are portable: the whole support [f hop - 512,
 // f hop + 512) lies inside the 16 kHz signal and every output in it is clean -- neither tap loop of crepe_resample is cut by an end of the signal
@@ -572,15 +674,30 @@ int launch_assemble_many(ry_ctx* ctx, const CrepeSeg* seg, int n_seg, const Crep
     return RY_OK;
 }
 
-// all bits set in every row of a kept block that is not portable (every row when nothing is kept) -> the rows left alone
-int poison_kept(DevBuf<float>& b, const KeptCall& k, ry_stream_t s, int* left) {
+// all bits set in the block of a slot about to be written and in every row of the other block that is not a portable kept row (every row when
+// nothing is kept): the rows the rule may hand to the next call are the only ones left alone -> their number
+int poison_slot(Slot& sl, ry_stream_t s, int* left) {
     *left = 0;
+    const int w = sl.next();
+    RY_TRY(sl.act(w).poison(s));
+    DevBuf<float>& b = sl.act(1 - w);
+    const KeptCall& k = sl.k;
     if (!k.valid) return b.poison(s);
     for (long long f = 0; f * CREPE_BINS < b.cap; ++f) {
         if (f < k.nf && k.portable[(size_t)f]) { ++*left; continue; }
         const long long n = std::min((long long)CREPE_BINS, b.cap - f * CREPE_BINS);
         RT_TRY(rt::dmemset(b.ptr() + f * CREPE_BINS, 0xff, (size_t)n * sizeof(float), s));
     }
+    return RY_OK;
+}
+
+// the activation of the window a slot keeps (k.valid), to the host or to a device pointer
+int read_activation(ry_ctx* ctx, Slot& sl, float* out, int on_device) {
+    const ry_stream_t s = ctx->stream;
+    const size_t bytes = (size_t)sl.k.nf * CREPE_BINS * sizeof(float);
+    if (on_device) { RT_TRY(rt::d2d(out, sl.act(sl.k.kept).ptr(), bytes, s)); return RY_OK; }
+    RT_TRY(rt::d2h(out, sl.act(sl.k.kept).ptr(), bytes, s));
+    RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }
 }  // namespace
@@ -778,9 +895,9 @@ int ry_crepe_resample(ry_crepe* c, const float* audio, int n_samples, int sr, fl
     const ry_stream_t s = c->ctx->stream;
     if (on_device) return launch_resample(c, *r, audio, n_samples, sr, out16k, n_out);
     RY_TRY(c->audio.reserve(c->ctx, n_out));
-    RY_TRY(c->audio_sr.reserve(c->ctx, n_samples));
-    RT_TRY(rt::h2d(c->audio_sr.ptr(), audio, (size_t)n_samples * sizeof(float), s));
-    RY_TRY(launch_resample(c, *r, c->audio_sr.ptr(), n_samples, sr, c->audio.ptr(), n_out));
+    float* wave = nullptr;
+    RY_TRY(upload_audio(c, r, audio, n_samples, &wave));
+    RY_TRY(launch_resample(c, *r, wave, n_samples, sr, c->audio.ptr(), n_out));
     RT_TRY(rt::d2h(out16k, c->audio.ptr(), (size_t)n_out * sizeof(float), s));
     RT_TRY(rt::stream_sync(s));
     return RY_OK;
@@ -796,16 +913,11 @@ int ry_crepe_predict_sr(ry_crepe* c, const float* audio, int n_samples, int sr, 
     int n_out = 0, nf = 0;
     RY_TRY(resample_plan(c, n_samples, sr, &r, &n_out));
     RY_TRY(frame_count(n_out, hop, center, &nf));
-    const ry_stream_t s = c->ctx->stream;
     RY_TRY(ensure_chunk(c, std::min(nf, CHUNK)));
     RY_TRY(ensure_call(c, nf, n_out));
-    const float* d_in = audio;
-    if (!on_device) {
-        RY_TRY(c->audio_sr.reserve(c->ctx, n_samples));
-        RT_TRY(rt::h2d(c->audio_sr.ptr(), audio, (size_t)n_samples * sizeof(float), s));
-        d_in = c->audio_sr.ptr();
-    }
-    RY_TRY(launch_resample(c, *r, d_in, n_samples, sr, c->audio.ptr(), n_out));
+    float* wave = nullptr;
+    if (!on_device) RY_TRY(upload_audio(c, r, audio, n_samples, &wave));
+    RY_TRY(launch_resample(c, *r, on_device ? audio : wave, n_samples, sr, c->audio.ptr(), n_out));
     return run_network(c, c->audio.ptr(), n_out, hop, center, viterbi, nf, f0, confidence, activation, on_device);
 }
 
@@ -852,11 +964,7 @@ int ry_crepe_voicing(ry_crepe* c, const float* confidence, const float* f0, int 
     RT_TRY(rt::h2d(c->conf.ptr(), confidence, (size_t)n * sizeof(float), s));
     RT_TRY(rt::h2d(c->f0.ptr(), f0, (size_t)n * sizeof(float), s));
     RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), n, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr()));
-    RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)n, s));
-    RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)n * sizeof(double), s));
-    RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)n * sizeof(double), s));
-    RT_TRY(rt::stream_sync(s));
-    return RY_OK;
+    return download_track(c, n, voiced, f0_64, t_64);
 }
 
 int ry_crepe_track(ry_crepe* c, const float* audio, int n_samples, int sr, int hop, double step_ms, double threshold, int* n_frames,
@@ -865,32 +973,13 @@ int ry_crepe_track(ry_crepe* c, const float* audio, int n_samples, int sr, int h
     if (!audio || !n_frames || n_samples < 1 || hop < 1) return fail(RY_EINVAL, "bad argument");
     if (!on_device_out && (!voiced || !f0_64 || !t_64)) return fail(RY_EINVAL, "null output");
     RY_TRY(voicing_args(threshold, step_ms));
-    forget_track(c);
-    const ry_stream_t s = c->ctx->stream;
-    const Resampler* r = nullptr;
-    int n16 = n_samples, nf = 0;
-    if (sr != 16000) RY_TRY(resample_plan(c, n_samples, sr, &r, &n16));
-    RY_TRY(frame_count(n16, hop, 1, &nf));
-    RY_TRY(ensure_chunk(c, std::min(nf, CHUNK)));
-    RY_TRY(ensure_call(c, nf, n16));
-    RY_TRY(ensure_track(c, nf));
-    float* wave = c->audio.ptr();                                    // the one upload: the wave at the caller's rate
-    if (r) {
-        RY_TRY(c->audio_sr.reserve(c->ctx, n_samples));
-        wave = c->audio_sr.ptr();
-    }
-    RT_TRY(rt::h2d(wave, audio, (size_t)n_samples * sizeof(float), s));
-    if (r) RY_TRY(launch_resample(c, *r, wave, n_samples, sr, c->audio.ptr(), n16));
-    RY_TRY(run_network(c, c->audio.ptr(), n16, hop, 1, 1, nf, nullptr, nullptr, nullptr, 1));
-    RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), nf, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr()));
-    c->trk_wave = wave; c->trk_samples = n_samples; c->trk_frames = nf;
-    *n_frames = nf;
-    if (on_device_out) return RY_OK;
-    RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)nf, s));
-    RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)nf * sizeof(double), s));
-    RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)nf * sizeof(double), s));
-    RT_TRY(rt::stream_sync(s));
-    return RY_OK;
+    forget_track(c);                                                 // after the argument refusals: such a call keeps the previous track
+    TrackCall z;
+    RY_TRY(size_call(c, n_samples, sr, hop, &z));
+    RY_TRY(reserve_call(c, z, z.total_nf));
+    RY_TRY(bring_up(c, &z, audio));
+    RY_TRY(run_network(c, c->audio.ptr(), z.total16, hop, 1, 1, z.total_nf, nullptr, nullptr, nullptr, 1));
+    return finish_track(c, z, threshold, step_ms, n_frames, voiced, f0_64, t_64, on_device_out);
 }
 
 int ry_crepe_track_buffers(ry_crepe* c, const float** wave_dev, int* n_samples, int* n_frames, const unsigned char** voiced_dev,
@@ -917,47 +1006,12 @@ static int track_many_impl(ry_crepe* c, const float* audio, const int* first_sam
     if (!on_device_out && (!voiced || !f0_64 || !t_64)) return fail(RY_EINVAL, "null output");
     if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
     RY_TRY(voicing_args(threshold, step_ms));
-    // every refusal first: each wave is held to what ry_crepe_track asks of it, the list to the sizes one call takes
-    const Resampler* r = nullptr;
-    std::vector<int> n16((size_t)n_waves), nf((size_t)n_waves);
-    for (int i = 0; i < n_waves; ++i) {
-        if (n_samples[i] < 1) return fail(RY_EINVAL, "wave %d has %d samples", i, n_samples[i]);
-        n16[(size_t)i] = n_samples[i];
-        if (sr != 16000) RY_TRY(resample_plan(c, n_samples[i], sr, &r, &n16[(size_t)i]));
-        RY_TRY(frame_count(n16[(size_t)i], hop, 1, &nf[(size_t)i]));
-    }
-    std::vector<CrepeSeg> plan;
-    RY_TRY(plan_segments(n_waves, n_samples, n16.data(), nf.data(), &plan));
-    if (uploaded) RY_TRY(place_uploaded(c, first_sample, n_samples, n_waves, sr, &plan));
-    const CrepeSeg& last = plan.back();
-    const int total_in = last.in_off + last.in_len, total16 = last.off16 + last.n16, total_nf = last.frame0 + last.n_frames;
-    const ry_stream_t s = c->ctx->stream;
-    RY_TRY(ensure_chunk(c, std::min(total_nf, CHUNK)));
-    RY_TRY(ensure_call(c, total_nf, total16));                         // an upload at 16 kHz lies in `audio`: it is longer than total16 and stays
-    RY_TRY(ensure_track(c, total_nf));
-    float* wave = const_cast<float*>(c->up_wave);
-    if (!uploaded) RY_TRY(upload_audio(c, r, audio, total_in, &wave));     // the one upload: the waves at the caller's rate, back to back
-    RY_TRY(upload_segments(c, plan));
-    const CrepeSeg* seg = c->segs.ptr();
-    if (r) RY_TRY(launch_resample(c, *r, wave, total_in, sr, c->audio.ptr(), total16, seg, n_waves));
-    RY_TRY(run_network(c, c->audio.ptr(), total16, hop, 1, 1, total_nf, nullptr, nullptr, nullptr, 1, seg, n_waves));
-    RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), total_nf, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr(), seg, n_waves));
-    c->trk_wave = wave;
-    c->trk_sample_off.assign((size_t)n_waves + 1, 0);
-    c->trk_frame_off.assign((size_t)n_waves + 1, 0);
-    for (int i = 0; i < n_waves; ++i) {
-        c->trk_sample_off[(size_t)i + 1] = (long long)plan[(size_t)i].in_off + plan[(size_t)i].in_len;
-        c->trk_frame_off[(size_t)i + 1] = plan[(size_t)i].frame0 + plan[(size_t)i].n_frames;
-        n_frames[i] = nf[(size_t)i];
-    }
-    if (uploaded) { c->sub_frame_off = c->trk_frame_off; c->sub_waves = n_waves; }    // the waves are not back to back: ry_crepe_uploaded_buffers reports them
-    else c->trk_waves = n_waves;
-    if (on_device_out) return RY_OK;
-    RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)total_nf, s));
-    RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)total_nf * sizeof(double), s));
-    RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)total_nf * sizeof(double), s));
-    RT_TRY(rt::stream_sync(s));
-    return RY_OK;
+    TrackCall z;
+    RY_TRY(size_call(c, uploaded ? first_sample : nullptr, n_samples, n_waves, sr, hop, &z, any_wave));
+    RY_TRY(reserve_call(c, z, z.total_nf));
+    RY_TRY(bring_up(c, &z, audio));
+    RY_TRY(run_network(c, c->audio.ptr(), z.total16, hop, 1, 1, z.total_nf, nullptr, nullptr, nullptr, 1, z.seg, n_waves));
+    return finish_track(c, z, threshold, step_ms, n_frames, voiced, f0_64, t_64, on_device_out);
 }
 
 int ry_crepe_track_many(ry_crepe* c, const float* audio, const int* n_samples, int n_waves, int sr, int hop, double step_ms, double threshold,
@@ -1065,11 +1119,7 @@ int ry_crepe_voicing_many(ry_crepe* c, const float* confidence, const float* f0,
     RT_TRY(rt::h2d(c->conf.ptr(), confidence, (size_t)n * sizeof(float), s));
     RT_TRY(rt::h2d(c->f0.ptr(), f0, (size_t)n * sizeof(float), s));
     RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), n, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr(), c->segs.ptr(), n_tracks));
-    RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)n, s));
-    RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)n * sizeof(double), s));
-    RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)n * sizeof(double), s));
-    RT_TRY(rt::stream_sync(s));
-    return RY_OK;
+    return download_track(c, n, voiced, f0_64, t_64);
 }
 
 int ry_crepe_debug_layer(ry_crepe* c, int layer, int n_frames, float* out) {
@@ -1146,7 +1196,7 @@ void ry_crepe_stream_destroy(ry_crepe_stream* s) {
 
 int ry_crepe_stream_reset(ry_crepe_stream* s) {
     if (!s) return fail(RY_ESTATE, "null crepe stream handle");
-    s->k.valid = false;
+    s->rows.k.valid = false;
     return RY_OK;
 }
 
@@ -1160,20 +1210,18 @@ int ry_crepe_stream_track(ry_crepe_stream* st, const float* audio, int n_samples
     RY_TRY(voicing_args(threshold, step_ms));
     forget_track(c);
     const ry_stream_t s = c->ctx->stream;
-    const Resampler* r = nullptr;
-    int n16 = n_samples, nf = 0;
-    if (sr != 16000) RY_TRY(resample_plan(c, n_samples, sr, &r, &n16));
-    RY_TRY(frame_count(n16, hop, 1, &nf));
+    Slot& rows = st->rows;
+    TrackCall z;
+    RY_TRY(size_call(c, n_samples, sr, hop, &z));
+    const int nf = z.total_nf;
     std::vector<int>& tab = st->tab_host[st->tab_cur == 0 ? 1 : 0];
-    const int n_comp = plan_stream(c, &st->cache, &st->k, r, n_samples, sr, hop, nf, advance, overlap_ok, &tab);
+    const int n_comp = plan_stream(c, &st->cache, &rows.k, z.r, n_samples, sr, hop, nf, advance, overlap_ok, &tab);
     const bool all = n_comp == nf;                                    // nothing kept: the dense layer writes the window's block itself
-    const int w = st->k.valid ? 1 - st->k.kept : 0;
-    const float* keep = st->k.valid ? st->act(st->k.kept).ptr() : nullptr;
-    const int n_keep = st->k.valid ? st->k.nf : 0;
-    RY_TRY(ensure_chunk(c, std::min(n_comp, CHUNK)));
-    RY_TRY(ensure_call(c, nf, n16));
-    RY_TRY(ensure_track(c, nf));
-    RY_TRY(st->act(w).grow(c->ctx, (long long)nf * CREPE_BINS));      // the other block: the kept rows do not move
+    const int w = rows.next();
+    const float* keep = rows.keep();
+    const int n_keep = rows.n_keep();
+    RY_TRY(reserve_call(c, z, n_comp));
+    RY_TRY(rows.act(w).grow(c->ctx, (long long)nf * CREPE_BINS));
     if (!all) {
         RY_TRY(st->fresh.grow(c->ctx, (long long)n_comp * CREPE_BINS));
         RY_TRY(st->tab.grow(c->ctx, (long long)tab.size()));
@@ -1182,45 +1230,27 @@ int ry_crepe_stream_track(ry_crepe_stream* st, const float* audio, int n_samples
             st->tab_cur = st->tab_cur == 0 ? 1 : 0;
         }
     }
-    st->k.valid = false;                                              // from here on the block about to be written is in play
-    float* wave = c->audio.ptr();                                     // the one upload: the wave at the caller's rate
-    if (r) {
-        RY_TRY(c->audio_sr.reserve(c->ctx, n_samples));
-        wave = c->audio_sr.ptr();
-    }
-    RT_TRY(rt::h2d(wave, audio, (size_t)n_samples * sizeof(float), s));
-    if (r) RY_TRY(launch_resample(c, *r, wave, n_samples, sr, c->audio.ptr(), n16));
-    float* act = st->act(w).ptr();
+    rows.k.valid = false;                                             // from here on the block about to be written is in play
+    RY_TRY(bring_up(c, &z, audio));
+    float* act = rows.act(w).ptr();
     if (all) {
-        RY_TRY(run_passes(c, c->audio.ptr(), n16, hop, 1, nf, nullptr, act));
+        RY_TRY(run_passes(c, c->audio.ptr(), z.total16, hop, 1, nf, nullptr, act));
     } else {
-        RY_TRY(run_passes(c, c->audio.ptr(), n16, hop, 1, n_comp, st->tab.ptr() + nf, st->fresh.ptr()));
+        RY_TRY(run_passes(c, c->audio.ptr(), z.total16, hop, 1, n_comp, st->tab.ptr() + nf, st->fresh.ptr()));
         RY_TRY(launch_assemble(c->ctx, keep, n_keep, st->fresh.ptr(), n_comp, st->tab.ptr(), act, nf));
     }
     RY_TRY(launch_decode(c, act, nf, 1));
-    RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), nf, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr()));
-    c->trk_wave = wave; c->trk_samples = n_samples; c->trk_frames = nf;
-    keep_call(c, &st->cache, &st->k, w, r, n_samples, n16, sr, hop, nf);
-    *n_frames = nf;
+    RY_TRY(finish_track(c, z, threshold, step_ms, n_frames, voiced, f0_64, t_64, on_device_out));
+    keep_call(c, &st->cache, &rows.k, w, z.r, n_samples, z.total16, sr, hop, nf);
     *n_computed = n_comp;
-    if (on_device_out) return RY_OK;
-    RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)nf, s));
-    RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)nf * sizeof(double), s));
-    RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)nf * sizeof(double), s));
-    RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }
 
 int ry_crepe_stream_activation(ry_crepe_stream* st, float* out, int on_device) {
     RY_TRY(check_handle(st, "crepe stream"));
     if (!out) return fail(RY_EINVAL, "bad argument");
-    if (!st->k.valid) return fail(RY_ESTATE, "the stream holds no window: ry_crepe_stream_track has not run, or ry_crepe_stream_reset came after it");
-    const ry_stream_t s = st->ctx->stream;
-    const size_t bytes = (size_t)st->k.nf * CREPE_BINS * sizeof(float);
-    if (on_device) { RT_TRY(rt::d2d(out, st->act(st->k.kept).ptr(), bytes, s)); return RY_OK; }
-    RT_TRY(rt::d2h(out, st->act(st->k.kept).ptr(), bytes, s));
-    RT_TRY(rt::stream_sync(s));
-    return RY_OK;
+    if (!st->rows.k.valid) return fail(RY_ESTATE, "the stream holds no window: ry_crepe_stream_track has not run, or ry_crepe_stream_reset came after it");
+    return read_activation(st->ctx, st->rows, out, on_device);
 }
 
 int ry_crepe_stream_debug_poison(ry_crepe_stream* st, int* rows_left) {
@@ -1228,15 +1258,12 @@ int ry_crepe_stream_debug_poison(ry_crepe_stream* st, int* rows_left) {
     if (!rows_left) return fail(RY_EINVAL, "bad argument");
     const ry_stream_t s = st->ctx->stream;
     RT_TRY(rt::stream_sync(s));
-    // all bits set in the packed block, the tables on the card, the block about to be written and every kept row that is not portable: the rows
-    // the rule may hand to the next call are the only ones left alone
+    // all bits set in the packed block, the tables on the card and whatever of the slot the rule may not hand to the next call
     RY_TRY(st->fresh.poison(s));
     RY_TRY(st->tab.poison(s));
     st->tab_cur = -1;
-    const int w = st->k.valid ? 1 - st->k.kept : 0;
-    RY_TRY(st->act(w).poison(s));
     int left = 0;
-    RY_TRY(poison_kept(st->act(1 - w), st->k, s, &left));
+    RY_TRY(poison_slot(st->rows, s, &left));
     RT_TRY(rt::stream_sync(s));
     *rows_left = left;
     return RY_OK;
@@ -1264,7 +1291,7 @@ int ry_crepe_bank_create(ry_crepe* c, int n_streams, ry_crepe_bank** out) {
     std::unique_ptr<ry_crepe_bank> b(new ry_crepe_bank());
     b->ctx = c->ctx;
     b->model = c;
-    for (int i = 0; i < n_streams; ++i) b->slots.emplace_back(new ry_crepe_bank::Slot(b->bufs));
+    for (int i = 0; i < n_streams; ++i) b->slots.emplace_back(new Slot(b->bufs));
     *out = b.release();
     return RY_OK;
 }
@@ -1300,33 +1327,25 @@ static int bank_track_impl(ry_crepe_bank* b, const float* audio, const int* firs
     if (n_waves < 1) return fail(RY_EINVAL, "%d waves", n_waves);
     RY_TRY(voicing_args(threshold, step_ms));
     const int n_streams = (int)b->slots.size();
-    const Resampler* r = nullptr;
-    std::vector<int> n16((size_t)n_waves), nf((size_t)n_waves);
     std::vector<char> named((size_t)n_streams, 0);
-    for (int i = 0; i < n_waves; ++i) {
-        if (n_samples[i] < 1) return fail(RY_EINVAL, "wave %d has %d samples", i, n_samples[i]);
-        n16[(size_t)i] = n_samples[i];
-        if (sr != 16000) RY_TRY(resample_plan(c, n_samples[i], sr, &r, &n16[(size_t)i]));
-        RY_TRY(frame_count(n16[(size_t)i], hop, 1, &nf[(size_t)i]));
+    TrackCall z;
+    RY_TRY(size_call(c, uploaded ? first_sample : nullptr, n_samples, n_waves, sr, hop, &z, [&](int i) {
         const int st = stream_of[i];
         if (st < 0 || st >= n_streams) return fail(RY_EINVAL, "wave %d names stream %d of %d", i, st, n_streams);
         if (named[(size_t)st]) return fail(RY_EINVAL, "stream %d is named twice in one call", st);
         named[(size_t)st] = 1;
-    }
-    std::vector<CrepeSeg> plan;
-    RY_TRY(plan_segments(n_waves, n_samples, n16.data(), nf.data(), &plan));
-    if (uploaded) RY_TRY(place_uploaded(c, first_sample, n_samples, n_waves, sr, &plan));
-    const CrepeSeg& last = plan.back();
-    const int total_in = last.in_off + last.in_len, total16 = last.off16 + last.n16, total_nf = last.frame0 + last.n_frames;
+        return (int)RY_OK;
+    }));
+    const int total_nf = z.total_nf;
     // the tables, host work only: per wave the rule against that stream's kept call, the packed rows numbered through the call, the frames call-global
     static_assert(sizeof(CrepeBankWave) == 6 * sizeof(int), "the descriptors are copied as six ints each");
     const size_t desc_ints = 6 * (size_t)n_waves;
     std::vector<int> tab(desc_ints + (size_t)total_nf), idx, one;
     std::vector<int> comp((size_t)n_waves);
     for (int i = 0; i < n_waves; ++i) {
-        const CrepeSeg& g = plan[(size_t)i];
+        const CrepeSeg& g = z.plan[(size_t)i];
         const KeptCall& k = b->slots[(size_t)stream_of[i]]->k;
-        const int n_comp = plan_stream(c, &b->cache, &k, r, n_samples[i], sr, hop, g.n_frames, advance[i], overlap_ok[i], &one);
+        const int n_comp = plan_stream(c, &b->cache, &k, z.r, n_samples[i], sr, hop, g.n_frames, advance[i], overlap_ok[i], &one);
         const int base = (int)idx.size();
         for (int j = 0; j < g.n_frames; ++j) tab[desc_ints + (size_t)(g.frame0 + j)] = one[(size_t)j] >= 0 ? one[(size_t)j] : one[(size_t)j] - base;
         for (int q = 0; q < n_comp; ++q) idx.push_back(g.frame0 + one[(size_t)g.n_frames + (size_t)q]);
@@ -1335,16 +1354,14 @@ static int bank_track_impl(ry_crepe_bank* b, const float* audio, const int* firs
     const int total_comp = (int)idx.size();
     tab.insert(tab.end(), idx.begin(), idx.end());
     const ry_stream_t s = c->ctx->stream;
-    RY_TRY(ensure_chunk(c, std::min(total_comp, CHUNK)));
-    RY_TRY(ensure_call(c, total_nf, total16));
-    RY_TRY(ensure_track(c, total_nf));
+    RY_TRY(reserve_call(c, z, total_comp));
     RY_TRY(b->fresh.grow(c->ctx, (long long)total_comp * CREPE_BINS));
-    for (int i = 0; i < n_waves; ++i) {                                 // the slot each wave writes: the other one of its stream, whose kept rows do not move
-        ry_crepe_bank::Slot& sl = *b->slots[(size_t)stream_of[i]];
-        const int w = sl.k.valid ? 1 - sl.k.kept : 0;
-        RY_TRY(sl.act(w).grow(c->ctx, (long long)nf[(size_t)i] * CREPE_BINS));
+    for (int i = 0; i < n_waves; ++i) {                                 // the block each wave writes, and the descriptor that says so
+        Slot& sl = *b->slots[(size_t)stream_of[i]];
+        const int w = sl.next();
+        RY_TRY(sl.act(w).grow(c->ctx, (long long)z.nf[(size_t)i] * CREPE_BINS));
         CrepeBankWave d;
-        d.keep = sl.k.valid ? sl.act(sl.k.kept).ptr() : nullptr; d.n_keep = sl.k.valid ? sl.k.nf : 0; d.write = sl.act(w).ptr(); d.pad = 0;
+        d.keep = sl.keep(); d.n_keep = sl.n_keep(); d.write = sl.act(w).ptr(); d.pad = 0;
         memcpy(&tab[6 * (size_t)i], &d, sizeof d);
     }
     // one copy for the descriptors and both tables, and only when neither of the two sets the card holds is this one
@@ -1365,37 +1382,20 @@ static int bank_track_impl(ry_crepe_bank* b, const float* audio, const int* firs
     const int* d_src = b->tab(t).ptr() + desc_ints;
     const int* d_idx = d_src + total_nf;
     std::vector<int> wrote((size_t)n_waves);
-    for (int i = 0; i < n_waves; ++i) {                                 // from here on the slots about to be written are in play
-        KeptCall& k = b->slots[(size_t)stream_of[i]]->k;
-        wrote[(size_t)i] = k.valid ? 1 - k.kept : 0;
-        k.valid = false;
+    for (int i = 0; i < n_waves; ++i) {                                 // from here on the blocks about to be written are in play
+        Slot& sl = *b->slots[(size_t)stream_of[i]];
+        wrote[(size_t)i] = sl.next();
+        sl.k.valid = false;
     }
-    float* wave = const_cast<float*>(c->up_wave);
-    if (!uploaded) RY_TRY(upload_audio(c, r, audio, total_in, &wave));     // the one upload: the waves at the caller's rate, back to back
-    RY_TRY(upload_segments(c, plan));
-    const CrepeSeg* seg = c->segs.ptr();
-    if (r) RY_TRY(launch_resample(c, *r, wave, total_in, sr, c->audio.ptr(), total16, seg, n_waves));
-    RY_TRY(run_passes(c, c->audio.ptr(), total16, hop, 1, total_comp, d_idx, b->fresh.ptr(), seg, n_waves));
-    RY_TRY(launch_assemble_many(c->ctx, seg, n_waves, d_wave, d_src, b->fresh.ptr(), total_comp, c->act.ptr(), total_nf));
-    RY_TRY(launch_decode(c, c->act.ptr(), total_nf, 1, seg, n_waves));
-    RY_TRY(launch_voicing(c, c->conf.ptr(), c->f0.ptr(), total_nf, threshold, step_ms, c->voiced.ptr(), c->f0_64.ptr(), c->t_64.ptr(), seg, n_waves));
-    c->trk_wave = wave;
-    c->trk_sample_off.assign((size_t)n_waves + 1, 0);
-    c->trk_frame_off.assign((size_t)n_waves + 1, 0);
+    RY_TRY(bring_up(c, &z, audio));
+    RY_TRY(run_passes(c, c->audio.ptr(), z.total16, hop, 1, total_comp, d_idx, b->fresh.ptr(), z.seg, n_waves));
+    RY_TRY(launch_assemble_many(c->ctx, z.seg, n_waves, d_wave, d_src, b->fresh.ptr(), total_comp, c->act.ptr(), total_nf));
+    RY_TRY(launch_decode(c, c->act.ptr(), total_nf, 1, z.seg, n_waves));
+    RY_TRY(finish_track(c, z, threshold, step_ms, n_frames, voiced, f0_64, t_64, on_device_out));
     for (int i = 0; i < n_waves; ++i) {
-        c->trk_sample_off[(size_t)i + 1] = (long long)plan[(size_t)i].in_off + plan[(size_t)i].in_len;
-        c->trk_frame_off[(size_t)i + 1] = plan[(size_t)i].frame0 + plan[(size_t)i].n_frames;
-        keep_call(c, &b->cache, &b->slots[(size_t)stream_of[i]]->k, wrote[(size_t)i], r, n_samples[i], n16[(size_t)i], sr, hop, nf[(size_t)i]);
-        n_frames[i] = nf[(size_t)i];
+        keep_call(c, &b->cache, &b->slots[(size_t)stream_of[i]]->k, wrote[(size_t)i], z.r, n_samples[i], z.n16[(size_t)i], sr, hop, z.nf[(size_t)i]);
         n_computed[i] = comp[(size_t)i];
     }
-    if (uploaded) { c->sub_frame_off = c->trk_frame_off; c->sub_waves = n_waves; }
-    else c->trk_waves = n_waves;
-    if (on_device_out) return RY_OK;
-    RT_TRY(rt::d2h(voiced, c->voiced.ptr(), (size_t)total_nf, s));
-    RT_TRY(rt::d2h(f0_64, c->f0_64.ptr(), (size_t)total_nf * sizeof(double), s));
-    RT_TRY(rt::d2h(t_64, c->t_64.ptr(), (size_t)total_nf * sizeof(double), s));
-    RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }
 
@@ -1416,14 +1416,9 @@ int ry_crepe_bank_track_uploaded(ry_crepe_bank* b, const int* first_sample, cons
 int ry_crepe_bank_activation(ry_crepe_bank* b, int stream, float* out, int on_device) {
     RY_TRY(check_handle(b, "crepe bank"));
     if (!out || stream < 0 || stream >= (int)b->slots.size()) return fail(RY_EINVAL, "bad argument");
-    ry_crepe_bank::Slot& sl = *b->slots[(size_t)stream];
+    Slot& sl = *b->slots[(size_t)stream];
     if (!sl.k.valid) return fail(RY_ESTATE, "stream %d holds no window: no ry_crepe_bank_track has named it, or ry_crepe_bank_reset came after it", stream);
-    const ry_stream_t s = b->ctx->stream;
-    const size_t bytes = (size_t)sl.k.nf * CREPE_BINS * sizeof(float);
-    if (on_device) { RT_TRY(rt::d2d(out, sl.act(sl.k.kept).ptr(), bytes, s)); return RY_OK; }
-    RT_TRY(rt::d2h(out, sl.act(sl.k.kept).ptr(), bytes, s));
-    RT_TRY(rt::stream_sync(s));
-    return RY_OK;
+    return read_activation(b->ctx, sl, out, on_device);
 }
 
 int ry_crepe_bank_debug_poison(ry_crepe_bank* b, int* rows_left) {
@@ -1431,18 +1426,13 @@ int ry_crepe_bank_debug_poison(ry_crepe_bank* b, int* rows_left) {
     if (!rows_left) return fail(RY_EINVAL, "bad argument");
     const ry_stream_t s = b->ctx->stream;
     RT_TRY(rt::stream_sync(s));
-    // all bits set in the packed block, both sets of tables, every slot about to be written and every kept row that is not portable
+    // all bits set in the packed block, both sets of tables and whatever of every slot the rule may not hand to the next call
     RY_TRY(b->fresh.poison(s));
     for (int i = 0; i < 2; ++i) {
         RY_TRY(b->tab(i).poison(s));
         b->tab_on_card[i] = false;
     }
-    for (size_t i = 0; i < b->slots.size(); ++i) {
-        ry_crepe_bank::Slot& sl = *b->slots[i];
-        const int w = sl.k.valid ? 1 - sl.k.kept : 0;
-        RY_TRY(sl.act(w).poison(s));
-        RY_TRY(poison_kept(sl.act(1 - w), sl.k, s, &rows_left[i]));
-    }
+    for (size_t i = 0; i < b->slots.size(); ++i) RY_TRY(poison_slot(*b->slots[i], s, &rows_left[i]));
     RT_TRY(rt::stream_sync(s));
     return RY_OK;
 }
